@@ -11,8 +11,14 @@ N > 1 is weak scaling: the global text is N x 16 GiB, rank g scans shard g (plus
 context); the needles are planted anywhere in the global text.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload c3|c3r|c2|c4|c5|reads100] [--text-gib G] [--engine auto|brute|filter]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the result line; nothing else.  --full adds what the headline
+does not need: the brute-force engine on a slice, the 2-bit shadow, c3r's parity slice, the CPU baseline and, for the
+default C3 run, C2 / C4 / C5 / c3r / reads100 as `other_configs` and the live HBM streaming probe.
+--dump-outputs DIR writes the hit records of the last timed step as DIR/<field>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -51,6 +57,22 @@ WORKLOADS = {
                                           "64 haplotypes over a 2^27-base reference per GPU (2^30 on 8)"),
 }
 SEED_VAR = 0x5EED0003
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, rec, fields):
+    """--dump-outputs: the hit records the last timed step delivered, one float64 array per field (DIR/<field>.npy; exact,
+    every field is an integer below 2^53) plus DIR/hit_count.npy.  Records are put in one canonical order (sorted by
+    `fields`) so that two builds compare record for record; a set above DUMP_MAX_BYTES is cut to a fixed, seeded sample."""
+    os.makedirs(path, exist_ok=True)
+    rec = np.sort(rec, order=list(fields))
+    n = len(rec)
+    cap = (DUMP_MAX_BYTES - 4096) // (8 * len(fields))
+    if n > cap:
+        rec = rec[np.sort(np.random.default_rng(SEED_PAT).choice(n, cap, replace=False))]
+    for f in fields:
+        np.save(os.path.join(path, f"{f}.npy"), rec[f].astype(np.float64))
+    np.save(os.path.join(path, "hit_count.npy"), np.array([n], dtype=np.float64))
 
 
 VALU_PEAK_LANE_OPS = 6.5e13   # measured: v_add_u32 / v_bitop3_b32 chains, 8 waves per SIMD (tools/valu_probe.hip)
@@ -208,6 +230,9 @@ def run_c5(args, S, sdist, torch, dist, rank, world, dev, ctx):
     # every planted needle must be reported on its source haplotype where it was cut
     rec = h.view()
     h.close()
+    if rank == 0 and args.dump_outputs:   # what the step delivered to rank 0: every rank's records
+        out = np.frombuffer(gathered.cpu().numpy().tobytes(), dtype=S.JST_HIT_DTYPE)
+        dump_outputs(args.dump_outputs, out, ("haplotype", "pos", "pattern", "score"))
     found = 0
     by_needle = {}
     for q in np.nonzero(np.isin(rec["pattern"], list(planted)))[0] if planted else []:
@@ -422,16 +447,28 @@ def main():
     ap.add_argument("--text-gib", type=float, default=None, help="text per GPU in GiB (default: the workload's)")
     ap.add_argument("--needles", type=int, default=None)
     ap.add_argument("--engine", default="auto", choices=["auto", "brute", "filter"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--brute-sample-mib", type=int, default=256)
-    ap.add_argument("--packed-steps", type=int, default=10, help="steps of the packed-shadow variant (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (module docstring); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit records of the last timed step as DIR/<field>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--brute-sample-mib", type=int, default=None,
+                    help="brute-force engine on a slice of this size (default: 256 with --full, else 0 = skip)")
+    ap.add_argument("--packed-steps", type=int, default=None,
+                    help="steps of the packed-shadow variant (default: 10 with --full, else 0 = skip)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default single-GPU C3 run only: skip the C2 / C4 / C5 (/ c3r) lines attached as other_configs")
+                    help="--full, default single-GPU C3 run only: skip the C2 / C4 / C5 (/ c3r) lines attached as other_configs")
     ap.add_argument("--repeat-frac", type=float, default=0.01, help="c3r: fraction of the text inside repeat stretches")
     ap.add_argument("--repeat-needle-every", type=int, default=64,
                     help="c3r: besides the needles that cross a stretch by chance (uniform cut positions: ~1.7 %% of them at "
                          "1 %% repeats), every N-th needle is cut across a stretch on purpose (0: none)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_configs = True
+    if args.brute_sample_mib is None:
+        args.brute_sample_mib = 256 if args.full else 0
+    if args.packed_steps is None:
+        args.packed_steps = 10 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -512,7 +549,7 @@ def other_configs(args, env):
     for name, steps, warmup in (("c2", 20, 3), ("c4", 5, 3), ("c5", 10, 2), ("c3r", 5, 2), ("reads100", 5, 3)):
         a = copy.copy(args)
         a.workload, a.steps, a.warmup = name, steps, warmup
-        a.no_cpu_baseline, a.brute_sample_mib, a.packed_steps = True, 0, 0
+        a.no_cpu_baseline, a.brute_sample_mib, a.packed_steps, a.dump_outputs = True, 0, 0, None
         t0 = time.perf_counter()
         try:
             r = run_c5(a, *env) if name == "c5" else run_scan(a, *env, workload=name)
@@ -640,6 +677,8 @@ def run_scan(args, S, sdist, torch, dist, rank, world, dev, ctx, workload):
         return None
     recs = xp.records(gathered).cpu().numpy().view(np.uint8).reshape(-1, 16)
     hits = np.frombuffer(recs.tobytes(), dtype=S.HIT_DTYPE)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hits, ("pattern", "pos", "score"))
     found = np.unique(hits["pattern"])
     ms_per_step = dt / args.steps * 1e3
     value = n_total / (dt / args.steps) / 1e9
@@ -726,6 +765,7 @@ def run_scan(args, S, sdist, torch, dist, rank, world, dev, ctx, workload):
                          "every --repeat-needle-every-th one across a stretch on purpose (random overlap)",
             "fallback_symbols": int(st.fallback_symbols),
         }
+    if repeats and args.full:
         # parity on a slice: the filter's hits == the brute-force engine's, on 64 MiB of this text
         nb = min(hi - lo, 64 << 20)
         hb = S.scan(ctx, text, ps, 0, nb, engine=S.ENGINE_BRUTE, max_hits=max_hits)

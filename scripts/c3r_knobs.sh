@@ -1,7 +1,7 @@
 #!/bin/bash
 # c3r at 1 % and 5 %: step time under a few scan-time knobs (resolve residency, band width, run length threshold)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-B="python3 bench.py --no-cpu-baseline --brute-sample-mib 0 --packed-steps 0 --no-other-configs --workload c3r --steps 4 --warmup 3"
+B="python3 bench.py --full --no-cpu-baseline --brute-sample-mib 0 --packed-steps 0 --no-other-configs --workload c3r --steps 4 --warmup 3"
 run() { # label, env...
   local label=$1; shift
   for f in 0.01 0.05; do

@@ -11,7 +11,7 @@ B="python3 $R/bench.py --no-cpu-baseline --brute-sample-mib 0 --packed-steps 0 -
 steps_of() { case $1 in c4|reads100) echo "--steps 5 --warmup 3";; c3r) echo "--steps 5 --warmup 3";; *) echo "--steps 10 --warmup 3";; esac; }
 if [ $PART = 1 ]; then
   say "default bench line (all configs)"
-  timeout -k 10 600 python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+  timeout -k 10 600 python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
   for W in c3 c2 c4 c5 c3r reads100; do
     say "kernel trace $W"
     rm -rf $OUT/trace_$W
@@ -37,7 +37,7 @@ else
   say "repeat sweep (c3r at 0 / 0.1 / 1 / 5 %, needles across a stretch every 128th / 64th / 16th / 8th)"
   cd $R
   for f in 0 0.001 0.01 0.05; do for e in 128 64 16 8; do
-    timeout -k 10 400 python3 bench.py --workload c3r --repeat-frac $f --repeat-needle-every $e --steps 5 --warmup 3 --no-cpu-baseline --brute-sample-mib 0 --packed-steps 0 2>/dev/null | tail -1 > $OUT/c3r_f${f}_e${e}.json
+    timeout -k 10 400 python3 bench.py --full --workload c3r --repeat-frac $f --repeat-needle-every $e --steps 5 --warmup 3 --no-cpu-baseline --brute-sample-mib 0 --packed-steps 0 2>/dev/null | tail -1 > $OUT/c3r_f${f}_e${e}.json
     python3 -c "
 import json; r=json.load(open('$OUT/c3r_f${f}_e${e}.json'))
 print('c3r frac $f every $e:', round(r['value'],1), 'Gbases/s', round(r['ms_per_step'],3), 'ms  kernel', round(r['roofline']['kernel_ms'],3), 'cand', r['candidates'], 'bands', r['bands_verified'], 'hits', r['hits'], 'fallback_spans', r['fallback_spans'], 'parity', r['parity_slice']['equal_to_brute_force_engine'])" | tee -a $OUT/progress.log

@@ -9,7 +9,7 @@ if [ "${TESTS:-all}" != none ]; then
   tail -3 gpurun_out/pytest_gpu.log
 fi
 for w in ${BENCH:-}; do
-  extra="--no-other-configs"
+  extra="--full --no-other-configs"
   [ $w = c4 ] && extra="$extra --steps 3 --warmup 1 --packed-steps 0"
   [ $w = reads100 ] && extra="$extra --steps 3 --warmup 1 --packed-steps 0"
   [ $w = c5 ] && extra="--steps 10 --warmup 2"
