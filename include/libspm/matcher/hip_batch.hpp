@@ -82,7 +82,58 @@ public:
         run_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
     }
 
+    // Scan + align: callback(needle_index, finder, alignment) in the order of operator(), the finder carrying the TRUE
+    // begin of every hit (hip_pattern_base::locate).
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void locate(haystack_t && haystack, callback_t && callback) noexcept
+    {
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (_lengths.empty() || ranks.empty())
+            return;
+        spm_ctx * ctx = hip::default_context();
+        spm_text * t = nullptr;
+        if (spm_hip_text_upload(ctx, ranks.data(), ranks.size(), _sigma, &t) != SPM_OK)
+            hip::fatal("spm_hip_text_upload", ctx);
+        hip::text_ptr text{t};
+        locate_on(text.get(), 0, ranks.size(), callback);
+    }
+
+    template <typename callback_t>
+    void locate(hip::resident_haystack const & haystack, callback_t && callback) noexcept
+    {
+        if (_lengths.empty() || haystack.empty())
+            return;
+        if (haystack.sigma() != _sigma) {
+            std::fprintf(stderr, "libspm (MI355X back-end): the resident haystack's alphabet (%u symbols) is not the needles' (%u)\n",
+                         haystack.sigma(), _sigma);
+            std::abort();
+        }
+        locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
+    }
+
 private:
+    template <typename callback_t>
+    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_hit const * rec = nullptr;
+        std::uint64_t cnt = 0;
+        hip::hits_ptr hits = hip::scan_all_hits(
+            ctx, spm_scan_opts{},
+            [&](spm_scan_opts const & o, spm_hits ** h) {
+                return spm_hip_scan(ctx, text, base, base + n, _patterns.get(), &o, nullptr, nullptr, h);
+            },
+            rec, cnt, "spm_hip_scan");
+        spm_aln const * al = nullptr;
+        std::uint32_t const * ops = nullptr;
+        hip::alns_ptr alns = hip::align_hits(ctx, hits.get(), al, cnt, ops);
+        for (std::uint64_t i = 0; i < cnt; ++i) {
+            std::size_t const b = static_cast<std::size_t>(al[i].begin) - base, e = static_cast<std::size_t>(al[i].end) - base;
+            callback(static_cast<std::size_t>(al[i].pattern), finder{b, e, n, al[i].score},
+                     alignment{b, e, al[i].score, ops + al[i].cigar_off, al[i].cigar_len});
+        }
+    }
+
     template <typename callback_t>
     void run_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
     {
@@ -98,6 +149,7 @@ private:
         for (std::uint64_t i = 0; i < cnt; ++i) {
             std::size_t const m = _lengths[rec[i].pattern];
             std::size_t const pos = static_cast<std::size_t>(rec[i].pos) - base;
+            // (Myers: the begin is end - |P|, right only for a hit without indels; locate() gives the true one)
             finder f = reports_begin_v ? finder{pos, pos + m, n, 0} : finder{pos >= m ? pos - m : 0, pos, n, rec[i].score};
             callback(static_cast<std::size_t>(rec[i].pattern), f);
         }

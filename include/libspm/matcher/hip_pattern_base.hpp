@@ -20,6 +20,7 @@
 
 #include <libspm/hip/context.hpp>
 #include <libspm/seqan/container_adapter.hpp>
+#include <libspm/matcher/alignment.hpp>
 #include <libspm/matcher/concept.hpp>
 #include <libspm/seqan/alphabet.hpp>
 
@@ -207,6 +208,34 @@ public:
         static_cast<derived_t *>(this)->run_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
     }
 
+    // Scan + align: callback(finder, alignment) once per hit, in the order of operator(), with the TRUE begin of every hit
+    // (the largest begin at the hit's distance) -- what seqan2's findBegin gives a reference call site.  Always a fresh
+    // matcher (a restorable matcher's saved state is neither used nor changed).
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void locate(haystack_t && haystack, callback_t && callback) noexcept
+    {
+        static_assert(locatable(), "locate() is not available for this matcher (prefix hits are not aligned)");
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (ranks.empty() || _needle.empty())
+            return;
+        hip::text_ptr text = upload(ranks.data(), ranks.size());
+        locate_on(text.get(), 0, ranks.size(), callback);
+    }
+
+    template <typename callback_t>
+    void locate(hip::resident_haystack const & haystack, callback_t && callback) noexcept
+    {
+        static_assert(locatable(), "locate() is not available for this matcher (prefix hits are not aligned)");
+        if (haystack.empty() || _needle.empty())
+            return;
+        if (haystack.sigma() != _sigma) {
+            std::fprintf(stderr, "libspm (MI355X back-end): the resident haystack's alphabet (%u symbols) is not the needle's (%u)\n",
+                         haystack.sigma(), _sigma);
+            std::abort();
+        }
+        locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
+    }
+
     bool empty() const noexcept { return _needle.empty(); }
 
 protected:
@@ -231,7 +260,32 @@ protected:
             callback(make_finder(rec[i], n, base));
     }
 
-    // (hit positions arrive relative to text[0]; the finder speaks in haystack coordinates)
+    // every matcher can locate its hits except those that say otherwise (restorable_myers_prefix_matcher)
+    static constexpr bool locatable() noexcept
+    {
+        if constexpr (requires { derived_t::has_alignments; })
+            return derived_t::has_alignments;
+        else
+            return true;
+    }
+
+    template <typename callback_t>
+    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
+    {
+        spm_hit const * rec = nullptr;
+        std::uint64_t cnt = 0;
+        hip::hits_ptr hits = scan_text(text, base, base + n, nullptr, nullptr, rec, cnt);
+        spm_aln const * al = nullptr;
+        std::uint32_t const * ops = nullptr;
+        hip::alns_ptr alns = hip::align_hits(hip::default_context(), hits.get(), al, cnt, ops);
+        for (std::uint64_t i = 0; i < cnt; ++i) {
+            std::size_t const b = static_cast<std::size_t>(al[i].begin) - base, e = static_cast<std::size_t>(al[i].end) - base;
+            callback(finder{b, e, n, al[i].score}, alignment{b, e, al[i].score, ops + al[i].cigar_off, al[i].cigar_len});
+        }
+    }
+
+    // (hit positions arrive relative to text[0]; the finder speaks in haystack coordinates).  The begin of a Myers hit
+    // reported here is end - |P|: right only for a hit without insertions or deletions; locate() gives the true one.
     finder make_finder(spm_hit const & h, std::size_t n, std::size_t base = 0) const noexcept
     {
         std::size_t const m = _needle.size();

@@ -16,6 +16,7 @@ class restorable_myers_prefix_matcher : public restorable_base<restorable_myers_
     friend base_t;
     friend hip_pattern_base<restorable_myers_prefix_matcher<needle_t>>;
     static constexpr bool reports_begin = false;
+    static constexpr bool has_alignments = false; // spm_hip_hits_align does not align prefix hits: no locate()
 
     std::size_t bound(std::size_t n) const noexcept
     {

@@ -225,6 +225,58 @@ int spm_hip_hits_stats(const spm_hits *hits, spm_scan_stats *out);
 uint64_t spm_hip_hits_checksum(spm_hits *hits);
 void spm_hip_hits_destroy(spm_hits *hits);
 
+/* ---- begins and alignments of hits: what seqan2's findBegin adds to a Myers finder ----------------------------------
+ * A Myers hit is (end e, distance d).  Its begin is the LARGEST b in [lo, e] with ED(P, text[b, e)) = d -- the shortest
+ * text span, the begin a backward scan from e reaches first.  lo is the first symbol the scan let an alignment use:
+ * spm_hip_scan's `begin` (left_context = 0), 0 (left_context = 1), or the start of the hit's segment
+ * (spm_hip_scan_segments).  ED is unit-cost edit distance over ranks; a needle rank >= sigma matches nothing.
+ * The transcript is one optimal global alignment of P against text[b, e) with exactly d edits, as BAM-style CIGAR words
+ * len << 4 | op, the needle being the query and the text the reference: SPM_CIGAR_EQ (match), SPM_CIGAR_X (mismatch),
+ * SPM_CIGAR_INS (a needle symbol only), SPM_CIGAR_DEL (a text symbol only); adjacent equal ops are merged.
+ * Tie order: walking back from (|P|, e - b), a diagonal step (= or X) is taken whenever it is optimal, else an
+ * insertion, else a deletion.  The result depends only on (P, text, e, d): bit-identical across runs and engines.
+ * Exact sets (Shift-Or, Horspool): begin = pos, end = pos + |P|, CIGAR |P|=.
+ * Not supported (SPM_E_UNSUPPORTED): MYERS_PREFIX sets, stateful scans (state_in != NULL), hits of journaled sequences.
+ * The scan's text and needle set must still be alive. */
+typedef struct spm_aln {
+    uint64_t begin;       /* b + pos_offset (exact sets: pos) */
+    uint64_t end;         /* the hit's pos (Myers) / pos + |P| (exact) */
+    uint32_t pattern;
+    int32_t score;        /* the hit's distance */
+    uint32_t cigar_off;   /* first word of this record's transcript in the ops pool */
+    uint32_t cigar_len;   /* words; 0 with SPM_ALIGN_BEGIN_ONLY */
+} spm_aln;
+typedef struct spm_alns spm_alns;
+
+enum spm_cigar_op { SPM_CIGAR_INS = 1, SPM_CIGAR_DEL = 2, SPM_CIGAR_EQ = 7, SPM_CIGAR_X = 8 };
+#define SPM_ALIGN_BEGIN_ONLY 1u /* begins only: skip the transcript stage (cigar_len = 0, empty ops pool) */
+
+/* Device timings (ms, HIP events) and how the hits were split over the kernel classes. */
+typedef struct spm_align_stats {
+    float ms_total;        /* both stages */
+    float ms_begin;        /* stage A: backward bit-vector scan to the begin */
+    float ms_cigar;        /* stage B: banded DP + traceback */
+    float ms_host;         /* wall clock of the whole call, host side included */
+    uint64_t n_alns;
+    uint64_t n_ops;        /* CIGAR words in the pool (sum of 2 score + 1 over the hits) */
+    uint32_t begin_lane;        /* stage A, one lane per hit (|P| <= 256) */
+    uint32_t begin_wave;        /* stage A, one wave per hit, a 64-bit word per lane */
+    uint32_t cigar_lane;        /* stage B, one lane per hit, traceback in LDS (slots <= 1 KiB) */
+    uint32_t cigar_wave;        /* stage B, one wave per hit, traceback in LDS (slots <= 64 KiB) */
+    uint32_t cigar_wave_global; /* stage B, one wave per hit, traceback in a global scratch slice */
+    uint32_t reserved[3];
+} spm_align_stats;
+
+/* Align every hit.  Records follow the hits: host view record i belongs to spm_hip_hits_view record i (order
+ * (pattern, pos)), device record i to device hit i.  cigar_off is the exclusive prefix sum of 2 score + 1 in host order.
+ * A deferred scan is completed first; an overflowed scan returns its SPM_E_OVERFLOW. */
+int spm_hip_hits_align(spm_hits *hits, uint32_t flags, spm_alns **out);
+int spm_hip_alns_view(spm_alns *a, const spm_aln **records, uint64_t *n, const uint32_t **ops, uint64_t *n_ops);
+/* Device view: records in device hit order and the ops pool, in HBM, owned by the handle. */
+int spm_hip_alns_device(spm_alns *a, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops);
+int spm_hip_alns_stats(const spm_alns *a, spm_align_stats *out);
+void spm_hip_alns_destroy(spm_alns *a);
+
 /* ---- journaled-sequence (pan-genome) search, config C5 ----------------------------------------------------
  * The reference only designs the journaled sequence (specs/journaled_sequence_class_diagram.drawio:7-298) and gives the
  * matcher-side hooks a traverser needs (spm::window_size / capture / restore, matcher/concept.hpp:26-161).  The

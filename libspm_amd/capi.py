@@ -104,6 +104,32 @@ class JstStats(C.Structure):
     ]
 
 
+class Aln(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64), ("pattern", C.c_uint32), ("score", C.c_int32),
+                ("cigar_off", C.c_uint32), ("cigar_len", C.c_uint32)]
+
+
+class AlignStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_begin", C.c_float),
+        ("ms_cigar", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_alns", C.c_uint64),
+        ("n_ops", C.c_uint64),
+        ("begin_lane", C.c_uint32),
+        ("begin_wave", C.c_uint32),
+        ("cigar_lane", C.c_uint32),
+        ("cigar_wave", C.c_uint32),
+        ("cigar_wave_global", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+ALIGN_BEGIN_ONLY = 1
+CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
+
+
 def build(force: bool = False) -> str:
     """Compile libspm_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".cpp"))]
@@ -160,6 +186,12 @@ def lib():
         "spm_hip_hits_stats": (C.c_int, [vp, C.POINTER(ScanStats)]),
         "spm_hip_hits_checksum": (C.c_uint64, [vp]),
         "spm_hip_hits_destroy": (None, [vp]),
+        "spm_hip_hits_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(Aln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
+                                        C.POINTER(C.c_uint64)]),
+        "spm_hip_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_alns_stats": (C.c_int, [vp, C.POINTER(AlignStats)]),
+        "spm_hip_alns_destroy": (None, [vp]),
         "spm_hip_synth_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                                C.c_uint32, u8p]),
         "spm_hip_synth_repeat_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -207,7 +239,9 @@ EXPORTS = [
     "spm_hip_text_device_ptr", "spm_hip_text_destroy", "spm_hip_patterns_create", "spm_hip_patterns_destroy",
     "spm_hip_patterns_window_size", "spm_hip_patterns_filterable", "spm_hip_patterns_build_stats", "spm_hip_patterns_state_stride",
     "spm_hip_patterns_state_init", "spm_hip_scan", "spm_hip_scan_segments", "spm_hip_hits_view", "spm_hip_hits_device",
-    "spm_hip_hits_copy_device", "spm_hip_hits_copy_fused", "spm_hip_hits_copy_fused_device", "spm_hip_hits_stats", "spm_hip_hits_checksum", "spm_hip_hits_destroy", "spm_hip_synth_pattern",
+    "spm_hip_hits_copy_device", "spm_hip_hits_copy_fused", "spm_hip_hits_copy_fused_device", "spm_hip_hits_stats", "spm_hip_hits_checksum", "spm_hip_hits_destroy",
+    "spm_hip_hits_align", "spm_hip_alns_view", "spm_hip_alns_device", "spm_hip_alns_stats", "spm_hip_alns_destroy",
+    "spm_hip_synth_pattern",
     "spm_hip_synth_repeat_pattern", "spm_hip_synth_repeat_text", "spm_hip_mix64", "spm_hip_host_selftest", "spm_hip_version",
     "spm_hip_jst_create", "spm_hip_jst_destroy", "spm_hip_jst_haplotype_length", "spm_hip_jst_extract",
     "spm_hip_jst_index", "spm_hip_jst_search", "spm_hip_jst_stats", "spm_hip_jst_hits_view", "spm_hip_jst_hits_device",

@@ -104,6 +104,14 @@ struct spm_hits
     const struct spm_patterns *d_patterns = nullptr;
     uint64_t d_begin = 0, d_end = 0;
     spm_scan_opts d_opts{};
+    // what spm_hip_hits_align needs to know about the scan that made these hits (align.hip)
+    const spm_text *al_text = nullptr;
+    const struct spm_patterns *al_patterns = nullptr;
+    uint64_t al_lo = 0;             // first symbol an alignment may use (whole scans; segmented: the hit's segment start)
+    uint64_t al_pos_offset = 0;
+    bool al_stateful = false;       // state_in != NULL
+    bool al_device_segs = false;    // segment table only on the device (journaled-sequence search)
+    std::vector<uint64_t> al_segs;  // segmented scans: the segment table (n_segments + 1 offsets)
 };
 
 struct pass_entry // key directory of one pass of the seed filter, in L2 (filter.hpp: resolve_kernel)

@@ -57,6 +57,13 @@ struct spm_patterns : spm_hip::seed_index // (the seed index: passes, entries, s
     mutable int exact_whole = -1;     // 1: k = 0 and every needle is its own single seed (decided at the first scan)
     mutable uint64_t band_hint = 0;   // ... and band-list slots it drew (sizes the verification grid)
     spm_build_stats build{};          // what spm_hip_patterns_create spent where
+    // alignment tables, built at the first spm_hip_hits_align of the set (align.hip): one allocation holding the reversed
+    // needles' 64-bit match masks [sigma][words] per needle, their word offsets, the needle ranks and their offsets
+    mutable void *d_align = nullptr;
+    mutable const uint64_t *d_al_rpeq = nullptr;
+    mutable const uint32_t *d_al_rpeq_off = nullptr;
+    mutable const uint8_t *d_al_ranks = nullptr;
+    mutable const uint32_t *d_al_offsets = nullptr;
 };
 
 using clk = std::chrono::steady_clock;
@@ -197,6 +204,7 @@ void spm_warm_brute_kernels();
 void spm_warm_filter_kernels();
 void spm_warm_hits_kernels();
 void spm_warm_jst_kernels();
+void spm_warm_align_kernels();
 
 // deferred scans (SPM_SCAN_DEFER): read the counters back, and repeat the scan if it needs attention   (scan.hip)
 int spm_complete_deferred(spm_hits *h);

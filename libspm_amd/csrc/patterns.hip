@@ -247,6 +247,7 @@ extern "C" void spm_hip_patterns_destroy(spm_patterns *p)
     if (!p)
         return;
     hipFree(p->d_arena); // (every d_* table of the set points into it)
+    hipFree(p->d_align);
     delete p;
 }
 

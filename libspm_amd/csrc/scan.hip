@@ -109,6 +109,14 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
                 SPM_HIP_CHECK(ctx, hipEventCreate(&H->ev[i]));
         }
     }
+    H->al_text = text;
+    H->al_patterns = patterns;
+    H->al_lo = opts.left_context ? 0 : begin;
+    H->al_pos_offset = opts.pos_offset;
+    H->al_stateful = state_in != nullptr;
+    H->al_device_segs = d_seg_offsets != nullptr && seg_offsets == nullptr;
+    if (seg_offsets)
+        H->al_segs.assign(seg_offsets, seg_offsets + n_segments + 1);
     if (!counters_clear) // (a recycled block was cleared when it went back to the pool, off this scan's critical path)
         SPM_HIP_CHECK(ctx, hipMemsetAsync(H->d_count, 0, 16 * sizeof(unsigned long long), ctx->stream));
 

@@ -13,6 +13,9 @@ import numpy as np
 from . import capi
 
 HIT_DTYPE = np.dtype([("pos", "<u8"), ("pattern", "<u4"), ("score", "<i4")])
+ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("pattern", "<u4"), ("score", "<i4"), ("cigar_off", "<u4"),
+                      ("cigar_len", "<u4")])
+_CIGAR_CHAR = {capi.CIGAR_INS: "I", capi.CIGAR_DEL: "D", capi.CIGAR_EQ: "=", capi.CIGAR_X: "X"}
 
 
 def _check(rc, ctx_handle):
@@ -178,8 +181,9 @@ class PatternSet:
 
 
 class Hits:
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    def __init__(self, ctx, h, text=None, pats=None):
+        # the scan's haystack and needle set: align() reads both, so they live at least as long as the hits
+        self.ctx, self._h, self._text, self._pats = ctx, h, text, pats
 
     def view(self) -> np.ndarray:
         """Hits sorted by (pattern, pos): per pattern, the order the reference's callback fires in."""
@@ -214,6 +218,13 @@ class Hits:
         counters (status != 0: the scan needs the host -- call view() / stats() and copy again).  No synchronisation."""
         _check(capi.lib().spm_hip_hits_copy_fused_device(self._h, C.c_void_p(device_ptr), cap), self.ctx._h)
 
+    def align(self, begin_only: bool = False) -> "Alignments":
+        """Begin + CIGAR transcript of every hit (spm_hip_hits_align); record i belongs to view() record i."""
+        a = C.c_void_p()
+        _check(capi.lib().spm_hip_hits_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
+               self.ctx._h)
+        return Alignments(self.ctx, a)
+
     def stats(self) -> capi.ScanStats:
         s = capi.ScanStats()
         _check(capi.lib().spm_hip_hits_stats(self._h, C.byref(s)), self.ctx._h)
@@ -226,6 +237,71 @@ class Hits:
         if self._h:
             if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
                 capi.lib().spm_hip_hits_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Alignments:
+    """Result of Hits.align(): ALN_DTYPE records in the order of Hits.view(), and the pool of CIGAR words
+    (len << 4 | op) they point into."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def _raw(self):
+        rec = C.POINTER(capi.Aln)()
+        ops = C.POINTER(C.c_uint32)()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
+               self.ctx._h)
+        return rec, n.value, ops, n_ops.value
+
+    def __len__(self):
+        return self._raw()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n, _, _ = self._raw()
+        if n == 0:
+            return np.zeros(0, dtype=ALN_DTYPE)
+        buf = (capi.Aln * n).from_address(C.addressof(rec.contents))
+        return np.frombuffer(buf, dtype=ALN_DTYPE).copy()
+
+    @property
+    def ops(self) -> np.ndarray:
+        _, _, ops, n_ops = self._raw()
+        if n_ops == 0:
+            return np.zeros(0, dtype=np.uint32)
+        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
+        return np.frombuffer(buf, dtype=np.uint32).copy()
+
+    def device(self):
+        """(records, n, ops, n_ops): device pointers, records in device hit order."""
+        r, o = C.c_void_p(), C.c_void_p()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)), self.ctx._h)
+        return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
+
+    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
+        """SAM string of record i, e.g. "41=1X12=1I45=" (records / ops: views already fetched, to save the copies)."""
+        r = (self.view() if records is None else records)[i]
+        o = self.ops if ops is None else ops
+        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
+        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+
+    def stats(self) -> capi.AlignStats:
+        s = capi.AlignStats()
+        _check(capi.lib().spm_hip_alns_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_alns_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -251,7 +327,7 @@ def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | 
         st_out = np.zeros(pats.state_stride() * max(1, pats.n), dtype=np.uint8)
     _check(capi.lib().spm_hip_scan(ctx._h, text._h, begin, end, pats._h, C.byref(opts), st_in,
                                    st_out.ctypes.data if st_out is not None else None, C.byref(h)), ctx._h)
-    hits = Hits(ctx, h)
+    hits = Hits(ctx, h, text, pats)
     return (hits, st_out) if want_state else hits
 
 
@@ -263,7 +339,7 @@ def scan_segments(ctx: Context, text: Text, pats: PatternSet, seg_offsets, *, en
     h = C.c_void_p()
     _check(capi.lib().spm_hip_scan_segments(ctx._h, text._h, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
                                             len(offs) - 1, pats._h, C.byref(opts), C.byref(h)), ctx._h)
-    return Hits(ctx, h)
+    return Hits(ctx, h, text, pats)
 
 
 def synth_pattern(seed_text: int, seed_pat: int, n_total: int, p: int, L: int, kmax: int):
