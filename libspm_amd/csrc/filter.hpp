@@ -98,7 +98,7 @@ struct filter_params
     uint32_t dynamic;         // 1: waves draw spans from counters[4] instead of a static round-robin
     uint32_t key_len;         // H: symbols per key (12..16); windows are H symbols, keys 2H bits
     uint32_t key_mask;        // (1 << 2H) - 1
-    uint32_t hash_variant;    // 0/1: Bloom cascade with mul / xor-shift hashes, 2: perfect-hash fingerprints
+    uint32_t hash_variant;    // 1: Bloom cascade, 2: perfect-hash fingerprints, 3: dense pass, 4: presence bits
     uint32_t lds_words;       // size of the LDS image (bitmap, or fingerprint table + displacement table)
     uint32_t chd_slot_mask;   // fingerprint slots - 1
     uint32_t chd_bucket_shift; // bucket = x >> shift
@@ -111,7 +111,6 @@ struct filter_params
     // dense passes (filter_shared.hpp): lds = presence bits; a window is looked up iff its dimer matches one of the n_pat patterns
     uint32_t n_pat, pat_c[kDensePatterns], pat_cm[kDensePatterns];
     uint32_t bucket_shift;
-    uint32_t dense_debug;     // diagnostics (SPM_HIP_DENSE_DEBUG): 1 drop the windows that pass level 1, 2 skip level 1 too, 4 gather from 256 buckets only (L1 hits; wrong hits)
     const uint4 *buckets;     // fingerprint buckets, L2-resident
     survivor *surv;
     unsigned long long *counters; // [1] = survivor slots drawn, [6] = spans that gave up, [2] = hard overflow
@@ -292,7 +291,7 @@ __device__ __forceinline__ void filter_words(const filter_params &P, const uint3
             for (int i = 0; i < NWIN; ++i) {
                 const int d = S * (i + 1);
                 const uint32_t key = (d == 16 ? w[u] : alignbit(w[u], prev[u], (2 * d) & 31)) & kmask;
-                const uint32_t h = bloom_hash<HV>(key, 0) & idx_mask;
+                const uint32_t h = bloom_hash(key, 0) & idx_mask;
                 const uint32_t word = lds[h >> 5];
                 pos_mask |= __builtin_amdgcn_ubfe(word, h, 1) << (u * NWIN + i);
             }
@@ -309,7 +308,7 @@ __device__ __forceinline__ void filter_words(const filter_params &P, const uint3
                     if (pos_mask & (1u << (u * NWIN + i))) {
                         const int d = S * (i + 1);
                         const uint32_t key = (d == 16 ? w[u] : alignbit(w[u], prev[u], (2 * d) & 31)) & kmask;
-                        const uint32_t h = bloom_hash<HV>(key, pr) & idx_mask;
+                        const uint32_t h = bloom_hash(key, pr) & idx_mask;
                         const uint32_t word = lds[h >> 5];
                         keep |= __builtin_amdgcn_ubfe(word, h, 1) << (u * NWIN + i);
                     }
@@ -464,7 +463,7 @@ __device__ __forceinline__ void filter_group(const filter_params &P, const uint4
 // which made the masked-key stride-2 variant spill to scratch inside the streaming loop (+31 % kernel time).
 // Stride 1 without key masks (C4-sized needle sets: LDS-bound at 16 windows per lane, see DESIGN) fits 128 VGPRs and may run
 // 16 waves per CU.
-template <int S, int U, bool NT, int HV, int SIG, bool KM, bool AN = false>
+template <int S, int U, int HV, int SIG, bool KM, bool AN = false>
 __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2)) ? 1024 : 512) void seed_filter_kernel(const filter_params P)
 {
     extern __shared__ uint32_t lds[];
@@ -547,7 +546,7 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
             uint4 nxt[U];
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                nxt[u] = load16_stream<NT>(lane_text + (ch + u) * 1024);
+                nxt[u] = load16_stream(lane_text + (ch + u) * 1024);
             for (; ch < fast_end; ch += U) {
                 uint4 cur[U];
 #pragma unroll
@@ -560,7 +559,7 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
                 const uint64_t ustride = more ? 1024 : 0;
 #pragma unroll
                 for (int u = 0; u < U; ++u)
-                    nxt[u] = load16_stream<NT>(lane_text + pf * 1024 + (uint64_t)u * ustride);
+                    nxt[u] = load16_stream(lane_text + pf * 1024 + (uint64_t)u * ustride);
                 // strides 1 and 2: keep the loads here -- left alone, the scheduler sinks them to the very end of the
                 // group's work and the next iteration waits out the whole HBM latency.  (The larger strides are
                 // scheduled well as they are; a barrier there only forces the packing to wait for all eight loads.)
@@ -641,7 +640,7 @@ __device__ __forceinline__ void dense_drain(const filter_params &P, dense_queue 
             if (v[b]) {
                 key[b] = Q.key[e];
                 off[b] = Q.off[e];
-                bk[b] = P.buckets[dense_bucket(key[b], P.bucket_shift) & ((P.dense_debug & 4u) ? 255u : 0xFFFFFFFFu)];
+                bk[b] = P.buckets[dense_bucket(key[b], P.bucket_shift)];
             }
         }
         qn = qn > 64 * nb ? qn - 64 * nb : 0;
@@ -698,8 +697,6 @@ __device__ __forceinline__ void dense_group(const filter_params &P, const uint4 
                 todo |= dense_select<NP>(P, w1, p1) << 1;
             // level 1, every lane for itself (a lane runs as long as it has anchored windows -- no wave-wide steps in
             // here, the loop is what this kernel spends its time in): which of them have their presence bit set
-            if (P.dense_debug & 2u)
-                todo = 0;
             while (todo != 0) {
                 const uint32_t b = (uint32_t)__ffs(todo) - 1u;
                 todo &= todo - 1;
@@ -724,8 +721,6 @@ __device__ __forceinline__ void dense_group(const filter_params &P, const uint4 
             }
         }
         // level 1b: those that do wait in the queue until the wave has a batch of them (wave-wide steps from here on)
-        if (P.dense_debug & 1u)
-            pm = 0;
         while (__ballot(pm != 0) != 0) {
             const bool pos = pm != 0;
             const uint32_t b = pos ? (uint32_t)__ffs(pm) - 1u : 0u;
@@ -821,7 +816,7 @@ __global__ __launch_bounds__(1024) void seed_filter_dense_kernel(const filter_pa
             uint4 nxt[U];
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                nxt[u] = load16_stream<true>(lane_text + (ch + u) * 1024);
+                nxt[u] = load16_stream(lane_text + (ch + u) * 1024);
             for (; ch < fast_end; ch += U) {
                 uint4 cur[U];
 #pragma unroll
@@ -832,7 +827,7 @@ __global__ __launch_bounds__(1024) void seed_filter_dense_kernel(const filter_pa
                 const uint64_t ustride = more ? 1024 : 0;
 #pragma unroll
                 for (int u = 0; u < U; ++u)
-                    nxt[u] = load16_stream<true>(lane_text + pf * 1024 + (uint64_t)u * ustride);
+                    nxt[u] = load16_stream(lane_text + pf * 1024 + (uint64_t)u * ustride);
                 __builtin_amdgcn_sched_barrier(0); // the prefetch stays ahead of the group's work
                 dense_group<U, NP, S, KM>(P, cur, base0 + ch * 1024, span_base, carry_in, lane, lds, Q, qn);
             }
@@ -919,7 +914,7 @@ __global__ __launch_bounds__(1024) void seed_filter_packed_kernel(const filter_p
         uint4 nxt[U2];
 #pragma unroll
         for (int u = 0; u < U2; ++u)
-            nxt[u] = load16_stream<true>(reinterpret_cast<const uint8_t *>(lane_src + (c_begin + u) * 64));
+            nxt[u] = load16_stream(reinterpret_cast<const uint8_t *>(lane_src + (c_begin + u) * 64));
         for (uint64_t ch = c_begin; ch < fast_end; ch += U2) {
             uint4 cur[U2];
 #pragma unroll
@@ -930,7 +925,7 @@ __global__ __launch_bounds__(1024) void seed_filter_packed_kernel(const filter_p
             const uint64_t ustride = more ? 64 : 0;
 #pragma unroll
             for (int u = 0; u < U2; ++u)
-                nxt[u] = load16_stream<true>(reinterpret_cast<const uint8_t *>(lane_src + pf * 64 + (uint64_t)u * ustride));
+                nxt[u] = load16_stream(reinterpret_cast<const uint8_t *>(lane_src + pf * 64 + (uint64_t)u * ustride));
             __builtin_amdgcn_sched_barrier(0); // as in seed_filter_kernel: the prefetch stays ahead of the group's work
             uint32_t w[NWD], prev[NWD];
             const uint32_t nv[1] = {0};
@@ -1062,7 +1057,6 @@ struct resolve_params
     // the host looked (deferred completion, SPM_SCAN_DEFER).  So the overflow is also recorded HERE, on the device, where it
     // sticks until the host has emptied the table: a scan that finds it set declares itself void.
     uint32_t *table_poison;
-    uint32_t debug_stage;   // diagnostics (SPM_HIP_RESOLVE_DEBUG): cut the kernel short after stage 1..4 to time the stages (wrong results)
 };
 
 // Band table slot: .x = key (kBandEmpty = all ones: free), .y = value kept so that a free slot is ALL ONES (one memset
@@ -1458,8 +1452,6 @@ __device__ __forceinline__ void check_pairs(const resolve_params &R, resolve_wav
             live = seed_intact(R, t, val, (rng >> 16) & 0x1F, (rng & kRngWhole) ? R.key_len + ((rng >> 5) & 0x1F) : 0u, sb, se);
             rng |= kSeedChecked;
         }
-        if (R.debug_stage == 3)
-            live = false;
         through = live;
         if (live && R.pieces_check) {
             const uint32_t m = (uint32_t)R.m[pat], k = (uint32_t)R.k[pat];
@@ -1470,8 +1462,6 @@ __device__ __forceinline__ void check_pairs(const resolve_params &R, resolve_wav
             }
         }
     }
-    if (R.debug_stage == 4 && through)
-        live = false;
     // back into the queue: alive, not through
     {
         const bool back = live && !through;
@@ -1661,8 +1651,6 @@ __global__ __launch_bounds__(256) void resolve_kernel(const resolve_params R)
                 }
             }
         }
-        if (R.debug_stage == 1)
-            cnt = 0;
         // ... then the (survivor, entry) pairs of the whole wave are dealt to its lanes, 64 at a time: pair i belongs to the
         // lane whose inclusive prefix sum of `cnt` is the first one above i
         uint32_t incl = cnt;
@@ -1713,8 +1701,6 @@ __global__ __launch_bounds__(256) void resolve_kernel(const resolve_params R)
                     }
                 }
             }
-            if (R.debug_stage == 2)
-                have = false;
             // queue the pairs that are left; 64 waiting pairs are resolved at once
             const uint64_t mm = __ballot(have);
             if (mm != 0) {
@@ -2213,6 +2199,9 @@ __global__ __launch_bounds__(256) void verify_kernel(const verify_params P)
 // lanes, a wave holds two bands, and 2 800 bands are 1 400 busy waves on 1 024 SIMDs: the SIMDs that got two of them run
 // every step twice, and they set the kernel's duration.  Two blocks per lane (the second takes the first one's hout in the
 // same step) put four bands into a wave -- 700 busy waves, at most one per SIMD -- at ~1.7x the instructions of a step.
+// Measured on C5 (2 798 bands of |P| = 1024): one block per lane 0.300 ms, two 0.358 -- a step is a chain of dependent
+// instructions, and the second block lengthens it -- so only NB = 1 is launched.  (Written out without the NB loops, the
+// kernel compiles to the same registers but a schedule that measured 2 % slower.)
 template <int G, int NB>
 __global__ __launch_bounds__(256) void verify_wave_kernel(const verify_params P, const uint32_t *__restrict__ peq_bot)
 {

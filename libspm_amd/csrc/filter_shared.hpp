@@ -29,23 +29,16 @@ SPM_HD inline seed_plan plan_seeds(uint32_t m, uint32_t k)
     return {k + surplus, m / (k + surplus)};
 }
 
-template <int HV>
+constexpr uint32_t kBloomProbes = 4; // Bloom cascade: probes per key
+
+// i-th probe index of the Bloom cascade (before masking to the bitmap size): xor-shift + rotate, 3 full-rate VALU.  Index
+// bits are GF(2)-linear in the key; on the text side the keys are (near) uniform 16-mers, so linearity costs nothing there.
 SPM_HD inline uint32_t bloom_hash(uint32_t key, uint32_t i)
 {
-    // i-th probe index (before masking to the bitmap size).
-    if (HV != 1) {
-        // multiplicative hashing, distinct odd constants (v_mul_lo_u32 is quarter rate on CDNA)
-        const uint32_t c[4] = {0x9E3779B1u, 0x85EBCA6Bu, 0xC2B2AE35u, 0x27D4EB2Fu};
-        uint32_t x = key ^ (key >> (15 + i));
-        return (x * c[i & 3]) >> 7;
-    } else {
-        // xor-shift + rotate: 3 full-rate VALU.  Index bits are GF(2)-linear in the key; on the text side the
-        // keys are (near) uniform 16-mers, so linearity costs nothing there.
-        const uint32_t sh[4] = {14, 11, 17, 9};
-        const uint32_t ro[4] = {0, 7, 13, 19};
-        const uint32_t x = key ^ (key >> sh[i & 3]);
-        return ro[i & 3] ? ((x >> ro[i & 3]) | (x << (32 - ro[i & 3]))) : x;
-    }
+    const uint32_t sh[4] = {14, 11, 17, 9};
+    const uint32_t ro[4] = {0, 7, 13, 19};
+    const uint32_t x = key ^ (key >> sh[i & 3]);
+    return ro[i & 3] ? ((x >> ro[i & 3]) | (x << (32 - ro[i & 3]))) : x;
 }
 
 // ---- perfect-hash fingerprint table (hash-and-displace) ---------------------------------------------------------

@@ -40,41 +40,28 @@ inline uint32_t next_pow2(uint32_t x)
     return p;
 }
 
-// every knob of the index build, read from the environment in ONE place (spm_hip_patterns_create / the self-check)
+// every knob of the index build, read from the environment in ONE place (spm_hip_patterns_create / the self-check).  Apart
+// from the thread count, each one is set by a test to reach a path that some needle set also takes by default.
 struct index_tuning
 {
-    int force_keylen = 0, force_stride = 0;
+    int force_stride = 0;
     int max_keys = 57344; // keys per LDS fingerprint table
-    int max_passes = 256;
-    int hash = 2, probes = 4, bitmap_words = 0;
+    int hash = 2;           // 2: perfect-hash fingerprint table (Bloom cascade where it cannot be built), 1: Bloom cascade
     int anchor = 1;
-    int dedupe = 1, merge_run = 12;
+    int dedupe = 1;
     int dense = 1;          // 0: never, 1: when the sparse plan needs several passes or stride 1, 2: whenever the set admits it
-    int dense_min_density = 0; // force at least this many sixteenths of the dimers as anchors (diagnostics)
-    int dense_max_density = 8; // a set that needs more than this many sixteenths keeps its sparse passes (dense = 2: no limit)
-    int dense_cmax = 4;     // pieces of a needle may overlap up to this many deep (c k + 1 pieces then)
-    int dense_sweeps = 2;   // rounds of key re-selection that make needles share presence bits (0: first-fit keys)
-    int sparse_bits = 1;    // sparse passes of stride 1 / 2 over dna4: presence bits + L2 buckets as level 1 (0: fingerprint table)
+    int dense_min_density = 0; // force at least this many sixteenths of the dimers as anchors
     int threads = 0;        // 0: hardware concurrency, at most 16
     static index_tuning from_env()
     {
         index_tuning T;
-        T.force_keylen = env_int("SPM_HIP_FILTER_KEYLEN", 0);
         T.force_stride = env_int("SPM_HIP_FILTER_STRIDE", 0);
         T.max_keys = std::max(1024, env_int("SPM_HIP_FILTER_MAX_KEYS", 57344));
-        T.max_passes = std::max(1, env_int("SPM_HIP_FILTER_MAX_PASSES", 256));
-        T.hash = std::max(0, std::min(2, env_int("SPM_HIP_FILTER_HASH", 2)));
-        T.probes = std::max(1, std::min(4, env_int("SPM_HIP_FILTER_PROBES", 4)));
-        T.bitmap_words = env_int("SPM_HIP_FILTER_BITMAP_WORDS", 0);
+        T.hash = std::max(1, std::min(2, env_int("SPM_HIP_FILTER_HASH", 2)));
         T.anchor = env_int("SPM_HIP_FILTER_ANCHOR", 1);
         T.dedupe = env_int("SPM_HIP_FILTER_DEDUPE", 1);
-        T.merge_run = std::max(1, env_int("SPM_HIP_FILTER_MERGE_RUN", 12));
         T.dense = env_int("SPM_HIP_FILTER_DENSE", 1);
         T.dense_min_density = env_int("SPM_HIP_FILTER_DENSE_MIN_DENSITY", 0);
-        T.dense_max_density = std::max(2, std::min(16, env_int("SPM_HIP_FILTER_DENSE_MAX_DENSITY", 8)));
-        T.dense_cmax = std::max(1, std::min(8, env_int("SPM_HIP_FILTER_DENSE_CMAX", 4)));
-        T.dense_sweeps = std::max(0, std::min(8, env_int("SPM_HIP_FILTER_DENSE_SWEEPS", 2)));
-        T.sparse_bits = env_int("SPM_HIP_FILTER_BITS", 1);
         T.threads = env_int("SPM_HIP_BUILD_THREADS", 0);
         return T;
     }
@@ -246,6 +233,8 @@ struct seed_index
 // text, 16 / 128 needles across a stretch: > 4: 6.4 / 12.2 ms, > 8: 5.0 / 9.2, > 12: 5.0 / 8.4, > 24: 5.1 / 8.7, never: 5.1 /
 // 9.4 -- merged entries skip the per-offset checks and cost bands, single ones cost checks.)
 constexpr size_t kMergeRun = 12;
+// a set that needs more passes than this is left to the brute-force engine
+constexpr size_t kMaxPasses = 256;
 
 struct seed_key // one indexed window: needle p, seed at offset o of the needle, window starting r symbols into the seed
 {
@@ -465,7 +454,7 @@ inline int build_one_index(const needle_view &nv, const index_tuning &T, const s
             size_t j = i + 1;
             while (j < keys.size() && keys[j].key == keys[i].key && (keys[j].val >> 11) == (keys[i].val >> 11))
                 ++j;
-            if (j - i > (size_t)T.merge_run) {
+            if (j - i > kMergeRun) {
                 const uint32_t span = (keys[j - 1].val & 0x7FF) - (keys[i].val & 0x7FF);
                 keys[w] = keys[i];
                 ranges[w] = (uint16_t)(kRngRun | span);
@@ -485,11 +474,11 @@ inline int build_one_index(const needle_view &nv, const index_tuning &T, const s
     }
     F.n_entries = keys.size();
     F.stride = S;
-    F.n_probes = (uint32_t)T.probes;
+    F.n_probes = kBloomProbes;
     F.hash_variant = (uint32_t)T.hash;
     std::vector<uint32_t> &image = F.h_image; // what every workgroup stages into LDS
     image.clear();
-    if (T.sparse_bits != 0 && T.hash == 2 && nv.sigma == 4 && S <= 2 && F.anchor_cm == 0) {
+    if (T.hash == 2 && nv.sigma == 4 && S <= 2 && F.anchor_cm == 0) {
         // 8 or 16 windows of every 16 symbols are looked up: presence bits (one LDS read, no multiply) + L2 buckets
         F.hash_variant = 4;
         build_bits_level1(keys, F);
@@ -593,15 +582,12 @@ inline int build_one_index(const needle_view &nv, const index_tuning &T, const s
         uint32_t words = 1024;
         while ((uint64_t)words * 32 < want_bits && words < 32768)
             words <<= 1;
-        const int force_w = T.bitmap_words;
-        if (force_w >= 256 && force_w <= 32768 && (force_w & (force_w - 1)) == 0)
-            words = (uint32_t)force_w;
         F.bitmap_words = words;
         image.assign(words, 0);
         const uint32_t idx_mask = words * 32 - 1;
         for (const index_kv &e : keys)
             for (uint32_t pr = 0; pr < F.n_probes; ++pr) {
-                const uint32_t hh = (F.hash_variant ? bloom_hash<1>(e.key, pr) : bloom_hash<0>(e.key, pr)) & idx_mask;
+                const uint32_t hh = bloom_hash(e.key, pr) & idx_mask;
                 image[hh >> 5] |= 1u << (hh & 31);
             }
     }
@@ -620,7 +606,7 @@ inline int build_one_index(const needle_view &nv, const index_tuning &T, const s
 // key window that begins with an anchor dimer, plus (c = 1 only) up to 16 neighbouring symbols that no other piece claims
 // -- they go into the entry's signature, so a chance match of the key dies in registers.  Keys are taken greedily from
 // the left: position p is taken if it is anchored and p >= (the c-th last one taken) + 16.  A needle that cannot fill
-// k + 1 pieces tries c = 2, 3, .. dense_cmax; if one needle still fails, the anchor set grows.
+// k + 1 pieces tries c = 2, 3, .. kDenseCmax; if one needle still fails, the anchor set grows.
 //
 // Anchors.  A union of <= kDensePatterns dimer patterns.  Densities are tried in ascending order (1/8, 3/16, 1/4, 5/16,
 // 3/8, 1/2, 3/4, 1); at every density the candidate sets are ranked on a sample of the needles by how many of them they
@@ -675,11 +661,12 @@ inline uint32_t dense_pick(const uint8_t *pat, uint32_t m, uint32_t dimers, uint
     return n;
 }
 
-// smallest overlap depth with which the needle gets its c k + 1 pieces (0: none up to cmax)
-inline uint32_t dense_layout(const uint8_t *pat, uint32_t m, uint32_t k, uint32_t dimers, uint32_t cmax, uint16_t *pos,
-                             uint32_t &n_out)
+constexpr uint32_t kDenseCmax = 4; // pieces of a needle may overlap up to this many deep (c k + 1 pieces then)
+
+// smallest overlap depth with which the needle gets its c k + 1 pieces (0: none up to kDenseCmax)
+inline uint32_t dense_layout(const uint8_t *pat, uint32_t m, uint32_t k, uint32_t dimers, uint16_t *pos, uint32_t &n_out)
 {
-    for (uint32_t c = 1; c <= cmax; ++c) {
+    for (uint32_t c = 1; c <= kDenseCmax; ++c) {
         const uint32_t want = c * k + 1;
         if (want > 255)
             break;
@@ -691,7 +678,7 @@ inline uint32_t dense_layout(const uint8_t *pat, uint32_t m, uint32_t k, uint32_
     return 0;
 }
 
-constexpr uint32_t kDenseMaxPieces = 8 * 7 + 1; // cmax <= 8, k <= 7
+constexpr uint32_t kDenseMaxPieces = kDenseCmax * 7 + 1; // k <= 7
 
 inline bool dense_eligible(const needle_view &nv)
 {
@@ -706,7 +693,7 @@ inline bool dense_eligible(const needle_view &nv)
 }
 
 // the needles of [begin, end) (every step-th one) that have no layout with this anchor set: counted, and listed up to `cap`
-inline uint64_t dense_uncovered(const needle_view &nv, uint32_t dimers, uint32_t cmax, size_t begin, size_t end, size_t step,
+inline uint64_t dense_uncovered(const needle_view &nv, uint32_t dimers, size_t begin, size_t end, size_t step,
                                 std::vector<uint32_t> *list = nullptr, size_t cap = 0)
 {
     uint64_t bad = 0;
@@ -714,7 +701,7 @@ inline uint64_t dense_uncovered(const needle_view &nv, uint32_t dimers, uint32_t
     for (size_t p = begin; p < end; p += step) {
         uint32_t n = 0;
         const uint32_t k = nv.is_myers() ? (uint32_t)nv.k[p] : 0;
-        if (dense_layout(nv.ranks + nv.offsets[p], (uint32_t)nv.m[p], k, dimers, cmax, pos, n) == 0) {
+        if (dense_layout(nv.ranks + nv.offsets[p], (uint32_t)nv.m[p], k, dimers, pos, n) == 0) {
             ++bad;
             if (list && list->size() < cap)
                 list->push_back((uint32_t)p);
@@ -730,12 +717,11 @@ inline uint64_t dense_uncovered(const needle_view &nv, uint32_t dimers, uint32_t
 inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, dense_anchor_set &out)
 {
     const unsigned nt = T.n_threads();
-    const uint32_t cmax = (uint32_t)T.dense_cmax;
     std::vector<uint32_t> hard;
     auto uncovered_all = [&](uint32_t dimers) {
         std::vector<uint64_t> part(nt, 0);
         std::vector<std::vector<uint32_t>> lists(nt);
-        parallel_slices(nv.n, nt, [&](size_t b, size_t e, unsigned t) { part[t] = dense_uncovered(nv, dimers, cmax, b, e, 1, &lists[t], 8); });
+        parallel_slices(nv.n, nt, [&](size_t b, size_t e, unsigned t) { part[t] = dense_uncovered(nv, dimers, b, e, 1, &lists[t], 8); });
         uint64_t s = 0;
         for (unsigned t = 0; t < nt; ++t) {
             s += part[t];
@@ -752,7 +738,7 @@ inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, d
         std::vector<uint64_t> base(cands.size(), 0);
         parallel_slices(cands.size(), nt, [&](size_t b, size_t e, unsigned) {
             for (size_t i = b; i < e; ++i)
-                base[i] = dense_uncovered(nv, cands[i].dimers, cmax, 0, nv.n, sample_step);
+                base[i] = dense_uncovered(nv, cands[i].dimers, 0, nv.n, sample_step);
         });
         std::vector<uint8_t> tried(cands.size(), 0);
         uint64_t best_fail = ~0ull;
@@ -764,7 +750,7 @@ inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, d
                     continue;
                 uint64_t bad = base[i];
                 for (uint32_t p : hard)
-                    bad += 4096 * dense_uncovered(nv, cands[i].dimers, cmax, p, (size_t)p + 1, 1);
+                    bad += 4096 * dense_uncovered(nv, cands[i].dimers, p, (size_t)p + 1, 1);
                 if (bad < best_bad) {
                     best_bad = bad;
                     best = i;
@@ -792,7 +778,7 @@ inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, d
             for (size_t h = hard_before; h < hard.size(); ++h)
                 for (size_t i = 0; i < cands.size(); i += 3) {
                     ++asked;
-                    placed += dense_uncovered(nv, cands[i].dimers, cmax, hard[h], (size_t)hard[h] + 1, 1) == 0 ? 1 : 0;
+                    placed += dense_uncovered(nv, cands[i].dimers, hard[h], (size_t)hard[h] + 1, 1) == 0 ? 1 : 0;
                 }
             if (2 * placed > asked)
                 break;
@@ -828,8 +814,8 @@ inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, d
         return r;
     };
     // the ladder: 2, 3, 4, 5, 6, 8, 12, 16 sixteenths of the dimers are anchors (a rung is built only if the ones below it
-    // leave a needle without a layout).  Beyond dense_max_density the set is not worth a dense pass (unless forced).
-    const int max_density = T.dense >= 2 ? 16 : T.dense_max_density;
+    // leave a needle without a layout).  Beyond 8 sixteenths the set is not worth a dense pass (unless forced).
+    const int max_density = T.dense >= 2 ? 16 : 8;
     dense_anchor_set e8, e4, e2;
     for (int rung = 0; rung < 8; ++rung) {
         std::vector<dense_anchor_set> c;
@@ -878,8 +864,6 @@ inline bool choose_dense_anchors(const needle_view &nv, const index_tuning &T, d
 inline void dense_share_bits(const needle_view &nv, const index_tuning &T, uint32_t dimers, const std::vector<uint8_t> &cc,
                              const std::vector<uint32_t> &first, std::vector<uint16_t> &pos_flat)
 {
-    if (T.dense_sweeps <= 0)
-        return;
     thread_team team(T.n_threads());
     std::vector<uint16_t> ref(1u << kDenseBloomBits, 0); // keys per presence bit
     auto key_at = [&](const uint8_t *pat, uint32_t i) {
@@ -905,7 +889,7 @@ inline void dense_share_bits(const needle_view &nv, const index_tuning &T, uint3
     const unsigned nt = team.size();
     std::vector<std::vector<std::vector<uint32_t>>> upd(nt, std::vector<std::vector<uint32_t>>(nt));
     auto range_of = [&](uint32_t bit) { return (unsigned)(((uint64_t)bit * nt) >> kDenseBloomBits); };
-    for (int sweep = 0; sweep < T.dense_sweeps; ++sweep)
+    for (int sweep = 0; sweep < 2; ++sweep)
         for (uint32_t round = 0; round < kRounds; ++round) {
             const size_t rb = (size_t)nv.n * round / kRounds, re = (size_t)nv.n * (round + 1) / kRounds;
             for (auto &per_thread : upd) // (every thread's files, also of threads that get no slice this round)
@@ -1021,7 +1005,6 @@ inline int build_dense_index(const needle_view &nv, const index_tuning &T, seed_
     const double ms_anchors = ms(t0);
     const auto t1 = iclk::now();
     const unsigned nt = T.n_threads();
-    const uint32_t cmax = (uint32_t)T.dense_cmax;
     // ---- layouts, per needle (threads): key positions first (first fit), then the keys laid out back to back ----
     std::vector<uint8_t> cc(nv.n, 0), nn(nv.n, 0);
     std::vector<uint32_t> first(nv.n + 1, 0);
@@ -1033,7 +1016,7 @@ inline int build_dense_index(const needle_view &nv, const index_tuning &T, seed_
         for (size_t p = b; p < e; ++p) {
             uint32_t n = 0;
             const uint32_t k = nv.is_myers() ? (uint32_t)nv.k[p] : 0;
-            cc[p] = (uint8_t)dense_layout(nv.ranks + nv.offsets[p], (uint32_t)nv.m[p], k, A.dimers, cmax, pos, n);
+            cc[p] = (uint8_t)dense_layout(nv.ranks + nv.offsets[p], (uint32_t)nv.m[p], k, A.dimers, pos, n);
             nn[p] = (uint8_t)n;
             out.insert(out.end(), pos, pos + n);
         }
@@ -1174,9 +1157,6 @@ inline int build_filter_index(const needle_view &nv, const index_tuning &T, seed
             sparse_ok = false; // too many keys for their length: most text windows would match one by chance
     }
     if (sparse_ok) {
-        const int force_h = T.force_keylen;
-        if (force_h >= (int)kKeyMin && force_h <= (int)std::min(qmin, kKeyMax))
-            H = (uint32_t)force_h;
         while (Smax * 2 <= 16 && Smax * 2 <= qmin - (H - 1))
             Smax *= 2;
         if (T.force_stride > 0 && (uint32_t)T.force_stride <= Smax)
@@ -1240,7 +1220,6 @@ inline int build_filter_index(const needle_view &nv, const index_tuning &T, seed
                 }
             }
         }
-        const uint32_t max_passes = (uint32_t)T.max_passes;
         X.filter_stride = S;
         X.filter_key_len = H;
         // ---- which windows are indexed, and in which pass ----
@@ -1359,7 +1338,7 @@ inline int build_filter_index(const needle_view &nv, const index_tuning &T, seed
                 p0 = p1;
             }
         }
-        if (pass_items.size() > max_passes) {
+        if (pass_items.size() > kMaxPasses) {
             X = seed_index();
             return SPM_OK; // too many passes to be worth it: brute force
         }
@@ -1484,7 +1463,7 @@ inline int host_selftest(int algo, const uint8_t *ranks_concat, const uint32_t *
         }
         const uint32_t idx_mask = F.bitmap_words * 32 - 1;
         for (uint32_t pr = 0; pr < F.n_probes; ++pr) {
-            const uint32_t x = (F.hash_variant ? bloom_hash<1>(key, pr) : bloom_hash<0>(key, pr)) & idx_mask;
+            const uint32_t x = bloom_hash(key, pr) & idx_mask;
             if (!((F.h_image[x >> 5] >> (x & 31)) & 1))
                 return false;
         }

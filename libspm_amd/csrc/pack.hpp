@@ -84,17 +84,13 @@ __device__ __forceinline__ uint4 load_text16(const uint8_t *text, uint64_t idx, 
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-template <bool NT>
+// streamed once: nontemporal keeps it from displacing the key table in L2 and measures +13 % on a pure 16 GiB read
+// (tools/hbm_read_probe: 7.0 vs 6.2 TB/s)
 __device__ __forceinline__ uint4 load16_stream(const uint8_t *p)
 {
-    if (NT) {
-        // streamed once: nontemporal keeps it from displacing the key table in L2 and measures +13 % on a pure
-        // 16 GiB read (tools/hbm_read_probe: 7.0 vs 6.2 TB/s)
-        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
-        return make_uint4(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1),
-                          __builtin_nontemporal_load(q + 2), __builtin_nontemporal_load(q + 3));
-    }
-    return *reinterpret_cast<const uint4 *>(p);
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+    return make_uint4(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1),
+                      __builtin_nontemporal_load(q + 2), __builtin_nontemporal_load(q + 3));
 }
 
 } // namespace spm_hip

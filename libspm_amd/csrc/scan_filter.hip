@@ -5,6 +5,85 @@
 
 namespace
 {
+// raise the kernel's dynamic LDS limit to what this launch asks for, then launch it
+template <typename K, typename... Args>
+void launch(K kernel, dim3 grid, uint32_t threads, size_t lds, hipStream_t s, Args... args)
+{
+    hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, args...);
+}
+
+using filter_kernel = void (*)(filter_params);
+using packed_kernel = void (*)(filter_params, const uint4 *);
+
+// The streaming kernel of each pass the index build (index_build.hpp) can produce; nullptr for any other combination.
+// Sparse passes on the 1-byte text, seed_filter_kernel<S, U, HV, SIG, KM>: U 1-KiB chunks per group (8 from stride 4 on,
+// 2 at strides 1 and 2); KM = keys shorter than 16 symbols, which only strides 1 and 2 carry.
+//   dna4, fingerprint table (HV 2): strides 4..16 (strides 1 and 2 use presence bits, unless anchored);
+//   dna4, Bloom cascade (HV 1): every stride -- SPM_HIP_FILTER_HASH=1, or a fingerprint table that could not be built;
+//   dna5 / dna15: fingerprint table only, every stride.
+template <int S, int U, bool KM>
+filter_kernel sparse_kernel(uint32_t hv, uint32_t sigma)
+{
+    if (hv == 2 && sigma == 5)
+        return seed_filter_kernel<S, U, 2, 5, KM>;
+    if (hv == 2 && sigma == 15)
+        return seed_filter_kernel<S, U, 2, 15, KM>;
+    if (hv == 1 && sigma == 4)
+        return seed_filter_kernel<S, U, 1, 4, KM>;
+    if constexpr (S >= 4)
+        if (hv == 2 && sigma == 4)
+            return seed_filter_kernel<S, U, 2, 4, KM>;
+    return nullptr;
+}
+
+filter_kernel select_filter_kernel(const filter_index &F, uint32_t sigma, bool km)
+{
+    if (F.dense) { // the dense pass: anchors = a union of n_pat dimer patterns
+        switch (F.n_pat) {
+        case 0:
+        case 1: return seed_filter_dense_kernel<4, 1>;
+        case 2: return seed_filter_dense_kernel<4, 2>;
+        case 3: return seed_filter_dense_kernel<4, 3>;
+        default: return nullptr;
+        }
+    }
+    if (F.hash_variant == 4) { // presence bits + L2 buckets as level 1 of a sparse dna4 pass
+        if (F.stride == 1)
+            return km ? seed_filter_dense_kernel<4, 1, 1, true> : seed_filter_dense_kernel<4, 1, 1, false>;
+        if (F.stride == 2)
+            return km ? seed_filter_dense_kernel<4, 1, 2, true> : seed_filter_dense_kernel<4, 1, 2, false>;
+        return nullptr;
+    }
+    switch (F.stride) {
+    case 16: return km ? nullptr : sparse_kernel<16, 8, false>(F.hash_variant, sigma);
+    case 8: return km ? nullptr : sparse_kernel<8, 8, false>(F.hash_variant, sigma);
+    case 4: return km ? nullptr : sparse_kernel<4, 8, false>(F.hash_variant, sigma);
+    case 2: return km ? sparse_kernel<2, 2, true>(F.hash_variant, sigma) : sparse_kernel<2, 2, false>(F.hash_variant, sigma);
+    case 1:
+        // anchored pass: few windows per lane are looked up, so a lane can hold more text
+        if (F.anchor_cm != 0 && F.hash_variant == 2 && sigma == 4 && !km)
+            return seed_filter_kernel<1, 4, 2, 4, false, true>;
+        return km ? sparse_kernel<1, 2, true>(F.hash_variant, sigma) : sparse_kernel<1, 2, false>(F.hash_variant, sigma);
+    default: return nullptr;
+    }
+}
+
+// sparse dna4 passes with the fingerprint table over the 2-bit shadow, seed_filter_packed_kernel<S, U2, 2, false>: strides
+// 4..16 (stride 1 has 16 windows per word, and 4 words already fill the 32-bit survivor mask twice over; stride 2 uses
+// presence bits)
+packed_kernel select_packed_kernel(uint32_t stride, bool km)
+{
+    if (km)
+        return nullptr;
+    switch (stride) {
+    case 16: return seed_filter_packed_kernel<16, 4, 2, false>;
+    case 8: return seed_filter_packed_kernel<8, 4, 2, false>;
+    case 4: return seed_filter_packed_kernel<4, 2, 2, false>;
+    default: return nullptr;
+    }
+}
+
 template <int NWN>
 void launch_verify_nw(const verify_params &V, dim3 grid, hipStream_t s)
 {
@@ -14,52 +93,35 @@ void launch_verify_nw(const verify_params &V, dim3 grid, hipStream_t s)
     while (threads > 64 && per_thread * threads > 128 * 1024)
         threads >>= 1;
     const size_t lds = per_thread * threads + (size_t)(threads / 64) * kHitStage * sizeof(spm_hit);
-    hipFuncSetAttribute((const void *)verify_kernel<NWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((verify_kernel<NWN>), grid, dim3(threads), lds, s, V);
+    launch(verify_kernel<NWN>, grid, threads, lds, s, V);
 }
 
-template <int G, int NB>
-void launch_verify_wave_g(const scan_tuning &T, verify_params V, const uint32_t *peq_bot, uint32_t max_m, dim3 grid, hipStream_t s)
+template <int G>
+void launch_verify_wave_g(verify_params V, const uint32_t *peq_bot, uint32_t max_m, dim3 grid, hipStream_t s)
 {
     // One wave per workgroup: a scan leaves a few thousand long bands, i.e. far fewer busy waves than the GPU has SIMDs,
     // and each is a serial chain ~1500 steps long.  With four-wave workgroups filled in order, the dispatcher packed the
     // busy waves four to a SIMD on a third of the CUs and left the rest idle.
-    const uint32_t threads = (uint32_t)std::max(64, std::min(256, T.verify_wave_threads));
-    grid.x *= 256 / threads;
+    grid.x *= 4;
     const uint32_t n_slots = 2 * V.max_k + 1 + V.max_span;
     // text window of one candidate: cold start |P| + k symbols before the first end position, then the end positions
     V.wave_text = ((max_m + V.max_k + n_slots + 16 + 15) & ~15u) + 16;
     const size_t per_group = ((n_slots * 2 + 15) & ~15u) + V.wave_text;
-    size_t lds = (size_t)(threads / 64) * (64 / G) * per_group;
-    // (diagnostics: a larger LDS claim per workgroup caps how many of them a CU takes at once)
-    lds = std::max<size_t>(lds, (size_t)std::max(0, std::min(160, T.verify_wave_lds_kb)) * 1024);
-    hipFuncSetAttribute((const void *)verify_wave_kernel<G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((verify_wave_kernel<G, NB>), grid, dim3(threads), lds, s, V, peq_bot);
+    launch(verify_wave_kernel<G, 1>, grid, 64, (64 / G) * per_group, s, V, peq_bot);
 }
 
-// long needles: NB 32-row blocks per lane, G = lanes per band >= blocks of the longest needle / NB.  SPM_HIP_VERIFY_WAVE_NB=2:
-// two blocks per lane from 17 blocks on (four |P| = 1024 bands share a wave instead of two).
-void launch_verify_wave(const scan_tuning &T, uint32_t n_blocks, const verify_params &V, const uint32_t *peq_bot, uint32_t max_m,
-                        dim3 grid, hipStream_t s)
+// long needles: one 32-row block per lane, G = lanes per band >= blocks of the longest needle
+void launch_verify_wave(uint32_t n_blocks, const verify_params &V, const uint32_t *peq_bot, uint32_t max_m, dim3 grid,
+                        hipStream_t s)
 {
-    // (measured on C5, 2 798 bands of |P| = 1024: one block per lane 0.300 ms, two 0.358 -- a step is a chain of dependent
-    // instructions, its latency and not its issue slots set the pace, and the second block lengthens the chain.)
-    const bool two = T.verify_wave_nb >= 2;
     if (n_blocks <= 8)
-        launch_verify_wave_g<8, 1>(T, V, peq_bot, max_m, grid, s);
+        launch_verify_wave_g<8>(V, peq_bot, max_m, grid, s);
     else if (n_blocks <= 16)
-        launch_verify_wave_g<16, 1>(T, V, peq_bot, max_m, grid, s);
-    else if (n_blocks <= 32) {
-        if (two)
-            launch_verify_wave_g<16, 2>(T, V, peq_bot, max_m, grid, s);
-        else
-            launch_verify_wave_g<32, 1>(T, V, peq_bot, max_m, grid, s);
-    } else {
-        if (two)
-            launch_verify_wave_g<32, 2>(T, V, peq_bot, max_m, grid, s);
-        else
-            launch_verify_wave_g<64, 1>(T, V, peq_bot, max_m, grid, s);
-    }
+        launch_verify_wave_g<16>(V, peq_bot, max_m, grid, s);
+    else if (n_blocks <= 32)
+        launch_verify_wave_g<32>(V, peq_bot, max_m, grid, s);
+    else
+        launch_verify_wave_g<64>(V, peq_bot, max_m, grid, s);
 }
 
 // nwn = 32-bit words that can hold needle rows = ceil(max |P| / 32), rounded up to an instantiated width
@@ -146,23 +208,20 @@ int run_filter(const scan_args &A)
     uint64_t band_slots = 1u << 12;
     while (band_slots < 2 * band_cap)
         band_slots <<= 1;
-    // bands: Bw diagonals each.  Sets with surplus seeds: (k+1) x factor, overlapping by k + 1 (wider bands mean fewer
-    // occurrences whose seeds straddle two of them at the price of more end positions per verification; 4(k+1) measured
-    // best for |P| = 1024, k = 64; the lane-per-band kernel keeps its end-position slots per thread: narrow bands there).
-    // Other sets: 64 diagonals, no overlap -- every band with a seed hit is verified.
+    // bands: Bw diagonals each.  Sets with surplus seeds: 4(k+1), overlapping by k + 1 (wider bands mean fewer occurrences
+    // whose seeds straddle two of them at the price of more end positions per verification; 4(k+1) measured best for
+    // |P| = 1024, k = 64; the lane-per-band kernel keeps its end-position slots per thread: k + 1 there).
+    // Other sets: 32 diagonals, no overlap -- every band with a seed hit is verified.
     uint32_t nwn = std::max(1u, (ps->max_m + 31) / 32);
     const int wave_min = A.tune.verify_wave_min_words; // 0 = never use the wave-per-band kernel
     // (the wave-per-band kernel keeps the match masks of <= 5 symbols in registers: dna15 sets use the lane-per-band one)
     const bool use_wave = ps->d_peq_bot && wave_min > 0 && nwn >= (uint32_t)wave_min && ps->sigma <= 5;
     const bool overlap = ps->d_surplus != nullptr;
-    uint32_t Bw;
+    uint32_t Bw = 32; // (one mask bit per diagonal)
     if (overlap) {
-        const uint32_t bw_factor = use_wave ? (uint32_t)std::max(1, A.tune.band_factor) : 1u;
-        Bw = (ps->max_k + 1) * bw_factor;
+        Bw = (ps->max_k + 1) * (use_wave ? 4 : 1);
         if (Bw + ps->max_k > 2047)
             Bw = ps->max_k + 1;
-    } else {
-        Bw = (uint32_t)std::max(8, std::min(64, A.tune.band)); // (one mask bit per diagonal)
     }
     const uint32_t max_span = Bw - 1 + (overlap ? ps->max_k + 1 : 0);
     // dedupe set: one key per reported hit, so twice the hit capacity is room enough; a caller with a huge hit buffer
@@ -185,8 +244,7 @@ int run_filter(const scan_args &A)
     // Exact sets whose needles are their own single seed (k = 0, no `N`, e.g. Shift-Or / Horspool sets): the whole-seed check
     // of the resolve kernel is the whole comparison, so it reports the hits itself -- no band table, no verification launch.
     // (Not for needles that are repeats: their merged index entries skip the per-offset check.)
-    bool exact_hits = ps->max_k == 0 && !overlap && ps->filter_max_range == 0 && ps->d_ranks &&
-                      A.tune.seed_check != 0 && A.tune.exact_from_resolve != 0;
+    bool exact_hits = ps->max_k == 0 && !overlap && ps->filter_max_range == 0 && ps->d_ranks;
     if (exact_hits && ps->exact_whole < 0) {
         bool whole = true;
         for (uint32_t p = 0; p < ps->n && whole; ++p)
@@ -212,7 +270,7 @@ int run_filter(const scan_args &A)
     // Exact sets whose hits come from the resolve kernel report every occurrence once by construction (one sampled window,
     // one entry): no dedupe set, no 4 MiB memset in front of a 0.2 ms scan -- unless a span gives up (the brute-force
     // re-scan of that span would report its hits a second time): then the scan runs again with the set.
-    const bool skip_seen = exact_hits && !A.need_seen && A.tune.exact_skip_dedupe != 0;
+    const bool skip_seen = exact_hits && !A.need_seen;
     const_cast<scan_args &>(A).seen_skipped = skip_seen;
     const_cast<scan_args &>(A).exact_used = exact_hits;
     if (!skip_seen)
@@ -254,220 +312,69 @@ int run_filter(const scan_args &A)
         P.pat_cm[i] = F.pat_cm[i];
     }
     P.bucket_shift = F.bucket_shift;
-    P.dense_debug = (uint32_t)A.tune.dense_debug;
     P.buckets = reinterpret_cast<const uint4 *>(F.d_buckets);
     if (fi > 0) // each pass draws its spans from a fresh head
         SPM_HIP_CHECK(ctx, hipMemsetAsync(H->d_count + 4, 0, sizeof(unsigned long long), ctx->stream));
+    const bool km = F.key_len < 16; // (masked keys)
     const bool bits = F.hash_variant == 4; // presence bits + L2 buckets as level 1 of a sparse pass: the dense kernel's machinery
-    const bool use_packed = !F.dense && !bits && A.text->d_packed && ps->sigma == 4 && F.hash_variant == 2 && F.stride >= 2 &&
+    const bool use_packed = F.hash_variant == 2 && A.text->d_packed && ps->sigma == 4 && F.stride >= 2 &&
                             !(A.opts.flags & SPM_SCAN_IGNORE_PACKED);
     // measured best: 8 waves per CU on the 1-byte text when HBM binds, 16 on the 2-bit shadow and at stride 1 with
     // 16-symbol keys (LDS-bound: C4 25.8 vs 29.1 ms; the other stride-1/2 variants need more than 128 VGPRs)
     // stride 2: two chunks per group (16 windows per lane) need < 128 VGPRs, so 16 waves per CU hide the LDS round trips
     // (C5: 0.53 -> 0.46 ms; four chunks per group hold 167 VGPRs at 8 waves)
-    const bool narrow2 = F.stride == 2 && !use_packed && A.tune.s2_u == 2;
-    const bool wide_ok = use_packed || narrow2 || (F.stride == 1 && F.key_len >= 16 && ps->sigma == 4 &&
-                                                   !A.tune.force_masked);
-    const uint32_t threads = (F.dense || bits) ? 1024u : (uint32_t)std::max(
-        64, std::min(wide_ok ? 1024 : 512, (A.tune.filter_threads > 0 ? A.tune.filter_threads : (wide_ok ? 1024 : 512))));
+    const bool wide_ok = use_packed || F.stride == 2 || (F.stride == 1 && !km && ps->sigma == 4);
+    const uint32_t threads = (F.dense || bits || wide_ok) ? 1024 : 512;
     // + the workgroup's span-dequeue slot (4 words) + one survivor-chunk record per wave (+ dense: one queue per wave)
     const size_t lds = (size_t)F.lds_words * 4 + 16 + 16 * kCandRec * 4 + ((F.dense || bits) ? 16 * sizeof(dense_queue) : 0);
     const uint32_t wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 2048 / threads));
     const uint32_t grid = ctx->n_cu * wg_per_cu;
     const uint64_t n_waves = (uint64_t)grid * (threads / 64);
     const uint64_t n_chunks = (P.hi - (P.lo & ~1023ull) + 1023) / 1024;
-    uint64_t span = n_chunks / (n_waves * (uint64_t)std::max(1, (A.tune.spans_per_wave > 0 ? A.tune.spans_per_wave : 32))) + 1;
+    uint64_t span = n_chunks / (n_waves * 32) + 1;
     // small texts: at least 64 KiB per dequeue as long as every wave still gets ~4 spans (a 1 GiB text ran 14 % faster
     // with 64-chunk spans than with the 24 the rule above gives: fewer dequeue rounds, each a workgroup barrier)
     if (span < 64)
         span = std::max<uint64_t>(span, std::min<uint64_t>(64, n_chunks / (n_waves * 4) + 1));
     span = std::min<uint64_t>(std::max<uint64_t>(span, 8), 4096);
-    const int fs = A.tune.span;
-    if (fs > 0)
-        span = (uint64_t)fs;
     span = (span + 7) & ~7ull; // whole groups of chunks
     P.span_chunks = (uint32_t)span;
     P.span_unit = 1024;
     // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
     // costs the verification about what the re-scan would
-    {
-        const int sb = A.tune.span_budget;
-        P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, span * 1024 / 4);
-    }
+    const int sb = A.tune.span_budget;
+    P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, span * 1024 / 4);
     // span dequeue: per wave while the dequeue rate stays far below what one atomic word sustains (~88/us, i.e.
     // spans >= 192 KiB at 7 TB/s), per workgroup otherwise (measured: C3 2.52 vs 2.59 ms, C2 0.88 vs 0.20 ms)
-    const int dyn = A.tune.dyn;
-    P.dynamic = dyn >= 0 ? (uint32_t)std::min(2, dyn) : (span >= 192 ? 1u : 2u);
-
-    const int U = A.tune.filter_u >= 8 ? 8 : 4;
-    const bool NT = A.tune.nt != 0;
+    P.dynamic = span >= 192 ? 1u : 2u;
     P.hash_variant = F.hash_variant;
-    const bool short_keys = F.key_len < 16 || A.tune.force_masked != 0; // (the env: diagnostics)
-#define LAUNCH_FILTER4(S, UU, NTT, HV, SG, KM)                                                                         \
-    do {                                                                                                               \
-        hipFuncSetAttribute((const void *)seed_filter_kernel<S, UU, NTT, HV, SG, KM>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-        hipLaunchKernelGGL((seed_filter_kernel<S, UU, NTT, HV, SG, KM>), dim3(grid), dim3(threads), lds, ctx->stream,  \
-                           P);                                                                                         \
-    } while (0)
-    // keys shorter than 16 symbols only occur with strides 1 and 2: the masked variants exist for those alone
-#define LAUNCH_FILTER3(S, UU, NTT, HV)                                                                                 \
-    do {                                                                                                               \
-        constexpr bool km = (S) <= 2;                                                                                  \
-        if (ps->sigma == 5) {                                                                                          \
-            if (short_keys)                                                                                            \
-                LAUNCH_FILTER4(S, UU, true, 2, 5, km);                                                                 \
-            else                                                                                                       \
-                LAUNCH_FILTER4(S, UU, true, 2, 5, false);                                                              \
-        } else if (ps->sigma == 15) {                                                                                  \
-            if (short_keys)                                                                                            \
-                LAUNCH_FILTER4(S, UU, true, 2, 15, km);                                                                \
-            else                                                                                                       \
-                LAUNCH_FILTER4(S, UU, true, 2, 15, false);                                                             \
-        } else {                                                                                                       \
-            if (short_keys)                                                                                            \
-                LAUNCH_FILTER4(S, UU, NTT, HV, 4, km);                                                                 \
-            else                                                                                                       \
-                LAUNCH_FILTER4(S, UU, NTT, HV, 4, false);                                                              \
-        }                                                                                                              \
-    } while (0)
-#define LAUNCH_FILTER2(S, UU)                                                                                          \
-    do {                                                                                                               \
-        if (NT) {                                                                                                      \
-            if (F.hash_variant == 2)                                                                                   \
-                LAUNCH_FILTER3(S, UU, true, 2);                                                                        \
-            else if (F.hash_variant == 1)                                                                              \
-                LAUNCH_FILTER3(S, UU, true, 1);                                                                        \
-            else                                                                                                       \
-                LAUNCH_FILTER3(S, UU, true, 0);                                                                        \
-        } else {                                                                                                       \
-            if (F.hash_variant == 2)                                                                                   \
-                LAUNCH_FILTER3(S, UU, false, 2);                                                                       \
-            else if (F.hash_variant == 1)                                                                              \
-                LAUNCH_FILTER3(S, UU, false, 1);                                                                       \
-            else                                                                                                       \
-                LAUNCH_FILTER3(S, UU, false, 0);                                                                       \
-        }                                                                                                              \
-    } while (0)
-#define LAUNCH_FILTER(S, UMAX)                                                                                         \
-    do {                                                                                                               \
-        if (U >= 8 && UMAX >= 8)                                                                                       \
-            LAUNCH_FILTER2(S, (UMAX >= 8 ? 8 : UMAX));                                                                 \
-        else                                                                                                           \
-            LAUNCH_FILTER2(S, (UMAX >= 4 ? 4 : UMAX));                                                                 \
-    } while (0)
-    if (bits) {
-#define LAUNCH_BITS(S, KM)                                                                                             \
-    do {                                                                                                               \
-        hipFuncSetAttribute((const void *)seed_filter_dense_kernel<4, 1, S, KM>,                                       \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-        hipLaunchKernelGGL((seed_filter_dense_kernel<4, 1, S, KM>), dim3(grid), dim3(threads), lds, ctx->stream, P);   \
-    } while (0)
-        const bool km = F.key_len < 16;
-        if (F.stride == 1) {
-            if (km)
-                LAUNCH_BITS(1, true);
-            else
-                LAUNCH_BITS(1, false);
-        } else {
-            if (km)
-                LAUNCH_BITS(2, true);
-            else
-                LAUNCH_BITS(2, false);
-        }
-#undef LAUNCH_BITS
-    } else if (F.dense) {
-#define LAUNCH_DENSE(NP)                                                                                               \
-    do {                                                                                                               \
-        hipFuncSetAttribute((const void *)seed_filter_dense_kernel<4, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (int)lds);                                                                                 \
-        hipLaunchKernelGGL((seed_filter_dense_kernel<4, NP>), dim3(grid), dim3(threads), lds, ctx->stream, P);         \
-    } while (0)
-        if (F.n_pat <= 1)
-            LAUNCH_DENSE(1);
-        else if (F.n_pat == 2)
-            LAUNCH_DENSE(2);
-        else
-            LAUNCH_DENSE(3);
-#undef LAUNCH_DENSE
-    } else if (use_packed) {
+    if (use_packed) {
         // p-chunks of 4096 symbols: recompute the span geometry in those units
         filter_params Q = P;
         const uint64_t n_pchunks = (Q.hi - (Q.lo & ~4095ull) + 4095) / 4096;
-        uint64_t pspan = n_pchunks / (n_waves * (uint64_t)std::max(1, (A.tune.spans_per_wave > 0 ? A.tune.spans_per_wave : 8))) + 1;
+        uint64_t pspan = n_pchunks / (n_waves * 8) + 1;
         pspan = std::min<uint64_t>(std::max<uint64_t>(pspan, 4), 4096);
         pspan = (pspan + 3) & ~3ull;
         Q.span_chunks = (uint32_t)pspan;
         Q.span_unit = 4096;
-        if (A.tune.span_budget <= 0)
+        if (sb <= 0)
             Q.span_budget = (uint32_t)std::max<uint64_t>(256, pspan * 4096 / 4);
-        Q.dynamic = dyn >= 0 ? (uint32_t)std::min(2, dyn) : (pspan >= 48 ? 1u : 2u);
-        const uint4 *shadow = reinterpret_cast<const uint4 *>(A.text->d_packed);
-#define LAUNCH_PACKED2(S, U2, KM)                                                                                      \
-    do {                                                                                                               \
-        hipFuncSetAttribute((const void *)seed_filter_packed_kernel<S, U2, 2, KM>,                                     \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-        hipLaunchKernelGGL((seed_filter_packed_kernel<S, U2, 2, KM>), dim3(grid), dim3(threads), lds, ctx->stream, Q,  \
-                           shadow);                                                                                    \
-    } while (0)
-#define LAUNCH_PACKED(S, U2)                                                                                           \
-    do {                                                                                                               \
-        constexpr bool km = (S) <= 2;                                                                                  \
-        if (short_keys)                                                                                                \
-            LAUNCH_PACKED2(S, U2, km);                                                                                 \
-        else                                                                                                           \
-            LAUNCH_PACKED2(S, U2, false);                                                                              \
-    } while (0)
-        switch (F.stride) {
-        case 16: LAUNCH_PACKED(16, 4); break;
-        case 8: LAUNCH_PACKED(8, 4); break;
-        case 4: LAUNCH_PACKED(4, 2); break;
-        case 2: LAUNCH_PACKED(2, 1); break;
-        default:
-            // stride 1 has 16 windows per word: 4 words already fill the 32-bit survivor mask twice over
-            SPM_SET_ERR(ctx, "internal: packed filter with stride 1");
+        Q.dynamic = pspan >= 48 ? 1u : 2u;
+        const packed_kernel k = select_packed_kernel(F.stride, km);
+        if (!k) {
+            SPM_SET_ERR(ctx, "internal: no packed filter kernel for stride %u, key length %u", F.stride, F.key_len);
             return SPM_E_UNSUPPORTED;
         }
-#undef LAUNCH_PACKED
-#undef LAUNCH_PACKED2
-    } else
-    switch (F.stride) {
-    case 16: LAUNCH_FILTER(16, 8); break;
-    case 8: LAUNCH_FILTER(8, 8); break;
-    case 4: LAUNCH_FILTER(4, 8); break;
-    case 2:
-        if (narrow2)
-            LAUNCH_FILTER2(2, 2);
-        else
-            LAUNCH_FILTER(2, 4);
-        break;
-    default:
-        if (F.anchor_cm != 0 && F.hash_variant == 2 && ps->sigma == 4 && !short_keys) {
-            // anchored pass: few windows per lane are looked up, so a lane can hold more text
-            const int au = A.tune.anchor_u;
-#define LAUNCH_ANCHORED(UU)                                                                                            \
-    do {                                                                                                               \
-        hipFuncSetAttribute((const void *)seed_filter_kernel<1, UU, true, 2, 4, false, true>,                          \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-        hipLaunchKernelGGL((seed_filter_kernel<1, UU, true, 2, 4, false, true>), dim3(grid), dim3(threads), lds,       \
-                           ctx->stream, P);                                                                            \
-    } while (0)
-            if (au >= 8)
-                LAUNCH_ANCHORED(8);
-            else if (au >= 4)
-                LAUNCH_ANCHORED(4);
-            else
-                LAUNCH_ANCHORED(2);
-#undef LAUNCH_ANCHORED
-        } else {
-            LAUNCH_FILTER(1, 2);
+        launch(k, dim3(grid), threads, lds, ctx->stream, Q, reinterpret_cast<const uint4 *>(A.text->d_packed));
+    } else {
+        const filter_kernel k = select_filter_kernel(F, ps->sigma, km);
+        if (!k) {
+            SPM_SET_ERR(ctx, "internal: no filter kernel for stride %u, key length %u, sigma %u, hash variant %u, %u patterns",
+                        F.stride, F.key_len, ps->sigma, F.hash_variant, F.n_pat);
+            return SPM_E_UNSUPPORTED;
         }
-        break;
+        launch(k, dim3(grid), threads, lds, ctx->stream, P);
     }
-#undef LAUNCH_FILTER2
-#undef LAUNCH_FILTER3
-#undef LAUNCH_FILTER4
-#undef LAUNCH_FILTER
     SPM_HIP_CHECK(ctx, hipGetLastError());
     H->stats.main_launches++;
     }
@@ -501,11 +408,11 @@ int run_filter(const scan_args &A)
     R.key_len = ps->filter_key_len;
     R.text = A.text->d;
     R.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
-    R.needle_ranks = A.tune.seed_check ? ps->d_ranks : nullptr;
+    R.needle_ranks = ps->d_ranks;
     R.needle_offsets = ps->d_offsets;
     R.seed_q = ps->d_seed_q;
-    R.flank_check = (ps->sigma == 4 && !overlap && R.needle_ranks && A.tune.flank_check) ? 1u : 0u;
-    R.pieces_check = A.tune.pieces_check ? R.flank_check : 0u;
+    R.flank_check = (ps->sigma == 4 && !overlap && R.needle_ranks) ? 1u : 0u;
+    R.pieces_check = R.flank_check;
     R.m = ps->d_m;
     R.k = ps->d_k;
     R.hay_begin = A.ctx_begin;
@@ -532,7 +439,6 @@ int run_filter(const scan_args &A)
     R.overflow = H->d_count + 2;
     R.hit_cap = H->cap;
     R.table_poison = ctx->d_table_poison;
-    R.debug_stage = (uint32_t)A.tune.resolve_debug;
     R.table_mask = (uint32_t)(band_slots - 1);
     R.bands = d_bands;
     R.band_cap = band_cap;
@@ -542,9 +448,9 @@ int run_filter(const scan_args &A)
     // (5 workgroups per CU are resident at once -- LDS queues, 84 VGPRs --: a larger grid only adds a second, partly filled
     // round.  A lane takes ~4 survivors in turn: measured on C5, whose survivors are few and cheap, 0.137 -> 0.10 ms;
     // c3r 1.33 -> 1.25 ms with the cap alone.)
-    const uint64_t rmax = (uint64_t)ctx->n_cu * (uint64_t)std::max(1, A.tune.resolve_wgs_per_cu);
+    const uint64_t rmax = (uint64_t)ctx->n_cu * 5;
     // (a short survivor list: one survivor per lane, its latency is the kernel's; a long one: four per lane)
-    const uint64_t per_wg = (surv_expect + 255) / 256 <= rmax ? 256 : (uint64_t)std::max(256, A.tune.resolve_surv_per_wg);
+    const uint64_t per_wg = (surv_expect + 255) / 256 <= rmax ? 256 : 1024;
     const uint32_t rgrid = (uint32_t)std::min<uint64_t>(rmax, std::max<uint64_t>(ctx->n_cu / 2, (surv_expect + per_wg - 1) / per_wg));
     hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, R);
     SPM_HIP_CHECK(ctx, hipGetLastError());
@@ -612,7 +518,7 @@ int run_filter(const scan_args &A)
         // (the resolve kernel reported the hits)
     } else if (use_wave) {
         // one verification is a ~1400-step serial chain: enough waves that every band gets its own right away
-        launch_verify_wave(A.tune, nwn, V, ps->d_peq_bot, ps->max_m, dim3(ctx->n_cu * 16), ctx->stream);
+        launch_verify_wave(nwn, V, ps->d_peq_bot, ps->max_m, dim3(ctx->n_cu * 16), ctx->stream);
     } else {
         if (nwn > 8)
             nwn = ps->NW; // power of two beyond 8 words

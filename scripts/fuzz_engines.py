@@ -75,8 +75,6 @@ def make_case(rng, spm, big=0.0):
         env["SPM_HIP_FILTER_DENSE"] = "0"
     if rng.random() < 0.15:
         env["SPM_HIP_FILTER_SPAN_BUDGET"] = str(int(rng.choice([1, 4, 16])))
-    if rng.random() < 0.1:
-        env["SPM_HIP_FILTER_BITS"] = "0"
     return dict(n=n, sigma=sigma, T=T, algo=algo, needles=needles, ks=np.asarray(ks, dtype=np.uint16), env=env)
 
 
