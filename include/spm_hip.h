@@ -181,16 +181,22 @@ int spm_hip_patterns_build_stats(const spm_patterns *p, spm_build_stats *out);
 /* ---- matcher state: replaces capture()/restore() (myers_matcher_restorable.hpp:57-63,136-142;
  * shiftor_matcher_restorable.hpp:44-50).  A state blob holds one record per pattern, each
  * spm_hip_patterns_state_stride() bytes:
- *   Myers:    int32 score; uint32 n_words; uint64 vp[n_words]; uint64 vn[n_words]     (n_words = ceil(|P|/64))
- *   Shift-Or: uint32 n_words; uint32 pad;  uint32 r[n_words]                          (n_words = ceil(|P|/32))
- * spm_hip_patterns_state_init writes the constructor-time state (VP=~0, VN=0, score=|P|; R=~0). */
+ *   Myers:    int32 score; uint32 n_words; uint64 vp[n_words]; uint64 vn[n_words]
+ *   Shift-Or: uint32 n_words; uint32 pad;  uint32 r[n_words]   (stride rounded up to a multiple of 8 bytes)
+ * n_words is set-wide, the same in every record: ceil(max|P| / 64) Myers, ceil(max|P| / 32) Shift-Or, max over the set.
+ * Bit j of vp / vn / r is row j of the needle.  Myers: the DP column after the symbols read, vp bit j set iff
+ * D[j+1] - D[j] = +1, vn bit j iff it is -1, score = D[|P|].  Shift-Or: r bit j clear iff P[0..j] equals the last j+1
+ * symbols read.  Bits at or above the needle's own |P| are zero (vp, vn) or set (r) on output and ignored on input.
+ * spm_hip_patterns_state_init writes the constructor-time state (vp bits of rows below |P| set, vn = 0, score = |P|;
+ * r = ~0). */
 size_t spm_hip_patterns_state_stride(const spm_patterns *p);
 int spm_hip_patterns_state_init(const spm_patterns *p, void *state);
 
 /* ---- scan: replaces seqan_pattern_base::operator()(haystack, callback), seqan_pattern_base.hpp:40-52 ----
  * Scans text[begin,end).  state_in == NULL: fresh matcher (non-restorable semantics).  state_in != NULL:
  * continue from that state (restorable semantics, myers_matcher_restorable.hpp:72-82); state_out (may alias
- * state_in, may be NULL) receives the state after the last symbol. */
+ * state_in, may be NULL) receives the state after the last symbol.  With state_in, left_context changes nothing;
+ * without it and with left_context = 1, state_out is the state after text[0, end). */
 int spm_hip_scan(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, const spm_patterns *patterns,
                  const spm_scan_opts *opts, const void *state_in, void *state_out, spm_hits **out);
 

@@ -140,6 +140,11 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
     // Short chunks stay with the brute-force kernel (unless the caller asks for the filter).
     const bool stateful = has_state || state_out != nullptr;
     const uint64_t state_prefix = has_state && patterns->max_window > 0 ? patterns->max_window - 1 : 0;
+    // First symbol of a state-only pass that ends at `end`: from a cold start there the exit state is exact, because it
+    // is the haystack's first symbol or lies 2 max|P| + 4 symbols before end (every DP cell D[i][j] <= i has an optimal
+    // alignment spanning <= 2i symbols).  With state_in the pass continues from the state at begin instead.
+    const uint64_t tail_len = 2ull * patterns->max_m + 4;
+    const uint64_t tail_begin = std::max(has_state ? begin : A.ctx_begin, end > tail_len ? end - tail_len : 0);
     bool use_filter = want_filter && patterns->n > 0 && end > begin;
     if (stateful && use_filter &&
         (seg_offsets || d_seg_offsets || end - begin <= state_prefix ||
@@ -157,13 +162,20 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
 
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[0], ctx->stream));
     H->timed = true;
-    if (patterns->n == 0 || end == begin) {
+    // (an empty range with left context and no state_in still owes the state after text[0, end): the brute path below)
+    // A prefix hit ends within max_window symbols of the haystack start: a stateless prefix scan that begins later
+    // has nothing to report and nothing to compute.
+    const bool past_prefix_hits = patterns->algo == SPM_ALGO_MYERS_PREFIX && !stateful &&
+                                  begin - A.ctx_begin >= patterns->max_window;
+    if (patterns->n == 0 || past_prefix_hits || (end == begin && (has_state || !state_out || A.ctx_begin == begin))) {
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[3], ctx->stream));
         H->stats.engine_used = SPM_ENGINE_BRUTE;
         if (state_in && state_out && state_out != state_in)
             memcpy(state_out, state_in, spm_hip_patterns_state_stride(patterns) * patterns->n);
+        else if (state_out && !state_in)
+            spm_hip_patterns_state_init(patterns, state_out);
         *out = H.release();
         return SPM_OK;
     }
@@ -399,9 +411,7 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
             H->counted = false;       // more hits may have arrived
         }
         if (state_out) {
-            const uint64_t range = end - begin;
-            const uint64_t tail = std::min<uint64_t>(range, 2ull * patterns->max_m + 4);
-            const uint64_t tb = end - tail;
+            const uint64_t tb = tail_begin;
             const bool from_state = has_state && tb == begin;
             int rc = run_brute(A, tb, end, tb, from_state ? d_in : nullptr, d_out, false, true);
             if (rc != SPM_OK)
@@ -433,8 +443,12 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
         }
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
         const uint64_t range = end - begin;
-        // a scan that must hand back an exact state and fits one tile does both in one pass
-        const bool one_pass_state = state_out && (range <= (1u << 16) || patterns->algo == SPM_ALGO_MYERS_PREFIX);
+        // A scan that must hand back an exact state and fits one tile does both in one pass, unless that pass starts too
+        // late: a single tile cold-starts max_window - 1 symbols before begin, or at ctx_begin (a prefix set's always).
+        const bool prefix = patterns->algo == SPM_ALGO_MYERS_PREFIX;
+        const uint64_t warm = patterns->max_window > 0 ? patterns->max_window - 1 : 0;
+        const uint64_t pass_begin = begin - std::min(warm, begin - A.ctx_begin);
+        const bool one_pass_state = state_out && (prefix || (range <= (1u << 16) && (has_state || pass_begin <= tail_begin)));
         int rc = run_brute(A, begin, end, A.ctx_begin, has_state ? d_in : nullptr, one_pass_state ? d_out : nullptr,
                            true, one_pass_state);
         if (rc != SPM_OK) {
@@ -443,10 +457,8 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
         }
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
         if (state_out && !one_pass_state) {
-            // State after the last symbol: sequentially exact from a cold start 2*max|P| symbols earlier
-            // (every DP cell D[i][j] <= i has an optimal alignment spanning <= 2i symbols).
-            const uint64_t tail = std::min<uint64_t>(range, 2ull * patterns->max_m + 4);
-            const uint64_t tb = end - tail;
+            // State after the last symbol: a state-only pass from tail_begin
+            const uint64_t tb = tail_begin;
             const bool from_state = has_state && tb == begin;
             rc = run_brute(A, tb, end, tb, from_state ? d_in : nullptr, d_out, false, true);
             if (rc != SPM_OK) {

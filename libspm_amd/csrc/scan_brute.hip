@@ -59,6 +59,16 @@ int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_beg
     P.pos_offset = A.opts.pos_offset;
     P.n_groups = ps->n_groups;
     P.warm = ps->max_window > 0 ? ps->max_window - 1 : 0;
+    if (ps->algo == SPM_ALGO_MYERS_PREFIX && !d_state_in) {
+        // a prefix needle's column depends on every symbol since the haystack start: the warm-up begins at ctx_begin
+        // (a cold start later would be taken for the haystack start and report prefix hits that are none).  With a
+        // state the single tile resumes at begin and reads no warm-up.
+        if (begin - ctx_begin > 0xFFFFFF00ull) {
+            SPM_SET_ERR(ctx, "prefix matcher: %llu symbols of left context", (unsigned long long)(begin - ctx_begin));
+            return SPM_E_UNSUPPORTED;
+        }
+        P.warm = (uint32_t)(begin - ctx_begin);
+    }
     P.sigma = ps->sigma;
     P.has_state = d_state_in ? 1 : 0;
     P.peq = ps->d_peq;

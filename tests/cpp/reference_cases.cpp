@@ -558,6 +558,75 @@ static void resident_haystack_cases()
     }
 }
 
+// The chunk-of-13 walk and capture() at every hit again, with a restorable Myers needle of |P| = 1500, k = 20 and a
+// restorable Shift-Or needle of |P| = 100: the mirror's in-callback capture path through the 64-word kernel.
+template <typename get_matcher_t, typename pos_t>
+static void wide_restorable_walks(sequence_t const & hay, get_matcher_t get_matcher, pos_t pos_of)
+{
+    std::vector<std::size_t> all{};
+    auto whole = get_matcher();
+    whole(hay, [&](auto const & finder) { all.push_back(pos_of(finder)); });
+    EXPECT_TRUE(all.size() >= 2);
+    { // chunks of 13, restore(state) before and capture() after each chunk
+        auto matcher = get_matcher();
+        auto state = matcher.capture();
+        std::vector<std::size_t> actual{};
+        for (std::size_t offset = 0; offset < hay.size(); offset += 13) {
+            sequence_t chunk{hay.begin() + offset, hay.begin() + std::min<std::size_t>(offset + 13, hay.size())};
+            matcher.restore(state);
+            matcher(chunk, [&](auto const & finder) { actual.push_back(pos_of(finder) + offset); });
+            state = matcher.capture();
+        }
+        EXPECT_TRUE(actual == all);
+    }
+    { // capture() at every hit: each state, resumed on the rest of the haystack, yields exactly the remaining hits
+        auto matcher = get_matcher();
+        using state_t = spm::matcher_state_t<decltype(matcher)>;
+        std::vector<std::pair<std::size_t, state_t>> at;
+        std::vector<std::size_t> seen;
+        std::size_t last_end = 0;
+        matcher(hay, [&](auto const & finder) {
+            seen.push_back(pos_of(finder));
+            last_end = seqan2::endPosition(finder);
+            at.emplace_back(last_end, spm::capture(matcher));
+        });
+        EXPECT_TRUE(seen == all);
+        for (std::size_t i = 0; i < at.size(); ++i) {
+            auto resumed = get_matcher();
+            spm::restore(resumed, at[i].second);
+            sequence_t rest{hay.begin() + at[i].first, hay.end()};
+            std::vector<std::size_t> got{};
+            resumed(rest, [&](auto const & finder) { got.push_back(pos_of(finder) + at[i].first); });
+            EXPECT_TRUE(std::ranges::equal(got, std::vector<std::size_t>(all.begin() + i + 1, all.end())));
+        }
+        auto plain = get_matcher();
+        plain(hay, [](auto const &) {});
+        EXPECT_TRUE(spm::capture(matcher) == spm::capture(plain));
+    }
+}
+
+static void wide_restorable_cases()
+{
+    std::uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto next_rank = [&] {
+        x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+        return (std::uint8_t)(x >> 62);
+    };
+    sequence_t hay(5000);
+    for (auto & s : hay)
+        s.assign_rank(next_rank());
+    sequence_t long_needle{hay.begin() + 300, hay.begin() + 1800};
+    sequence_t short_needle{hay.begin() + 4000, hay.begin() + 4100};
+    std::copy(long_needle.begin(), long_needle.end(), hay.begin() + 2100); // a second occurrence, 10 substitutions
+    for (std::size_t i = 0; i < 1500; i += 150)
+        hay[2100 + i].assign_rank((long_needle[i].to_rank() + 1) & 3);
+    std::copy(short_needle.begin(), short_needle.end(), hay.begin() + 4500);
+    wide_restorable_walks(hay, [&] { return spm::restorable_myers_matcher{long_needle, 20u}; },
+                          [](auto const & finder) { return (std::size_t)seqan2::endPosition(finder); });
+    wide_restorable_walks(hay, [&] { return spm::restorable_shiftor_matcher{short_needle}; },
+                          [](auto const & finder) { return (std::size_t)seqan2::beginPosition(finder); });
+}
+
 int main()
 {
     horspool_cases();
@@ -572,6 +641,7 @@ int main()
     container_adapter_cases();
     paused_scan_cases();
     resident_haystack_cases();
+    wide_restorable_cases();
     std::printf("%d checks, %d failures\n", checks, failures);
     return failures;
 }

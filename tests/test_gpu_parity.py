@@ -337,7 +337,8 @@ def test_prefix_matcher(spm, ctx, oracle):
         assert len(want) >= 1
 
 
-@pytest.mark.parametrize("m,k", [(33, 1), (64, 3), (100, 3), (100, 40), (129, 5), (300, 10), (1024, 64)])
+@pytest.mark.parametrize("m,k", [(33, 1), (64, 3), (100, 3), (100, 40), (129, 5), (300, 10), (1024, 64),
+                                 (2048, 100), (1500, 30)])
 def test_brute_cutoff_kernel_equals_full_kernel_and_oracle(spm, ctx, oracle, m, k):
     """Ukkonen cut-off kernel (band of active 32-row words per lane) vs the full-width kernel vs the oracle, on a
     text built to make the band grow and shrink constantly: long near-matches of needle prefixes."""
