@@ -24,11 +24,13 @@
 #include <map>
 #include <memory>
 #include <string_view>
+#include <tuple>
 #include <unordered_map>
 
 #include <libspm/hip/context.hpp>
 #include <libspm/jst/io.hpp>
 #include <libspm/jst/journaled_sequence.hpp>
+#include <libspm/matcher/alignment.hpp>
 
 namespace spm
 {
@@ -40,6 +42,15 @@ struct jst_hit
     std::int32_t errors;
     bool operator==(jst_hit const &) const noexcept = default;
     auto operator<=>(jst_hit const &) const noexcept = default;
+};
+
+// where a hit begins in its haplotype and how it aligns there (journaled_sequence_tree::locate)
+struct jst_alignment
+{
+    std::uint32_t haplotype;
+    std::uint32_t needle;
+    spm::alignment aln; // begin / end in haplotype coordinates, errors, CIGAR transcript
+    bool operator==(jst_alignment const &) const noexcept = default;
 };
 
 struct jst_search_stats
@@ -329,8 +340,74 @@ public:
         return D.usable;
     }
 
+    // search + begin and transcript of every hit: what batch_matcher::locate returns on each materialised haplotype, sorted
+    // like search's hits.  One alignment per segment hit is computed and shared by the haplotypes of its context
+    // (spm_hip_jst_hits_align); trees the device path does not take go through locate_host.  Both return the same vector.
+    std::vector<jst_alignment> locate(spm_patterns * needles, std::size_t window, std::vector<std::uint32_t> const & needle_len,
+                                      bool reports_begin, std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_device(needles, window, reports_begin, block, stats);
+        return locate_host(needles, window, needle_len, reports_begin, block, stats);
+    }
+
+    std::vector<jst_alignment> locate_device(spm_patterns * needles, std::size_t window, bool reports_begin,
+                                             std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, SPM_SCAN_ALIGNABLE, stats);
+        spm_jst_alns * a = nullptr;
+        if (spm_hip_jst_hits_align(hh, 0, &a) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_align", ctx);
+        hip::jst_alns_ptr alns{a};
+        spm_jst_aln const * rec = nullptr;
+        std::uint32_t const * ops = nullptr;
+        std::uint64_t n = 0, n_ops = 0;
+        if (spm_hip_jst_alns_view(a, &rec, &n, &ops, &n_ops) != SPM_OK)
+            hip::fatal("spm_hip_jst_alns_view", ctx);
+        std::vector<jst_alignment> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            out.push_back({rec[i].haplotype, rec[i].pattern,
+                           alignment{static_cast<std::size_t>(rec[i].begin), static_cast<std::size_t>(rec[i].end), rec[i].score,
+                                     ops + rec[i].cigar_off, rec[i].cigar_len}});
+        spm_hip_jst_hits_destroy(hh);
+        sort_alignments(out, reports_begin);
+        return out;
+    }
+
     std::vector<jst_hit> search_device(spm_patterns * needles, std::size_t window, std::size_t block = 0,
                                        jst_search_stats * stats = nullptr) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, 0, stats);
+        spm_jst_hit const * rec = nullptr;
+        std::uint64_t n = 0;
+        if (spm_hip_jst_hits_view(hh, &rec, &n) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_view", ctx);
+        std::vector<jst_hit> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            out.push_back({rec[i].haplotype, rec[i].pos, rec[i].pattern, rec[i].score});
+        spm_hip_jst_hits_destroy(hh);
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+
+    // the order of search's hits: (haplotype, position, needle, errors), position = begin (exact) / end (Myers)
+    static void sort_alignments(std::vector<jst_alignment> & v, bool reports_begin)
+    {
+        auto key = [reports_begin](jst_alignment const & x) {
+            return std::tuple{x.haplotype, reports_begin ? x.aln.begin_position() : x.aln.end_position(), x.needle,
+                              x.aln.errors()};
+        };
+        std::sort(v.begin(), v.end(), [&](jst_alignment const & a, jst_alignment const & b) { return key(a) < key(b); });
+    }
+
+private:
+    // index (once per (window, block)) and search on the device; the caller owns the result
+    spm_jst_hits * device_search(spm_patterns * needles, std::size_t window, std::size_t block, std::uint32_t flags,
+                                 jst_search_stats * stats) const
     {
         spm_ctx * ctx = hip::default_context();
         if (!device_ready())
@@ -347,6 +424,7 @@ public:
         spm_hip_jst_stats(D.tree, &st);
         spm_scan_opts opts{};
         opts.max_hits = std::max<std::uint64_t>(1u << 22, 8 * st.context_symbols / window);
+        opts.flags = flags;
         spm_jst_hits * hh = nullptr;
         for (int attempt = 0;; ++attempt) { // (a hit buffer that proves too small is doubled, not fatal)
             int const rc = spm_hip_jst_search(D.tree, needles, &opts, &hh);
@@ -356,24 +434,16 @@ public:
                 hip::fatal("spm_hip_jst_search", ctx);
             opts.max_hits *= 2;
         }
-        spm_jst_hit const * rec = nullptr;
-        std::uint64_t n = 0;
-        if (spm_hip_jst_hits_view(hh, &rec, &n) != SPM_OK)
-            hip::fatal("spm_hip_jst_hits_view", ctx);
-        std::vector<jst_hit> out;
-        out.reserve(n);
-        for (std::uint64_t i = 0; i < n; ++i)
-            out.push_back({rec[i].haplotype, rec[i].pos, rec[i].pattern, rec[i].score});
-        spm_hip_jst_hits_destroy(hh);
         if (stats) {
             stats->haplotype_symbols = st.haplotype_symbols;
             stats->context_symbols = st.context_symbols;
             stats->contexts = st.contexts;
             stats->unique_contexts = st.unique_contexts;
         }
-        std::sort(out.begin(), out.end());
-        return out;
+        return hh;
     }
+
+public:
 
     // The same search with the contexts built on the host (any allele table) and uploaded.
     std::vector<jst_hit> search_host(spm_patterns * needles, std::size_t window, std::vector<std::uint32_t> const & needle_len,
@@ -424,6 +494,60 @@ public:
                 out.push_back({m.haplotype, m.ctx_lo + local, rec[i].pattern, rec[i].score});
         }
         std::sort(out.begin(), out.end());
+        return out;
+    }
+
+    // locate with the contexts built on the host: the segment hits of spm_hip_scan_segments are aligned as they are
+    // (spm_hip_hits_align, lo = the start of the hit's context) and begin / transcript are fanned out exactly as the hits.
+    std::vector<jst_alignment> locate_host(spm_patterns * needles, std::size_t window, std::vector<std::uint32_t> const & needle_len,
+                                           bool reports_begin, std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        std::size_t const L = block ? block : std::max<std::size_t>(256, 4 * window);
+        context_index const X = build_contexts(window, L);
+        auto const & contexts = X.contexts;
+        auto const & buffer = X.buffer;
+        using member = typename context_index::member;
+        using context = typename context_index::context;
+        if (stats)
+            *stats = X.stats;
+        std::vector<jst_alignment> out;
+        if (contexts.empty())
+            return out;
+        std::vector<std::uint64_t> seg(contexts.size() + 1);
+        for (std::size_t i = 0; i < contexts.size(); ++i)
+            seg[i] = contexts[i].offset;
+        seg.back() = buffer.size();
+        spm_text * t = nullptr;
+        if (spm_hip_text_upload(ctx, buffer.data(), buffer.size(), 4, &t) != SPM_OK)
+            hip::fatal("spm_hip_text_upload", ctx);
+        hip::text_ptr text{t};
+        spm_scan_opts opts{};
+        opts.max_hits = std::max<std::uint64_t>(1u << 20, 4 * buffer.size() / std::max<std::size_t>(window, 1));
+        spm_hit const * rec = nullptr;
+        std::uint64_t n = 0;
+        hip::hits_ptr hits = hip::scan_all_hits(
+            ctx, opts,
+            [&](spm_scan_opts const & o, spm_hits ** h) {
+                return spm_hip_scan_segments(ctx, text.get(), seg.data(), contexts.size(), needles, &o, h);
+            },
+            rec, n, "spm_hip_scan_segments");
+        spm_aln const * al = nullptr;
+        std::uint32_t const * ops = nullptr;
+        hip::alns_ptr alns = hip::align_hits(ctx, hits.get(), al, n, ops);
+        for (std::uint64_t i = 0; i < n; ++i) {
+            std::uint64_t const last = reports_begin ? al[i].begin + needle_len[al[i].pattern] - 1 : al[i].end - 1;
+            std::size_t const c = static_cast<std::size_t>(std::upper_bound(seg.begin(), seg.end(), last) - seg.begin()) - 1;
+            context const & cx = contexts[c];
+            if (last - cx.offset < cx.owned_from)
+                continue; // ends in the left context: owned by the previous block's context
+            for (member const & m : cx.members) {
+                std::size_t const b = static_cast<std::size_t>(m.ctx_lo + (al[i].begin - cx.offset));
+                std::size_t const e = static_cast<std::size_t>(m.ctx_lo + (al[i].end - cx.offset));
+                out.push_back({m.haplotype, al[i].pattern, alignment{b, e, al[i].score, ops + al[i].cigar_off, al[i].cigar_len}});
+            }
+        }
+        sort_alignments(out, reports_begin);
         return out;
     }
 };

@@ -32,6 +32,7 @@ public:
     std::size_t begin_position() const noexcept { return _begin; }
     std::size_t end_position() const noexcept { return _end; }
     int errors() const noexcept { return _errors; }
+    bool operator==(alignment const &) const noexcept = default;
     // BAM-style words len << 4 | op
     std::vector<std::uint32_t> const & cigar() const noexcept { return _cigar; }
     // the same as a SAM string, e.g. "41=1X12=1I45="
@@ -58,6 +59,11 @@ struct alns_deleter
     void operator()(spm_alns * a) const noexcept { spm_hip_alns_destroy(a); }
 };
 using alns_ptr = std::unique_ptr<spm_alns, alns_deleter>;
+struct jst_alns_deleter
+{
+    void operator()(spm_jst_alns * a) const noexcept { spm_hip_jst_alns_destroy(a); }
+};
+using jst_alns_ptr = std::unique_ptr<spm_jst_alns, jst_alns_deleter>;
 
 // the alignments of a completed scan, host order (= the order of spm_hip_hits_view); failures are fatal like every other
 // call of the mirror

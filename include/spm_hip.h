@@ -93,6 +93,10 @@ typedef struct spm_scan_opts {
  * With spm_hip_hits_copy_fused_device a step of a scan loop has no host synchronisation at all: the GPU never waits for
  * the host between steps (the status word of its header says whether the host has to look). */
 #define SPM_SCAN_DEFER 2u
+/* Only spm_hip_jst_search looks at this bit (it never reaches a scan): the result keeps the search's segment hits -- the
+ * hits in context coordinates, before the fan-out -- until it is destroyed, so that spm_hip_jst_hits_align can align
+ * them.  Without it a search holds what it always held and its hits cannot be aligned. */
+#define SPM_SCAN_ALIGNABLE 4u
 
 /* Per-scan device timings, HIP events on the context's stream (ms). */
 typedef struct spm_scan_stats {
@@ -242,7 +246,8 @@ void spm_hip_hits_destroy(spm_hits *hits);
  * Tie order: walking back from (|P|, e - b), a diagonal step (= or X) is taken whenever it is optimal, else an
  * insertion, else a deletion.  The result depends only on (P, text, e, d): bit-identical across runs and engines.
  * Exact sets (Shift-Or, Horspool): begin = pos, end = pos + |P|, CIGAR |P|=.
- * Not supported (SPM_E_UNSUPPORTED): MYERS_PREFIX sets, stateful scans (state_in != NULL), hits of journaled sequences.
+ * Not supported (SPM_E_UNSUPPORTED): MYERS_PREFIX sets, stateful scans (state_in != NULL).  The hits of a
+ * journaled-sequence search have an entry point of their own, spm_hip_jst_hits_align below.
  * The scan's text and needle set must still be alive. */
 typedef struct spm_aln {
     uint64_t begin;       /* b + pos_offset (exact sets: pos) */
@@ -355,6 +360,60 @@ int spm_hip_jst_hits_device(spm_jst_hits *hits, const void **device_records, uin
 /* Copy the first min(n, cap) records into a caller-owned device buffer, asynchronously on the context's stream. */
 int spm_hip_jst_hits_copy_device(spm_jst_hits *hits, void *device_dst, uint64_t cap, uint64_t *n);
 void spm_hip_jst_hits_destroy(spm_jst_hits *hits);
+
+/* ---- begins and alignments of pan-genome hits: spm_hip_hits_align for the result of spm_hip_jst_search -------------
+ * The haplotypes that share a context share it byte for byte, window - 1 symbols of left context included, and begin and
+ * transcript depend only on (P, text, end, distance).  So ONE alignment per segment hit, computed in the context buffer by
+ * the kernels of spm_hip_hits_align (lo = the start of the hit's context), serves every haplotype of that context; a
+ * fan-out kernel writes one record per (haplotype, hit) with the haplotype's coordinates.
+ *   * The search must have been made with spm_scan_opts.flags & SPM_SCAN_ALIGNABLE, else SPM_E_INVALID.  Tree and needle
+ *     set must still be alive, and the tree must not have been indexed again since the search (spm_hip_jst_index frees
+ *     the context buffer the alignment reads): SPM_E_INVALID otherwise.  MYERS_PREFIX sets cannot be searched at all.
+ *   * Host view: record i belongs to record i of spm_hip_jst_hits_view (order (haplotype, pos, pattern)).  The device
+ *     view is in the arrival order of this call's fan-out and is NOT matched to spm_hip_jst_hits_device; every record
+ *     names its own (haplotype, end, pattern, score).
+ *   * begin is the largest b >= 0 OF THAT HAPLOTYPE with ED(P, hap[b, end)) = score, the transcript the one the tie order
+ *     above gives for P against hap[b, end): exactly what spm_hip_scan + spm_hip_hits_align return on the materialised
+ *     haplotype.  (A context starts at the haplotype's first symbol or carries window - 1 >= |P| + k - 1 symbols of left
+ *     context, a reported hit ends on an owned symbol, and an alignment with d <= k edits spans at most |P| + d symbols:
+ *     its begin cannot lie left of the context.)
+ *   * Records of haplotypes that share a context share one transcript: the same cigar_off / cigar_len.  The pool holds
+ *     one slot of 2 score + 1 words per aligned segment hit, in the order (pattern, position in the context buffer).
+ *   * Two calls on the same hits give byte-identical host views (records and pool).
+ *   * Exact sets: begin = pos, end = pos + |P|, transcript |P|=. */
+typedef struct spm_jst_aln {      /* 40 bytes */
+    uint64_t begin;               /* haplotype coordinates; exact sets: pos */
+    uint64_t end;                 /* the hit's pos (Myers) / pos + |P| (exact) */
+    uint32_t haplotype;
+    uint32_t pattern;
+    int32_t score;
+    uint32_t cigar_off;           /* first word of the transcript in the ops pool */
+    uint32_t cigar_len;           /* 0 with SPM_ALIGN_BEGIN_ONLY */
+    uint32_t reserved;
+} spm_jst_aln;
+typedef struct spm_jst_alns spm_jst_alns;
+
+typedef struct spm_jst_align_stats { /* 80 bytes */
+    float ms_total;        /* device: stage A + stage B + fan-out (HIP events) */
+    float ms_begin;        /* stage A over the segment hits */
+    float ms_cigar;        /* stage B over the segment hits */
+    float ms_fanout;       /* the alignment fan-out */
+    float ms_host;         /* wall clock of the whole call, host side included */
+    float ms_worklist;     /* ... of which: reading the segment hits back and building the work list on the host */
+    uint64_t n_alns;         /* records = the search's hit count */
+    uint64_t n_segment_alns; /* alignments actually computed (segment hits that end on an owned symbol) */
+    uint64_t n_ops;          /* CIGAR words in the pool (sum of 2 score + 1 over the segment alignments) */
+    uint32_t begin_lane, begin_wave, cigar_lane, cigar_wave, cigar_wave_global; /* as in spm_align_stats */
+    uint32_t reserved[3];
+} spm_jst_align_stats;
+
+/* flags: SPM_ALIGN_BEGIN_ONLY */
+int spm_hip_jst_hits_align(spm_jst_hits *hits, uint32_t flags, spm_jst_alns **out);
+int spm_hip_jst_alns_view(spm_jst_alns *a, const spm_jst_aln **records, uint64_t *n, const uint32_t **ops, uint64_t *n_ops);
+int spm_hip_jst_alns_device(spm_jst_alns *a, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops);
+int spm_hip_jst_alns_stats(const spm_jst_alns *a, spm_jst_align_stats *out);
+void spm_hip_jst_alns_destroy(spm_jst_alns *a);
+
 /* Synthetic variants of config C5: one SNP per 1000 reference bases, one indel of length 1..50 per
  * 10 000, each carried by a random non-empty subset of n_haplotypes <= 64; the reference is the synthetic text of
  * `seed_text`.  Call with alleles == NULL to get the counts (*n_alleles, *alt_pool_len) first.  Host side. */

@@ -16,6 +16,7 @@ ALGO_SHIFTOR, ALGO_MYERS, ALGO_MYERS_PREFIX, ALGO_HORSPOOL = 0, 1, 2, 3
 ENGINE_AUTO, ENGINE_BRUTE, ENGINE_FILTER = 0, 1, 2
 SCAN_IGNORE_PACKED = 1
 SCAN_DEFER = 2
+SCAN_ALIGNABLE = 4  # spm_hip_jst_search only: the result keeps its segment hits for spm_hip_jst_hits_align
 MAX_NEEDLE = 2048
 
 
@@ -126,6 +127,31 @@ class AlignStats(C.Structure):
     ]
 
 
+class JstAln(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64), ("haplotype", C.c_uint32), ("pattern", C.c_uint32),
+                ("score", C.c_int32), ("cigar_off", C.c_uint32), ("cigar_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JstAlignStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_begin", C.c_float),
+        ("ms_cigar", C.c_float),
+        ("ms_fanout", C.c_float),
+        ("ms_host", C.c_float),
+        ("ms_worklist", C.c_float),
+        ("n_alns", C.c_uint64),
+        ("n_segment_alns", C.c_uint64),
+        ("n_ops", C.c_uint64),
+        ("begin_lane", C.c_uint32),
+        ("begin_wave", C.c_uint32),
+        ("cigar_lane", C.c_uint32),
+        ("cigar_wave", C.c_uint32),
+        ("cigar_wave_global", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
 ALIGN_BEGIN_ONLY = 1
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
 
@@ -212,6 +238,13 @@ def lib():
         "spm_hip_jst_hits_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_hits_copy_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "spm_hip_jst_hits_destroy": (None, [vp]),
+        "spm_hip_jst_hits_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstAln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
+                                            C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
+                                              C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_alns_stats": (C.c_int, [vp, C.POINTER(JstAlignStats)]),
+        "spm_hip_jst_alns_destroy": (None, [vp]),
         "spm_hip_comm_unique_id": (C.c_int, [vp]),
         "spm_hip_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
         "spm_hip_comm_destroy": (None, [vp]),
@@ -246,6 +279,8 @@ EXPORTS = [
     "spm_hip_jst_create", "spm_hip_jst_destroy", "spm_hip_jst_haplotype_length", "spm_hip_jst_extract",
     "spm_hip_jst_index", "spm_hip_jst_search", "spm_hip_jst_stats", "spm_hip_jst_hits_view", "spm_hip_jst_hits_device",
     "spm_hip_jst_hits_copy_device", "spm_hip_jst_hits_destroy", "spm_hip_jst_synth_variants",
+    "spm_hip_jst_hits_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
+    "spm_hip_jst_alns_destroy",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",
 ]

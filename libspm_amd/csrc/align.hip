@@ -95,6 +95,205 @@ std::vector<uint32_t> counting_order(const std::vector<uint32_t> &key, uint32_t 
 }
 } // namespace
 
+// The Myers path both entry points share (spm_hip_hits_align; spm_hip_jst_hits_align over a search's segment hits): the
+// work list, the kernel class of every hit, stage A and stage B.  Record i of W.d_recs belongs to W.hits[i]; records, pool
+// and the error counters come back to the host behind one synchronisation.
+int align_run(spm_ctx *ctx, const align_work &W, spm_align_stats &stats)
+{
+    const spm_patterns *ps = W.ps;
+    const uint64_t n = W.n;
+    const bool begin_only = W.begin_only;
+    const spm_hit *dh = W.hits;
+    if (n == 0)
+        return SPM_OK;
+    int rc = ensure_align_tables(ps);
+    if (rc != SPM_OK)
+        return rc;
+    // ---- the work list: stage-A class = words of the needle (1..4 lane per hit, 5: wave per hit) ----
+    const spm_text *text = W.text;
+    std::vector<spm_hip::aln_item> items(n);
+    std::vector<uint32_t> cls_a(n), cls_b(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        spm_hip::aln_item &it = items[i];
+        const uint64_t e = dh[i].pos - W.pos_offset;
+        const uint64_t lo = W.lo[i];
+        it.e = e;
+        it.lo = lo;
+        it.pattern = dh[i].pattern;
+        it.d = dh[i].score;
+        it.m = (uint32_t)ps->m[dh[i].pattern];
+        it.cigar_off = begin_only ? 0 : W.cig_off[i];
+        it.rec = (uint32_t)i;
+        it.pad = 0;
+        if (e > text->n || e < lo || it.d < 0 || (uint32_t)it.d > it.m) {
+            SPM_SET_ERR(ctx, "%s: hit %llu (end %llu, distance %d) does not fit its scan", W.who,
+                        (unsigned long long)i, (unsigned long long)e, it.d);
+            return SPM_E_INVALID;
+        }
+        const uint32_t nw = std::max(1u, (it.m + 63) / 64);
+        cls_a[i] = nw <= 4 ? nw - 1 : 4;
+    }
+    const std::vector<uint32_t> oa = counting_order(cls_a, 5);
+    std::vector<spm_hip::aln_item> items_a(n);
+    uint64_t cnt_a[5] = {0, 0, 0, 0, 0};
+    for (uint64_t s = 0; s < n; ++s) {
+        items_a[s] = items[oa[s]];
+        ++cnt_a[cls_a[oa[s]]];
+    }
+    // stage-B classes over items_a indices: one lane per hit with LDS slots of <= 32, 64, 128, 256 words; beyond that one
+    // wave per hit (class 4), its slot in LDS up to kWaveLdsWords, else in the context's scratch
+    std::vector<uint64_t> need(n);
+    for (uint64_t s = 0; s < n; ++s) {
+        need[s] = cigar_slot_words(items_a[s].m, items_a[s].d);
+        cls_b[s] = need[s] <= 32 ? 0 : need[s] <= 64 ? 1 : need[s] <= 128 ? 2 : need[s] <= kLdsSlotWords ? 3 : 4;
+        if (cls_b[s] == 4)
+            need[s] = wave_slot_words(items_a[s].m, items_a[s].d);
+    }
+    std::vector<uint32_t> ob = counting_order(cls_b, 5);
+    uint64_t cnt_b[5] = {0, 0, 0, 0, 0};
+    for (uint64_t s = 0; s < n; ++s)
+        ++cnt_b[cls_b[s]];
+    // the wave class by slot size (launches of like slots)
+    const uint64_t g0 = n - cnt_b[4];
+    std::stable_sort(ob.begin() + g0, ob.end(), [&](uint32_t x, uint32_t y) { return need[x] < need[y]; });
+    uint64_t wave_lds = 0;
+    while (g0 + wave_lds < n && need[ob[g0 + wave_lds]] <= kWaveLdsWords)
+        ++wave_lds;
+
+    dev_scratch tmp;
+    spm_hip::aln_item *d_items = nullptr;
+    uint32_t *d_ob = nullptr;
+    unsigned long long *d_err = nullptr;
+    SPM_HIP_CHECK(ctx, tmp.alloc(&d_items, n * sizeof(spm_hip::aln_item)));
+    SPM_HIP_CHECK(ctx, tmp.alloc(&d_ob, n * sizeof(uint32_t)));
+    SPM_HIP_CHECK(ctx, tmp.alloc(&d_err, 2 * sizeof(unsigned long long)));
+    if (W.n_ops)
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(W.d_ops, 0, W.n_ops * 4, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_items, items_a.data(), n * sizeof(spm_hip::aln_item), hipMemcpyHostToDevice, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_ob, ob.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipMemsetAsync(d_err, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    // a global-class batch may need the context's scratch: grown now, before the timed launches
+    if (!begin_only && g0 + wave_lds < n) {
+        rc = ensure_scratch(ctx, std::max<size_t>(kGlobalBatchBytes, need[ob[n - 1]] * 4));
+        if (rc != SPM_OK)
+            return rc;
+    }
+
+    spm_hip::align_params P{};
+    P.text = text->d;
+    P.rpeq = ps->d_al_rpeq;
+    P.rpeq_off = ps->d_al_rpeq_off;
+    P.ranks = ps->d_al_ranks;
+    P.offsets = ps->d_al_offsets;
+    P.sigma = ps->sigma;
+    P.pos_offset = W.pos_offset;
+    P.recs = W.d_recs;
+    P.ops = W.d_ops;
+    P.err = d_err;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct ev_guard
+    {
+        hipEvent_t *e;
+        ~ev_guard()
+        {
+            for (int i = 0; i < 3; ++i)
+                if (e[i])
+                    hipEventDestroy(e[i]);
+        }
+    } eg{ev};
+    for (int i = 0; i < 3; ++i)
+        SPM_HIP_CHECK(ctx, hipEventCreate(&ev[i]));
+    SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
+    // ---- stage A ----
+    uint64_t s0 = 0;
+    for (int c = 0; c < 5; ++c) {
+        const uint32_t cn = (uint32_t)cnt_a[c];
+        if (cn) {
+            const spm_hip::aln_item *it = d_items + s0;
+            if (c < 4) {
+                const dim3 g((cn + 255) / 256), b(256);
+                if (c == 0)
+                    hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<1>, g, b, 0, ctx->stream, P, it, cn);
+                else if (c == 1)
+                    hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<2>, g, b, 0, ctx->stream, P, it, cn);
+                else if (c == 2)
+                    hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<3>, g, b, 0, ctx->stream, P, it, cn);
+                else
+                    hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<4>, g, b, 0, ctx->stream, P, it, cn);
+            } else {
+                hipLaunchKernelGGL(spm_hip::align_begin_wave_kernel, dim3((cn + 3) / 4), dim3(256), 0, ctx->stream, P, it, cn);
+            }
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+        }
+        s0 += cnt_a[c];
+    }
+    SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
+    // ---- stage B ----
+    if (!begin_only) {
+        uint64_t b0 = 0;
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t cn = (uint32_t)cnt_b[c];
+            if (cn) {
+                const size_t lds = (size_t)kWave * 4 * (32u << c);
+                hipLaunchKernelGGL(spm_hip::align_cigar_kernel, dim3((cn + 63) / 64), dim3(64), lds, ctx->stream, P,
+                                   d_items, d_ob + b0, cn);
+                SPM_HIP_CHECK(ctx, hipGetLastError());
+            }
+            b0 += cnt_b[c];
+        }
+        // the wave class: LDS launches of slots up to the next power of two, then scratch batches within its size
+        for (uint64_t s = g0; s < g0 + wave_lds;) {
+            uint64_t cap_w = 1024;
+            while (cap_w < need[ob[s]])
+                cap_w <<= 1;
+            cap_w = std::min<uint64_t>(cap_w, kWaveLdsWords);
+            uint64_t z = s;
+            while (z < g0 + wave_lds && need[ob[z]] <= cap_w)
+                ++z;
+            const uint32_t cn = (uint32_t)(z - s);
+            hipLaunchKernelGGL(spm_hip::align_cigar_wave_kernel<true>, dim3(cn), dim3(64), cap_w * 4, ctx->stream, P, d_items,
+                               d_ob + s, cn, nullptr, (uint64_t)0);
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+            s = z;
+        }
+        const uint64_t budget_words = ctx->scratch_bytes / 4;
+        for (uint64_t s = g0 + wave_lds; s < n;) {
+            uint64_t z = s + 1;
+            while (z < n && (z + 1 - s) * need[ob[z]] <= budget_words)
+                ++z;
+            const uint32_t cn = (uint32_t)(z - s);
+            hipLaunchKernelGGL(spm_hip::align_cigar_wave_kernel<false>, dim3(cn), dim3(64), 0, ctx->stream, P, d_items,
+                               d_ob + s, cn, static_cast<uint32_t *>(ctx->d_scratch), need[ob[z - 1]]);
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+            s = z;
+        }
+    }
+    SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], ctx->stream));
+    unsigned long long err[2] = {0, 0};
+    if (W.h_recs)
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(W.h_recs, W.d_recs, n * sizeof(spm_aln), hipMemcpyDeviceToHost, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
+    if (W.n_ops && W.h_ops)
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(W.h_ops, W.d_ops, W.n_ops * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (err[0] || err[1]) {
+        SPM_SET_ERR(ctx, "%s: %llu begins not found, %llu transcripts failed their check (hits that do not "
+                         "belong to this text?)", W.who, err[0], err[1]);
+        return SPM_E_INVALID;
+    }
+    hipEventElapsedTime(&stats.ms_total, ev[0], ev[2]);
+    hipEventElapsedTime(&stats.ms_begin, ev[0], ev[1]);
+    hipEventElapsedTime(&stats.ms_cigar, ev[1], ev[2]);
+    stats.begin_lane = (uint32_t)(n - cnt_a[4]);
+    stats.begin_wave = (uint32_t)cnt_a[4];
+    if (!begin_only) {
+        stats.cigar_lane = (uint32_t)(n - cnt_b[4]);
+        stats.cigar_wave = (uint32_t)wave_lds;
+        stats.cigar_wave_global = (uint32_t)(cnt_b[4] - wave_lds);
+    }
+    return SPM_OK;
+}
+
 extern "C" int spm_hip_hits_align(spm_hits *h, uint32_t flags, spm_alns **out)
 {
     if (!h || !out || (flags & ~SPM_ALIGN_BEGIN_ONLY))
@@ -190,200 +389,38 @@ extern "C" int spm_hip_hits_align(spm_hits *h, uint32_t flags, spm_alns **out)
         }
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     } else if (n) {
-        rc = ensure_align_tables(ps);
+        std::vector<uint64_t> lo(n, h->al_lo);
+        if (!h->al_segs.empty()) { // the segment holding the hit's last symbol
+            const uint64_t *segs = h->al_segs.data();
+            const uint64_t n_segs = h->al_segs.size() - 1;
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint64_t e = dh[i].pos - h->al_pos_offset;
+                const uint64_t *u = std::upper_bound(segs, segs + n_segs + 1, e ? e - 1 : 0);
+                lo[i] = u == segs ? segs[0] : *(u - 1);
+            }
+        }
+        SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_aln)));
+        if (A->n_ops)
+            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
+        A->host_ops.resize(A->n_ops);
+        align_work W{};
+        W.ps = ps;
+        W.text = h->al_text;
+        W.pos_offset = h->al_pos_offset;
+        W.hits = dh.data();
+        W.n = n;
+        W.lo = lo.data();
+        W.cig_off = cig_off.data();
+        W.begin_only = begin_only;
+        W.d_recs = A->d_recs;
+        W.d_ops = A->d_ops;
+        W.n_ops = A->n_ops;
+        W.h_recs = drec.data();
+        W.h_ops = A->host_ops.data();
+        W.who = "spm_hip_hits_align";
+        rc = align_run(ctx, W, A->stats);
         if (rc != SPM_OK)
             return rc;
-        // ---- the work list: stage-A class = words of the needle (1..4 lane per hit, 5: wave per hit) ----
-        const spm_text *text = h->al_text;
-        const uint64_t *segs = h->al_segs.empty() ? nullptr : h->al_segs.data();
-        const uint64_t n_segs = h->al_segs.empty() ? 0 : h->al_segs.size() - 1;
-        std::vector<spm_hip::aln_item> items(n);
-        std::vector<uint32_t> cls_a(n), cls_b(n);
-        for (uint64_t i = 0; i < n; ++i) {
-            spm_hip::aln_item &it = items[i];
-            const uint64_t e = dh[i].pos - h->al_pos_offset;
-            uint64_t lo = h->al_lo;
-            if (segs) { // the segment holding the hit's last symbol
-                const uint64_t *u = std::upper_bound(segs, segs + n_segs + 1, e ? e - 1 : 0);
-                lo = u == segs ? segs[0] : *(u - 1);
-            }
-            it.e = e;
-            it.lo = lo;
-            it.pattern = dh[i].pattern;
-            it.d = dh[i].score;
-            it.m = (uint32_t)ps->m[dh[i].pattern];
-            it.cigar_off = begin_only ? 0 : cig_off[i];
-            it.rec = (uint32_t)i;
-            it.pad = 0;
-            if (e > text->n || e < lo || it.d < 0 || (uint32_t)it.d > it.m) {
-                SPM_SET_ERR(ctx, "spm_hip_hits_align: hit %llu (end %llu, distance %d) does not fit its scan",
-                            (unsigned long long)i, (unsigned long long)e, it.d);
-                return SPM_E_INVALID;
-            }
-            const uint32_t nw = std::max(1u, (it.m + 63) / 64);
-            cls_a[i] = nw <= 4 ? nw - 1 : 4;
-        }
-        const std::vector<uint32_t> oa = counting_order(cls_a, 5);
-        std::vector<spm_hip::aln_item> items_a(n);
-        uint64_t cnt_a[5] = {0, 0, 0, 0, 0};
-        for (uint64_t s = 0; s < n; ++s) {
-            items_a[s] = items[oa[s]];
-            ++cnt_a[cls_a[oa[s]]];
-        }
-        // stage-B classes over items_a indices: one lane per hit with LDS slots of <= 32, 64, 128, 256 words; beyond that one
-        // wave per hit (class 4), its slot in LDS up to kWaveLdsWords, else in the context's scratch
-        std::vector<uint64_t> need(n);
-        for (uint64_t s = 0; s < n; ++s) {
-            need[s] = cigar_slot_words(items_a[s].m, items_a[s].d);
-            cls_b[s] = need[s] <= 32 ? 0 : need[s] <= 64 ? 1 : need[s] <= 128 ? 2 : need[s] <= kLdsSlotWords ? 3 : 4;
-            if (cls_b[s] == 4)
-                need[s] = wave_slot_words(items_a[s].m, items_a[s].d);
-        }
-        std::vector<uint32_t> ob = counting_order(cls_b, 5);
-        uint64_t cnt_b[5] = {0, 0, 0, 0, 0};
-        for (uint64_t s = 0; s < n; ++s)
-            ++cnt_b[cls_b[s]];
-        // the wave class by slot size (launches of like slots)
-        const uint64_t g0 = n - cnt_b[4];
-        std::stable_sort(ob.begin() + g0, ob.end(), [&](uint32_t x, uint32_t y) { return need[x] < need[y]; });
-        uint64_t wave_lds = 0;
-        while (g0 + wave_lds < n && need[ob[g0 + wave_lds]] <= kWaveLdsWords)
-            ++wave_lds;
-
-        dev_scratch tmp;
-        spm_hip::aln_item *d_items = nullptr;
-        uint32_t *d_ob = nullptr;
-        unsigned long long *d_err = nullptr;
-        SPM_HIP_CHECK(ctx, tmp.alloc(&d_items, n * sizeof(spm_hip::aln_item)));
-        SPM_HIP_CHECK(ctx, tmp.alloc(&d_ob, n * sizeof(uint32_t)));
-        SPM_HIP_CHECK(ctx, tmp.alloc(&d_err, 2 * sizeof(unsigned long long)));
-        SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_aln)));
-        if (A->n_ops) {
-            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
-            SPM_HIP_CHECK(ctx, hipMemsetAsync(A->d_ops, 0, A->n_ops * 4, ctx->stream));
-        }
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_items, items_a.data(), n * sizeof(spm_hip::aln_item), hipMemcpyHostToDevice, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_ob, ob.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_err, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        // a global-class batch may need the context's scratch: grown now, before the timed launches
-        if (!begin_only && g0 + wave_lds < n) {
-            rc = ensure_scratch(ctx, std::max<size_t>(kGlobalBatchBytes, need[ob[n - 1]] * 4));
-            if (rc != SPM_OK)
-                return rc;
-        }
-
-        spm_hip::align_params P{};
-        P.text = text->d;
-        P.rpeq = ps->d_al_rpeq;
-        P.rpeq_off = ps->d_al_rpeq_off;
-        P.ranks = ps->d_al_ranks;
-        P.offsets = ps->d_al_offsets;
-        P.sigma = ps->sigma;
-        P.pos_offset = h->al_pos_offset;
-        P.recs = A->d_recs;
-        P.ops = A->d_ops;
-        P.err = d_err;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        struct ev_guard
-        {
-            hipEvent_t *e;
-            ~ev_guard()
-            {
-                for (int i = 0; i < 3; ++i)
-                    if (e[i])
-                        hipEventDestroy(e[i]);
-            }
-        } eg{ev};
-        for (int i = 0; i < 3; ++i)
-            SPM_HIP_CHECK(ctx, hipEventCreate(&ev[i]));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-        // ---- stage A ----
-        uint64_t s0 = 0;
-        for (int c = 0; c < 5; ++c) {
-            const uint32_t cn = (uint32_t)cnt_a[c];
-            if (cn) {
-                const spm_hip::aln_item *it = d_items + s0;
-                if (c < 4) {
-                    const dim3 g((cn + 255) / 256), b(256);
-                    if (c == 0)
-                        hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<1>, g, b, 0, ctx->stream, P, it, cn);
-                    else if (c == 1)
-                        hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<2>, g, b, 0, ctx->stream, P, it, cn);
-                    else if (c == 2)
-                        hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<3>, g, b, 0, ctx->stream, P, it, cn);
-                    else
-                        hipLaunchKernelGGL(spm_hip::align_begin_lane_kernel<4>, g, b, 0, ctx->stream, P, it, cn);
-                } else {
-                    hipLaunchKernelGGL(spm_hip::align_begin_wave_kernel, dim3((cn + 3) / 4), dim3(256), 0, ctx->stream, P, it, cn);
-                }
-                SPM_HIP_CHECK(ctx, hipGetLastError());
-            }
-            s0 += cnt_a[c];
-        }
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-        // ---- stage B ----
-        if (!begin_only) {
-            uint64_t b0 = 0;
-            for (int c = 0; c < 4; ++c) {
-                const uint32_t cn = (uint32_t)cnt_b[c];
-                if (cn) {
-                    const size_t lds = (size_t)kWave * 4 * (32u << c);
-                    hipLaunchKernelGGL(spm_hip::align_cigar_kernel, dim3((cn + 63) / 64), dim3(64), lds, ctx->stream, P,
-                                       d_items, d_ob + b0, cn);
-                    SPM_HIP_CHECK(ctx, hipGetLastError());
-                }
-                b0 += cnt_b[c];
-            }
-            // the wave class: LDS launches of slots up to the next power of two, then scratch batches within its size
-            for (uint64_t s = g0; s < g0 + wave_lds;) {
-                uint64_t cap_w = 1024;
-                while (cap_w < need[ob[s]])
-                    cap_w <<= 1;
-                cap_w = std::min<uint64_t>(cap_w, kWaveLdsWords);
-                uint64_t z = s;
-                while (z < g0 + wave_lds && need[ob[z]] <= cap_w)
-                    ++z;
-                const uint32_t cn = (uint32_t)(z - s);
-                hipLaunchKernelGGL(spm_hip::align_cigar_wave_kernel<true>, dim3(cn), dim3(64), cap_w * 4, ctx->stream, P, d_items,
-                                   d_ob + s, cn, nullptr, (uint64_t)0);
-                SPM_HIP_CHECK(ctx, hipGetLastError());
-                s = z;
-            }
-            const uint64_t budget_words = ctx->scratch_bytes / 4;
-            for (uint64_t s = g0 + wave_lds; s < n;) {
-                uint64_t z = s + 1;
-                while (z < n && (z + 1 - s) * need[ob[z]] <= budget_words)
-                    ++z;
-                const uint32_t cn = (uint32_t)(z - s);
-                hipLaunchKernelGGL(spm_hip::align_cigar_wave_kernel<false>, dim3(cn), dim3(64), 0, ctx->stream, P, d_items,
-                                   d_ob + s, cn, static_cast<uint32_t *>(ctx->d_scratch), need[ob[z - 1]]);
-                SPM_HIP_CHECK(ctx, hipGetLastError());
-                s = z;
-            }
-        }
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], ctx->stream));
-        unsigned long long err[2] = {0, 0};
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(drec.data(), A->d_recs, n * sizeof(spm_aln), hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
-        A->host_ops.resize(A->n_ops);
-        if (A->n_ops)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host_ops.data(), A->d_ops, A->n_ops * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (err[0] || err[1]) {
-            SPM_SET_ERR(ctx, "spm_hip_hits_align: %llu begins not found, %llu transcripts failed their check (hits that do not "
-                             "belong to this text?)", err[0], err[1]);
-            return SPM_E_INVALID;
-        }
-        hipEventElapsedTime(&A->stats.ms_total, ev[0], ev[2]);
-        hipEventElapsedTime(&A->stats.ms_begin, ev[0], ev[1]);
-        hipEventElapsedTime(&A->stats.ms_cigar, ev[1], ev[2]);
-        A->stats.begin_lane = (uint32_t)(n - cnt_a[4]);
-        A->stats.begin_wave = (uint32_t)cnt_a[4];
-        if (!begin_only) {
-            A->stats.cigar_lane = (uint32_t)(n - cnt_b[4]);
-            A->stats.cigar_wave = (uint32_t)wave_lds;
-            A->stats.cigar_wave_global = (uint32_t)(cnt_b[4] - wave_lds);
-        }
     }
     A->host.resize(n);
     for (uint64_t s = 0; s < n; ++s)

@@ -152,6 +152,27 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
               uint64_t n_segments, spm_hits **out, const uint64_t *d_seg_offsets = nullptr,
               const uint32_t *d_seg_owned = nullptr, const std::function<int(spm_hits *)> *after_launch = nullptr);
 
+// ---- alignment of Myers hits (align.hip): the work list, the kernel classes, stage A and stage B.  Shared by
+// spm_hip_hits_align (hits of a scan) and spm_hip_jst_hits_align (segment hits of a journaled-sequence search). ----
+struct align_work
+{
+    const spm_patterns *ps = nullptr;
+    const spm_text *text = nullptr;
+    uint64_t pos_offset = 0;          // hits[i].pos - pos_offset = the hit's end in text coordinates
+    const spm_hit *hits = nullptr;    // host copies; record i of d_recs belongs to hits[i]
+    uint64_t n = 0;
+    const uint64_t *lo = nullptr;     // per hit: the first text symbol its alignment may use
+    const uint32_t *cig_off = nullptr; // per hit: first word of its transcript in the pool
+    bool begin_only = false;
+    spm_aln *d_recs = nullptr;        // [n], allocated by the caller
+    uint32_t *d_ops = nullptr;        // [n_ops]
+    uint64_t n_ops = 0;               // 0 with begin_only
+    spm_aln *h_recs = nullptr;        // optional: where the records are copied back to
+    uint32_t *h_ops = nullptr;        // optional: ... and the pool
+    const char *who = "";             // the C-ABI call, for messages
+};
+int align_run(spm_ctx *ctx, const align_work &W, spm_align_stats &stats);
+
 // Every translation unit with kernels is a code object of its own, loaded by the HIP runtime at the first launch out of
 // it (~1-3 ms each).  spm_hip_init loads them all, so that the first scan of a process does not pay for it.
 void spm_warm_text_kernels();

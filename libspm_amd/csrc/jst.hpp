@@ -24,6 +24,7 @@
 
 // the ctypes binding (libspm_amd/capi.py) mirrors these layouts
 static_assert(sizeof(spm_jst_allele) == 24 && sizeof(spm_jst_hit) == 24 && sizeof(spm_jst_stats) == 104, "C ABI layout");
+static_assert(sizeof(spm_jst_aln) == 40 && sizeof(spm_jst_align_stats) == 80, "C ABI layout");
 
 namespace spm_hip
 {
@@ -579,6 +580,118 @@ __global__ void jst_fanout_kernel(jst_dev J, jst_fan_params F)
     }
 }
 
+struct jst_alnfan_params
+{
+    const spm_aln *segs; // one alignment per segment hit, context-buffer coordinates (stage A / stage B of align.hpp)
+    uint64_t n_segs;
+    const uint64_t *ctx_off;
+    uint64_t n_ctx;
+    const uint32_t *ctx_block, *ctx_owned;
+    const uint64_t *ctx_base;
+    const uint16_t *local_id;
+    spm_jst_aln *out;
+    unsigned long long *out_count;
+    uint64_t out_cap;
+};
+
+// The alignment fan-out, sibling of jst_fanout_kernel: one thread per segment alignment.  It is dropped if its last symbol
+// lies in the left context; else every haplotype of the context's group gets a record with its own coordinates and the
+// SHARED transcript (cigar_off / cigar_len of the segment alignment).  Slots are drawn with one atomic per wave.
+__global__ __launch_bounds__(256) void jst_aln_fanout_kernel(jst_dev J, jst_alnfan_params F)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t rounds = (F.n_segs + stride - 1) / stride; // wave-uniform trip count: the slot reservation is wave-collective
+    for (uint64_t rd = 0; rd < rounds; ++rd) {
+        const uint64_t t = rd * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        // pass 1: which context, and how many haplotypes share it
+        bool live = t < F.n_segs;
+        spm_aln al{};
+        uint64_t c = 0, local_end = 0, jr = 0;
+        uint32_t id = 0, members = 0, h_lo = 0, h_hi = 0;
+        if (live) {
+            al = F.segs[t];
+            live = al.end > 0 && al.begin <= al.end;
+        }
+        if (live) {
+            const uint64_t probe = al.end - 1; // the alignment's last symbol: a symbol of its own context
+            uint64_t lo = 0, hi = F.n_ctx;     // ctx_off[lo] <= probe < ctx_off[hi]
+            while (hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (F.ctx_off[mid] <= probe)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            c = lo;
+            live = probe >= F.ctx_off[c] && probe - F.ctx_off[c] >= F.ctx_owned[c] && al.begin >= F.ctx_off[c];
+            local_end = al.end - F.ctx_off[c];
+        }
+        if (live) {
+            const uint64_t cb = F.ctx_block[c]; // (block, haplotype group) cell of the context
+            jr = cb / J.n_groups;
+            h_lo = (uint32_t)(cb % J.n_groups) * kJstGroup;
+            h_hi = min(J.n_hap, h_lo + kJstGroup);
+            id = (uint32_t)(c - F.ctx_base[cb]);
+            for (uint32_t h = h_lo; h < h_hi; h += 8) {
+                uint16_t v[8];
+                jst_load_ids8(F.local_id + jr * J.n_hap + h, h_hi - h, v);
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    members += (v[i] != kJstNone && (uint32_t)(v[i] & 0x7FFFu) == id) ? 1u : 0u;
+            }
+        }
+        // one atomic per wave: exclusive prefix of the member counts over the lanes
+        uint32_t incl = members;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_up(incl, o);
+            if ((int)lane >= o)
+                incl += up;
+        }
+        const uint32_t total = __shfl(incl, 63);
+        unsigned long long base = 0;
+        if (lane == 0 && total)
+            base = atomicAdd(F.out_count, (unsigned long long)total);
+        base = __shfl(base, 0);
+        if (!live || members == 0)
+            continue;
+        // pass 2: one record per haplotype of the group, eight haplotypes at a time (their start coordinates loaded together)
+        unsigned long long slot = base + (incl - members);
+        const uint64_t j = J.jb + jr;
+        const uint64_t span = al.end - al.begin;
+        for (uint32_t h = h_lo; h < h_hi; h += 8) {
+            uint16_t v[8];
+            jst_load_ids8(F.local_id + jr * J.n_hap + h, h_hi - h, v);
+            bool mem[8];
+            uint64_t a[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                mem[i] = v[i] != kJstNone && (uint32_t)(v[i] & 0x7FFFu) == id;
+                a[i] = mem[i] ? J.hap_start[j * J.n_hap + h + i] : 0;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (!mem[i])
+                    continue;
+                const uint64_t ctx_lo = a[i] - std::min<uint64_t>(J.window ? J.window - 1 : 0, a[i]);
+                if (slot < F.out_cap) {
+                    spm_jst_aln o;
+                    o.end = ctx_lo + local_end;
+                    o.begin = o.end - span;
+                    o.haplotype = h + i;
+                    o.pattern = al.pattern;
+                    o.score = al.score;
+                    o.cigar_off = al.cigar_off;
+                    o.cigar_len = al.cigar_len;
+                    o.reserved = 0;
+                    F.out[slot] = o;
+                }
+                ++slot;
+            }
+        }
+    }
+}
+
 } // namespace spm_hip
 
 // ----------------------------------------------------------------------------------------------------
@@ -612,6 +725,11 @@ struct spm_jst
     unsigned long long *d_fan_count = nullptr;
     uint64_t seg_hit_hint = 0; // most segment hits a search has seen (sizes the grid of the fan-out launched behind the scan)
     hipEvent_t fan_ev[2] = {nullptr, nullptr};
+    // alignment of hits (spm_hip_jst_hits_align): every spm_hip_jst_index starts a new generation -- results of earlier
+    // searches point into buffers it freed -- and the context tables are fetched to the host once per generation
+    uint64_t generation = 0, h_generation = ~0ull;
+    std::vector<uint64_t> h_ctx_off;   // [n_ctx + 1]
+    std::vector<uint32_t> h_ctx_owned; // [n_ctx]
 
     spm_hip::jst_dev dev() const
     {
@@ -655,6 +773,7 @@ struct spm_jst
             spm_hip_text_destroy(ctx_text);
         ctx_text = nullptr;
         indexed = false;
+        ++generation;
     }
 };
 
@@ -666,6 +785,12 @@ struct spm_jst_hits
     uint64_t n = 0;
     bool sorted = false;
     std::vector<spm_jst_hit> host;
+    // searches with SPM_SCAN_ALIGNABLE: what spm_hip_jst_hits_align needs
+    bool alignable = false;
+    spm_jst *jst = nullptr;
+    const spm_patterns *patterns = nullptr;
+    uint64_t generation = 0;
+    spm_hits *seg = nullptr; // the search's segment hits, owned (nullptr: the search had nothing to scan)
 };
 
 extern "C" int spm_hip_jst_create(spm_ctx *ctx, const spm_text *reference, const spm_jst_allele *alleles,
@@ -986,6 +1111,8 @@ extern "C" void spm_hip_jst_hits_destroy(spm_jst_hits *h)
 {
     if (!h)
         return;
+    if (h->seg)
+        spm_hip_hits_destroy(h->seg);
     if (h->d) {
         if (h->ctx && h->ctx->jst_pool.size() < 4)
             h->ctx->jst_pool.push_back({h->d, h->cap});
@@ -1028,6 +1155,11 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
         o = *opts_in;
     o.left_context = 0;
     o.pos_offset = 0;
+    R->alignable = (o.flags & SPM_SCAN_ALIGNABLE) != 0; // ours alone: the scan never sees the bit
+    o.flags &= ~SPM_SCAN_ALIGNABLE;
+    R->jst = J;
+    R->patterns = patterns;
+    R->generation = J->generation;
     const uint64_t out_cap = o.max_hits ? o.max_hits : (1ull << 22);
     if (o.max_hits == 0)
         o.max_hits = 1ull << 22;
@@ -1137,6 +1269,8 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
         fprintf(stderr, "[spm_hip] jst_search: %llu segment hits -> %llu records; scan %.3f ms (main %.3f, verification %.3f), "
                         "fan-out %.3f ms%s\n", (unsigned long long)n_seg_hits, n_out, J->stats.ms_scan, J->stats.ms_main,
                 J->stats.ms_verify, J->stats.ms_fanout, J->stats.fell_back ? "; the seed filter fell back" : "");
+    if (R->alignable)
+        R->seg = S.release(); // kept for spm_hip_jst_hits_align; otherwise back to the context's pool right here
     *out = R.release();
     return SPM_OK;
 }
@@ -1186,6 +1320,286 @@ extern "C" int spm_hip_jst_hits_copy_device(spm_jst_hits *h, void *device_dst, u
     if (c)
         SPM_HIP_CHECK(h->ctx, hipMemcpyAsync(device_dst, h->d, c * sizeof(spm_jst_hit), hipMemcpyDeviceToDevice,
                                              h->ctx->stream));
+    return SPM_OK;
+}
+
+// ---- begins and alignments of the hits of a search -------------------------------------------------------------------
+struct spm_jst_alns
+{
+    spm_ctx *ctx = nullptr;
+    spm_jst_aln *d_recs = nullptr; // arrival order of the fan-out
+    uint32_t *d_ops = nullptr;
+    uint64_t n = 0, n_ops = 0;
+    std::vector<spm_jst_aln> host; // (haplotype, pos, pattern): the order of spm_hip_jst_hits_view
+    std::vector<uint32_t> host_ops;
+    spm_jst_align_stats stats{};
+};
+
+extern "C" void spm_hip_jst_alns_destroy(spm_jst_alns *a)
+{
+    if (!a)
+        return;
+    if (a->ctx && (a->d_recs || a->d_ops))
+        hipStreamSynchronize(a->ctx->stream);
+    hipFree(a->d_recs);
+    hipFree(a->d_ops);
+    delete a;
+}
+
+extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_alns **out)
+{
+    using namespace spm_hip;
+    if (!h || !out || (flags & ~SPM_ALIGN_BEGIN_ONLY))
+        return SPM_E_INVALID;
+    spm_ctx *ctx = h->ctx;
+    const auto t_call = clk::now();
+    if (!h->alignable) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: these hits do not keep their segment hits; search with "
+                         "spm_scan_opts.flags & SPM_SCAN_ALIGNABLE");
+        return SPM_E_INVALID;
+    }
+    spm_jst *J = h->jst;
+    const spm_patterns *ps = h->patterns;
+    if (!J->indexed || J->generation != h->generation) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: the tree has been indexed again since this search (its context buffer is "
+                         "gone); search again");
+        return SPM_E_INVALID;
+    }
+    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<spm_jst_alns, void (*)(spm_jst_alns *)> A(new spm_jst_alns, spm_hip_jst_alns_destroy);
+    A->ctx = ctx;
+    A->n = h->n;
+    const bool begin_only = (flags & SPM_ALIGN_BEGIN_ONLY) != 0;
+    const bool myers = ps->is_myers();
+    const uint64_t n = h->n;
+    hipStream_t st = ctx->stream;
+
+    // ---- the segment hits that end on an owned symbol, in the order (pattern, position in the context buffer) ----
+    struct kept_hit
+    {
+        spm_hit hit;
+        uint64_t lo;
+    };
+    std::vector<kept_hit> kept;
+    if (n && h->seg) {
+        const void *d_seg = nullptr;
+        uint64_t n_seg = 0;
+        int rc = spm_hip_hits_device(h->seg, &d_seg, &n_seg);
+        if (rc != SPM_OK)
+            return rc;
+        std::vector<spm_hit> sh(n_seg);
+        if (J->h_generation != J->generation) { // the context tables: once per index generation
+            J->h_ctx_off.resize(J->n_ctx + 1);
+            J->h_ctx_owned.resize(J->n_ctx);
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(J->h_ctx_off.data(), J->d_ctx_off, (J->n_ctx + 1) * 8, hipMemcpyDeviceToHost, st));
+            if (J->n_ctx)
+                SPM_HIP_CHECK(ctx, hipMemcpyAsync(J->h_ctx_owned.data(), J->d_ctx_owned, J->n_ctx * 4, hipMemcpyDeviceToHost, st));
+        }
+        if (n_seg)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(sh.data(), d_seg, n_seg * sizeof(spm_hit), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        J->h_generation = J->generation;
+        const std::vector<uint64_t> &off = J->h_ctx_off;
+        kept.reserve(n_seg);
+        for (uint64_t i = 0; i < n_seg; ++i) {
+            const spm_hit &x = sh[i];
+            if (x.pattern >= ps->n) {
+                SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: segment hit of pattern %u outside the set", x.pattern);
+                return SPM_E_INVALID;
+            }
+            const uint64_t last = myers ? x.pos - 1 : x.pos + (uint64_t)ps->m[x.pattern] - 1; // (pos = 0 wraps: rejected below)
+            if (last >= J->ctx_bytes || J->n_ctx == 0) {
+                SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: segment hit %llu lies outside the context buffer", (unsigned long long)i);
+                return SPM_E_INVALID;
+            }
+            const uint64_t c = (uint64_t)(std::upper_bound(off.begin(), off.begin() + (long)J->n_ctx, last) - off.begin()) - 1;
+            if (last - off[c] < J->h_ctx_owned[c])
+                continue; // ends in the left context: the previous block's context reports it
+            kept.push_back({x, off[c]});
+        }
+        std::sort(kept.begin(), kept.end(), [](const kept_hit &a, const kept_hit &b) {
+            if (a.hit.pattern != b.hit.pattern)
+                return a.hit.pattern < b.hit.pattern;
+            if (a.hit.pos != b.hit.pos)
+                return a.hit.pos < b.hit.pos;
+            return a.hit.score < b.hit.score;
+        });
+    }
+    const uint64_t nk = kept.size();
+    std::vector<spm_hit> kh(nk);
+    std::vector<uint64_t> lo(nk);
+    std::vector<uint32_t> cig_off(nk, 0);
+    uint64_t total_ops = 0;
+    for (uint64_t i = 0; i < nk; ++i) {
+        kh[i] = kept[i].hit;
+        lo[i] = kept[i].lo;
+        cig_off[i] = (uint32_t)total_ops;
+        total_ops += myers ? 2 * (uint64_t)std::max(0, kh[i].score) + 1 : 1;
+    }
+    if (total_ops > 0xFFFFFFFFull || nk > 0xFFFFFFFFull) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: the CIGAR pool would exceed 2^32 words");
+        return SPM_E_UNSUPPORTED;
+    }
+    A->n_ops = begin_only ? 0 : total_ops;
+    A->host_ops.resize(A->n_ops);
+    A->stats.ms_worklist = ms_since(t_call);
+
+    if (nk) {
+        dev_scratch tmp;
+        spm_aln *d_seg_alns = nullptr;
+        unsigned long long *d_count = nullptr;
+        SPM_HIP_CHECK(ctx, tmp.alloc(&d_seg_alns, nk * sizeof(spm_aln)));
+        SPM_HIP_CHECK(ctx, tmp.alloc(&d_count, 8));
+        SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_jst_aln)));
+        if (A->n_ops)
+            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
+        if (myers) {
+            // stage A / stage B over the context buffer: lo = the start of the hit's context, positions as they are
+            align_work W{};
+            W.ps = ps;
+            W.text = J->ctx_text;
+            W.pos_offset = 0;
+            W.hits = kh.data();
+            W.n = nk;
+            W.lo = lo.data();
+            W.cig_off = cig_off.data();
+            W.begin_only = begin_only;
+            W.d_recs = d_seg_alns;
+            W.d_ops = A->d_ops;
+            W.n_ops = A->n_ops;
+            W.h_ops = A->host_ops.data();
+            W.who = "spm_hip_jst_hits_align";
+            spm_align_stats as{};
+            const int rc = align_run(ctx, W, as);
+            if (rc != SPM_OK)
+                return rc;
+            A->stats.ms_begin = as.ms_begin;
+            A->stats.ms_cigar = as.ms_cigar;
+            A->stats.begin_lane = as.begin_lane;
+            A->stats.begin_wave = as.begin_wave;
+            A->stats.cigar_lane = as.cigar_lane;
+            A->stats.cigar_wave = as.cigar_wave;
+            A->stats.cigar_wave_global = as.cigar_wave_global;
+        } else {
+            // exact sets: nothing to compute
+            std::vector<spm_aln> sa(nk);
+            for (uint64_t i = 0; i < nk; ++i) {
+                const uint32_t m = (uint32_t)ps->m[kh[i].pattern];
+                sa[i] = spm_aln{kh[i].pos, kh[i].pos + m, kh[i].pattern, kh[i].score, begin_only ? 0u : cig_off[i],
+                                begin_only ? 0u : 1u};
+                if (!begin_only)
+                    A->host_ops[cig_off[i]] = (m << 4) | SPM_CIGAR_EQ;
+            }
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_seg_alns, sa.data(), nk * sizeof(spm_aln), hipMemcpyHostToDevice, st));
+            if (A->n_ops)
+                SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->d_ops, A->host_ops.data(), A->n_ops * 4, hipMemcpyHostToDevice, st));
+            SPM_HIP_CHECK(ctx, hipStreamSynchronize(st)); // (sa is read by the copy)
+        }
+        // ---- the fan-out: one record per (haplotype, hit), the transcript shared ----
+        struct event_pair
+        {
+            hipEvent_t a = nullptr, b = nullptr;
+            ~event_pair()
+            {
+                if (a)
+                    hipEventDestroy(a);
+                if (b)
+                    hipEventDestroy(b);
+            }
+        } ev;
+        SPM_HIP_CHECK(ctx, hipEventCreate(&ev.a));
+        SPM_HIP_CHECK(ctx, hipEventCreate(&ev.b));
+        jst_alnfan_params F{};
+        F.segs = d_seg_alns;
+        F.n_segs = nk;
+        F.ctx_off = J->d_ctx_off;
+        F.n_ctx = J->n_ctx;
+        F.ctx_block = J->d_ctx_block;
+        F.ctx_owned = J->d_ctx_owned;
+        F.ctx_base = J->d_ctx_base;
+        F.local_id = J->d_local_id;
+        F.out = A->d_recs;
+        F.out_count = d_count;
+        F.out_cap = n;
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_count, 0, 8, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.a, st));
+        hipLaunchKernelGGL(jst_aln_fanout_kernel, dim3((unsigned)std::min<uint64_t>((nk + 255) / 256, (uint64_t)ctx->n_cu * 64)),
+                           dim3(256), 0, st, J->dev(), F);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.b, st));
+        unsigned long long n_out = 0;
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(&n_out, d_count, 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        hipEventElapsedTime(&A->stats.ms_fanout, ev.a, ev.b);
+        if (n_out != n) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: the fan-out wrote %llu alignment records for %llu hits", n_out,
+                        (unsigned long long)n);
+            return SPM_E_INVALID;
+        }
+        A->host.resize(n);
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        // the order of spm_hip_jst_hits_view: (haplotype, pos, pattern, score), pos = end (Myers) / begin (exact)
+        std::sort(A->host.begin(), A->host.end(), [myers](const spm_jst_aln &a, const spm_jst_aln &b) {
+            if (a.haplotype != b.haplotype)
+                return a.haplotype < b.haplotype;
+            const uint64_t pa = myers ? a.end : a.begin, pb = myers ? b.end : b.begin;
+            if (pa != pb)
+                return pa < pb;
+            if (a.pattern != b.pattern)
+                return a.pattern < b.pattern;
+            return a.score < b.score;
+        });
+    } else if (n) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: %llu hits but no segment hit to align", (unsigned long long)n);
+        return SPM_E_INVALID;
+    }
+    A->stats.ms_total = A->stats.ms_begin + A->stats.ms_cigar + A->stats.ms_fanout;
+    A->stats.n_alns = n;
+    A->stats.n_segment_alns = nk;
+    A->stats.n_ops = A->n_ops;
+    A->stats.ms_host = ms_since(t_call);
+    if (spm_trace_on())
+        fprintf(stderr, "[spm_hip] jst align: %llu segment alignments -> %llu records%s: begins %.3f ms, transcripts %.3f, "
+                        "fan-out %.3f; %.3f ms in all (work list %.3f)\n", (unsigned long long)nk, (unsigned long long)n,
+                begin_only ? " (begins only)" : "", A->stats.ms_begin, A->stats.ms_cigar, A->stats.ms_fanout,
+                A->stats.ms_host, A->stats.ms_worklist);
+    *out = A.release();
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_alns_view(spm_jst_alns *a, const spm_jst_aln **records, uint64_t *n, const uint32_t **ops,
+                                     uint64_t *n_ops)
+{
+    if (!a || !records || !n)
+        return SPM_E_INVALID;
+    *records = a->host.data();
+    *n = a->n;
+    if (ops)
+        *ops = a->host_ops.data();
+    if (n_ops)
+        *n_ops = a->n_ops;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_alns_device(spm_jst_alns *a, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops)
+{
+    if (!a || !records || !n)
+        return SPM_E_INVALID;
+    *records = a->d_recs;
+    *n = a->n;
+    if (ops)
+        *ops = a->d_ops;
+    if (n_ops)
+        *n_ops = a->n_ops;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_alns_stats(const spm_jst_alns *a, spm_jst_align_stats *out)
+{
+    if (!a || !out)
+        return SPM_E_INVALID;
+    *out = a->stats;
     return SPM_OK;
 }
 
@@ -1255,4 +1669,5 @@ void spm_warm_jst_kernels()
 {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, (const void *)spm_hip::jst_fanout_kernel);
+    (void)hipFuncGetAttributes(&a, (const void *)spm_hip::jst_aln_fanout_kernel);
 }

@@ -366,6 +366,8 @@ def synth_repeat_text(seed: int, repeat_ppm: int, begin: int, n: int) -> np.ndar
 ALLELE_DTYPE = np.dtype([("pos", "<u8"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("alt_off", "<u8")])
 JST_HIT_DTYPE = np.dtype([("pos", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"), ("score", "<i4"),
                           ("reserved", "<u4")])
+JST_ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"), ("score", "<i4"),
+                          ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("reserved", "<u4")])
 
 
 def synth_variants(seed_text: int, seed_var: int, ref_begin: int, n_ref: int, n_haplotypes: int):
@@ -423,12 +425,15 @@ class Jst:
         _check(capi.lib().spm_hip_jst_stats(self._h, C.byref(st)), self.ctx._h)
         return st
 
-    def search_device(self, pats: PatternSet, *, engine: int = capi.ENGINE_AUTO, max_hits: int = 0) -> "JstHits":
-        """One search over all haplotypes; the records stay in HBM (arrival order) until view()/copy_to()."""
-        opts = capi.ScanOpts(engine=engine, left_context=0, pos_offset=0, max_hits=max_hits, flags=0, reserved=0)
+    def search_device(self, pats: PatternSet, *, engine: int = capi.ENGINE_AUTO, max_hits: int = 0,
+                      alignable: bool = False) -> "JstHits":
+        """One search over all haplotypes; the records stay in HBM (arrival order) until view()/copy_to().
+        alignable: the result keeps the search's segment hits, so that JstHits.align() can align them."""
+        opts = capi.ScanOpts(engine=engine, left_context=0, pos_offset=0, max_hits=max_hits,
+                             flags=capi.SCAN_ALIGNABLE if alignable else 0, reserved=0)
         hh = C.c_void_p()
         _check(capi.lib().spm_hip_jst_search(self._h, pats._h, C.byref(opts), C.byref(hh)), self.ctx._h)
-        return JstHits(self.ctx, hh)
+        return JstHits(self.ctx, hh, self, pats)
 
     def search(self, pats: PatternSet, *, engine: int = capi.ENGINE_AUTO, max_hits: int = 0) -> np.ndarray:
         """All hits over all haplotypes, sorted by (haplotype, pos, pattern): JST_HIT_DTYPE records."""
@@ -452,8 +457,9 @@ class Jst:
 
 
 class JstHits:
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    def __init__(self, ctx, h, jst=None, pats=None):
+        # the search's tree and needle set: align() reads both, so they live at least as long as the hits
+        self.ctx, self._h, self._jst, self._pats = ctx, h, jst, pats
 
     def __len__(self):
         p, n = C.c_void_p(), C.c_uint64(0)
@@ -474,11 +480,87 @@ class JstHits:
         _check(capi.lib().spm_hip_jst_hits_copy_device(self._h, device_ptr, cap, C.byref(n)), self.ctx._h)
         return int(n.value)
 
+    def align(self, begin_only: bool = False) -> "JstAlignments":
+        """Begin + CIGAR transcript of every record (spm_hip_jst_hits_align), one alignment per segment hit shared by the
+        haplotypes of its context; record i belongs to view() record i.  Needs search_device(..., alignable=True)."""
+        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
+            raise capi.SpmError("JstHits.align: the tree or the needle set of this search has been closed")
+        a = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_hits_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
+               self.ctx._h)
+        return JstAlignments(self.ctx, a)
+
     def close(self):
         if self._h:
             if self.ctx._h:
                 capi.lib().spm_hip_jst_hits_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JstAlignments:
+    """Result of JstHits.align(): JST_ALN_DTYPE records in the order of JstHits.view(), and the pool of CIGAR words
+    (len << 4 | op) they point into -- one transcript per segment hit, shared by the haplotypes of its context."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def _raw(self):
+        rec = C.POINTER(capi.JstAln)()
+        ops = C.POINTER(C.c_uint32)()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
+               self.ctx._h)
+        return rec, n.value, ops, n_ops.value
+
+    def __len__(self):
+        return self._raw()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n, _, _ = self._raw()
+        if n == 0:
+            return np.zeros(0, dtype=JST_ALN_DTYPE)
+        buf = (capi.JstAln * n).from_address(C.addressof(rec.contents))
+        return np.frombuffer(buf, dtype=JST_ALN_DTYPE).copy()
+
+    @property
+    def ops(self) -> np.ndarray:
+        _, _, ops, n_ops = self._raw()
+        if n_ops == 0:
+            return np.zeros(0, dtype=np.uint32)
+        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
+        return np.frombuffer(buf, dtype=np.uint32).copy()
+
+    def device(self):
+        """(records, n, ops, n_ops): device pointers, records in the arrival order of the alignment fan-out."""
+        r, o = C.c_void_p(), C.c_void_p()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)),
+               self.ctx._h)
+        return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
+
+    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
+        """SAM string of record i (records / ops: views already fetched, to save the copies)."""
+        r = (self.view() if records is None else records)[i]
+        o = self.ops if ops is None else ops
+        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
+        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+
+    def stats(self) -> capi.JstAlignStats:
+        s = capi.JstAlignStats()
+        _check(capi.lib().spm_hip_jst_alns_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_jst_alns_destroy(self._h)
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:
