@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/spm_hip.h"
+#include "scan_plan.hpp"
 
 namespace spm_hip
 {
@@ -29,9 +31,9 @@ extern thread_local std::string g_init_error;
 struct hits_block // device buffers + events of one scan result, recycled through the context
 {
     spm_hit *d_hits = nullptr;
-    unsigned long long *d_count = nullptr;
+    unsigned long long *d_count = nullptr; // kCntBlock counters (scan_plan.hpp: scan_counter)
     uint64_t cap = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // scan begins, main pass begins, ... ends, verification ends
     bool zeroed = false; // the counters were cleared when the block went back to the pool
     unsigned long long *h_c = nullptr; // pinned: where a deferred scan's counters land (allocated on first use, recycled)
     hipEvent_t ev_done = nullptr;
@@ -74,22 +76,18 @@ struct spm_text
     uint64_t packed_words = 0;
 };
 
-struct spm_hits
+struct spm_hits : hits_block // (its buffers, counters and events: taken from the context's pool and given back to it)
 {
     spm_ctx *ctx = nullptr;
-    spm_hit *d_hits = nullptr;
-    unsigned long long *d_count = nullptr; // [0] hits, [1] candidates, [2] overflow flags
-    uint64_t cap = 0;
     uint64_t cand_cap = 0; // survivor list capacity of the filter run
     uint64_t band_cap = 0;
     uint64_t n = 0;
     bool counted = false;
     bool hook_final = false;          // the caller's after-launch work (scan_impl) ran on the final hit list ...
-    unsigned long long fan_count = 0; // ... and counted this much into counter slot 12
+    unsigned long long fan_count = 0; // ... and counted this much into kCntFanOut
     bool sorted_host = false;
     std::vector<spm_hit> host;
     spm_scan_stats stats{};
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
     void *d_aux[2] = {nullptr, nullptr}; // segmented scans: tile table, segment offsets (freed with the hits)
     // deferred completion (SPM_SCAN_DEFER): the counters are on their way to h_c behind ev_done; what the scan was, in case
@@ -98,8 +96,6 @@ struct spm_hits
     bool c_on_the_way = false;  // ... the copy of the counters into h_c has been enqueued (by the scan, or by the device-side
                                 // fused copy, whose kernel writes them itself: one launch less in a C2 step)
     bool d_count_cleared = false; // the fused-copy kernel consumed the device counters and cleared them for the next scan
-    unsigned long long *h_c = nullptr;
-    hipEvent_t ev_done = nullptr;
     const spm_text *d_text = nullptr;
     const struct spm_patterns *d_patterns = nullptr;
     uint64_t d_begin = 0, d_end = 0;
@@ -113,6 +109,35 @@ struct spm_hits
     bool al_device_segs = false;    // segment table only on the device (journaled-sequence search)
     std::vector<uint64_t> al_segs;  // segmented scans: the segment table (n_segments + 1 offsets)
 };
+
+// A deferred scan that had to be repeated: `h` takes over the buffers and the outcome of the repeated scan, which gets
+// h's in exchange and is destroyed by the caller.  The only place that knows which members are device resources: the
+// hits_block (whose pinned block and event stay where they are) and the per-scan tables in d_aux.
+inline void hits_adopt(spm_hits &h, spm_hits &from)
+{
+    std::swap(static_cast<hits_block &>(h), static_cast<hits_block &>(from));
+    std::swap(h.h_c, from.h_c);
+    std::swap(h.ev_done, from.ev_done);
+    std::swap(h.d_aux, from.d_aux);
+    from.d_count_cleared = h.d_count_cleared; // (the flags follow the buffers they describe)
+    h.d_count_cleared = false;
+    h.n = from.n;
+    h.counted = from.counted;
+    h.stats = from.stats;
+    h.cand_cap = from.cand_cap;
+    h.band_cap = from.band_cap;
+    h.timed = from.timed;
+    h.sorted_host = false;
+    h.host.clear();
+}
+
+// a step of a scan that reports through its return code, like SPM_HIP_CHECK for HIP calls
+#define SPM_TRY(call)                                                                                                  \
+    do {                                                                                                               \
+        const int _rc = (call);                                                                                        \
+        if (_rc != SPM_OK)                                                                                             \
+            return _rc;                                                                                                \
+    } while (0)
 
 struct pass_entry // key directory of one pass of the seed filter, in L2 (filter.hpp: resolve_kernel)
 {

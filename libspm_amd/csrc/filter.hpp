@@ -71,7 +71,7 @@ constexpr unsigned long long kBandEmpty = ~0ull;
 // instead of one per ballot (a single address takes ~100 atomics/us).  Chunks grow as a wave keeps drawing -- 32, 64, ..
 // 1024 -- so a quiet text costs a few hundred wasted slots and a repeat-rich one (10^7 survivors) a few thousand atomics.
 // Slots a wave reserved but did not fill are marked invalid.
-constexpr uint32_t kChunkMin = 32;
+// (kChunkMin = 32: scan_plan.hpp, which sizes the lists for it)
 constexpr uint32_t kChunkMax = 1024;
 // The chunk a wave of the streaming kernel is filling lives in LDS behind the level-1 table (kCandRec words per wave:
 // {base lo, base hi, used, size, survivors of the current span, span given up, span begin lo, hi}; touched only on the
@@ -95,7 +95,7 @@ struct filter_params
     uint32_t n_probes;        // Bloom probes per key
     uint32_t span_chunks;     // chunks per span
     uint32_t span_unit;       // symbols per chunk: 1024 (1-byte text) or 4096 (2-bit shadow)
-    uint32_t dynamic;         // 1: waves draw spans from counters[4] instead of a static round-robin
+    uint32_t dynamic;         // 1: waves draw spans from counters[kCntSpanHead] instead of a static round-robin
     uint32_t key_len;         // H: symbols per key (12..16); windows are H symbols, keys 2H bits
     uint32_t key_mask;        // (1 << 2H) - 1
     uint32_t hash_variant;    // 1: Bloom cascade, 2: perfect-hash fingerprints, 3: dense pass, 4: presence bits
@@ -113,7 +113,7 @@ struct filter_params
     uint32_t bucket_shift;
     const uint4 *buckets;     // fingerprint buckets, L2-resident
     survivor *surv;
-    unsigned long long *counters; // [1] = survivor slots drawn, [6] = spans that gave up, [2] = hard overflow
+    unsigned long long *counters; // the scan's counter block (scan_plan.hpp: scan_counter)
     uint64_t surv_cap;
     uint64_t *ovf_spans;      // [ovf_cap][2]: {first text index, symbols} of every span that gave up
     uint64_t ovf_cap;
@@ -152,12 +152,12 @@ __device__ __forceinline__ void span_give_up(const filter_params &P, uint32_t *c
 {
     if (lane == 0) {
         ck[5] = 1;
-        const unsigned long long i = atomicAdd(&P.counters[6], 1ull);
+        const unsigned long long i = atomicAdd(&P.counters[kCntSpansGaveUp], 1ull);
         if (i < P.ovf_cap) {
             P.ovf_spans[2 * i] = ((uint64_t)ck[7] << 32) | ck[6];
             P.ovf_spans[2 * i + 1] = (uint64_t)P.span_chunks * (uint64_t)P.span_unit;
         } else {
-            atomicAdd(&P.counters[2], 1ull); // no room to remember it: the host re-runs the whole scan
+            atomicAdd(&P.counters[kCntVoid], 1ull); // no room to remember it: the host re-runs the whole scan
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -201,7 +201,7 @@ __device__ __forceinline__ void emit_survivors(const filter_params &P, bool has,
         uint32_t next = size * 2 < kChunkMin ? kChunkMin : (size * 2 > kChunkMax ? kChunkMax : size * 2);
         next = next < n ? n : next;
         if (lane == 0) {
-            const unsigned long long b = atomicAdd(&P.counters[1], (unsigned long long)next);
+            const unsigned long long b = atomicAdd(&P.counters[kCntSurvSlots], (unsigned long long)next);
             ck[0] = (uint32_t)b;
             ck[1] = (uint32_t)(b >> 32);
             ck[2] = 0;
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
     const uint8_t *lane_text = P.text + base0 + (uint64_t)lane * 16;
 
     // Dynamic scheduling (evens out the tail; static round-robin measured 15-20 % slower on 16 GiB):
-    //   dynamic == 1: every wave draws its next span with one returning atomic on counters[4];
+    //   dynamic == 1: every wave draws its next span with one returning atomic on counters[kCntSpanHead];
     //   dynamic == 2: one atomic per WORKGROUP hands one span to each of its waves (waves_per_wg times fewer
     //                 atomics at the same granularity; a single head saturates near 88 dequeues/us, which a 1 GiB
     //                 text with 16 KiB spans would exceed).  Sharding the head per XCD group was slower (no
@@ -503,13 +503,13 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
         if (P.dynamic == 1) {
             unsigned long long t = 0;
             if (lane == 0)
-                t = atomicAdd(&P.counters[4], 1ull);
+                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
             sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
         } else if (P.dynamic == 2) {
             __syncthreads(); // every wave has read the previous base
             if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[4], (unsigned long long)waves_per_wg);
+                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
                 lds[P.lds_words] = (uint32_t)t;
                 lds[P.lds_words + 1] = (uint32_t)(t >> 32);
             }
@@ -777,13 +777,13 @@ __global__ __launch_bounds__(1024) void seed_filter_dense_kernel(const filter_pa
         if (P.dynamic == 1) {
             unsigned long long t = 0;
             if (lane == 0)
-                t = atomicAdd(&P.counters[4], 1ull);
+                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
             sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
         } else if (P.dynamic == 2) {
             __syncthreads();
             if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[4], (unsigned long long)waves_per_wg);
+                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
                 lds[P.lds_words] = (uint32_t)t;
                 lds[P.lds_words + 1] = (uint32_t)(t >> 32);
             }
@@ -878,13 +878,13 @@ __global__ __launch_bounds__(1024) void seed_filter_packed_kernel(const filter_p
         if (P.dynamic == 1) {
             unsigned long long t = 0;
             if (lane == 0)
-                t = atomicAdd(&P.counters[4], 1ull);
+                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
             sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
         } else if (P.dynamic == 2) {
             __syncthreads();
             if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[4], (unsigned long long)waves_per_wg);
+                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
                 lds[P.lds_words] = (uint32_t)t;
                 lds[P.lds_words + 1] = (uint32_t)(t >> 32);
             }
@@ -964,7 +964,7 @@ struct verify_params
     uint64_t pos_offset;
     const band_rec *bands;
     const unsigned long long *counters; // [band_counter] = entries of the band list
-    uint32_t band_counter;              // 3: the list resolve_kernel wrote; 10: the list band_select_kernel kept
+    uint32_t band_counter;              // kCntBandSlots: the list resolve_kernel wrote; kCntBandsSelected / kCntRunHeads: the kept list
     uint32_t preselected;               // 1: the list holds only bands with enough seed hits, their table slots reset
     uint64_t band_cap;
     ulonglong2 *band_tab;               // band table (slots are given back as the bands are consumed), see band_value()
@@ -986,9 +986,9 @@ struct verify_params
     unsigned long long *seen; // hash set of (pattern << 40 | end)
     uint32_t seen_mask;
     spm_hit *hits;
-    unsigned long long *hit_counter; // counters[0]
+    unsigned long long *hit_counter; // counters[kCntHits]
     uint64_t hit_cap;
-    unsigned long long *overflow; // counters[2]
+    unsigned long long *overflow; // counters[kCntVoid]
     const uint64_t *seg_offsets;  // segmented haystacks: n_segments+1 ascending offsets, or nullptr
     uint64_t n_segments;
     const uint32_t *seg_owned;    // optional, per segment: only hits whose last symbol lies at or behind this offset
@@ -1014,8 +1014,7 @@ struct verify_params
 struct resolve_params
 {
     const survivor *surv;
-    unsigned long long *counters; // [1] survivor slots drawn (this pass), [3] band slots drawn, [5] candidates (stat),
-                                  // [8] survivors over all passes, [9] largest survivor demand of a pass, [2] overflow
+    unsigned long long *counters; // the scan's counter block (scan_plan.hpp: scan_counter)
     uint64_t surv_cap;
     const pass_entry *passes; // key directories, one per pass
     const uint4 *entries;     // {val = needle << 11 | offset, seed signature, range code, key}: a key's entries side by side
@@ -1298,7 +1297,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
         for (uint32_t tries = 0; tries < 8192 && !placed; ++tries) {
             // (a table that has overflowed is lost -- the host repeats the scan with a larger one: do not walk a full table
             // 8192 slots per band, which cost 5 s on a text with 5 % repeats whose first attempt was sized for 1 %)
-            if ((tries & 31u) == 31u && __hip_atomic_load(&R.counters[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+            if ((tries & 31u) == 31u && __hip_atomic_load(&R.counters[kCntVoid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
                 break;
             const unsigned long long o = atomicCAS(&R.band_tab[s2].x, kBandEmpty, bkey);
             if (o == kBandEmpty) {
@@ -1311,7 +1310,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
             }
         }
         if (!placed) {
-            atomicAdd(&R.counters[2], 1ull); // table full: the host starts over with more room
+            atomicAdd(&R.counters[kCntVoid], 1ull); // table full: the host starts over with more room
             *R.table_poison = 1u;
         }
         else if (R.overlap)
@@ -1335,7 +1334,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
         }
         unsigned long long b = 0;
         if (lane == 0)
-            b = atomicAdd(&R.counters[3], (unsigned long long)next);
+            b = atomicAdd(&R.counters[kCntBandSlots], (unsigned long long)next);
         C.base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
         C.used = 0;
@@ -1351,7 +1350,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
             br.band = (uint32_t)(bkey & ((1ull << R.band_bits) - 1));
             R.bands[idx] = br;
         } else {
-            atomicAdd(&R.counters[2], 1ull); // band list full: the slot this lane claimed is never given back
+            atomicAdd(&R.counters[kCntVoid], 1ull); // band list full: the slot this lane claimed is never given back
             *R.table_poison = 1u;
         }
     }
@@ -1515,7 +1514,7 @@ __device__ __forceinline__ void check_pairs(const resolve_params &R, resolve_wav
         if (R.overlap && b_cur > 0 && d_lo - b_cur * (int64_t)R.Bw <= (int64_t)R.k[pat])
             --b_cur;
         if ((uint64_t)b_last >> R.band_bits) {
-            atomicAdd(&R.counters[2], 1ull); // a haystack too long for the key layout: the host falls back
+            atomicAdd(&R.counters[kCntVoid], 1ull); // a haystack too long for the key layout: the host falls back
             b_last = b_cur - 1;
         }
     }
@@ -1554,17 +1553,17 @@ __global__ __launch_bounds__(256) void resolve_kernel(const resolve_params R)
 {
     __shared__ pair_queue pair_queues[4];
     __shared__ band_queue band_queues[4];
-    unsigned long long n = R.counters[1];
+    unsigned long long n = R.counters[kCntSurvSlots];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd(&R.counters[8], n);
-        atomicMax(&R.counters[9], n);
+        atomicAdd(&R.counters[kCntUnreadSurvSum], n);
+        atomicMax(&R.counters[kCntUnreadSurvMax], n);
     }
     if (n > R.surv_cap)
         n = R.surv_cap;
     if (!R.exact_hits && __hip_atomic_load(R.table_poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
         // an earlier scan left slots in the band table and the host has not emptied it yet: this scan is void
         if (blockIdx.x == 0 && threadIdx.x == 0)
-            atomicAdd(&R.counters[2], 1ull);
+            atomicAdd(&R.counters[kCntVoid], 1ull);
         return;
     }
     const uint32_t lane = threadIdx.x & 63;
@@ -1584,7 +1583,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const resolve_params R)
     for (uint64_t r = 0; r < rounds; ++r) {
         // a list or table of this attempt has overflowed: its results are void (the host starts over), stop feeding it
         if ((r & 7u) == 7u &&
-            __builtin_amdgcn_readfirstlane((uint32_t)(__hip_atomic_load(&R.counters[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)))
+            __builtin_amdgcn_readfirstlane((uint32_t)(__hip_atomic_load(&R.counters[kCntVoid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)))
             break;
         const uint64_t i = r * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
         bool probing = false;
@@ -1726,7 +1725,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const resolve_params R)
     for (uint32_t q = S.C.used + lane; q < S.C.size; q += 64)
         if (S.C.base + q < R.band_cap)
             R.bands[S.C.base + q].val = kBandInvalid;
-    wave_count_add(R.counters + 5, S.n_cand);
+    wave_count_add(R.counters + kCntPairs, S.n_cand);
 }
 
 // one key per reported hit in the scan's dedupe set; true if this is the first report of (pattern, end)
@@ -1741,7 +1740,7 @@ __device__ __forceinline__ bool seen_insert(const verify_params &P, uint32_t pat
 // slot back.
 __global__ __launch_bounds__(256) void band_select_kernel(const verify_params P, band_rec *out, unsigned long long *out_count)
 {
-    unsigned long long n = P.counters[3];
+    unsigned long long n = P.counters[kCntBandSlots];
     if (n > P.band_cap)
         n = P.band_cap;
     const uint32_t lane = threadIdx.x & 63;
@@ -2183,7 +2182,7 @@ __global__ __launch_bounds__(256) void verify_kernel(const verify_params P)
         }
     }
     flush();
-    wave_count_add(P.hit_counter + 7, n_valid); // bands verified
+    wave_count_add(P.hit_counter + kCntBandsVerified, n_valid); // bands verified
 }
 
 
@@ -2441,7 +2440,7 @@ __global__ __launch_bounds__(256) void verify_wave_kernel(const verify_params P,
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    wave_count_add(P.hit_counter + 7, n_valid); // bands verified
+    wave_count_add(P.hit_counter + kCntBandsVerified, n_valid); // bands verified
 }
 
 } // namespace spm_hip

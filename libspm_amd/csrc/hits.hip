@@ -16,9 +16,9 @@ static int hits_count(spm_hits *h)
     }
     if (!h->counted) {
         unsigned long long *c = ctx->h_counters;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, h->d_count, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, h->d_count, kCntReadBackCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        h->n = c[0];
+        h->n = c[kCntHits];
         h->counted = true;
     }
     if (h->n > h->cap) {
@@ -118,7 +118,7 @@ extern "C" int spm_hip_hits_copy_fused(spm_hits *h, void *device_dst, uint64_t c
 // [count | status | records] without the host: the counters are read on the device.  status != 0: a list overflowed or
 // spans gave up -- the host has to complete the scan (scan.hip: spm_complete_deferred).  The kernel also delivers the
 // counters to the result's pinned block (`host_c`, device-visible host memory) and, once every workgroup has read them
-// (a ticket in the spare slot 15), clears them for the scan that will reuse the block: a deferred C2 step is three
+// (a ticket in the spare slot kCntTicket), clears them for the scan that will reuse the block: a deferred C2 step is three
 // launches -- streaming, resolve, this -- instead of five.
 __global__ __launch_bounds__(256) void hits_fused_copy_device_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src,
                                                                        unsigned long long *__restrict__ counters,
@@ -126,13 +126,13 @@ __global__ __launch_bounds__(256) void hits_fused_copy_device_kernel(uint4 *__re
                                                                        unsigned long long cap, unsigned long long hit_cap,
                                                                        unsigned long long cand_cap)
 {
-    const unsigned long long n = counters[0];
-    const unsigned long long status = (counters[2] != 0 || counters[6] != 0 || counters[1] > cand_cap || n > hit_cap) ? 1ull : 0ull;
+    const unsigned long long n = counters[kCntHits];
+    const unsigned long long status = scan_needs_host(counters, cand_cap, n, hit_cap) ? 1ull : 0ull;
     const unsigned long long n_copy = n < cap ? (n < hit_cap ? n : hit_cap) : cap;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0)
         dst[0] = make_uint4((uint32_t)n, (uint32_t)(n >> 32), (uint32_t)status, 0u);
-    if (blockIdx.x == 0 && threadIdx.x < 13 && host_c)
+    if (blockIdx.x == 0 && threadIdx.x < kCntReadBack && host_c)
         host_c[threadIdx.x] = counters[threadIdx.x];
     for (uint64_t r = i; r < n_copy; r += (uint64_t)gridDim.x * blockDim.x)
         dst[1 + r] = src[r];
@@ -141,10 +141,10 @@ __global__ __launch_bounds__(256) void hits_fused_copy_device_kernel(uint4 *__re
         __shared__ unsigned int last;
         if (threadIdx.x == 0) {
             __threadfence();
-            last = atomicAdd(&counters[15], 1ull) == (unsigned long long)gridDim.x - 1 ? 1u : 0u;
+            last = atomicAdd(&counters[kCntTicket], 1ull) == (unsigned long long)gridDim.x - 1 ? 1u : 0u;
         }
         __syncthreads();
-        if (last && threadIdx.x < 16)
+        if (last && threadIdx.x < kCntBlock)
             counters[threadIdx.x] = 0;
     }
 }
@@ -228,24 +228,17 @@ extern "C" void spm_hip_hits_destroy(spm_hits *h)
         hipFree(h->d_aux[1]);
     }
     if (h->ctx && h->d_hits && h->d_count && h->ev[3] && h->ctx->pool.size() < 8) {
-        hits_block b;
-        b.d_hits = h->d_hits;
-        b.d_count = h->d_count;
-        b.cap = h->cap;
-        for (int e = 0; e < 4; ++e)
-            b.ev[e] = h->ev[e];
-        b.h_c = h->h_c;
-        b.ev_done = h->ev_done;
+        hits_block b = *h;
         // the next scan's counters: cleared now, behind this scan's last read of them (stream order), not in front of that scan
         // (a deferred scan whose counters went out through the device-side fused copy has cleared them there)
-        b.zeroed = h->d_count_cleared || hipMemsetAsync(b.d_count, 0, 16 * sizeof(unsigned long long), h->ctx->stream) == hipSuccess;
+        b.zeroed = h->d_count_cleared || hipMemsetAsync(b.d_count, 0, kCntBlock * sizeof(unsigned long long), h->ctx->stream) == hipSuccess;
         h->ctx->pool.push_back(b); // stream order makes reuse by the next scan safe
     } else {
         if (h->ctx)
             hipStreamSynchronize(h->ctx->stream);
         hipFree(h->d_hits);
         hipFree(h->d_count);
-        for (int i = 0; i < 6; ++i)
+        for (int i = 0; i < 4; ++i)
             if (h->ev[i])
                 hipEventDestroy(h->ev[i]);
         if (h->h_c)

@@ -3,6 +3,7 @@
 // CPU test leg (tests/test_host_sanitizers.py); the product compiles the same header into libspm_hip.so.
 #include "comm_protocol.hpp"
 #include "index_build.hpp"
+#include "scan_plan.hpp"
 #include "tables_build.hpp"
 
 extern "C" int spm_hip_host_selftest(int algo, const uint8_t *ranks_concat, const uint32_t *offsets, uint32_t n_patterns,

@@ -101,37 +101,29 @@ struct scan_tuning
     }
 };
 
-struct scan_args
+struct scan_args // what the caller asked for: const for the whole call
 {
     spm_ctx *ctx;
     const spm_text *text;
-    uint64_t begin, end, ctx_begin;
+    uint64_t begin, end, ctx_begin; // owned end positions of the filter engine's share, and where its haystack begins
     const spm_patterns *ps;
     spm_scan_opts opts;
-    const void *state_in;
-    void *state_out;
     spm_hits *hits;
     scan_tuning tune;                        // the environment's knobs, as this call found them
     const uint64_t *seg_offsets = nullptr; // host; n_segments + 1 entries
     uint64_t n_segments = 0;
     const uint64_t *d_seg_offsets = nullptr; // the same table already resident on the device (journaled-sequence index)
     const uint32_t *d_seg_owned = nullptr;   // optional per-segment offset of the first wanted end symbol (filter engine)
-    uint64_t cand_cap_override = 0;          // retry after a survivor overflow: the count the first attempt needed
-    uint64_t band_scale = 0;                 // retry after a band list / table overflow: that much more room
-    bool seen_full = false;                  // retry after a dedupe-set overflow: size it for the caller's hit buffer
-    bool need_seen = false;                  // exact sets reporting from the resolve kernel: the dedupe set after all (spans gave up)
-    bool seen_skipped = false;               // ... this run went without it
-    bool exact_used = false;                 // this run reported its hits from the resolve kernel (no bands, no verification)
-    std::vector<uint64_t> seg_host;          // host copy fetched on demand when only the device table was given
-    // span-local fallback: the filter run leaves these for the brute-force re-scan of the spans that gave up
-    unsigned long long *d_seen = nullptr;
-    uint32_t seen_mask = 0;
-    uint64_t *d_ovf = nullptr;               // overflow list in the scratch buffer: {begin, symbols} per span
-    const std::vector<uint64_t> *tiles = nullptr; // brute pass over an explicit tile table {scan_lo, own_lo, own_hi}
 };
 
-constexpr uint64_t kOvfCap = 1ull << 17; // spans the overflow list holds (2 MiB); beyond: whole-scan fallback
-
+struct scan_state // what scan_impl owns between the attempts and passes of one call
+{
+    retry_state retry;
+    filter_result filt;                           // of the latest filter run
+    const uint64_t *segs = nullptr;               // segmented scans: the table on the host (host_segments, scan.hip)
+    std::vector<uint64_t> seg_host;               // ... fetched once per call when only the device table was given
+    const std::vector<uint64_t> *tiles = nullptr; // brute pass over an explicit tile table {scan_lo, own_lo, own_hi}
+};
 
 // ---- state blobs: ABI state <-> the kernels' [group][rows][64] layout (patterns.hip) ----
 void state_to_internal(const spm_patterns *p, const void *state, std::vector<uint32_t> &out);
@@ -141,10 +133,10 @@ int text_alloc(spm_ctx *ctx, uint64_t n, uint32_t sigma, spm_text **out);
 // ---- the engines ----
 int ensure_scratch(spm_ctx *ctx, size_t bytes);
 // one brute-force pass; `report` = false suppresses hits (state-only pass)   (scan_brute.hip)
-int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_begin, const uint32_t *d_state_in,
-              uint32_t *d_state_out, bool report, bool single_tile);
+int run_brute(const scan_args &A, const scan_state &S, uint64_t begin, uint64_t end, uint64_t ctx_begin,
+              const uint32_t *d_state_in, uint32_t *d_state_out, bool report, bool single_tile);
 // the seed filter's launches for one scan: streaming pass(es), resolve, verification   (scan_filter.hip)
-int run_filter(const scan_args &A);
+int run_filter(const scan_args &A, const retry_state &R, filter_result &out);
 // after_launch: work the caller wants on the stream right behind the filter scan's kernels, before the host reads the
 // counters (the pan-genome search's fan-out); spm_hits::hook_final tells whether it saw the final hit list.   (scan.hip)
 int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, const spm_patterns *patterns,

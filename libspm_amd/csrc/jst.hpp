@@ -1204,7 +1204,7 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
         G.n_hits = 0;
         G.n_hits_dev = h->d_count;
         G.hit_cap = h->cap;
-        G.out_count = h->d_count + 12;
+        G.out_count = h->d_count + kCntFanOut;
         const uint64_t expect = std::max<uint64_t>(1u << 16, 2 * J->seg_hit_hint);
         SPM_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
         hipLaunchKernelGGL(jst_fanout_kernel, dim3((unsigned)std::min<uint64_t>((expect + 255) / 256, (uint64_t)ctx->n_cu * 64)),
@@ -1254,9 +1254,9 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
             SPM_HIP_CHECK(ctx, hipGetLastError());
         }
         SPM_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_counters + 8, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_counters + kLandFanOut, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        n_out = ctx->h_counters[8];
+        n_out = ctx->h_counters[kLandFanOut];
     }
     hipEventElapsedTime(&J->stats.ms_fanout, e0, e1);
     if (n_out > out_cap) {

@@ -44,9 +44,24 @@ void launch_brute(const spm_patterns *ps, const brute_params &P, dim3 grid, dim3
 
 } // namespace
 
+// the pass's tile table goes to the device; the result owns it (d_aux[0], freed with the hits)
+static int upload_tiles(const scan_args &A, const std::vector<uint64_t> &tab, brute_params &P)
+{
+    spm_ctx *ctx = A.ctx;
+    P.n_tiles = (uint32_t)(tab.size() / 3);
+    uint64_t *d_tab = nullptr;
+    SPM_HIP_CHECK(ctx, hipMalloc(&d_tab, tab.size() * sizeof(uint64_t)));
+    hipFree(A.hits->d_aux[0]);
+    A.hits->d_aux[0] = d_tab;
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); // (`tab` may be a host temporary)
+    P.tile_tab = d_tab;
+    return SPM_OK;
+}
+
 // one brute-force pass; `report` = false suppresses hits (state-only pass)
-int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_begin, const uint32_t *d_state_in,
-              uint32_t *d_state_out, bool report, bool single_tile)
+int run_brute(const scan_args &A, const scan_state &S, uint64_t begin, uint64_t end, uint64_t ctx_begin,
+              const uint32_t *d_state_in, uint32_t *d_state_out, bool report, bool single_tile)
 {
     spm_ctx *ctx = A.ctx;
     const spm_patterns *ps = A.ps;
@@ -78,12 +93,12 @@ int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_beg
     P.state_in = d_state_in;
     P.state_out = d_state_out;
     P.hits = A.hits->d_hits;
-    P.counters = A.hits->d_count + (report ? 0 : 3); // a state-only pass counts into a dummy slot
+    P.counters = A.hits->d_count + (report ? kCntHits : kCntStateOnly); // (a state-only pass reports nothing)
     P.hit_cap = report ? A.hits->cap : 0;
-    if (A.tiles) { // re-scan of the filter's overflowed spans: report only what its verification has not reported
-        P.seen = A.d_seen;
-        P.seen_mask = A.seen_mask;
-        P.overflow = A.hits->d_count + 2;
+    if (S.tiles) { // re-scan of the filter's overflowed spans: report only what its verification has not reported
+        P.seen = S.filt.d_seen;
+        P.seen_mask = S.filt.seen_mask;
+        P.overflow = A.hits->d_count + kCntVoid;
     }
 
     const size_t lds_per_wave = (size_t)(ps->sigma + 1) * ps->NW * 64 * sizeof(uint32_t);
@@ -113,37 +128,13 @@ int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_beg
         tile = 4;
     P.tile = (uint32_t)std::min<uint64_t>(tile, 0xFFFFFF00u);
     P.n_tiles = (uint32_t)std::max<uint64_t>(1, (range + P.tile - 1) / P.tile);
-    if (A.tiles) {
-        P.n_tiles = (uint32_t)(A.tiles->size() / 3);
-        uint64_t *d_tab = nullptr;
-        SPM_HIP_CHECK(ctx, hipMalloc(&d_tab, A.tiles->size() * sizeof(uint64_t)));
-        hipFree(A.hits->d_aux[0]);
-        A.hits->d_aux[0] = d_tab;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, A.tiles->data(), A.tiles->size() * sizeof(uint64_t),
-                                          hipMemcpyHostToDevice, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        P.tile_tab = d_tab;
-    } else if (!A.seg_offsets && A.d_seg_offsets) {
-        // brute-force run over a device-resident segment table (fallback of the journaled-sequence search)
-        scan_args &W = const_cast<scan_args &>(A);
-        W.seg_host.resize(A.n_segments + 1);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(W.seg_host.data(), A.d_seg_offsets, (A.n_segments + 1) * sizeof(uint64_t),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        W.seg_offsets = W.seg_host.data();
-    }
-    if (A.seg_offsets && !A.tiles) {
+    if (S.tiles) {
+        SPM_TRY(upload_tiles(A, *S.tiles, P));
+    } else if (S.segs) {
         // every segment is its own haystack: tiles never cross a segment, warm-up stays inside it
         std::vector<uint64_t> tab;
-        for (uint64_t s = 0; s < A.n_segments; ++s) {
-            const uint64_t sb = A.seg_offsets[s], se = A.seg_offsets[s + 1];
-            for (uint64_t lo = sb; lo < se; lo += P.tile) {
-                const uint64_t hi = std::min<uint64_t>(lo + P.tile, se);
-                tab.push_back(lo >= sb + P.warm ? lo - P.warm : sb);
-                tab.push_back(lo);
-                tab.push_back(hi);
-            }
-        }
+        for (uint64_t s = 0; s < A.n_segments; ++s)
+            append_tiles(tab, S.segs[s], S.segs[s + 1], S.segs[s], P.warm, P.tile);
         if (tab.empty()) { // only empty segments
             tab = {begin, begin, begin};
         }
@@ -151,15 +142,7 @@ int run_brute(const scan_args &A, uint64_t begin, uint64_t end, uint64_t ctx_beg
             SPM_SET_ERR(ctx, "segmented scan: too many tiles");
             return SPM_E_UNSUPPORTED;
         }
-        P.n_tiles = (uint32_t)(tab.size() / 3);
-        uint64_t *d_tab = nullptr;
-        SPM_HIP_CHECK(ctx, hipMalloc(&d_tab, tab.size() * sizeof(uint64_t)));
-        hipFree(A.hits->d_aux[0]);
-        A.hits->d_aux[0] = d_tab;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                          ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); // `tab` is a host temporary
-        P.tile_tab = d_tab;
+        SPM_TRY(upload_tiles(A, tab, P));
     }
     if (single_tile && P.n_tiles != 1) {
         SPM_SET_ERR(ctx, "internal: single-tile pass over %llu symbols", (unsigned long long)range);

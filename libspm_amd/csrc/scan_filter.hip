@@ -169,371 +169,319 @@ int ensure_band_table(spm_ctx *ctx, uint64_t slots)
     return SPM_OK;
 }
 
-int run_filter(const scan_args &A)
+namespace
 {
-    spm_ctx *ctx = A.ctx;
-    const spm_patterns *ps = A.ps;
-    spm_hits *H = A.hits;
-    const uint64_t kmax = ps->max_k;
-    // ---- sizes: survivor list, band list, band table, dedupe set ----
-    constexpr uint64_t kSurvMax = 1ull << 27; // 2 GiB of survivors: beyond that spans give up (brute-force re-scan)
-    uint64_t est = std::max<uint64_t>(4096, 8ull * ps->n * (kmax + 1)); // a handful of true seed hits per needle
-    // real texts are not uniform: room for the seed hits of repeat stretches -- one survivor per 2048 symbols (1 % of a
-    // text in repeats needs one per 2800; a scan that outgrows its lists is repeated once with room for what it counted, and
-    // the needle set remembers).  The first scan on a context pays for these buffers: sized for one survivor per 512
-    // symbols (and as many bands) they were 2 GB of lists and a 4 GB band table to clear for a 16 GiB text -- 1.6 ms in
-    // front of a 2.7 ms scan.
-    est = std::max<uint64_t>(est, (A.end - A.begin) / (ps->scanned ? 4096 : 2048));
-    // chance hits of short keys: windows looked at x keys / 4^key_len, per pass (negligible for 16-symbol keys)
-    double chance = 0;
-    for (const filter_index &F : ps->fidx)
-        chance += (double)(A.end - A.begin) / std::max(1u, F.stride) * (double)F.n_keys / std::pow(4.0, (double)F.key_len);
-    est = std::max<uint64_t>(est, (uint64_t)(2.0 * chance));
-    est = std::max<uint64_t>(est, ps->cand_hint + ps->cand_hint / 4);
-    // slots are drawn in growing chunks per wave (unused tails stay invalid): twice the estimate + the first chunks
-    uint64_t surv_cap = std::min(2 * est + (uint64_t)ctx->n_cu * 16 * kChunkMin, kSurvMax);
-    if (A.cand_cap_override)
-        surv_cap = A.cand_cap_override;
-    const int cc = A.tune.cand_cap;
-    if (cc > 0)
-        surv_cap = (uint64_t)cc;
-    // (+ the first chunk of every wave of resolve_kernel: n_cu x 8 workgroups of 4 waves)
-    // bands: at most one per candidate pair, usually far fewer (uniform text: 1 000 for 20 000 survivors; 1 % repeats: 1.6 M
-    // for 6 M; 5 %: as many as survivors) -- a quarter of the survivor slots unless earlier scans needed more
-    const uint64_t band_want = std::max<uint64_t>(surv_cap / 4, 2 * ps->band_hint);
-    uint64_t band_cap = std::max<uint64_t>(band_want, 4096) * (A.band_scale ? A.band_scale : 1) +
-                        (uint64_t)ctx->n_cu * 32 * kChunkMin;
-    if (A.tune.band_cap > 0 && !A.band_scale) // (tests force the band-list-full path with it; a repeated attempt sizes itself)
-        band_cap = (uint64_t)A.tune.band_cap;
-    uint64_t band_slots = 1u << 12;
-    while (band_slots < 2 * band_cap)
-        band_slots <<= 1;
-    // bands: Bw diagonals each.  Sets with surplus seeds: 4(k+1), overlapping by k + 1 (wider bands mean fewer occurrences
-    // whose seeds straddle two of them at the price of more end positions per verification; 4(k+1) measured best for
-    // |P| = 1024, k = 64; the lane-per-band kernel keeps its end-position slots per thread: k + 1 there).
-    // Other sets: 32 diagonals, no overlap -- every band with a seed hit is verified.
-    uint32_t nwn = std::max(1u, (ps->max_m + 31) / 32);
-    const int wave_min = A.tune.verify_wave_min_words; // 0 = never use the wave-per-band kernel
-    // (the wave-per-band kernel keeps the match masks of <= 5 symbols in registers: dna15 sets use the lane-per-band one)
-    const bool use_wave = ps->d_peq_bot && wave_min > 0 && nwn >= (uint32_t)wave_min && ps->sigma <= 5;
-    const bool overlap = ps->d_surplus != nullptr;
-    uint32_t Bw = 32; // (one mask bit per diagonal)
-    if (overlap) {
-        Bw = (ps->max_k + 1) * (use_wave ? 4 : 1);
-        if (Bw + ps->max_k > 2047)
-            Bw = ps->max_k + 1;
-    }
-    const uint32_t max_span = Bw - 1 + (overlap ? ps->max_k + 1 : 0);
-    // dedupe set: one key per reported hit, so twice the hit capacity is room enough; a caller with a huge hit buffer
-    // (repeat-rich texts) pays for what earlier scans of this needle set actually reported
-    uint64_t want_seen = std::min<uint64_t>(band_cap * (2 * kmax + 1 + max_span), std::max<uint64_t>(H->cap, 1));
-    if (!A.seen_full)
-        // (the first scan of a needle set knows nothing yet: room for 4 M hits -- a 64 MiB memset, 10 us -- rather than a
-        // set that a repeat-rich text fills up, which costs a second run of the whole scan)
-        want_seen = std::min<uint64_t>(want_seen, ps->scanned ? std::max<uint64_t>(1u << 18, 4 * ps->hit_hint) : (1ull << 22));
-    uint64_t seen_slots = 1u << 16;
-    while (seen_slots < 2 * want_seen)
-        seen_slots <<= 1;
-    const size_t surv_bytes = surv_cap * sizeof(survivor);
-    const size_t seen_bytes = seen_slots * sizeof(unsigned long long);
-    const size_t band_bytes = band_cap * sizeof(band_rec) * 2; // (+ the selected bands of overlapping sets / the heads of runs)
-    const size_t ovf_bytes = kOvfCap * 2 * sizeof(uint64_t);
-    int rc = ensure_scratch(ctx, surv_bytes + seen_bytes + band_bytes + ovf_bytes);
-    if (rc != SPM_OK)
-        return rc;
-    // Exact sets whose needles are their own single seed (k = 0, no `N`, e.g. Shift-Or / Horspool sets): the whole-seed check
-    // of the resolve kernel is the whole comparison, so it reports the hits itself -- no band table, no verification launch.
-    // (Not for needles that are repeats: their merged index entries skip the per-offset check.)
-    bool exact_hits = ps->max_k == 0 && !overlap && ps->filter_max_range == 0 && ps->d_ranks;
-    if (exact_hits && ps->exact_whole < 0) {
-        bool whole = true;
-        for (uint32_t p = 0; p < ps->n && whole; ++p)
-            whole = ps->seed_n[p] == 1 && ps->seed_q[p] == (uint32_t)ps->m[p];
-        ps->exact_whole = whole ? 1 : 0;
-    }
-    exact_hits = exact_hits && ps->exact_whole == 1;
-    if (!exact_hits) {
-        rc = ensure_band_table(ctx, band_slots);
-        if (rc != SPM_OK)
-            return rc;
-    }
-    survivor *d_surv = (survivor *)ctx->d_scratch;
-    unsigned long long *d_seen = (unsigned long long *)((uint8_t *)ctx->d_scratch + surv_bytes);
-    band_rec *d_bands = (band_rec *)((uint8_t *)d_seen + seen_bytes);
-    uint64_t *d_ovf = (uint64_t *)((uint8_t *)d_bands + band_bytes);
-    {
-        scan_args &W = const_cast<scan_args &>(A);
-        W.d_seen = d_seen;
-        W.seen_mask = (uint32_t)(seen_slots - 1);
-        W.d_ovf = d_ovf;
-    }
-    // Exact sets whose hits come from the resolve kernel report every occurrence once by construction (one sampled window,
-    // one entry): no dedupe set, no 4 MiB memset in front of a 0.2 ms scan -- unless a span gives up (the brute-force
-    // re-scan of that span would report its hits a second time): then the scan runs again with the set.
-    const bool skip_seen = exact_hits && !A.need_seen;
-    const_cast<scan_args &>(A).seen_skipped = skip_seen;
-    const_cast<scan_args &>(A).exact_used = exact_hits;
-    if (!skip_seen)
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_seen, 0xFF, seen_bytes, ctx->stream));
-    if (!exact_hits)
-        ctx->band_dirty = true; // until the verification has consumed every band of this scan
+static_assert(sizeof(survivor) == kSurvivorBytes && sizeof(band_rec) == kBandRecBytes, "scan_plan.hpp sizes the lists");
 
-    filter_params P{};
-    P.text = A.text->d;
-    P.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
-    // windows that can belong to an occurrence whose last symbol is owned
-    const uint64_t reach = ps->max_window;
-    P.lo = A.begin >= A.ctx_begin + reach ? A.begin - reach : A.ctx_begin;
-    P.hi = A.end;
-    P.surv = d_surv;
-    P.counters = H->d_count;
-    P.surv_cap = surv_cap;
-    P.ovf_spans = d_ovf;
-    P.ovf_cap = kOvfCap;
-    SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
-    for (size_t fi = 0; fi < ps->fidx.size(); ++fi) {
-    const filter_index &F = ps->fidx[fi];
-    P.stride = F.stride;
-    P.key_len = F.key_len;
-    P.key_mask = F.key_len >= 16 ? 0xFFFFFFFFu : ((1u << (2 * F.key_len)) - 1);
-    P.bitmap_words = F.hash_variant == 2 ? 1024 : F.bitmap_words;
-    P.lds_words = F.lds_words;
-    P.chd_slot_mask = F.chd_slot_mask;
-    P.chd_bucket_shift = F.chd_bucket_shift;
-    P.chd_disp_off = F.chd_disp_off;
-    P.n_probes = F.n_probes;
-    P.bitmap = F.d_bitmap;
-    P.pass = (uint32_t)fi;
-    P.anchor_c = F.anchor_c;
-    P.anchor_cm = F.anchor_cm;
-    P.n_pat = F.n_pat;
-    for (uint32_t i = 0; i < kDensePatterns; ++i) {
-        P.pat_c[i] = F.pat_c[i];
-        P.pat_cm[i] = F.pat_cm[i];
-    }
-    P.bucket_shift = F.bucket_shift;
-    P.buckets = reinterpret_cast<const uint4 *>(F.d_buckets);
-    if (fi > 0) // each pass draws its spans from a fresh head
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(H->d_count + 4, 0, sizeof(unsigned long long), ctx->stream));
-    const bool km = F.key_len < 16; // (masked keys)
-    const bool bits = F.hash_variant == 4; // presence bits + L2 buckets as level 1 of a sparse pass: the dense kernel's machinery
-    const bool use_packed = F.hash_variant == 2 && A.text->d_packed && ps->sigma == 4 && F.stride >= 2 &&
-                            !(A.opts.flags & SPM_SCAN_IGNORE_PACKED);
-    // measured best: 8 waves per CU on the 1-byte text when HBM binds, 16 on the 2-bit shadow and at stride 1 with
-    // 16-symbol keys (LDS-bound: C4 25.8 vs 29.1 ms; the other stride-1/2 variants need more than 128 VGPRs)
-    // stride 2: two chunks per group (16 windows per lane) need < 128 VGPRs, so 16 waves per CU hide the LDS round trips
-    // (C5: 0.53 -> 0.46 ms; four chunks per group hold 167 VGPRs at 8 waves)
-    const bool wide_ok = use_packed || F.stride == 2 || (F.stride == 1 && !km && ps->sigma == 4);
-    const uint32_t threads = (F.dense || bits || wide_ok) ? 1024 : 512;
-    // + the workgroup's span-dequeue slot (4 words) + one survivor-chunk record per wave (+ dense: one queue per wave)
-    const size_t lds = (size_t)F.lds_words * 4 + 16 + 16 * kCandRec * 4 + ((F.dense || bits) ? 16 * sizeof(dense_queue) : 0);
-    const uint32_t wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 2048 / threads));
-    const uint32_t grid = ctx->n_cu * wg_per_cu;
-    const uint64_t n_waves = (uint64_t)grid * (threads / 64);
-    const uint64_t n_chunks = (P.hi - (P.lo & ~1023ull) + 1023) / 1024;
-    uint64_t span = n_chunks / (n_waves * 32) + 1;
-    // small texts: at least 64 KiB per dequeue as long as every wave still gets ~4 spans (a 1 GiB text ran 14 % faster
-    // with 64-chunk spans than with the 24 the rule above gives: fewer dequeue rounds, each a workgroup barrier)
-    if (span < 64)
-        span = std::max<uint64_t>(span, std::min<uint64_t>(64, n_chunks / (n_waves * 4) + 1));
-    span = std::min<uint64_t>(std::max<uint64_t>(span, 8), 4096);
-    span = (span + 7) & ~7ull; // whole groups of chunks
-    P.span_chunks = (uint32_t)span;
-    P.span_unit = 1024;
-    // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
-    // costs the verification about what the re-scan would
-    const int sb = A.tune.span_budget;
-    P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, span * 1024 / 4);
-    // span dequeue: per wave while the dequeue rate stays far below what one atomic word sustains (~88/us, i.e.
-    // spans >= 192 KiB at 7 TB/s), per workgroup otherwise (measured: C3 2.52 vs 2.59 ms, C2 0.88 vs 0.20 ms)
-    P.dynamic = span >= 192 ? 1u : 2u;
-    P.hash_variant = F.hash_variant;
-    if (use_packed) {
-        // p-chunks of 4096 symbols: recompute the span geometry in those units
-        filter_params Q = P;
-        const uint64_t n_pchunks = (Q.hi - (Q.lo & ~4095ull) + 4095) / 4096;
-        uint64_t pspan = n_pchunks / (n_waves * 8) + 1;
-        pspan = std::min<uint64_t>(std::max<uint64_t>(pspan, 4), 4096);
-        pspan = (pspan + 3) & ~3ull;
-        Q.span_chunks = (uint32_t)pspan;
-        Q.span_unit = 4096;
-        if (sb <= 0)
-            Q.span_budget = (uint32_t)std::max<uint64_t>(256, pspan * 4096 / 4);
-        Q.dynamic = pspan >= 48 ? 1u : 2u;
-        const packed_kernel k = select_packed_kernel(F.stride, km);
-        if (!k) {
-            SPM_SET_ERR(ctx, "internal: no packed filter kernel for stride %u, key length %u", F.stride, F.key_len);
-            return SPM_E_UNSUPPORTED;
+struct filter_run // one run_filter: the request, its sizes, the scratch buffer laid out for them, and the launches in order
+{
+    const scan_args &A;
+    const retry_state &retry;
+    spm_ctx *ctx;
+    const spm_patterns *ps;
+    spm_hits *H;
+    filter_sizes Z;
+    survivor *surv = nullptr;
+    unsigned long long *seen = nullptr;
+    band_rec *bands = nullptr;
+    uint64_t *ovf = nullptr;
+    const uint64_t *d_seg = nullptr; // the segment table on the device
+    uint64_t n_seg = 0;
+    uint32_t seg_bits = 0;
+    bool exact_hits = false, skip_seen = false;
+
+    // scratch and band table for these sizes; which reporting path the set takes; the dedupe set cleared
+    int lay_out()
+    {
+        SPM_TRY(ensure_scratch(ctx, Z.surv_bytes + Z.seen_bytes + Z.band_bytes + Z.ovf_bytes));
+        // Exact sets whose needles are their own single seed (k = 0, no `N`, e.g. Shift-Or / Horspool sets): the whole-seed check
+        // of the resolve kernel is the whole comparison, so it reports the hits itself -- no band table, no verification launch.
+        // (Not for needles that are repeats: their merged index entries skip the per-offset check.)
+        exact_hits = ps->max_k == 0 && !Z.overlap && ps->filter_max_range == 0 && ps->d_ranks;
+        if (exact_hits && ps->exact_whole < 0) {
+            bool whole = true;
+            for (uint32_t p = 0; p < ps->n && whole; ++p)
+                whole = ps->seed_n[p] == 1 && ps->seed_q[p] == (uint32_t)ps->m[p];
+            ps->exact_whole = whole ? 1 : 0;
         }
-        launch(k, dim3(grid), threads, lds, ctx->stream, Q, reinterpret_cast<const uint4 *>(A.text->d_packed));
-    } else {
-        const filter_kernel k = select_filter_kernel(F, ps->sigma, km);
-        if (!k) {
-            SPM_SET_ERR(ctx, "internal: no filter kernel for stride %u, key length %u, sigma %u, hash variant %u, %u patterns",
-                        F.stride, F.key_len, ps->sigma, F.hash_variant, F.n_pat);
-            return SPM_E_UNSUPPORTED;
+        exact_hits = exact_hits && ps->exact_whole == 1;
+        if (!exact_hits)
+            SPM_TRY(ensure_band_table(ctx, Z.band_slots));
+        surv = (survivor *)ctx->d_scratch;
+        seen = (unsigned long long *)((uint8_t *)surv + Z.surv_bytes);
+        bands = (band_rec *)((uint8_t *)seen + Z.seen_bytes);
+        ovf = (uint64_t *)((uint8_t *)bands + Z.band_bytes);
+        // Exact sets whose hits come from the resolve kernel report every occurrence once by construction (one sampled window,
+        // one entry): no dedupe set, no 4 MiB memset in front of a 0.2 ms scan -- unless a span gives up (the brute-force
+        // re-scan of that span would report its hits a second time): then the scan runs again with the set.
+        skip_seen = exact_hits && !retry.need_seen;
+        if (!skip_seen)
+            SPM_HIP_CHECK(ctx, hipMemsetAsync(seen, 0xFF, Z.seen_bytes, ctx->stream));
+        if (!exact_hits)
+            ctx->band_dirty = true; // until the verification has consumed every band of this scan
+        return SPM_OK;
+    }
+
+    // the streaming pass(es): one launch per pass of the seed index
+    int launch_passes()
+    {
+        filter_params P{};
+        P.text = A.text->d;
+        P.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
+        // windows that can belong to an occurrence whose last symbol is owned
+        const uint64_t reach = ps->max_window;
+        P.lo = A.begin >= A.ctx_begin + reach ? A.begin - reach : A.ctx_begin;
+        P.hi = A.end;
+        P.surv = surv;
+        P.counters = H->d_count;
+        P.surv_cap = Z.surv_cap;
+        P.ovf_spans = ovf;
+        P.ovf_cap = kOvfCap;
+        for (size_t fi = 0; fi < ps->fidx.size(); ++fi) {
+            const filter_index &F = ps->fidx[fi];
+            P.stride = F.stride;
+            P.key_len = F.key_len;
+            P.key_mask = F.key_len >= 16 ? 0xFFFFFFFFu : ((1u << (2 * F.key_len)) - 1);
+            P.bitmap_words = F.hash_variant == 2 ? 1024 : F.bitmap_words;
+            P.lds_words = F.lds_words;
+            P.chd_slot_mask = F.chd_slot_mask;
+            P.chd_bucket_shift = F.chd_bucket_shift;
+            P.chd_disp_off = F.chd_disp_off;
+            P.n_probes = F.n_probes;
+            P.bitmap = F.d_bitmap;
+            P.pass = (uint32_t)fi;
+            P.anchor_c = F.anchor_c;
+            P.anchor_cm = F.anchor_cm;
+            P.n_pat = F.n_pat;
+            for (uint32_t i = 0; i < kDensePatterns; ++i) {
+                P.pat_c[i] = F.pat_c[i];
+                P.pat_cm[i] = F.pat_cm[i];
+            }
+            P.bucket_shift = F.bucket_shift;
+            P.buckets = reinterpret_cast<const uint4 *>(F.d_buckets);
+            if (fi > 0) // each pass draws its spans from a fresh head
+                SPM_HIP_CHECK(ctx, hipMemsetAsync(H->d_count + kCntSpanHead, 0, sizeof(unsigned long long), ctx->stream));
+            const bool km = F.key_len < 16; // (masked keys)
+            const bool bits = F.hash_variant == 4; // presence bits + L2 buckets as level 1 of a sparse pass: the dense kernel's machinery
+            const bool use_packed = F.hash_variant == 2 && A.text->d_packed && ps->sigma == 4 && F.stride >= 2 &&
+                                    !(A.opts.flags & SPM_SCAN_IGNORE_PACKED);
+            // measured best: 8 waves per CU on the 1-byte text when HBM binds, 16 on the 2-bit shadow and at stride 1 with
+            // 16-symbol keys (LDS-bound: C4 25.8 vs 29.1 ms; the other stride-1/2 variants need more than 128 VGPRs)
+            // stride 2: two chunks per group (16 windows per lane) need < 128 VGPRs, so 16 waves per CU hide the LDS round trips
+            // (C5: 0.53 -> 0.46 ms; four chunks per group hold 167 VGPRs at 8 waves)
+            const bool wide_ok = use_packed || F.stride == 2 || (F.stride == 1 && !km && ps->sigma == 4);
+            const uint32_t threads = (F.dense || bits || wide_ok) ? 1024 : 512;
+            // + the workgroup's span-dequeue slot (4 words) + one survivor-chunk record per wave (+ dense: one queue per wave)
+            const size_t lds = (size_t)F.lds_words * 4 + 16 + 16 * kCandRec * 4 + ((F.dense || bits) ? 16 * sizeof(dense_queue) : 0);
+            const uint32_t wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 2048 / threads));
+            const uint32_t grid = ctx->n_cu * wg_per_cu;
+            const uint64_t n_waves = (uint64_t)grid * (threads / 64);
+            const uint64_t n_chunks = (P.hi - (P.lo & ~1023ull) + 1023) / 1024;
+            uint64_t span = n_chunks / (n_waves * 32) + 1;
+            // small texts: at least 64 KiB per dequeue as long as every wave still gets ~4 spans (a 1 GiB text ran 14 % faster
+            // with 64-chunk spans than with the 24 the rule above gives: fewer dequeue rounds, each a workgroup barrier)
+            if (span < 64)
+                span = std::max<uint64_t>(span, std::min<uint64_t>(64, n_chunks / (n_waves * 4) + 1));
+            span = std::min<uint64_t>(std::max<uint64_t>(span, 8), 4096);
+            span = (span + 7) & ~7ull; // whole groups of chunks
+            P.span_chunks = (uint32_t)span;
+            P.span_unit = 1024;
+            // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
+            // costs the verification about what the re-scan would
+            const int sb = A.tune.span_budget;
+            P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, span * 1024 / 4);
+            // span dequeue: per wave while the dequeue rate stays far below what one atomic word sustains (~88/us, i.e.
+            // spans >= 192 KiB at 7 TB/s), per workgroup otherwise (measured: C3 2.52 vs 2.59 ms, C2 0.88 vs 0.20 ms)
+            P.dynamic = span >= 192 ? 1u : 2u;
+            P.hash_variant = F.hash_variant;
+            if (use_packed) {
+                // p-chunks of 4096 symbols: recompute the span geometry in those units
+                filter_params Q = P;
+                const uint64_t n_pchunks = (Q.hi - (Q.lo & ~4095ull) + 4095) / 4096;
+                uint64_t pspan = n_pchunks / (n_waves * 8) + 1;
+                pspan = std::min<uint64_t>(std::max<uint64_t>(pspan, 4), 4096);
+                pspan = (pspan + 3) & ~3ull;
+                Q.span_chunks = (uint32_t)pspan;
+                Q.span_unit = 4096;
+                if (sb <= 0)
+                    Q.span_budget = (uint32_t)std::max<uint64_t>(256, pspan * 4096 / 4);
+                Q.dynamic = pspan >= 48 ? 1u : 2u;
+                const packed_kernel k = select_packed_kernel(F.stride, km);
+                if (!k) {
+                    SPM_SET_ERR(ctx, "internal: no packed filter kernel for stride %u, key length %u", F.stride, F.key_len);
+                    return SPM_E_UNSUPPORTED;
+                }
+                launch(k, dim3(grid), threads, lds, ctx->stream, Q, reinterpret_cast<const uint4 *>(A.text->d_packed));
+            } else {
+                const filter_kernel k = select_filter_kernel(F, ps->sigma, km);
+                if (!k) {
+                    SPM_SET_ERR(ctx, "internal: no filter kernel for stride %u, key length %u, sigma %u, hash variant %u, %u patterns",
+                                F.stride, F.key_len, ps->sigma, F.hash_variant, F.n_pat);
+                    return SPM_E_UNSUPPORTED;
+                }
+                launch(k, dim3(grid), threads, lds, ctx->stream, P);
+            }
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+            H->stats.main_launches++;
         }
-        launch(k, dim3(grid), threads, lds, ctx->stream, P);
+        return SPM_OK;
     }
-    SPM_HIP_CHECK(ctx, hipGetLastError());
-    H->stats.main_launches++;
+
+    // what resolve_params and verify_params share: text, ranges, segments, band table, hit buffer, dedupe set
+    template <typename Params>
+    void fill_shared(Params &X) const
+    {
+        X.text = A.text->d;
+        X.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
+        X.scan_begin = A.begin;
+        X.scan_end = A.end;
+        X.pos_offset = A.opts.pos_offset;
+        X.counters = H->d_count;
+        X.bands = bands;
+        X.band_cap = Z.band_cap;
+        X.band_tab = ctx->d_band_tab;
+        X.table_mask = (uint32_t)(Z.band_slots - 1);
+        X.band_bits = 43 - seg_bits;
+        X.Bw = Z.Bw;
+        X.overlap = Z.overlap ? 1u : 0u;
+        X.max_m = ps->max_m;
+        X.m = ps->d_m;
+        X.k = ps->d_k;
+        X.report_begin = ps->is_myers() ? 0 : 1;
+        X.seen_mask = (uint32_t)(Z.seen_slots - 1);
+        X.hits = H->d_hits;
+        X.hit_counter = H->d_count + kCntHits;
+        X.overflow = H->d_count + kCntVoid;
+        X.hit_cap = H->cap;
+        X.seg_offsets = d_seg;
+        X.n_segments = n_seg;
+        X.seg_owned = A.d_seg_owned;
     }
-    SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
 
     // ---- resolve: survivors -> needles -> whole-seed check -> diagonal bands (one launch for all passes) ----
-    const uint64_t *d_seg = nullptr;
-    uint64_t n_seg = 0;
-    if (A.d_seg_offsets) {
-        d_seg = A.d_seg_offsets;
-        n_seg = A.n_segments;
-    } else if (A.seg_offsets) {
-        uint64_t *d = nullptr;
-        SPM_HIP_CHECK(ctx, hipMalloc(&d, (A.n_segments + 1) * sizeof(uint64_t)));
-        hipFree(H->d_aux[1]);
-        H->d_aux[1] = d;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d, A.seg_offsets, (A.n_segments + 1) * sizeof(uint64_t),
-                                          hipMemcpyHostToDevice, ctx->stream));
-        d_seg = d;
-        n_seg = A.n_segments;
+    int launch_resolve()
+    {
+        // segmented scans: the table on the device (a host table is uploaded; the result owns the copy)
+        if (A.d_seg_offsets) {
+            d_seg = A.d_seg_offsets;
+            n_seg = A.n_segments;
+        } else if (A.seg_offsets) {
+            uint64_t *d = nullptr;
+            SPM_HIP_CHECK(ctx, hipMalloc(&d, (A.n_segments + 1) * sizeof(uint64_t)));
+            hipFree(H->d_aux[1]);
+            H->d_aux[1] = d;
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(d, A.seg_offsets, (A.n_segments + 1) * sizeof(uint64_t),
+                                              hipMemcpyHostToDevice, ctx->stream));
+            d_seg = d;
+            n_seg = A.n_segments;
+        }
+        while (n_seg && (1ull << seg_bits) < n_seg + 1)
+            ++seg_bits;
+        resolve_params R{};
+        fill_shared(R);
+        R.surv = surv;
+        R.surv_cap = Z.surv_cap;
+        R.passes = ps->d_pass_tab;
+        R.entries = ps->d_entries;
+        R.key_len = ps->filter_key_len;
+        R.needle_ranks = ps->d_ranks;
+        R.needle_offsets = ps->d_offsets;
+        R.seed_q = ps->d_seed_q;
+        R.flank_check = (ps->sigma == 4 && !Z.overlap && R.needle_ranks) ? 1u : 0u;
+        R.pieces_check = R.flank_check;
+        R.hay_begin = A.ctx_begin;
+        R.hay_end = A.end;
+        R.needle_pk = ps->d_needle_pk;
+        R.pk_offsets = ps->d_pk_offsets;
+        R.exact_hits = exact_hits ? 1u : 0u;
+        R.seen = skip_seen ? nullptr : seen;
+        R.table_poison = ctx->d_table_poison;
+        // grid: what earlier scans of this needle set produced (a full grid of idle workgroups costs ~30 us on a 2.6 ms scan);
+        // a scan that produces more simply loops
+        const uint64_t surv_expect = ps->cand_hint ? 2 * ps->cand_hint : Z.surv_cap;
+        // (5 workgroups per CU are resident at once -- LDS queues, 84 VGPRs --: a larger grid only adds a second, partly filled
+        // round.  A lane takes ~4 survivors in turn: measured on C5, whose survivors are few and cheap, 0.137 -> 0.10 ms;
+        // c3r 1.33 -> 1.25 ms with the cap alone.)
+        const uint64_t rmax = (uint64_t)ctx->n_cu * 5;
+        // (a short survivor list: one survivor per lane, its latency is the kernel's; a long one: four per lane)
+        const uint64_t per_wg = (surv_expect + 255) / 256 <= rmax ? 256 : 1024;
+        const uint32_t rgrid = (uint32_t)std::min<uint64_t>(rmax, std::max<uint64_t>(ctx->n_cu / 2, (surv_expect + per_wg - 1) / per_wg));
+        hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, R);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        return SPM_OK;
     }
-    uint32_t seg_bits = 0;
-    while (n_seg && (1ull << seg_bits) < n_seg + 1)
-        ++seg_bits;
-    resolve_params R{};
-    R.surv = d_surv;
-    R.counters = H->d_count;
-    R.surv_cap = surv_cap;
-    R.passes = ps->d_pass_tab;
-    R.entries = ps->d_entries;
-    R.key_len = ps->filter_key_len;
-    R.text = A.text->d;
-    R.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
-    R.needle_ranks = ps->d_ranks;
-    R.needle_offsets = ps->d_offsets;
-    R.seed_q = ps->d_seed_q;
-    R.flank_check = (ps->sigma == 4 && !overlap && R.needle_ranks) ? 1u : 0u;
-    R.pieces_check = R.flank_check;
-    R.m = ps->d_m;
-    R.k = ps->d_k;
-    R.hay_begin = A.ctx_begin;
-    R.hay_end = A.end;
-    R.seg_offsets = d_seg;
-    R.n_segments = n_seg;
-    R.Bw = Bw;
-    R.overlap = overlap ? 1u : 0u;
-    R.max_m = ps->max_m;
-    R.band_bits = 43 - seg_bits;
-    R.band_tab = ctx->d_band_tab;
-    R.needle_pk = ps->d_needle_pk;
-    R.pk_offsets = ps->d_pk_offsets;
-    R.exact_hits = exact_hits ? 1u : 0u;
-    R.report_begin = ps->is_myers() ? 0 : 1;
-    R.scan_begin = A.begin;
-    R.scan_end = A.end;
-    R.pos_offset = A.opts.pos_offset;
-    R.seg_owned = A.d_seg_owned;
-    R.seen = skip_seen ? nullptr : d_seen;
-    R.seen_mask = (uint32_t)(seen_slots - 1);
-    R.hits = H->d_hits;
-    R.hit_counter = H->d_count;
-    R.overflow = H->d_count + 2;
-    R.hit_cap = H->cap;
-    R.table_poison = ctx->d_table_poison;
-    R.table_mask = (uint32_t)(band_slots - 1);
-    R.bands = d_bands;
-    R.band_cap = band_cap;
-    // grid: what earlier scans of this needle set produced (a full grid of idle workgroups costs ~30 us on a 2.6 ms scan);
-    // a scan that produces more simply loops
-    const uint64_t surv_expect = ps->cand_hint ? 2 * ps->cand_hint : surv_cap;
-    // (5 workgroups per CU are resident at once -- LDS queues, 84 VGPRs --: a larger grid only adds a second, partly filled
-    // round.  A lane takes ~4 survivors in turn: measured on C5, whose survivors are few and cheap, 0.137 -> 0.10 ms;
-    // c3r 1.33 -> 1.25 ms with the cap alone.)
-    const uint64_t rmax = (uint64_t)ctx->n_cu * 5;
-    // (a short survivor list: one survivor per lane, its latency is the kernel's; a long one: four per lane)
-    const uint64_t per_wg = (surv_expect + 255) / 256 <= rmax ? 256 : 1024;
-    const uint32_t rgrid = (uint32_t)std::min<uint64_t>(rmax, std::max<uint64_t>(ctx->n_cu / 2, (surv_expect + per_wg - 1) / per_wg));
-    hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, R);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
 
-    // ---- verification: one band = one verification ----
-    verify_params V{};
-    V.text = A.text->d;
-    V.text_alloc = A.text->owned ? A.text->alloc : A.text->n;
-    V.ctx_begin = A.ctx_begin;
-    V.scan_begin = A.begin;
-    V.scan_end = A.end;
-    V.pos_offset = A.opts.pos_offset;
-    V.bands = d_bands;
-    V.counters = H->d_count;
-    V.band_cap = band_cap;
-    V.band_tab = ctx->d_band_tab;
-    V.surplus = ps->d_surplus;
-    V.Bw = Bw;
-    V.overlap = overlap ? 1u : 0u;
-    V.max_m = ps->max_m;
-    V.peq32 = ps->d_peq_verify ? ps->d_peq_verify : ps->d_peq;
-    V.sigma = ps->sigma;
-    V.nw_table = ps->NW;
-    V.max_k = ps->max_k;
-    V.max_span = max_span;
-    V.m = ps->d_m;
-    V.k = ps->d_k;
-    V.report_begin = ps->is_myers() ? 0 : 1;
-    V.seen = d_seen;
-    V.seen_mask = (uint32_t)(seen_slots - 1);
-    V.hits = H->d_hits;
-    V.hit_counter = H->d_count;
-    V.hit_cap = H->cap;
-    V.overflow = H->d_count + 2;
-    V.seg_offsets = d_seg;
-    V.n_segments = n_seg;
-    V.seg_owned = A.d_seg_owned;
-    V.band_counter = 3;
-    V.table_mask = (uint32_t)(band_slots - 1);
-    V.band_bits = 43 - seg_bits;
+    // ---- verification: one band = one verification.  `runs`: heads of runs of adjacent bands first (band_runs_kernel) ----
+    int launch_bands(bool runs)
+    {
+        verify_params V{};
+        fill_shared(V);
+        V.ctx_begin = A.ctx_begin;
+        V.surplus = ps->d_surplus;
+        V.peq32 = ps->d_peq_verify ? ps->d_peq_verify : ps->d_peq;
+        V.sigma = ps->sigma;
+        V.nw_table = ps->NW;
+        V.max_k = ps->max_k;
+        V.max_span = Z.max_span;
+        V.seen = seen;
+        V.band_counter = kCntBandSlots;
+        band_rec *kept = bands + Z.band_cap; // the second half of the band list: the bands a pre-pass keeps
+        if (runs) {
+            hipLaunchKernelGGL(band_runs_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, bands, kept, H->d_count + kCntRunHeads);
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+            V.runs = 1;
+            V.bands = kept;
+            V.band_counter = kCntRunHeads;
+        }
+        if (Z.overlap) {
+            hipLaunchKernelGGL(band_select_kernel, dim3(ctx->n_cu * 2), dim3(256), 0, ctx->stream, V, kept, H->d_count + kCntBandsSelected);
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+            V.bands = kept;
+            V.band_counter = kCntBandsSelected;
+            V.preselected = 1;
+        }
+        if (exact_hits) {
+            // (the resolve kernel reported the hits)
+        } else if (Z.use_wave) {
+            // one verification is a ~1400-step serial chain: enough waves that every band gets its own right away
+            launch_verify_wave(Z.nwn, V, ps->d_peq_bot, ps->max_m, dim3(ctx->n_cu * 16), ctx->stream);
+        } else {
+            const uint32_t nwn = Z.nwn > 8 ? ps->NW : Z.nwn; // power of two beyond 8 words
+            const uint64_t band_expect = ps->band_hint ? 2 * ps->band_hint : Z.band_cap;
+            const uint32_t vgrid = (uint32_t)std::min<uint64_t>((uint64_t)ctx->n_cu * 4, std::max<uint64_t>(ctx->n_cu / 2, (band_expect + 255) / 256));
+            launch_verify(nwn, V, dim3(vgrid), ctx->stream);
+        }
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        if (runs) {
+            hipLaunchKernelGGL(band_release_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, bands, (uint32_t)kCntBandSlots);
+            SPM_HIP_CHECK(ctx, hipGetLastError());
+        }
+        return SPM_OK;
+    }
+};
+
+} // namespace
+
+int run_filter(const scan_args &A, const retry_state &R, filter_result &out)
+{
+    spm_ctx *ctx = A.ctx;
+    spm_hits *H = A.hits;
+    filter_run F{A, R, ctx, A.ps, H, size_filter(*A.ps, A.tune, A.end - A.begin, (uint64_t)ctx->n_cu, H->cap, R)};
+    const filter_sizes &Z = F.Z;
+    SPM_TRY(F.lay_out());
     // runs of adjacent bands (filter.hpp, band_runs_kernel): when earlier scans of this set left a long band list -- a
     // repeat-rich text --, sets without surplus seeds, lane-per-band verification
-    const bool runs = !overlap && !exact_hits && !use_wave && Bw <= 32 && !A.need_seen && A.tune.verify_runs != 0 &&
-                      ps->band_hint >= (uint64_t)std::max(0, A.tune.verify_runs_min_bands);
-    if (runs) {
-        // (heads report most end positions without asking the dedupe set: if a span gives up, the brute-force re-scan
-        // could report them again -- the scan then runs once more without runs, as for exact sets without the set)
-        const_cast<scan_args &>(A).seen_skipped = true;
-        hipLaunchKernelGGL(band_runs_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, d_bands, d_bands + band_cap,
-                           H->d_count + 11);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        V.runs = 1;
-        V.bands = d_bands + band_cap;
-        V.band_counter = 11;
-    }
-    if (overlap) {
-        hipLaunchKernelGGL(band_select_kernel, dim3(ctx->n_cu * 2), dim3(256), 0, ctx->stream, V, d_bands + band_cap,
-                           H->d_count + 10);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        V.bands = d_bands + band_cap;
-        V.band_counter = 10;
-        V.preselected = 1;
-    }
-    if (exact_hits) {
-        // (the resolve kernel reported the hits)
-    } else if (use_wave) {
-        // one verification is a ~1400-step serial chain: enough waves that every band gets its own right away
-        launch_verify_wave(nwn, V, ps->d_peq_bot, ps->max_m, dim3(ctx->n_cu * 16), ctx->stream);
-    } else {
-        if (nwn > 8)
-            nwn = ps->NW; // power of two beyond 8 words
-        const uint64_t band_expect = ps->band_hint ? 2 * ps->band_hint : band_cap;
-        const uint32_t vgrid = (uint32_t)std::min<uint64_t>((uint64_t)ctx->n_cu * 4, std::max<uint64_t>(ctx->n_cu / 2, (band_expect + 255) / 256));
-        launch_verify(nwn, V, dim3(vgrid), ctx->stream);
-    }
-    SPM_HIP_CHECK(ctx, hipGetLastError());
-    if (runs) {
-        hipLaunchKernelGGL(band_release_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, d_bands, 3u);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-    }
+    const bool runs = !Z.overlap && !F.exact_hits && !Z.use_wave && Z.Bw <= 32 && !R.need_seen && A.tune.verify_runs != 0 &&
+                      A.ps->band_hint >= (uint64_t)std::max(0, A.tune.verify_runs_min_bands);
+    // (heads of runs report most end positions without asking the dedupe set: if a span gives up, the brute-force re-scan
+    // could report them again -- the scan then runs once more without runs, as for exact sets without the set)
+    out = {F.seen, (uint32_t)(Z.seen_slots - 1), F.ovf, F.skip_seen || runs, Z.surv_cap, Z.band_cap};
+    SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
+    SPM_TRY(F.launch_passes());
+    SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
+    SPM_TRY(F.launch_resolve());
+    SPM_TRY(F.launch_bands(runs));
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[3], ctx->stream));
-    H->cand_cap = surv_cap;
-    H->band_cap = band_cap;
     return SPM_OK;
 }
 

@@ -38,7 +38,7 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
         SPM_HIP_CHECK(none, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->own_stream = true;
     }
-    SPM_HIP_CHECK(none, hipHostMalloc(&ctx->h_counters, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    SPM_HIP_CHECK(none, hipHostMalloc(&ctx->h_counters, kCntBlock * sizeof(unsigned long long), hipHostMallocDefault));
     // needle sets go up through pinned memory in one stream of chunks (a pageable hipMemcpy per table costs a staging hop
     // and a synchronisation each: 12 of the 16 ms of creating 1024 needles)
     ctx->stage_half = (size_t)8 << 20;
@@ -52,7 +52,7 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
         memset(ctx->h_stage, 0, ctx->stage_half); // (a copy of the size the uploads use: small ones take another path)
         (void)hipMemcpyAsync(ctx->d_scratch, ctx->h_stage, ctx->stage_half, hipMemcpyHostToDevice, ctx->stream);
         (void)hipEventRecord(ctx->stage_ev[0], ctx->stream);
-        (void)hipMemcpyAsync(ctx->h_counters, ctx->d_scratch, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+        (void)hipMemcpyAsync(ctx->h_counters, ctx->d_scratch, kCntBlock * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
         (void)hipStreamSynchronize(ctx->stream);
     } else {
         ctx->d_scratch = nullptr;
@@ -65,15 +65,15 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
         hits_block b;
         b.cap = 1ull << 20;
         bool ok = hipMalloc(&b.d_hits, b.cap * sizeof(spm_hit)) == hipSuccess &&
-                  hipMalloc(&b.d_count, 16 * sizeof(unsigned long long)) == hipSuccess;
+                  hipMalloc(&b.d_count, kCntBlock * sizeof(unsigned long long)) == hipSuccess;
         for (int e = 0; e < 4 && ok; ++e)
             ok = hipEventCreate(&b.ev[e]) == hipSuccess;
         // (what a deferred scan adds: its own pinned counter block -- a pinned allocation costs ~0.1 ms -- and an event)
-        if (ok && hipHostMalloc(reinterpret_cast<void **>(&b.h_c), 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        if (ok && hipHostMalloc(reinterpret_cast<void **>(&b.h_c), kCntBlock * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
             b.h_c = nullptr;
         if (ok && hipEventCreateWithFlags(&b.ev_done, hipEventDisableTiming) != hipSuccess)
             b.ev_done = nullptr;
-        if (ok && hipMemsetAsync(b.d_count, 0, 16 * sizeof(unsigned long long), ctx->stream) == hipSuccess) {
+        if (ok && hipMemsetAsync(b.d_count, 0, kCntBlock * sizeof(unsigned long long), ctx->stream) == hipSuccess) {
             b.zeroed = true;
             ctx->pool.push_back(b);
         } else {

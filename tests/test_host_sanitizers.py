@@ -56,3 +56,8 @@ def test_journal_and_ingestion_under_sanitizers():
     assert "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
     assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
     assert "0 failures" in p.stdout
+    # the scan driver's host-side decisions (tests/cpp/scan_plan_cases: libspm_amd/csrc/scan_plan.hpp alone), same build
+    p = subprocess.run([os.path.join(cpp, "scan_plan_cases_asan")], capture_output=True, text=True, env=_env(), timeout=900)
+    assert "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
+    assert "0 failures" in p.stdout
