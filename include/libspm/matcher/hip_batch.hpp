@@ -111,9 +111,67 @@ public:
         locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
     }
 
-private:
+    // The same calls with a selection of the hits (hip::hit_selection: one per locus, the best strata of every needle):
+    // only the selected hits fire; the order stays per needle, ascending.
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void operator()(haystack_t && haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (_lengths.empty() || ranks.empty())
+            return;
+        spm_ctx * ctx = hip::default_context();
+        spm_text * t = nullptr;
+        if (spm_hip_text_upload(ctx, ranks.data(), ranks.size(), _sigma, &t) != SPM_OK)
+            hip::fatal("spm_hip_text_upload", ctx);
+        hip::text_ptr text{t};
+        run_on(text.get(), 0, ranks.size(), callback, &selection);
+    }
+
     template <typename callback_t>
-    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
+    void operator()(hip::resident_haystack const & haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        if (_lengths.empty() || haystack.empty())
+            return;
+        check_alphabet(haystack);
+        run_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback, &selection);
+    }
+
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void locate(haystack_t && haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (_lengths.empty() || ranks.empty())
+            return;
+        spm_ctx * ctx = hip::default_context();
+        spm_text * t = nullptr;
+        if (spm_hip_text_upload(ctx, ranks.data(), ranks.size(), _sigma, &t) != SPM_OK)
+            hip::fatal("spm_hip_text_upload", ctx);
+        hip::text_ptr text{t};
+        locate_on(text.get(), 0, ranks.size(), callback, &selection);
+    }
+
+    template <typename callback_t>
+    void locate(hip::resident_haystack const & haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        if (_lengths.empty() || haystack.empty())
+            return;
+        check_alphabet(haystack);
+        locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback, &selection);
+    }
+
+private:
+    void check_alphabet(hip::resident_haystack const & haystack) const noexcept
+    {
+        if (haystack.sigma() != _sigma) {
+            std::fprintf(stderr, "libspm (MI355X back-end): the resident haystack's alphabet (%u symbols) is not the needles' (%u)\n",
+                         haystack.sigma(), _sigma);
+            std::abort();
+        }
+    }
+
+    template <typename callback_t>
+    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback,
+                   hip::hit_selection const * selection = nullptr) noexcept
     {
         spm_ctx * ctx = hip::default_context();
         spm_hit const * rec = nullptr;
@@ -124,6 +182,8 @@ private:
                 return spm_hip_scan(ctx, text, base, base + n, _patterns.get(), &o, nullptr, nullptr, h);
             },
             rec, cnt, "spm_hip_scan");
+        if (selection != nullptr)
+            hits = hip::select_hits(ctx, hits.get(), *selection, rec, cnt);
         spm_aln const * al = nullptr;
         std::uint32_t const * ops = nullptr;
         hip::alns_ptr alns = hip::align_hits(ctx, hits.get(), al, cnt, ops);
@@ -135,7 +195,8 @@ private:
     }
 
     template <typename callback_t>
-    void run_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
+    void run_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback,
+                hip::hit_selection const * selection = nullptr) noexcept
     {
         spm_ctx * ctx = hip::default_context();
         spm_hit const * rec = nullptr;
@@ -146,6 +207,8 @@ private:
                 return spm_hip_scan(ctx, text, base, base + n, _patterns.get(), &o, nullptr, nullptr, h);
             },
             rec, cnt, "spm_hip_scan");
+        if (selection != nullptr)
+            hits = hip::select_hits(ctx, hits.get(), *selection, rec, cnt);
         for (std::uint64_t i = 0; i < cnt; ++i) {
             std::size_t const m = _lengths[rec[i].pattern];
             std::size_t const pos = static_cast<std::size_t>(rec[i].pos) - base;

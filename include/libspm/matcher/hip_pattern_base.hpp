@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <concepts>
 #include <cstring>
+#include <optional>
 #include <ranges>
 #include <vector>
 
@@ -123,6 +124,32 @@ public:
     std::size_t begin_offset() const noexcept { return _begin; }
     std::size_t end_offset() const noexcept { return _end; }
 };
+
+// Which hits a call reports (spm_hip_hits_select): one per locus -- within `window` positions only the best hit of a needle
+// survives, no window given: the needle's own max_error_count --, and with `strata` only the hits within that many errors
+// of the needle's best one.  The third argument of operator()(haystack, callback, selection) and locate(...).
+struct hit_selection
+{
+    bool loci{true};
+    std::optional<std::uint32_t> window{};
+    std::optional<std::uint32_t> strata{};
+};
+
+// the selected hits of a completed scan in callback order; failures are fatal like every other call of the mirror
+inline hits_ptr select_hits(spm_ctx * ctx, spm_hits * hits, hit_selection const & sel, spm_hit const *& rec, std::uint64_t & n) noexcept
+{
+    spm_select_opts o{};
+    o.flags = (sel.loci ? SPM_SELECT_LOCI : 0u) | (sel.strata ? SPM_SELECT_BEST : 0u);
+    o.window = sel.window.value_or(SPM_SELECT_WINDOW_K);
+    o.strata = sel.strata.value_or(0u);
+    spm_hits * s = nullptr;
+    if (spm_hip_hits_select(hits, &o, &s) != SPM_OK)
+        fatal("spm_hip_hits_select", ctx);
+    hits_ptr out{s};
+    if (spm_hip_hits_view(s, &rec, &n) != SPM_OK)
+        fatal("spm_hip_hits_view", ctx);
+    return out;
+}
 } // namespace hip
 
 template <typename derived_t>
@@ -236,6 +263,56 @@ public:
         locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback);
     }
 
+    // The same calls with a selection of the hits (hip::hit_selection): only the selected hits fire, in the same order.
+    // Always a fresh matcher, like locate().
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void operator()(haystack_t && haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (ranks.empty() || _needle.empty())
+            return;
+        hip::text_ptr text = upload(ranks.data(), ranks.size());
+        select_on(text.get(), 0, ranks.size(), callback, selection);
+    }
+
+    template <typename callback_t>
+    void operator()(hip::resident_haystack const & haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        if (haystack.empty() || _needle.empty())
+            return;
+        if (haystack.sigma() != _sigma) {
+            std::fprintf(stderr, "libspm (MI355X back-end): the resident haystack's alphabet (%u symbols) is not the needle's (%u)\n",
+                         haystack.sigma(), _sigma);
+            std::abort();
+        }
+        select_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback, selection);
+    }
+
+    template <std::ranges::viewable_range haystack_t, typename callback_t>
+    void locate(haystack_t && haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        static_assert(locatable(), "locate() is not available for this matcher (prefix hits are not aligned)");
+        std::vector<std::uint8_t> const ranks = detail::to_ranks(haystack);
+        if (ranks.empty() || _needle.empty())
+            return;
+        hip::text_ptr text = upload(ranks.data(), ranks.size());
+        locate_on(text.get(), 0, ranks.size(), callback, &selection);
+    }
+
+    template <typename callback_t>
+    void locate(hip::resident_haystack const & haystack, callback_t && callback, hip::hit_selection const & selection) noexcept
+    {
+        static_assert(locatable(), "locate() is not available for this matcher (prefix hits are not aligned)");
+        if (haystack.empty() || _needle.empty())
+            return;
+        if (haystack.sigma() != _sigma) {
+            std::fprintf(stderr, "libspm (MI355X back-end): the resident haystack's alphabet (%u symbols) is not the needle's (%u)\n",
+                         haystack.sigma(), _sigma);
+            std::abort();
+        }
+        locate_on(haystack.text(), haystack.begin_offset(), haystack.size(), callback, &selection);
+    }
+
     bool empty() const noexcept { return _needle.empty(); }
 
 protected:
@@ -269,12 +346,27 @@ protected:
             return true;
     }
 
+    // a fresh scan of text[base, base + n), the selected hits only
     template <typename callback_t>
-    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback) noexcept
+    void select_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback, hip::hit_selection const & selection) noexcept
     {
         spm_hit const * rec = nullptr;
         std::uint64_t cnt = 0;
         hip::hits_ptr hits = scan_text(text, base, base + n, nullptr, nullptr, rec, cnt);
+        hip::hits_ptr kept = hip::select_hits(hip::default_context(), hits.get(), selection, rec, cnt);
+        for (std::uint64_t i = 0; i < cnt; ++i)
+            callback(make_finder(rec[i], n, base));
+    }
+
+    template <typename callback_t>
+    void locate_on(spm_text * text, std::size_t base, std::size_t n, callback_t && callback,
+                   hip::hit_selection const * selection = nullptr) noexcept
+    {
+        spm_hit const * rec = nullptr;
+        std::uint64_t cnt = 0;
+        hip::hits_ptr hits = scan_text(text, base, base + n, nullptr, nullptr, rec, cnt);
+        if (selection != nullptr)
+            hits = hip::select_hits(hip::default_context(), hits.get(), *selection, rec, cnt);
         spm_aln const * al = nullptr;
         std::uint32_t const * ops = nullptr;
         hip::alns_ptr alns = hip::align_hits(hip::default_context(), hits.get(), al, cnt, ops);

@@ -288,6 +288,66 @@ int spm_hip_alns_device(spm_alns *a, const void **records, uint64_t *n, const vo
 int spm_hip_alns_stats(const spm_alns *a, spm_align_stats *out);
 void spm_hip_alns_destroy(spm_alns *a);
 
+/* ---- selection of hits: one record per locus, the best error stratum per needle, on the device -------------------------
+ * A Myers scan reports EVERY end position whose distance is <= k, so one occurrence comes back as a cluster of neighbouring
+ * ends.  A selection turns the records of a scan into a new, smaller spm_hits.  For a record r = (pos, pattern, score):
+ *   SPM_SELECT_LOCI   r is kept iff there is no other record r' of the same pattern -- and, in a segmented scan, of the same
+ *                     segment -- with |pos' - pos| <= w and (score', pos') < (score, pos) lexicographically.
+ *                     w = spm_select_opts.window; SPM_SELECT_WINDOW_K: the needle's own k (0 for exact sets, whose k the
+ *                     matchers ignore); window = 0 keeps everything.  Suppression is strict: a record dominated by a record
+ *                     that is itself dominated is still dropped.  The rule depends only on the SET of records, so the
+ *                     result is bit-identical across engines, runs and arrival orders.  Any two kept records of one pattern
+ *                     (and segment) are more than w apart; of a plateau of equal scores the leftmost survives.
+ *                     Segment of a record, p = pos - pos_offset: Myers seg_off[s] < p <= seg_off[s+1]; exact sets
+ *                     seg_off[s] <= p < seg_off[s+1].
+ *   SPM_SELECT_BEST   applied after LOCI: r is kept iff score <= min_score(pattern) + spm_select_opts.strata, the minimum
+ *                     taken over that pattern's INPUT records, over the whole result (not per segment).  LOCI never removes
+ *                     a pattern's minimum -- the leftmost minimal record inside its window always survives -- so the minimum
+ *                     before LOCI is the minimum after it.
+ *   neither flag      a sorted copy.
+ * The result is a new spm_hits with a hit block of its own.  BOTH its host view and its device view are in (pattern, pos)
+ * order (positions compare as in spm_hip_hits_view) -- the one device view with a defined order.  It copies the source's
+ * alignment context (text, needle set, pos_offset, left context, segment table, statefulness): spm_hip_hits_align accepts
+ * it and refuses exactly what it refuses on the source.  It stays valid after the source is destroyed; text and needle set
+ * must stay alive, as for any hits.  spm_hip_hits_stats on it returns the source's scan statistics with n_hits set to the
+ * selected count.  Every other accessor (view, device, copies, checksum, gatherv) takes it unchanged.
+ * Exact sets and MYERS_PREFIX sets go through the same rule (exact: score 0).  Stateful scans can be selected.  A deferred
+ * source is completed first; an overflowed source returns its SPM_E_OVERFLOW.  SPM_E_UNSUPPORTED, decided on the host before
+ * any launch: more than 2^32 - 1 records; bits(n_patterns) + bits(largest position) above 64.  Unknown flag bits, a nonzero
+ * reserved field or a NULL opts: SPM_E_INVALID.
+ * LOCI and BEST are not shard-local -- a locus can straddle a shard boundary, the best stratum is global -- so under the
+ * sharding of the multi-GPU exchange below the order is: gatherv first, spm_hip_records_select on the root second. */
+#define SPM_SELECT_LOCI 1u
+#define SPM_SELECT_BEST 2u
+#define SPM_SELECT_WINDOW_K 0xFFFFFFFFu
+typedef struct spm_select_opts {
+    uint32_t flags;    /* SPM_SELECT_* */
+    uint32_t window;   /* LOCI: w, or SPM_SELECT_WINDOW_K */
+    uint32_t strata;   /* BEST: strata kept above the needle's minimum (0: the best stratum only) */
+    uint32_t reserved; /* 0 */
+} spm_select_opts;
+typedef struct spm_select_stats {
+    float ms_total;    /* device: order + select (HIP events) */
+    float ms_order;    /* keys + radix sort of (key, index) pairs */
+    float ms_select;   /* selection, scan of the keep flags, compaction */
+    float ms_host;     /* wall clock of the whole call (the first selection of a process loads the unit's code object) */
+    uint64_t n_in;     /* records of the source */
+    uint64_t n_loci;   /* records LOCI kept (n_in without the flag) */
+    uint64_t n_out;    /* records of the result */
+    uint32_t key_bits; /* bits of the sort key the radix passes covered */
+    uint32_t reserved;
+} spm_select_stats;
+int spm_hip_hits_select(spm_hits *hits, const spm_select_opts *opts, spm_hits **out);
+/* The same on a device buffer of n spm_hit records that no spm_hits owns -- what spm_hip_gatherv_hits delivers on the root.
+ * patterns: the needle set the records belong to; may be NULL if window is explicit.  The records are taken as they are:
+ * positions of one buffer share one coordinate system, there is no segment table.  (The host reads the range of the
+ * positions back before it plans the sort: one synchronisation more than spm_hip_hits_select.)  The result carries no
+ * alignment context: spm_hip_hits_align returns SPM_E_INVALID on it, spm_hip_hits_stats zeros but for n_hits. */
+int spm_hip_records_select(spm_ctx *ctx, const void *device_records, uint64_t n, const spm_patterns *patterns,
+                           const spm_select_opts *opts, spm_hits **out);
+/* SPM_E_INVALID on a result no selection made */
+int spm_hip_hits_select_stats(const spm_hits *hits, spm_select_stats *out);
+
 /* ---- journaled-sequence (pan-genome) search, config C5 ----------------------------------------------------
  * The reference only designs the journaled sequence (specs/journaled_sequence_class_diagram.drawio:7-298) and gives the
  * matcher-side hooks a traverser needs (spm::window_size / capture / restore, matcher/concept.hpp:26-161).  The

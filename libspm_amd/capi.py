@@ -153,6 +153,28 @@ class JstAlignStats(C.Structure):
 
 
 ALIGN_BEGIN_ONLY = 1
+
+
+class SelectOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("window", C.c_uint32), ("strata", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_order", C.c_float),
+        ("ms_select", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_in", C.c_uint64),
+        ("n_loci", C.c_uint64),
+        ("n_out", C.c_uint64),
+        ("key_bits", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+SELECT_LOCI, SELECT_BEST = 1, 2
+SELECT_WINDOW_K = 0xFFFFFFFF
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
 
 
@@ -218,6 +240,9 @@ def lib():
         "spm_hip_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_alns_stats": (C.c_int, [vp, C.POINTER(AlignStats)]),
         "spm_hip_alns_destroy": (None, [vp]),
+        "spm_hip_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
+        "spm_hip_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
+        "spm_hip_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
         "spm_hip_synth_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                                C.c_uint32, u8p]),
         "spm_hip_synth_repeat_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -274,6 +299,7 @@ EXPORTS = [
     "spm_hip_patterns_state_init", "spm_hip_scan", "spm_hip_scan_segments", "spm_hip_hits_view", "spm_hip_hits_device",
     "spm_hip_hits_copy_device", "spm_hip_hits_copy_fused", "spm_hip_hits_copy_fused_device", "spm_hip_hits_stats", "spm_hip_hits_checksum", "spm_hip_hits_destroy",
     "spm_hip_hits_align", "spm_hip_alns_view", "spm_hip_alns_device", "spm_hip_alns_stats", "spm_hip_alns_destroy",
+    "spm_hip_hits_select", "spm_hip_records_select", "spm_hip_hits_select_stats",
     "spm_hip_synth_pattern",
     "spm_hip_synth_repeat_pattern", "spm_hip_synth_repeat_text", "spm_hip_mix64", "spm_hip_host_selftest", "spm_hip_version",
     "spm_hip_jst_create", "spm_hip_jst_destroy", "spm_hip_jst_haplotype_length", "spm_hip_jst_extract",

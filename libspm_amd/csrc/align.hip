@@ -301,6 +301,10 @@ extern "C" int spm_hip_hits_align(spm_hits *h, uint32_t flags, spm_alns **out)
     spm_ctx *ctx = h->ctx;
     const auto t_call = clk::now();
     const spm_patterns *ps = h->al_patterns;
+    if (h->sel_records) {
+        SPM_SET_ERR(ctx, "spm_hip_hits_align: a selection of raw records (spm_hip_records_select) carries no text to align against");
+        return SPM_E_INVALID;
+    }
     if (!ps || !h->al_text) {
         SPM_SET_ERR(ctx, "spm_hip_hits_align: these hits do not come from spm_hip_scan / spm_hip_scan_segments");
         return SPM_E_UNSUPPORTED;

@@ -108,6 +108,12 @@ struct spm_hits : hits_block // (its buffers, counters and events: taken from th
     bool al_stateful = false;       // state_in != NULL
     bool al_device_segs = false;    // segment table only on the device (journaled-sequence search)
     std::vector<uint64_t> al_segs;  // segmented scans: the segment table (n_segments + 1 offsets)
+    // a result made by spm_hip_hits_select / spm_hip_records_select (select.hip): ev[0..2] time its order and select steps
+    bool selected = false;
+    bool sel_records = false;       // ... out of a raw record buffer: no alignment context
+    bool sel_timed = false;         // sel.ms_* still have to be read off the events
+    uint64_t sel_n_patterns = 0, sel_bias = 0, sel_max_rel = 0; // sel_records: what the buffer's range was found to be
+    spm_select_stats sel{};
 };
 
 // A deferred scan that had to be repeated: `h` takes over the buffers and the outcome of the repeated scan, which gets

@@ -1,0 +1,232 @@
+// select.hpp -- the kernels of hit selection (spm_hip_hits_select / spm_hip_records_select; contract in spm_hip.h, scheme in
+// DESIGN.md 4.7).  gfx950.  The records are ordered by a radix sort of (key, index) pairs, key = pattern << pos_bits |
+// (pos - bias); then
+//   select_loci_kernel     one lane per sorted record: is a record of the same pattern (and segment) within the window
+//                          better?  Neighbours inside the window are contiguous in sorted order, so a tile of keys and
+//                          scores with a halo on either side is staged in LDS; also the per-pattern score minima;
+//   select_compact_kernel  the stratum test, and the stable compaction of the kept records into the new hit block through an
+//                          exclusive scan of the keep flags (the order IS the contract: no slot atomics).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "select_plan.hpp"
+
+namespace spm_hip
+{
+
+struct select_params
+{
+    const spm_hit *recs = nullptr;            // the source's records, in their arrival order
+    unsigned long long *keys = nullptr;       // [n] sorted keys
+    uint32_t *idx = nullptr;                  // [n] record index of sorted entry i
+    uint32_t n = 0;
+    uint32_t pos_bits = 0;                    // key >> pos_bits = pattern (pos_bits == 64: one pattern, index 0)
+    unsigned long long pos_mask = 0;          // key & pos_mask = pos - bias
+    unsigned long long bias = 0;
+    uint32_t loci = 0;
+    uint32_t best = 0;
+    uint32_t window = 0;                      // SPM_SELECT_WINDOW_K: k_tab[pattern]
+    const int32_t *k_tab = nullptr;
+    uint32_t halo = 0;                        // <= kSelHaloCap
+    const unsigned long long *segs = nullptr; // segmented sources: n_segs + 1 ascending offsets, text coordinates
+    unsigned long long n_segs = 0;
+    unsigned long long seg_bias = 0;          // (pos - bias) + seg_bias = pos - pos_offset
+    uint32_t seg_myers = 0;                   // a record at p belongs to the segment of symbol p - 1 (Myers: pos is an end)
+    long long strata = 0;
+    // out
+    uint8_t *keep = nullptr;                  // [n] LOCI's verdict
+    int32_t *score = nullptr;                 // [n] scores in sorted order
+    int32_t *pat_min = nullptr;               // [n_patterns] minimal score of every pattern (BEST only; preset to INT_MAX)
+    unsigned long long *counts = nullptr;     // [0] records LOCI kept, [1] records of the result
+};
+
+__device__ __forceinline__ uint32_t sel_pattern(const select_params &P, unsigned long long key)
+{
+    return P.pos_bits < 64 ? (uint32_t)(key >> P.pos_bits) : 0u;
+}
+
+// one lane per record: key and index, ready for the sort
+__global__ __launch_bounds__(256) void select_keys_kernel(const spm_hit *__restrict__ recs, unsigned long long *__restrict__ keys,
+                                                            uint32_t *__restrict__ idx, uint32_t n, uint32_t pos_bits,
+                                                            unsigned long long bias)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint4 r = reinterpret_cast<const uint4 *>(recs)[i];
+    const unsigned long long pos = ((unsigned long long)r.y << 32 | r.x) - bias;
+    keys[i] = (pos_bits < 64 ? (unsigned long long)r.z << pos_bits : 0ull) | pos;
+    idx[i] = i;
+}
+
+// spm_hip_records_select: the range of what a raw buffer holds -- out[0] = min pos, out[1] = max pos (both as signed
+// values, sign bit flipped so that unsigned atomics order them), out[2] = max pattern
+__global__ __launch_bounds__(256) void select_range_kernel(const spm_hit *__restrict__ recs, uint32_t n,
+                                                             unsigned long long *__restrict__ out)
+{
+    constexpr unsigned long long kSign = 1ull << 63;
+    unsigned long long lo = ~0ull, hi = 0, pat = 0;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint4 r = reinterpret_cast<const uint4 *>(recs)[i];
+        const unsigned long long pos = ((unsigned long long)r.y << 32 | r.x) ^ kSign;
+        lo = pos < lo ? pos : lo;
+        hi = pos > hi ? pos : hi;
+        pat = r.z > pat ? r.z : pat;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d), p2 = __shfl_xor(pat, d);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+        pat = p2 > pat ? p2 : pat;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&out[0], lo);
+        atomicMax(&out[1], hi);
+        atomicMax(&out[2], pat);
+    }
+}
+
+// One lane per sorted record.  LDS holds the keys and scores of the tile and of `halo` records on either side; a lane whose
+// window reaches further reads the rest from global memory (windows above kSelHaloCap, i.e. needles with k > 32).
+__global__ __launch_bounds__(kSelTile) void select_loci_kernel(const select_params P)
+{
+    __shared__ unsigned long long s_key[kSelTile + 2 * kSelHaloCap];
+    __shared__ int32_t s_score[kSelTile + 2 * kSelHaloCap];
+    const uint32_t H = P.halo;
+    const long long tile0 = (long long)blockIdx.x * kSelTile;
+    const long long lds0 = tile0 - H; // sorted index of s_key[0]
+    const long long n = P.n;
+    for (uint32_t t = threadIdx.x; t < kSelTile + 2 * H; t += kSelTile) {
+        const long long j = lds0 + t;
+        if (j >= 0 && j < n) {
+            s_key[t] = P.keys[j];
+            s_score[t] = P.recs[P.idx[j]].score;
+        }
+    }
+    __syncthreads();
+
+    const long long i = tile0 + threadIdx.x;
+    const bool valid = i < n;
+    const long long lds_end = lds0 + kSelTile + 2 * H;
+    uint32_t pat = 0xFFFFFFFFu;
+    int32_t sc = 0x7FFFFFFF;
+    bool kept = false;
+    if (valid) {
+        const unsigned long long key = s_key[H + threadIdx.x];
+        sc = s_score[H + threadIdx.x];
+        pat = sel_pattern(P, key);
+        P.score[i] = sc;
+        kept = true;
+        const unsigned long long w = !P.loci ? 0ull : P.window == SPM_SELECT_WINDOW_K ? (unsigned long long)max(P.k_tab[pat], 0) : P.window;
+        if (w) {
+            const unsigned long long rel = key & P.pos_mask;
+            // the record's segment, as the closed range of positions (pos - pos_offset) its records can have
+            unsigned long long p_lo = 0, p_hi = ~0ull;
+            if (P.segs) {
+                const unsigned long long p = rel + P.seg_bias;
+                const unsigned long long sym = P.seg_myers && p ? p - 1 : p; // the symbol that decides the segment
+                unsigned long long a = 0, b = P.n_segs;                       // last s with segs[s] <= sym (0 if none)
+                while (b - a > 1) {
+                    const unsigned long long mid = a + (b - a) / 2;
+                    if (P.segs[mid] <= sym)
+                        a = mid;
+                    else
+                        b = mid;
+                }
+                // (positions outside the table count to the first / last segment)
+                p_lo = a == 0 ? 0ull : P.segs[a] + P.seg_myers;
+                p_hi = a + 1 == P.n_segs ? ~0ull : P.segs[a + 1] - 1 + P.seg_myers;
+            }
+            // to the left: a record there is better when its score is not larger (its position is smaller)
+            for (long long j = i - 1; j >= 0; --j) {
+                const bool in_lds = j >= lds0;
+                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
+                if (sel_pattern(P, kj) != pat)
+                    break;
+                const unsigned long long rj = kj & P.pos_mask;
+                if (rel - rj > w)
+                    break;
+                const unsigned long long pj = rj + P.seg_bias;
+                if (pj < p_lo || pj > p_hi)
+                    break; // (segments are ranges of positions: nothing further left is in this one)
+                const int32_t sj = in_lds ? s_score[j - lds0] : P.recs[P.idx[j]].score;
+                if (sj < sc || (sj == sc && rj < rel)) {
+                    kept = false;
+                    break;
+                }
+            }
+            // to the right: only a strictly smaller score is better
+            for (long long j = i + 1; kept && j < n; ++j) {
+                const bool in_lds = j < lds_end;
+                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
+                if (sel_pattern(P, kj) != pat)
+                    break;
+                const unsigned long long rj = kj & P.pos_mask;
+                if (rj - rel > w)
+                    break;
+                const unsigned long long pj = rj + P.seg_bias;
+                if (pj < p_lo || pj > p_hi)
+                    break;
+                const int32_t sj = in_lds ? s_score[j - lds0] : P.recs[P.idx[j]].score;
+                if (sj < sc)
+                    kept = false;
+            }
+        }
+        P.keep[i] = kept ? 1 : 0;
+    }
+    // records LOCI kept: one atomic per wave
+    const unsigned long long kept_mask = __ballot(kept);
+    if ((threadIdx.x & 63) == 0 && kept_mask)
+        atomicAdd(&P.counts[0], (unsigned long long)__popcll(kept_mask));
+    // per-pattern minima: lanes of one pattern are contiguous (sorted input), so a segmented min-scan over the wave leaves
+    // the minimum of every run in its last lane, which issues the one atomicMin of that wave and pattern
+    if (P.best) {
+        const uint32_t lane = threadIdx.x & 63;
+        int32_t m = sc;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int32_t m2 = __shfl_up(m, d);
+            const uint32_t p2 = __shfl_up(pat, d);
+            if (lane >= (uint32_t)d && p2 == pat)
+                m = m2 < m ? m2 : m;
+        }
+        const uint32_t p_next = __shfl_down(pat, 1);
+        if (valid && (lane == 63 || p_next != pat || i + 1 >= n))
+            atomicMin(&P.pat_min[pat], m);
+    }
+}
+
+// what the exclusive scan adds up and the compaction tests again: LOCI's verdict and the stratum test
+__device__ __forceinline__ uint32_t sel_final_flag(const select_params &P, uint32_t i)
+{
+    uint32_t f = P.keep[i];
+    if (f && P.best)
+        f = (long long)P.score[i] <= (long long)P.pat_min[sel_pattern(P, P.keys[i])] + P.strata ? 1u : 0u;
+    return f;
+}
+struct sel_flag_op
+{
+    select_params P;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return sel_final_flag(P, i); }
+};
+
+// offs: exclusive scan of the final flags.  A kept record travels as one 16-byte load and one 16-byte store.
+__global__ __launch_bounds__(256) void select_compact_kernel(const select_params P, const uint32_t *__restrict__ offs,
+                                                               spm_hit *__restrict__ out,
+                                                               unsigned long long *__restrict__ hit_counter)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n)
+        return;
+    const uint32_t f = sel_final_flag(P, i);
+    const uint32_t o = offs[i];
+    if (f)
+        reinterpret_cast<uint4 *>(out)[o] = reinterpret_cast<const uint4 *>(P.recs)[P.idx[i]];
+    if (i == P.n - 1) {
+        P.counts[1] = (unsigned long long)o + f;
+        *hit_counter = (unsigned long long)o + f;
+    }
+}
+
+} // namespace spm_hip

@@ -1,0 +1,95 @@
+// select_plan.hpp -- what one hit selection (spm_hip_hits_select / spm_hip_records_select) decides on the host, as pure
+// functions (plain C++17, no HIP: select.hip and tests/cpp/select_plan_cases.cpp both compile it): the window a needle
+// gets, the bit budget of the sort key, the halo the selection kernel stages in LDS, and the two refusals that are made
+// before anything is launched.  select.hip keeps the HIP calls and acts on the answers.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+#include "../../include/spm_hip.h"
+
+namespace spm_hip
+{
+
+constexpr uint32_t kSelTile = 256;    // records per workgroup of select_loci_kernel (one lane each)
+constexpr uint32_t kSelHaloCap = 32;  // records staged in LDS on either side of a tile, at most
+
+// bits needed to hold v: 0 for 0, 1 for 1, 2 for 2..3, ... 64 for v >= 2^63
+inline uint32_t bits_for(uint64_t v)
+{
+    uint32_t b = 0;
+    while (v) {
+        ++b;
+        v >>= 1;
+    }
+    return b;
+}
+
+// The window of one needle.  SPM_SELECT_WINDOW_K: the needle's own k -- 0 for exact sets, whose k the matchers ignore.
+inline uint32_t select_window(uint32_t opt_window, bool myers_set, uint32_t k)
+{
+    if (opt_window != SPM_SELECT_WINDOW_K)
+        return opt_window;
+    return myers_set ? k : 0u;
+}
+
+// Records of one pattern have distinct positions, so at most `window` neighbours on either side lie inside the window:
+// that many are staged beside the tile, up to the cap (beyond it the kernel reads global memory).
+inline uint32_t select_halo(uint32_t max_window, uint32_t cap = kSelHaloCap) { return std::min(max_window, cap); }
+
+struct select_plan
+{
+    int status = SPM_OK;       // SPM_E_UNSUPPORTED / SPM_E_INVALID: refused, `why` says it
+    const char *why = "";
+    uint32_t pat_bits = 0;     // key = pattern << pos_bits | (pos - bias)
+    uint32_t pos_bits = 0;
+    uint32_t key_bits = 0;     // the radix sort's end_bit
+    uint32_t window = 0;       // the one window of every needle, or SPM_SELECT_WINDOW_K: read k per needle on the device
+    uint32_t max_window = 0;   // the largest window any needle gets
+    uint32_t halo = 0;
+    bool loci = false, best = false;
+};
+
+// n_records: records to select from; n_patterns: patterns the records can name (>= 1); max_rel_pos: the largest
+// pos - bias a record can hold; myers_set / have_k / max_k: the needle set (have_k false: no set was given).
+inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uint64_t n_patterns, uint64_t max_rel_pos,
+                               bool have_k, bool myers_set, uint32_t max_k)
+{
+    select_plan P;
+    if ((o.flags & ~(SPM_SELECT_LOCI | SPM_SELECT_BEST)) || o.reserved) {
+        P.status = SPM_E_INVALID;
+        P.why = "unknown flag bits, or a nonzero reserved field";
+        return P;
+    }
+    P.loci = (o.flags & SPM_SELECT_LOCI) != 0;
+    P.best = (o.flags & SPM_SELECT_BEST) != 0;
+    if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k) {
+        P.status = SPM_E_INVALID;
+        P.why = "SPM_SELECT_WINDOW_K needs the needle set";
+        return P;
+    }
+    if (n_records > 0xFFFFFFFFull) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "more than 2^32 - 1 records";
+        return P;
+    }
+    P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
+    P.pos_bits = bits_for(max_rel_pos);
+    P.key_bits = P.pat_bits + P.pos_bits;
+    if (P.key_bits > 64) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "pattern index and position do not fit one 64-bit sort key";
+        return P;
+    }
+    P.key_bits = std::max(P.key_bits, 1u);
+    if (P.loci) {
+        const bool per_needle = o.window == SPM_SELECT_WINDOW_K && myers_set && max_k > 0;
+        P.window = per_needle ? SPM_SELECT_WINDOW_K : select_window(o.window, myers_set, max_k);
+        P.max_window = select_window(o.window, myers_set, max_k);
+    }
+    P.halo = select_halo(P.max_window);
+    return P;
+}
+
+} // namespace spm_hip

@@ -225,6 +225,20 @@ class Hits:
                self.ctx._h)
         return Alignments(self.ctx, a)
 
+    def select(self, loci: bool = True, window: int | None = None, best: int | None = None) -> "Hits":
+        """A new, smaller Hits (spm_hip_hits_select): one record per locus (loci; window=None: every needle's own k) and,
+        with best=s, only the records within s errors of their needle's minimum.  Host AND device view of the result are
+        sorted by (pattern, pos); it stays valid after this object is closed."""
+        opts = _select_opts(loci, window, best)
+        h = C.c_void_p()
+        _check(capi.lib().spm_hip_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
+        return Hits(self.ctx, h, self._text, self._pats)
+
+    def select_stats(self) -> capi.SelectStats:
+        s = capi.SelectStats()
+        _check(capi.lib().spm_hip_hits_select_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
     def stats(self) -> capi.ScanStats:
         s = capi.ScanStats()
         _check(capi.lib().spm_hip_hits_stats(self._h, C.byref(s)), self.ctx._h)
@@ -329,6 +343,23 @@ def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | 
                                    st_out.ctypes.data if st_out is not None else None, C.byref(h)), ctx._h)
     hits = Hits(ctx, h, text, pats)
     return (hits, st_out) if want_state else hits
+
+
+def _select_opts(loci, window, best) -> capi.SelectOpts:
+    flags = (capi.SELECT_LOCI if loci else 0) | (capi.SELECT_BEST if best is not None else 0)
+    return capi.SelectOpts(flags=flags, window=capi.SELECT_WINDOW_K if window is None else int(window),
+                           strata=0 if best is None else int(best), reserved=0)
+
+
+def select_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet | None = None, *, loci: bool = True,
+                   window: int | None = None, best: int | None = None) -> Hits:
+    """Hits.select() on a device buffer of n HIT_DTYPE records that no Hits owns -- what a gatherv delivers on the root
+    (spm_hip_records_select).  pats may be None when window is explicit.  The result cannot be aligned."""
+    opts = _select_opts(loci, window, best)
+    h = C.c_void_p()
+    _check(capi.lib().spm_hip_records_select(ctx._h, C.c_void_p(device_ptr), n, pats._h if pats is not None else None,
+                                             C.byref(opts), C.byref(h)), ctx._h)
+    return Hits(ctx, h, None, pats)
 
 
 def scan_segments(ctx: Context, text: Text, pats: PatternSet, seg_offsets, *, engine: int = capi.ENGINE_AUTO,
