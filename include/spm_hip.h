@@ -114,8 +114,10 @@ typedef struct spm_scan_stats {
                              k >= 8), else the candidates whose whole seed matches the text */
     uint32_t fallback_spans;   /* filter engine: spans of the text whose seed hits exceeded their budget (repeat-rich
                                   stretches); only those were scanned again by the brute-force kernel */
-    uint32_t reserved;
-    uint64_t fallback_symbols; /* ... and how many text symbols that re-scan covered */
+    uint32_t span_symbols;     /* filter engine: text symbols per span of the streaming launch of the last pass (the unit
+                                  the waves draw work in: span borders are where a window's symbols come from two
+                                  dequeues); 0 for the brute engine */
+    uint64_t fallback_symbols; /* how many text symbols the re-scan of the fallback_spans covered */
 } spm_scan_stats;
 
 /* ---- context -------------------------------------------------------------------------------------- */

@@ -51,7 +51,7 @@ class ScanStats(C.Structure):
         ("main_launches", C.c_uint32),
         ("n_bands", C.c_uint32),
         ("fallback_spans", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("span_symbols", C.c_uint32),
         ("fallback_symbols", C.c_uint64),
     ]
 

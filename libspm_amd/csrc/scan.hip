@@ -344,6 +344,7 @@ struct scan_call // one scan_impl call: the request, what was decided about it, 
     int brute_engine()
     {
         H->stats.engine_used = SPM_ENGINE_BRUTE;
+        H->stats.span_symbols = 0; // (no streaming launch, or one whose scan is being replaced)
         SPM_TRY(state_open());
         SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
         const uint64_t range = end - begin;

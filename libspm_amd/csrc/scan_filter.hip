@@ -277,35 +277,27 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
             const uint32_t grid = ctx->n_cu * wg_per_cu;
             const uint64_t n_waves = (uint64_t)grid * (threads / 64);
             const uint64_t n_chunks = (P.hi - (P.lo & ~1023ull) + 1023) / 1024;
-            uint64_t span = n_chunks / (n_waves * 32) + 1;
-            // small texts: at least 64 KiB per dequeue as long as every wave still gets ~4 spans (a 1 GiB text ran 14 % faster
-            // with 64-chunk spans than with the 24 the rule above gives: fewer dequeue rounds, each a workgroup barrier)
-            if (span < 64)
-                span = std::max<uint64_t>(span, std::min<uint64_t>(64, n_chunks / (n_waves * 4) + 1));
-            span = std::min<uint64_t>(std::max<uint64_t>(span, 8), 4096);
-            span = (span + 7) & ~7ull; // whole groups of chunks
-            P.span_chunks = (uint32_t)span;
+            const span_plan span = plan_span(n_chunks, n_waves, 1024);
+            P.span_chunks = span.span_chunks;
             P.span_unit = 1024;
             // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
             // costs the verification about what the re-scan would
             const int sb = A.tune.span_budget;
-            P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, span * 1024 / 4);
-            // span dequeue: per wave while the dequeue rate stays far below what one atomic word sustains (~88/us, i.e.
-            // spans >= 192 KiB at 7 TB/s), per workgroup otherwise (measured: C3 2.52 vs 2.59 ms, C2 0.88 vs 0.20 ms)
-            P.dynamic = span >= 192 ? 1u : 2u;
+            P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, (uint64_t)span.span_chunks * 1024 / 4);
+            P.dynamic = span.dynamic;
             P.hash_variant = F.hash_variant;
+            H->stats.span_symbols = P.span_chunks * P.span_unit;
             if (use_packed) {
                 // p-chunks of 4096 symbols: recompute the span geometry in those units
                 filter_params Q = P;
                 const uint64_t n_pchunks = (Q.hi - (Q.lo & ~4095ull) + 4095) / 4096;
-                uint64_t pspan = n_pchunks / (n_waves * 8) + 1;
-                pspan = std::min<uint64_t>(std::max<uint64_t>(pspan, 4), 4096);
-                pspan = (pspan + 3) & ~3ull;
-                Q.span_chunks = (uint32_t)pspan;
+                const span_plan pspan = plan_span(n_pchunks, n_waves, 4096);
+                Q.span_chunks = pspan.span_chunks;
                 Q.span_unit = 4096;
                 if (sb <= 0)
-                    Q.span_budget = (uint32_t)std::max<uint64_t>(256, pspan * 4096 / 4);
-                Q.dynamic = pspan >= 48 ? 1u : 2u;
+                    Q.span_budget = (uint32_t)std::max<uint64_t>(256, (uint64_t)pspan.span_chunks * 4096 / 4);
+                Q.dynamic = pspan.dynamic;
+                H->stats.span_symbols = Q.span_chunks * Q.span_unit;
                 const packed_kernel k = select_packed_kernel(F.stride, km);
                 if (!k) {
                     SPM_SET_ERR(ctx, "internal: no packed filter kernel for stride %u, key length %u", F.stride, F.key_len);

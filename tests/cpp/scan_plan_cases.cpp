@@ -276,8 +276,43 @@ static void sizing_cases()
     EXPECT_TRUE(Z.use_wave && Z.overlap && Z.nwn == 32 && Z.Bw == 260 && Z.max_span == 259 + 65);
 }
 
+// the span of a streaming pass: values worked out by hand from the rule (256 CUs; 512-thread workgroups, two per CU:
+// 4096 waves; 1024-thread workgroups, two per CU: 8192 waves)
+static void span_cases()
+{
+    auto is = [](span_plan s, uint32_t chunks, uint32_t dynamic) { return s.span_chunks == chunks && s.dynamic == dynamic; };
+    // a small text, 64 Ki symbols: 64 / (4096 * 32) + 1 = 1; the 64 KiB rule offers min(64, 64 / 16384 + 1) = 1; minimum 8
+    EXPECT_TRUE(is(plan_span(64, 4096, 1024), 8, 2));
+    EXPECT_TRUE(is(plan_span(0, 4096, 1024), 8, 2) && is(plan_span(1, 1, 1024), 8, 2));
+    // ... its 16 p-chunks: 16 / (8192 * 8) + 1 = 1; minimum 4
+    EXPECT_TRUE(is(plan_span(16, 8192, 4096), 4, 2));
+    // 4 Mi symbols: 4096 / 131072 + 1 = 1 -> max(1, min(64, 4096 / 16384 + 1 = 1)) = 1 -> 8
+    EXPECT_TRUE(is(plan_span(4096, 4096, 1024), 8, 2));
+    // 256 Mi symbols: 262144 / 131072 + 1 = 3 -> max(3, min(64, 262144 / 16384 + 1 = 17)) = 17 -> rounded up to 24
+    EXPECT_TRUE(is(plan_span(262144, 4096, 1024), 24, 2));
+    // 1 GiB: 2^20 / 2^17 + 1 = 9 -> max(9, min(64, 2^20 / 2^14 + 1 = 65)) = 64
+    EXPECT_TRUE(is(plan_span(1u << 20, 4096, 1024), 64, 2));
+    // ... in p-chunks on 8192 waves: 2^18 / 2^16 + 1 = 5 -> 8
+    EXPECT_TRUE(is(plan_span(1u << 18, 8192, 4096), 8, 2));
+    // 16 GiB: 2^24 / 2^17 + 1 = 129 (>= 64: the small-text rule is out) -> 136; below 192: per workgroup
+    EXPECT_TRUE(is(plan_span(1u << 24, 4096, 1024), 136, 2));
+    // ... on 8192 waves: 2^24 / 2^18 + 1 = 65 -> 72;  packed: 2^22 / 2^16 + 1 = 65 -> 68, >= 48: per wave
+    EXPECT_TRUE(is(plan_span(1u << 24, 8192, 1024), 72, 2));
+    EXPECT_TRUE(is(plan_span(1u << 22, 8192, 4096), 68, 1));
+    // the dequeue threshold: 191 * 2^17 chunks give 192 (per wave), one chunk less 191 -> 192 as well
+    EXPECT_TRUE(is(plan_span(191ull << 17, 4096, 1024), 192, 1) && is(plan_span((191ull << 17) - 1, 4096, 1024), 192, 1));
+    EXPECT_TRUE(is(plan_span(183ull << 17, 4096, 1024), 184, 2)); // 183 + 1 = 184, a multiple of 8: per workgroup
+    EXPECT_TRUE(is(plan_span(47ull << 16, 8192, 4096), 48, 1) && is(plan_span(43ull << 16, 8192, 4096), 44, 2));
+    // the caps: 4096 chunks (and p-chunks) per span
+    EXPECT_TRUE(is(plan_span(1ull << 40, 4096, 1024), 4096, 1) && is(plan_span(1ull << 40, 8192, 4096), 4096, 1));
+    // few waves (a small device): 64 chunks on 64 waves: 64 / 2048 + 1 = 1 -> max(1, min(64, 64 / 256 + 1)) = 1 -> 8;
+    // 2^16 chunks: 2^16 / 2^11 + 1 = 33 -> max(33, min(64, 2^16 / 2^8 + 1)) = 64
+    EXPECT_TRUE(is(plan_span(64, 64, 1024), 8, 2) && is(plan_span(1u << 16, 64, 1024), 64, 2));
+}
+
 int main()
 {
+    span_cases();
     tiler_cases();
     policy_cases();
     clean_cases();
