@@ -21,6 +21,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <string_view>
@@ -31,6 +32,7 @@
 #include <libspm/jst/io.hpp>
 #include <libspm/jst/journaled_sequence.hpp>
 #include <libspm/matcher/alignment.hpp>
+#include <libspm/matcher/hip_pattern_base.hpp>
 
 namespace spm
 {
@@ -297,6 +299,89 @@ public:
         if (device_ready())
             return search_device(needles, window, block, stats);
         return search_host(needles, window, needle_len, reports_begin, block, stats);
+    }
+
+    // The same search with a selection of the hits (spm_hip_jst_hits_select): one hit per locus of every haplotype -- the locus
+    // is (haplotype, needle) --, with `strata` only the hits within that many errors of the best one of their (haplotype,
+    // needle), with `across` of their needle on all haplotypes.  Restricted to one haplotype these are the hits
+    // batch_matcher's operator()(haystack, callback, selection) fires on that haplotype spelled out.  The order is search's.
+    // Trees the device path does not take go through search_host and select_host; both routes return the same vector.
+    std::vector<jst_hit> search(spm_patterns * needles, std::size_t window, std::vector<std::uint32_t> const & needle_len,
+                                bool reports_begin, hip::hit_selection const & selection, std::size_t block = 0,
+                                jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return search_device(needles, window, selection, block, stats);
+        return select_host(search_host(needles, window, needle_len, reports_begin, block, stats), needles, needle_len,
+                           reports_begin, selection);
+    }
+
+    std::vector<jst_hit> search_device(spm_patterns * needles, std::size_t window, hip::hit_selection const & selection,
+                                       std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, 0, stats);
+        spm_select_opts o{};
+        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
+                  (selection.across ? SPM_SELECT_ACROSS : 0u);
+        o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
+        o.strata = selection.strata.value_or(0u);
+        spm_jst_hits * sel = nullptr;
+        if (spm_hip_jst_hits_select(hh, &o, &sel) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_select", ctx);
+        spm_hip_jst_hits_destroy(hh); // (the selection has a buffer of its own)
+        spm_jst_hit const * rec = nullptr;
+        std::uint64_t n = 0;
+        if (spm_hip_jst_hits_view(sel, &rec, &n) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_view", ctx);
+        std::vector<jst_hit> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            out.push_back({rec[i].haplotype, rec[i].pos, rec[i].pattern, rec[i].score});
+        spm_hip_jst_hits_destroy(sel);
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+
+    // The rule of spm_hip_jst_hits_select written out on the host, for the hits of search_host.
+    static std::vector<jst_hit> select_host(std::vector<jst_hit> hits, spm_patterns * needles,
+                                            std::vector<std::uint32_t> const & needle_len, bool reports_begin,
+                                            hip::hit_selection const & selection)
+    {
+        if (selection.across && !selection.strata)
+            hip::fatal("journaled_sequence_tree::search (hit_selection::across needs strata)", hip::default_context());
+        std::sort(hits.begin(), hits.end(), [](jst_hit const & a, jst_hit const & b) {
+            return std::tuple{a.haplotype, a.needle, a.position} < std::tuple{b.haplotype, b.needle, b.position};
+        });
+        auto const same = [&](std::size_t i, std::size_t j) {
+            return hits[i].haplotype == hits[j].haplotype && hits[i].needle == hits[j].needle;
+        };
+        std::vector<std::int64_t> best(selection.across ? needle_len.size() : hits.size(), INT64_MAX); // per needle / group head
+        std::vector<std::size_t> slot(hits.size());
+        for (std::size_t i = 0; i < hits.size(); ++i) {
+            slot[i] = selection.across ? hits[i].needle : i && same(i, i - 1) ? slot[i - 1] : i;
+            best[slot[i]] = std::min<std::int64_t>(best[slot[i]], hits[i].errors);
+        }
+        std::vector<jst_hit> out;
+        for (std::size_t i = 0; i < hits.size(); ++i) {
+            std::uint32_t const p = hits[i].needle;
+            // the needle's own k: what its window exceeds its length by (exact matchers: 0)
+            std::uint64_t const w = !selection.loci     ? 0
+                                    : selection.window ? *selection.window
+                                    : reports_begin    ? 0
+                                                       : spm_hip_patterns_window_size(needles, p) - needle_len[p];
+            bool keep = true;
+            for (std::size_t j = i; keep && j-- > 0 && same(i, j) && hits[i].position - hits[j].position <= w;)
+                keep = hits[j].errors > hits[i].errors; // to the left: a tie is better
+            for (std::size_t j = i + 1; keep && j < hits.size() && same(i, j) && hits[j].position - hits[i].position <= w; ++j)
+                keep = hits[j].errors >= hits[i].errors;
+            if (keep && selection.strata)
+                keep = hits[i].errors <= best[slot[i]] + static_cast<std::int64_t>(*selection.strata);
+            if (keep)
+                out.push_back(hits[i]);
+        }
+        std::sort(out.begin(), out.end());
+        return out;
     }
 
     // true once the tree is resident on the device (first call uploads it)

@@ -128,11 +128,14 @@ public:
 // Which hits a call reports (spm_hip_hits_select): one per locus -- within `window` positions only the best hit of a needle
 // survives, no window given: the needle's own max_error_count --, and with `strata` only the hits within that many errors
 // of the needle's best one.  The third argument of operator()(haystack, callback, selection) and locate(...).
+// `across` belongs to journaled_sequence_tree::search alone (SPM_SELECT_ACROSS: the best one on ALL haplotypes, needs
+// `strata`); a matcher over one haystack has nothing to take a minimum across, ignores it and never forwards it.
 struct hit_selection
 {
     bool loci{true};
     std::optional<std::uint32_t> window{};
     std::optional<std::uint32_t> strata{};
+    bool across{false};
 };
 
 // the selected hits of a completed scan in callback order; failures are fatal like every other call of the mirror

@@ -476,6 +476,46 @@ int spm_hip_jst_alns_device(spm_jst_alns *a, const void **records, uint64_t *n, 
 int spm_hip_jst_alns_stats(const spm_jst_alns *a, spm_jst_align_stats *out);
 void spm_hip_jst_alns_destroy(spm_jst_alns *a);
 
+/* ---- selection of pan-genome hits: one record per haplotype locus, the best stratum per (haplotype, needle) -------------
+ * spm_hip_hits_select for the 24-byte records of spm_hip_jst_search.  The locus is (haplotype, pattern).  For a record
+ * r = (haplotype, pos, pattern, score):
+ *   SPM_SELECT_LOCI    r is dropped iff another record r' has the same haplotype and the same pattern, |pos' - pos| <= w and
+ *                      (score', pos') < (score, pos) lexicographically.  w as in spm_hip_hits_select (window, or with
+ *                      SPM_SELECT_WINDOW_K the needle's own k, 0 for exact sets; w = 0 keeps everything).  Suppression is
+ *                      strict: a dominated record still dominates.  Records of different haplotypes never see each other,
+ *                      and there is no segment notion: haplotype coordinates are one range per haplotype.
+ *   SPM_SELECT_BEST    applied after LOCI: r is kept iff score <= min + strata, min taken over the INPUT records of the same
+ *                      (haplotype, pattern) ...
+ *   SPM_SELECT_ACROSS  ... or, with this flag, over the input records of the same pattern on ALL haplotypes ("the best place
+ *                      of this read anywhere in the pan-genome").  ACROSS without BEST is SPM_E_INVALID.
+ *   neither flag       a sorted copy.
+ * Without ACROSS the records of haplotype h in the result are exactly what spm_hip_scan + spm_hip_hits_select with the same
+ * opts return on the materialised haplotype h.  The rule reads only the SET of records: the result is bit-identical across
+ * engines, block lengths, runs and arrival orders.
+ * The result is a new spm_jst_hits with a buffer of its own; it stays valid after the source is destroyed (the needle set
+ * must stay alive if the result is selected again with SPM_SELECT_WINDOW_K).  Its DEVICE view is in (haplotype, pattern,
+ * pos) order -- the one device view of pan-genome hits with a defined order; its host view is in the order of every
+ * spm_hip_jst_hits_view, (haplotype, pos, pattern, score).  copy_device, gatherv_jst_hits and destroy take it unchanged, and
+ * it may be selected again.  It is NOT alignable, whatever the source was: spm_hip_jst_hits_align on it returns
+ * SPM_E_INVALID.
+ * Decided on the host before any launch: SPM_E_UNSUPPORTED for more than 2^32 - 1 records, or
+ * bits(n_haplotypes - 1) + bits(n_patterns - 1) + bits(largest position) above 64 (for a tree the position bound is the
+ * reference length plus all inserted symbols), or SPM_SELECT_ACROSS on records that name a pattern index of 2^24 or above
+ * (only a raw buffer without a needle set can); SPM_E_INVALID for unknown flag bits, a nonzero reserved field or NULL opts.
+ * No records: an empty result and SPM_OK.  spm_hip_hits_select and spm_hip_records_select refuse SPM_SELECT_ACROSS. */
+#define SPM_SELECT_ACROSS 4u   /* pan-genome selections only, with SPM_SELECT_BEST */
+int spm_hip_jst_hits_select(spm_jst_hits *hits, const spm_select_opts *opts, spm_jst_hits **out);
+/* The same on a device buffer of n spm_jst_hit records (8-byte aligned) that no handle owns -- what spm_hip_gatherv_jst_hits
+ * delivers on the root.  A locus can straddle the block shards of several GPUs and the best stratum is global, so under
+ * sharding the order is: gatherv first, select on the root second.  patterns may be NULL if the window is explicit
+ * (SPM_SELECT_WINDOW_K without a set: SPM_E_INVALID).  (haplotype, pattern, pos) must be unique in the buffer; the search
+ * guarantees that.  The ranges of haplotype, pattern and position are read off the buffer by a reduction kernel and one
+ * small read-back before the sort is planned. */
+int spm_hip_jst_records_select(spm_ctx *ctx, const void *device_records, uint64_t n, const spm_patterns *patterns,
+                               const spm_select_opts *opts, spm_jst_hits **out);
+/* n_in, n_loci, n_out, key_bits and the order / select / host times; SPM_E_INVALID on a result no selection made */
+int spm_hip_jst_hits_select_stats(const spm_jst_hits *hits, spm_select_stats *out);
+
 /* Synthetic variants of config C5: one SNP per 1000 reference bases, one indel of length 1..50 per
  * 10 000, each carried by a random non-empty subset of n_haplotypes <= 64; the reference is the synthetic text of
  * `seed_text`.  Call with alleles == NULL to get the counts (*n_alleles, *alt_pool_len) first.  Host side. */

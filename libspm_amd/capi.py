@@ -174,6 +174,7 @@ class SelectStats(C.Structure):
 
 
 SELECT_LOCI, SELECT_BEST = 1, 2
+SELECT_ACROSS = 4   # pan-genome selections only, with SELECT_BEST
 SELECT_WINDOW_K = 0xFFFFFFFF
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
 
@@ -270,6 +271,9 @@ def lib():
                                               C.POINTER(C.c_uint64)]),
         "spm_hip_jst_alns_stats": (C.c_int, [vp, C.POINTER(JstAlignStats)]),
         "spm_hip_jst_alns_destroy": (None, [vp]),
+        "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
+        "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
+        "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
         "spm_hip_comm_unique_id": (C.c_int, [vp]),
         "spm_hip_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
         "spm_hip_comm_destroy": (None, [vp]),
@@ -307,6 +311,7 @@ EXPORTS = [
     "spm_hip_jst_hits_copy_device", "spm_hip_jst_hits_destroy", "spm_hip_jst_synth_variants",
     "spm_hip_jst_hits_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
     "spm_hip_jst_alns_destroy",
+    "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",
 ]

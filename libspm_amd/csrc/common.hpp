@@ -116,6 +116,31 @@ struct spm_hits : hits_block // (its buffers, counters and events: taken from th
     spm_select_stats sel{};
 };
 
+struct spm_jst_hits // (jst.hip: searches; jst_select.hip: selections)
+{
+    spm_ctx *ctx = nullptr;
+    spm_jst_hit *d = nullptr;
+    uint64_t cap = 0;
+    uint64_t n = 0;
+    bool sorted = false;
+    std::vector<spm_jst_hit> host;
+    // searches with SPM_SCAN_ALIGNABLE: what spm_hip_jst_hits_align needs
+    bool alignable = false;
+    spm_jst *jst = nullptr;
+    const struct spm_patterns *patterns = nullptr;
+    uint64_t generation = 0;
+    spm_hits *seg = nullptr; // the search's segment hits, owned (nullptr: the search had nothing to scan)
+    // what a selection plans its sort key from: set by the search (the tree's bounds), or by the range kernel of
+    // spm_hip_jst_records_select, and inherited by every selection of a selection
+    uint64_t sel_n_hap = 1, sel_n_patterns = 1, sel_max_pos = 0;
+    // a result made by spm_hip_jst_hits_select / spm_hip_jst_records_select: a buffer of exactly n records that is freed, not
+    // pooled, and three events that time its order and select steps
+    bool selected = false;
+    bool sel_timed = false;
+    hipEvent_t sel_ev[3] = {nullptr, nullptr, nullptr};
+    spm_select_stats sel{};
+};
+
 // A deferred scan that had to be repeated: `h` takes over the buffers and the outcome of the repeated scan, which gets
 // h's in exchange and is destroyed by the caller.  The only place that knows which members are device resources: the
 // hits_block (whose pinned block and event stay where they are) and the per-scan tables in d_aux.

@@ -705,6 +705,7 @@ struct spm_jst
     std::vector<uint8_t> alt;
     std::vector<uint64_t> cov;
     uint32_t H = 0, cw = 0, max_rlen = 0;
+    uint64_t max_hap_len = 0; // reference length plus all inserted symbols: no haplotype position lies beyond it
     // device allele table
     uint64_t *d_pos = nullptr, *d_aoff = nullptr, *d_cov = nullptr;
     uint32_t *d_rlen = nullptr, *d_alen = nullptr;
@@ -777,22 +778,6 @@ struct spm_jst
     }
 };
 
-struct spm_jst_hits
-{
-    spm_ctx *ctx = nullptr;
-    spm_jst_hit *d = nullptr;
-    uint64_t cap = 0;
-    uint64_t n = 0;
-    bool sorted = false;
-    std::vector<spm_jst_hit> host;
-    // searches with SPM_SCAN_ALIGNABLE: what spm_hip_jst_hits_align needs
-    bool alignable = false;
-    spm_jst *jst = nullptr;
-    const spm_patterns *patterns = nullptr;
-    uint64_t generation = 0;
-    spm_hits *seg = nullptr; // the search's segment hits, owned (nullptr: the search had nothing to scan)
-};
-
 extern "C" int spm_hip_jst_create(spm_ctx *ctx, const spm_text *reference, const spm_jst_allele *alleles,
                                   uint64_t n_alleles, const uint8_t *alt_pool, uint64_t alt_pool_len,
                                   const uint64_t *coverage, uint32_t n_haplotypes, spm_jst **out)
@@ -809,6 +794,7 @@ extern "C" int spm_hip_jst_create(spm_ctx *ctx, const spm_text *reference, const
     std::unique_ptr<spm_jst> J(new spm_jst);
     J->ctx = ctx;
     J->ref = reference;
+    J->max_hap_len = reference->n;
     J->H = n_haplotypes;
     J->cw = cw;
     J->al.assign(alleles, alleles + n_alleles);
@@ -825,6 +811,7 @@ extern "C" int spm_hip_jst_create(spm_ctx *ctx, const spm_text *reference, const
         }
         a.ref_len = (uint32_t)std::min<uint64_t>(a.ref_len, reference->n - a.pos); // clamp to the reference
         J->max_rlen = std::max(J->max_rlen, a.ref_len);
+        J->max_hap_len += a.alt_len;
         for (uint32_t x = 0; x < a.alt_len; ++x)
             if (J->alt[a.alt_off + x] >= reference->sigma) {
                 SPM_SET_ERR(ctx, "spm_hip_jst_create: allele %llu holds a symbol that is not a rank < sigma",
@@ -1113,8 +1100,11 @@ extern "C" void spm_hip_jst_hits_destroy(spm_jst_hits *h)
         return;
     if (h->seg)
         spm_hip_hits_destroy(h->seg);
+    for (hipEvent_t e : h->sel_ev)
+        if (e)
+            hipEventDestroy(e);
     if (h->d) {
-        if (h->ctx && h->ctx->jst_pool.size() < 4)
+        if (h->ctx && !h->selected && h->ctx->jst_pool.size() < 4)
             h->ctx->jst_pool.push_back({h->d, h->cap});
         else
             hipFree(h->d);
@@ -1160,6 +1150,9 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
     R->jst = J;
     R->patterns = patterns;
     R->generation = J->generation;
+    R->sel_n_hap = J->H;
+    R->sel_n_patterns = std::max<uint64_t>(patterns->n, 1);
+    R->sel_max_pos = J->max_hap_len;
     const uint64_t out_cap = o.max_hits ? o.max_hits : (1ull << 22);
     if (o.max_hits == 0)
         o.max_hits = 1ull << 22;
@@ -1353,6 +1346,11 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
         return SPM_E_INVALID;
     spm_ctx *ctx = h->ctx;
     const auto t_call = clk::now();
+    if (h->selected) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: these hits are a selection, and a selection is not alignable (it keeps no "
+                         "map from its records back to the search's segment hits); align the search's own result");
+        return SPM_E_INVALID;
+    }
     if (!h->alignable) {
         SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: these hits do not keep their segment hits; search with "
                          "spm_scan_opts.flags & SPM_SCAN_ALIGNABLE");

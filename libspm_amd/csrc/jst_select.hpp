@@ -1,0 +1,262 @@
+// jst_select.hpp -- the kernels of pan-genome hit selection (spm_hip_jst_hits_select / spm_hip_jst_records_select; contract
+// in spm_hip.h, scheme in DESIGN.md 4.7).  gfx950.  The siblings of select.hpp for the 24-byte spm_jst_hit: the records are
+// ordered by a radix sort of (key, index) pairs, key = haplotype << (pat_bits + pos_bits) | pattern << pos_bits | pos, so
+// that key >> pos_bits names the group (haplotype, pattern) whose records see each other; then
+//   jst_select_loci_kernel     one lane per sorted record: is a record of the same group within the window better?  Also the
+//                              head flag of every group;
+//   jst_select_minima_kernel   BEST: the minimal score of every group, into an array indexed by the group's number (the
+//                              exclusive sum of the head flags) -- or, with ACROSS, by the pattern;
+//   jst_select_compact_kernel  the stratum test and the stable compaction of the kept records, three 8-byte words each.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "select_plan.hpp"
+
+namespace spm_hip
+{
+
+struct jst_select_params
+{
+    const unsigned long long *recs = nullptr; // the source's records as 8-byte words, three each, in their arrival order:
+                                              // pos | pattern << 32 + haplotype | reserved << 32 + score
+    unsigned long long *keys = nullptr;       // [n] sorted keys
+    uint32_t *idx = nullptr;                  // [n] record index of sorted entry i
+    const int32_t *score_in = nullptr;        // [n] scores in arrival order (the keys kernel wrote them)
+    uint32_t n = 0;
+    uint32_t pos_bits = 0;                    // key >> pos_bits = group (pos_bits == 64: one group, number 0)
+    unsigned long long pos_mask = 0;
+    uint32_t pat_mask = 0;                    // group & pat_mask = pattern
+    uint32_t loci = 0, best = 0, across = 0;
+    uint32_t window = 0;                      // SPM_SELECT_WINDOW_K: k_tab[pattern]
+    const int32_t *k_tab = nullptr;
+    uint32_t halo = 0;                        // <= kSelHaloCap
+    long long strata = 0;
+    // out
+    uint8_t *keep = nullptr;                  // [n] LOCI's verdict
+    uint8_t *head = nullptr;                  // [n] 1 where a group begins
+    int32_t *score = nullptr;                 // [n] scores in sorted order
+    const uint32_t *gid = nullptr;            // [n] exclusive sum of head (BEST without ACROSS)
+    int32_t *grp_min = nullptr;               // BEST: minimal score per group number / per pattern (preset to INT_MAX)
+    unsigned long long *counts = nullptr;     // [0] records LOCI kept, [1] records of the result
+};
+
+__device__ __forceinline__ unsigned long long jsel_group(const jst_select_params &P, unsigned long long key)
+{
+    return P.pos_bits < 64 ? key >> P.pos_bits : 0ull;
+}
+
+__device__ __forceinline__ unsigned long long jsel_key(unsigned long long w_pos, unsigned long long w_hp, uint32_t pos_bits,
+                                                       uint32_t pat_bits)
+{
+    const unsigned long long hap = w_hp & 0xFFFFFFFFull, pat = w_hp >> 32;
+    const unsigned long long grp = pat_bits < 64 ? hap << pat_bits | pat : pat; // (pat_bits <= 32 in fact)
+    return (pos_bits < 64 ? grp << pos_bits : 0ull) | w_pos;
+}
+
+// One lane per record.  The 256 records of a workgroup are 768 contiguous 8-byte words (a wave's share: 1 536 bytes): they
+// are read as such, three coalesced loads per lane, and handed to their lanes through LDS.  Key, index and score leave in
+// arrival order: the later stages gather a 4-byte score through the sorted index, never a record.
+__global__ __launch_bounds__(256) void jst_select_keys_kernel(const unsigned long long *__restrict__ recs,
+                                                                unsigned long long *__restrict__ keys, uint32_t *__restrict__ idx,
+                                                                int32_t *__restrict__ score, uint32_t n, uint32_t pos_bits,
+                                                                uint32_t pat_bits)
+{
+    __shared__ unsigned long long s_w[3 * 256];
+    const unsigned long long base = (unsigned long long)blockIdx.x * 256ull;
+    const unsigned long long n_words = 3ull * n;
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+        const unsigned long long w = base * 3ull + r * 256u + threadIdx.x;
+        if (w < n_words)
+            s_w[r * 256u + threadIdx.x] = recs[w];
+    }
+    __syncthreads();
+    const unsigned long long i = base + threadIdx.x;
+    if (i >= n)
+        return;
+    const unsigned long long w_pos = s_w[3 * threadIdx.x], w_hp = s_w[3 * threadIdx.x + 1], w_sc = s_w[3 * threadIdx.x + 2];
+    keys[i] = jsel_key(w_pos, w_hp, pos_bits, pat_bits);
+    idx[i] = (uint32_t)i;
+    score[i] = (int32_t)(uint32_t)w_sc;
+}
+
+// spm_hip_jst_records_select: the range of what a raw buffer holds -- out[0] = max haplotype, out[1] = max pattern,
+// out[2] = max pos.  Grid-stride; one atomic triple per wave.
+__global__ __launch_bounds__(256) void jst_select_range_kernel(const unsigned long long *__restrict__ recs, uint32_t n,
+                                                                 unsigned long long *__restrict__ out)
+{
+    unsigned long long hap = 0, pat = 0, pos = 0;
+    for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
+        const unsigned long long w_pos = recs[3 * i], w_hp = recs[3 * i + 1];
+        const unsigned long long h = w_hp & 0xFFFFFFFFull, p = w_hp >> 32;
+        pos = w_pos > pos ? w_pos : pos;
+        hap = h > hap ? h : hap;
+        pat = p > pat ? p : pat;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long h2 = __shfl_xor(hap, d), p2 = __shfl_xor(pat, d), q2 = __shfl_xor(pos, d);
+        hap = h2 > hap ? h2 : hap;
+        pat = p2 > pat ? p2 : pat;
+        pos = q2 > pos ? q2 : pos;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&out[0], hap);
+        atomicMax(&out[1], pat);
+        atomicMax(&out[2], pos);
+    }
+}
+
+// One lane per sorted record, as select_loci_kernel: LDS holds the keys and scores of the tile and of `halo` records on either
+// side; a lane whose window reaches further reads the rest from global memory (needles with k > 32).  The group test is
+// key >> pos_bits, haplotype AND pattern: records of neighbouring haplotypes never see each other.
+__global__ __launch_bounds__(kSelTile) void jst_select_loci_kernel(const jst_select_params P)
+{
+    __shared__ unsigned long long s_key[kSelTile + 2 * kSelHaloCap];
+    __shared__ int32_t s_score[kSelTile + 2 * kSelHaloCap];
+    const uint32_t H = P.halo;
+    const long long tile0 = (long long)blockIdx.x * kSelTile;
+    const long long lds0 = tile0 - H; // sorted index of s_key[0]
+    const long long n = P.n;
+    for (uint32_t t = threadIdx.x; t < kSelTile + 2 * H; t += kSelTile) {
+        const long long j = lds0 + t;
+        if (j >= 0 && j < n) {
+            s_key[t] = P.keys[j];
+            s_score[t] = P.score_in[P.idx[j]];
+        }
+    }
+    __syncthreads();
+
+    const long long i = tile0 + threadIdx.x;
+    const long long lds_end = lds0 + kSelTile + 2 * H;
+    bool kept = false;
+    if (i < n) {
+        const unsigned long long key = s_key[H + threadIdx.x];
+        const int32_t sc = s_score[H + threadIdx.x];
+        const unsigned long long grp = jsel_group(P, key);
+        P.score[i] = sc;
+        kept = true;
+        if (i == 0)
+            P.head[i] = 1;
+        else {
+            const unsigned long long kp = i - 1 >= lds0 ? s_key[i - 1 - lds0] : P.keys[i - 1];
+            P.head[i] = jsel_group(P, kp) != grp ? 1 : 0;
+        }
+        const unsigned long long w = !P.loci                            ? 0ull
+                                     : P.window == SPM_SELECT_WINDOW_K ? (unsigned long long)max(P.k_tab[(uint32_t)grp & P.pat_mask], 0)
+                                                                       : P.window;
+        if (w) {
+            const unsigned long long rel = key & P.pos_mask;
+            // to the left: a record there is better when its score is not larger (its position is smaller)
+            for (long long j = i - 1; j >= 0; --j) {
+                const bool in_lds = j >= lds0;
+                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
+                if (jsel_group(P, kj) != grp)
+                    break;
+                const unsigned long long rj = kj & P.pos_mask;
+                if (rel - rj > w)
+                    break;
+                const int32_t sj = in_lds ? s_score[j - lds0] : P.score_in[P.idx[j]];
+                if (sj <= sc) {
+                    kept = false;
+                    break;
+                }
+            }
+            // to the right: only a strictly smaller score is better
+            for (long long j = i + 1; kept && j < n; ++j) {
+                const bool in_lds = j < lds_end;
+                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
+                if (jsel_group(P, kj) != grp)
+                    break;
+                const unsigned long long rj = kj & P.pos_mask;
+                if (rj - rel > w)
+                    break;
+                const int32_t sj = in_lds ? s_score[j - lds0] : P.score_in[P.idx[j]];
+                if (sj < sc)
+                    kept = false;
+            }
+        }
+        P.keep[i] = kept ? 1 : 0;
+    }
+    // records LOCI kept: one atomic per wave
+    const unsigned long long kept_mask = __ballot(kept);
+    if ((threadIdx.x & 63) == 0 && kept_mask)
+        atomicAdd(&P.counts[0], (unsigned long long)__popcll(kept_mask));
+}
+
+// the number of record i's group among the groups of the sorted list
+__device__ __forceinline__ uint32_t jsel_gid(const jst_select_params &P, uint32_t i) { return P.gid[i] + P.head[i] - 1u; }
+// where the minimum that record i is measured against lives
+__device__ __forceinline__ uint32_t jsel_min_slot(const jst_select_params &P, uint32_t i)
+{
+    return P.across ? (uint32_t)jsel_group(P, P.keys[i]) & P.pat_mask : jsel_gid(P, i);
+}
+
+// BEST: lanes of one group are contiguous (sorted input), so a segmented min-scan over the wave leaves the minimum of every
+// run in its last lane, which issues the one atomicMin of that wave and group.  A table of n_haplotypes x n_patterns minima
+// would not fit; the groups that occur are numbered instead, and there are at most n of them.
+__global__ __launch_bounds__(256) void jst_select_minima_kernel(const jst_select_params P)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    const bool valid = i < P.n;
+    const uint32_t lane = threadIdx.x & 63;
+    unsigned long long grp = ~0ull;
+    int32_t m = 0x7FFFFFFF;
+    if (valid) {
+        grp = jsel_group(P, P.keys[i]);
+        m = P.score[i];
+    }
+    for (int d = 1; d < 64; d <<= 1) {
+        const int32_t m2 = __shfl_up(m, d);
+        const unsigned long long g2 = __shfl_up(grp, d);
+        if (lane >= (uint32_t)d && g2 == grp)
+            m = m2 < m ? m2 : m;
+    }
+    const unsigned long long g_next = __shfl_down(grp, 1);
+    if (valid && (lane == 63 || g_next != grp || i + 1 >= P.n))
+        atomicMin(&P.grp_min[jsel_min_slot(P, (uint32_t)i)], m);
+}
+
+// what the exclusive scan adds up and the compaction tests again: LOCI's verdict and the stratum test
+__device__ __forceinline__ uint32_t jsel_final_flag(const jst_select_params &P, uint32_t i)
+{
+    uint32_t f = P.keep[i];
+    if (f && P.best)
+        f = (long long)P.score[i] <= (long long)P.grp_min[jsel_min_slot(P, i)] + P.strata ? 1u : 0u;
+    return f;
+}
+struct jsel_flag_op
+{
+    jst_select_params P;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return jsel_final_flag(P, i); }
+};
+struct jsel_head_op
+{
+    const uint8_t *head;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return head[i]; }
+};
+
+// offs: exclusive scan of the final flags.  A kept record travels as three 8-byte words.  The last lane writes the counts
+// the host reads back.
+__global__ __launch_bounds__(256) void jst_select_compact_kernel(const jst_select_params P, const uint32_t *__restrict__ offs,
+                                                                   unsigned long long *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n)
+        return;
+    const uint32_t f = jsel_final_flag(P, i);
+    const uint32_t o = offs[i];
+    if (f) {
+        const unsigned long long *src = P.recs + 3ull * P.idx[i];
+        unsigned long long *dst = out + 3ull * o;
+        const unsigned long long a = src[0], b = src[1], c = src[2];
+        dst[0] = a;
+        dst[1] = b;
+        dst[2] = c;
+    }
+    if (i == P.n - 1)
+        P.counts[1] = (unsigned long long)o + f;
+}
+
+} // namespace spm_hip

@@ -92,4 +92,67 @@ inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uin
     return P;
 }
 
+// ---- pan-genome selections (spm_hip_jst_hits_select / spm_hip_jst_records_select; jst_select.hip) -------------------------
+// The locus of a spm_jst_hit is (haplotype, pattern): key = haplotype << (pat_bits + pos_bits) | pattern << pos_bits | pos,
+// so key >> pos_bits names the group whose records see each other.  Positions are haplotype coordinates from 0: no bias.
+struct jst_select_plan
+{
+    int status = SPM_OK;
+    const char *why = "";
+    uint32_t hap_bits = 0, pat_bits = 0, pos_bits = 0;
+    uint32_t key_bits = 0;     // the radix sort's end_bit (>= 1)
+    uint32_t window = 0;       // as select_plan
+    uint32_t max_window = 0;
+    uint32_t halo = 0;
+    bool loci = false, best = false, across = false;
+};
+
+// n_haplotypes / n_patterns: what the records can name (>= 1 each); max_pos: the largest position a record can hold (for a
+// tree: reference length plus all inserted symbols); the needle set as in plan_select.
+inline jst_select_plan plan_jst_select(const spm_select_opts &o, uint64_t n_records, uint64_t n_haplotypes, uint64_t n_patterns,
+                                       uint64_t max_pos, bool have_k, bool myers_set, uint32_t max_k)
+{
+    jst_select_plan P;
+    if ((o.flags & ~(SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_ACROSS)) || o.reserved) {
+        P.status = SPM_E_INVALID;
+        P.why = "unknown flag bits, or a nonzero reserved field";
+        return P;
+    }
+    P.loci = (o.flags & SPM_SELECT_LOCI) != 0;
+    P.best = (o.flags & SPM_SELECT_BEST) != 0;
+    P.across = (o.flags & SPM_SELECT_ACROSS) != 0;
+    if (P.across && !P.best) {
+        P.status = SPM_E_INVALID;
+        P.why = "SPM_SELECT_ACROSS needs SPM_SELECT_BEST";
+        return P;
+    }
+    if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k) {
+        P.status = SPM_E_INVALID;
+        P.why = "SPM_SELECT_WINDOW_K needs the needle set";
+        return P;
+    }
+    if (n_records > 0xFFFFFFFFull) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "more than 2^32 - 1 records";
+        return P;
+    }
+    P.hap_bits = bits_for(n_haplotypes ? n_haplotypes - 1 : 0);
+    P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
+    P.pos_bits = bits_for(max_pos);
+    P.key_bits = P.hap_bits + P.pat_bits + P.pos_bits;
+    if (P.key_bits > 64) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "haplotype, pattern index and position do not fit one 64-bit sort key";
+        return P;
+    }
+    P.key_bits = std::max(P.key_bits, 1u);
+    if (P.loci) {
+        const bool per_needle = o.window == SPM_SELECT_WINDOW_K && myers_set && max_k > 0;
+        P.window = per_needle ? SPM_SELECT_WINDOW_K : select_window(o.window, myers_set, max_k);
+        P.max_window = select_window(o.window, myers_set, max_k);
+    }
+    P.halo = select_halo(P.max_window);
+    return P;
+}
+
 } // namespace spm_hip

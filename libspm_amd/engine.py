@@ -345,8 +345,9 @@ def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | 
     return (hits, st_out) if want_state else hits
 
 
-def _select_opts(loci, window, best) -> capi.SelectOpts:
-    flags = (capi.SELECT_LOCI if loci else 0) | (capi.SELECT_BEST if best is not None else 0)
+def _select_opts(loci, window, best, across=False) -> capi.SelectOpts:
+    flags = ((capi.SELECT_LOCI if loci else 0) | (capi.SELECT_BEST if best is not None else 0)
+             | (capi.SELECT_ACROSS if across else 0))
     return capi.SelectOpts(flags=flags, window=capi.SELECT_WINDOW_K if window is None else int(window),
                            strata=0 if best is None else int(best), reserved=0)
 
@@ -493,9 +494,14 @@ class JstHits:
         self.ctx, self._h, self._jst, self._pats = ctx, h, jst, pats
 
     def __len__(self):
+        return self.device()[1]
+
+    def device(self):
+        """(pointer, count) of the records in HBM: arrival order for a search, (haplotype, pattern, pos) order for a
+        selection."""
         p, n = C.c_void_p(), C.c_uint64(0)
         _check(capi.lib().spm_hip_jst_hits_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(n.value)
+        return int(p.value or 0), int(n.value)
 
     def view(self) -> np.ndarray:
         rec = C.POINTER(capi.JstHit)()
@@ -521,6 +527,25 @@ class JstHits:
                self.ctx._h)
         return JstAlignments(self.ctx, a)
 
+    def select(self, loci: bool = True, window: int | None = None, best: int | None = None,
+               across: bool = False) -> "JstHits":
+        """A new, smaller JstHits (spm_hip_jst_hits_select): one record per locus of every haplotype (loci; window=None:
+        every needle's own k) and, with best=s, only the records within s errors of the minimum of their (haplotype,
+        needle) -- with across=True, of their needle on all haplotypes.  The device view of the result is sorted by
+        (haplotype, pattern, pos), its host view as every view(); it stays valid after this object is closed, and it
+        cannot be aligned."""
+        if self._pats is not None and not self._pats._h:
+            raise capi.SpmError("JstHits.select: the needle set of these hits has been closed")
+        opts = _select_opts(loci, window, best, across)
+        h = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
+        return JstHits(self.ctx, h, self._jst, self._pats)
+
+    def select_stats(self) -> capi.SelectStats:
+        s = capi.SelectStats()
+        _check(capi.lib().spm_hip_jst_hits_select_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
     def close(self):
         if self._h:
             if self.ctx._h:
@@ -532,6 +557,17 @@ class JstHits:
             self.close()
         except Exception:
             pass
+
+
+def select_jst_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet | None = None, *, loci: bool = True,
+                       window: int | None = None, best: int | None = None, across: bool = False) -> JstHits:
+    """JstHits.select() on a device buffer of n JST_HIT_DTYPE records that no JstHits owns -- what a gatherv of the block
+    shards delivers on the root (spm_hip_jst_records_select).  pats may be None when window is explicit."""
+    opts = _select_opts(loci, window, best, across)
+    h = C.c_void_p()
+    _check(capi.lib().spm_hip_jst_records_select(ctx._h, C.c_void_p(device_ptr), n, pats._h if pats is not None else None,
+                                                 C.byref(opts), C.byref(h)), ctx._h)
+    return JstHits(ctx, h, None, pats)
 
 
 class JstAlignments:
