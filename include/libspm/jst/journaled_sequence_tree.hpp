@@ -436,6 +436,73 @@ public:
         return locate_host(needles, window, needle_len, reports_begin, block, stats);
     }
 
+    // locate of the SELECTED hits only: begin and transcript of the loci search(..., selection) keeps, in its order.  Device
+    // route: search, select, then spm_hip_jst_selection_align, which locates the kept records in the index and aligns their
+    // distinct segment hits once.  Trees the device path does not take: locate_host, filtered to the records select_host keeps,
+    // matched by (haplotype, needle, position, errors).  Both routes return the same vector.
+    std::vector<jst_alignment> locate(spm_patterns * needles, std::size_t window, std::vector<std::uint32_t> const & needle_len,
+                                      bool reports_begin, hip::hit_selection const & selection, std::size_t block = 0,
+                                      jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_device(needles, window, reports_begin, selection, block, stats);
+        return locate_selected_host(needles, window, needle_len, reports_begin, selection, block, stats);
+    }
+
+    std::vector<jst_alignment> locate_selected_host(spm_patterns * needles, std::size_t window,
+                                                    std::vector<std::uint32_t> const & needle_len, bool reports_begin,
+                                                    hip::hit_selection const & selection, std::size_t block = 0,
+                                                    jst_search_stats * stats = nullptr) const
+    {
+        std::vector<jst_alignment> all = locate_host(needles, window, needle_len, reports_begin, block, stats);
+        std::vector<jst_hit> hits;
+        hits.reserve(all.size());
+        auto const as_hit = [reports_begin](jst_alignment const & x) {
+            return jst_hit{x.haplotype, reports_begin ? x.aln.begin_position() : x.aln.end_position(), x.needle,
+                           static_cast<std::int32_t>(x.aln.errors())};
+        };
+        for (jst_alignment const & x : all)
+            hits.push_back(as_hit(x));
+        std::vector<jst_hit> const kept = select_host(std::move(hits), needles, needle_len, reports_begin, selection); // sorted
+        std::erase_if(all, [&](jst_alignment const & x) { return !std::binary_search(kept.begin(), kept.end(), as_hit(x)); });
+        return all;
+    }
+
+    std::vector<jst_alignment> locate_device(spm_patterns * needles, std::size_t window, bool reports_begin,
+                                             hip::hit_selection const & selection, std::size_t block = 0,
+                                             jst_search_stats * stats = nullptr) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, 0, stats); // (need not be alignable)
+        spm_select_opts o{};
+        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
+                  (selection.across ? SPM_SELECT_ACROSS : 0u);
+        o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
+        o.strata = selection.strata.value_or(0u);
+        spm_jst_hits * sel = nullptr;
+        if (spm_hip_jst_hits_select(hh, &o, &sel) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_select", ctx);
+        spm_hip_jst_hits_destroy(hh); // (the selection stays alignable without its source)
+        spm_jst_alns * a = nullptr;
+        if (spm_hip_jst_selection_align(sel, 0, &a) != SPM_OK)
+            hip::fatal("spm_hip_jst_selection_align", ctx);
+        spm_hip_jst_hits_destroy(sel);
+        hip::jst_alns_ptr alns{a};
+        spm_jst_aln const * rec = nullptr;
+        std::uint32_t const * ops = nullptr;
+        std::uint64_t n = 0, n_ops = 0;
+        if (spm_hip_jst_alns_view(a, &rec, &n, &ops, &n_ops) != SPM_OK)
+            hip::fatal("spm_hip_jst_alns_view", ctx);
+        std::vector<jst_alignment> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            out.push_back({rec[i].haplotype, rec[i].pattern,
+                           alignment{static_cast<std::size_t>(rec[i].begin), static_cast<std::size_t>(rec[i].end), rec[i].score,
+                                     ops + rec[i].cigar_off, rec[i].cigar_len}});
+        sort_alignments(out, reports_begin);
+        return out;
+    }
+
     std::vector<jst_alignment> locate_device(spm_patterns * needles, std::size_t window, bool reports_begin,
                                              std::size_t block = 0, jst_search_stats * stats = nullptr) const
     {

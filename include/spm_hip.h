@@ -95,7 +95,8 @@ typedef struct spm_scan_opts {
 #define SPM_SCAN_DEFER 2u
 /* Only spm_hip_jst_search looks at this bit (it never reaches a scan): the result keeps the search's segment hits -- the
  * hits in context coordinates, before the fan-out -- until it is destroyed, so that spm_hip_jst_hits_align can align
- * them.  Without it a search holds what it always held and its hits cannot be aligned. */
+ * them.  Without it a search holds what it always held and spm_hip_jst_hits_align refuses its hits (a selection of them
+ * is aligned by spm_hip_jst_selection_align, which needs no segment hits). */
 #define SPM_SCAN_ALIGNABLE 4u
 
 /* Per-scan device timings, HIP events on the context's stream (ms). */
@@ -476,6 +477,48 @@ int spm_hip_jst_alns_device(spm_jst_alns *a, const void **records, uint64_t *n, 
 int spm_hip_jst_alns_stats(const spm_jst_alns *a, spm_jst_align_stats *out);
 void spm_hip_jst_alns_destroy(spm_jst_alns *a);
 
+/* ---- begins and alignments of the records a SELECTION kept (spm_hip_jst_hits_select below) ---------------------------
+ * A read mapper wants begin and CIGAR of the loci it kept, not of every record.  A selection keeps no map from its records
+ * back to the search's segment hits, but the search's fan-out is a bijection from (segment hit that ends on an owned symbol,
+ * member haplotype of its context) to haplotype record, and it is inverted per kept record from the tables of the index:
+ * the block of the haplotype that owns the record's last symbol, that cell's context, where the context starts in the
+ * haplotype -- hence the segment hit in the context buffer.  Kept records of haplotypes that share a context land on the
+ * same segment hit; the DISTINCT ones are aligned once by the kernels of spm_hip_hits_align, then gathered.
+ *   * Accepted: the result of spm_hip_jst_hits_select whose source chain ends, through any number of selections, at a result
+ *     of spm_hip_jst_search.  Any select flags, SPM_SELECT_ACROSS included.  The search need NOT have been made with
+ *     SPM_SCAN_ALIGNABLE, and the selection's source may already be destroyed.  Tree and needle set must still be alive, and
+ *     the tree must not have been indexed again since the search (spm_hip_jst_index frees the context buffer the alignment
+ *     reads): SPM_E_INVALID otherwise.
+ *   * Refused with SPM_E_INVALID and a message that says why: a result of spm_hip_jst_records_select (it names no tree, and
+ *     its records may stem from several block shards); a search's own result (use spm_hip_jst_hits_align, or a selection
+ *     without flags, which is a sorted copy); unknown flag bits; NULL arguments.
+ *   * One spm_jst_aln per record of the selection, n_alns = its count.  begin, end and transcript are exactly those
+ *     spm_hip_jst_hits_align defines: begin is the largest b >= 0 OF THAT HAPLOTYPE with ED(P, hap[b, end)) = score, the
+ *     transcript the one the tie order above gives for P against hap[b, end).  (A context starts at the haplotype's first
+ *     symbol or carries window - 1 >= |P| + k - 1 symbols of left context, a reported hit ends on an owned symbol, and an
+ *     alignment with d <= k edits spans at most |P| + d symbols: its begin cannot lie left of the context.)  The record for
+ *     (haplotype, pattern, end, score) has the same begin and the same transcript words as that record of
+ *     spm_hip_jst_hits_align on an alignable search over the same tree and set; pool offsets differ.
+ *   * DEVICE view: record i belongs to record i of the selection's device view, in (haplotype, pattern, pos) order -- the
+ *     first device view of alignments with a defined order.  Host view: record i belongs to record i of
+ *     spm_hip_jst_hits_view of the selection.
+ *   * The pool holds one slot of 2 score + 1 words per DISTINCT segment hit among the kept records, in the order (pattern,
+ *     position in the context buffer).  Records that map to the same segment hit share cigar_off / cigar_len.  Two calls
+ *     give byte-identical host views (records and pool).
+ *   * Exact sets: begin = pos, end = pos + |P|, transcript |P|= (the last symbol of such a hit is pos + |P| - 1).
+ *   * A record that cannot be located -- its last symbol lies outside the indexed blocks, its cell owns nothing, its mapped
+ *     position falls outside its context or into the left context -- fails the whole call with SPM_E_INVALID and the count;
+ *     nothing is aligned.  The detection is a device counter read back with the count of distinct hits, never a fault: every
+ *     table index is tested against the table's size before it is read.
+ *   * SPM_E_UNSUPPORTED, decided on the host: bits(n_patterns - 1) + bits(context symbols) above 64 (before any launch); a
+ *     pool that would exceed 2^32 words (once the distinct hits are known, before anything is aligned).
+ *   * An empty selection: an empty result and SPM_OK.
+ *   * The result is an ordinary spm_jst_alns: view, device, stats and destroy take it unchanged.  In its spm_jst_align_stats
+ *     n_segment_alns counts the distinct segment hits aligned, ms_fanout is the device time of locate + order + gather, and
+ *     ms_worklist the host part (work list of the distinct hits; download and sort of the host view).
+ * flags: SPM_ALIGN_BEGIN_ONLY */
+int spm_hip_jst_selection_align(spm_jst_hits *selection, uint32_t flags, spm_jst_alns **out);
+
 /* ---- selection of pan-genome hits: one record per haplotype locus, the best stratum per (haplotype, needle) -------------
  * spm_hip_hits_select for the 24-byte records of spm_hip_jst_search.  The locus is (haplotype, pattern).  For a record
  * r = (haplotype, pos, pattern, score):
@@ -496,8 +539,9 @@ void spm_hip_jst_alns_destroy(spm_jst_alns *a);
  * must stay alive if the result is selected again with SPM_SELECT_WINDOW_K).  Its DEVICE view is in (haplotype, pattern,
  * pos) order -- the one device view of pan-genome hits with a defined order; its host view is in the order of every
  * spm_hip_jst_hits_view, (haplotype, pos, pattern, score).  copy_device, gatherv_jst_hits and destroy take it unchanged, and
- * it may be selected again.  It is NOT alignable, whatever the source was: spm_hip_jst_hits_align on it returns
- * SPM_E_INVALID.
+ * it may be selected again.  spm_hip_jst_hits_align does NOT take it, whatever the source was (SPM_E_INVALID): it keeps no
+ * map back to the search's segment hits.  The records it kept are aligned by spm_hip_jst_selection_align above, which
+ * locates them in the tree's index; for that a selection of a search's hits remembers the tree and its index generation.
  * Decided on the host before any launch: SPM_E_UNSUPPORTED for more than 2^32 - 1 records, or
  * bits(n_haplotypes - 1) + bits(n_patterns - 1) + bits(largest position) above 64 (for a tree the position bound is the
  * reference length plus all inserted symbols), or SPM_SELECT_ACROSS on records that name a pattern index of 2^24 or above

@@ -265,6 +265,7 @@ def lib():
         "spm_hip_jst_hits_copy_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "spm_hip_jst_hits_destroy": (None, [vp]),
         "spm_hip_jst_hits_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_selection_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
         "spm_hip_jst_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstAln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
                                             C.POINTER(C.c_uint64)]),
         "spm_hip_jst_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
@@ -309,7 +310,7 @@ EXPORTS = [
     "spm_hip_jst_create", "spm_hip_jst_destroy", "spm_hip_jst_haplotype_length", "spm_hip_jst_extract",
     "spm_hip_jst_index", "spm_hip_jst_search", "spm_hip_jst_stats", "spm_hip_jst_hits_view", "spm_hip_jst_hits_device",
     "spm_hip_jst_hits_copy_device", "spm_hip_jst_hits_destroy", "spm_hip_jst_synth_variants",
-    "spm_hip_jst_hits_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
+    "spm_hip_jst_hits_align", "spm_hip_jst_selection_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
     "spm_hip_jst_alns_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",

@@ -3,3 +3,4 @@
 #include "internal.hpp"
 #include "synth.hpp"
 #include "jst.hpp"
+#include "jst_locate.hpp"

@@ -757,6 +757,19 @@ struct spm_jst
         J.hap_start = d_hap_start;
         return J;
     }
+    // The context tables on the host, for the alignment entry points: enqueued once per index generation.  The caller
+    // synchronises the stream and then sets h_generation = generation.
+    int fetch_ctx_tables()
+    {
+        if (h_generation == generation)
+            return SPM_OK;
+        h_ctx_off.resize(n_ctx + 1);
+        h_ctx_owned.resize(n_ctx);
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(h_ctx_off.data(), d_ctx_off, (n_ctx + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (n_ctx)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(h_ctx_owned.data(), d_ctx_owned, n_ctx * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return SPM_OK;
+    }
     void free_index()
     {
         hipFree(d_alo);
@@ -1339,6 +1352,40 @@ extern "C" void spm_hip_jst_alns_destroy(spm_jst_alns *a)
     delete a;
 }
 
+// exact sets: nothing to compute -- begin = pos, end = pos + |P|, transcript |P|=, filled on the host
+static int jst_fill_exact_alns(spm_ctx *ctx, const spm_patterns *ps, const std::vector<spm_hit> &kh,
+                               const std::vector<uint32_t> &cig_off, bool begin_only, spm_aln *d_seg_alns, spm_jst_alns *A)
+{
+    const uint64_t nk = kh.size();
+    std::vector<spm_aln> sa(nk);
+    for (uint64_t i = 0; i < nk; ++i) {
+        const uint32_t m = (uint32_t)ps->m[kh[i].pattern];
+        sa[i] = spm_aln{kh[i].pos, kh[i].pos + m, kh[i].pattern, kh[i].score, begin_only ? 0u : cig_off[i], begin_only ? 0u : 1u};
+        if (!begin_only)
+            A->host_ops[cig_off[i]] = (m << 4) | SPM_CIGAR_EQ;
+    }
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_seg_alns, sa.data(), nk * sizeof(spm_aln), hipMemcpyHostToDevice, ctx->stream));
+    if (A->n_ops)
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->d_ops, A->host_ops.data(), A->n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
+    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); // (sa is read by the copy)
+    return SPM_OK;
+}
+
+// the order of spm_hip_jst_hits_view: (haplotype, pos, pattern, score), pos = end (Myers) / begin (exact)
+static void jst_sort_alns_host(std::vector<spm_jst_aln> &v, bool myers)
+{
+    std::sort(v.begin(), v.end(), [myers](const spm_jst_aln &a, const spm_jst_aln &b) {
+        if (a.haplotype != b.haplotype)
+            return a.haplotype < b.haplotype;
+        const uint64_t pa = myers ? a.end : a.begin, pb = myers ? b.end : b.begin;
+        if (pa != pb)
+            return pa < pb;
+        if (a.pattern != b.pattern)
+            return a.pattern < b.pattern;
+        return a.score < b.score;
+    });
+}
+
 extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_alns **out)
 {
     using namespace spm_hip;
@@ -1347,8 +1394,9 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
     spm_ctx *ctx = h->ctx;
     const auto t_call = clk::now();
     if (h->selected) {
-        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: these hits are a selection, and a selection is not alignable (it keeps no "
-                         "map from its records back to the search's segment hits); align the search's own result");
+        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: these hits are a selection, which keeps no map from its records back to the "
+                         "search's segment hits; align the search's own result, or the selection's records with "
+                         "spm_hip_jst_selection_align");
         return SPM_E_INVALID;
     }
     if (!h->alignable) {
@@ -1386,13 +1434,7 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
         if (rc != SPM_OK)
             return rc;
         std::vector<spm_hit> sh(n_seg);
-        if (J->h_generation != J->generation) { // the context tables: once per index generation
-            J->h_ctx_off.resize(J->n_ctx + 1);
-            J->h_ctx_owned.resize(J->n_ctx);
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(J->h_ctx_off.data(), J->d_ctx_off, (J->n_ctx + 1) * 8, hipMemcpyDeviceToHost, st));
-            if (J->n_ctx)
-                SPM_HIP_CHECK(ctx, hipMemcpyAsync(J->h_ctx_owned.data(), J->d_ctx_owned, J->n_ctx * 4, hipMemcpyDeviceToHost, st));
-        }
+        SPM_TRY(J->fetch_ctx_tables()); // once per index generation
         if (n_seg)
             SPM_HIP_CHECK(ctx, hipMemcpyAsync(sh.data(), d_seg, n_seg * sizeof(spm_hit), hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
@@ -1479,19 +1521,7 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
             A->stats.cigar_wave = as.cigar_wave;
             A->stats.cigar_wave_global = as.cigar_wave_global;
         } else {
-            // exact sets: nothing to compute
-            std::vector<spm_aln> sa(nk);
-            for (uint64_t i = 0; i < nk; ++i) {
-                const uint32_t m = (uint32_t)ps->m[kh[i].pattern];
-                sa[i] = spm_aln{kh[i].pos, kh[i].pos + m, kh[i].pattern, kh[i].score, begin_only ? 0u : cig_off[i],
-                                begin_only ? 0u : 1u};
-                if (!begin_only)
-                    A->host_ops[cig_off[i]] = (m << 4) | SPM_CIGAR_EQ;
-            }
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_seg_alns, sa.data(), nk * sizeof(spm_aln), hipMemcpyHostToDevice, st));
-            if (A->n_ops)
-                SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->d_ops, A->host_ops.data(), A->n_ops * 4, hipMemcpyHostToDevice, st));
-            SPM_HIP_CHECK(ctx, hipStreamSynchronize(st)); // (sa is read by the copy)
+            SPM_TRY(jst_fill_exact_alns(ctx, ps, kh, cig_off, begin_only, d_seg_alns, A.get()));
         }
         // ---- the fan-out: one record per (haplotype, hit), the transcript shared ----
         struct event_pair
@@ -1537,17 +1567,7 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
         A->host.resize(n);
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        // the order of spm_hip_jst_hits_view: (haplotype, pos, pattern, score), pos = end (Myers) / begin (exact)
-        std::sort(A->host.begin(), A->host.end(), [myers](const spm_jst_aln &a, const spm_jst_aln &b) {
-            if (a.haplotype != b.haplotype)
-                return a.haplotype < b.haplotype;
-            const uint64_t pa = myers ? a.end : a.begin, pb = myers ? b.end : b.begin;
-            if (pa != pb)
-                return pa < pb;
-            if (a.pattern != b.pattern)
-                return a.pattern < b.pattern;
-            return a.score < b.score;
-        });
+        jst_sort_alns_host(A->host, myers);
     } else if (n) {
         SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: %llu hits but no segment hit to align", (unsigned long long)n);
         return SPM_E_INVALID;

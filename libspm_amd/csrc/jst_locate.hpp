@@ -1,0 +1,478 @@
+// jst_locate.hpp -- begins and alignments of the records a pan-genome SELECTION kept (spm_hip_jst_selection_align; contract
+// in spm_hip.h, scheme in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst.hpp: it needs spm_jst and spm_jst_alns.
+//
+// jst_fanout_kernel is a bijection from (segment hit ending on an owned symbol, member haplotype of its context) to
+// haplotype record.  A selection keeps records, not segment hits, so the map is inverted per kept record from the tables of
+// the index, which are resident anyway:
+//   record (h, pattern, pos, score), last symbol l = pos - 1 (Myers) / pos + |P| - 1 (exact)
+//   block j of haplotype h that owns l:  hap_start[j][h] <= l < hap_start[j + 1][h]   (binary search down column h)
+//   context c = ctx_base[cell(j, h)] + (local_id[j][h] & 0x7FFF)
+//   ctx_lo(h) = hap_start[j][h] - min(window - 1, hap_start[j][h])
+//   segment hit (pattern, ctx_off[c] + pos - ctx_lo(h), score) in the context buffer.
+// Records of haplotypes that share a context land on the same segment hit: the DISTINCT ones are aligned once by the kernels
+// of align.hpp, then gathered, which preserves the sharing of the tree.
+//   jst_locate_kernel       one lane per kept record: the inversion, key = pattern << ctx_bits | context position
+//   (hipcub radix sort of (key, arrival index) over the key's bits)
+//   jst_locate_heads_kernel head flag of every run of equal keys; the scores of a run must agree
+//   (hipcub exclusive sum of the head flags: the number u of every distinct segment hit)
+//   jst_locate_emit_kernel  heads write the compact spm_hit list (already in pool order), every record uid[arrival] = u
+//   jst_aln_gather_kernel   one lane per kept record i: record i + seg_alns[uid[i]] -> the 40-byte spm_jst_aln i
+#pragma once
+
+#include "select_plan.hpp"
+
+namespace spm_hip
+{
+
+struct jst_locate_params
+{
+    const unsigned long long *recs; // the selection's records as 8-byte words, three each: pos | pattern << 32 + haplotype |
+                                    // reserved << 32 + score
+    uint32_t n;
+    // the index (all of it bounds-checked against the sizes below before it is read)
+    const uint64_t *hap_start; // [(n_blocks + 1) * n_hap]
+    const uint16_t *local_id;  // [(je - jb) * n_hap]
+    const uint64_t *ctx_base;  // [(je - jb) * n_groups + 1]
+    const uint64_t *ctx_off;   // [n_ctx + 1]
+    const uint32_t *ctx_owned; // [n_ctx]
+    uint64_t jb, je, n_ctx;
+    uint32_t n_hap, n_groups, window;
+    const int32_t *m;          // needle lengths [n_patterns]
+    uint32_t n_patterns;
+    uint32_t report_begin;     // exact sets: pos is the begin, the last symbol pos + |P| - 1
+    uint32_t ctx_bits;         // bits of a context position (<= ctx_bytes)
+    // out
+    unsigned long long *keys;  // [n] arrival order
+    uint32_t *idx;             // [n]
+    int32_t *score;            // [n]
+    unsigned long long *counts; // [0] distinct segment hits (emit), [1] records that cannot be located / disagree
+};
+
+// One lane per kept record.  The records are read as jst_select_keys_kernel reads them: 768 contiguous 8-byte words per
+// workgroup, handed to their lanes through LDS.  The selection's device order is haplotype-major, so the lanes of a wave
+// walk the same column of hap_start.  Every table index is tested against the table's size first: whatever a record holds,
+// the kernel reads inside the tables or counts an error.
+__global__ __launch_bounds__(256) void jst_locate_kernel(const jst_locate_params P)
+{
+    __shared__ unsigned long long s_w[3 * 256];
+    const unsigned long long base = (unsigned long long)blockIdx.x * 256ull;
+    const unsigned long long n_words = 3ull * P.n;
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+        const unsigned long long w = base * 3ull + r * 256u + threadIdx.x;
+        if (w < n_words)
+            s_w[r * 256u + threadIdx.x] = P.recs[w];
+    }
+    __syncthreads();
+    const unsigned long long i = base + threadIdx.x;
+    const bool valid = i < P.n;
+    bool ok = false;
+    unsigned long long key = ~0ull;
+    int32_t sc = 0;
+    if (valid) {
+        const unsigned long long pos = s_w[3 * threadIdx.x], w_hp = s_w[3 * threadIdx.x + 1];
+        const uint32_t h = (uint32_t)w_hp, pat = (uint32_t)(w_hp >> 32);
+        sc = (int32_t)(uint32_t)s_w[3 * threadIdx.x + 2];
+        ok = h < P.n_hap && pat < P.n_patterns && P.jb < P.je;
+        uint64_t last = 0;
+        if (ok) {
+            const uint64_t len = P.report_begin ? (uint64_t)max(P.m[pat], 0) : 0ull;
+            last = pos + len - 1;                     // exact: pos + |P| - 1; Myers: pos - 1
+            ok = pos + len >= 1 && pos + len >= pos;  // (pos = 0 of a Myers hit, or a wrap: no last symbol)
+        }
+        uint64_t j = P.jb;
+        if (ok) {
+            // the largest j in [jb, je] with hap_start[j][h] <= last (the column is non-decreasing; among equal starts the
+            // last one is the block that owns something)
+            uint64_t lo = P.jb, hi = P.je + 1; // hap_start[lo] <= last < hap_start[hi], once the first test holds
+            ok = P.hap_start[lo * P.n_hap + h] <= last;
+            while (ok && hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (P.hap_start[mid * P.n_hap + h] <= last)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            j = lo;
+            ok = ok && j < P.je; // (j == je: beyond the indexed blocks)
+        }
+        if (ok) {
+            const uint64_t jr = j - P.jb;
+            const uint16_t v = P.local_id[jr * P.n_hap + h];
+            const uint64_t cb = jr * P.n_groups + h / kJstGroup;
+            ok = v != kJstNone;
+            if (ok) {
+                const uint64_t c = P.ctx_base[cb] + (uint64_t)(v & 0x7FFFu);
+                ok = c < P.ctx_base[cb + 1] && c < P.n_ctx;
+                if (ok) {
+                    const uint64_t a = P.hap_start[j * P.n_hap + h];
+                    const uint64_t ctx_lo = a - min((uint64_t)(P.window ? P.window - 1 : 0), a);
+                    const uint64_t off = P.ctx_off[c], len_c = P.ctx_off[c + 1] - off;
+                    // the last symbol inside the context and not in its left context; the reported position inside it
+                    ok = pos >= ctx_lo && last >= ctx_lo && last - ctx_lo < len_c && last - ctx_lo >= P.ctx_owned[c];
+                    const uint64_t at = off + (pos - ctx_lo);
+                    ok = ok && (P.ctx_bits >= 64 || (at >> P.ctx_bits) == 0);
+                    if (ok)
+                        key = (P.ctx_bits < 64 ? (unsigned long long)pat << P.ctx_bits : 0ull) | at;
+                }
+            }
+        }
+        P.keys[i] = key; // (an unlocated record sorts last; the call fails before anything reads it)
+        P.idx[i] = (uint32_t)i;
+        P.score[i] = sc;
+    }
+    const unsigned long long bad = __ballot(valid && !ok);
+    if ((threadIdx.x & 63) == 0 && bad)
+        atomicAdd(&P.counts[1], (unsigned long long)__popcll(bad));
+}
+
+// One lane per sorted record: 1 where a run of equal keys begins.  Records of one run name the same segment hit, so their
+// scores agree; a run that disagrees is counted as an error (one atomic per wave).
+__global__ __launch_bounds__(256) void jst_locate_heads_kernel(const unsigned long long *__restrict__ keys,
+                                                                 const uint32_t *__restrict__ idx,
+                                                                 const int32_t *__restrict__ score, uint32_t n,
+                                                                 uint8_t *__restrict__ head, unsigned long long *counts)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const bool first = i == 0 || keys[i] != keys[i - 1];
+        head[i] = first ? 1 : 0;
+        bad = !first && score[idx[i]] != score[idx[i - 1]];
+    }
+    const unsigned long long m = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && m)
+        atomicAdd(&counts[1], (unsigned long long)__popcll(m));
+}
+
+struct jloc_head_op
+{
+    const uint8_t *head;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return head[i]; }
+};
+
+// offs: exclusive sum of the head flags.  The heads write the distinct segment hits, which the sort has put in pool order
+// (pattern, position in the context buffer); every record learns the number of its segment hit; the last lane writes the
+// count the host reads back.
+__global__ __launch_bounds__(256) void jst_locate_emit_kernel(const unsigned long long *__restrict__ keys,
+                                                                const uint32_t *__restrict__ idx,
+                                                                const int32_t *__restrict__ score,
+                                                                const uint8_t *__restrict__ head,
+                                                                const uint32_t *__restrict__ offs, uint32_t n, uint32_t ctx_bits,
+                                                                spm_hit *__restrict__ list, uint32_t *__restrict__ uid,
+                                                                unsigned long long *counts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t hd = head[i];
+    const uint32_t u = offs[i] + hd - 1u; // (offs[0] = 0 and head[0] = 1: never wraps)
+    const uint32_t from = idx[i];
+    if (hd) {
+        const unsigned long long key = keys[i];
+        spm_hit o;
+        o.pos = ctx_bits < 64 ? key & ((1ull << ctx_bits) - 1) : key;
+        o.pattern = ctx_bits < 64 ? (uint32_t)(key >> ctx_bits) : 0u;
+        o.score = score[from];
+        list[u] = o;
+    }
+    uid[from] = u;
+    if (i == n - 1)
+        counts[0] = (unsigned long long)u + 1ull;
+}
+
+// One lane per kept record i: its own record (through LDS, as above) and the alignment of its segment hit give the
+// spm_jst_aln i -- the haplotype's coordinates, the SHARED transcript.  The output index is the input index: no atomics, no
+// slot reservation.  A record is five 8-byte words; the 1280 words of a workgroup leave through LDS, contiguous per wave.
+__global__ __launch_bounds__(256) void jst_aln_gather_kernel(const unsigned long long *__restrict__ recs,
+                                                               const uint32_t *__restrict__ uid,
+                                                               const spm_aln *__restrict__ segs, uint32_t n, uint32_t n_segs,
+                                                               uint32_t report_begin, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long s_w[5 * 256];
+    const unsigned long long base = (unsigned long long)blockIdx.x * 256ull;
+    const unsigned long long n_in = 3ull * n, n_out = 5ull * n;
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+        const unsigned long long w = base * 3ull + r * 256u + threadIdx.x;
+        if (w < n_in)
+            s_w[r * 256u + threadIdx.x] = recs[w];
+    }
+    __syncthreads();
+    const unsigned long long i = base + threadIdx.x;
+    unsigned long long o[5] = {0, 0, 0, 0, 0};
+    if (i < n) {
+        const unsigned long long pos = s_w[3 * threadIdx.x], w_hp = s_w[3 * threadIdx.x + 1];
+        const uint32_t u = uid[i];
+        if (u < n_segs) {
+            const spm_aln a = segs[u];
+            const unsigned long long span = a.end - a.begin;
+            const unsigned long long end = report_begin ? pos + span : pos;
+            o[0] = end - span;                                                              // begin
+            o[1] = end;                                                                     // end
+            o[2] = w_hp;                                                                    // haplotype | pattern << 32
+            o[3] = (unsigned long long)(uint32_t)a.score | (unsigned long long)a.cigar_off << 32;
+            o[4] = (unsigned long long)a.cigar_len;                                         // cigar_len | reserved << 32
+        }
+    }
+    __syncthreads(); // every lane has read its record: the words may be overwritten
+#pragma unroll
+    for (uint32_t r = 0; r < 5; ++r)
+        s_w[5 * threadIdx.x + r] = o[r];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < 5; ++r) {
+        const unsigned long long w = base * 5ull + r * 256u + threadIdx.x;
+        if (w < n_out)
+            out[w] = s_w[r * 256u + threadIdx.x];
+    }
+}
+
+} // namespace spm_hip
+
+static_assert(sizeof(spm_jst_aln) == 5 * 8 && sizeof(spm_jst_hit) == 3 * 8 && sizeof(spm_aln) == 32, "word layouts of the gather");
+
+namespace
+{
+inline size_t jloc_align_up(size_t v) { return (v + 255) & ~size_t(255); }
+} // namespace
+
+extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_jst_alns **out)
+{
+    using namespace spm_hip;
+    if (!h || !out)
+        return SPM_E_INVALID;
+    spm_ctx *ctx = h->ctx;
+    if (flags & ~SPM_ALIGN_BEGIN_ONLY) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: unknown flag bits 0x%x", flags & ~SPM_ALIGN_BEGIN_ONLY);
+        return SPM_E_INVALID;
+    }
+    const auto t_call = clk::now();
+    if (!h->selected) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: these hits are a search's own result, not a selection; align them with "
+                         "spm_hip_jst_hits_align, or select them first (a selection without flags is a sorted copy)");
+        return SPM_E_INVALID;
+    }
+    if (!h->jst || !h->patterns) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: this selection was made from a raw record buffer "
+                         "(spm_hip_jst_records_select): it names no tree, and its records may stem from several block shards");
+        return SPM_E_INVALID;
+    }
+    spm_jst *J = h->jst;
+    const spm_patterns *ps = h->patterns;
+    if (!J->indexed || J->generation != h->generation) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: the tree has been indexed again since this search (its context buffer is "
+                         "gone); search and select again");
+        return SPM_E_INVALID;
+    }
+    const bool begin_only = (flags & SPM_ALIGN_BEGIN_ONLY) != 0;
+    const bool myers = ps->is_myers();
+    const uint64_t n = h->n;
+    const jst_locate_plan plan = plan_jst_locate(n, ps->n, J->ctx_bytes); // decided before any launch
+    if (plan.status != SPM_OK) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: %s (%u + %u bits)", plan.why, plan.pat_bits, plan.ctx_bits);
+        return plan.status;
+    }
+    const uint32_t ctx_bits = plan.ctx_bits;
+    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<spm_jst_alns, void (*)(spm_jst_alns *)> A(new spm_jst_alns, spm_hip_jst_alns_destroy);
+    A->ctx = ctx;
+    A->n = n;
+    A->stats.n_alns = n;
+    hipStream_t st = ctx->stream;
+    uint64_t nk = 0;
+    float ms_locate = 0, ms_gather = 0;
+    if (n) {
+        const uint32_t n32 = (uint32_t)n;
+        const int key_bits = (int)plan.key_bits;
+        struct event_set
+        {
+            hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+            ~event_set()
+            {
+                for (hipEvent_t x : e)
+                    if (x)
+                        hipEventDestroy(x);
+            }
+        } ev;
+        for (hipEvent_t &e : ev.e)
+            SPM_HIP_CHECK(ctx, hipEventCreate(&e));
+        // the scratch of locate + order: keys and indices twice (the sort's in and out), scores, head flags, their sums, the
+        // counts, the distinct hits.  uid and the records outlive align_run, which may grow the context's scratch: they are
+        // buffers of their own.
+        size_t sort_bytes = 0, scan_bytes = 0;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr,
+                                                              (unsigned long long *)nullptr, (const uint32_t *)nullptr,
+                                                              (uint32_t *)nullptr, (size_t)n32, 0, key_bits, st));
+        using count_iter = hipcub::CountingInputIterator<uint32_t>;
+        using head_iter = hipcub::TransformInputIterator<uint32_t, jloc_head_op, count_iter>;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, head_iter(count_iter(0), jloc_head_op{nullptr}),
+                                                            (uint32_t *)nullptr, (size_t)n32, st));
+        const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            const size_t at = off;
+            off += jloc_align_up(bytes);
+            return at;
+        };
+        const size_t o_keys0 = take(n * 8), o_keys1 = take(n * 8), o_idx0 = take(n * 4), o_idx1 = take(n * 4),
+                     o_score = take(n * 4), o_head = take(n), o_offs = take(n * 4), o_counts = take(16),
+                     o_tmp = take(tmp_bytes), o_list = take(n * sizeof(spm_hit));
+        SPM_TRY(ensure_scratch(ctx, off));
+        uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
+        unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + o_keys0);
+        unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + o_keys1);
+        uint32_t *idx_in = reinterpret_cast<uint32_t *>(base + o_idx0), *idx = reinterpret_cast<uint32_t *>(base + o_idx1);
+        int32_t *score = reinterpret_cast<int32_t *>(base + o_score);
+        uint8_t *head = base + o_head;
+        uint32_t *offs = reinterpret_cast<uint32_t *>(base + o_offs);
+        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + o_counts);
+        spm_hit *d_list = reinterpret_cast<spm_hit *>(base + o_list);
+        dev_scratch tmp;
+        uint32_t *d_uid = nullptr;
+        spm_aln *d_seg_alns = nullptr;
+        SPM_HIP_CHECK(ctx, tmp.alloc(&d_uid, n * 4));
+        SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_jst_aln)));
+
+        jst_locate_params P{};
+        P.recs = reinterpret_cast<const unsigned long long *>(h->d);
+        P.n = n32;
+        P.hap_start = J->d_hap_start;
+        P.local_id = J->d_local_id;
+        P.ctx_base = J->d_ctx_base;
+        P.ctx_off = J->d_ctx_off;
+        P.ctx_owned = J->d_ctx_owned;
+        P.jb = J->jb;
+        P.je = J->je;
+        P.n_ctx = J->n_ctx;
+        P.n_hap = J->H;
+        P.n_groups = (J->H + kJstGroup - 1) / kJstGroup;
+        P.window = J->window;
+        P.m = ps->d_m;
+        P.n_patterns = ps->n;
+        P.report_begin = myers ? 0 : 1;
+        P.ctx_bits = ctx_bits;
+        P.keys = keys_in;
+        P.idx = idx_in;
+        P.score = score;
+        P.counts = d_counts;
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 16, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[0], st));
+        hipLaunchKernelGGL(jst_locate_kernel, dim3(grid), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        size_t tb = tmp_bytes;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, (const unsigned long long *)keys_in, keys,
+                                                              (const uint32_t *)idx_in, idx, (size_t)n32, 0, key_bits, st));
+        hipLaunchKernelGGL(jst_locate_heads_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
+                           (const uint32_t *)idx, (const int32_t *)score, n32, head, d_counts);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        tb = tmp_bytes;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, head_iter(count_iter(0), jloc_head_op{head}), offs,
+                                                            (size_t)n32, st));
+        hipLaunchKernelGGL(jst_locate_emit_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
+                           (const uint32_t *)idx, (const int32_t *)score, (const uint8_t *)head, (const uint32_t *)offs, n32,
+                           ctx_bits, d_list, d_uid, d_counts);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[1], st));
+        // the one read-back: {distinct, errors}; the context tables travel with it, once per index generation
+        unsigned long long *c = ctx->h_counters;
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, 16, hipMemcpyDeviceToHost, st));
+        SPM_TRY(J->fetch_ctx_tables());
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        J->h_generation = J->generation;
+        const auto t_list = clk::now();
+        nk = c[0];
+        const unsigned long long n_bad = c[1];
+        if (n_bad || nk == 0 || nk > n) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: %llu of %llu records cannot be located in the indexed blocks of "
+                             "their tree (last symbol outside them, a cell that owns nothing, a position outside the owned "
+                             "part of its context, or haplotypes that disagree on a shared hit's score); nothing was aligned",
+                        n_bad ? n_bad : (unsigned long long)n, (unsigned long long)n);
+            return SPM_E_INVALID;
+        }
+        // ---- the distinct segment hits, already in pool order; lo = the start of the hit's context ----
+        std::vector<spm_hit> kh(nk);
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(kh.data(), d_list, nk * sizeof(spm_hit), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        const std::vector<uint64_t> &coff = J->h_ctx_off;
+        std::vector<uint64_t> lo(nk);
+        std::vector<uint32_t> cig_off(nk, 0);
+        uint64_t total_ops = 0;
+        for (uint64_t i = 0; i < nk; ++i) {
+            const spm_hit &x = kh[i];
+            const uint64_t last = x.pattern >= ps->n ? ~0ull : myers ? x.pos - 1 : x.pos + (uint64_t)ps->m[x.pattern] - 1;
+            if (last >= J->ctx_bytes) { // (pattern and position: the locate kernel has tested both)
+                SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: segment hit %llu lies outside the context buffer", (unsigned long long)i);
+                return SPM_E_INVALID;
+            }
+            lo[i] = coff[(uint64_t)(std::upper_bound(coff.begin(), coff.begin() + (long)J->n_ctx, last) - coff.begin()) - 1];
+            cig_off[i] = (uint32_t)total_ops;
+            total_ops += myers ? 2 * (uint64_t)std::max(0, x.score) + 1 : 1;
+        }
+        if (total_ops > 0xFFFFFFFFull) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: the CIGAR pool would exceed 2^32 words");
+            return SPM_E_UNSUPPORTED;
+        }
+        A->n_ops = begin_only ? 0 : total_ops;
+        A->host_ops.resize(A->n_ops);
+        A->stats.ms_worklist = ms_since(t_list);
+        SPM_HIP_CHECK(ctx, tmp.alloc(&d_seg_alns, nk * sizeof(spm_aln)));
+        if (A->n_ops)
+            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
+        if (myers) {
+            align_work W{};
+            W.ps = ps;
+            W.text = J->ctx_text;
+            W.pos_offset = 0;
+            W.hits = kh.data();
+            W.n = nk;
+            W.lo = lo.data();
+            W.cig_off = cig_off.data();
+            W.begin_only = begin_only;
+            W.d_recs = d_seg_alns;
+            W.d_ops = A->d_ops;
+            W.n_ops = A->n_ops;
+            W.h_ops = A->host_ops.data();
+            W.who = "spm_hip_jst_selection_align";
+            spm_align_stats as{};
+            SPM_TRY(align_run(ctx, W, as));
+            A->stats.ms_begin = as.ms_begin;
+            A->stats.ms_cigar = as.ms_cigar;
+            A->stats.begin_lane = as.begin_lane;
+            A->stats.begin_wave = as.begin_wave;
+            A->stats.cigar_lane = as.cigar_lane;
+            A->stats.cigar_wave = as.cigar_wave;
+            A->stats.cigar_wave_global = as.cigar_wave_global;
+        } else {
+            SPM_TRY(jst_fill_exact_alns(ctx, ps, kh, cig_off, begin_only, d_seg_alns, A.get()));
+        }
+        // ---- the gather: record i of the selection's device view -> alignment record i ----
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[2], st));
+        hipLaunchKernelGGL(jst_aln_gather_kernel, dim3(grid), dim3(256), 0, st, P.recs, (const uint32_t *)d_uid,
+                           (const spm_aln *)d_seg_alns, n32, (uint32_t)nk, P.report_begin,
+                           reinterpret_cast<unsigned long long *>(A->d_recs));
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[3], st));
+        A->host.resize(n);
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        hipEventElapsedTime(&ms_locate, ev.e[0], ev.e[1]);
+        hipEventElapsedTime(&ms_gather, ev.e[2], ev.e[3]);
+        const auto t_sort = clk::now();
+        jst_sort_alns_host(A->host, myers);
+        A->stats.ms_worklist += ms_since(t_sort);
+    }
+    A->stats.ms_fanout = ms_locate + ms_gather;
+    A->stats.ms_total = A->stats.ms_begin + A->stats.ms_cigar + A->stats.ms_fanout;
+    A->stats.n_segment_alns = nk;
+    A->stats.n_ops = A->n_ops;
+    A->stats.ms_host = ms_since(t_call);
+    if (spm_trace_on())
+        fprintf(stderr, "[spm_hip] jst selection align: %llu kept records -> %llu segment alignments%s: locate + order %.3f ms, "
+                        "begins %.3f, transcripts %.3f, gather %.3f; %.3f ms in all (work list %.3f)\n", (unsigned long long)n,
+                (unsigned long long)nk, begin_only ? " (begins only)" : "", ms_locate, A->stats.ms_begin, A->stats.ms_cigar,
+                ms_gather, A->stats.ms_host, A->stats.ms_worklist);
+    *out = A.release();
+    return SPM_OK;
+}

@@ -17,6 +17,8 @@ struct jsel_source // what the two entry points know about their records
     uint64_t n = 0;
     uint64_t n_hap = 1, n_patterns = 1, max_pos = 0;
     const spm_patterns *ps = nullptr; // may be null (records)
+    spm_jst *jst = nullptr;           // the tree and index generation of the search the records stem from (records: none):
+    uint64_t generation = 0;          // what spm_hip_jst_selection_align locates the kept records in
 };
 
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
@@ -168,8 +170,10 @@ int jsel_make(spm_ctx *ctx, const jsel_source &S, const spm_select_opts *opts, c
     SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<spm_jst_hits, void (*)(spm_jst_hits *)> R(new spm_jst_hits, spm_hip_jst_hits_destroy);
     R->ctx = ctx;
-    R->selected = true; // (not alignable, whatever the source was: spm_hip_jst_hits_align says so)
+    R->selected = true; // (spm_hip_jst_hits_align refuses it, whatever the source was: spm_hip_jst_selection_align takes it)
     R->patterns = S.ps;
+    R->jst = S.jst;
+    R->generation = S.generation;
     R->sel_n_hap = S.n_hap;
     R->sel_n_patterns = S.n_patterns;
     R->sel_max_pos = S.max_pos;
@@ -202,6 +206,8 @@ extern "C" int spm_hip_jst_hits_select(spm_jst_hits *h, const spm_select_opts *o
     S.d_recs = h->d;
     S.n = h->n;
     S.ps = h->patterns;
+    S.jst = h->jst;
+    S.generation = h->generation;
     S.n_hap = std::max<uint64_t>(h->sel_n_hap, 1);
     S.n_patterns = std::max<uint64_t>(h->sel_n_patterns, 1);
     S.max_pos = h->sel_max_pos;

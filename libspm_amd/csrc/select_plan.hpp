@@ -155,4 +155,33 @@ inline jst_select_plan plan_jst_select(const spm_select_opts &o, uint64_t n_reco
     return P;
 }
 
+// ---- spm_hip_jst_selection_align: the kept records of a pan-genome selection are ordered by the segment hit they map to,
+// key = pattern << ctx_bits | position in the context buffer (positions run up to ctx_symbols inclusive: an exclusive end).
+struct jst_locate_plan
+{
+    int status = SPM_OK;
+    const char *why = "";
+    uint32_t pat_bits = 0, ctx_bits = 0;
+    uint32_t key_bits = 0; // what the radix sort looks at (at least 1)
+};
+
+inline jst_locate_plan plan_jst_locate(uint64_t n_records, uint64_t n_patterns, uint64_t ctx_symbols)
+{
+    jst_locate_plan P;
+    P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
+    P.ctx_bits = bits_for(ctx_symbols);
+    if (n_records > 0xFFFFFFFFull) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "more than 2^32 - 1 records";
+        return P;
+    }
+    if (P.pat_bits + P.ctx_bits > 64) {
+        P.status = SPM_E_UNSUPPORTED;
+        P.why = "pattern index and context position do not fit a 64-bit sort key";
+        return P;
+    }
+    P.key_bits = std::max(1u, P.pat_bits + P.ctx_bits);
+    return P;
+}
+
 } // namespace spm_hip

@@ -527,13 +527,26 @@ class JstHits:
                self.ctx._h)
         return JstAlignments(self.ctx, a)
 
+    def align_selected(self, begin_only: bool = False) -> "JstAlignments":
+        """Begin + CIGAR transcript of the records this SELECTION kept (spm_hip_jst_selection_align): the kept records are
+        located in the tree's index, their distinct segment hits aligned once and shared.  Record i of the result's view()
+        belongs to view() record i of this selection, and record i of its device() to record i of this selection's
+        device(), in (haplotype, pattern, pos) order.  The search need not have been alignable and may be closed; the tree
+        and the needle set must be open, and the tree not indexed again since the search."""
+        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
+            raise capi.SpmError("JstHits.align_selected: the tree or the needle set of this selection has been closed")
+        a = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_selection_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
+               self.ctx._h)
+        return JstAlignments(self.ctx, a)
+
     def select(self, loci: bool = True, window: int | None = None, best: int | None = None,
                across: bool = False) -> "JstHits":
         """A new, smaller JstHits (spm_hip_jst_hits_select): one record per locus of every haplotype (loci; window=None:
         every needle's own k) and, with best=s, only the records within s errors of the minimum of their (haplotype,
         needle) -- with across=True, of their needle on all haplotypes.  The device view of the result is sorted by
-        (haplotype, pattern, pos), its host view as every view(); it stays valid after this object is closed, and it
-        cannot be aligned."""
+        (haplotype, pattern, pos), its host view as every view(); it stays valid after this object is closed.  align()
+        does not take it; align_selected() aligns the records it kept."""
         if self._pats is not None and not self._pats._h:
             raise capi.SpmError("JstHits.select: the needle set of these hits has been closed")
         opts = _select_opts(loci, window, best, across)
@@ -604,7 +617,8 @@ class JstAlignments:
         return np.frombuffer(buf, dtype=np.uint32).copy()
 
     def device(self):
-        """(records, n, ops, n_ops): device pointers, records in the arrival order of the alignment fan-out."""
+        """(records, n, ops, n_ops): device pointers.  From JstHits.align(): records in the arrival order of the alignment
+        fan-out.  From JstHits.align_selected(): record i matched to record i of the selection's device()."""
         r, o = C.c_void_p(), C.c_void_p()
         n, n_ops = C.c_uint64(), C.c_uint64()
         _check(capi.lib().spm_hip_jst_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)),
