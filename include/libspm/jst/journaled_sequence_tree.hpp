@@ -55,6 +55,16 @@ struct jst_alignment
     bool operator==(jst_alignment const &) const noexcept = default;
 };
 
+// the same alignment against the REFERENCE of the tree (journaled_sequence_tree::locate_reference): SAM POS, CIGAR and NM
+struct jst_ref_alignment
+{
+    std::uint32_t haplotype;
+    std::uint32_t needle;
+    spm::alignment aln;             // reference coordinates, errors = ref_score (X + I + D of the projected transcript)
+    std::int32_t haplotype_errors;  // the distance on the haplotype, as locate reports it
+    bool operator==(jst_ref_alignment const &) const noexcept = default;
+};
+
 struct jst_search_stats
 {
     std::uint64_t haplotype_symbols{}; // sum of haplotype lengths (what per-haplotype scans would read)
@@ -472,59 +482,148 @@ public:
                                              hip::hit_selection const & selection, std::size_t block = 0,
                                              jst_search_stats * stats = nullptr) const
     {
-        spm_ctx * ctx = hip::default_context();
-        spm_jst_hits * hh = device_search(needles, window, block, 0, stats); // (need not be alignable)
-        spm_select_opts o{};
-        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
-                  (selection.across ? SPM_SELECT_ACROSS : 0u);
-        o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
-        o.strata = selection.strata.value_or(0u);
-        spm_jst_hits * sel = nullptr;
-        if (spm_hip_jst_hits_select(hh, &o, &sel) != SPM_OK)
-            hip::fatal("spm_hip_jst_hits_select", ctx);
-        spm_hip_jst_hits_destroy(hh); // (the selection stays alignable without its source)
-        spm_jst_alns * a = nullptr;
-        if (spm_hip_jst_selection_align(sel, 0, &a) != SPM_OK)
-            hip::fatal("spm_hip_jst_selection_align", ctx);
-        spm_hip_jst_hits_destroy(sel);
-        hip::jst_alns_ptr alns{a};
-        spm_jst_aln const * rec = nullptr;
-        std::uint32_t const * ops = nullptr;
-        std::uint64_t n = 0, n_ops = 0;
-        if (spm_hip_jst_alns_view(a, &rec, &n, &ops, &n_ops) != SPM_OK)
-            hip::fatal("spm_hip_jst_alns_view", ctx);
-        std::vector<jst_alignment> out;
-        out.reserve(n);
-        for (std::uint64_t i = 0; i < n; ++i)
-            out.push_back({rec[i].haplotype, rec[i].pattern,
-                           alignment{static_cast<std::size_t>(rec[i].begin), static_cast<std::size_t>(rec[i].end), rec[i].score,
-                                     ops + rec[i].cigar_off, rec[i].cigar_len}});
-        sort_alignments(out, reports_begin);
-        return out;
+        return alignments_of(device_alns(needles, window, selection, block, stats).get(), reports_begin);
     }
 
     std::vector<jst_alignment> locate_device(spm_patterns * needles, std::size_t window, bool reports_begin,
                                              std::size_t block = 0, jst_search_stats * stats = nullptr) const
     {
-        spm_ctx * ctx = hip::default_context();
-        spm_jst_hits * hh = device_search(needles, window, block, SPM_SCAN_ALIGNABLE, stats);
-        spm_jst_alns * a = nullptr;
-        if (spm_hip_jst_hits_align(hh, 0, &a) != SPM_OK)
-            hip::fatal("spm_hip_jst_hits_align", ctx);
-        hip::jst_alns_ptr alns{a};
-        spm_jst_aln const * rec = nullptr;
-        std::uint32_t const * ops = nullptr;
-        std::uint64_t n = 0, n_ops = 0;
-        if (spm_hip_jst_alns_view(a, &rec, &n, &ops, &n_ops) != SPM_OK)
-            hip::fatal("spm_hip_jst_alns_view", ctx);
-        std::vector<jst_alignment> out;
-        out.reserve(n);
-        for (std::uint64_t i = 0; i < n; ++i)
-            out.push_back({rec[i].haplotype, rec[i].pattern,
-                           alignment{static_cast<std::size_t>(rec[i].begin), static_cast<std::size_t>(rec[i].end), rec[i].score,
-                                     ops + rec[i].cigar_off, rec[i].cigar_len}});
-        spm_hip_jst_hits_destroy(hh);
-        sort_alignments(out, reports_begin);
+        return alignments_of(device_alns(needles, window, block, stats).get(), reports_begin);
+    }
+
+    // ---- locate in REFERENCE coordinates: every alignment of locate projected through the alleles its haplotype carries
+    // (the contract of spm_hip_jst_alns_project in spm_hip.h), in locate's order.  needle_ranks: the needles' symbols -- an X of
+    // the haplotype transcript may be an = against the reference, which only the symbols tell.  Device route: locate_device
+    // followed by the projection, once per shared transcript.  Trees the device path does not take: the result of locate_host,
+    // projected on the host through the journal (project_host, a route of its own: it looks every haplotype position up in
+    // the event table instead of walking a cursor).  Both return the same vector.
+    std::vector<jst_ref_alignment> locate_reference(spm_patterns * needles, std::size_t window,
+                                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                                    std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_device(needles, window, reports_begin, block, stats);
+        return locate_reference_host(needles, window, needle_ranks, reports_begin, block, stats);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference(spm_patterns * needles, std::size_t window,
+                                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                                    hip::hit_selection const & selection, std::size_t block = 0,
+                                                    jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_device(needles, window, reports_begin, selection, block, stats);
+        return locate_reference_host(needles, window, needle_ranks, reports_begin, selection, block, stats);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_device(spm_patterns * needles, std::size_t window, bool reports_begin,
+                                                           std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return projections_of(device_alns(needles, window, block, stats).get(), reports_begin);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_device(spm_patterns * needles, std::size_t window, bool reports_begin,
+                                                           hip::hit_selection const & selection, std::size_t block = 0,
+                                                           jst_search_stats * stats = nullptr) const
+    {
+        return projections_of(device_alns(needles, window, selection, block, stats).get(), reports_begin);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_host(spm_patterns * needles, std::size_t window,
+                                                         std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                         bool reports_begin, std::size_t block = 0,
+                                                         jst_search_stats * stats = nullptr) const
+    {
+        return project_host(locate_host(needles, window, lengths_of(needle_ranks), reports_begin, block, stats), needle_ranks);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_host(spm_patterns * needles, std::size_t window,
+                                                         std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                         bool reports_begin, hip::hit_selection const & selection,
+                                                         std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return project_host(locate_selected_host(needles, window, lengths_of(needle_ranks), reports_begin, selection, block, stats),
+                            needle_ranks);
+    }
+
+    // The projection on the host.  Haplotype position x is looked up in the event table of its haplotype: inside the alt of
+    // allele (p, rend, alt) at offset k it is paired with p + k while k < rend - p and inserted with anchor p + min(rend - p,
+    // |alt|) beyond; in a reference run it is paired with x minus the shift of the alleles before it.
+    std::vector<jst_ref_alignment> project_host(std::vector<jst_alignment> const & alns,
+                                                std::vector<std::vector<std::uint8_t>> const & needle_ranks) const
+    {
+        std::vector<jst_ref_alignment> out;
+        out.reserve(alns.size());
+        std::uint32_t cached = ~0u;
+        hap_events E;
+        for (jst_alignment const & a : alns) {
+            if (a.haplotype != cached) { // (locate's order is haplotype-major)
+                E = events_of(a.haplotype);
+                cached = a.haplotype;
+            }
+            std::vector<std::uint8_t> const & P = needle_ranks[a.needle];
+            std::vector<std::uint32_t> words;
+            auto put = [&words](std::uint32_t op, std::uint64_t n) {
+                if (n == 0)
+                    return;
+                if (!words.empty() && (words.back() & 15u) == op)
+                    words.back() += static_cast<std::uint32_t>(n << 4);
+                else
+                    words.push_back(static_cast<std::uint32_t>(n << 4) | op);
+            };
+            std::uint64_t x = a.aln.begin_position(), first = 0, prev = 0, cost = 0;
+            std::size_t i = 0;
+            bool have = false;
+            auto where = [&](std::uint64_t hx, bool & paired) { // the reference position or the anchor of haplotype symbol hx
+                std::size_t const n = static_cast<std::size_t>(std::upper_bound(E.hs.begin(), E.hs.end(), hx) - E.hs.begin());
+                paired = true;
+                if (n == 0)
+                    return hx;
+                std::uint64_t const al = _variants.alleles[E.id[n - 1]].alt.size(), rl = E.rend[n - 1] - E.p[n - 1];
+                std::uint64_t const k = hx - E.hs[n - 1];
+                if (k >= al)
+                    return static_cast<std::uint64_t>(static_cast<std::int64_t>(hx) - E.cs[n - 1]);
+                paired = k < rl;
+                return E.p[n - 1] + (paired ? k : std::min(rl, al));
+            };
+            bool paired = true;
+            std::uint64_t const anchor = x < E.length ? where(x, paired) : _reference.size();
+            for (std::uint32_t const w : a.aln.cigar())
+                for (std::uint32_t c = 0; c < (w >> 4); ++c) {
+                    std::uint32_t const op = w & 15u;
+                    if (op == SPM_CIGAR_INS) {
+                        put(SPM_CIGAR_INS, 1);
+                        ++cost, ++i;
+                        continue;
+                    }
+                    std::uint64_t const rho = where(x++, paired);
+                    if (paired) {
+                        if (have) {
+                            put(SPM_CIGAR_DEL, rho - prev - 1);
+                            cost += rho - prev - 1;
+                        } else {
+                            first = rho;
+                        }
+                        have = true;
+                        prev = rho;
+                        if (op == SPM_CIGAR_DEL) {
+                            put(SPM_CIGAR_DEL, 1);
+                            ++cost;
+                        } else {
+                            bool const eq = P[i++] == _reference[rho];
+                            put(eq ? SPM_CIGAR_EQ : SPM_CIGAR_X, 1);
+                            cost += eq ? 0 : 1;
+                        }
+                    } else if (op != SPM_CIGAR_DEL) {
+                        put(SPM_CIGAR_INS, 1);
+                        ++cost, ++i;
+                    }
+                }
+            out.push_back({a.haplotype, a.needle,
+                           alignment{static_cast<std::size_t>(have ? first : anchor), static_cast<std::size_t>(have ? prev + 1 : anchor),
+                                     static_cast<int>(cost), words.data(), words.size()},
+                           static_cast<std::int32_t>(a.aln.errors())});
+        }
         return out;
     }
 
@@ -557,6 +656,98 @@ public:
     }
 
 private:
+    static std::vector<std::uint32_t> lengths_of(std::vector<std::vector<std::uint8_t>> const & needle_ranks)
+    {
+        std::vector<std::uint32_t> len;
+        for (auto const & nd : needle_ranks)
+            len.push_back(static_cast<std::uint32_t>(nd.size()));
+        return len;
+    }
+
+    // the device alignments of a search: of every hit (the search is made alignable) ...
+    hip::jst_alns_ptr device_alns(spm_patterns * needles, std::size_t window, std::size_t block, jst_search_stats * stats) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, SPM_SCAN_ALIGNABLE, stats);
+        spm_jst_alns * a = nullptr;
+        if (spm_hip_jst_hits_align(hh, 0, &a) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_align", ctx);
+        spm_hip_jst_hits_destroy(hh);
+        return hip::jst_alns_ptr{a};
+    }
+
+    // ... and of the hits a selection keeps
+    hip::jst_alns_ptr device_alns(spm_patterns * needles, std::size_t window, hip::hit_selection const & selection,
+                                  std::size_t block, jst_search_stats * stats) const
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_hits * hh = device_search(needles, window, block, 0, stats); // (need not be alignable)
+        spm_select_opts o{};
+        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
+                  (selection.across ? SPM_SELECT_ACROSS : 0u);
+        o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
+        o.strata = selection.strata.value_or(0u);
+        spm_jst_hits * sel = nullptr;
+        if (spm_hip_jst_hits_select(hh, &o, &sel) != SPM_OK)
+            hip::fatal("spm_hip_jst_hits_select", ctx);
+        spm_hip_jst_hits_destroy(hh); // (the selection stays alignable without its source)
+        spm_jst_alns * a = nullptr;
+        if (spm_hip_jst_selection_align(sel, 0, &a) != SPM_OK)
+            hip::fatal("spm_hip_jst_selection_align", ctx);
+        spm_hip_jst_hits_destroy(sel);
+        return hip::jst_alns_ptr{a};
+    }
+
+    static std::vector<jst_alignment> alignments_of(spm_jst_alns * a, bool reports_begin)
+    {
+        spm_jst_aln const * rec = nullptr;
+        std::uint32_t const * ops = nullptr;
+        std::uint64_t n = 0, n_ops = 0;
+        if (spm_hip_jst_alns_view(a, &rec, &n, &ops, &n_ops) != SPM_OK)
+            hip::fatal("spm_hip_jst_alns_view", hip::default_context());
+        std::vector<jst_alignment> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            out.push_back({rec[i].haplotype, rec[i].pattern,
+                           alignment{static_cast<std::size_t>(rec[i].begin), static_cast<std::size_t>(rec[i].end), rec[i].score,
+                                     ops + rec[i].cigar_off, rec[i].cigar_len}});
+        sort_alignments(out, reports_begin);
+        return out;
+    }
+
+    // the projection of device alignments, in the order alignments_of gives the alignments themselves: record i of the
+    // projection's host view belongs to record i of the source's
+    static std::vector<jst_ref_alignment> projections_of(spm_jst_alns * a, bool reports_begin)
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_ref_alns * r = nullptr;
+        if (spm_hip_jst_alns_project(a, 0, &r) != SPM_OK)
+            hip::fatal("spm_hip_jst_alns_project", ctx);
+        std::unique_ptr<spm_jst_ref_alns, decltype(&spm_hip_jst_ref_alns_destroy)> owner{r, &spm_hip_jst_ref_alns_destroy};
+        spm_jst_aln const * src = nullptr;
+        spm_jst_ref_aln const * rec = nullptr;
+        std::uint32_t const * ops = nullptr;
+        std::uint64_t n = 0, n_src = 0, n_ops = 0;
+        if (spm_hip_jst_alns_view(a, &src, &n_src, nullptr, nullptr) != SPM_OK ||
+            spm_hip_jst_ref_alns_view(r, &rec, &n, &ops, &n_ops) != SPM_OK || n != n_src)
+            hip::fatal("spm_hip_jst_ref_alns_view", ctx);
+        std::vector<std::uint64_t> order(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            order[i] = i;
+        auto key = [&](std::uint64_t i) {
+            return std::tuple{src[i].haplotype, reports_begin ? src[i].begin : src[i].end, src[i].pattern, src[i].score};
+        };
+        std::sort(order.begin(), order.end(), [&](std::uint64_t x, std::uint64_t y) { return key(x) < key(y); });
+        std::vector<jst_ref_alignment> out;
+        out.reserve(n);
+        for (std::uint64_t const i : order)
+            out.push_back({rec[i].haplotype, rec[i].pattern,
+                           alignment{static_cast<std::size_t>(rec[i].ref_begin), static_cast<std::size_t>(rec[i].ref_end),
+                                     rec[i].ref_score, ops + rec[i].cigar_off, rec[i].cigar_len},
+                           rec[i].score});
+        return out;
+    }
+
     // index (once per (window, block)) and search on the device; the caller owns the result
     spm_jst_hits * device_search(spm_patterns * needles, std::size_t window, std::size_t block, std::uint32_t flags,
                                  jst_search_stats * stats) const

@@ -519,6 +519,87 @@ void spm_hip_jst_alns_destroy(spm_jst_alns *a);
  * flags: SPM_ALIGN_BEGIN_ONLY */
 int spm_hip_jst_selection_align(spm_jst_hits *selection, uint32_t flags, spm_jst_alns **out);
 
+/* ---- pan-genome alignments in reference coordinates: SAM POS, CIGAR and NM of what the two calls above return -------------
+ * spm_hip_jst_hits_align and spm_hip_jst_selection_align end at begin, end and a transcript in the coordinates of ONE
+ * haplotype.  This call projects them through the alleles that haplotype carries onto the reference of the tree.
+ *
+ * Journal of haplotype h.  The carried alleles are applied in table order.  A carried allele (pos p, ref_len r, alt a[0..al))
+ * pairs its first min(r, al) alt symbols with the reference positions p .. p + min - 1.  If al > r the remaining al - r alt
+ * symbols are INSERTED: they have no reference position, and their ANCHOR is p + min(r, al).  If r > al the reference positions
+ * p + al .. p + r - 1 are DELETED.  Every other haplotype symbol is paired with the reference position it was copied from.
+ *
+ * Projection of a record (h, begin, end, transcript of P against hap[begin, end)).  Walk the transcript with a haplotype
+ * cursor x = begin and a needle cursor i = 0:
+ *     transcript column | hap[x] paired with rho                          | hap[x] inserted
+ *     = / X             | = if P[i] == ref[rho], else X; consumes rho     | I
+ *     D                 | D; consumes rho                                 | nothing
+ *     I                 | I                                               | I
+ * Before every column that consumes a reference position rho, except the first such column, rho - rho_prev - 1 D columns are
+ * emitted: the reference positions a carried allele deleted between the two.  Nothing else ever emits them, so leading and
+ * trailing deleted stretches are not part of the alignment.
+ *   * Adjacent equal ops are merged; words are len << 4 | op with the SPM_CIGAR_* values above.
+ *   * ref_begin is the first consumed rho, ref_end the last consumed rho plus 1.
+ *   * If no column consumes a reference position the alignment lies wholly inside one inserted stretch: the transcript is
+ *     |P| I, and ref_begin = ref_end = the anchor of hap[begin].
+ *   * ref_score is the number of X, I and D symbols of the projected transcript (SAM NM); score stays the haplotype distance.
+ *   * = / X compare ranks, as everywhere else (dna5 / dna15 included).
+ * It follows that the projected transcript consumes exactly P and ref[ref_begin, ref_end).
+ * Example, ref = AACCGGTTAACC, one carried allele each (every haplotype transcript is a single = run):
+ *     SNP at pos 5, G->T                     CGTT  = hap[3,7)   2=1X1=     [3,7)  ref_score 1
+ *     deletion at pos 4, ref_len 2           CCTT  = hap[2,6)   2=2D2=     [2,8)  2
+ *     insertion at pos 4, ref_len 0, alt TTT CTTTG = hap[3,8)   1=3I1=     [3,5)  3
+ *     the same insertion                     TT    = hap[4,6)   2I         [4,4)  2
+ *     replacement at pos 4, GG->TAC          CTACT = hap[3,8)   1=2X1I1=   [3,7)  3
+ *
+ *   * Accepted: the result of spm_hip_jst_hits_align or of spm_hip_jst_selection_align, Myers and exact sets.  Tree and
+ *     needle set must still be alive.
+ *   * Refused with SPM_E_INVALID and a message that says why: alignments made with SPM_ALIGN_BEGIN_ONLY (there is no
+ *     transcript to project); a tree that has been indexed again since the search (the rule of the align calls: the tables
+ *     the projection walks belong to an index generation); unknown flag bits; NULL arguments.
+ *   * Host view: record i belongs to record i of spm_hip_jst_alns_view of the source.  Device view: record i belongs to
+ *     record i of spm_hip_jst_alns_device of the source.  Two calls give byte-identical host views (records and pool).
+ *   * Records that share a transcript slot share a context, hence the alleles over it: the projection is computed once per
+ *     distinct source slot.  Two source records with equal cigar_off get equal cigar_off, ref_begin, ref_end and ref_score.
+ *     The pool holds one projected transcript per distinct source slot, in source pool order.
+ *   * A record that cannot be projected -- a transcript outside the source pool, a begin outside its haplotype, a
+ *     transcript that does not consume its needle -- fails the whole call with SPM_E_INVALID; the detection is a device
+ *     counter, never a fault: every table index is tested against the table's size before it is read.
+ *   * More than 2^32 - 1 pool words: SPM_E_UNSUPPORTED, decided once the words are counted and before any is written.
+ *   * No records: an empty result and SPM_OK.
+ * flags: must be 0 */
+typedef struct spm_jst_ref_aln {  /* 40 bytes */
+    uint64_t ref_begin;           /* reference coordinates; inside an insertion: the anchor */
+    uint64_t ref_end;
+    uint32_t haplotype;
+    uint32_t pattern;
+    int32_t score;                /* the haplotype distance, as in the source record */
+    int32_t ref_score;            /* X + I + D symbols of the projected transcript */
+    uint32_t cigar_off;           /* first word of the projected transcript in the ops pool of this result */
+    uint32_t cigar_len;
+} spm_jst_ref_aln;
+typedef struct spm_jst_ref_alns spm_jst_ref_alns;
+
+typedef struct spm_jst_project_stats { /* 64 bytes */
+    float ms_total;            /* device: the four stages below (HIP events) */
+    float ms_representatives;  /* one representative record per distinct source slot, slots numbered in pool order */
+    float ms_count;            /* the projection with a counting sink, and the offsets of the projected transcripts */
+    float ms_emit;             /* the projection with a writing sink */
+    float ms_gather;           /* one record per source record */
+    float ms_host;             /* wall clock of the whole call, host view included */
+    uint64_t n_alns;             /* records = the source's count */
+    uint64_t n_projected;        /* distinct slots projected */
+    uint64_t n_ops;              /* words in the projected pool */
+    uint64_t n_inside_insertion; /* slots whose alignment lies wholly inside an inserted stretch (ref_begin == ref_end) */
+    uint64_t n_changed;          /* slots whose projected words differ from their haplotype words */
+} spm_jst_project_stats;
+
+int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst_ref_alns **out);
+int spm_hip_jst_ref_alns_view(spm_jst_ref_alns *a, const spm_jst_ref_aln **records, uint64_t *n, const uint32_t **ops,
+                              uint64_t *n_ops);
+int spm_hip_jst_ref_alns_device(spm_jst_ref_alns *a, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops);
+int spm_hip_jst_ref_alns_stats(const spm_jst_ref_alns *a, spm_jst_project_stats *out);
+void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a);
+
 /* ---- selection of pan-genome hits: one record per haplotype locus, the best stratum per (haplotype, needle) -------------
  * spm_hip_hits_select for the 24-byte records of spm_hip_jst_search.  The locus is (haplotype, pattern).  For a record
  * r = (haplotype, pos, pattern, score):

@@ -152,6 +152,27 @@ class JstAlignStats(C.Structure):
     ]
 
 
+class JstRefAln(C.Structure):
+    _fields_ = [("ref_begin", C.c_uint64), ("ref_end", C.c_uint64), ("haplotype", C.c_uint32), ("pattern", C.c_uint32),
+                ("score", C.c_int32), ("ref_score", C.c_int32), ("cigar_off", C.c_uint32), ("cigar_len", C.c_uint32)]
+
+
+class JstProjectStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_representatives", C.c_float),
+        ("ms_count", C.c_float),
+        ("ms_emit", C.c_float),
+        ("ms_gather", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_alns", C.c_uint64),
+        ("n_projected", C.c_uint64),
+        ("n_ops", C.c_uint64),
+        ("n_inside_insertion", C.c_uint64),
+        ("n_changed", C.c_uint64),
+    ]
+
+
 ALIGN_BEGIN_ONLY = 1
 
 
@@ -272,6 +293,13 @@ def lib():
                                               C.POINTER(C.c_uint64)]),
         "spm_hip_jst_alns_stats": (C.c_int, [vp, C.POINTER(JstAlignStats)]),
         "spm_hip_jst_alns_destroy": (None, [vp]),
+        "spm_hip_jst_alns_project": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_ref_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRefAln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
+                                                C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_ref_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
+                                                  C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_ref_alns_stats": (C.c_int, [vp, C.POINTER(JstProjectStats)]),
+        "spm_hip_jst_ref_alns_destroy": (None, [vp]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -312,6 +340,8 @@ EXPORTS = [
     "spm_hip_jst_hits_copy_device", "spm_hip_jst_hits_destroy", "spm_hip_jst_synth_variants",
     "spm_hip_jst_hits_align", "spm_hip_jst_selection_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
     "spm_hip_jst_alns_destroy",
+    "spm_hip_jst_alns_project", "spm_hip_jst_ref_alns_view", "spm_hip_jst_ref_alns_device", "spm_hip_jst_ref_alns_stats",
+    "spm_hip_jst_ref_alns_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

@@ -95,6 +95,9 @@ std::vector<uint32_t> counting_order(const std::vector<uint32_t> &key, uint32_t 
 }
 } // namespace
 
+// the needles' ranks on the device for callers outside this unit (jst_project.hpp)
+int spm_align_tables(const spm_patterns *ps) { return ensure_align_tables(ps); }
+
 // The Myers path both entry points share (spm_hip_hits_align; spm_hip_jst_hits_align over a search's segment hits): the
 // work list, the kernel class of every hit, stage A and stage B.  Record i of W.d_recs belongs to W.hits[i]; records, pool
 // and the error counters come back to the host behind one synchronisation.

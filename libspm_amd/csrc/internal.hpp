@@ -164,6 +164,8 @@ struct align_work
     const char *who = "";             // the C-ABI call, for messages
 };
 int align_run(spm_ctx *ctx, const align_work &W, spm_align_stats &stats);
+// builds, once per set, the alignment tables of spm_patterns (d_al_*): the projection reads the needle ranks among them
+int spm_align_tables(const spm_patterns *ps);
 
 // Every translation unit with kernels is a code object of its own, loaded by the HIP runtime at the first launch out of
 // it (~1-3 ms each).  spm_hip_init loads them all, so that the first scan of a process does not pay for it.

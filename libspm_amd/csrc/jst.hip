@@ -4,3 +4,4 @@
 #include "synth.hpp"
 #include "jst.hpp"
 #include "jst_locate.hpp"
+#include "jst_project.hpp"

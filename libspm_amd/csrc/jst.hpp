@@ -1339,6 +1339,12 @@ struct spm_jst_alns
     std::vector<spm_jst_aln> host; // (haplotype, pos, pattern): the order of spm_hip_jst_hits_view
     std::vector<uint32_t> host_ops;
     spm_jst_align_stats stats{};
+    // what spm_hip_jst_alns_project needs to know about the call that made these alignments (jst_project.hpp): the tree and
+    // its index generation, the needle set, and whether there are transcripts at all
+    spm_jst *jst = nullptr;
+    const spm_patterns *patterns = nullptr;
+    uint64_t generation = 0;
+    bool begin_only = false;
 };
 
 extern "C" void spm_hip_jst_alns_destroy(spm_jst_alns *a)
@@ -1416,6 +1422,10 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
     A->ctx = ctx;
     A->n = h->n;
     const bool begin_only = (flags & SPM_ALIGN_BEGIN_ONLY) != 0;
+    A->jst = J;
+    A->patterns = ps;
+    A->generation = J->generation;
+    A->begin_only = begin_only;
     const bool myers = ps->is_myers();
     const uint64_t n = h->n;
     hipStream_t st = ctx->stream;

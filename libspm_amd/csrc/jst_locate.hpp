@@ -278,6 +278,10 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
     std::unique_ptr<spm_jst_alns, void (*)(spm_jst_alns *)> A(new spm_jst_alns, spm_hip_jst_alns_destroy);
     A->ctx = ctx;
     A->n = n;
+    A->jst = J;
+    A->patterns = ps;
+    A->generation = J->generation;
+    A->begin_only = begin_only;
     A->stats.n_alns = n;
     hipStream_t st = ctx->stream;
     uint64_t nk = 0;

@@ -1,0 +1,510 @@
+// jst_project.hpp -- pan-genome alignments in reference coordinates (spm_hip_jst_alns_project; contract in spm_hip.h, scheme
+// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp: it needs spm_jst, spm_jst_alns and jst_first_ref.
+//
+// Records that share a transcript slot share a context: they carry the same alleles over it and lie on the same reference
+// positions.  So the projection is computed once per distinct slot of the source pool and gathered:
+//   jst_proj_rep_kernel      one lane per record: atomicMin of the record index into rep[cigar_off] -- the smallest arrival
+//                            index represents its slot
+//   (hipcub exclusive sum of rep[w] != none over the source pool: the number of every slot, in pool order)
+//   jst_proj_compact_kernel  one lane per pool word: slot number -> representative record; the last lane writes the count
+//   jst_proj_count_kernel    one lane per slot: the block of its haplotype that holds `begin` (binary search down column h of
+//                            hap_start), the journal walked from jst_first_ref / a_lo up to begin, then jst_project_compose
+//                            with a counting sink: words, ref_begin, ref_end, ref_score
+//   (hipcub exclusive sum of the word counts, 64 bits; jst_proj_total_kernel; the one read-back that sizes the pool)
+//   jst_proj_emit_kernel     the same walk with a writing sink
+//   jst_proj_gather_kernel   one lane per record i: its own record + the result of its slot -> spm_jst_ref_aln i
+// The walk starts from the tables of the index and runs forward as far as the transcript reaches: it assumes neither that a
+// carried deletion ends inside its block nor that begin and end lie in the same block.
+#pragma once
+
+#include "jst_project_core.hpp"
+
+static_assert(sizeof(spm_jst_ref_aln) == 40 && sizeof(spm_jst_project_stats) == 64, "C ABI layout");
+static_assert(SPM_CIGAR_INS == spm_hip::kProjIns && SPM_CIGAR_DEL == spm_hip::kProjDel && SPM_CIGAR_EQ == spm_hip::kProjEq &&
+                  SPM_CIGAR_X == spm_hip::kProjX, "the core header's op values are the ABI's");
+
+namespace spm_hip
+{
+
+constexpr uint32_t kProjNone = 0xFFFFFFFFu;
+enum { kProjCntSlots = 0, kProjCntBad = 1, kProjCntInside = 2, kProjCntChanged = 3, kProjCntWords = 4, kProjCnts = 5 };
+
+struct jst_project_params
+{
+    jst_dev J;                       // allele table, coverage, a_lo, hap_start (all blocks of the reference)
+    const spm_jst_aln *recs;         // the source's device view
+    uint32_t n;
+    const uint32_t *ops;             // the source's pool
+    uint64_t n_ops;
+    const uint8_t *ranks;            // the needles' symbols, back to back ...
+    const uint32_t *offsets;         // ... and where each starts
+    const int32_t *m;
+    uint32_t n_patterns;
+    uint32_t cap;                    // slots the per-slot tables hold: min(n, n_ops)
+    uint32_t *rep;                   // [n_ops] smallest record index whose transcript starts at this word, or none
+    const uint32_t *sid;             // [n_ops] exclusive sum of rep != none: the slot's number
+    uint32_t *slot_rec;              // [cap] representative record of slot s
+    unsigned long long *slot_range;  // [2 * cap] ref_begin, ref_end
+    uint32_t *slot_words;            // [cap] words of the projected transcript
+    int32_t *slot_score;             // [cap] ref_score
+    const unsigned long long *slot_off; // [cap] exclusive sum of slot_words
+    uint32_t *out_ops;
+    unsigned long long *counts;      // kProjCnt*
+    spm_jst_ref_aln *out;            // [n]
+};
+
+__global__ __launch_bounds__(256) void jst_proj_rep_kernel(const jst_project_params P)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    bool bad = false;
+    if (i < P.n) {
+        const spm_jst_aln a = P.recs[i];
+        bad = a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops;
+        if (!bad)
+            atomicMin(&P.rep[a.cigar_off], (uint32_t)i);
+    }
+    const unsigned long long mb = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && mb)
+        atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
+}
+
+struct jproj_flag_op
+{
+    const uint32_t *rep;
+    __device__ __forceinline__ uint32_t operator()(uint32_t w) const { return rep[w] != kProjNone ? 1u : 0u; }
+};
+
+struct jproj_widen_op
+{
+    const uint32_t *v;
+    __device__ __forceinline__ unsigned long long operator()(uint32_t s) const { return v[s]; }
+};
+
+__global__ __launch_bounds__(256) void jst_proj_compact_kernel(const jst_project_params P)
+{
+    const unsigned long long w = blockIdx.x * 256ull + threadIdx.x;
+    if (w >= P.n_ops)
+        return;
+    const uint32_t r = P.rep[w];
+    const uint32_t s = P.sid[w];
+    if (r != kProjNone && s < P.cap)
+        P.slot_rec[s] = r;
+    if (w == P.n_ops - 1)
+        P.counts[kProjCntSlots] = (unsigned long long)s + (r != kProjNone ? 1ull : 0ull);
+}
+
+// The projection of slot s into sink S.  Every table index is tested against its size before it is read; false counts as an
+// error of the call, never a fault.
+template <class Sink>
+__device__ __forceinline__ bool jproj_run(const jst_project_params &P, uint32_t s, Sink &S, jst_proj_result &R, spm_jst_aln &a)
+{
+    const jst_dev &J = P.J;
+    const uint32_t ri = P.slot_rec[s];
+    if (ri >= P.n)
+        return false;
+    a = P.recs[ri];
+    const uint32_t h = a.haplotype;
+    if (h >= J.n_hap || a.pattern >= P.n_patterns || a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops ||
+        a.begin > a.end)
+        return false;
+    const int32_t m = P.m[a.pattern];
+    if (m <= 0)
+        return false;
+    // the largest j in [0, n_blocks] with hap_start[j][h] <= begin (the column is non-decreasing and starts at 0)
+    uint64_t lo = 0, hi = J.n_blocks + 1;
+    if (J.hap_start[h] > a.begin)
+        return false;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (J.hap_start[mid * J.n_hap + h] <= a.begin)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    jst_journal_view V;
+    V.pos = J.pos;
+    V.rlen = J.rlen;
+    V.alen = J.alen;
+    V.cov = J.cov;
+    V.n_alleles = J.n_alleles;
+    V.cw = J.cw;
+    V.n_hap = J.n_hap;
+    V.n_ref = J.n_ref;
+    jst_journal_cursor C;
+    const uint64_t first_allele = J.a_lo[lo];
+    if (first_allele > J.n_alleles)
+        return false;
+    C.start(V, h, jst_first_ref(J, lo, h), first_allele);
+    if (!C.skip(a.begin - J.hap_start[lo * J.n_hap + h]))
+        return false;
+    return jst_project_compose(C, P.ops + a.cigar_off, a.cigar_len, P.ranks + P.offsets[a.pattern], (uint32_t)m, J.ref, J.n_ref,
+                               S, R);
+}
+
+__global__ __launch_bounds__(256) void jst_proj_count_kernel(const jst_project_params P)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
+    bool bad = false, inside = false;
+    if (s < n_slots) {
+        jst_proj_count_sink S;
+        jst_proj_result R;
+        spm_jst_aln a;
+        bad = !jproj_run(P, s, S, R, a) || R.n_words > 0xFFFFFFFFull || R.ref_score > 0x7FFFFFFFull;
+        inside = !bad && R.inside;
+        P.slot_range[2 * (uint64_t)s] = bad ? 0ull : R.ref_begin;
+        P.slot_range[2 * (uint64_t)s + 1] = bad ? 0ull : R.ref_end;
+        P.slot_words[s] = bad ? 0u : (uint32_t)R.n_words;
+        P.slot_score[s] = bad ? 0 : (int32_t)R.ref_score;
+    }
+    const unsigned long long mb = __ballot(bad), mi = __ballot(inside);
+    if ((threadIdx.x & 63) == 0) {
+        if (mb)
+            atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
+        if (mi)
+            atomicAdd(&P.counts[kProjCntInside], (unsigned long long)__popcll(mi));
+    }
+}
+
+__global__ void jst_proj_total_kernel(const jst_project_params P)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
+        P.counts[kProjCntWords] = n_slots ? P.slot_off[n_slots - 1] + P.slot_words[n_slots - 1] : 0ull;
+    }
+}
+
+// pool_words: the size of out_ops, which the host allocated from the total the count stage found
+__global__ __launch_bounds__(256) void jst_proj_emit_kernel(const jst_project_params P, uint64_t pool_words)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
+    bool bad = false, changed = false;
+    if (s < n_slots) {
+        const unsigned long long off = P.slot_off[s];
+        const uint32_t nw = P.slot_words[s];
+        bad = off + nw > pool_words;
+        if (!bad) {
+            jst_proj_write_sink S;
+            S.out = P.out_ops + off;
+            S.cap = nw;
+            jst_proj_result R;
+            spm_jst_aln a;
+            bad = !jproj_run(P, s, S, R, a) || R.n_words != nw; // (both walks instantiate the same code)
+            if (!bad) {
+                changed = nw != a.cigar_len;
+                for (uint32_t w = 0; !changed && w < nw; ++w)
+                    changed = P.out_ops[off + w] != P.ops[a.cigar_off + w];
+            }
+        }
+    }
+    const unsigned long long mb = __ballot(bad), mc = __ballot(changed);
+    if ((threadIdx.x & 63) == 0) {
+        if (mb)
+            atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
+        if (mc)
+            atomicAdd(&P.counts[kProjCntChanged], (unsigned long long)__popcll(mc));
+    }
+}
+
+__global__ __launch_bounds__(256) void jst_proj_gather_kernel(const jst_project_params P)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    if (i >= P.n)
+        return;
+    const spm_jst_aln a = P.recs[i];
+    spm_jst_ref_aln o;
+    o.ref_begin = o.ref_end = 0;
+    o.haplotype = a.haplotype;
+    o.pattern = a.pattern;
+    o.score = a.score;
+    o.ref_score = 0;
+    o.cigar_off = o.cigar_len = 0;
+    if (a.cigar_off < P.n_ops) { // (the representatives stage has counted the records this does not hold for)
+        const uint32_t s = P.sid[a.cigar_off];
+        if (s < P.cap) {
+            o.ref_begin = P.slot_range[2 * (uint64_t)s];
+            o.ref_end = P.slot_range[2 * (uint64_t)s + 1];
+            o.ref_score = P.slot_score[s];
+            o.cigar_off = (uint32_t)P.slot_off[s];
+            o.cigar_len = P.slot_words[s];
+        }
+    }
+    P.out[i] = o;
+}
+
+} // namespace spm_hip
+
+struct spm_jst_ref_alns
+{
+    spm_ctx *ctx = nullptr;
+    spm_jst_ref_aln *d_recs = nullptr; // record i belongs to record i of the source's device view
+    uint32_t *d_ops = nullptr;
+    uint64_t n = 0, n_ops = 0;
+    std::vector<spm_jst_ref_aln> host; // record i belongs to record i of the source's host view
+    std::vector<uint32_t> host_ops;
+    spm_jst_project_stats stats{};
+};
+
+extern "C" void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a)
+{
+    if (!a)
+        return;
+    if (a->ctx && (a->d_recs || a->d_ops))
+        hipStreamSynchronize(a->ctx->stream);
+    hipFree(a->d_recs);
+    hipFree(a->d_ops);
+    delete a;
+}
+
+extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst_ref_alns **out)
+{
+    using namespace spm_hip;
+    if (!a || !out)
+        return SPM_E_INVALID;
+    spm_ctx *ctx = a->ctx;
+    const auto t_call = clk::now();
+    if (flags) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: unknown flag bits 0x%x", flags);
+        return SPM_E_INVALID;
+    }
+    if (a->begin_only) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: these alignments were made with SPM_ALIGN_BEGIN_ONLY: there is no "
+                         "transcript to project");
+        return SPM_E_INVALID;
+    }
+    spm_jst *J = a->jst;
+    const spm_patterns *ps = a->patterns;
+    if (!J || !ps) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: these alignments name no tree");
+        return SPM_E_INVALID;
+    }
+    if (!J->indexed || J->generation != a->generation) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: the tree has been indexed again since the search behind these alignments "
+                         "(the tables the projection walks are gone); search and align again");
+        return SPM_E_INVALID;
+    }
+    const uint64_t n = a->n, n_src_ops = a->n_ops;
+    if (n > 0xFFFFFFFFull) {
+        SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: more than 2^32 - 1 records");
+        return SPM_E_UNSUPPORTED;
+    }
+    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<spm_jst_ref_alns, void (*)(spm_jst_ref_alns *)> R(new spm_jst_ref_alns, spm_hip_jst_ref_alns_destroy);
+    R->ctx = ctx;
+    R->n = n;
+    R->stats.n_alns = n;
+    hipStream_t st = ctx->stream;
+    float ms_rep = 0, ms_count = 0, ms_emit = 0, ms_gather = 0;
+    uint64_t n_slots = 0;
+    if (n) {
+        if (n_src_ops == 0 || !a->d_ops || !a->d_recs) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: %llu records but no transcript pool", (unsigned long long)n);
+            return SPM_E_INVALID;
+        }
+        SPM_TRY(spm_align_tables(ps)); // the needles' ranks on the device (built once per set)
+        const uint32_t n32 = (uint32_t)n;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(n, n_src_ops);
+        struct event_set
+        {
+            hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            ~event_set()
+            {
+                for (hipEvent_t x : e)
+                    if (x)
+                        hipEventDestroy(x);
+            }
+        } ev;
+        for (hipEvent_t &e : ev.e)
+            SPM_HIP_CHECK(ctx, hipEventCreate(&e));
+        using count_iter = hipcub::CountingInputIterator<uint32_t>;
+        using flag_iter = hipcub::TransformInputIterator<uint32_t, jproj_flag_op, count_iter>;
+        using wide_iter = hipcub::TransformInputIterator<unsigned long long, jproj_widen_op, count_iter>;
+        size_t b_flag = 0, b_wide = 0;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, b_flag, flag_iter(count_iter(0), jproj_flag_op{nullptr}),
+                                                            (uint32_t *)nullptr, (size_t)n_src_ops, st));
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, b_wide, wide_iter(count_iter(0), jproj_widen_op{nullptr}),
+                                                            (unsigned long long *)nullptr, (size_t)cap, st));
+        const size_t tmp_bytes = std::max(b_flag, b_wide);
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            const size_t at = off;
+            off += jloc_align_up(bytes);
+            return at;
+        };
+        const size_t o_rep = take(n_src_ops * 4), o_sid = take(n_src_ops * 4), o_rec = take((size_t)cap * 4),
+                     o_range = take((size_t)cap * 16), o_words = take((size_t)cap * 4), o_score = take((size_t)cap * 4),
+                     o_off = take((size_t)cap * 8), o_counts = take(kProjCnts * 8), o_tmp = take(tmp_bytes);
+        SPM_TRY(ensure_scratch(ctx, off));
+        uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
+        uint32_t *d_rep = reinterpret_cast<uint32_t *>(base + o_rep), *d_sid = reinterpret_cast<uint32_t *>(base + o_sid);
+        uint32_t *d_words = reinterpret_cast<uint32_t *>(base + o_words);
+        unsigned long long *d_off = reinterpret_cast<unsigned long long *>(base + o_off);
+        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + o_counts);
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_recs, n * sizeof(spm_jst_ref_aln)));
+
+        jst_project_params P{};
+        P.J = J->dev();
+        P.recs = a->d_recs;
+        P.n = n32;
+        P.ops = a->d_ops;
+        P.n_ops = n_src_ops;
+        P.ranks = ps->d_al_ranks;
+        P.offsets = ps->d_al_offsets;
+        P.m = ps->d_m;
+        P.n_patterns = ps->n;
+        P.cap = cap;
+        P.rep = d_rep;
+        P.sid = d_sid;
+        P.slot_rec = reinterpret_cast<uint32_t *>(base + o_rec);
+        P.slot_range = reinterpret_cast<unsigned long long *>(base + o_range);
+        P.slot_words = d_words;
+        P.slot_score = reinterpret_cast<int32_t *>(base + o_score);
+        P.slot_off = d_off;
+        P.out_ops = nullptr;
+        P.counts = d_counts;
+        P.out = R->d_recs;
+        const unsigned g_rec = (unsigned)((n + 255) / 256), g_pool = (unsigned)((n_src_ops + 255) / 256),
+                       g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
+        // ---- representatives: one per distinct slot of the source pool, numbered in pool order ----
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kProjCnts * 8, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[0], st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_rep, 0xFF, n_src_ops * 4, st));
+        hipLaunchKernelGGL(jst_proj_rep_kernel, dim3(g_rec), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        size_t tb = tmp_bytes;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, flag_iter(count_iter(0), jproj_flag_op{d_rep}), d_sid,
+                                                            (size_t)n_src_ops, st));
+        hipLaunchKernelGGL(jst_proj_compact_kernel, dim3(g_pool), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[1], st));
+        // ---- count: the projection of every slot with a counting sink, then where its words go ----
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_words, 0, (size_t)cap * 4, st));
+        hipLaunchKernelGGL(jst_proj_count_kernel, dim3(g_slot), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        tb = tmp_bytes;
+        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, wide_iter(count_iter(0), jproj_widen_op{d_words}),
+                                                            d_off, (size_t)cap, st));
+        hipLaunchKernelGGL(jst_proj_total_kernel, dim3(1), dim3(64), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[2], st));
+        // the one read-back that sizes the pool: {slots, errors, inside an insertion, -, words}
+        unsigned long long *c = ctx->h_counters;
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        n_slots = c[kProjCntSlots];
+        const unsigned long long n_bad = c[kProjCntBad], total = c[kProjCntWords];
+        R->stats.n_inside_insertion = c[kProjCntInside];
+        if (n_bad || n_slots == 0 || n_slots > cap) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: %llu records or transcript slots cannot be projected (a transcript "
+                             "outside the pool, a begin outside its haplotype, or a transcript that does not consume its needle "
+                             "and its haplotype stretch); nothing was projected", n_bad ? n_bad : (unsigned long long)n);
+            return SPM_E_INVALID;
+        }
+        if (total > 0xFFFFFFFFull) { // decided before the emit launch
+            SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: the projected CIGAR pool would exceed 2^32 - 1 words");
+            return SPM_E_UNSUPPORTED;
+        }
+        R->n_ops = total;
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_ops, std::max<uint64_t>(total, 1) * 4));
+        P.out_ops = R->d_ops;
+        // ---- emit, gather ----
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[3], st));
+        hipLaunchKernelGGL(jst_proj_emit_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, P, (uint64_t)total);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[4], st));
+        hipLaunchKernelGGL(jst_proj_gather_kernel, dim3(g_rec), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[5], st));
+        // ---- the host view: record i of the source's host view through the slot tables ----
+        std::vector<uint32_t> sid(n_src_ops), words(n_slots);
+        std::vector<int32_t> score(n_slots);
+        std::vector<unsigned long long> range(2 * n_slots), woff(n_slots);
+        R->host_ops.resize(total);
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(sid.data(), d_sid, n_src_ops * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), d_words, n_slots * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(score.data(), P.slot_score, n_slots * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(range.data(), P.slot_range, n_slots * 16, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(woff.data(), d_off, n_slots * 8, hipMemcpyDeviceToHost, st));
+        if (total)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host_ops.data(), R->d_ops, total * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        hipEventElapsedTime(&ms_rep, ev.e[0], ev.e[1]);
+        hipEventElapsedTime(&ms_count, ev.e[1], ev.e[2]);
+        hipEventElapsedTime(&ms_emit, ev.e[3], ev.e[4]);
+        hipEventElapsedTime(&ms_gather, ev.e[4], ev.e[5]);
+        if (c[kProjCntBad]) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: %llu transcript slots came out of the emit stage differently from the "
+                             "count stage", c[kProjCntBad]);
+            return SPM_E_INVALID;
+        }
+        R->stats.n_changed = c[kProjCntChanged];
+        if (a->host.size() != n) {
+            SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: the source holds no host view");
+            return SPM_E_INVALID;
+        }
+        R->host.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const spm_jst_aln &x = a->host[i];
+            const uint32_t s = x.cigar_off < n_src_ops ? sid[x.cigar_off] : kProjNone;
+            if (s >= n_slots) {
+                SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: host record %llu names no projected slot", (unsigned long long)i);
+                return SPM_E_INVALID;
+            }
+            R->host[i] = spm_jst_ref_aln{range[2 * (uint64_t)s], range[2 * (uint64_t)s + 1], x.haplotype, x.pattern, x.score,
+                                         score[s], (uint32_t)woff[s], words[s]};
+        }
+    }
+    R->stats.ms_representatives = ms_rep;
+    R->stats.ms_count = ms_count;
+    R->stats.ms_emit = ms_emit;
+    R->stats.ms_gather = ms_gather;
+    R->stats.ms_total = ms_rep + ms_count + ms_emit + ms_gather;
+    R->stats.n_projected = n_slots;
+    R->stats.n_ops = R->n_ops;
+    R->stats.ms_host = ms_since(t_call);
+    if (spm_trace_on())
+        fprintf(stderr, "[spm_hip] jst project: %llu records, %llu slots -> %llu words (%llu changed, %llu inside an insertion): "
+                        "representatives %.3f ms, count %.3f, emit %.3f, gather %.3f; %.3f ms in all\n", (unsigned long long)n,
+                (unsigned long long)n_slots, (unsigned long long)R->n_ops, (unsigned long long)R->stats.n_changed,
+                (unsigned long long)R->stats.n_inside_insertion, ms_rep, ms_count, ms_emit, ms_gather, R->stats.ms_host);
+    *out = R.release();
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_alns_view(spm_jst_ref_alns *a, const spm_jst_ref_aln **records, uint64_t *n, const uint32_t **ops,
+                                         uint64_t *n_ops)
+{
+    if (!a || !records || !n)
+        return SPM_E_INVALID;
+    *records = a->host.data();
+    *n = a->n;
+    if (ops)
+        *ops = a->host_ops.data();
+    if (n_ops)
+        *n_ops = a->n_ops;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_alns_device(spm_jst_ref_alns *a, const void **records, uint64_t *n, const void **ops,
+                                           uint64_t *n_ops)
+{
+    if (!a || !records || !n)
+        return SPM_E_INVALID;
+    *records = a->d_recs;
+    *n = a->n;
+    if (ops)
+        *ops = a->d_ops;
+    if (n_ops)
+        *n_ops = a->n_ops;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_alns_stats(const spm_jst_ref_alns *a, spm_jst_project_stats *out)
+{
+    if (!a || !out)
+        return SPM_E_INVALID;
+    *out = a->stats;
+    return SPM_OK;
+}

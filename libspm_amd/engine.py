@@ -400,6 +400,8 @@ JST_HIT_DTYPE = np.dtype([("pos", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4
                           ("reserved", "<u4")])
 JST_ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"), ("score", "<i4"),
                           ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("reserved", "<u4")])
+JST_REF_ALN_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"),
+                              ("score", "<i4"), ("ref_score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4")])
 
 
 def synth_variants(seed_text: int, seed_var: int, ref_begin: int, n_ref: int, n_haplotypes: int):
@@ -525,7 +527,7 @@ class JstHits:
         a = C.c_void_p()
         _check(capi.lib().spm_hip_jst_hits_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
                self.ctx._h)
-        return JstAlignments(self.ctx, a)
+        return JstAlignments(self.ctx, a, self._jst, self._pats)
 
     def align_selected(self, begin_only: bool = False) -> "JstAlignments":
         """Begin + CIGAR transcript of the records this SELECTION kept (spm_hip_jst_selection_align): the kept records are
@@ -538,7 +540,7 @@ class JstHits:
         a = C.c_void_p()
         _check(capi.lib().spm_hip_jst_selection_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
                self.ctx._h)
-        return JstAlignments(self.ctx, a)
+        return JstAlignments(self.ctx, a, self._jst, self._pats)
 
     def select(self, loci: bool = True, window: int | None = None, best: int | None = None,
                across: bool = False) -> "JstHits":
@@ -587,8 +589,9 @@ class JstAlignments:
     """Result of JstHits.align(): JST_ALN_DTYPE records in the order of JstHits.view(), and the pool of CIGAR words
     (len << 4 | op) they point into -- one transcript per segment hit, shared by the haplotypes of its context."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    def __init__(self, ctx, h, jst=None, pats=None):
+        # the tree and the needle set behind these alignments: project() reads both
+        self.ctx, self._h, self._jst, self._pats = ctx, h, jst, pats
 
     def _raw(self):
         rec = C.POINTER(capi.JstAln)()
@@ -637,10 +640,87 @@ class JstAlignments:
         _check(capi.lib().spm_hip_jst_alns_stats(self._h, C.byref(s)), self.ctx._h)
         return s
 
+    def project(self) -> "JstRefAlignments":
+        """These alignments in REFERENCE coordinates (spm_hip_jst_alns_project): ref_begin, ref_end, ref_score and a
+        transcript against the reference, computed once per shared transcript slot.  Record i of the result's view()
+        belongs to view() record i, record i of its device() to device() record i.  Not for begin_only alignments; the
+        tree and the needle set must be open, and the tree not indexed again since the search."""
+        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
+            raise capi.SpmError("JstAlignments.project: the tree or the needle set of these alignments has been closed")
+        r = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_alns_project(self._h, 0, C.byref(r)), self.ctx._h)
+        return JstRefAlignments(self.ctx, r)
+
     def close(self):
         if self._h:
             if self.ctx._h:
                 capi.lib().spm_hip_jst_alns_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JstRefAlignments:
+    """Result of JstAlignments.project(): JST_REF_ALN_DTYPE records matched to the source's records, and the pool of CIGAR
+    words (len << 4 | op) against the reference -- one transcript per distinct transcript slot of the source."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def _raw(self):
+        rec = C.POINTER(capi.JstRefAln)()
+        ops = C.POINTER(C.c_uint32)()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_ref_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
+               self.ctx._h)
+        return rec, n.value, ops, n_ops.value
+
+    def __len__(self):
+        return self._raw()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n, _, _ = self._raw()
+        if n == 0:
+            return np.zeros(0, dtype=JST_REF_ALN_DTYPE)
+        buf = (capi.JstRefAln * n).from_address(C.addressof(rec.contents))
+        return np.frombuffer(buf, dtype=JST_REF_ALN_DTYPE).copy()
+
+    @property
+    def ops(self) -> np.ndarray:
+        _, _, ops, n_ops = self._raw()
+        if n_ops == 0:
+            return np.zeros(0, dtype=np.uint32)
+        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
+        return np.frombuffer(buf, dtype=np.uint32).copy()
+
+    def device(self):
+        """(records, n, ops, n_ops): device pointers; record i matched to record i of the source's device()."""
+        r, o = C.c_void_p(), C.c_void_p()
+        n, n_ops = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_ref_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)),
+               self.ctx._h)
+        return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
+
+    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
+        """SAM string of record i (records / ops: views already fetched, to save the copies)."""
+        r = (self.view() if records is None else records)[i]
+        o = self.ops if ops is None else ops
+        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
+        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+
+    def stats(self) -> capi.JstProjectStats:
+        s = capi.JstProjectStats()
+        _check(capi.lib().spm_hip_jst_ref_alns_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_jst_ref_alns_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
