@@ -1,0 +1,82 @@
+// device_order.hpp -- the host side of "order the records, then compact them", written once for the drivers that do it
+// (select.hip, jst_select.hip, jst_locate.hpp, jst_project.hpp): the hipcub radix sort of (64-bit key, 32-bit index) pairs
+// over the key's low bits, the hipcub exclusive sum over any input iterator, the read-back of a call's counts, and the
+// events a call times its stages with.  HIP, host code only: hipcub instantiates for the callers' own iterator types what
+// a direct call would.  Every function returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "common.hpp"
+
+namespace spm_hip
+{
+
+// ---- the sort: keys_in/idx_in -> keys_out/idx_out, stable, by bits [0, key_bits) of the key ----
+inline hipError_t sort_pairs_tmp_bytes(spm_ctx *ctx, size_t n, uint32_t key_bits, size_t *tmp_bytes)
+{
+    *tmp_bytes = 0;
+    return hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, (const unsigned long long *)nullptr,
+                                              (unsigned long long *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, n, 0,
+                                              (int)key_bits, ctx->stream);
+}
+
+inline hipError_t sort_pairs(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const unsigned long long *keys_in,
+                             unsigned long long *keys_out, const uint32_t *idx_in, uint32_t *idx_out, size_t n,
+                             uint32_t key_bits)
+{
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, (int)key_bits,
+                                              ctx->stream);
+}
+
+// ---- the exclusive sum of n items of `in` into out[0..n) ----
+template <class Out, class Iter> hipError_t exclusive_sum_tmp_bytes(spm_ctx *ctx, Iter in, size_t n, size_t *tmp_bytes)
+{
+    *tmp_bytes = 0;
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, *tmp_bytes, in, (Out *)nullptr, n, ctx->stream);
+}
+
+template <class Iter, class Out> hipError_t exclusive_sum(spm_ctx *ctx, void *tmp, size_t tmp_bytes, Iter in, Out *out, size_t n)
+{
+    return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, in, out, n, ctx->stream);
+}
+
+// f(0), f(1), ... as an input iterator: what the sums above add up
+template <class T, class Op> using counted_iter = hipcub::TransformInputIterator<T, Op, hipcub::CountingInputIterator<uint32_t>>;
+template <class T, class Op> counted_iter<T, Op> counted(Op op)
+{
+    return counted_iter<T, Op>(hipcub::CountingInputIterator<uint32_t>(0), op);
+}
+
+// ---- the one read-back of a call: n_words counters into ctx->h_counters, and the synchronisation ----
+inline hipError_t read_counts(spm_ctx *ctx, const unsigned long long *d_counts, size_t n_words)
+{
+    const hipError_t e = hipMemcpyAsync(ctx->h_counters, d_counts, n_words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+
+// ---- N events that live as long as the call that times its stages with them ----
+template <int N> struct hip_events
+{
+    hipEvent_t e[N] = {};
+    hip_events() = default;
+    hip_events(const hip_events &) = delete; // (e is an array of handles this object destroys)
+    hip_events &operator=(const hip_events &) = delete;
+    ~hip_events()
+    {
+        for (hipEvent_t x : e)
+            if (x)
+                hipEventDestroy(x);
+    }
+    hipError_t create()
+    {
+        hipError_t r = hipSuccess;
+        for (int i = 0; i < N && r == hipSuccess; ++i)
+            r = hipEventCreate(&e[i]);
+        return r;
+    }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
+} // namespace spm_hip

@@ -68,6 +68,19 @@ struct spm_patterns : spm_hip::seed_index // (the seed index: passes, entries, s
 
 using clk = std::chrono::steady_clock;
 inline float ms_since(clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); }
+// the three events of a selection -> the times of spm_select_stats, once (`timed`: they are still to be read)
+inline hipError_t select_stats_close(bool &timed, hipEvent_t begin, hipEvent_t ordered, hipEvent_t end, spm_select_stats &s)
+{
+    const hipError_t e = timed ? hipEventSynchronize(end) : hipSuccess;
+    if (!timed || e != hipSuccess)
+        return e;
+    hipEventElapsedTime(&s.ms_total, begin, end);
+    hipEventElapsedTime(&s.ms_order, begin, ordered);
+    hipEventElapsedTime(&s.ms_select, ordered, end);
+    timed = false;
+    return hipSuccess;
+}
+
 // SPM_HIP_TRACE=1: one stderr line per C-ABI call that does work, with its timings
 inline bool spm_trace_on()
 {
@@ -145,7 +158,8 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
               const uint32_t *d_seg_owned = nullptr, const std::function<int(spm_hits *)> *after_launch = nullptr);
 
 // ---- alignment of Myers hits (align.hip): the work list, the kernel classes, stage A and stage B.  Shared by
-// spm_hip_hits_align (hits of a scan) and spm_hip_jst_hits_align (segment hits of a journaled-sequence search). ----
+// spm_hip_hits_align (hits of a scan) and, through jst_align_segments (jst.hpp), by spm_hip_jst_hits_align (segment hits of
+// a journaled-sequence search) and spm_hip_jst_selection_align (the distinct segment hits of a selection's records). ----
 struct align_work
 {
     const spm_patterns *ps = nullptr;

@@ -18,9 +18,14 @@
 //      last symbol lies in the owned part is fanned out to the haplotypes of its group.
 // By the window property (a hit depends only on the window_size symbols ending at it) this is exact; work on the
 // device is proportional to the distinct sequence content, not to haplotypes x length.
+// Also here: spm_hip_jst_hits_align, and what it shares with spm_hip_jst_selection_align (jst_locate.hpp) --
+// jst_align_segments (distinct segment hits -> their alignments on the device) and jst_alns_download / jst_alns_close (host view, statistics).
 #pragma once
 
 #include <hipcub/hipcub.hpp>
+
+#include "device_order.hpp"
+#include "scratch_layout.hpp"
 
 // the ctypes binding (libspm_amd/capi.py) mirrors these layouts
 static_assert(sizeof(spm_jst_allele) == 24 && sizeof(spm_jst_hit) == 24 && sizeof(spm_jst_stats) == 104, "C ABI layout");
@@ -974,20 +979,9 @@ extern "C" int spm_hip_jst_index(spm_jst *J, uint32_t window, uint32_t block_len
     const uint64_t nb = je - jb;
     hipStream_t st = ctx->stream;
     dev_scratch tmp_bufs; // temporaries of the build, released on every return path
-    struct event_pair
-    {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~event_pair()
-        {
-            if (a)
-                hipEventDestroy(a);
-            if (b)
-                hipEventDestroy(b);
-        }
-    } ev;
-    SPM_HIP_CHECK(ctx, hipEventCreate(&ev.a));
-    SPM_HIP_CHECK(ctx, hipEventCreate(&ev.b));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
+    hip_events<2> ev;
+    SPM_HIP_CHECK(ctx, ev.create());
+    const hipEvent_t e0 = ev[0], e1 = ev[1];
     SPM_HIP_CHECK(ctx, hipEventRecord(e0, st));
 
     SPM_HIP_CHECK(ctx, hipMalloc(&J->d_alo, (n_blocks + 2) * 8));
@@ -1392,6 +1386,83 @@ static void jst_sort_alns_host(std::vector<spm_jst_aln> &v, bool myers)
     });
 }
 
+// What the two pan-genome align calls share.  From the distinct segment hits kh (pool order) and lo[i], the start of hit i's
+// context, to their alignments on the device (*d_seg_alns, owned by `tmp`) and the transcript pool in A: sizes the pool,
+// ends the caller's work-list clock (ms_worklist = time since t_list), allocates, runs stage A / stage B or the exact fill.
+static int jst_align_segments(spm_ctx *ctx, spm_jst *J, const spm_patterns *ps, const std::vector<spm_hit> &kh,
+                              const std::vector<uint64_t> &lo, bool begin_only, clk::time_point t_list, const char *who,
+                              dev_scratch &tmp, spm_jst_alns *A, spm_aln **d_seg_alns)
+{
+    using namespace spm_hip;
+    const bool myers = ps->is_myers();
+    const uint64_t nk = kh.size();
+    std::vector<uint32_t> cig_off(nk, 0);
+    uint64_t total_ops = 0;
+    for (uint64_t i = 0; i < nk; ++i) {
+        cig_off[i] = (uint32_t)total_ops;
+        total_ops += myers ? 2 * (uint64_t)std::max(0, kh[i].score) + 1 : 1;
+    }
+    if (total_ops > 0xFFFFFFFFull) { // (every hit has a word: this bounds the number of hits too)
+        SPM_SET_ERR(ctx, "%s: the CIGAR pool would exceed 2^32 words", who);
+        return SPM_E_UNSUPPORTED;
+    }
+    A->n_ops = begin_only ? 0 : total_ops;
+    A->host_ops.resize(A->n_ops);
+    A->stats.ms_worklist = ms_since(t_list);
+    SPM_HIP_CHECK(ctx, tmp.alloc(d_seg_alns, nk * sizeof(spm_aln)));
+    if (A->n_ops)
+        SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
+    if (!myers)
+        return jst_fill_exact_alns(ctx, ps, kh, cig_off, begin_only, *d_seg_alns, A);
+    align_work W{}; // over the context buffer: lo = the start of the hit's context, positions as they are (pos_offset 0)
+    W.ps = ps;
+    W.text = J->ctx_text;
+    W.hits = kh.data();
+    W.n = nk;
+    W.lo = lo.data();
+    W.cig_off = cig_off.data();
+    W.begin_only = begin_only;
+    W.d_recs = *d_seg_alns;
+    W.d_ops = A->d_ops;
+    W.n_ops = A->n_ops;
+    W.h_ops = A->host_ops.data();
+    W.who = who;
+    spm_align_stats as{};
+    SPM_TRY(align_run(ctx, W, as));
+    A->stats.ms_begin = as.ms_begin;
+    A->stats.ms_cigar = as.ms_cigar;
+    A->stats.begin_lane = as.begin_lane;
+    A->stats.begin_wave = as.begin_wave;
+    A->stats.cigar_lane = as.cigar_lane;
+    A->stats.cigar_wave = as.cigar_wave;
+    A->stats.cigar_wave_global = as.cigar_wave_global;
+    return SPM_OK;
+}
+
+// ... and their tail in two steps.  The host view of A->d_recs, once the caller's last stage is enqueued; behind its
+// synchronisation every event of the call has happened, and the caller reads its own stage's time into ms_fanout.
+static int jst_alns_download(spm_ctx *ctx, spm_jst_alns *A)
+{
+    A->host.resize(A->n);
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, A->n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost,
+                                      ctx->stream));
+    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return SPM_OK;
+}
+// ... then the order of spm_hip_jst_hits_view and the statistics; returns the host sort's ms (work list time to one caller)
+static float jst_alns_close(spm_jst_alns *A, uint64_t nk, bool myers, clk::time_point t_call)
+{
+    const auto t_sort = clk::now();
+    jst_sort_alns_host(A->host, myers);
+    const float ms_sort = ms_since(t_sort);
+    A->stats.ms_total = A->stats.ms_begin + A->stats.ms_cigar + A->stats.ms_fanout;
+    A->stats.n_alns = A->n;
+    A->stats.n_segment_alns = nk;
+    A->stats.n_ops = A->n_ops;
+    A->stats.ms_host = ms_since(t_call);
+    return ms_sort;
+}
+
 extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_alns **out)
 {
     using namespace spm_hip;
@@ -1478,75 +1549,20 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
     const uint64_t nk = kept.size();
     std::vector<spm_hit> kh(nk);
     std::vector<uint64_t> lo(nk);
-    std::vector<uint32_t> cig_off(nk, 0);
-    uint64_t total_ops = 0;
     for (uint64_t i = 0; i < nk; ++i) {
         kh[i] = kept[i].hit;
         lo[i] = kept[i].lo;
-        cig_off[i] = (uint32_t)total_ops;
-        total_ops += myers ? 2 * (uint64_t)std::max(0, kh[i].score) + 1 : 1;
     }
-    if (total_ops > 0xFFFFFFFFull || nk > 0xFFFFFFFFull) {
-        SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: the CIGAR pool would exceed 2^32 words");
-        return SPM_E_UNSUPPORTED;
-    }
-    A->n_ops = begin_only ? 0 : total_ops;
-    A->host_ops.resize(A->n_ops);
-    A->stats.ms_worklist = ms_since(t_call);
-
     if (nk) {
-        dev_scratch tmp;
+        dev_scratch tmp; // (released inside this block: its hipFree is part of ms_host, as it always was)
         spm_aln *d_seg_alns = nullptr;
         unsigned long long *d_count = nullptr;
-        SPM_HIP_CHECK(ctx, tmp.alloc(&d_seg_alns, nk * sizeof(spm_aln)));
         SPM_HIP_CHECK(ctx, tmp.alloc(&d_count, 8));
         SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_jst_aln)));
-        if (A->n_ops)
-            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
-        if (myers) {
-            // stage A / stage B over the context buffer: lo = the start of the hit's context, positions as they are
-            align_work W{};
-            W.ps = ps;
-            W.text = J->ctx_text;
-            W.pos_offset = 0;
-            W.hits = kh.data();
-            W.n = nk;
-            W.lo = lo.data();
-            W.cig_off = cig_off.data();
-            W.begin_only = begin_only;
-            W.d_recs = d_seg_alns;
-            W.d_ops = A->d_ops;
-            W.n_ops = A->n_ops;
-            W.h_ops = A->host_ops.data();
-            W.who = "spm_hip_jst_hits_align";
-            spm_align_stats as{};
-            const int rc = align_run(ctx, W, as);
-            if (rc != SPM_OK)
-                return rc;
-            A->stats.ms_begin = as.ms_begin;
-            A->stats.ms_cigar = as.ms_cigar;
-            A->stats.begin_lane = as.begin_lane;
-            A->stats.begin_wave = as.begin_wave;
-            A->stats.cigar_lane = as.cigar_lane;
-            A->stats.cigar_wave = as.cigar_wave;
-            A->stats.cigar_wave_global = as.cigar_wave_global;
-        } else {
-            SPM_TRY(jst_fill_exact_alns(ctx, ps, kh, cig_off, begin_only, d_seg_alns, A.get()));
-        }
+        SPM_TRY(jst_align_segments(ctx, J, ps, kh, lo, begin_only, t_call, "spm_hip_jst_hits_align", tmp, A.get(), &d_seg_alns));
         // ---- the fan-out: one record per (haplotype, hit), the transcript shared ----
-        struct event_pair
-        {
-            hipEvent_t a = nullptr, b = nullptr;
-            ~event_pair()
-            {
-                if (a)
-                    hipEventDestroy(a);
-                if (b)
-                    hipEventDestroy(b);
-            }
-        } ev;
-        SPM_HIP_CHECK(ctx, hipEventCreate(&ev.a));
-        SPM_HIP_CHECK(ctx, hipEventCreate(&ev.b));
+        hip_events<2> ev;
+        SPM_HIP_CHECK(ctx, ev.create());
         jst_alnfan_params F{};
         F.segs = d_seg_alns;
         F.n_segs = nk;
@@ -1560,33 +1576,27 @@ extern "C" int spm_hip_jst_hits_align(spm_jst_hits *h, uint32_t flags, spm_jst_a
         F.out_count = d_count;
         F.out_cap = n;
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_count, 0, 8, st));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.a, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         hipLaunchKernelGGL(jst_aln_fanout_kernel, dim3((unsigned)std::min<uint64_t>((nk + 255) / 256, (uint64_t)ctx->n_cu * 64)),
                            dim3(256), 0, st, J->dev(), F);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.b, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         unsigned long long n_out = 0;
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(&n_out, d_count, 8, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        hipEventElapsedTime(&A->stats.ms_fanout, ev.a, ev.b);
+        hipEventElapsedTime(&A->stats.ms_fanout, ev[0], ev[1]);
         if (n_out != n) {
             SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: the fan-out wrote %llu alignment records for %llu hits", n_out,
                         (unsigned long long)n);
             return SPM_E_INVALID;
         }
-        A->host.resize(n);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost, st));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        jst_sort_alns_host(A->host, myers);
+        SPM_TRY(jst_alns_download(ctx, A.get()));
     } else if (n) {
         SPM_SET_ERR(ctx, "spm_hip_jst_hits_align: %llu hits but no segment hit to align", (unsigned long long)n);
         return SPM_E_INVALID;
-    }
-    A->stats.ms_total = A->stats.ms_begin + A->stats.ms_cigar + A->stats.ms_fanout;
-    A->stats.n_alns = n;
-    A->stats.n_segment_alns = nk;
-    A->stats.n_ops = A->n_ops;
-    A->stats.ms_host = ms_since(t_call);
+    } else
+        A->stats.ms_worklist = ms_since(t_call); // (nothing to align: an empty pool)
+    jst_alns_close(A.get(), nk, myers, t_call);
     if (spm_trace_on())
         fprintf(stderr, "[spm_hip] jst align: %llu segment alignments -> %llu records%s: begins %.3f ms, transcripts %.3f, "
                         "fan-out %.3f; %.3f ms in all (work list %.3f)\n", (unsigned long long)nk, (unsigned long long)n,

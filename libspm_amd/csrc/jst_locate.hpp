@@ -17,6 +17,8 @@
 //   (hipcub exclusive sum of the head flags: the number u of every distinct segment hit)
 //   jst_locate_emit_kernel  heads write the compact spm_hit list (already in pool order), every record uid[arrival] = u
 //   jst_aln_gather_kernel   one lane per kept record i: record i + seg_alns[uid[i]] -> the 40-byte spm_jst_aln i
+// Between emit and gather: jst_align_segments; the end: jst_alns_download / _close (jst.hpp's, shared with spm_hip_jst_hits_align).
+// The scratch is laid out with scratch_layout.hpp; the sort, the sum and the events are device_order.hpp's.
 #pragma once
 
 #include "select_plan.hpp"
@@ -232,11 +234,6 @@ __global__ __launch_bounds__(256) void jst_aln_gather_kernel(const unsigned long
 
 static_assert(sizeof(spm_jst_aln) == 5 * 8 && sizeof(spm_jst_hit) == 3 * 8 && sizeof(spm_aln) == 32, "word layouts of the gather");
 
-namespace
-{
-inline size_t jloc_align_up(size_t v) { return (v + 255) & ~size_t(255); }
-} // namespace
-
 extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_jst_alns **out)
 {
     using namespace spm_hip;
@@ -273,7 +270,6 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: %s (%u + %u bits)", plan.why, plan.pat_bits, plan.ctx_bits);
         return plan.status;
     }
-    const uint32_t ctx_bits = plan.ctx_bits;
     SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<spm_jst_alns, void (*)(spm_jst_alns *)> A(new spm_jst_alns, spm_hip_jst_alns_destroy);
     A->ctx = ctx;
@@ -282,56 +278,34 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
     A->patterns = ps;
     A->generation = J->generation;
     A->begin_only = begin_only;
-    A->stats.n_alns = n;
     hipStream_t st = ctx->stream;
     uint64_t nk = 0;
     float ms_locate = 0, ms_gather = 0;
     if (n) {
         const uint32_t n32 = (uint32_t)n;
-        const int key_bits = (int)plan.key_bits;
-        struct event_set
-        {
-            hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-            ~event_set()
-            {
-                for (hipEvent_t x : e)
-                    if (x)
-                        hipEventDestroy(x);
-            }
-        } ev;
-        for (hipEvent_t &e : ev.e)
-            SPM_HIP_CHECK(ctx, hipEventCreate(&e));
+        hip_events<4> ev; // locate + order [0, 1], gather [2, 3]
+        SPM_HIP_CHECK(ctx, ev.create());
         // the scratch of locate + order: keys and indices twice (the sort's in and out), scores, head flags, their sums, the
         // counts, the distinct hits.  uid and the records outlive align_run, which may grow the context's scratch: they are
         // buffers of their own.
         size_t sort_bytes = 0, scan_bytes = 0;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr,
-                                                              (unsigned long long *)nullptr, (const uint32_t *)nullptr,
-                                                              (uint32_t *)nullptr, (size_t)n32, 0, key_bits, st));
-        using count_iter = hipcub::CountingInputIterator<uint32_t>;
-        using head_iter = hipcub::TransformInputIterator<uint32_t, jloc_head_op, count_iter>;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, head_iter(count_iter(0), jloc_head_op{nullptr}),
-                                                            (uint32_t *)nullptr, (size_t)n32, st));
+        SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n32, plan.key_bits, &sort_bytes));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jloc_head_op{nullptr}), n32, &scan_bytes));
         const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += jloc_align_up(bytes);
-            return at;
-        };
-        const size_t o_keys0 = take(n * 8), o_keys1 = take(n * 8), o_idx0 = take(n * 4), o_idx1 = take(n * 4),
-                     o_score = take(n * 4), o_head = take(n), o_offs = take(n * 4), o_counts = take(16),
-                     o_tmp = take(tmp_bytes), o_list = take(n * sizeof(spm_hit));
-        SPM_TRY(ensure_scratch(ctx, off));
-        uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
-        unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + o_keys0);
-        unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + o_keys1);
-        uint32_t *idx_in = reinterpret_cast<uint32_t *>(base + o_idx0), *idx = reinterpret_cast<uint32_t *>(base + o_idx1);
-        int32_t *score = reinterpret_cast<int32_t *>(base + o_score);
-        uint8_t *head = base + o_head;
-        uint32_t *offs = reinterpret_cast<uint32_t *>(base + o_offs);
-        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + o_counts);
-        spm_hit *d_list = reinterpret_cast<spm_hit *>(base + o_list);
+        scratch_layout L;
+        const size_t o_keys0 = L.take(n * 8), o_keys1 = L.take(n * 8), o_idx0 = L.take(n * 4), o_idx1 = L.take(n * 4),
+                     o_score = L.take(n * 4), o_head = L.take(n), o_offs = L.take(n * 4), o_counts = L.take(16),
+                     o_tmp = L.take(tmp_bytes), o_list = L.take(n * sizeof(spm_hit));
+        SPM_TRY(ensure_scratch(ctx, L.bytes()));
+        void *base = ctx->d_scratch;
+        unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0), *keys = L.at<unsigned long long>(base, o_keys1);
+        uint32_t *idx_in = L.at<uint32_t>(base, o_idx0), *idx = L.at<uint32_t>(base, o_idx1);
+        int32_t *score = L.at<int32_t>(base, o_score);
+        uint8_t *head = L.at<uint8_t>(base, o_head);
+        uint32_t *offs = L.at<uint32_t>(base, o_offs);
+        unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
+        void *d_tmp = L.at<uint8_t>(base, o_tmp);
+        spm_hit *d_list = L.at<spm_hit>(base, o_list);
         dev_scratch tmp;
         uint32_t *d_uid = nullptr;
         spm_aln *d_seg_alns = nullptr;
@@ -355,30 +329,26 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         P.m = ps->d_m;
         P.n_patterns = ps->n;
         P.report_begin = myers ? 0 : 1;
-        P.ctx_bits = ctx_bits;
+        P.ctx_bits = plan.ctx_bits;
         P.keys = keys_in;
         P.idx = idx_in;
         P.score = score;
         P.counts = d_counts;
         const unsigned grid = (unsigned)((n + 255) / 256);
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 16, st));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[0], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         hipLaunchKernelGGL(jst_locate_kernel, dim3(grid), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        size_t tb = tmp_bytes;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, (const unsigned long long *)keys_in, keys,
-                                                              (const uint32_t *)idx_in, idx, (size_t)n32, 0, key_bits, st));
+        SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, keys_in, keys, idx_in, idx, n32, plan.key_bits));
         hipLaunchKernelGGL(jst_locate_heads_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
                            (const uint32_t *)idx, (const int32_t *)score, n32, head, d_counts);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        tb = tmp_bytes;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, head_iter(count_iter(0), jloc_head_op{head}), offs,
-                                                            (size_t)n32, st));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jloc_head_op{head}), offs, n32));
         hipLaunchKernelGGL(jst_locate_emit_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
                            (const uint32_t *)idx, (const int32_t *)score, (const uint8_t *)head, (const uint32_t *)offs, n32,
-                           ctx_bits, d_list, d_uid, d_counts);
+                           plan.ctx_bits, d_list, d_uid, d_counts);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[1], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // the one read-back: {distinct, errors}; the context tables travel with it, once per index generation
         unsigned long long *c = ctx->h_counters;
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, 16, hipMemcpyDeviceToHost, st));
@@ -401,8 +371,6 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
         const std::vector<uint64_t> &coff = J->h_ctx_off;
         std::vector<uint64_t> lo(nk);
-        std::vector<uint32_t> cig_off(nk, 0);
-        uint64_t total_ops = 0;
         for (uint64_t i = 0; i < nk; ++i) {
             const spm_hit &x = kh[i];
             const uint64_t last = x.pattern >= ps->n ? ~0ull : myers ? x.pos - 1 : x.pos + (uint64_t)ps->m[x.pattern] - 1;
@@ -411,67 +379,24 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
                 return SPM_E_INVALID;
             }
             lo[i] = coff[(uint64_t)(std::upper_bound(coff.begin(), coff.begin() + (long)J->n_ctx, last) - coff.begin()) - 1];
-            cig_off[i] = (uint32_t)total_ops;
-            total_ops += myers ? 2 * (uint64_t)std::max(0, x.score) + 1 : 1;
         }
-        if (total_ops > 0xFFFFFFFFull) {
-            SPM_SET_ERR(ctx, "spm_hip_jst_selection_align: the CIGAR pool would exceed 2^32 words");
-            return SPM_E_UNSUPPORTED;
-        }
-        A->n_ops = begin_only ? 0 : total_ops;
-        A->host_ops.resize(A->n_ops);
-        A->stats.ms_worklist = ms_since(t_list);
-        SPM_HIP_CHECK(ctx, tmp.alloc(&d_seg_alns, nk * sizeof(spm_aln)));
-        if (A->n_ops)
-            SPM_HIP_CHECK(ctx, hipMalloc(&A->d_ops, A->n_ops * 4));
-        if (myers) {
-            align_work W{};
-            W.ps = ps;
-            W.text = J->ctx_text;
-            W.pos_offset = 0;
-            W.hits = kh.data();
-            W.n = nk;
-            W.lo = lo.data();
-            W.cig_off = cig_off.data();
-            W.begin_only = begin_only;
-            W.d_recs = d_seg_alns;
-            W.d_ops = A->d_ops;
-            W.n_ops = A->n_ops;
-            W.h_ops = A->host_ops.data();
-            W.who = "spm_hip_jst_selection_align";
-            spm_align_stats as{};
-            SPM_TRY(align_run(ctx, W, as));
-            A->stats.ms_begin = as.ms_begin;
-            A->stats.ms_cigar = as.ms_cigar;
-            A->stats.begin_lane = as.begin_lane;
-            A->stats.begin_wave = as.begin_wave;
-            A->stats.cigar_lane = as.cigar_lane;
-            A->stats.cigar_wave = as.cigar_wave;
-            A->stats.cigar_wave_global = as.cigar_wave_global;
-        } else {
-            SPM_TRY(jst_fill_exact_alns(ctx, ps, kh, cig_off, begin_only, d_seg_alns, A.get()));
-        }
+        SPM_TRY(jst_align_segments(ctx, J, ps, kh, lo, begin_only, t_list, "spm_hip_jst_selection_align", tmp, A.get(),
+                                   &d_seg_alns));
         // ---- the gather: record i of the selection's device view -> alignment record i ----
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[2], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         hipLaunchKernelGGL(jst_aln_gather_kernel, dim3(grid), dim3(256), 0, st, P.recs, (const uint32_t *)d_uid,
                            (const spm_aln *)d_seg_alns, n32, (uint32_t)nk, P.report_begin,
                            reinterpret_cast<unsigned long long *>(A->d_recs));
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[3], st));
-        A->host.resize(n);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(A->host.data(), A->d_recs, n * sizeof(spm_jst_aln), hipMemcpyDeviceToHost, st));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        hipEventElapsedTime(&ms_locate, ev.e[0], ev.e[1]);
-        hipEventElapsedTime(&ms_gather, ev.e[2], ev.e[3]);
-        const auto t_sort = clk::now();
-        jst_sort_alns_host(A->host, myers);
-        A->stats.ms_worklist += ms_since(t_sort);
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
+        SPM_TRY(jst_alns_download(ctx, A.get()));
+        hipEventElapsedTime(&ms_locate, ev[0], ev[1]);
+        hipEventElapsedTime(&ms_gather, ev[2], ev[3]);
+        A->stats.ms_fanout = ms_locate + ms_gather;
     }
-    A->stats.ms_fanout = ms_locate + ms_gather;
-    A->stats.ms_total = A->stats.ms_begin + A->stats.ms_cigar + A->stats.ms_fanout;
-    A->stats.n_segment_alns = nk;
-    A->stats.n_ops = A->n_ops;
-    A->stats.ms_host = ms_since(t_call);
+    const float ms_sort = jst_alns_close(A.get(), nk, myers, t_call);
+    if (n)
+        A->stats.ms_worklist += ms_sort; // the work list's second piece: the host order of the records
     if (spm_trace_on())
         fprintf(stderr, "[spm_hip] jst selection align: %llu kept records -> %llu segment alignments%s: locate + order %.3f ms, "
                         "begins %.3f, transcripts %.3f, gather %.3f; %.3f ms in all (work list %.3f)\n", (unsigned long long)n,

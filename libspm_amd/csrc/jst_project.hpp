@@ -13,6 +13,7 @@
 //   (hipcub exclusive sum of the word counts, 64 bits; jst_proj_total_kernel; the one read-back that sizes the pool)
 //   jst_proj_emit_kernel     the same walk with a writing sink
 //   jst_proj_gather_kernel   one lane per record i: its own record + the result of its slot -> spm_jst_ref_aln i
+// The scratch is laid out with scratch_layout.hpp; the sums, the first read-back and the events are device_order.hpp's.
 // The walk starts from the tables of the index and runs forward as far as the transcript reaches: it assumes neither that a
 // carried deletion ends inside its block nor that begin and end lie in the same block.
 #pragma once
@@ -305,42 +306,24 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         SPM_TRY(spm_align_tables(ps)); // the needles' ranks on the device (built once per set)
         const uint32_t n32 = (uint32_t)n;
         const uint32_t cap = (uint32_t)std::min<uint64_t>(n, n_src_ops);
-        struct event_set
-        {
-            hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            ~event_set()
-            {
-                for (hipEvent_t x : e)
-                    if (x)
-                        hipEventDestroy(x);
-            }
-        } ev;
-        for (hipEvent_t &e : ev.e)
-            SPM_HIP_CHECK(ctx, hipEventCreate(&e));
-        using count_iter = hipcub::CountingInputIterator<uint32_t>;
-        using flag_iter = hipcub::TransformInputIterator<uint32_t, jproj_flag_op, count_iter>;
-        using wide_iter = hipcub::TransformInputIterator<unsigned long long, jproj_widen_op, count_iter>;
+        hip_events<6> ev;
+        SPM_HIP_CHECK(ctx, ev.create());
         size_t b_flag = 0, b_wide = 0;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, b_flag, flag_iter(count_iter(0), jproj_flag_op{nullptr}),
-                                                            (uint32_t *)nullptr, (size_t)n_src_ops, st));
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, b_wide, wide_iter(count_iter(0), jproj_widen_op{nullptr}),
-                                                            (unsigned long long *)nullptr, (size_t)cap, st));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jproj_flag_op{nullptr}), n_src_ops, &b_flag));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(jproj_widen_op{nullptr}),
+                                                                       cap, &b_wide));
         const size_t tmp_bytes = std::max(b_flag, b_wide);
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += jloc_align_up(bytes);
-            return at;
-        };
-        const size_t o_rep = take(n_src_ops * 4), o_sid = take(n_src_ops * 4), o_rec = take((size_t)cap * 4),
-                     o_range = take((size_t)cap * 16), o_words = take((size_t)cap * 4), o_score = take((size_t)cap * 4),
-                     o_off = take((size_t)cap * 8), o_counts = take(kProjCnts * 8), o_tmp = take(tmp_bytes);
-        SPM_TRY(ensure_scratch(ctx, off));
-        uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
-        uint32_t *d_rep = reinterpret_cast<uint32_t *>(base + o_rep), *d_sid = reinterpret_cast<uint32_t *>(base + o_sid);
-        uint32_t *d_words = reinterpret_cast<uint32_t *>(base + o_words);
-        unsigned long long *d_off = reinterpret_cast<unsigned long long *>(base + o_off);
-        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + o_counts);
+        scratch_layout L;
+        const size_t o_rep = L.take(n_src_ops * 4), o_sid = L.take(n_src_ops * 4), o_rec = L.take((size_t)cap * 4),
+                     o_range = L.take((size_t)cap * 16), o_words = L.take((size_t)cap * 4), o_score = L.take((size_t)cap * 4),
+                     o_off = L.take((size_t)cap * 8), o_counts = L.take(kProjCnts * 8), o_tmp = L.take(tmp_bytes);
+        SPM_TRY(ensure_scratch(ctx, L.bytes()));
+        void *base = ctx->d_scratch;
+        uint32_t *d_rep = L.at<uint32_t>(base, o_rep), *d_sid = L.at<uint32_t>(base, o_sid);
+        uint32_t *d_words = L.at<uint32_t>(base, o_words);
+        unsigned long long *d_off = L.at<unsigned long long>(base, o_off);
+        unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
+        void *d_tmp = L.at<uint8_t>(base, o_tmp);
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_recs, n * sizeof(spm_jst_ref_aln)));
 
         jst_project_params P{};
@@ -356,10 +339,10 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         P.cap = cap;
         P.rep = d_rep;
         P.sid = d_sid;
-        P.slot_rec = reinterpret_cast<uint32_t *>(base + o_rec);
-        P.slot_range = reinterpret_cast<unsigned long long *>(base + o_range);
+        P.slot_rec = L.at<uint32_t>(base, o_rec);
+        P.slot_range = L.at<unsigned long long>(base, o_range);
         P.slot_words = d_words;
-        P.slot_score = reinterpret_cast<int32_t *>(base + o_score);
+        P.slot_score = L.at<int32_t>(base, o_score);
         P.slot_off = d_off;
         P.out_ops = nullptr;
         P.counts = d_counts;
@@ -368,30 +351,26 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
                        g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- representatives: one per distinct slot of the source pool, numbered in pool order ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kProjCnts * 8, st));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[0], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_rep, 0xFF, n_src_ops * 4, st));
         hipLaunchKernelGGL(jst_proj_rep_kernel, dim3(g_rec), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        size_t tb = tmp_bytes;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, flag_iter(count_iter(0), jproj_flag_op{d_rep}), d_sid,
-                                                            (size_t)n_src_ops, st));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jproj_flag_op{d_rep}), d_sid, n_src_ops));
         hipLaunchKernelGGL(jst_proj_compact_kernel, dim3(g_pool), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[1], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- count: the projection of every slot with a counting sink, then where its words go ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_words, 0, (size_t)cap * 4, st));
         hipLaunchKernelGGL(jst_proj_count_kernel, dim3(g_slot), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        tb = tmp_bytes;
-        SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, wide_iter(count_iter(0), jproj_widen_op{d_words}),
-                                                            d_off, (size_t)cap, st));
+        SPM_HIP_CHECK(ctx,
+                      exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(jproj_widen_op{d_words}), d_off, cap));
         hipLaunchKernelGGL(jst_proj_total_kernel, dim3(1), dim3(64), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[2], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         // the one read-back that sizes the pool: {slots, errors, inside an insertion, -, words}
+        SPM_HIP_CHECK(ctx, read_counts(ctx, d_counts, kProjCnts));
         unsigned long long *c = ctx->h_counters;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
         n_slots = c[kProjCntSlots];
         const unsigned long long n_bad = c[kProjCntBad], total = c[kProjCntWords];
         R->stats.n_inside_insertion = c[kProjCntInside];
@@ -409,13 +388,13 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_ops, std::max<uint64_t>(total, 1) * 4));
         P.out_ops = R->d_ops;
         // ---- emit, gather ----
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[3], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
         hipLaunchKernelGGL(jst_proj_emit_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, P, (uint64_t)total);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[4], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
         hipLaunchKernelGGL(jst_proj_gather_kernel, dim3(g_rec), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev.e[5], st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
         // ---- the host view: record i of the source's host view through the slot tables ----
         std::vector<uint32_t> sid(n_src_ops), words(n_slots);
         std::vector<int32_t> score(n_slots);
@@ -430,10 +409,10 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         if (total)
             SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host_ops.data(), R->d_ops, total * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        hipEventElapsedTime(&ms_rep, ev.e[0], ev.e[1]);
-        hipEventElapsedTime(&ms_count, ev.e[1], ev.e[2]);
-        hipEventElapsedTime(&ms_emit, ev.e[3], ev.e[4]);
-        hipEventElapsedTime(&ms_gather, ev.e[4], ev.e[5]);
+        hipEventElapsedTime(&ms_rep, ev[0], ev[1]);
+        hipEventElapsedTime(&ms_count, ev[1], ev[2]);
+        hipEventElapsedTime(&ms_emit, ev[3], ev[4]);
+        hipEventElapsedTime(&ms_gather, ev[4], ev[5]);
         if (c[kProjCntBad]) {
             SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: %llu transcript slots came out of the emit stage differently from the "
                              "count stage", c[kProjCntBad]);

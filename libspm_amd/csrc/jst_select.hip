@@ -1,12 +1,13 @@
 // jst_select.hip -- selection of pan-genome hits behind the C ABI: spm_hip_jst_hits_select, spm_hip_jst_records_select,
 // spm_hip_jst_hits_select_stats.  The host side of jst_select.hpp: plan (select_plan.hpp: plan_jst_select), lay the scratch
-// out, enqueue keys -> sort -> loci -> [group numbers -> minima] -> scan -> compact on the context's stream, read the two
-// counts back (the one synchronisation), hand out a new spm_jst_hits with a buffer of exactly the kept records.
+// out (scratch_layout.hpp), enqueue keys -> sort -> loci -> [group numbers -> minima] -> scan -> compact on the context's
+// stream, read the two counts back (the one synchronisation; sort, scans and read-back are device_order.hpp's), hand out a
+// new spm_jst_hits with a buffer of exactly the kept records.
 // MI355X only; no CPU path exists in this library: if HIP fails the call fails.
 #include "internal.hpp"
+#include "device_order.hpp"
 #include "jst_select.hpp"
-
-#include <hipcub/hipcub.hpp>
+#include "scratch_layout.hpp"
 
 namespace
 {
@@ -21,7 +22,6 @@ struct jsel_source // what the two entry points know about their records
     uint64_t generation = 0;          // what spm_hip_jst_selection_align locates the kept records in
 };
 
-size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 constexpr uint64_t kJselAcrossPatterns = 1ull << 24; // entries of the per-pattern minima of SPM_SELECT_ACROSS, at most (64 MiB)
 
 int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, uint32_t strata, spm_jst_hits *R)
@@ -42,42 +42,32 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
 
     // the scratch: keys and indices twice (the sort's in and out), scores in arrival and in sorted order, flags, offsets,
     // group numbers, minima, counts, the compacted records (their count is known only after the read-back)
-    size_t sort_bytes = 0, scan_bytes = 0, head_bytes = 0;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr,
-                                                          (unsigned long long *)nullptr, (const uint32_t *)nullptr,
-                                                          (uint32_t *)nullptr, (size_t)n, 0, (int)plan.key_bits, ctx->stream));
+    using flag_op = sel_flag_op<jst_select_params>;
     jst_select_params P{};
-    using count_iter = hipcub::CountingInputIterator<uint32_t>;
-    using flag_iter = hipcub::TransformInputIterator<uint32_t, jsel_flag_op, count_iter>;
-    using head_iter = hipcub::TransformInputIterator<uint32_t, jsel_head_op, count_iter>;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flag_iter(count_iter(0), jsel_flag_op{P}),
-                                                        (uint32_t *)nullptr, (size_t)n, ctx->stream));
-    SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, head_bytes, head_iter(count_iter(0), jsel_head_op{nullptr}),
-                                                        (uint32_t *)nullptr, (size_t)n, ctx->stream));
+    size_t sort_bytes = 0, scan_bytes = 0, head_bytes = 0;
+    SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n, plan.key_bits, &sort_bytes));
+    SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(flag_op{P}), n, &scan_bytes));
+    SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jsel_head_op{nullptr}), n, &head_bytes));
     const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, head_bytes));
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes);
-        return at;
-    };
-    const size_t o_keys0 = take((size_t)n * 8), o_keys1 = take((size_t)n * 8), o_idx0 = take((size_t)n * 4),
-                 o_idx1 = take((size_t)n * 4), o_sc0 = take((size_t)n * 4), o_sc1 = take((size_t)n * 4), o_keep = take(n),
-                 o_head = take(n), o_offs = take((size_t)n * 4), o_gid = take(numbered ? (size_t)n * 4 : 0),
-                 o_min = take(n_min * 4), o_counts = take(16), o_tmp = take(tmp_bytes),
-                 o_out = take((size_t)n * sizeof(spm_jst_hit));
-    SPM_TRY(ensure_scratch(ctx, off));
-    uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
-    unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + o_keys0);
-    uint32_t *idx_in = reinterpret_cast<uint32_t *>(base + o_idx0);
-    int32_t *score_in = reinterpret_cast<int32_t *>(base + o_sc0);
-    uint32_t *offs = reinterpret_cast<uint32_t *>(base + o_offs);
-    uint32_t *gid = reinterpret_cast<uint32_t *>(base + o_gid);
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(base + o_out);
+    scratch_layout L;
+    const size_t o_keys0 = L.take((size_t)n * 8), o_keys1 = L.take((size_t)n * 8), o_idx0 = L.take((size_t)n * 4),
+                 o_idx1 = L.take((size_t)n * 4), o_sc0 = L.take((size_t)n * 4), o_sc1 = L.take((size_t)n * 4), o_keep = L.take(n),
+                 o_head = L.take(n), o_offs = L.take((size_t)n * 4), o_gid = L.take(numbered ? (size_t)n * 4 : 0),
+                 o_min = L.take(n_min * 4), o_counts = L.take(16), o_tmp = L.take(tmp_bytes),
+                 o_out = L.take((size_t)n * sizeof(spm_jst_hit));
+    SPM_TRY(ensure_scratch(ctx, L.bytes()));
+    void *base = ctx->d_scratch;
+    unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0);
+    uint32_t *idx_in = L.at<uint32_t>(base, o_idx0);
+    int32_t *score_in = L.at<int32_t>(base, o_sc0);
+    uint32_t *offs = L.at<uint32_t>(base, o_offs);
+    uint32_t *gid = L.at<uint32_t>(base, o_gid);
+    void *tmp = L.at<uint8_t>(base, o_tmp);
+    unsigned long long *d_out = L.at<unsigned long long>(base, o_out);
 
     P.recs = reinterpret_cast<const unsigned long long *>(S.d_recs);
-    P.keys = reinterpret_cast<unsigned long long *>(base + o_keys1);
-    P.idx = reinterpret_cast<uint32_t *>(base + o_idx1);
+    P.keys = L.at<unsigned long long>(base, o_keys1);
+    P.idx = L.at<uint32_t>(base, o_idx1);
     P.score_in = score_in;
     P.n = n;
     P.pos_bits = plan.pos_bits;
@@ -90,49 +80,41 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr; // (WINDOW_K: the set is alive, jsel_make)
     P.halo = plan.halo;
     P.strata = strata;
-    P.keep = base + o_keep;
-    P.head = base + o_head;
-    P.score = reinterpret_cast<int32_t *>(base + o_sc1);
+    P.keep = L.at<uint8_t>(base, o_keep);
+    P.head = L.at<uint8_t>(base, o_head);
+    P.score = L.at<int32_t>(base, o_sc1);
     P.gid = numbered ? gid : nullptr;
-    P.grp_min = plan.best ? reinterpret_cast<int32_t *>(base + o_min) : nullptr;
-    P.counts = reinterpret_cast<unsigned long long *>(base + o_counts);
+    P.minima = plan.best ? L.at<int32_t>(base, o_min) : nullptr;
+    P.counts = L.at<unsigned long long>(base, o_counts);
     SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, 16, ctx->stream));
     if (plan.best)
-        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.grp_min), 0x7FFFFFFF, n_min, ctx->stream));
+        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, n_min, ctx->stream));
 
     // order
     const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256);
     hipLaunchKernelGGL(jst_select_keys_kernel, dim3(grid), dim3(256), 0, ctx->stream, P.recs, keys_in, idx_in, score_in, n,
                        plan.pos_bits, plan.pat_bits);
     SPM_HIP_CHECK(ctx, hipGetLastError());
-    size_t tb = tmp_bytes;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, (const unsigned long long *)keys_in, P.keys,
-                                                          (const uint32_t *)idx_in, P.idx, (size_t)n, 0, (int)plan.key_bits, ctx->stream));
+    SPM_HIP_CHECK(ctx, sort_pairs(ctx, tmp, tmp_bytes, keys_in, P.keys, idx_in, P.idx, n, plan.key_bits));
     SPM_HIP_CHECK(ctx, hipEventRecord(R->sel_ev[1], ctx->stream));
 
     // select
     hipLaunchKernelGGL(jst_select_loci_kernel, dim3((unsigned)(((uint64_t)n + kSelTile - 1) / kSelTile)), dim3(kSelTile), 0, ctx->stream, P);
     SPM_HIP_CHECK(ctx, hipGetLastError());
     if (plan.best) {
-        if (numbered) {
-            tb = tmp_bytes;
-            SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, head_iter(count_iter(0), jsel_head_op{P.head}),
-                                                                gid, (size_t)n, ctx->stream));
-        }
+        if (numbered)
+            SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(jsel_head_op{P.head}), gid, n));
         hipLaunchKernelGGL(jst_select_minima_kernel, dim3(grid), dim3(256), 0, ctx->stream, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
     }
-    tb = tmp_bytes;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb, flag_iter(count_iter(0), jsel_flag_op{P}), offs,
-                                                        (size_t)n, ctx->stream));
+    SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(flag_op{P}), offs, n));
     hipLaunchKernelGGL(jst_select_compact_kernel, dim3(grid), dim3(256), 0, ctx->stream, P, (const uint32_t *)offs, d_out);
     SPM_HIP_CHECK(ctx, hipGetLastError());
     SPM_HIP_CHECK(ctx, hipEventRecord(R->sel_ev[2], ctx->stream));
 
     // the one read-back: how many records LOCI kept, how many the result has
-    unsigned long long *c = ctx->h_counters;
-    SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, 16, hipMemcpyDeviceToHost, ctx->stream));
-    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, 2));
+    const unsigned long long *c = ctx->h_counters;
     R->sel.n_loci = c[0];
     R->sel.n_out = c[1];
     if (c[1] > S.n) {
@@ -250,8 +232,7 @@ extern "C" int spm_hip_jst_records_select(spm_ctx *ctx, const void *device_recor
         hipLaunchKernelGGL(jst_select_range_kernel, dim3(grid), dim3(256), 0, ctx->stream,
                            static_cast<const unsigned long long *>(device_records), (uint32_t)n, d_rng);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_rng, 24, hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, d_rng, 3));
         const uint64_t max_hap = c[0], max_pat = c[1], max_pos = c[2];
         if (patterns && max_pat >= std::max<uint64_t>(patterns->n, 1)) {
             SPM_SET_ERR(ctx, "spm_hip_jst_records_select: a record names pattern %llu, outside the set of %u",
@@ -275,13 +256,7 @@ extern "C" int spm_hip_jst_hits_select_stats(const spm_jst_hits *hc, spm_select_
         SPM_SET_ERR(h->ctx, "spm_hip_jst_hits_select_stats: no selection made these hits");
         return SPM_E_INVALID;
     }
-    if (h->sel_timed) {
-        SPM_HIP_CHECK(h->ctx, hipEventSynchronize(h->sel_ev[2]));
-        hipEventElapsedTime(&h->sel.ms_total, h->sel_ev[0], h->sel_ev[2]);
-        hipEventElapsedTime(&h->sel.ms_order, h->sel_ev[0], h->sel_ev[1]);
-        hipEventElapsedTime(&h->sel.ms_select, h->sel_ev[1], h->sel_ev[2]);
-        h->sel_timed = false;
-    }
+    SPM_HIP_CHECK(h->ctx, select_stats_close(h->sel_timed, h->sel_ev[0], h->sel_ev[1], h->sel_ev[2], h->sel));
     *out = h->sel;
     return SPM_OK;
 }

@@ -7,12 +7,15 @@
 //   jst_select_minima_kernel   BEST: the minimal score of every group, into an array indexed by the group's number (the
 //                              exclusive sum of the head flags) -- or, with ACROSS, by the pattern;
 //   jst_select_compact_kernel  the stratum test and the stable compaction of the kept records, three 8-byte words each.
+// Also here: jst_select_params, the keys and range kernels, the group numbering (jsel_gid, jsel_min_slot), sel_final.
+// Staging, walks, min-scan and the flag functor are select_walk.hpp's, shared with select.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 #include "select_plan.hpp"
+#include "select_walk.hpp"
 
 namespace spm_hip
 {
@@ -38,7 +41,7 @@ struct jst_select_params
     uint8_t *head = nullptr;                  // [n] 1 where a group begins
     int32_t *score = nullptr;                 // [n] scores in sorted order
     const uint32_t *gid = nullptr;            // [n] exclusive sum of head (BEST without ACROSS)
-    int32_t *grp_min = nullptr;               // BEST: minimal score per group number / per pattern (preset to INT_MAX)
+    int32_t *minima = nullptr;                // BEST: minimal score per group number / per pattern (preset to INT_MAX)
     unsigned long long *counts = nullptr;     // [0] records LOCI kept, [1] records of the result
 };
 
@@ -108,81 +111,40 @@ __global__ __launch_bounds__(256) void jst_select_range_kernel(const unsigned lo
     }
 }
 
-// One lane per sorted record, as select_loci_kernel: LDS holds the keys and scores of the tile and of `halo` records on either
-// side; a lane whose window reaches further reads the rest from global memory (needles with k > 32).  The group test is
-// key >> pos_bits, haplotype AND pattern: records of neighbouring haplotypes never see each other.
+// One lane per sorted record, as select_loci_kernel and from the same pieces (select_walk.hpp).  The group test is
+// key >> pos_bits, haplotype AND pattern: records of neighbouring haplotypes never see each other, and every position is
+// allowed (no segment notion).
 __global__ __launch_bounds__(kSelTile) void jst_select_loci_kernel(const jst_select_params P)
 {
-    __shared__ unsigned long long s_key[kSelTile + 2 * kSelHaloCap];
-    __shared__ int32_t s_score[kSelTile + 2 * kSelHaloCap];
-    const uint32_t H = P.halo;
-    const long long tile0 = (long long)blockIdx.x * kSelTile;
-    const long long lds0 = tile0 - H; // sorted index of s_key[0]
-    const long long n = P.n;
-    for (uint32_t t = threadIdx.x; t < kSelTile + 2 * H; t += kSelTile) {
-        const long long j = lds0 + t;
-        if (j >= 0 && j < n) {
-            s_key[t] = P.keys[j];
-            s_score[t] = P.score_in[P.idx[j]];
-        }
-    }
-    __syncthreads();
+    __shared__ unsigned long long s_key[kSelLdsEntries];
+    __shared__ int32_t s_score[kSelLdsEntries];
+    const auto score_of = [&](long long j) { return P.score_in[P.idx[j]]; };
+    const sel_tile T = sel_stage_tile(s_key, s_score, P.keys, P.n, P.halo, score_of);
 
-    const long long i = tile0 + threadIdx.x;
-    const long long lds_end = lds0 + kSelTile + 2 * H;
+    const long long i = (long long)blockIdx.x * kSelTile + threadIdx.x;
     bool kept = false;
-    if (i < n) {
-        const unsigned long long key = s_key[H + threadIdx.x];
-        const int32_t sc = s_score[H + threadIdx.x];
+    if (i < T.n) {
+        const unsigned long long key = s_key[P.halo + threadIdx.x];
+        const int32_t sc = s_score[P.halo + threadIdx.x];
         const unsigned long long grp = jsel_group(P, key);
         P.score[i] = sc;
         kept = true;
         if (i == 0)
             P.head[i] = 1;
         else {
-            const unsigned long long kp = i - 1 >= lds0 ? s_key[i - 1 - lds0] : P.keys[i - 1];
+            const unsigned long long kp = i - 1 >= T.lds0 ? s_key[i - 1 - T.lds0] : P.keys[i - 1];
             P.head[i] = jsel_group(P, kp) != grp ? 1 : 0;
         }
         const unsigned long long w = !P.loci                            ? 0ull
                                      : P.window == SPM_SELECT_WINDOW_K ? (unsigned long long)max(P.k_tab[(uint32_t)grp & P.pat_mask], 0)
                                                                        : P.window;
-        if (w) {
-            const unsigned long long rel = key & P.pos_mask;
-            // to the left: a record there is better when its score is not larger (its position is smaller)
-            for (long long j = i - 1; j >= 0; --j) {
-                const bool in_lds = j >= lds0;
-                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
-                if (jsel_group(P, kj) != grp)
-                    break;
-                const unsigned long long rj = kj & P.pos_mask;
-                if (rel - rj > w)
-                    break;
-                const int32_t sj = in_lds ? s_score[j - lds0] : P.score_in[P.idx[j]];
-                if (sj <= sc) {
-                    kept = false;
-                    break;
-                }
-            }
-            // to the right: only a strictly smaller score is better
-            for (long long j = i + 1; kept && j < n; ++j) {
-                const bool in_lds = j < lds_end;
-                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
-                if (jsel_group(P, kj) != grp)
-                    break;
-                const unsigned long long rj = kj & P.pos_mask;
-                if (rj - rel > w)
-                    break;
-                const int32_t sj = in_lds ? s_score[j - lds0] : P.score_in[P.idx[j]];
-                if (sj < sc)
-                    kept = false;
-            }
-        }
+        if (w)
+            kept = sel_walk_keeps(
+                s_key, s_score, P.keys, T, i, grp, key & P.pos_mask, sc, P.pos_mask, w,
+                [&](unsigned long long k) { return jsel_group(P, k); }, score_of, [](unsigned long long) { return true; });
         P.keep[i] = kept ? 1 : 0;
     }
-    // records LOCI kept: one atomic per wave
-    const unsigned long long kept_mask = __ballot(kept);
-    if ((threadIdx.x & 63) == 0 && kept_mask)
-        atomicAdd(&P.counts[0], (unsigned long long)__popcll(kept_mask));
+    sel_count_kept(kept, &P.counts[0]);
 }
 
 // the number of record i's group among the groups of the sorted list
@@ -193,44 +155,30 @@ __device__ __forceinline__ uint32_t jsel_min_slot(const jst_select_params &P, ui
     return P.across ? (uint32_t)jsel_group(P, P.keys[i]) & P.pat_mask : jsel_gid(P, i);
 }
 
-// BEST: lanes of one group are contiguous (sorted input), so a segmented min-scan over the wave leaves the minimum of every
-// run in its last lane, which issues the one atomicMin of that wave and group.  A table of n_haplotypes x n_patterns minima
-// would not fit; the groups that occur are numbered instead, and there are at most n of them.
+// BEST: the last lane of every run of one group in a wave (sel_run_min) issues the one atomicMin of that wave and group.  A
+// table of n_haplotypes x n_patterns minima would not fit; the groups that occur are numbered instead, and there are at
+// most n of them.
 __global__ __launch_bounds__(256) void jst_select_minima_kernel(const jst_select_params P)
 {
     const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
     const bool valid = i < P.n;
-    const uint32_t lane = threadIdx.x & 63;
     unsigned long long grp = ~0ull;
-    int32_t m = 0x7FFFFFFF;
+    int32_t sc = 0x7FFFFFFF;
     if (valid) {
         grp = jsel_group(P, P.keys[i]);
-        m = P.score[i];
+        sc = P.score[i];
     }
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t m2 = __shfl_up(m, d);
-        const unsigned long long g2 = __shfl_up(grp, d);
-        if (lane >= (uint32_t)d && g2 == grp)
-            m = m2 < m ? m2 : m;
-    }
-    const unsigned long long g_next = __shfl_down(grp, 1);
-    if (valid && (lane == 63 || g_next != grp || i + 1 >= P.n))
-        atomicMin(&P.grp_min[jsel_min_slot(P, (uint32_t)i)], m);
+    bool run_ends;
+    const int32_t m = sel_run_min(grp, sc, run_ends);
+    if (valid && (run_ends || i + 1 >= P.n))
+        atomicMin(&P.minima[jsel_min_slot(P, (uint32_t)i)], m);
 }
 
-// what the exclusive scan adds up and the compaction tests again: LOCI's verdict and the stratum test
-__device__ __forceinline__ uint32_t jsel_final_flag(const jst_select_params &P, uint32_t i)
+// the final flag of sorted record i
+__device__ __forceinline__ uint32_t sel_final(const jst_select_params &P, uint32_t i)
 {
-    uint32_t f = P.keep[i];
-    if (f && P.best)
-        f = (long long)P.score[i] <= (long long)P.grp_min[jsel_min_slot(P, i)] + P.strata ? 1u : 0u;
-    return f;
+    return sel_final_flag(P, i, [&](uint32_t r) { return jsel_min_slot(P, r); });
 }
-struct jsel_flag_op
-{
-    jst_select_params P;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return jsel_final_flag(P, i); }
-};
 struct jsel_head_op
 {
     const uint8_t *head;
@@ -245,7 +193,7 @@ __global__ __launch_bounds__(256) void jst_select_compact_kernel(const jst_selec
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= P.n)
         return;
-    const uint32_t f = jsel_final_flag(P, i);
+    const uint32_t f = sel_final(P, i);
     const uint32_t o = offs[i];
     if (f) {
         const unsigned long long *src = P.recs + 3ull * P.idx[i];

@@ -1,11 +1,12 @@
 // select.hip -- selection of hits behind the C ABI: spm_hip_hits_select, spm_hip_records_select, spm_hip_hits_select_stats.
-// The host side of select.hpp: plan (select_plan.hpp), lay the scratch out, enqueue keys -> sort -> loci -> scan -> compact
-// on the context's stream, read the two counts back (the one synchronisation), hand out a new spm_hits.
+// The host side of select.hpp: plan (select_plan.hpp), lay the scratch out (scratch_layout.hpp), enqueue keys -> sort -> loci
+// -> scan -> compact on the context's stream, read the two counts back (the one synchronisation; device_order.hpp has the
+// sort, the scan and the read-back), hand out a new spm_hits.
 // MI355X only; no CPU path exists in this library: if HIP fails the call fails.
 #include "internal.hpp"
+#include "device_order.hpp"
+#include "scratch_layout.hpp"
 #include "select.hpp"
-
-#include <hipcub/hipcub.hpp>
 
 namespace
 {
@@ -41,8 +42,6 @@ struct select_source // what the two entry points know about their records
     uint64_t cap = 0;                    // capacity of the result's hit block
 };
 
-size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
-
 int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, uint32_t strata, spm_hits *H)
 {
     const uint32_t n = (uint32_t)S.n;
@@ -57,35 +56,27 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     const uint64_t n_segs = S.segs && S.segs->size() > 1 ? S.segs->size() - 1 : 0;
 
     // the scratch: keys and indices twice (the sort's in and out), flags, scores, offsets, minima, segment table, counts
-    size_t sort_bytes = 0, scan_bytes = 0;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long *)nullptr,
-                                                          (unsigned long long *)nullptr, (const uint32_t *)nullptr,
-                                                          (uint32_t *)nullptr, (size_t)n, 0, (int)plan.key_bits, ctx->stream));
+    using flag_op = sel_flag_op<select_params>;
     select_params P{};
-    using flag_iter = hipcub::TransformInputIterator<uint32_t, sel_flag_op, hipcub::CountingInputIterator<uint32_t>>;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes,
-                                                        flag_iter(hipcub::CountingInputIterator<uint32_t>(0), sel_flag_op{P}),
-                                                        (uint32_t *)nullptr, (size_t)n, ctx->stream));
+    size_t sort_bytes = 0, scan_bytes = 0;
+    SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n, plan.key_bits, &sort_bytes));
+    SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(flag_op{P}), n, &scan_bytes));
     const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes);
-        return at;
-    };
-    const size_t o_keys0 = take((size_t)n * 8), o_keys1 = take((size_t)n * 8), o_idx0 = take((size_t)n * 4),
-                 o_idx1 = take((size_t)n * 4), o_keep = take(n), o_score = take((size_t)n * 4), o_offs = take((size_t)n * 4),
-                 o_min = take(plan.best ? S.n_patterns * 4 : 0), o_segs = take(n_segs ? (n_segs + 1) * 8 : 0), o_counts = take(16),
-                 o_tmp = take(tmp_bytes);
-    SPM_TRY(ensure_scratch(ctx, off));
-    uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
-    unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + o_keys0);
-    uint32_t *idx_in = reinterpret_cast<uint32_t *>(base + o_idx0);
-    uint32_t *offs = reinterpret_cast<uint32_t *>(base + o_offs);
+    scratch_layout L;
+    const size_t o_keys0 = L.take((size_t)n * 8), o_keys1 = L.take((size_t)n * 8), o_idx0 = L.take((size_t)n * 4),
+                 o_idx1 = L.take((size_t)n * 4), o_keep = L.take(n), o_score = L.take((size_t)n * 4),
+                 o_offs = L.take((size_t)n * 4), o_min = L.take(plan.best ? S.n_patterns * 4 : 0),
+                 o_segs = L.take(n_segs ? (n_segs + 1) * 8 : 0), o_counts = L.take(16), o_tmp = L.take(tmp_bytes);
+    SPM_TRY(ensure_scratch(ctx, L.bytes()));
+    void *base = ctx->d_scratch;
+    unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0);
+    uint32_t *idx_in = L.at<uint32_t>(base, o_idx0);
+    uint32_t *offs = L.at<uint32_t>(base, o_offs);
+    void *tmp = L.at<uint8_t>(base, o_tmp);
 
     P.recs = S.d_recs;
-    P.keys = reinterpret_cast<unsigned long long *>(base + o_keys1);
-    P.idx = reinterpret_cast<uint32_t *>(base + o_idx1);
+    P.keys = L.at<unsigned long long>(base, o_keys1);
+    P.idx = L.at<uint32_t>(base, o_idx1);
     P.n = n;
     P.pos_bits = plan.pos_bits;
     P.pos_mask = plan.pos_bits >= 64 ? ~0ull : (1ull << plan.pos_bits) - 1;
@@ -96,12 +87,12 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr;
     P.halo = plan.halo;
     P.strata = strata;
-    P.keep = base + o_keep;
-    P.score = reinterpret_cast<int32_t *>(base + o_score);
-    P.pat_min = plan.best ? reinterpret_cast<int32_t *>(base + o_min) : nullptr;
-    P.counts = reinterpret_cast<unsigned long long *>(base + o_counts);
+    P.keep = L.at<uint8_t>(base, o_keep);
+    P.score = L.at<int32_t>(base, o_score);
+    P.minima = plan.best ? L.at<int32_t>(base, o_min) : nullptr;
+    P.counts = L.at<unsigned long long>(base, o_counts);
     if (n_segs) {
-        unsigned long long *d_segs = reinterpret_cast<unsigned long long *>(base + o_segs);
+        unsigned long long *d_segs = L.at<unsigned long long>(base, o_segs);
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, S.segs->data(), (n_segs + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         P.segs = d_segs;
         P.n_segs = n_segs;
@@ -110,34 +101,28 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     }
     SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, 16, ctx->stream));
     if (plan.best)
-        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.pat_min), 0x7FFFFFFF, S.n_patterns, ctx->stream));
+        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, S.n_patterns, ctx->stream));
 
     // order
     const unsigned grid = (n + 255u) / 256u;
     hipLaunchKernelGGL(select_keys_kernel, dim3(grid), dim3(256), 0, ctx->stream, S.d_recs, keys_in, idx_in, n, plan.pos_bits,
                        (unsigned long long)S.bias);
     SPM_HIP_CHECK(ctx, hipGetLastError());
-    size_t tb = tmp_bytes;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, (const unsigned long long *)keys_in, P.keys,
-                                                          (const uint32_t *)idx_in, P.idx, (size_t)n, 0, (int)plan.key_bits, ctx->stream));
+    SPM_HIP_CHECK(ctx, sort_pairs(ctx, tmp, tmp_bytes, keys_in, P.keys, idx_in, P.idx, n, plan.key_bits));
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
 
     // select
     hipLaunchKernelGGL(select_loci_kernel, dim3((n + kSelTile - 1) / kSelTile), dim3(kSelTile), 0, ctx->stream, P);
     SPM_HIP_CHECK(ctx, hipGetLastError());
-    tb = tmp_bytes;
-    SPM_HIP_CHECK(ctx, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, tb,
-                                                        flag_iter(hipcub::CountingInputIterator<uint32_t>(0), sel_flag_op{P}),
-                                                        offs, (size_t)n, ctx->stream));
+    SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(flag_op{P}), offs, n));
     hipLaunchKernelGGL(select_compact_kernel, dim3(grid), dim3(256), 0, ctx->stream, P, (const uint32_t *)offs, H->d_hits,
                        H->d_count + kCntHits);
     SPM_HIP_CHECK(ctx, hipGetLastError());
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
 
     // the one read-back: how many records LOCI kept, how many the result has
-    unsigned long long *c = ctx->h_counters;
-    SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, 16, hipMemcpyDeviceToHost, ctx->stream));
-    SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, 2));
+    const unsigned long long *c = ctx->h_counters;
     H->sel.n_loci = c[0];
     H->sel.n_out = c[1];
     H->n = c[1];
@@ -282,8 +267,7 @@ extern "C" int spm_hip_records_select(spm_ctx *ctx, const void *device_records, 
         const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 8);
         hipLaunchKernelGGL(select_range_kernel, dim3(grid), dim3(256), 0, ctx->stream, S.d_recs, (uint32_t)n, d_rng);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_rng, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, d_rng, 3));
         const uint64_t lo = c[0] ^ (1ull << 63), hi = c[1] ^ (1ull << 63), max_pat = c[2];
         if (patterns && max_pat >= std::max<uint64_t>(patterns->n, 1)) {
             SPM_SET_ERR(ctx, "spm_hip_records_select: a record names pattern %llu, outside the set of %u",
@@ -315,13 +299,7 @@ extern "C" int spm_hip_hits_select_stats(const spm_hits *hc, spm_select_stats *o
         SPM_SET_ERR(h->ctx, "spm_hip_hits_select_stats: no selection made these hits");
         return SPM_E_INVALID;
     }
-    if (h->sel_timed) {
-        SPM_HIP_CHECK(h->ctx, hipEventSynchronize(h->ev[2]));
-        hipEventElapsedTime(&h->sel.ms_total, h->ev[0], h->ev[2]);
-        hipEventElapsedTime(&h->sel.ms_order, h->ev[0], h->ev[1]);
-        hipEventElapsedTime(&h->sel.ms_select, h->ev[1], h->ev[2]);
-        h->sel_timed = false;
-    }
+    SPM_HIP_CHECK(h->ctx, select_stats_close(h->sel_timed, h->ev[0], h->ev[1], h->ev[2], h->sel));
     *out = h->sel;
     return SPM_OK;
 }

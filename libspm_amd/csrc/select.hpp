@@ -6,12 +6,14 @@
 //                          scores with a halo on either side is staged in LDS; also the per-pattern score minima;
 //   select_compact_kernel  the stratum test, and the stable compaction of the kept records into the new hit block through an
 //                          exclusive scan of the keep flags (the order IS the contract: no slot atomics).
+// Also here: select_params, the keys and range kernels, sel_final.  Staging, walks, min-scan, flag functor: select_walk.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 #include "select_plan.hpp"
+#include "select_walk.hpp"
 
 namespace spm_hip
 {
@@ -38,7 +40,7 @@ struct select_params
     // out
     uint8_t *keep = nullptr;                  // [n] LOCI's verdict
     int32_t *score = nullptr;                 // [n] scores in sorted order
-    int32_t *pat_min = nullptr;               // [n_patterns] minimal score of every pattern (BEST only; preset to INT_MAX)
+    int32_t *minima = nullptr;                // [n_patterns] minimal score of every pattern (BEST only; preset to INT_MAX)
     unsigned long long *counts = nullptr;     // [0] records LOCI kept, [1] records of the result
 };
 
@@ -89,33 +91,22 @@ __global__ __launch_bounds__(256) void select_range_kernel(const spm_hit *__rest
 }
 
 // One lane per sorted record.  LDS holds the keys and scores of the tile and of `halo` records on either side; a lane whose
-// window reaches further reads the rest from global memory (windows above kSelHaloCap, i.e. needles with k > 32).
+// window reaches further reads global memory (needles with k > 32).  Here: the pattern as the group, the segment range.
 __global__ __launch_bounds__(kSelTile) void select_loci_kernel(const select_params P)
 {
-    __shared__ unsigned long long s_key[kSelTile + 2 * kSelHaloCap];
-    __shared__ int32_t s_score[kSelTile + 2 * kSelHaloCap];
-    const uint32_t H = P.halo;
-    const long long tile0 = (long long)blockIdx.x * kSelTile;
-    const long long lds0 = tile0 - H; // sorted index of s_key[0]
-    const long long n = P.n;
-    for (uint32_t t = threadIdx.x; t < kSelTile + 2 * H; t += kSelTile) {
-        const long long j = lds0 + t;
-        if (j >= 0 && j < n) {
-            s_key[t] = P.keys[j];
-            s_score[t] = P.recs[P.idx[j]].score;
-        }
-    }
-    __syncthreads();
+    __shared__ unsigned long long s_key[kSelLdsEntries];
+    __shared__ int32_t s_score[kSelLdsEntries];
+    const auto score_of = [&](long long j) { return P.recs[P.idx[j]].score; };
+    const sel_tile T = sel_stage_tile(s_key, s_score, P.keys, P.n, P.halo, score_of);
 
-    const long long i = tile0 + threadIdx.x;
-    const bool valid = i < n;
-    const long long lds_end = lds0 + kSelTile + 2 * H;
+    const long long i = (long long)blockIdx.x * kSelTile + threadIdx.x;
+    const bool valid = i < T.n;
     uint32_t pat = 0xFFFFFFFFu;
     int32_t sc = 0x7FFFFFFF;
     bool kept = false;
     if (valid) {
-        const unsigned long long key = s_key[H + threadIdx.x];
-        sc = s_score[H + threadIdx.x];
+        const unsigned long long key = s_key[P.halo + threadIdx.x];
+        sc = s_score[P.halo + threadIdx.x];
         pat = sel_pattern(P, key);
         P.score[i] = sc;
         kept = true;
@@ -139,77 +130,27 @@ __global__ __launch_bounds__(kSelTile) void select_loci_kernel(const select_para
                 p_lo = a == 0 ? 0ull : P.segs[a] + P.seg_myers;
                 p_hi = a + 1 == P.n_segs ? ~0ull : P.segs[a + 1] - 1 + P.seg_myers;
             }
-            // to the left: a record there is better when its score is not larger (its position is smaller)
-            for (long long j = i - 1; j >= 0; --j) {
-                const bool in_lds = j >= lds0;
-                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
-                if (sel_pattern(P, kj) != pat)
-                    break;
-                const unsigned long long rj = kj & P.pos_mask;
-                if (rel - rj > w)
-                    break;
-                const unsigned long long pj = rj + P.seg_bias;
-                if (pj < p_lo || pj > p_hi)
-                    break; // (segments are ranges of positions: nothing further left is in this one)
-                const int32_t sj = in_lds ? s_score[j - lds0] : P.recs[P.idx[j]].score;
-                if (sj < sc || (sj == sc && rj < rel)) {
-                    kept = false;
-                    break;
-                }
-            }
-            // to the right: only a strictly smaller score is better
-            for (long long j = i + 1; kept && j < n; ++j) {
-                const bool in_lds = j < lds_end;
-                const unsigned long long kj = in_lds ? s_key[j - lds0] : P.keys[j];
-                if (sel_pattern(P, kj) != pat)
-                    break;
-                const unsigned long long rj = kj & P.pos_mask;
-                if (rj - rel > w)
-                    break;
-                const unsigned long long pj = rj + P.seg_bias;
-                if (pj < p_lo || pj > p_hi)
-                    break;
-                const int32_t sj = in_lds ? s_score[j - lds0] : P.recs[P.idx[j]].score;
-                if (sj < sc)
-                    kept = false;
-            }
+            kept = sel_walk_keeps(
+                s_key, s_score, P.keys, T, i, pat, rel, sc, P.pos_mask, w, [&](unsigned long long k) { return sel_pattern(P, k); },
+                score_of, [&](unsigned long long rj) { return rj + P.seg_bias >= p_lo && rj + P.seg_bias <= p_hi; });
         }
         P.keep[i] = kept ? 1 : 0;
     }
-    // records LOCI kept: one atomic per wave
-    const unsigned long long kept_mask = __ballot(kept);
-    if ((threadIdx.x & 63) == 0 && kept_mask)
-        atomicAdd(&P.counts[0], (unsigned long long)__popcll(kept_mask));
-    // per-pattern minima: lanes of one pattern are contiguous (sorted input), so a segmented min-scan over the wave leaves
-    // the minimum of every run in its last lane, which issues the one atomicMin of that wave and pattern
+    sel_count_kept(kept, &P.counts[0]);
+    // per-pattern minima: the last lane of every run issues the one atomicMin of that wave and pattern
     if (P.best) {
-        const uint32_t lane = threadIdx.x & 63;
-        int32_t m = sc;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int32_t m2 = __shfl_up(m, d);
-            const uint32_t p2 = __shfl_up(pat, d);
-            if (lane >= (uint32_t)d && p2 == pat)
-                m = m2 < m ? m2 : m;
-        }
-        const uint32_t p_next = __shfl_down(pat, 1);
-        if (valid && (lane == 63 || p_next != pat || i + 1 >= n))
-            atomicMin(&P.pat_min[pat], m);
+        bool run_ends;
+        const int32_t m = sel_run_min(pat, sc, run_ends);
+        if (valid && (run_ends || i + 1 >= T.n))
+            atomicMin(&P.minima[pat], m);
     }
 }
 
-// what the exclusive scan adds up and the compaction tests again: LOCI's verdict and the stratum test
-__device__ __forceinline__ uint32_t sel_final_flag(const select_params &P, uint32_t i)
+// the final flag of sorted record i: the minimum it is measured against is its pattern's
+__device__ __forceinline__ uint32_t sel_final(const select_params &P, uint32_t i)
 {
-    uint32_t f = P.keep[i];
-    if (f && P.best)
-        f = (long long)P.score[i] <= (long long)P.pat_min[sel_pattern(P, P.keys[i])] + P.strata ? 1u : 0u;
-    return f;
+    return sel_final_flag(P, i, [&](uint32_t r) { return sel_pattern(P, P.keys[r]); });
 }
-struct sel_flag_op
-{
-    select_params P;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return sel_final_flag(P, i); }
-};
 
 // offs: exclusive scan of the final flags.  A kept record travels as one 16-byte load and one 16-byte store.
 __global__ __launch_bounds__(256) void select_compact_kernel(const select_params P, const uint32_t *__restrict__ offs,
@@ -219,7 +160,7 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const select_params
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= P.n)
         return;
-    const uint32_t f = sel_final_flag(P, i);
+    const uint32_t f = sel_final(P, i);
     const uint32_t o = offs[i];
     if (f)
         reinterpret_cast<uint4 *>(out)[o] = reinterpret_cast<const uint4 *>(P.recs)[P.idx[i]];

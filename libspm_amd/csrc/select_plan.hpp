@@ -1,7 +1,8 @@
 // select_plan.hpp -- what one hit selection (spm_hip_hits_select / spm_hip_records_select) decides on the host, as pure
 // functions (plain C++17, no HIP: select.hip and tests/cpp/select_plan_cases.cpp both compile it): the window a needle
 // gets, the bit budget of the sort key, the halo the selection kernel stages in LDS, and the two refusals that are made
-// before anything is launched.  select.hip keeps the HIP calls and acts on the answers.
+// before anything is launched.  select.hip keeps the HIP calls and acts on the answers.  Also here: plan_jst_select for
+// pan-genome selections (front and back shared with plan_select) and plan_jst_locate for spm_hip_jst_selection_align's sort.
 #pragma once
 
 #include <algorithm>
@@ -51,36 +52,38 @@ struct select_plan
     bool loci = false, best = false;
 };
 
-// n_records: records to select from; n_patterns: patterns the records can name (>= 1); max_rel_pos: the largest
-// pos - bias a record can hold; myers_set / have_k / max_k: the needle set (have_k false: no set was given).
-inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uint64_t n_patterns, uint64_t max_rel_pos,
-                               bool have_k, bool myers_set, uint32_t max_k)
+// a refusal: status and why are set, and nothing else of P means anything
+template <class Plan> bool plan_refuse(Plan &P, int status, const char *why)
 {
-    select_plan P;
-    if ((o.flags & ~(SPM_SELECT_LOCI | SPM_SELECT_BEST)) || o.reserved) {
-        P.status = SPM_E_INVALID;
-        P.why = "unknown flag bits, or a nonzero reserved field";
-        return P;
-    }
+    P.status = status;
+    P.why = why;
+    return false;
+}
+
+// The front that every selection plan shares: the flag bits (`allowed`: the flags this kind of selection takes), what
+// the flags need, and the record count.  False: refused.
+template <class Plan> bool plan_select_front(Plan &P, const spm_select_opts &o, uint32_t allowed, uint64_t n_records, bool have_k)
+{
+    if ((o.flags & ~allowed) || o.reserved)
+        return plan_refuse(P, SPM_E_INVALID, "unknown flag bits, or a nonzero reserved field");
     P.loci = (o.flags & SPM_SELECT_LOCI) != 0;
     P.best = (o.flags & SPM_SELECT_BEST) != 0;
-    if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k) {
-        P.status = SPM_E_INVALID;
-        P.why = "SPM_SELECT_WINDOW_K needs the needle set";
-        return P;
-    }
-    if (n_records > 0xFFFFFFFFull) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "more than 2^32 - 1 records";
-        return P;
-    }
-    P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
-    P.pos_bits = bits_for(max_rel_pos);
-    P.key_bits = P.pat_bits + P.pos_bits;
+    if ((o.flags & SPM_SELECT_ACROSS) && !P.best)
+        return plan_refuse(P, SPM_E_INVALID, "SPM_SELECT_ACROSS needs SPM_SELECT_BEST");
+    if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k)
+        return plan_refuse(P, SPM_E_INVALID, "SPM_SELECT_WINDOW_K needs the needle set");
+    if (n_records > 0xFFFFFFFFull)
+        return plan_refuse(P, SPM_E_UNSUPPORTED, "more than 2^32 - 1 records");
+    return true;
+}
+
+// ... and the back, once the key's fields are sized: above 64 bits refused with `too_wide`; the window(s) and the halo
+template <class Plan>
+void plan_select_back(Plan &P, const spm_select_opts &o, bool myers_set, uint32_t max_k, const char *too_wide)
+{
     if (P.key_bits > 64) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "pattern index and position do not fit one 64-bit sort key";
-        return P;
+        plan_refuse(P, SPM_E_UNSUPPORTED, too_wide);
+        return;
     }
     P.key_bits = std::max(P.key_bits, 1u);
     if (P.loci) {
@@ -89,6 +92,20 @@ inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uin
         P.max_window = select_window(o.window, myers_set, max_k);
     }
     P.halo = select_halo(P.max_window);
+}
+
+// n_records: records to select from; n_patterns: patterns the records can name (>= 1); max_rel_pos: the largest
+// pos - bias a record can hold; myers_set / have_k / max_k: the needle set (have_k false: no set was given).
+inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uint64_t n_patterns, uint64_t max_rel_pos,
+                               bool have_k, bool myers_set, uint32_t max_k)
+{
+    select_plan P;
+    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST, n_records, have_k))
+        return P;
+    P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
+    P.pos_bits = bits_for(max_rel_pos);
+    P.key_bits = P.pat_bits + P.pos_bits;
+    plan_select_back(P, o, myers_set, max_k, "pattern index and position do not fit one 64-bit sort key");
     return P;
 }
 
@@ -113,45 +130,14 @@ inline jst_select_plan plan_jst_select(const spm_select_opts &o, uint64_t n_reco
                                        uint64_t max_pos, bool have_k, bool myers_set, uint32_t max_k)
 {
     jst_select_plan P;
-    if ((o.flags & ~(SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_ACROSS)) || o.reserved) {
-        P.status = SPM_E_INVALID;
-        P.why = "unknown flag bits, or a nonzero reserved field";
+    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_ACROSS, n_records, have_k))
         return P;
-    }
-    P.loci = (o.flags & SPM_SELECT_LOCI) != 0;
-    P.best = (o.flags & SPM_SELECT_BEST) != 0;
     P.across = (o.flags & SPM_SELECT_ACROSS) != 0;
-    if (P.across && !P.best) {
-        P.status = SPM_E_INVALID;
-        P.why = "SPM_SELECT_ACROSS needs SPM_SELECT_BEST";
-        return P;
-    }
-    if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k) {
-        P.status = SPM_E_INVALID;
-        P.why = "SPM_SELECT_WINDOW_K needs the needle set";
-        return P;
-    }
-    if (n_records > 0xFFFFFFFFull) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "more than 2^32 - 1 records";
-        return P;
-    }
     P.hap_bits = bits_for(n_haplotypes ? n_haplotypes - 1 : 0);
     P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
     P.pos_bits = bits_for(max_pos);
     P.key_bits = P.hap_bits + P.pat_bits + P.pos_bits;
-    if (P.key_bits > 64) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "haplotype, pattern index and position do not fit one 64-bit sort key";
-        return P;
-    }
-    P.key_bits = std::max(P.key_bits, 1u);
-    if (P.loci) {
-        const bool per_needle = o.window == SPM_SELECT_WINDOW_K && myers_set && max_k > 0;
-        P.window = per_needle ? SPM_SELECT_WINDOW_K : select_window(o.window, myers_set, max_k);
-        P.max_window = select_window(o.window, myers_set, max_k);
-    }
-    P.halo = select_halo(P.max_window);
+    plan_select_back(P, o, myers_set, max_k, "haplotype, pattern index and position do not fit one 64-bit sort key");
     return P;
 }
 
@@ -171,13 +157,11 @@ inline jst_locate_plan plan_jst_locate(uint64_t n_records, uint64_t n_patterns, 
     P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
     P.ctx_bits = bits_for(ctx_symbols);
     if (n_records > 0xFFFFFFFFull) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "more than 2^32 - 1 records";
+        plan_refuse(P, SPM_E_UNSUPPORTED, "more than 2^32 - 1 records");
         return P;
     }
     if (P.pat_bits + P.ctx_bits > 64) {
-        P.status = SPM_E_UNSUPPORTED;
-        P.why = "pattern index and context position do not fit a 64-bit sort key";
+        plan_refuse(P, SPM_E_UNSUPPORTED, "pattern index and context position do not fit a 64-bit sort key");
         return P;
     }
     P.key_bits = std::max(1u, P.pat_bits + P.ctx_bits);

@@ -201,6 +201,91 @@ def test_hand_worked_lists_through_select_records(spm, ctx, case):
         sel.align()
 
 
+def _select_records(spm, ctx, a, w, **kw):
+    """a: records in arrival order -> (the selection, the device buffer it reads, to be kept alive by the caller)"""
+    buf = upload_records(a) if len(a) else None
+    sel = spm.select_records(ctx, buf.data_ptr() if buf is not None else 0, len(a), None, loci=kw.get("loci", True), window=w,
+                             best=kw.get("best"))
+    return sel, buf
+
+
+@gpu
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257])
+def test_record_counts_around_one_tile(spm, ctx, n):
+    """one pattern, n records: an empty list, one lane, one lane short of a tile, a full tile, one record in a second tile"""
+    rng = np.random.default_rng(n)
+    a = recs([(1, 2 * i + int(rng.integers(0, 2)), int(rng.integers(0, 4))) for i in range(n)])
+    srt = a.copy()
+    a = a[rng.permutation(n)]
+    for kw in (dict(best=0), dict(), dict(best=1, loci=False)):
+        sel, _buf = _select_records(spm, ctx, a, 3, **kw)
+        st = check(ctx, sel, rule(srt, 3, **kw))
+        assert st.n_in == n
+
+
+@gpu
+def test_one_pattern_of_700_walks_beyond_the_halo_on_both_sides(spm, ctx):
+    """700 consecutive positions of one pattern, scores falling to 0 at the middle and rising again: three tiles.  With
+    w = 200 and w = 33 the walks of the middle record find nothing better for w records on either side and leave the 32
+    staged records behind, across the tile borders at 256 and 512 for w = 200.  The two data sets after it make a walk FIND
+    its suppressor out there: to the left (isolated low records) and to the right (plateaus)."""
+    given = [(1, 1000 + i, abs(i - 350)) for i in range(700)] + [(0, 1000 + 3 * i, 5) for i in range(10)] + [(2, 1350, 7)]
+    srt = recs(given)
+    a = srt[np.random.default_rng(7).permutation(len(srt))]
+    for w in (200, 33):
+        sel, _buf = _select_records(spm, ctx, a, w)
+        want = rule(srt, w)
+        assert rows(want)[-2:] == [(1, 1350, 0), (2, 1350, 7)]
+        assert [r for r in rows(want) if r[0] == 1] == [(1, 1350, 0)]       # the descent on either side suppresses the rest
+        check(ctx, sel, want)
+    # ... the mirror image: a record whose suppressor lies to its LEFT, behind more than 32 worse records, in the tile
+    # before its own and outside that tile's halo (tile 1 stages sorted indices 224.., tile 2 480..): low records at 200 and
+    # 470, the contenders 60 places after them at 260 and 530, one more at 300 that loses to 260 inside the tile
+    score = {200: 0, 260: 3, 300: 5, 470: 1, 530: 4}
+    srt = recs([(1, 1000 + i, score.get(i, 9)) for i in range(700)])
+    a = srt[np.random.default_rng(9).permutation(len(srt))]
+    kept_at = {200: [200, 470], 60: [0, 200, 470], 59: [0, 200, 260, 470, 530], 33: [0, 200, 260, 300, 470, 530]}
+    for w, at in kept_at.items():
+        want = rule(srt, w)
+        assert rows(want) == [(1, 1000 + i, score.get(i, 9)) for i in at], w   # (record 0 loses only at w = 200, to record 200)
+        sel, _buf = _select_records(spm, ctx, a, w)
+        check(ctx, sel, want)
+    # ... and with plateaus of equal scores, where only the leftmost record of a plateau can survive
+    srt = recs([(1, 1000 + i, abs(i - 350) // 100) for i in range(700)] + [(0, 5, 0)])
+    a = srt[np.random.default_rng(8).permutation(len(srt))]
+    for w in (200, 33):
+        for kw in (dict(), dict(best=1)):
+            sel, _buf = _select_records(spm, ctx, a, w, **kw)
+            check(ctx, sel, rule(srt, w, **kw))
+
+
+@gpu
+def test_pattern_change_exactly_at_sorted_index_256(spm, ctx):
+    """two patterns whose boundary is the tile border, records within w of each other across it: no record is suppressed by
+    the other pattern's records, and each pattern's BEST minimum is its own"""
+    rng = np.random.default_rng(256)
+    first = [(6, 10 + i, int(rng.integers(1, 5))) for i in range(256)]
+    second = [(7, 260 + i, int(rng.integers(0, 5))) for i in range(120)]
+    second[40] = (7, 300, 0)
+    srt = recs(first + second)
+    assert rows(srt)[256] == second[0] and rows(srt)[255] == first[-1]
+    assert abs(second[0][1] - first[-1][1]) <= 5 and min(s for _, _, s in first) != min(s for _, _, s in second)
+    a = srt[rng.permutation(len(srt))]
+    for kw in (dict(), dict(best=0), dict(best=1, loci=False)):
+        sel, _buf = _select_records(spm, ctx, a, 5, **kw)
+        want = rule(srt, 5, **kw)
+        check(ctx, sel, want)
+    # the head of the second pattern would lose to the last record of the first, 5 positions on, if the two saw each other
+    first[-1] = (6, 265, 0)                                                 # the best of its window in pattern 6
+    second[:6] = [(7, 260, 3)] + [(7, 261 + i, 4) for i in range(5)]        # ... and the head the best of its own
+    srt = recs(first + second)
+    assert rows(srt)[255] == first[-1] and rows(srt)[256] == second[0]
+    sel, _buf = _select_records(spm, ctx, srt[rng.permutation(len(srt))], 5)
+    want = rule(srt, 5)
+    assert first[-1] in rows(want) and second[0] in rows(want)
+    check(ctx, sel, want)
+
+
 def plant(rng, n_text, specs, gap=None):
     """Uniform text with every needle of `specs` (length, k) planted three times with <= k random edits, the copies at
     least 4 (|P| + k) apart.  Returns text, needles, ks, planted [(needle, end of the planted copy)]."""
