@@ -27,6 +27,8 @@
 #include <string_view>
 #include <tuple>
 #include <unordered_map>
+#include <utility>
+#include <vector>
 
 #include <libspm/hip/context.hpp>
 #include <libspm/jst/io.hpp>
@@ -63,6 +65,18 @@ struct jst_ref_alignment
     spm::alignment aln;             // reference coordinates, errors = ref_score (X + I + D of the projected transcript)
     std::int32_t haplotype_errors;  // the distance on the haplotype, as locate reports it
     bool operator==(jst_ref_alignment const &) const noexcept = default;
+};
+
+// one distinct reference alignment of a needle (journaled_sequence_tree::locate_reference_loci): the alignments of
+// locate_reference that agree in needle, reference range and transcript, merged, with the haplotypes that support it
+struct jst_ref_locus
+{
+    std::uint32_t needle;
+    spm::alignment aln;             // reference coordinates, errors = ref_score
+    std::int32_t haplotype_errors;  // the smallest distance on any supporting haplotype
+    std::uint32_t records;          // alignments of locate_reference merged
+    std::vector<std::pair<std::uint32_t, std::int32_t>> members; // (haplotype, its smallest distance), ascending haplotype
+    bool operator==(jst_ref_locus const &) const noexcept = default;
 };
 
 struct jst_search_stats
@@ -546,6 +560,86 @@ public:
                             needle_ranks);
     }
 
+    // ---- one record per distinct reference alignment: locate_reference collapsed by the contract of
+    // spm_hip_jst_ref_alns_collapse in spm_hip.h -- loci in (needle, begin, end, errors, CIGAR length, CIGAR words) order.
+    // Device route: locate on the device, projection, collapse.  Trees the device path does not take, and the second opinion of
+    // the tests: locate_reference_host, sorted and folded on the host (collapse_host).  Both return the same vector.
+    std::vector<jst_ref_locus> locate_reference_loci(spm_patterns * needles, std::size_t window,
+                                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                                     std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_loci_device(needles, window, block, stats);
+        return locate_reference_loci_host(needles, window, needle_ranks, reports_begin, block, stats);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci(spm_patterns * needles, std::size_t window,
+                                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                                     hip::hit_selection const & selection, std::size_t block = 0,
+                                                     jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_loci_device(needles, window, selection, block, stats);
+        return locate_reference_loci_host(needles, window, needle_ranks, reports_begin, selection, block, stats);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_device(spm_patterns * needles, std::size_t window, std::size_t block = 0,
+                                                            jst_search_stats * stats = nullptr) const
+    {
+        return loci_of(device_alns(needles, window, block, stats).get());
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_device(spm_patterns * needles, std::size_t window,
+                                                            hip::hit_selection const & selection, std::size_t block = 0,
+                                                            jst_search_stats * stats = nullptr) const
+    {
+        return loci_of(device_alns(needles, window, selection, block, stats).get());
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_host(spm_patterns * needles, std::size_t window,
+                                                          std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                          bool reports_begin, std::size_t block = 0,
+                                                          jst_search_stats * stats = nullptr) const
+    {
+        return collapse_host(locate_reference_host(needles, window, needle_ranks, reports_begin, block, stats));
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_host(spm_patterns * needles, std::size_t window,
+                                                          std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                          bool reports_begin, hip::hit_selection const & selection,
+                                                          std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return collapse_host(locate_reference_host(needles, window, needle_ranks, reports_begin, selection, block, stats));
+    }
+
+    // The collapse on the host: sort by content, fold equal neighbours, then sort and fold the members of every locus.
+    static std::vector<jst_ref_locus> collapse_host(std::vector<jst_ref_alignment> alns)
+    {
+        auto key = [](jst_ref_alignment const & x) {
+            return std::tuple{x.needle, x.aln.begin_position(), x.aln.end_position(), x.aln.errors(), x.aln.cigar().size()};
+        };
+        auto less = [&](jst_ref_alignment const & a, jst_ref_alignment const & b) {
+            return key(a) != key(b) ? key(a) < key(b) : a.aln.cigar() < b.aln.cigar(); // (equal sizes: word by word)
+        };
+        std::sort(alns.begin(), alns.end(), less);
+        std::vector<jst_ref_locus> out;
+        for (jst_ref_alignment const & x : alns) {
+            if (out.empty() || out.back().needle != x.needle || !(out.back().aln == x.aln))
+                out.push_back({x.needle, x.aln, x.haplotype_errors, 0u, {}});
+            jst_ref_locus & l = out.back();
+            l.haplotype_errors = std::min(l.haplotype_errors, x.haplotype_errors);
+            ++l.records;
+            l.members.emplace_back(x.haplotype, x.haplotype_errors);
+        }
+        for (jst_ref_locus & l : out) {
+            std::sort(l.members.begin(), l.members.end()); // (haplotype, errors): the smallest distance of a haplotype comes first
+            l.members.erase(std::unique(l.members.begin(), l.members.end(),
+                                        [](auto const & a, auto const & b) { return a.first == b.first; }),
+                            l.members.end());
+        }
+        return out;
+    }
+
     // The projection on the host.  Haplotype position x is looked up in the event table of its haplotype: inside the alt of
     // allele (p, rend, alt) at offset k it is paired with p + k while k < rend - p and inserted with anchor p + min(rend - p,
     // |alt|) beyond; in a reference run it is paired with x minus the shift of the alleles before it.
@@ -745,6 +839,39 @@ private:
                            alignment{static_cast<std::size_t>(rec[i].ref_begin), static_cast<std::size_t>(rec[i].ref_end),
                                      rec[i].ref_score, ops + rec[i].cigar_off, rec[i].cigar_len},
                            rec[i].score});
+        return out;
+    }
+
+    // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
+    static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a)
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_ref_alns * r = nullptr;
+        if (spm_hip_jst_alns_project(a, 0, &r) != SPM_OK)
+            hip::fatal("spm_hip_jst_alns_project", ctx);
+        spm_jst_ref_loci * l = nullptr;
+        int const rc = spm_hip_jst_ref_alns_collapse(r, 0, &l);
+        spm_hip_jst_ref_alns_destroy(r); // (the loci stay valid without their source)
+        if (rc != SPM_OK)
+            hip::fatal("spm_hip_jst_ref_alns_collapse", ctx);
+        std::unique_ptr<spm_jst_ref_loci, decltype(&spm_hip_jst_ref_loci_destroy)> owner{l, &spm_hip_jst_ref_loci_destroy};
+        spm_jst_ref_locus const * rec = nullptr;
+        std::uint32_t const *ops = nullptr, *members = nullptr;
+        std::int32_t const * scores = nullptr;
+        std::uint64_t n = 0, n_ops = 0, n_members = 0;
+        if (spm_hip_jst_ref_loci_view(l, &rec, &n, &ops, &n_ops, &members, &scores, &n_members) != SPM_OK)
+            hip::fatal("spm_hip_jst_ref_loci_view", ctx);
+        std::vector<jst_ref_locus> out;
+        out.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i) {
+            jst_ref_locus x{rec[i].pattern,
+                            alignment{static_cast<std::size_t>(rec[i].ref_begin), static_cast<std::size_t>(rec[i].ref_end),
+                                      rec[i].ref_score, ops + rec[i].cigar_off, rec[i].cigar_len},
+                            rec[i].score, rec[i].n_records, {}};
+            for (std::uint32_t m = 0; m < rec[i].n_haplotypes; ++m)
+                x.members.emplace_back(members[rec[i].member_off + m], scores[rec[i].member_off + m]);
+            out.push_back(std::move(x));
+        }
         return out;
     }
 

@@ -600,6 +600,93 @@ int spm_hip_jst_ref_alns_device(spm_jst_ref_alns *a, const void **records, uint6
 int spm_hip_jst_ref_alns_stats(const spm_jst_ref_alns *a, spm_jst_project_stats *out);
 void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a);
 
+/* ---- projected alignments collapsed to one record per locus: what a mapper prints ---------------------------------------
+ * spm_hip_jst_alns_project returns one record per (haplotype, needle) hit: a read that maps to one place of the reference
+ * comes back once per haplotype.  This call merges the records that say the same thing about the reference and keeps, per
+ * merged record, the haplotypes that support it and their haplotype distances.
+ *
+ * Locus.  Two source records belong to the same locus iff they have equal pattern, ref_begin and ref_end and equal projected
+ * transcripts: the same cigar_len and the same words.  (ref_score is a function of the words.)  Haplotype, haplotype distance
+ * and slot do not enter: haplotypes whose contexts differ by an allele elsewhere in the block have distinct slots and may
+ * have identical projections, so the question is one about CONTENT and is decided by comparing the words.
+ * Order of the loci, in the host view and in the device view alike: ascending (pattern, ref_begin, ref_end, ref_score,
+ * cigar_len), then the transcripts compared word by word as uint32.  The order is total on loci and reads only content.
+ * Record.  score is the smallest haplotype distance among the source records of the locus, n_records their number.  The ops
+ * pool holds exactly one transcript per locus, in locus order: cigar_off is the exclusive prefix sum of cigar_len.
+ * Members.  Two parallel pools, haplotype (uint32) and score (int32).  members[member_off .. member_off + n_haplotypes) are
+ * the DISTINCT haplotypes among the source records of the locus, ascending, each with the smallest score it has in that
+ * locus.  member_off is the exclusive prefix sum of n_haplotypes.
+ * Map.  locus_of[i] is the locus of source record i: the host map belongs to spm_hip_jst_ref_alns_view of the source, the
+ * device map to spm_hip_jst_ref_alns_device of the source (the two views of a projection may differ in order).
+ * The result is a function of the SET of source records only: records, the three pools and the host map are byte-identical
+ * across engines, block lengths, arrival orders and runs.
+ *
+ * Worked cases.
+ *  1. Same range, different transcripts.  ref = GATTCGCAAAAGTCCATG, one allele deletes the A at position 10; haplotype 0
+ *     carries it, haplotype 1 does not.  Needle TTCGCAAAGTCCA, k = 1.  Haplotype 0: distance 0, projected 8=1D5=, [2,16),
+ *     NM 1.  Haplotype 1: distance 1, projected 5=1D8=, [2,16), NM 1.  TWO loci, in this order (the word 5= is smaller than
+ *     8=).  Left-normalisation of indels would merge them; it is not part of this call.
+ *  2. One haplotype twice.  ref = GATTCGCATGTCCATG, one allele inserts G at position 8, carried by haplotype 0.  Needle
+ *     ATTCGCA, k = 1.  The hit ending at 8 is 7= with distance 0; the hit ending at 9 is 7=1D with distance 1, and its D
+ *     falls on the inserted symbol and projects to nothing.  Both records project to 7=, [1,8): ONE locus, n_records 2,
+ *     n_haplotypes 1, member score 0.
+ *  3. One member score per haplotype.  A read cut across a carried SNP: the carrier has distance 0, a non-carrier distance 1,
+ *     both project to the same ...1X...: one locus, score 0, members (carrier, 0), (other, 1).
+ *  4. Inside an insertion.  Alignments wholly inside one inserted stretch (ref_begin == ref_end, transcript |P| I) say nothing
+ *     about WHERE in the stretch they lie: they merge whenever pattern and anchor agree.
+ *
+ *   * Accepted: any result of spm_hip_jst_alns_project (of a search's alignments or of a selection's; Myers and exact sets).
+ *     The call reads only the projected records and their pool: tree and needle set need NOT be alive.  The result stays
+ *     valid after the source is destroyed.
+ *   * SPM_E_INVALID with a message: unknown flag bits, NULL arguments.
+ *   * SPM_E_UNSUPPORTED, decided on the host before any launch: bits(n_patterns - 1) + bits(reference length) above 64.
+ *   * A record whose transcript lies outside the source pool, or that disagrees with the record that represents its slot,
+ *     fails the whole call with SPM_E_INVALID; the detection is a device counter, never a fault: every table index is tested
+ *     against the table's size before it is read.
+ *   * No records: an empty result and SPM_OK.
+ * flags: must be 0 */
+typedef struct spm_jst_ref_locus {  /* 48 bytes */
+    uint64_t ref_begin;             /* reference coordinates; inside an insertion: the anchor */
+    uint64_t ref_end;
+    uint32_t pattern;
+    int32_t ref_score;              /* X + I + D symbols of the transcript (SAM NM) */
+    int32_t score;                  /* the smallest haplotype distance among the source records */
+    uint32_t n_records;             /* source records merged */
+    uint32_t cigar_off;             /* first word of the transcript in the ops pool of this result */
+    uint32_t cigar_len;
+    uint32_t member_off;            /* first member in the two member pools */
+    uint32_t n_haplotypes;          /* distinct haplotypes among the source records */
+} spm_jst_ref_locus;
+typedef struct spm_jst_ref_loci spm_jst_ref_loci;
+
+typedef struct spm_jst_collapse_stats { /* 80 bytes */
+    float ms_total;            /* device: the four stages below (HIP events) */
+    float ms_slots;            /* one representative record per distinct source slot */
+    float ms_order;            /* slots sorted by (pattern, ref_begin), the rule inside every group, the locus of every slot */
+    float ms_records;          /* records sorted by (locus, haplotype), the member heads */
+    float ms_emit;             /* loci, transcripts, members */
+    float ms_host;             /* wall clock of the whole call, host view included */
+    uint64_t n_alns;           /* source records */
+    uint64_t n_slots;          /* distinct source slots */
+    uint64_t n_loci;
+    uint64_t n_members;
+    uint64_t n_ops;            /* words in the pool of this result */
+    uint64_t n_multi_slot;     /* loci that merge more than one slot */
+    uint64_t max_run;          /* longest run of slots with equal (pattern, ref_begin, ref_end, ref_score, cigar_len): the
+                                  comparison of words is quadratic in it */
+} spm_jst_collapse_stats;
+
+int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags, spm_jst_ref_loci **out);
+/* every pointer but records and n may be NULL */
+int spm_hip_jst_ref_loci_view(spm_jst_ref_loci *l, const spm_jst_ref_locus **records, uint64_t *n, const uint32_t **ops,
+                              uint64_t *n_ops, const uint32_t **members, const int32_t **member_scores, uint64_t *n_members);
+int spm_hip_jst_ref_loci_device(spm_jst_ref_loci *l, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops,
+                                const void **members, const void **member_scores, uint64_t *n_members);
+/* locus_of: n_alns uint32 each; host_map or device_map may be NULL */
+int spm_hip_jst_ref_loci_map(spm_jst_ref_loci *l, const uint32_t **host_map, const void **device_map, uint64_t *n_alns);
+int spm_hip_jst_ref_loci_stats(const spm_jst_ref_loci *l, spm_jst_collapse_stats *out);
+void spm_hip_jst_ref_loci_destroy(spm_jst_ref_loci *l);
+
 /* ---- selection of pan-genome hits: one record per haplotype locus, the best stratum per (haplotype, needle) -------------
  * spm_hip_hits_select for the 24-byte records of spm_hip_jst_search.  The locus is (haplotype, pattern).  For a record
  * r = (haplotype, pos, pattern, score):

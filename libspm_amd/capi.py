@@ -173,6 +173,30 @@ class JstProjectStats(C.Structure):
     ]
 
 
+class JstRefLocus(C.Structure):
+    _fields_ = [("ref_begin", C.c_uint64), ("ref_end", C.c_uint64), ("pattern", C.c_uint32), ("ref_score", C.c_int32),
+                ("score", C.c_int32), ("n_records", C.c_uint32), ("cigar_off", C.c_uint32), ("cigar_len", C.c_uint32),
+                ("member_off", C.c_uint32), ("n_haplotypes", C.c_uint32)]
+
+
+class JstCollapseStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_slots", C.c_float),
+        ("ms_order", C.c_float),
+        ("ms_records", C.c_float),
+        ("ms_emit", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_alns", C.c_uint64),
+        ("n_slots", C.c_uint64),
+        ("n_loci", C.c_uint64),
+        ("n_members", C.c_uint64),
+        ("n_ops", C.c_uint64),
+        ("n_multi_slot", C.c_uint64),
+        ("max_run", C.c_uint64),
+    ]
+
+
 ALIGN_BEGIN_ONLY = 1
 
 
@@ -300,6 +324,15 @@ def lib():
                                                   C.POINTER(C.c_uint64)]),
         "spm_hip_jst_ref_alns_stats": (C.c_int, [vp, C.POINTER(JstProjectStats)]),
         "spm_hip_jst_ref_alns_destroy": (None, [vp]),
+        "spm_hip_jst_ref_alns_collapse": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_ref_loci_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRefLocus)), C.POINTER(C.c_uint64), C.POINTER(u32p),
+                                                C.POINTER(C.c_uint64), C.POINTER(u32p), C.POINTER(C.POINTER(C.c_int32)),
+                                                C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_ref_loci_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
+                                                  C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_ref_loci_map": (C.c_int, [vp, C.POINTER(u32p), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_ref_loci_stats": (C.c_int, [vp, C.POINTER(JstCollapseStats)]),
+        "spm_hip_jst_ref_loci_destroy": (None, [vp]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -342,6 +375,8 @@ EXPORTS = [
     "spm_hip_jst_alns_destroy",
     "spm_hip_jst_alns_project", "spm_hip_jst_ref_alns_view", "spm_hip_jst_ref_alns_device", "spm_hip_jst_ref_alns_stats",
     "spm_hip_jst_ref_alns_destroy",
+    "spm_hip_jst_ref_alns_collapse", "spm_hip_jst_ref_loci_view", "spm_hip_jst_ref_loci_device", "spm_hip_jst_ref_loci_map",
+    "spm_hip_jst_ref_loci_stats", "spm_hip_jst_ref_loci_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

@@ -5,3 +5,4 @@
 #include "jst.hpp"
 #include "jst_locate.hpp"
 #include "jst_project.hpp"
+#include "jst_collapse.hpp"

@@ -245,6 +245,8 @@ struct spm_jst_ref_alns
     std::vector<spm_jst_ref_aln> host; // record i belongs to record i of the source's host view
     std::vector<uint32_t> host_ops;
     spm_jst_project_stats stats{};
+    uint32_t n_patterns = 0; // what spm_hip_jst_ref_alns_collapse plans its keys from: the needles of the set ...
+    uint64_t n_ref = 0;      // ... and the reference length (the collapse reads neither tree nor set)
 };
 
 extern "C" void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a)
@@ -295,6 +297,8 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
     R->ctx = ctx;
     R->n = n;
     R->stats.n_alns = n;
+    R->n_patterns = ps->n;
+    R->n_ref = J->ref->n;
     hipStream_t st = ctx->stream;
     float ms_rep = 0, ms_count = 0, ms_emit = 0, ms_gather = 0;
     uint64_t n_slots = 0;

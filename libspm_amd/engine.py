@@ -402,6 +402,9 @@ JST_ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4")
                           ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("reserved", "<u4")])
 JST_REF_ALN_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"),
                               ("score", "<i4"), ("ref_score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4")])
+JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
+                                ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
+                                ("member_off", "<u4"), ("n_haplotypes", "<u4")])
 
 
 def synth_variants(seed_text: int, seed_var: int, ref_begin: int, n_ref: int, n_haplotypes: int):
@@ -717,10 +720,116 @@ class JstRefAlignments:
         _check(capi.lib().spm_hip_jst_ref_alns_stats(self._h, C.byref(s)), self.ctx._h)
         return s
 
+    def collapse(self) -> "JstRefLoci":
+        """One record per distinct reference alignment (spm_hip_jst_ref_alns_collapse): records that agree in needle,
+        reference range and transcript are merged; the result carries the haplotypes that support each locus and their
+        haplotype distances.  Reads only these records and their pool: tree and needle set may be closed, and the result
+        stays valid after this object is closed."""
+        r = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_ref_alns_collapse(self._h, 0, C.byref(r)), self.ctx._h)
+        return JstRefLoci(self.ctx, r)
+
     def close(self):
         if self._h:
             if self.ctx._h:
                 capi.lib().spm_hip_jst_ref_alns_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _as_array(ptr, n, ctype, dtype):
+    if n == 0:
+        return np.zeros(0, dtype=dtype)
+    buf = (ctype * n).from_address(C.addressof(ptr.contents))
+    return np.frombuffer(buf, dtype=dtype).copy()
+
+
+class JstRefLoci:
+    """Result of JstRefAlignments.collapse(): JST_REF_LOCUS_DTYPE records in (pattern, ref_begin, ref_end, ref_score,
+    cigar_len, transcript words) order, one transcript per locus in `ops`, and per locus the distinct haplotypes that
+    support it (`members`, ascending) with the smallest haplotype distance each has there (`member_scores`)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def _raw(self):
+        rec = C.POINTER(capi.JstRefLocus)()
+        ops, mem = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        msc = C.POINTER(C.c_int32)()
+        n, n_ops, n_mem = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_ref_loci_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops),
+                                                    C.byref(mem), C.byref(msc), C.byref(n_mem)), self.ctx._h)
+        return rec, n.value, ops, n_ops.value, mem, msc, n_mem.value
+
+    def __len__(self):
+        return self._raw()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n = self._raw()[:2]
+        return _as_array(rec, n, capi.JstRefLocus, JST_REF_LOCUS_DTYPE)
+
+    @property
+    def ops(self) -> np.ndarray:
+        r = self._raw()
+        return _as_array(r[2], r[3], C.c_uint32, np.uint32)
+
+    @property
+    def members(self) -> np.ndarray:
+        r = self._raw()
+        return _as_array(r[4], r[6], C.c_uint32, np.uint32)
+
+    @property
+    def member_scores(self) -> np.ndarray:
+        r = self._raw()
+        return _as_array(r[5], r[6], C.c_int32, np.int32)
+
+    @property
+    def locus_of(self) -> np.ndarray:
+        """locus_of[i]: the locus of record i of the source's view()"""
+        m = C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        _check(capi.lib().spm_hip_jst_ref_loci_map(self._h, C.byref(m), None, C.byref(n)), self.ctx._h)
+        return _as_array(m, n.value, C.c_uint32, np.uint32)
+
+    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
+        """SAM string of locus i (records / ops: views already fetched, to save the copies)."""
+        r = (self.view() if records is None else records)[i]
+        o = self.ops if ops is None else ops
+        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
+        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+
+    def haplotypes(self, i: int, records: np.ndarray | None = None):
+        """(haplotypes, scores) of locus i"""
+        r = (self.view() if records is None else records)[i]
+        lo, hi = int(r["member_off"]), int(r["member_off"]) + int(r["n_haplotypes"])
+        return self.members[lo:hi], self.member_scores[lo:hi]
+
+    def device(self):
+        """dict of device pointers and counts: records, n, ops, n_ops, members, member_scores, n_members, and locus_of
+        (matched to the source's device() records) with n_alns."""
+        r, o, m, s, mp = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n, n_ops, n_mem, n_alns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_ref_loci_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops), C.byref(m),
+                                                      C.byref(s), C.byref(n_mem)), self.ctx._h)
+        _check(capi.lib().spm_hip_jst_ref_loci_map(self._h, None, C.byref(mp), C.byref(n_alns)), self.ctx._h)
+        return {"records": int(r.value or 0), "n": int(n.value), "ops": int(o.value or 0), "n_ops": int(n_ops.value),
+                "members": int(m.value or 0), "member_scores": int(s.value or 0), "n_members": int(n_mem.value),
+                "locus_of": int(mp.value or 0), "n_alns": int(n_alns.value)}
+
+    def stats(self) -> capi.JstCollapseStats:
+        s = capi.JstCollapseStats()
+        _check(capi.lib().spm_hip_jst_ref_loci_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_jst_ref_loci_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
