@@ -445,28 +445,16 @@ extern "C" int spm_hip_hits_align(spm_hits *h, uint32_t flags, spm_alns **out)
 
 extern "C" int spm_hip_alns_view(spm_alns *a, const spm_aln **records, uint64_t *n, const uint32_t **ops, uint64_t *n_ops)
 {
-    if (!a || !records || !n)
+    if (!a)
         return SPM_E_INVALID;
-    *records = a->host.data();
-    *n = a->n;
-    if (ops)
-        *ops = a->host_ops.data();
-    if (n_ops)
-        *n_ops = a->n_ops;
-    return SPM_OK;
+    return pool_out(pool_src<spm_aln>{a->host.data(), a->n, a->host_ops.data(), a->n_ops}, records, n, ops, n_ops);
 }
 
 extern "C" int spm_hip_alns_device(spm_alns *a, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops)
 {
-    if (!a || !records || !n)
+    if (!a)
         return SPM_E_INVALID;
-    *records = a->d_recs;
-    *n = a->n;
-    if (ops)
-        *ops = a->d_ops;
-    if (n_ops)
-        *n_ops = a->n_ops;
-    return SPM_OK;
+    return pool_out(pool_src<void, void, void>{a->d_recs, a->n, a->d_ops, a->n_ops}, records, n, ops, n_ops);
 }
 
 extern "C" int spm_hip_alns_stats(const spm_alns *a, spm_align_stats *out)

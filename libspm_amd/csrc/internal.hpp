@@ -181,6 +181,40 @@ int align_run(spm_ctx *ctx, const align_work &W, spm_align_stats &stats);
 // builds, once per set, the alignment tables of spm_patterns (d_al_*): the projection reads the needle ranks among them
 int spm_align_tables(const spm_patterns *ps);
 
+// ---- the out-parameters of a "records + CIGAR pool" result: what the _view (host pointers) and _device (R = W = S = void)
+// entry points of spm_alns, spm_jst_alns, spm_jst_ref_alns and spm_jst_ref_loci hand out.  records and n are required;
+// every other out-parameter is filled where the caller asked for it. ----
+template <class R, class W = uint32_t, class S = int32_t> struct pool_src
+{
+    const R *recs;
+    uint64_t n;
+    const W *ops;
+    uint64_t n_ops;
+    const W *members = nullptr; // loci only: the haplotypes that support each locus ...
+    const S *member_scores = nullptr; // ... and their distances
+    uint64_t n_members = 0;
+};
+template <class R, class W, class S>
+int pool_out(const pool_src<R, W, S> &src, const R **records, uint64_t *n, const W **ops, uint64_t *n_ops,
+             const W **members = nullptr, const S **member_scores = nullptr, uint64_t *n_members = nullptr)
+{
+    if (!records || !n)
+        return SPM_E_INVALID;
+    *records = src.recs;
+    *n = src.n;
+    if (ops)
+        *ops = src.ops;
+    if (n_ops)
+        *n_ops = src.n_ops;
+    if (members)
+        *members = src.members;
+    if (member_scores)
+        *member_scores = src.member_scores;
+    if (n_members)
+        *n_members = src.n_members;
+    return SPM_OK;
+}
+
 // Every translation unit with kernels is a code object of its own, loaded by the HIP runtime at the first launch out of
 // it (~1-3 ms each).  spm_hip_init loads them all, so that the first scan of a process does not pay for it.
 void spm_warm_text_kernels();

@@ -4,5 +4,6 @@
 #include "synth.hpp"
 #include "jst.hpp"
 #include "jst_locate.hpp"
+#include "transcript_slots.hpp"
 #include "jst_project.hpp"
 #include "jst_collapse.hpp"

@@ -4,9 +4,8 @@
 //
 // Records that share a projected slot share their content, so the content is compared once per distinct slot of the source
 // pool, and the records are ordered afterwards:
-//   jst_col_rep_kernel      one lane per record: atomicMin of the record index into rep[cigar_off]
-//   (hipcub exclusive sum of rep[w] != none over the source pool: the number of every slot, in pool order)
-//   jst_col_compact_kernel  one lane per pool word: slot number -> representative record; the last lane writes the count
+//   (the slot stage of transcript_slots.hpp: a representative record and a number for every distinct slot, in pool order --
+//   the numbering the projection gave these records' slots)
 //   jst_col_key_kernel      one lane per slot: pattern << ref_bits | ref_begin (slots past the count: all ones; the sort is
 //                           stable, so they stay behind the real ones)
 //   (radix sort of the slots by that key: a GROUP is the slots of one (pattern, ref_begin))
@@ -35,8 +34,8 @@ static_assert(sizeof(spm_jst_ref_locus) == 48 && sizeof(spm_jst_collapse_stats) 
 namespace spm_hip
 {
 
-constexpr uint32_t kColNone = 0xFFFFFFFFu;
 enum { kColCntSlots = 0, kColCntBad, kColCntLoci, kColCntMembers, kColCntWords, kColCntMulti, kColCntMaxRun, kColCnts };
+static_assert(kColCntSlots == kSlotCntSlots && kColCntBad == kSlotCntBad, "the slot stage writes the first two counters");
 
 struct jst_collapse_params
 {
@@ -49,7 +48,7 @@ struct jst_collapse_params
     uint32_t ref_bits;
     uint32_t cap;                    // slots the per-slot tables hold: min(n, n_ops)
     uint32_t *rep;                   // [n_ops] smallest record index whose transcript starts at this word, or none
-    const uint32_t *sid;             // [n_ops] exclusive sum of rep != none: the slot's number
+    uint32_t *sid;                   // [n_ops] exclusive sum of rep != none: the slot's number
     uint32_t *slot_rec;              // [cap] representative record of slot s
     unsigned long long *key_in;      // [cap] the group key of slot s ...
     uint32_t *idx_in;                // [cap] ... and s
@@ -71,14 +70,24 @@ struct jst_collapse_params
     const uint32_t *msum;            // [n] exclusive sum of mhead
     uint32_t *map;                   // [n] locus of record i (a buffer of the result)
     unsigned long long *counts;      // kColCnt*
+    slot_tables slots() const { return slot_tables{rep, sid, slot_rec, n_ops, cap, counts}; } // (what the slot stage takes)
 };
 
-// what makes a record unusable: tested before any of its fields indexes a table
-__device__ __forceinline__ bool jcol_bad(const jst_collapse_params &P, const spm_jst_ref_aln &a)
+// what makes a record unusable: tested before any of its fields indexes a table.  P: the kernels' parameters, or the three
+// limits alone -- the predicate the slot stage takes
+template <class Limits> __device__ __forceinline__ bool jcol_bad(const Limits &P, const spm_jst_ref_aln &a)
 {
     return a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops || a.pattern >= P.n_patterns ||
            a.ref_begin > a.ref_end || a.ref_end > P.n_ref;
 }
+
+struct jcol_unusable
+{
+    uint64_t n_ops;
+    uint32_t n_patterns;
+    uint64_t n_ref;
+    __device__ __forceinline__ bool operator()(const spm_jst_ref_aln &a) const { return jcol_bad(*this, a); }
+};
 
 __device__ __forceinline__ jst_locus_key jcol_key(const spm_jst_ref_aln &a)
 {
@@ -98,53 +107,7 @@ __device__ __forceinline__ uint32_t jcol_n_slots(const jst_collapse_params &P)
 
 __device__ __forceinline__ void jcol_count_bad(const jst_collapse_params &P, bool bad)
 {
-    const unsigned long long mb = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && mb)
-        atomicAdd(&P.counts[kColCntBad], (unsigned long long)__popcll(mb));
-}
-
-__global__ __launch_bounds__(256) void jst_col_rep_kernel(const jst_collapse_params P)
-{
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    bool bad = false;
-    if (i < P.n) {
-        const spm_jst_ref_aln a = P.recs[i];
-        bad = jcol_bad(P, a);
-        if (!bad)
-            atomicMin(&P.rep[a.cigar_off], (uint32_t)i);
-    }
-    jcol_count_bad(P, bad);
-}
-
-struct jcol_flag_op
-{
-    const uint32_t *rep;
-    __device__ __forceinline__ uint32_t operator()(uint32_t w) const { return rep[w] != kColNone ? 1u : 0u; }
-};
-
-struct jcol_byte_op
-{
-    const uint8_t *v;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return v[i]; }
-};
-
-struct jcol_widen_op
-{
-    const uint32_t *v;
-    __device__ __forceinline__ unsigned long long operator()(uint32_t i) const { return v[i]; }
-};
-
-__global__ __launch_bounds__(256) void jst_col_compact_kernel(const jst_collapse_params P)
-{
-    const unsigned long long w = blockIdx.x * 256ull + threadIdx.x;
-    if (w >= P.n_ops)
-        return;
-    const uint32_t r = P.rep[w];
-    const uint32_t s = P.sid[w];
-    if (r != kColNone && s < P.cap)
-        P.slot_rec[s] = r;
-    if (w == P.n_ops - 1)
-        P.counts[kColCntSlots] = (unsigned long long)s + (r != kColNone ? 1ull : 0ull);
+    count_flagged(&P.counts[kColCntBad], bad);
 }
 
 __global__ __launch_bounds__(256) void jst_col_key_kernel(const jst_collapse_params P)
@@ -164,14 +127,14 @@ __global__ __launch_bounds__(256) void jst_col_key_kernel(const jst_collapse_par
     P.idx_in[s] = s;
 }
 
-// the sorted slots as jst_collapse_rank reads them; a slot is usable if its representative passed jst_col_rep_kernel
+// the sorted slots as jst_collapse_rank reads them; a slot is usable if its representative passed the slot stage
 struct jcol_view
 {
     const jst_collapse_params &P;
     __device__ __forceinline__ spm_jst_ref_aln rec(uint32_t j) const
     {
         const uint32_t s = P.idx[j];
-        const uint32_t r = s < P.cap ? P.slot_rec[s] : kColNone;
+        const uint32_t r = s < P.cap ? P.slot_rec[s] : kSlotNone;
         spm_jst_ref_aln a{};
         if (r < P.n)
             a = P.recs[r];
@@ -236,16 +199,16 @@ __global__ __launch_bounds__(256) void jst_col_reckey_kernel(const jst_collapse_
     bool bad = false;
     if (i < P.n) {
         const spm_jst_ref_aln a = P.recs[i];
-        uint32_t locus = kColNone;
+        uint32_t locus = kSlotNone;
         if (!jcol_bad(P, a)) {
             const uint32_t s = P.sid[a.cigar_off];
-            const uint32_t r = s < P.cap ? P.slot_rec[s] : kColNone;
+            const uint32_t r = s < P.cap ? P.slot_rec[s] : kSlotNone;
             // a record must say what the representative of its slot says: the content was compared through that one
             if (r < P.n && jst_collapse_cmp_tuple(jcol_key(P.recs[r]), jcol_key(a)) == 0 && P.recs[r].cigar_off == a.cigar_off)
                 locus = P.slot_locus[s];
         }
         bad = locus >= P.cap;
-        P.map[i] = bad ? kColNone : locus;
+        P.map[i] = bad ? kSlotNone : locus;
         P.rkey_in[i] = bad ? ~0ull : ((unsigned long long)locus << 32) | a.haplotype;
         P.ridx_in[i] = (uint32_t)i;
     }
@@ -414,11 +377,10 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         hip_events<6> ev;
         SPM_HIP_CHECK(ctx, ev.create());
         size_t b[5] = {};
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jcol_flag_op{nullptr}), n_src_ops, &b[0]));
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jcol_byte_op{nullptr}), std::max(n32, cap),
-                                                             &b[1]));
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(jcol_widen_op{nullptr}),
-                                                                       cap, &b[2]));
+        SPM_HIP_CHECK(ctx, slot_stage_tmp_bytes(ctx, n_src_ops, &b[0]));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(byte_op{nullptr}), std::max(n32, cap), &b[1]));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(widen_op{nullptr}), cap,
+                                                                       &b[2]));
         SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, cap, slot_key_bits, &b[3]));
         SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n32, rec_key_bits, &b[4]));
         const size_t tmp_bytes = *std::max_element(b, b + 5);
@@ -438,14 +400,13 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         P.recs = a->d_recs;
         P.n = n32;
         P.ops = a->d_ops;
-        P.n_ops = n_src_ops;
         P.n_patterns = a->n_patterns;
         P.n_ref = a->n_ref;
         P.ref_bits = plan.ref_bits;
+        P.n_ops = n_src_ops;
         P.cap = cap;
-        uint32_t *d_rep = P.rep = L.at<uint32_t>(base, o_rep);
-        uint32_t *d_sid = L.at<uint32_t>(base, o_sid);
-        P.sid = d_sid;
+        P.rep = L.at<uint32_t>(base, o_rep);
+        P.sid = L.at<uint32_t>(base, o_sid);
         P.slot_rec = L.at<uint32_t>(base, o_srec);
         P.key_in = L.at<unsigned long long>(base, o_key0);
         unsigned long long *d_key = L.at<unsigned long long>(base, o_key1);
@@ -475,17 +436,11 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         P.map = R->d_map;
         unsigned long long *d_counts = P.counts = L.at<unsigned long long>(base, o_counts);
         void *d_tmp = L.at<uint8_t>(base, o_tmp);
-        const unsigned g_rec = (unsigned)((n + 255) / 256), g_pool = (unsigned)((n_src_ops + 255) / 256),
-                       g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
+        const unsigned g_rec = (unsigned)((n + 255) / 256), g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- slots: one representative per distinct slot of the source pool, numbered in pool order ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kColCnts * 8, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_rep, 0xFF, n_src_ops * 4, st));
-        hipLaunchKernelGGL(jst_col_rep_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jcol_flag_op{d_rep}), d_sid, n_src_ops));
-        hipLaunchKernelGGL(jst_col_compact_kernel, dim3(g_pool), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), jcol_unusable{P.n_ops, P.n_patterns, P.n_ref}, d_tmp, tmp_bytes));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- order: groups of one (pattern, ref_begin), the rule inside a group, the locus of every slot ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.is_first, 0, cap, st));
@@ -496,10 +451,10 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, P.key_in, d_key, P.idx_in, d_idx, cap, slot_key_bits));
         hipLaunchKernelGGL(jst_col_walk_kernel, dim3(g_slot), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jcol_byte_op{P.is_first}), d_lsum, cap));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(byte_op{P.is_first}), d_lsum, cap));
         hipLaunchKernelGGL(jst_col_number_kernel, dim3(g_slot), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(jcol_widen_op{P.loc_len}), d_loff, cap));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{P.loc_len}), d_loff, cap));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         // ---- records: (locus, haplotype) order, the member heads ----
         hipLaunchKernelGGL(jst_col_reckey_kernel, dim3(g_rec), dim3(256), 0, st, P);
@@ -507,7 +462,7 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, P.rkey_in, d_rkey, P.ridx_in, d_ridx, n32, rec_key_bits));
         hipLaunchKernelGGL(jst_col_mhead_kernel, dim3(g_rec), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jcol_byte_op{P.mhead}), d_msum, n32));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(byte_op{P.mhead}), d_msum, n32));
         hipLaunchKernelGGL(jst_col_total_kernel, dim3(1), dim3(64), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
@@ -539,13 +494,14 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
         // ---- the host view: a plain download; the host map goes through the slot tables ----
-        std::vector<uint32_t> sid(n_src_ops), sloc(n_slots);
+        slot_host_map slot(n_src_ops);
+        std::vector<uint32_t> sloc(n_slots);
         R->host.resize(n_loci);
         R->host_ops.resize(total);
         R->host_members.resize(n_members);
         R->host_member_scores.resize(n_members);
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kColCnts * 8, hipMemcpyDeviceToHost, st));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(sid.data(), d_sid, n_src_ops * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, slot.download(ctx, P.slots()));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(sloc.data(), P.slot_locus, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d_loci, n_loci * sizeof(spm_jst_ref_locus), hipMemcpyDeviceToHost, st));
         if (total)
@@ -565,7 +521,7 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         R->host_map.resize(n);
         for (uint64_t i = 0; i < n; ++i) {
             const spm_jst_ref_aln &x = a->host[i];
-            const uint32_t s = x.cigar_off < n_src_ops ? sid[x.cigar_off] : kColNone;
+            const uint32_t s = slot.of(x.cigar_off);
             if (s >= n_slots || sloc[s] >= n_loci) {
                 SPM_SET_ERR(ctx, "spm_hip_jst_ref_alns_collapse: host record %llu names no locus", (unsigned long long)i);
                 return SPM_E_INVALID;
@@ -599,41 +555,21 @@ extern "C" int spm_hip_jst_ref_loci_view(spm_jst_ref_loci *l, const spm_jst_ref_
                                          uint64_t *n_ops, const uint32_t **members, const int32_t **member_scores,
                                          uint64_t *n_members)
 {
-    if (!l || !records || !n)
+    if (!l)
         return SPM_E_INVALID;
-    *records = l->host.data();
-    *n = l->n;
-    if (ops)
-        *ops = l->host_ops.data();
-    if (n_ops)
-        *n_ops = l->n_ops;
-    if (members)
-        *members = l->host_members.data();
-    if (member_scores)
-        *member_scores = l->host_member_scores.data();
-    if (n_members)
-        *n_members = l->n_members;
-    return SPM_OK;
+    return pool_out(pool_src<spm_jst_ref_locus>{l->host.data(), l->n, l->host_ops.data(), l->n_ops, l->host_members.data(),
+                                                l->host_member_scores.data(), l->n_members},
+                    records, n, ops, n_ops, members, member_scores, n_members);
 }
 
 extern "C" int spm_hip_jst_ref_loci_device(spm_jst_ref_loci *l, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops,
                                            const void **members, const void **member_scores, uint64_t *n_members)
 {
-    if (!l || !records || !n)
+    if (!l)
         return SPM_E_INVALID;
-    *records = l->d_loci;
-    *n = l->n;
-    if (ops)
-        *ops = l->d_ops;
-    if (n_ops)
-        *n_ops = l->n_ops;
-    if (members)
-        *members = l->d_members;
-    if (member_scores)
-        *member_scores = l->d_member_scores;
-    if (n_members)
-        *n_members = l->n_members;
-    return SPM_OK;
+    return pool_out(pool_src<void, void, void>{l->d_loci, l->n, l->d_ops, l->n_ops, l->d_members, l->d_member_scores,
+                                               l->n_members},
+                    records, n, ops, n_ops, members, member_scores, n_members);
 }
 
 extern "C" int spm_hip_jst_ref_loci_map(spm_jst_ref_loci *l, const uint32_t **host_map, const void **device_map, uint64_t *n_alns)

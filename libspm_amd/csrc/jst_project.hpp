@@ -1,19 +1,18 @@
 // jst_project.hpp -- pan-genome alignments in reference coordinates (spm_hip_jst_alns_project; contract in spm_hip.h, scheme
-// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp: it needs spm_jst, spm_jst_alns and jst_first_ref.
+// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp (it needs spm_jst, spm_jst_alns and jst_first_ref)
+// and transcript_slots.hpp (the slot stage it begins with).
 //
 // Records that share a transcript slot share a context: they carry the same alleles over it and lie on the same reference
 // positions.  So the projection is computed once per distinct slot of the source pool and gathered:
-//   jst_proj_rep_kernel      one lane per record: atomicMin of the record index into rep[cigar_off] -- the smallest arrival
-//                            index represents its slot
-//   (hipcub exclusive sum of rep[w] != none over the source pool: the number of every slot, in pool order)
-//   jst_proj_compact_kernel  one lane per pool word: slot number -> representative record; the last lane writes the count
+//   (the slot stage of transcript_slots.hpp: a representative record and a number for every distinct slot, in pool order)
 //   jst_proj_count_kernel    one lane per slot: the block of its haplotype that holds `begin` (binary search down column h of
 //                            hap_start), the journal walked from jst_first_ref / a_lo up to begin, then jst_project_compose
 //                            with a counting sink: words, ref_begin, ref_end, ref_score
 //   (hipcub exclusive sum of the word counts, 64 bits; jst_proj_total_kernel; the one read-back that sizes the pool)
 //   jst_proj_emit_kernel     the same walk with a writing sink
 //   jst_proj_gather_kernel   one lane per record i: its own record + the result of its slot -> spm_jst_ref_aln i
-// The scratch is laid out with scratch_layout.hpp; the sums, the first read-back and the events are device_order.hpp's.
+// The scratch is laid out with scratch_layout.hpp; the sums, the first read-back and the events are device_order.hpp's; the
+// ballot-and-count of the flagged lanes is transcript_slots.hpp's.
 // The walk starts from the tables of the index and runs forward as far as the transcript reaches: it assumes neither that a
 // carried deletion ends inside its block nor that begin and end lie in the same block.
 #pragma once
@@ -27,8 +26,8 @@ static_assert(SPM_CIGAR_INS == spm_hip::kProjIns && SPM_CIGAR_DEL == spm_hip::kP
 namespace spm_hip
 {
 
-constexpr uint32_t kProjNone = 0xFFFFFFFFu;
 enum { kProjCntSlots = 0, kProjCntBad = 1, kProjCntInside = 2, kProjCntChanged = 3, kProjCntWords = 4, kProjCnts = 5 };
+static_assert(kProjCntSlots == kSlotCntSlots && kProjCntBad == kSlotCntBad, "the slot stage writes the first two counters");
 
 struct jst_project_params
 {
@@ -43,7 +42,7 @@ struct jst_project_params
     uint32_t n_patterns;
     uint32_t cap;                    // slots the per-slot tables hold: min(n, n_ops)
     uint32_t *rep;                   // [n_ops] smallest record index whose transcript starts at this word, or none
-    const uint32_t *sid;             // [n_ops] exclusive sum of rep != none: the slot's number
+    uint32_t *sid;                   // [n_ops] exclusive sum of rep != none: the slot's number
     uint32_t *slot_rec;              // [cap] representative record of slot s
     unsigned long long *slot_range;  // [2 * cap] ref_begin, ref_end
     uint32_t *slot_words;            // [cap] words of the projected transcript
@@ -52,47 +51,18 @@ struct jst_project_params
     uint32_t *out_ops;
     unsigned long long *counts;      // kProjCnt*
     spm_jst_ref_aln *out;            // [n]
+    slot_tables slots() const { return slot_tables{rep, sid, slot_rec, n_ops, cap, counts}; } // (what the slot stage takes)
 };
 
-__global__ __launch_bounds__(256) void jst_proj_rep_kernel(const jst_project_params P)
+// what makes a record unusable for the slot stage
+struct jproj_unusable
 {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    bool bad = false;
-    if (i < P.n) {
-        const spm_jst_aln a = P.recs[i];
-        bad = a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops;
-        if (!bad)
-            atomicMin(&P.rep[a.cigar_off], (uint32_t)i);
+    uint64_t n_ops;
+    __device__ __forceinline__ bool operator()(const spm_jst_aln &a) const
+    {
+        return a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > n_ops;
     }
-    const unsigned long long mb = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && mb)
-        atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
-}
-
-struct jproj_flag_op
-{
-    const uint32_t *rep;
-    __device__ __forceinline__ uint32_t operator()(uint32_t w) const { return rep[w] != kProjNone ? 1u : 0u; }
 };
-
-struct jproj_widen_op
-{
-    const uint32_t *v;
-    __device__ __forceinline__ unsigned long long operator()(uint32_t s) const { return v[s]; }
-};
-
-__global__ __launch_bounds__(256) void jst_proj_compact_kernel(const jst_project_params P)
-{
-    const unsigned long long w = blockIdx.x * 256ull + threadIdx.x;
-    if (w >= P.n_ops)
-        return;
-    const uint32_t r = P.rep[w];
-    const uint32_t s = P.sid[w];
-    if (r != kProjNone && s < P.cap)
-        P.slot_rec[s] = r;
-    if (w == P.n_ops - 1)
-        P.counts[kProjCntSlots] = (unsigned long long)s + (r != kProjNone ? 1ull : 0ull);
-}
 
 // The projection of slot s into sink S.  Every table index is tested against its size before it is read; false counts as an
 // error of the call, never a fault.
@@ -158,13 +128,8 @@ __global__ __launch_bounds__(256) void jst_proj_count_kernel(const jst_project_p
         P.slot_words[s] = bad ? 0u : (uint32_t)R.n_words;
         P.slot_score[s] = bad ? 0 : (int32_t)R.ref_score;
     }
-    const unsigned long long mb = __ballot(bad), mi = __ballot(inside);
-    if ((threadIdx.x & 63) == 0) {
-        if (mb)
-            atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
-        if (mi)
-            atomicAdd(&P.counts[kProjCntInside], (unsigned long long)__popcll(mi));
-    }
+    count_flagged(&P.counts[kProjCntBad], bad);
+    count_flagged(&P.counts[kProjCntInside], inside);
 }
 
 __global__ void jst_proj_total_kernel(const jst_project_params P)
@@ -199,13 +164,8 @@ __global__ __launch_bounds__(256) void jst_proj_emit_kernel(const jst_project_pa
             }
         }
     }
-    const unsigned long long mb = __ballot(bad), mc = __ballot(changed);
-    if ((threadIdx.x & 63) == 0) {
-        if (mb)
-            atomicAdd(&P.counts[kProjCntBad], (unsigned long long)__popcll(mb));
-        if (mc)
-            atomicAdd(&P.counts[kProjCntChanged], (unsigned long long)__popcll(mc));
-    }
+    count_flagged(&P.counts[kProjCntBad], bad);
+    count_flagged(&P.counts[kProjCntChanged], changed);
 }
 
 __global__ __launch_bounds__(256) void jst_proj_gather_kernel(const jst_project_params P)
@@ -313,9 +273,9 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         hip_events<6> ev;
         SPM_HIP_CHECK(ctx, ev.create());
         size_t b_flag = 0, b_wide = 0;
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jproj_flag_op{nullptr}), n_src_ops, &b_flag));
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(jproj_widen_op{nullptr}),
-                                                                       cap, &b_wide));
+        SPM_HIP_CHECK(ctx, slot_stage_tmp_bytes(ctx, n_src_ops, &b_flag));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(widen_op{nullptr}), cap,
+                                                                       &b_wide));
         const size_t tmp_bytes = std::max(b_flag, b_wide);
         scratch_layout L;
         const size_t o_rep = L.take(n_src_ops * 4), o_sid = L.take(n_src_ops * 4), o_rec = L.take((size_t)cap * 4),
@@ -323,7 +283,6 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
                      o_off = L.take((size_t)cap * 8), o_counts = L.take(kProjCnts * 8), o_tmp = L.take(tmp_bytes);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
         void *base = ctx->d_scratch;
-        uint32_t *d_rep = L.at<uint32_t>(base, o_rep), *d_sid = L.at<uint32_t>(base, o_sid);
         uint32_t *d_words = L.at<uint32_t>(base, o_words);
         unsigned long long *d_off = L.at<unsigned long long>(base, o_off);
         unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
@@ -335,40 +294,33 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         P.recs = a->d_recs;
         P.n = n32;
         P.ops = a->d_ops;
-        P.n_ops = n_src_ops;
         P.ranks = ps->d_al_ranks;
         P.offsets = ps->d_al_offsets;
         P.m = ps->d_m;
         P.n_patterns = ps->n;
+        P.n_ops = n_src_ops;
         P.cap = cap;
-        P.rep = d_rep;
-        P.sid = d_sid;
+        P.rep = L.at<uint32_t>(base, o_rep);
+        P.sid = L.at<uint32_t>(base, o_sid);
         P.slot_rec = L.at<uint32_t>(base, o_rec);
+        P.counts = d_counts;
         P.slot_range = L.at<unsigned long long>(base, o_range);
         P.slot_words = d_words;
         P.slot_score = L.at<int32_t>(base, o_score);
         P.slot_off = d_off;
         P.out_ops = nullptr;
-        P.counts = d_counts;
         P.out = R->d_recs;
-        const unsigned g_rec = (unsigned)((n + 255) / 256), g_pool = (unsigned)((n_src_ops + 255) / 256),
-                       g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
+        const unsigned g_rec = (unsigned)((n + 255) / 256), g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- representatives: one per distinct slot of the source pool, numbered in pool order ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kProjCnts * 8, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_rep, 0xFF, n_src_ops * 4, st));
-        hipLaunchKernelGGL(jst_proj_rep_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jproj_flag_op{d_rep}), d_sid, n_src_ops));
-        hipLaunchKernelGGL(jst_proj_compact_kernel, dim3(g_pool), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), jproj_unusable{n_src_ops}, d_tmp, tmp_bytes));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- count: the projection of every slot with a counting sink, then where its words go ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(d_words, 0, (size_t)cap * 4, st));
         hipLaunchKernelGGL(jst_proj_count_kernel, dim3(g_slot), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx,
-                      exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(jproj_widen_op{d_words}), d_off, cap));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{d_words}), d_off, cap));
         hipLaunchKernelGGL(jst_proj_total_kernel, dim3(1), dim3(64), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
@@ -400,12 +352,13 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
         // ---- the host view: record i of the source's host view through the slot tables ----
-        std::vector<uint32_t> sid(n_src_ops), words(n_slots);
+        slot_host_map slot(n_src_ops);
+        std::vector<uint32_t> words(n_slots);
         std::vector<int32_t> score(n_slots);
         std::vector<unsigned long long> range(2 * n_slots), woff(n_slots);
         R->host_ops.resize(total);
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(sid.data(), d_sid, n_src_ops * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, slot.download(ctx, P.slots()));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), d_words, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(score.data(), P.slot_score, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(range.data(), P.slot_range, n_slots * 16, hipMemcpyDeviceToHost, st));
@@ -430,7 +383,7 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         R->host.resize(n);
         for (uint64_t i = 0; i < n; ++i) {
             const spm_jst_aln &x = a->host[i];
-            const uint32_t s = x.cigar_off < n_src_ops ? sid[x.cigar_off] : kProjNone;
+            const uint32_t s = slot.of(x.cigar_off);
             if (s >= n_slots) {
                 SPM_SET_ERR(ctx, "spm_hip_jst_alns_project: host record %llu names no projected slot", (unsigned long long)i);
                 return SPM_E_INVALID;
@@ -459,29 +412,17 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
 extern "C" int spm_hip_jst_ref_alns_view(spm_jst_ref_alns *a, const spm_jst_ref_aln **records, uint64_t *n, const uint32_t **ops,
                                          uint64_t *n_ops)
 {
-    if (!a || !records || !n)
+    if (!a)
         return SPM_E_INVALID;
-    *records = a->host.data();
-    *n = a->n;
-    if (ops)
-        *ops = a->host_ops.data();
-    if (n_ops)
-        *n_ops = a->n_ops;
-    return SPM_OK;
+    return pool_out(pool_src<spm_jst_ref_aln>{a->host.data(), a->n, a->host_ops.data(), a->n_ops}, records, n, ops, n_ops);
 }
 
 extern "C" int spm_hip_jst_ref_alns_device(spm_jst_ref_alns *a, const void **records, uint64_t *n, const void **ops,
                                            uint64_t *n_ops)
 {
-    if (!a || !records || !n)
+    if (!a)
         return SPM_E_INVALID;
-    *records = a->d_recs;
-    *n = a->n;
-    if (ops)
-        *ops = a->d_ops;
-    if (n_ops)
-        *n_ops = a->n_ops;
-    return SPM_OK;
+    return pool_out(pool_src<void, void, void>{a->d_recs, a->n, a->d_ops, a->n_ops}, records, n, ops, n_ops);
 }
 
 extern "C" int spm_hip_jst_ref_alns_stats(const spm_jst_ref_alns *a, spm_jst_project_stats *out)

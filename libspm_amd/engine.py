@@ -260,62 +260,64 @@ class Hits:
             pass
 
 
-class Alignments:
-    """Result of Hits.align(): ALN_DTYPE records in the order of Hits.view(), and the pool of CIGAR words
-    (len << 4 | op) they point into."""
+def _as_array(ptr, n, ctype, dtype):
+    if n == 0:
+        return np.zeros(0, dtype=dtype)
+    buf = (ctype * n).from_address(C.addressof(ptr.contents))
+    return np.frombuffer(buf, dtype=dtype).copy()
+
+
+class _RecordPool:
+    """What the results made of records + a pool of CIGAR words (len << 4 | op) share: a handle of the C type
+    spm_hip_<_PREFIX>_*, whose view hands out _REC records (numpy: _DTYPE) and the pool they point into, and whose
+    statistics are a _STATS.  The subclasses declare the four and keep what is their own."""
+    _PREFIX = _REC = _DTYPE = _STATS = None
 
     def __init__(self, ctx, h):
         self.ctx, self._h = ctx, h
 
+    def _call(self, name, *args):
+        _check(getattr(capi.lib(), f"spm_hip_{self._PREFIX}_{name}")(self._h, *args), self.ctx._h)
+
     def _raw(self):
-        rec = C.POINTER(capi.Aln)()
-        ops = C.POINTER(C.c_uint32)()
+        rec, ops = C.POINTER(self._REC)(), C.POINTER(C.c_uint32)()
         n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
-               self.ctx._h)
+        self._call("view", C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops))
         return rec, n.value, ops, n_ops.value
 
     def __len__(self):
         return self._raw()[1]
 
     def view(self) -> np.ndarray:
-        rec, n, _, _ = self._raw()
-        if n == 0:
-            return np.zeros(0, dtype=ALN_DTYPE)
-        buf = (capi.Aln * n).from_address(C.addressof(rec.contents))
-        return np.frombuffer(buf, dtype=ALN_DTYPE).copy()
+        r = self._raw()
+        return _as_array(r[0], r[1], self._REC, self._DTYPE)
 
     @property
     def ops(self) -> np.ndarray:
-        _, _, ops, n_ops = self._raw()
-        if n_ops == 0:
-            return np.zeros(0, dtype=np.uint32)
-        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
-        return np.frombuffer(buf, dtype=np.uint32).copy()
+        r = self._raw()
+        return _as_array(r[2], r[3], C.c_uint32, np.uint32)
 
-    def device(self):
-        """(records, n, ops, n_ops): device pointers, records in device hit order."""
+    def _device(self):
         r, o = C.c_void_p(), C.c_void_p()
         n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)), self.ctx._h)
+        self._call("device", C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops))
         return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
 
-    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
-        """SAM string of record i, e.g. "41=1X12=1I45=" (records / ops: views already fetched, to save the copies)."""
+    def _cigar(self, i, records, ops) -> str:
         r = (self.view() if records is None else records)[i]
         o = self.ops if ops is None else ops
         words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
         return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
 
-    def stats(self) -> capi.AlignStats:
-        s = capi.AlignStats()
-        _check(capi.lib().spm_hip_alns_stats(self._h, C.byref(s)), self.ctx._h)
+    def _stats(self):
+        s = self._STATS()
+        self._call("stats", C.byref(s))
         return s
 
     def close(self):
         if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_alns_destroy(self._h)
+            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
+                getattr(capi.lib(), f"spm_hip_{self._PREFIX}_destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -323,6 +325,23 @@ class Alignments:
             self.close()
         except Exception:
             pass
+
+
+class Alignments(_RecordPool):
+    """Result of Hits.align(): ALN_DTYPE records in the order of Hits.view(), and the pool of CIGAR words
+    (len << 4 | op) they point into."""
+    _PREFIX, _REC, _DTYPE, _STATS = "alns", capi.Aln, ALN_DTYPE, capi.AlignStats
+
+    def device(self):
+        """(records, n, ops, n_ops): device pointers, records in device hit order."""
+        return self._device()
+
+    def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
+        """SAM string of record i, e.g. "41=1X12=1I45=" (records / ops: views already fetched, to save the copies)."""
+        return self._cigar(i, records, ops)
+
+    def stats(self) -> capi.AlignStats:
+        return self._stats()
 
 
 def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | None = None, *,
@@ -588,60 +607,27 @@ def select_jst_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet |
     return JstHits(ctx, h, None, pats)
 
 
-class JstAlignments:
+class JstAlignments(_RecordPool):
     """Result of JstHits.align(): JST_ALN_DTYPE records in the order of JstHits.view(), and the pool of CIGAR words
     (len << 4 | op) they point into -- one transcript per segment hit, shared by the haplotypes of its context."""
+    _PREFIX, _REC, _DTYPE, _STATS = "jst_alns", capi.JstAln, JST_ALN_DTYPE, capi.JstAlignStats
 
     def __init__(self, ctx, h, jst=None, pats=None):
         # the tree and the needle set behind these alignments: project() reads both
-        self.ctx, self._h, self._jst, self._pats = ctx, h, jst, pats
-
-    def _raw(self):
-        rec = C.POINTER(capi.JstAln)()
-        ops = C.POINTER(C.c_uint32)()
-        n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
-               self.ctx._h)
-        return rec, n.value, ops, n_ops.value
-
-    def __len__(self):
-        return self._raw()[1]
-
-    def view(self) -> np.ndarray:
-        rec, n, _, _ = self._raw()
-        if n == 0:
-            return np.zeros(0, dtype=JST_ALN_DTYPE)
-        buf = (capi.JstAln * n).from_address(C.addressof(rec.contents))
-        return np.frombuffer(buf, dtype=JST_ALN_DTYPE).copy()
-
-    @property
-    def ops(self) -> np.ndarray:
-        _, _, ops, n_ops = self._raw()
-        if n_ops == 0:
-            return np.zeros(0, dtype=np.uint32)
-        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
-        return np.frombuffer(buf, dtype=np.uint32).copy()
+        super().__init__(ctx, h)
+        self._jst, self._pats = jst, pats
 
     def device(self):
         """(records, n, ops, n_ops): device pointers.  From JstHits.align(): records in the arrival order of the alignment
         fan-out.  From JstHits.align_selected(): record i matched to record i of the selection's device()."""
-        r, o = C.c_void_p(), C.c_void_p()
-        n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)),
-               self.ctx._h)
-        return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
+        return self._device()
 
     def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
         """SAM string of record i (records / ops: views already fetched, to save the copies)."""
-        r = (self.view() if records is None else records)[i]
-        o = self.ops if ops is None else ops
-        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
-        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+        return self._cigar(i, records, ops)
 
     def stats(self) -> capi.JstAlignStats:
-        s = capi.JstAlignStats()
-        _check(capi.lib().spm_hip_jst_alns_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats()
 
     def project(self) -> "JstRefAlignments":
         """These alignments in REFERENCE coordinates (spm_hip_jst_alns_project): ref_begin, ref_end, ref_score and a
@@ -651,74 +637,25 @@ class JstAlignments:
         if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
             raise capi.SpmError("JstAlignments.project: the tree or the needle set of these alignments has been closed")
         r = C.c_void_p()
-        _check(capi.lib().spm_hip_jst_alns_project(self._h, 0, C.byref(r)), self.ctx._h)
+        self._call("project", 0, C.byref(r))
         return JstRefAlignments(self.ctx, r)
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_alns_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class JstRefAlignments:
+class JstRefAlignments(_RecordPool):
     """Result of JstAlignments.project(): JST_REF_ALN_DTYPE records matched to the source's records, and the pool of CIGAR
     words (len << 4 | op) against the reference -- one transcript per distinct transcript slot of the source."""
-
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
-
-    def _raw(self):
-        rec = C.POINTER(capi.JstRefAln)()
-        ops = C.POINTER(C.c_uint32)()
-        n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_ref_alns_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops)),
-               self.ctx._h)
-        return rec, n.value, ops, n_ops.value
-
-    def __len__(self):
-        return self._raw()[1]
-
-    def view(self) -> np.ndarray:
-        rec, n, _, _ = self._raw()
-        if n == 0:
-            return np.zeros(0, dtype=JST_REF_ALN_DTYPE)
-        buf = (capi.JstRefAln * n).from_address(C.addressof(rec.contents))
-        return np.frombuffer(buf, dtype=JST_REF_ALN_DTYPE).copy()
-
-    @property
-    def ops(self) -> np.ndarray:
-        _, _, ops, n_ops = self._raw()
-        if n_ops == 0:
-            return np.zeros(0, dtype=np.uint32)
-        buf = (C.c_uint32 * n_ops).from_address(C.addressof(ops.contents))
-        return np.frombuffer(buf, dtype=np.uint32).copy()
+    _PREFIX, _REC, _DTYPE, _STATS = "jst_ref_alns", capi.JstRefAln, JST_REF_ALN_DTYPE, capi.JstProjectStats
 
     def device(self):
         """(records, n, ops, n_ops): device pointers; record i matched to record i of the source's device()."""
-        r, o = C.c_void_p(), C.c_void_p()
-        n, n_ops = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_ref_alns_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops)),
-               self.ctx._h)
-        return int(r.value or 0), int(n.value), int(o.value or 0), int(n_ops.value)
+        return self._device()
 
     def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
         """SAM string of record i (records / ops: views already fetched, to save the copies)."""
-        r = (self.view() if records is None else records)[i]
-        o = self.ops if ops is None else ops
-        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
-        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+        return self._cigar(i, records, ops)
 
     def stats(self) -> capi.JstProjectStats:
-        s = capi.JstProjectStats()
-        _check(capi.lib().spm_hip_jst_ref_alns_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats()
 
     def collapse(self) -> "JstRefLoci":
         """One record per distinct reference alignment (spm_hip_jst_ref_alns_collapse): records that agree in needle,
@@ -726,57 +663,23 @@ class JstRefAlignments:
         haplotype distances.  Reads only these records and their pool: tree and needle set may be closed, and the result
         stays valid after this object is closed."""
         r = C.c_void_p()
-        _check(capi.lib().spm_hip_jst_ref_alns_collapse(self._h, 0, C.byref(r)), self.ctx._h)
+        self._call("collapse", 0, C.byref(r))
         return JstRefLoci(self.ctx, r)
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_ref_alns_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _as_array(ptr, n, ctype, dtype):
-    if n == 0:
-        return np.zeros(0, dtype=dtype)
-    buf = (ctype * n).from_address(C.addressof(ptr.contents))
-    return np.frombuffer(buf, dtype=dtype).copy()
-
-
-class JstRefLoci:
+class JstRefLoci(_RecordPool):
     """Result of JstRefAlignments.collapse(): JST_REF_LOCUS_DTYPE records in (pattern, ref_begin, ref_end, ref_score,
     cigar_len, transcript words) order, one transcript per locus in `ops`, and per locus the distinct haplotypes that
     support it (`members`, ascending) with the smallest haplotype distance each has there (`member_scores`)."""
-
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    _PREFIX, _REC, _DTYPE, _STATS = "jst_ref_loci", capi.JstRefLocus, JST_REF_LOCUS_DTYPE, capi.JstCollapseStats
 
     def _raw(self):
         rec = C.POINTER(capi.JstRefLocus)()
         ops, mem = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
         msc = C.POINTER(C.c_int32)()
         n, n_ops, n_mem = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_ref_loci_view(self._h, C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops),
-                                                    C.byref(mem), C.byref(msc), C.byref(n_mem)), self.ctx._h)
+        self._call("view", C.byref(rec), C.byref(n), C.byref(ops), C.byref(n_ops), C.byref(mem), C.byref(msc), C.byref(n_mem))
         return rec, n.value, ops, n_ops.value, mem, msc, n_mem.value
-
-    def __len__(self):
-        return self._raw()[1]
-
-    def view(self) -> np.ndarray:
-        rec, n = self._raw()[:2]
-        return _as_array(rec, n, capi.JstRefLocus, JST_REF_LOCUS_DTYPE)
-
-    @property
-    def ops(self) -> np.ndarray:
-        r = self._raw()
-        return _as_array(r[2], r[3], C.c_uint32, np.uint32)
 
     @property
     def members(self) -> np.ndarray:
@@ -793,15 +696,12 @@ class JstRefLoci:
         """locus_of[i]: the locus of record i of the source's view()"""
         m = C.POINTER(C.c_uint32)()
         n = C.c_uint64()
-        _check(capi.lib().spm_hip_jst_ref_loci_map(self._h, C.byref(m), None, C.byref(n)), self.ctx._h)
+        self._call("map", C.byref(m), None, C.byref(n))
         return _as_array(m, n.value, C.c_uint32, np.uint32)
 
     def cigar(self, i: int, records: np.ndarray | None = None, ops: np.ndarray | None = None) -> str:
         """SAM string of locus i (records / ops: views already fetched, to save the copies)."""
-        r = (self.view() if records is None else records)[i]
-        o = self.ops if ops is None else ops
-        words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
-        return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
+        return self._cigar(i, records, ops)
 
     def haplotypes(self, i: int, records: np.ndarray | None = None):
         """(haplotypes, scores) of locus i"""
@@ -814,26 +714,11 @@ class JstRefLoci:
         (matched to the source's device() records) with n_alns."""
         r, o, m, s, mp = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         n, n_ops, n_mem, n_alns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_ref_loci_device(self._h, C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops), C.byref(m),
-                                                      C.byref(s), C.byref(n_mem)), self.ctx._h)
-        _check(capi.lib().spm_hip_jst_ref_loci_map(self._h, None, C.byref(mp), C.byref(n_alns)), self.ctx._h)
+        self._call("device", C.byref(r), C.byref(n), C.byref(o), C.byref(n_ops), C.byref(m), C.byref(s), C.byref(n_mem))
+        self._call("map", None, C.byref(mp), C.byref(n_alns))
         return {"records": int(r.value or 0), "n": int(n.value), "ops": int(o.value or 0), "n_ops": int(n_ops.value),
                 "members": int(m.value or 0), "member_scores": int(s.value or 0), "n_members": int(n_mem.value),
                 "locus_of": int(mp.value or 0), "n_alns": int(n_alns.value)}
 
     def stats(self) -> capi.JstCollapseStats:
-        s = capi.JstCollapseStats()
-        _check(capi.lib().spm_hip_jst_ref_loci_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_ref_loci_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats()

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import build_mirror
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
 
@@ -175,12 +177,7 @@ int main(int argc, char ** argv)
 def _build_locate(tmp_path):
     src = tmp_path / "locate.cpp"
     src.write_text(LOCATE_CPP)
-    exe = tmp_path / "locate"
-    lib = os.path.join(ROOT, "libspm_amd")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-pedantic", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src), "-L" + lib, "-l:libspm_hip.so",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
-    return exe
+    return build_mirror(str(src), tmp_path, fixtures=False)
 
 
 def test_locate_program_compiles_with_reference_flags(spm, tmp_path):

@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import build_mirror
 from test_align import ref_begins, replay
 from test_gpu_jst import _apply, _random_alleles
 
@@ -70,15 +71,7 @@ def test_record_layout_matches_the_header(spm, tmp_path):
 
 
 def _build_locate_cases(out_dir):
-    exe = out_dir / "jst_locate_cases"
-    lib = os.path.join(ROOT, "libspm_amd")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-pedantic", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"),
-                           '-DSPM_TEST_DATA="' + os.path.join(ROOT, "tests", "golden", "jst") + '"',
-                           "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "jst_locate_cases.cpp"),
-                           "-L" + lib, "-l:libspm_hip.so", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib",
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-lz"])
-    return exe
+    return build_mirror("jst_locate_cases.cpp", out_dir)
 
 
 def test_locate_program_compiles_with_reference_flags(spm, tmp_path):

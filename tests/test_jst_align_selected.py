@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import download
 from test_gpu_jst import _apply, _random_alleles
 from test_jst_align import SEED_TEXT, SEED_VAR, SHAPES, _check_against_haplotypes, _edited, _rows
 from test_jst_select import JH, ROWS, device_view, jrule, tree_of
@@ -219,12 +220,7 @@ ALN = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4"), ("patter
 def aln_device_view(ctx, a):
     """the records behind JstAlignments.device(), downloaded in their device order"""
     ptr, n, _, _ = a.device()
-    out = np.zeros(n, dtype=ALN)
-    if n:
-        ctx.synchronize()
-        hip = ctypes.CDLL("libamdhip64.so")
-        assert hip.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), 40 * n, 2) == 0   # device to host
-    return out
+    return download(ctx, ptr, n, ALN)
 
 
 def _open(spm, ctx, t):

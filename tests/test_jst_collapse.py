@@ -12,9 +12,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import download
 from test_align import replay
 from test_gpu_jst import _apply
-from test_jst_project import (ALL_KINDS, DEL, EQ, INS, X, Journal, _check, _cig, _device_view, _global_dp, _hap, _make_tree, _open,
+from test_jst_project import (ALL_KINDS, DEL, EQ, INS, X, Journal, _check, _cig, _global_dp, _hap, _make_tree, _open,
                               _plant, _r, _row1_tree, _window, np_project)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -337,6 +338,9 @@ def _collapse_checked(spm, ctx, t, needles, src, block, need=(), min_shared=True
     lc = pr.collapse()
     try:
         _compare(lc, want, rv)
+        # every projected slot has a pool offset of its own, so the collapse finds the projection's slots again: both number
+        # them with the one stage of transcript_slots.hpp
+        assert lc.stats().n_slots == pr.stats().n_projected
         return want, rv, _blob(lc)
     finally:
         lc.close()
@@ -485,7 +489,7 @@ def test_row5_locus_counts_around_a_workgroup(spm, ctx, n):
         lc = pr.collapse()
         d = lc.device()
         assert len(lc) == 0 and len(lc.ops) == 0 and len(lc.members) == 0 and len(lc.locus_of) == 0
-        assert d["n"] == d["n_ops"] == d["n_members"] == d["n_alns"] == 0 and lc.stats().n_slots == 0
+        assert d["n"] == d["n_ops"] == d["n_members"] == d["n_alns"] == 0 and lc.stats().n_slots == 0 == pr.stats().n_projected
         lc.close()
         pr.close()
     for x in (a, h, jst, ps, ref_text):
@@ -611,13 +615,13 @@ def test_row8_refusals_lifetimes_and_the_device_view(spm, ctx):
     # the device view equals the host view; the device map belongs to the source's DEVICE view
     d = l1.device()
     assert (d["n"], d["n_ops"], d["n_members"], d["n_alns"]) == (len(want["loci"]), len(want["ops"]), len(want["members"]), len(rv))
-    assert _device_view(ctx, d["records"], d["n"], LOCUS).tobytes() == want["loci"].tobytes()
-    assert _device_view(ctx, d["ops"], d["n_ops"], np.dtype("<u4")).tobytes() == want["ops"].tobytes()
-    assert _device_view(ctx, d["members"], d["n_members"], np.dtype("<u4")).tobytes() == want["members"].tobytes()
-    assert _device_view(ctx, d["member_scores"], d["n_members"], np.dtype("<i4")).tobytes() == want["member_scores"].tobytes()
-    dmap = _device_view(ctx, d["locus_of"], d["n_alns"], np.dtype("<u4"))
+    assert download(ctx, d["records"], d["n"], LOCUS).tobytes() == want["loci"].tobytes()
+    assert download(ctx, d["ops"], d["n_ops"], np.dtype("<u4")).tobytes() == want["ops"].tobytes()
+    assert download(ctx, d["members"], d["n_members"], np.dtype("<u4")).tobytes() == want["members"].tobytes()
+    assert download(ctx, d["member_scores"], d["n_members"], np.dtype("<i4")).tobytes() == want["member_scores"].tobytes()
+    dmap = download(ctx, d["locus_of"], d["n_alns"], np.dtype("<u4"))
     rp, rn, _ro, _rno = pr.device()
-    drv = _device_view(ctx, rp, rn, REF_ALN)
+    drv = download(ctx, rp, rn, REF_ALN)
     dwant = np_collapse(drv, rops)                            # (the same set of records in another order: the same loci)
     assert dwant["loci"].tobytes() == want["loci"].tobytes() and dmap.tobytes() == dwant["locus_of"].tobytes()
     assert l1.cigar(0) == _cig(want["ops"][:int(want["loci"][0]["cigar_len"])])
@@ -632,7 +636,7 @@ def test_row8_refusals_lifetimes_and_the_device_view(spm, ctx):
     pr.close()
     _compare(l1, want, rv)
     _compare(l3, want, rv)
-    assert _device_view(ctx, d["records"], d["n"], LOCUS).tobytes() == want["loci"].tobytes()
+    assert download(ctx, d["records"], d["n"], LOCUS).tobytes() == want["loci"].tobytes()
     # a closed source
     with pytest.raises(spm.SpmError):
         pr.collapse()

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import download
 from test_align import replay
 from test_gpu_jst import _apply, _random_alleles
 
@@ -635,15 +636,6 @@ def test_row11_slot_counts_around_a_workgroup(spm, ctx, n):
         x.close()
 
 
-def _device_view(ctx, ptr, n, dtype):
-    out = np.zeros(n, dtype=dtype)
-    if n:
-        ctx.synchronize()
-        hip = ctypes.CDLL("libamdhip64.so")
-        assert hip.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), dtype.itemsize * n, 2) == 0
-    return out
-
-
 @pytest.mark.gpu
 def test_row12_refusals_repeatability_and_the_device_view(spm, ctx):
     t, needles = _row1_tree()
@@ -660,8 +652,8 @@ def test_row12_refusals_repeatability_and_the_device_view(spm, ctx):
     sp, sn, _so, _sno = a.device()
     rp, rn, ro, rno = p1.device()
     assert sn == rn == len(p1) and rno == len(p1.ops)
-    sd, rd = _device_view(ctx, sp, sn, spm.JST_ALN_DTYPE), _device_view(ctx, rp, rn, spm.JST_REF_ALN_DTYPE)
-    assert np.array_equal(_device_view(ctx, ro, rno, np.dtype("<u4")), p1.ops)
+    sd, rd = download(ctx, sp, sn, spm.JST_ALN_DTYPE), download(ctx, rp, rn, spm.JST_REF_ALN_DTYPE)
+    assert np.array_equal(download(ctx, ro, rno, np.dtype("<u4")), p1.ops)
     for f in ("haplotype", "pattern", "score"):
         assert np.array_equal(sd[f], rd[f]), f
     sv, rv = a.view(), p1.view()

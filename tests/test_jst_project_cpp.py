@@ -3,23 +3,17 @@ libspm_amd/csrc/jst_project_core.hpp -- the code both kernels instantiate -- thr
 header alone, plain asserts, no device, as a stand-alone program, also under AddressSanitizer + UndefinedBehaviorSanitizer;
 and the mirror's journaled_sequence_tree::locate_reference through tests/cpp/jst_project_cases on the VCF fixtures, compiled
 with the reference's warning flags and run on the GPU.  The programs are compiled here, into the test's own directory."""
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
+from cpp_programs import build_cases, build_mirror
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan+ubsan"])
 def test_jst_project_core_cases(tmp_path, sanitize):
-    exe = tmp_path / ("jst_project_core_cases" + ("_asan" if sanitize else ""))
-    flags = ["-std=c++20", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-             "-fno-sanitize-recover=undefined"] if sanitize else ["-std=c++20", "-O2", "-pedantic"]
-    subprocess.check_call(["g++"] + flags + ["-Wall", "-Wextra", "-Werror", "-o", str(exe),
-                                             os.path.join(CPP, "jst_project_core_cases.cpp")])
+    exe = build_cases("jst_project_core_cases.cpp", tmp_path, sanitize=sanitize)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     print(r.stdout, r.stderr)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -30,18 +24,8 @@ def test_jst_project_core_cases(tmp_path, sanitize):
     assert kinds and all(int(x) > 0 for x in kinds.groups()), r.stdout
 
 
-LIB = os.path.join(ROOT, "libspm_amd")
-
-
 def _mirror_exe(out_dir):
-    exe = out_dir / "jst_project_cases"
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-pedantic", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"),
-                           '-DSPM_TEST_DATA="' + os.path.join(ROOT, "tests", "golden", "jst") + '"',
-                           "-o", str(exe), os.path.join(CPP, "jst_project_cases.cpp"),
-                           "-L" + LIB, "-l:libspm_hip.so", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-lz"])
-    return exe
+    return build_mirror("jst_project_cases.cpp", out_dir)
 
 
 def test_mirror_program_compiles_with_reference_flags(spm, tmp_path):

@@ -3,24 +3,16 @@ tests/cpp/jst_select_plan_cases -- plain asserts, no device, also under AddressS
 the mirror's journaled_sequence_tree::search(..., hit_selection) through tests/cpp/jst_select_cases on the VCF fixtures,
 compiled with the reference's warning flags and run on the GPU.  The programs are compiled here, into the test's own
 directory."""
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-LIB = os.path.join(ROOT, "libspm_amd")
+from cpp_programs import build_cases, build_mirror
 
 
 def _plan_exe(out_dir, sanitize):
-    exe = out_dir / ("jst_select_plan_cases" + ("_asan" if sanitize else ""))
-    flags = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-             "-fno-sanitize-recover=undefined"] if sanitize else ["-std=c++20", "-O2", "-pedantic"]
-    subprocess.check_call(["g++"] + flags + ["-Wall", "-Wextra", "-Werror", "-o", str(exe),
-                                             os.path.join(CPP, "jst_select_plan_cases.cpp")])
-    return exe
+    return build_cases("jst_select_plan_cases.cpp", out_dir, std="c++17" if sanitize else "c++20", sanitize=sanitize)
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan+ubsan"])
@@ -33,14 +25,7 @@ def test_jst_select_plan_cases(tmp_path, sanitize):
 
 
 def _mirror_exe(out_dir):
-    exe = out_dir / "jst_select_cases"
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-pedantic", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"),
-                           '-DSPM_TEST_DATA="' + os.path.join(ROOT, "tests", "golden", "jst") + '"',
-                           "-o", str(exe), os.path.join(CPP, "jst_select_cases.cpp"),
-                           "-L" + LIB, "-l:libspm_hip.so", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-lz"])
-    return exe
+    return build_mirror("jst_select_cases.cpp", out_dir)
 
 
 def test_mirror_program_compiles_with_reference_flags(spm, tmp_path):

@@ -1,23 +1,16 @@
 """The scratch layout of the sort-and-compact drivers (scratch_layout, libspm_amd/csrc/scratch_layout.hpp) through
 tests/cpp/scratch_layout_cases -- plain asserts, no device, also under AddressSanitizer + UndefinedBehaviorSanitizer.  The
 program is compiled here, into the test's own directory."""
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
+from cpp_programs import build_cases
 
 
 def _exe(out_dir, sanitize):
-    exe = out_dir / ("scratch_layout_cases" + ("_asan" if sanitize else ""))
-    flags = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-             "-fno-sanitize-recover=undefined"] if sanitize else ["-std=c++17", "-O2", "-pedantic"]
-    subprocess.check_call(["g++"] + flags + ["-Wall", "-Wextra", "-Werror", "-o", str(exe),
-                                             os.path.join(CPP, "scratch_layout_cases.cpp")])
-    return exe
+    return build_cases("scratch_layout_cases.cpp", out_dir, std="c++17", sanitize=sanitize)
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan+ubsan"])

@@ -9,11 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from cpp_programs import build_cases, build_mirror
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, "tests", "cpp")
-FLAGS = ["-std=c++20", "-O2", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libspm_amd"), "-l:libspm_hip.so", "-Wl,-rpath," + os.path.join(ROOT, "libspm_amd"),
-        "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
 
 
 def _sources(dirs):
@@ -29,7 +28,10 @@ def _build(name, deps, link):
     src, exe = os.path.join(CPP, name + ".cpp"), os.path.join(CPP, name)
     newest = max(os.path.getmtime(f) for f in [src] + deps)
     if not os.path.exists(exe) or os.path.getmtime(exe) < newest:
-        subprocess.check_call(["g++"] + FLAGS + ["-o", exe, src] + (LINK if link else []))
+        if link:
+            build_mirror(name + ".cpp", CPP, fixtures=False)
+        else:
+            build_cases(name + ".cpp", CPP, include=[os.path.join(ROOT, "include")])
     return exe
 
 
