@@ -63,13 +63,6 @@ __device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t 
     return __builtin_amdgcn_alignbit(hi, lo, sh);
 }
 
-// a value that is the same in every lane, moved to SGPRs (the compiler cannot prove uniformity of a loaded value)
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
-{
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-}
-
 // append the hits of one wave: ballot + popc prefix, one atomic per wave
 __device__ __forceinline__ void wave_append_hits(bool is_hit, uint64_t pos, uint32_t pattern, int32_t score,
                                                  spm_hit *hits, unsigned long long *counter, uint64_t cap)

@@ -19,6 +19,13 @@ namespace spm_hip
 
 constexpr int kWave = 64; // CDNA wavefront
 
+// a value that is the same in every lane, moved to SGPRs (the compiler cannot prove uniformity of a loaded value)
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
 struct error_sink
 {
     std::string msg;

@@ -95,7 +95,7 @@ struct filter_params
     uint32_t n_probes;        // Bloom probes per key
     uint32_t span_chunks;     // chunks per span
     uint32_t span_unit;       // symbols per chunk: 1024 (1-byte text) or 4096 (2-bit shadow)
-    uint32_t dynamic;         // 1: waves draw spans from counters[kCntSpanHead] instead of a static round-robin
+    uint32_t dynamic;         // how spans leave the queue at counters[kCntSpanHead]: 1 per wave, 2 per workgroup (plan_span)
     uint32_t key_len;         // H: symbols per key (12..16); windows are H symbols, keys 2H bits
     uint32_t key_mask;        // (1 << 2H) - 1
     uint32_t hash_variant;    // 1: Bloom cascade, 2: perfect-hash fingerprints, 3: dense pass, 4: presence bits
@@ -126,6 +126,20 @@ __device__ __forceinline__ void wave_count_add(unsigned long long *counter, uint
         v += __shfl_xor(v, o);
     if ((threadIdx.x & 63) == 0 && v)
         atomicAdd(counter, (unsigned long long)v);
+}
+
+// what one lane of the wave wrote to LDS (a queue, a chunk record) is there for the others
+__device__ __forceinline__ void queue_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The next chunk of list slots a wave draws after one of `size`: 32, 64, .. kChunkMax, and at least the n it needs now.
+__device__ __forceinline__ uint32_t chunk_grow(uint32_t size, uint32_t n)
+{
+    const uint32_t next = size * 2 < kChunkMin ? kChunkMin : (size * 2 > kChunkMax ? kChunkMax : size * 2);
+    return next < n ? n : next;
 }
 
 // this wave's chunk record in LDS
@@ -160,8 +174,7 @@ __device__ __forceinline__ void span_give_up(const filter_params &P, uint32_t *c
             atomicAdd(&P.counters[kCntVoid], 1ull); // no room to remember it: the host re-runs the whole scan
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    queue_sync();
 }
 
 // mark the unused tail of a wave's chunk invalid (wave-uniform call)
@@ -198,8 +211,7 @@ __device__ __forceinline__ void emit_survivors(const filter_params &P, bool has,
     }
     if (used + n > size) { // close this chunk, draw the next (twice as large, up to kChunkMax)
         surv_close(P, ck, lane);
-        uint32_t next = size * 2 < kChunkMin ? kChunkMin : (size * 2 > kChunkMax ? kChunkMax : size * 2);
-        next = next < n ? n : next;
+        const uint32_t next = chunk_grow(size, n);
         if (lane == 0) {
             const unsigned long long b = atomicAdd(&P.counters[kCntSurvSlots], (unsigned long long)next);
             ck[0] = (uint32_t)b;
@@ -208,11 +220,9 @@ __device__ __forceinline__ void emit_survivors(const filter_params &P, bool has,
             ck[3] = next;
         }
         used = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
     }
-    const uint64_t cbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(ck[1]) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane(ck[0]);
+    const uint64_t cbase = uniform_u64(((uint64_t)ck[1] << 32) | ck[0]);
     if (cbase + used + n > P.surv_cap) { // the survivor buffer is full
         span_give_up(P, ck, lane);
         return;
@@ -229,8 +239,7 @@ __device__ __forceinline__ void emit_survivors(const filter_params &P, bool has,
         ck[2] = used + n;
         ck[4] = cnt;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    queue_sync();
 }
 
 // Level 1 + level 2 on NWD 2-bit-packed words per lane (w[j] = 16 bases, prev[j] = the 16 bases before them).
@@ -424,6 +433,95 @@ __device__ __forceinline__ void filter_words_anchored(const filter_params &P, co
     }
 }
 
+// ---- the skeleton of a streaming pass: what seed_filter_kernel, seed_filter_dense_kernel and seed_filter_packed_kernel
+// share (stage, draw a span, its chunks, the word in front of it, every word's predecessor) ----
+
+// Prologue: stage the level-1 table in LDS (once per workgroup; the grid is persistent) and clear the waves' chunk records.
+__device__ __forceinline__ void stream_stage(const filter_params &P, uint32_t *lds)
+{
+    for (uint32_t i = threadIdx.x; i < P.lds_words; i += blockDim.x)
+        lds[i] = P.bitmap[i];
+    if ((threadIdx.x & 63) == 0) { // this wave's candidate chunk: none drawn yet
+        uint32_t *ck = lds + P.lds_words + kCandLdsSlot + kCandRec * (threadIdx.x >> 6);
+        for (uint32_t i = 0; i < kCandRec; ++i)
+            ck[i] = 0; // size 0: the first survivor draws a chunk; no span open yet
+    }
+    __syncthreads();
+}
+
+enum class span_draw
+{
+    run,  // `sp` is this wave's next span
+    idle, // the workgroup's last round has no span for this wave: draw again, to keep meeting the barriers
+    done, // the queue is empty
+};
+
+// Spans are drawn from a queue, counters[kCntSpanHead] (evens out the tail; a static round-robin measured 15-20 % slower
+// on 16 GiB and is gone):
+//   dynamic == 1: every wave draws its next span with one returning atomic;
+//   dynamic == 2: one atomic per WORKGROUP hands one span to each of its waves (waves_per_wg times fewer
+//                 atomics at the same granularity; a single head saturates near 88 dequeues/us, which a 1 GiB
+//                 text with 16 KiB spans would exceed).  Sharding the head per XCD group was slower (no
+//                 balancing across shards).
+// Every wave of the workgroup calls it in step (dynamic == 2 meets two workgroup barriers); `done` is then uniform over
+// the workgroup.
+__device__ __forceinline__ span_draw draw_span(const filter_params &P, uint32_t *lds, uint32_t lane, uint32_t wave_in_wg,
+                                               uint32_t waves_per_wg, uint64_t n_spans, uint64_t &sp)
+{
+    if (P.dynamic == 1) {
+        unsigned long long t = 0;
+        if (lane == 0)
+            t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
+        sp = uniform_u64(t);
+        return sp >= n_spans ? span_draw::done : span_draw::run;
+    }
+    __syncthreads(); // every wave has read the previous base
+    if (threadIdx.x == 0) {
+        const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
+        lds[P.lds_words] = (uint32_t)t;
+        lds[P.lds_words + 1] = (uint32_t)(t >> 32);
+    }
+    __syncthreads();
+    const uint64_t base = uniform_u64(((uint64_t)lds[P.lds_words + 1] << 32) | lds[P.lds_words]);
+    if (base >= n_spans)
+        return span_draw::done; // uniform over the workgroup
+    sp = base + wave_in_wg;
+    return sp >= n_spans ? span_draw::idle : span_draw::run;
+}
+
+// The word in front of a span that begins at text index span_base of the 1-byte text (the word of the lane "before lane
+// 0": the last 16 bytes of the previous chunk), and its N mask; wave-uniform.
+template <int SIG>
+__device__ __forceinline__ uint32_t span_carry_in(const filter_params &P, uint64_t span_base, uint32_t lane, uint32_t &carry_n)
+{
+    uint32_t carry_in = 0;
+    carry_n = 0;
+    if (span_base >= 16 && lane == 0) {
+        const uint4 before = load_text16(P.text, span_base - 16, P.hi);
+        carry_in = pack16_sig<SIG>(before, carry_n);
+    }
+    carry_n = __builtin_amdgcn_readfirstlane(carry_n);
+    return __builtin_amdgcn_readfirstlane(carry_in);
+}
+
+__device__ __forceinline__ uint32_t span_carry_in(const filter_params &P, uint64_t span_base, uint32_t lane) // dna4: no N mask
+{
+    uint32_t no_n;
+    return span_carry_in<4>(P, span_base, lane, no_n);
+}
+
+// dna4: pack this lane's 16 text bytes into w and give it its predecessor -- the previous lane's word through DPP, lane 0
+// takes the carry; the carry becomes lane 63's word.  (dna5 / dna15 keep the sequence, interleaved with its twin on the N
+// masks, flat in filter_group: shared, the compiler schedules their packing differently.)
+__device__ __forceinline__ void pack_with_prev(const uint4 &cur, uint32_t lane, uint32_t &carry_in, uint32_t &w, uint32_t &prev)
+{
+    w = pack16(cur);
+    prev = __builtin_amdgcn_update_dpp(0u, w, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
+    if (lane == 0)
+        prev = carry_in;
+    carry_in = __builtin_amdgcn_readlane(w, 63);
+}
+
 // One group of UU consecutive 1-KiB chunks, already in registers.  chunk u of the group starts at text index
 // gbase + 1024*u; this lane holds its bytes [16*lane, 16*lane+16).
 template <int S, int UU, int HV, int SIG, bool KM, bool AN = false>
@@ -435,13 +533,15 @@ __device__ __forceinline__ void filter_group(const filter_params &P, const uint4
     uint32_t nv[SIG != 4 ? UU : 1]; // dna5 / dna15: (this lane's N mask << 16) | previous lane's N mask
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
-        uint32_t nm = 0;
-        w[u] = pack16_sig<SIG>(cur[u], nm);
-        prev[u] = __builtin_amdgcn_update_dpp(0u, w[u], 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (lane == 0)
-            prev[u] = carry_in;
-        carry_in = __builtin_amdgcn_readlane(w[u], 63);
-        if (SIG != 4) {
+        if constexpr (SIG == 4) {
+            pack_with_prev(cur[u], lane, carry_in, w[u], prev[u]);
+        } else {
+            uint32_t nm = 0;
+            w[u] = pack16_sig<SIG>(cur[u], nm);
+            prev[u] = __builtin_amdgcn_update_dpp(0u, w[u], 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
+            if (lane == 0)
+                prev[u] = carry_in;
+            carry_in = __builtin_amdgcn_readlane(w[u], 63);
             uint32_t np = __builtin_amdgcn_update_dpp(0u, nm, 0x138, 0xF, 0xF, false);
             if (lane == 0)
                 np = carry_n;
@@ -467,80 +567,32 @@ template <int S, int U, int HV, int SIG, bool KM, bool AN = false>
 __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2)) ? 1024 : 512) void seed_filter_kernel(const filter_params P)
 {
     extern __shared__ uint32_t lds[];
-    // ---- stage the level-1 table in LDS (once per workgroup; the grid is persistent) ----
-    for (uint32_t i = threadIdx.x; i < P.lds_words; i += blockDim.x)
-        lds[i] = P.bitmap[i];
-    if ((threadIdx.x & 63) == 0) { // this wave's candidate chunk: none drawn yet
-        uint32_t *ck = lds + P.lds_words + kCandLdsSlot + kCandRec * (threadIdx.x >> 6);
-        for (uint32_t i = 0; i < kCandRec; ++i)
-            ck[i] = 0; // size 0: the first survivor draws a chunk; no span open yet
-    }
-    __syncthreads();
+    stream_stage(P, lds);
 
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t waves_per_wg = blockDim.x >> 6;
-    const uint64_t wave_id =
-        (uint64_t)blockIdx.x * waves_per_wg + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_wg;
+    const uint32_t wave_in_wg = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t idx_mask = P.bitmap_words * 32 - 1;
 
-    const uint64_t base0 = P.lo & ~1023ull; // chunks are 1 KiB aligned relative to text[0]
-    const uint64_t n_chunks = (P.hi - base0 + 1023) / 1024;
-    const uint64_t n_whole = (P.hi - base0) / 1024; // chunks that lie fully inside the text
-    const uint64_t span = P.span_chunks;            // multiple of U (host guarantees)
-    const uint64_t n_spans = (n_chunks + span - 1) / span;
-    const uint8_t *lane_text = P.text + base0 + (uint64_t)lane * 16;
+    const stream_geometry G = stream_geometry_of(P.lo, P.hi, 1024, P.span_chunks);
+    const uint64_t span = P.span_chunks; // multiple of U (host guarantees)
+    const uint8_t *lane_text = P.text + G.base0 + (uint64_t)lane * 16;
 
-    // Dynamic scheduling (evens out the tail; static round-robin measured 15-20 % slower on 16 GiB):
-    //   dynamic == 1: every wave draws its next span with one returning atomic on counters[kCntSpanHead];
-    //   dynamic == 2: one atomic per WORKGROUP hands one span to each of its waves (waves_per_wg times fewer
-    //                 atomics at the same granularity; a single head saturates near 88 dequeues/us, which a 1 GiB
-    //                 text with 16 KiB spans would exceed).  Sharding the head per XCD group was slower (no
-    //                 balancing across shards).
-    const uint32_t wave_in_wg = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint64_t sp = wave_id;
+    uint64_t sp;
     for (;;) {
-        if (P.dynamic == 1) {
-            unsigned long long t = 0;
-            if (lane == 0)
-                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
-            sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
-        } else if (P.dynamic == 2) {
-            __syncthreads(); // every wave has read the previous base
-            if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
-                lds[P.lds_words] = (uint32_t)t;
-                lds[P.lds_words + 1] = (uint32_t)(t >> 32);
-            }
-            __syncthreads();
-            const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words + 1]) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words]);
-            if (base >= n_spans)
-                break; // uniform over the workgroup
-            sp = base + wave_in_wg;
-            if (sp >= n_spans)
-                continue; // this wave idles for the last round but keeps meeting the barriers
-        }
-        if (sp >= n_spans)
+        const span_draw drawn = draw_span(P, lds, lane, wave_in_wg, waves_per_wg, G.n_spans, sp);
+        if (drawn == span_draw::done)
             break;
+        if (drawn == span_draw::idle)
+            continue;
         const uint64_t c_begin = sp * span;
-        const uint64_t c_end = c_begin + span < n_chunks ? c_begin + span : n_chunks;
-        span_open(P, lds, lane, base0 + c_begin * 1024);
-        // word of the lane "before lane 0": last 16 bytes of the previous chunk
-        uint32_t carry_in = 0, carry_n = 0;
-        {
-            const uint64_t cb = base0 + c_begin * 1024;
-            if (cb >= 16 && lane == 0) {
-                const uint4 before = load_text16(P.text, cb - 16, P.hi);
-                carry_in = pack16_sig<SIG>(before, carry_n);
-            }
-            carry_in = __builtin_amdgcn_readfirstlane(carry_in);
-            carry_n = __builtin_amdgcn_readfirstlane(carry_n);
-        }
+        const uint64_t c_end = c_begin + span < G.n_chunks ? c_begin + span : G.n_chunks;
+        span_open(P, lds, lane, G.base0 + c_begin * 1024);
+        uint32_t carry_n;
+        uint32_t carry_in = span_carry_in<SIG>(P, G.base0 + c_begin * 1024, lane, carry_n);
         // ---- fast path: whole groups ----
         uint64_t ch = c_begin;
-        const uint64_t whole_end = c_end < n_whole ? c_end : n_whole;
+        const uint64_t whole_end = c_end < G.n_whole ? c_end : G.n_whole;
         const uint64_t fast_end = c_begin + (whole_end > c_begin ? (whole_end - c_begin) / U * U : 0);
         if (ch < fast_end) {
             uint4 nxt[U];
@@ -565,16 +617,16 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
                 // scheduled well as they are; a barrier there only forces the packing to wait for all eight loads.)
                 if constexpr (S <= 2)
                     __builtin_amdgcn_sched_barrier(0);
-                filter_group<S, U, HV, SIG, KM, AN>(P, cur, base0 + ch * 1024, carry_in, carry_n, lane, lds, idx_mask);
+                filter_group<S, U, HV, SIG, KM, AN>(P, cur, G.base0 + ch * 1024, carry_in, carry_n, lane, lds, idx_mask);
             }
         }
         // ---- ragged end ----
         for (; ch < c_end; ++ch) {
             uint4 one[1];
-            one[0] = load_text16(P.text, base0 + ch * 1024 + (uint64_t)lane * 16, P.hi);
-            filter_group<S, 1, HV, SIG, KM, AN>(P, one, base0 + ch * 1024, carry_in, carry_n, lane, lds, idx_mask);
+            // (chunks are 1 KiB aligned: the lane's offset is OR-ed in, which keeps this address apart from lane_text's sum)
+            one[0] = load_text16(P.text, (G.base0 + ch * 1024) | ((uint64_t)lane * 16), P.hi);
+            filter_group<S, 1, HV, SIG, KM, AN>(P, one, G.base0 + ch * 1024, carry_in, carry_n, lane, lds, idx_mask);
         }
-        sp += n_waves;
     }
     surv_close(P, cand_chunk_of(P, lds), lane);
 }
@@ -674,13 +726,8 @@ __device__ __forceinline__ void dense_group(const filter_params &P, const uint4 
     static_assert(UU % 2 == 0 || UU == 1, "words are taken in pairs");
     uint32_t w[UU], prev[UU];
 #pragma unroll
-    for (int u = 0; u < UU; ++u) {
-        w[u] = pack16(cur[u]);
-        prev[u] = __builtin_amdgcn_update_dpp(0u, w[u], 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (lane == 0)
-            prev[u] = carry_in;
-        carry_in = __builtin_amdgcn_readlane(w[u], 63);
-    }
+    for (int u = 0; u < UU; ++u)
+        pack_with_prev(cur[u], lane, carry_in, w[u], prev[u]);
     const uint32_t goff = (uint32_t)(gbase - span_base) + lane * 16; // (this lane's first base of chunk 0) - span begin
 #pragma unroll
     for (int j = 0; j < UU; j += 2) {
@@ -735,8 +782,7 @@ __device__ __forceinline__ void dense_group(const filter_params &P, const uint4 
                 Q.off[q] = goff + (uint32_t)j * 1024u + (odd ? 1024u : 0u) + (b >> 1) + 1u; // = window start - span begin + 16
             }
             qn += __popcll(mm);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            queue_sync();
             if (qn > kDenseQueueCap - 64)
                 dense_drain(P, Q, qn, false, span_base, lane, lds);
         }
@@ -747,70 +793,33 @@ template <int U, int NP, int S = 0, bool KM = false>
 __global__ __launch_bounds__(1024) void seed_filter_dense_kernel(const filter_params P)
 {
     extern __shared__ uint32_t lds[];
-    for (uint32_t i = threadIdx.x; i < P.lds_words; i += blockDim.x)
-        lds[i] = P.bitmap[i];
-    if ((threadIdx.x & 63) == 0) { // this wave's candidate chunk: none drawn yet
-        uint32_t *ck = lds + P.lds_words + kCandLdsSlot + kCandRec * (threadIdx.x >> 6);
-        for (uint32_t i = 0; i < kCandRec; ++i)
-            ck[i] = 0;
-    }
-    __syncthreads();
+    stream_stage(P, lds);
 
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t waves_per_wg = blockDim.x >> 6;
     const uint32_t wave_in_wg = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t wave_id = (uint64_t)blockIdx.x * waves_per_wg + wave_in_wg;
-    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_wg;
     dense_queue &Q = *reinterpret_cast<dense_queue *>(lds + P.lds_words + kCandLdsSlot + kCandRec * 16 +
                                                       (sizeof(dense_queue) / 4) * wave_in_wg);
     uint32_t qn = 0;
 
-    const uint64_t base0 = P.lo & ~1023ull; // chunks are 1 KiB aligned relative to text[0]
-    const uint64_t n_chunks = (P.hi - base0 + 1023) / 1024;
-    const uint64_t n_whole = (P.hi - base0) / 1024; // chunks that lie fully inside the text
-    const uint64_t span = P.span_chunks;            // multiple of U (host guarantees)
-    const uint64_t n_spans = (n_chunks + span - 1) / span;
-    const uint8_t *lane_text = P.text + base0 + (uint64_t)lane * 16;
+    const stream_geometry G = stream_geometry_of(P.lo, P.hi, 1024, P.span_chunks);
+    const uint64_t span = P.span_chunks; // multiple of U (host guarantees)
+    const uint8_t *lane_text = P.text + G.base0 + (uint64_t)lane * 16;
 
-    uint64_t sp = wave_id;
-    for (;;) { // (span scheduling as in seed_filter_kernel)
-        if (P.dynamic == 1) {
-            unsigned long long t = 0;
-            if (lane == 0)
-                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
-            sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
-        } else if (P.dynamic == 2) {
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
-                lds[P.lds_words] = (uint32_t)t;
-                lds[P.lds_words + 1] = (uint32_t)(t >> 32);
-            }
-            __syncthreads();
-            const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words + 1]) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words]);
-            if (base >= n_spans)
-                break;
-            sp = base + wave_in_wg;
-            if (sp >= n_spans)
-                continue;
-        }
-        if (sp >= n_spans)
+    uint64_t sp;
+    for (;;) {
+        const span_draw drawn = draw_span(P, lds, lane, wave_in_wg, waves_per_wg, G.n_spans, sp);
+        if (drawn == span_draw::done)
             break;
+        if (drawn == span_draw::idle)
+            continue;
         const uint64_t c_begin = sp * span;
-        const uint64_t c_end = c_begin + span < n_chunks ? c_begin + span : n_chunks;
-        const uint64_t span_base = base0 + c_begin * 1024;
+        const uint64_t c_end = c_begin + span < G.n_chunks ? c_begin + span : G.n_chunks;
+        const uint64_t span_base = G.base0 + c_begin * 1024;
         span_open(P, lds, lane, span_base);
-        uint32_t carry_in = 0;
-        {
-            uint32_t nm = 0;
-            if (span_base >= 16 && lane == 0)
-                carry_in = pack16_sig<4>(load_text16(P.text, span_base - 16, P.hi), nm);
-            carry_in = __builtin_amdgcn_readfirstlane(carry_in);
-        }
+        uint32_t carry_in = span_carry_in(P, span_base, lane);
         uint64_t ch = c_begin;
-        const uint64_t whole_end = c_end < n_whole ? c_end : n_whole;
+        const uint64_t whole_end = c_end < G.n_whole ? c_end : G.n_whole;
         const uint64_t fast_end = c_begin + (whole_end > c_begin ? (whole_end - c_begin) / U * U : 0);
         if (ch < fast_end) {
             uint4 nxt[U];
@@ -829,16 +838,15 @@ __global__ __launch_bounds__(1024) void seed_filter_dense_kernel(const filter_pa
                 for (int u = 0; u < U; ++u)
                     nxt[u] = load16_stream(lane_text + pf * 1024 + (uint64_t)u * ustride);
                 __builtin_amdgcn_sched_barrier(0); // the prefetch stays ahead of the group's work
-                dense_group<U, NP, S, KM>(P, cur, base0 + ch * 1024, span_base, carry_in, lane, lds, Q, qn);
+                dense_group<U, NP, S, KM>(P, cur, G.base0 + ch * 1024, span_base, carry_in, lane, lds, Q, qn);
             }
         }
         for (; ch < c_end; ++ch) { // ragged end
             uint4 one[1];
-            one[0] = load_text16(P.text, base0 + ch * 1024 + (uint64_t)lane * 16, P.hi);
-            dense_group<1, NP, S, KM>(P, one, base0 + ch * 1024, span_base, carry_in, lane, lds, Q, qn);
+            one[0] = load_text16(P.text, G.base0 + ch * 1024 + (uint64_t)lane * 16, P.hi);
+            dense_group<1, NP, S, KM>(P, one, G.base0 + ch * 1024, span_base, carry_in, lane, lds, Q, qn);
         }
         dense_drain(P, Q, qn, true, span_base, lane, lds); // (offsets in the queue are relative to this span)
-        sp += n_waves;
     }
     surv_close(P, cand_chunk_of(P, lds), lane);
 }
@@ -850,63 +858,33 @@ template <int S, int U2, int HV, bool KM>
 __global__ __launch_bounds__(1024) void seed_filter_packed_kernel(const filter_params P, const uint4 *__restrict__ shadow)
 {
     extern __shared__ uint32_t lds[];
-    for (uint32_t i = threadIdx.x; i < P.lds_words; i += blockDim.x)
-        lds[i] = P.bitmap[i];
-    if ((threadIdx.x & 63) == 0) { // this wave's candidate chunk: none drawn yet
-        uint32_t *ck = lds + P.lds_words + kCandLdsSlot + kCandRec * (threadIdx.x >> 6);
-        for (uint32_t i = 0; i < kCandRec; ++i)
-            ck[i] = 0; // size 0: the first survivor draws a chunk; no span open yet
-    }
-    __syncthreads();
+    stream_stage(P, lds);
 
     constexpr int NWD = 4 * U2;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t waves_per_wg = blockDim.x >> 6;
     const uint32_t wave_in_wg = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t wave_id = (uint64_t)blockIdx.x * waves_per_wg + wave_in_wg;
-    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_wg;
     const uint32_t idx_mask = P.bitmap_words * 32 - 1;
 
-    const uint64_t base0 = P.lo & ~4095ull;                   // p-chunks are aligned to 4096 symbols
-    const uint64_t n_chunks = (P.hi - base0 + 4095) / 4096;
-    const uint64_t span = P.span_chunks;                      // multiple of U2
-    const uint64_t n_spans = (n_chunks + span - 1) / span;
-    const uint4 *lane_src = shadow + (base0 / 64) + lane;     // one uint4 = 64 symbols
+    const stream_geometry G = stream_geometry_of(P.lo, P.hi, 4096, P.span_chunks); // p-chunks
+    const uint64_t span = P.span_chunks;                    // multiple of U2
+    const uint4 *lane_src = shadow + (G.base0 / 64) + lane; // one uint4 = 64 symbols
 
-    uint64_t sp = wave_id;
+    uint64_t sp;
     for (;;) {
-        if (P.dynamic == 1) {
-            unsigned long long t = 0;
-            if (lane == 0)
-                t = atomicAdd(&P.counters[kCntSpanHead], 1ull);
-            sp = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t);
-        } else if (P.dynamic == 2) {
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const unsigned long long t = atomicAdd(&P.counters[kCntSpanHead], (unsigned long long)waves_per_wg);
-                lds[P.lds_words] = (uint32_t)t;
-                lds[P.lds_words + 1] = (uint32_t)(t >> 32);
-            }
-            __syncthreads();
-            const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words + 1]) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane(lds[P.lds_words]);
-            if (base >= n_spans)
-                break;
-            sp = base + wave_in_wg;
-            if (sp >= n_spans)
-                continue;
-        }
-        if (sp >= n_spans)
+        const span_draw drawn = draw_span(P, lds, lane, wave_in_wg, waves_per_wg, G.n_spans, sp);
+        if (drawn == span_draw::done)
             break;
+        if (drawn == span_draw::idle)
+            continue;
         const uint64_t c_begin = sp * span;
-        const uint64_t c_end = c_begin + span < n_chunks ? c_begin + span : n_chunks;
+        const uint64_t c_end = c_begin + span < G.n_chunks ? c_begin + span : G.n_chunks;
         const uint64_t fast_end = c_begin + (c_end - c_begin + U2 - 1) / U2 * U2; // whole groups (shadow is padded)
-        span_open(P, lds, lane, base0 + c_begin * 4096);
+        span_open(P, lds, lane, G.base0 + c_begin * 4096);
         // the word in front of this span's first word
         uint32_t carry_in = 0;
         {
-            const uint64_t first_word = (base0 + c_begin * 4096) / 16;
+            const uint64_t first_word = (G.base0 + c_begin * 4096) / 16;
             if (first_word > 0 && lane == 0)
                 carry_in = reinterpret_cast<const uint32_t *>(shadow)[first_word - 1];
             carry_in = __builtin_amdgcn_readfirstlane(carry_in);
@@ -944,9 +922,8 @@ __global__ __launch_bounds__(1024) void seed_filter_packed_kernel(const filter_p
                 prev[4 * u + 2] = cur[u].y;
                 prev[4 * u + 3] = cur[u].z;
             }
-            filter_words<S, NWD, HV, 4, true, KM>(P, w, prev, nv, base0 + ch * 4096, lane, lds, idx_mask);
+            filter_words<S, NWD, HV, 4, true, KM>(P, w, prev, nv, G.base0 + ch * 4096, lane, lds, idx_mask);
         }
-        sp += n_waves;
     }
     surv_close(P, cand_chunk_of(P, lds), lane);
 }
@@ -1275,8 +1252,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
         const uint32_t h = (uint32_t)mix64(bkey) & 127u;
         if (act)
             B.elect[h] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
         const uint32_t w = act ? B.elect[h] : lane;
         const unsigned long long wkey = ((unsigned long long)B.key_hi[first + w] << 32) | B.key_lo[first + w];
         const bool follower = act && w != lane && wkey == bkey;
@@ -1285,8 +1261,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
             atomicOr(&B.run_hi[first + w], B.run_hi[first + lane]);
             act = false;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
     }
     if (act)
         run = ((unsigned long long)B.run_hi[first + lane] << 32) | B.run_lo[first + lane];
@@ -1326,8 +1301,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
         for (uint32_t q = C.used + lane; q < C.size; q += 64)
             if (C.base + q < R.band_cap)
                 R.bands[C.base + q].val = kBandInvalid;
-        uint32_t next = C.size * 2 < kChunkMin ? kChunkMin : (C.size * 2 > kChunkMax ? kChunkMax : C.size * 2);
-        next = next < nn ? nn : next;
+        uint32_t next = chunk_grow(C.size, nn);
         if (C.draws < kDenseDraws) {
             next = nn;
             ++C.draws;
@@ -1335,8 +1309,7 @@ __device__ __forceinline__ void insert_bands(const resolve_params &R, band_queue
         unsigned long long b = 0;
         if (lane == 0)
             b = atomicAdd(&R.counters[kCntBandSlots], (unsigned long long)next);
-        C.base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
+        C.base = uniform_u64(b);
         C.used = 0;
         C.size = next;
     }
@@ -1375,8 +1348,7 @@ __device__ __forceinline__ unsigned long long wave_reserve_hits(unsigned long lo
     if (total != 0) {
         if (lane == 0)
             base = atomicAdd(counter, (unsigned long long)total);
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)base);
+        base = uniform_u64(base);
     }
     return base + (incl - mine);
 }
@@ -1413,12 +1385,6 @@ struct resolve_wave // what a wave of resolve_kernel carries (wave-uniform)
     band_chunk C;
     uint32_t n_cand;
 };
-
-__device__ __forceinline__ void queue_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // n (<= 64) pairs from the top of the queue, one per lane: one visit of the checks; pairs with rounds to go return to the
 // queue, pairs that are through become band hits
@@ -2039,14 +2005,12 @@ __global__ __launch_bounds__(256) void verify_kernel(const verify_params P)
         unsigned long long base = 0;
         if (lane == 0)
             base = atomicAdd(P.hit_counter, (unsigned long long)n_staged);
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)base);
+        base = uniform_u64(base);
         for (uint32_t i = lane; i < n_staged; i += 64)
             if (base + i < P.hit_cap)
                 P.hits[base + i] = stage[i];
         n_staged = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
     };
     unsigned long long n_cand = P.counters[P.band_counter];
     if (n_cand > P.band_cap)
@@ -2158,8 +2122,7 @@ __global__ __launch_bounds__(256) void verify_kernel(const verify_params P)
             if (!staged) {
                 if (lane == 0)
                     direct = atomicAdd(P.hit_counter, (unsigned long long)total);
-                direct = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(direct >> 32)) << 32) |
-                         (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)direct);
+                direct = uniform_u64(direct);
             }
             uint32_t at = n_staged + incl - fresh;
             for (uint32_t mm = keep; mm != 0; mm &= mm - 1) {
@@ -2177,8 +2140,7 @@ __global__ __launch_bounds__(256) void verify_kernel(const verify_params P)
             }
             if (staged)
                 n_staged += total;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            queue_sync();
         }
     }
     flush();
@@ -2290,8 +2252,7 @@ __global__ __launch_bounds__(256) void verify_wave_kernel(const verify_params P,
                 e4[j] = P.sigma > 4 ? src[4 * rs] : 0u;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
         uint32_t Pv[NB], Mv[NB], ho = 0;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
@@ -2404,8 +2365,7 @@ __global__ __launch_bounds__(256) void verify_wave_kernel(const verify_params P,
         for (; t < t_wave; ++t)
             step(t, std::true_type{}, std::false_type{}, std::true_type{});
         // ---- emission: the lanes of a group share its slots; wave-converged appends ----
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
         if (__ballot(any_hit) != 0) {
             // pass 1: every lane of a group takes the slots r = gl, gl + G, ..: dedupe, keep what is new
             const uint32_t nr = active ? (uint32_t)(e_hi - e_lo) + 1 : 0u;
@@ -2437,8 +2397,7 @@ __global__ __launch_bounds__(256) void verify_wave_kernel(const verify_params P,
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        queue_sync();
     }
     wave_count_add(P.hit_counter + kCntBandsVerified, n_valid); // bands verified
 }

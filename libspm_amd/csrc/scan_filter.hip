@@ -276,8 +276,7 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
             const uint32_t wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 2048 / threads));
             const uint32_t grid = ctx->n_cu * wg_per_cu;
             const uint64_t n_waves = (uint64_t)grid * (threads / 64);
-            const uint64_t n_chunks = (P.hi - (P.lo & ~1023ull) + 1023) / 1024;
-            const span_plan span = plan_span(n_chunks, n_waves, 1024);
+            const span_plan span = plan_span(stream_geometry_of(P.lo, P.hi, 1024).n_chunks, n_waves, 1024);
             P.span_chunks = span.span_chunks;
             P.span_unit = 1024;
             // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
@@ -290,8 +289,7 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
             if (use_packed) {
                 // p-chunks of 4096 symbols: recompute the span geometry in those units
                 filter_params Q = P;
-                const uint64_t n_pchunks = (Q.hi - (Q.lo & ~4095ull) + 4095) / 4096;
-                const span_plan pspan = plan_span(n_pchunks, n_waves, 4096);
+                const span_plan pspan = plan_span(stream_geometry_of(Q.lo, Q.hi, 4096).n_chunks, n_waves, 4096);
                 Q.span_chunks = pspan.span_chunks;
                 Q.span_unit = 4096;
                 if (sb <= 0)

@@ -214,6 +214,26 @@ inline void fallback_tiles(const fallback_plan &F, uint64_t ctx_begin, const uin
     }
 }
 
+// ---- the chunks and spans of a streaming pass over the windows inside [lo, hi): the kernels and the driver ask here ----
+struct stream_geometry
+{
+    uint64_t base0;    // first symbol of chunk 0: chunks are aligned to `unit` symbols relative to text[0]
+    uint64_t n_chunks; // chunks that hold a symbol in front of hi
+    uint64_t n_whole;  // ... that lie fully in front of hi
+    uint64_t n_spans;  // spans of span_chunks chunks (the last one may be short)
+};
+// unit: symbols per chunk, 1024 (the 1-byte text) or 4096 (the p-chunks of the 2-bit shadow); lo < hi.  The driver counts
+// the chunks before it has planned the span: spans of one chunk.
+SPM_HD inline stream_geometry stream_geometry_of(uint64_t lo, uint64_t hi, uint32_t unit, uint32_t span_chunks = 1)
+{
+    stream_geometry G;
+    G.base0 = lo & ~(uint64_t)(unit - 1);
+    G.n_chunks = (hi - G.base0 + (unit - 1)) / unit;
+    G.n_whole = (hi - G.base0) / unit;
+    G.n_spans = (G.n_chunks + span_chunks - 1) / span_chunks;
+    return G;
+}
+
 // ---- the span of a streaming pass: how many chunks a wave (or workgroup) takes off the span queue at a time ----
 struct span_plan
 {
@@ -232,6 +252,7 @@ inline span_plan plan_span(uint64_t n_chunks, uint64_t n_waves, uint32_t unit)
         pspan = (pspan + 3) & ~3ull;
         S.span_chunks = (uint32_t)pspan;
         S.dynamic = pspan >= 48 ? 1u : 2u;
+        assert(S.dynamic == 1 || S.dynamic == 2);
         return S;
     }
     uint64_t span = n_chunks / (n_waves * 32) + 1;
@@ -245,6 +266,7 @@ inline span_plan plan_span(uint64_t n_chunks, uint64_t n_waves, uint32_t unit)
     // span dequeue: per wave while the dequeue rate stays far below what one atomic word sustains (~88/us, i.e.
     // spans >= 192 KiB at 7 TB/s), per workgroup otherwise (measured: C3 2.52 vs 2.59 ms, C2 0.88 vs 0.20 ms)
     S.dynamic = span >= 192 ? 1u : 2u;
+    assert(S.dynamic == 1 || S.dynamic == 2); // (the kernels know no other way to draw a span)
     return S;
 }
 

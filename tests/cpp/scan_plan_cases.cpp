@@ -1,6 +1,7 @@
 // scan_plan_cases.cpp -- the host-side decisions of one scan (libspm_amd/csrc/scan_plan.hpp) without a device: the tile
 // tables of the brute-force kernel and the span-local fallback's ranges on generated inputs, the retry policy row by row,
-// the clean predicate against the status expression of the device-side fused copy, the filter's buffer sizes.
+// the clean predicate against the status expression of the device-side fused copy, the filter's buffer sizes, the chunk
+// geometry of a streaming pass.
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -310,9 +311,39 @@ static void span_cases()
     EXPECT_TRUE(is(plan_span(64, 64, 1024), 8, 2) && is(plan_span(1u << 16, 64, 1024), 64, 2));
 }
 
+// the chunks and spans of a streaming pass: values worked out by hand (chunk 0 begins at the unit border at or below lo)
+static void geometry_cases()
+{
+    auto is = [](stream_geometry g, uint64_t base0, uint64_t n_chunks, uint64_t n_whole, uint64_t n_spans) {
+        return g.base0 == base0 && g.n_chunks == n_chunks && g.n_whole == n_whole && g.n_spans == n_spans;
+    };
+    // lo inside chunk 1 of the 1-byte text, hi inside chunk 9: chunks 1..9 = 9, the last one ragged; spans of 8: 2
+    EXPECT_TRUE(is(stream_geometry_of(1500, 10000, 1024, 8), 1024, 9, 8, 2));
+    // ... in p-chunks: lo and hi inside p-chunks 0 and 2: 3 p-chunks, 2 whole; spans of 4: 1
+    EXPECT_TRUE(is(stream_geometry_of(1500, 10000, 4096, 4), 0, 3, 2, 1));
+    // hi exactly on a chunk border: no ragged chunk; 8 chunks are one span of 8 and two spans of 4
+    EXPECT_TRUE(is(stream_geometry_of(1024, 9 * 1024, 1024, 8), 1024, 8, 8, 1));
+    EXPECT_TRUE(is(stream_geometry_of(1030, 9 * 1024, 1024, 4), 1024, 8, 8, 2));
+    EXPECT_TRUE(is(stream_geometry_of(5000, 3 * 4096, 4096, 4), 4096, 2, 2, 1));
+    // ... one symbol further: a ragged chunk, and with it a ninth chunk and a second span
+    EXPECT_TRUE(is(stream_geometry_of(1024, 9 * 1024 + 1, 1024, 8), 1024, 9, 8, 2));
+    EXPECT_TRUE(is(stream_geometry_of(5000, 3 * 4096 + 1, 4096, 4), 4096, 3, 2, 1));
+    // less than one chunk: inside one chunk (no whole chunk), and across a border (one ragged chunk behind a whole one)
+    EXPECT_TRUE(is(stream_geometry_of(100, 200, 1024, 8), 0, 1, 0, 1));
+    EXPECT_TRUE(is(stream_geometry_of(1000, 1100, 1024, 8), 0, 2, 1, 1));
+    EXPECT_TRUE(is(stream_geometry_of(4000, 4200, 4096, 4), 0, 2, 1, 1));
+    EXPECT_TRUE(is(stream_geometry_of(4097, 4100, 4096, 4), 4096, 1, 0, 1));
+    // lo on a border; a text beyond 2^32 symbols; the driver's count of chunks (spans of one chunk)
+    EXPECT_TRUE(is(stream_geometry_of(0, 1ull << 34, 1024, 136), 0, 1ull << 24, 1ull << 24, ((1ull << 24) + 135) / 136));
+    EXPECT_TRUE(is(stream_geometry_of((1ull << 33) + 7, (1ull << 34) + 5, 4096, 68), 1ull << 33, (1ull << 21) + 1, 1ull << 21,
+                   ((1ull << 21) + 1 + 67) / 68));
+    EXPECT_TRUE(is(stream_geometry_of(1500, 10000, 1024), 1024, 9, 8, 9) && is(stream_geometry_of(1500, 10000, 4096), 0, 3, 2, 3));
+}
+
 int main()
 {
     span_cases();
+    geometry_cases();
     tiler_cases();
     policy_cases();
     clean_cases();
