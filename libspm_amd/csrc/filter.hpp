@@ -632,7 +632,7 @@ __global__ __launch_bounds__(((S == 1 && !KM && SIG == 4) || (S == 2 && U == 2))
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Dense pass: every key of a needle set of any size in ONE pass over the text (filter_shared.hpp, index_build.hpp).
+// Dense pass: every key of a needle set of any size in ONE pass over the text (filter_shared.hpp, index_dense.hpp).
 //   level 0   which of a lane's 16 windows per word begin with an anchor dimer: bit-parallel on the packed word
 //             (dense_select: ~6 VALU per pattern and word); 1/8 .. 3/16 of the windows for the usual sets;
 //   level 1   one presence bit per key in LDS (2^20 bits), looked up for the anchored windows in a per-lane loop over the

@@ -85,7 +85,7 @@ SPM_HD inline uint32_t ht_hash(uint32_t key)
 // in L2 (one 16-byte gather per window that passed the bit test: 8 slots of {1, 15-bit fingerprint}), consulted from
 // inside the streaming kernel in batches of 64.  What makes that affordable is looking up few windows: every key begins
 // with an ANCHOR dimer (a union of <= kDensePatterns dimer patterns, 1/8 .. of all dimers), chosen on the host so that
-// every needle still has its disjoint intact-able pieces (index_build.hpp); a text window that begins with any other
+// every needle still has its disjoint intact-able pieces (index_dense.hpp); a text window that begins with any other
 // dimer cannot equal a key.
 constexpr uint32_t kDensePatterns = 3;
 constexpr uint32_t kDenseBloomBits = 20;          // 2^20 bits = 128 KiB of LDS

@@ -12,14 +12,14 @@
 #include <memory>
 
 #include "common.hpp"
-#include "index_build.hpp"
+#include "index_types.hpp"
 
 using namespace spm_hip;
 
 // ----------------------------------------------------------------------------------------------------
 // pattern set
 // ----------------------------------------------------------------------------------------------------
-struct spm_patterns : spm_hip::seed_index // (the seed index: passes, entries, seed layout -- index_build.hpp)
+struct spm_patterns : spm_hip::seed_index // (the seed index: passes, entries, seed layout -- index_types.hpp)
 {
     spm_ctx *ctx = nullptr;
     int algo = 0;
@@ -81,12 +81,7 @@ inline hipError_t select_stats_close(bool &timed, hipEvent_t begin, hipEvent_t o
     return hipSuccess;
 }
 
-// SPM_HIP_TRACE=1: one stderr line per C-ABI call that does work, with its timings
-inline bool spm_trace_on()
-{
-    const char *v = getenv("SPM_HIP_TRACE");
-    return v && *v && *v != '0';
-}
+inline bool spm_trace_on() { return trace_on(); } // (host_util.hpp)
 
 
 // every knob of a scan, read from the environment in ONE place, once per C-ABI call that scans.  Each one is set by a test:

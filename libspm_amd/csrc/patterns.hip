@@ -2,6 +2,7 @@
 // (/root/reference/libspm/libspm/matcher/myers_matcher.hpp:40-43) -- match-mask tables, seed index, state blobs.
 // MI355X only; no CPU scan path exists in this library: if HIP fails the call fails.
 #include "internal.hpp"
+#include "index_build.hpp"
 #include "tables_build.hpp"
 
 // Every table of a needle set lives in ONE device allocation and travels in one stream of pinned chunks: the sources are laid
@@ -393,7 +394,7 @@ void state_from_internal(const spm_patterns *p, const std::vector<uint32_t> &in,
     }
 }
 
-// Host-only self-check of the seed index (no device, no context): index_build.hpp
+// Host-only self-check of the seed index (no device, no context): index_selftest.hpp
 extern "C" int spm_hip_host_selftest(int algo, const uint8_t *ranks_concat, const uint32_t *offsets, uint32_t n_patterns,
                                      const uint16_t *k, uint32_t sigma, uint64_t *stats)
 {

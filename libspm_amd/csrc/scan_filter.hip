@@ -16,7 +16,8 @@ void launch(K kernel, dim3 grid, uint32_t threads, size_t lds, hipStream_t s, Ar
 using filter_kernel = void (*)(filter_params);
 using packed_kernel = void (*)(filter_params, const uint4 *);
 
-// The streaming kernel of each pass the index build (index_build.hpp) can produce; nullptr for any other combination.
+// The streaming kernel of each pass the index build (index_tables.hpp build_one_index, index_dense.hpp build_dense_index) can
+// produce; nullptr for any other combination.
 // Sparse passes on the 1-byte text, seed_filter_kernel<S, U, HV, SIG, KM>: U 1-KiB chunks per group (8 from stride 4 on,
 // 2 at strides 1 and 2); KM = keys shorter than 16 symbols, which only strides 1 and 2 carry.
 //   dna4, fingerprint table (HV 2): strides 4..16 (strides 1 and 2 use presence bits, unless anchored);

@@ -6,7 +6,7 @@
 
 #include <vector>
 
-#include "index_build.hpp"
+#include "index_types.hpp"
 
 namespace spm_hip
 {

@@ -15,13 +15,14 @@ WARN = ["-Wall", "-Wextra", "-Werror"]
 SANITIZE = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
-def build_cases(source, out_dir, std="c++20", include=(), sanitize=False):
+def build_cases(source, out_dir, std="c++20", include=(), sanitize=False, threads=False):
     """A host-only case program (its own main, no device, nothing to link): tests/cpp/<source> -> out_dir/<name>, or
-    <name>_asan with the sanitizers.  include: directories for -I."""
+    <name>_asan with the sanitizers.  include: directories for -I.  threads: the program starts std::threads."""
     name = os.path.splitext(os.path.basename(source))[0]
     exe = pathlib.Path(out_dir) / (name + ("_asan" if sanitize else ""))
     flags = ["-std=" + std] + (SANITIZE if sanitize else ["-O2", "-pedantic"])
-    subprocess.check_call(["g++"] + flags + WARN + ["-I" + d for d in include] + ["-o", str(exe), os.path.join(CPP, source)])
+    subprocess.check_call(["g++"] + flags + WARN + (["-pthread"] if threads else []) + ["-I" + d for d in include] +
+                          ["-o", str(exe), os.path.join(CPP, source)])
     return exe
 
 
