@@ -612,6 +612,164 @@ public:
         return collapse_host(locate_reference_host(needles, window, needle_ranks, reports_begin, selection, block, stats));
     }
 
+    // ---- locate_reference and locate_reference_loci with every indel at its leftmost equivalent place (the contract of
+    // spm_hip_jst_ref_alns_normalize in spm_hip.h): haplotypes that differ only in WHICH copy of a repeat an indel touches say
+    // the same about the reference, and collapse to one locus.  Device route: locate + projection + normalisation (+ collapse).
+    // Trees the device path does not take, and the second opinion of the tests: locate_reference_host through normalize_host,
+    // the rule in column form, a route of its own.  Both return the same vector.
+    std::vector<jst_ref_alignment> locate_reference_normalized(spm_patterns * needles, std::size_t window,
+                                                               std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                               bool reports_begin, std::size_t block = 0,
+                                                               jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_normalized_device(needles, window, reports_begin, block, stats);
+        return locate_reference_normalized_host(needles, window, needle_ranks, reports_begin, block, stats);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_normalized(spm_patterns * needles, std::size_t window,
+                                                               std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                               bool reports_begin, hip::hit_selection const & selection,
+                                                               std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_normalized_device(needles, window, reports_begin, selection, block, stats);
+        return locate_reference_normalized_host(needles, window, needle_ranks, reports_begin, selection, block, stats);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_normalized_device(spm_patterns * needles, std::size_t window,
+                                                                      bool reports_begin, std::size_t block = 0,
+                                                                      jst_search_stats * stats = nullptr) const
+    {
+        return projections_of(device_alns(needles, window, block, stats).get(), reports_begin, true);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_normalized_device(spm_patterns * needles, std::size_t window,
+                                                                      bool reports_begin, hip::hit_selection const & selection,
+                                                                      std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return projections_of(device_alns(needles, window, selection, block, stats).get(), reports_begin, true);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_normalized_host(spm_patterns * needles, std::size_t window,
+                                                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                    bool reports_begin, std::size_t block = 0,
+                                                                    jst_search_stats * stats = nullptr) const
+    {
+        return normalize_host(locate_reference_host(needles, window, needle_ranks, reports_begin, block, stats), needle_ranks,
+                              _reference);
+    }
+
+    std::vector<jst_ref_alignment> locate_reference_normalized_host(spm_patterns * needles, std::size_t window,
+                                                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                    bool reports_begin, hip::hit_selection const & selection,
+                                                                    std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return normalize_host(locate_reference_host(needles, window, needle_ranks, reports_begin, selection, block, stats),
+                              needle_ranks, _reference);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized(spm_patterns * needles, std::size_t window,
+                                                                std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                bool reports_begin, std::size_t block = 0,
+                                                                jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_loci_normalized_device(needles, window, block, stats);
+        return locate_reference_loci_normalized_host(needles, window, needle_ranks, reports_begin, block, stats);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized(spm_patterns * needles, std::size_t window,
+                                                                std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                bool reports_begin, hip::hit_selection const & selection,
+                                                                std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reference_loci_normalized_device(needles, window, selection, block, stats);
+        return locate_reference_loci_normalized_host(needles, window, needle_ranks, reports_begin, selection, block, stats);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized_device(spm_patterns * needles, std::size_t window,
+                                                                       std::size_t block = 0,
+                                                                       jst_search_stats * stats = nullptr) const
+    {
+        return loci_of(device_alns(needles, window, block, stats).get(), true);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized_device(spm_patterns * needles, std::size_t window,
+                                                                       hip::hit_selection const & selection, std::size_t block = 0,
+                                                                       jst_search_stats * stats = nullptr) const
+    {
+        return loci_of(device_alns(needles, window, selection, block, stats).get(), true);
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized_host(spm_patterns * needles, std::size_t window,
+                                                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                     bool reports_begin, std::size_t block = 0,
+                                                                     jst_search_stats * stats = nullptr) const
+    {
+        return collapse_host(locate_reference_normalized_host(needles, window, needle_ranks, reports_begin, block, stats));
+    }
+
+    std::vector<jst_ref_locus> locate_reference_loci_normalized_host(spm_patterns * needles, std::size_t window,
+                                                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                                     bool reports_begin, hip::hit_selection const & selection,
+                                                                     std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        return collapse_host(locate_reference_normalized_host(needles, window, needle_ranks, reports_begin, selection, block, stats));
+    }
+
+    // The normalisation on the host, in column form: one op per column, a gap run moved one step at a time by the rule of
+    // spm_hip.h.  i and r -- the needle symbols and reference positions the columns before the run consume -- are counted
+    // anew for every step.
+    template <typename reference_t>
+    static std::vector<jst_ref_alignment> normalize_host(std::vector<jst_ref_alignment> alns,
+                                                         std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                                                         reference_t const & reference)
+    {
+        for (jst_ref_alignment & a : alns) {
+            std::vector<std::uint8_t> const & P = needle_ranks[a.needle];
+            std::vector<std::uint32_t> col;
+            for (std::uint32_t const w : a.aln.cigar())
+                col.insert(col.end(), w >> 4, w & 15u);
+            std::size_t const n = col.size();
+            for (std::size_t at = 0; at < n;) {
+                std::uint32_t const op = col[at];
+                if (op != SPM_CIGAR_INS && op != SPM_CIGAR_DEL) {
+                    ++at;
+                    continue;
+                }
+                std::size_t c = at, L = 0;
+                while (c + L < n && col[c + L] == op)
+                    ++L;
+                while (c >= 2 && col[c - 1] == SPM_CIGAR_EQ) {
+                    std::size_t i = 0, r = a.aln.begin_position();
+                    for (std::size_t k = 0; k < c; ++k) {
+                        i += col[k] != SPM_CIGAR_DEL;
+                        r += col[k] != SPM_CIGAR_INS;
+                    }
+                    if (op == SPM_CIGAR_INS ? P[i - 1] != P[i + L - 1] : !(reference[r - 1] == reference[r + L - 1]))
+                        break;
+                    col[c - 1] = op;
+                    col[c - 1 + L] = SPM_CIGAR_EQ;
+                    for (--c; c >= 1 && col[c - 1] == op; --c) // a run of the same op on the left: one run from now on
+                        ++L;
+                }
+                at = c + L;
+            }
+            std::vector<std::uint32_t> words;
+            for (std::size_t lo = 0; lo < n;) {
+                std::size_t hi = lo;
+                while (hi < n && col[hi] == col[lo])
+                    ++hi;
+                words.push_back(static_cast<std::uint32_t>((hi - lo) << 4) | col[lo]);
+                lo = hi;
+            }
+            a.aln = alignment{a.aln.begin_position(), a.aln.end_position(), a.aln.errors(), words.data(), words.size()};
+        }
+        return alns;
+    }
+
     // The collapse on the host: sort by content, fold equal neighbours, then sort and fold the members of every locus.
     static std::vector<jst_ref_locus> collapse_host(std::vector<jst_ref_alignment> alns)
     {
@@ -809,14 +967,30 @@ private:
         return out;
     }
 
-    // the projection of device alignments, in the order alignments_of gives the alignments themselves: record i of the
-    // projection's host view belongs to record i of the source's
-    static std::vector<jst_ref_alignment> projections_of(spm_jst_alns * a, bool reports_begin)
+    // the projection of device alignments, left-normalised if asked for (record i still belongs to record i of the source);
+    // the caller owns the result
+    static spm_jst_ref_alns * projected(spm_jst_alns * a, bool normalized)
     {
         spm_ctx * ctx = hip::default_context();
         spm_jst_ref_alns * r = nullptr;
         if (spm_hip_jst_alns_project(a, 0, &r) != SPM_OK)
             hip::fatal("spm_hip_jst_alns_project", ctx);
+        if (!normalized)
+            return r;
+        spm_jst_ref_alns * z = nullptr;
+        int const rc = spm_hip_jst_ref_alns_normalize(r, 0, &z);
+        spm_hip_jst_ref_alns_destroy(r); // (the result stays valid without its source)
+        if (rc != SPM_OK)
+            hip::fatal("spm_hip_jst_ref_alns_normalize", ctx);
+        return z;
+    }
+
+    // the projection of device alignments, in the order alignments_of gives the alignments themselves: record i of the
+    // projection's host view belongs to record i of the source's
+    static std::vector<jst_ref_alignment> projections_of(spm_jst_alns * a, bool reports_begin, bool normalized = false)
+    {
+        spm_ctx * ctx = hip::default_context();
+        spm_jst_ref_alns * r = projected(a, normalized);
         std::unique_ptr<spm_jst_ref_alns, decltype(&spm_hip_jst_ref_alns_destroy)> owner{r, &spm_hip_jst_ref_alns_destroy};
         spm_jst_aln const * src = nullptr;
         spm_jst_ref_aln const * rec = nullptr;
@@ -843,12 +1017,10 @@ private:
     }
 
     // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
-    static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a)
+    static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false)
     {
         spm_ctx * ctx = hip::default_context();
-        spm_jst_ref_alns * r = nullptr;
-        if (spm_hip_jst_alns_project(a, 0, &r) != SPM_OK)
-            hip::fatal("spm_hip_jst_alns_project", ctx);
+        spm_jst_ref_alns * r = projected(a, normalized);
         spm_jst_ref_loci * l = nullptr;
         int const rc = spm_hip_jst_ref_alns_collapse(r, 0, &l);
         spm_hip_jst_ref_alns_destroy(r); // (the loci stay valid without their source)

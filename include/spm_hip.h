@@ -625,7 +625,8 @@ void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a);
  *  1. Same range, different transcripts.  ref = GATTCGCAAAAGTCCATG, one allele deletes the A at position 10; haplotype 0
  *     carries it, haplotype 1 does not.  Needle TTCGCAAAGTCCA, k = 1.  Haplotype 0: distance 0, projected 8=1D5=, [2,16),
  *     NM 1.  Haplotype 1: distance 1, projected 5=1D8=, [2,16), NM 1.  TWO loci, in this order (the word 5= is smaller than
- *     8=).  Left-normalisation of indels would merge them; it is not part of this call.
+ *     8=).  Left-normalisation of indels would merge them; it is not part of this call.  spm_hip_jst_ref_alns_normalize
+ *     (below) is that stage: on its result this call gives ONE locus, 5=1D8=.
  *  2. One haplotype twice.  ref = GATTCGCATGTCCATG, one allele inserts G at position 8, carried by haplotype 0.  Needle
  *     ATTCGCA, k = 1.  The hit ending at 8 is 7= with distance 0; the hit ending at 9 is 7=1D with distance 1, and its D
  *     falls on the inserted symbol and projects to nothing.  Both records project to 7=, [1,8): ONE locus, n_records 2,
@@ -686,6 +687,81 @@ int spm_hip_jst_ref_loci_device(spm_jst_ref_loci *l, const void **records, uint6
 int spm_hip_jst_ref_loci_map(spm_jst_ref_loci *l, const uint32_t **host_map, const void **device_map, uint64_t *n_alns);
 int spm_hip_jst_ref_loci_stats(const spm_jst_ref_loci *l, spm_jst_collapse_stats *out);
 void spm_hip_jst_ref_loci_destroy(spm_jst_ref_loci *l);
+
+/* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
+ * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
+ * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps
+ * them apart.  This call returns the records of a projection with every transcript LEFT-NORMALISED, in a form the collapse
+ * (and view, device, destroy and this call again) takes unchanged.  No other call changes its output.
+ *
+ * The rule.  Per record: the needle P, ref[ref_begin, ref_end) and the transcript as columns c_0 .. c_{n-1} (a word
+ * len << 4 | op is len columns).  A GAP RUN is a maximal stretch of consecutive columns of one gap op (I or D); adjacent words
+ * of one op are one run.  For the run in columns [c, c + L) let i be the number of needle symbols the columns before c
+ * consume and r be ref_begin plus the number of reference positions they consume.  One STEP LEFT is allowed iff
+ *     c >= 2             (the column on the run's left is not column 0: the first column of a transcript never moves, and a
+ *                         run never becomes a leading gap),
+ *     column c - 1 is =, and
+ *     P[i - 1] == P[i + L - 1] for an I run, ref[r - 1] == ref[r + L - 1] for a D run (ranks are compared, as everywhere).
+ * The step turns columns [c - 1, c - 1 + L) into the gap and column c - 1 + L into =.  If the run's new left neighbour is a
+ * run of the SAME op the two are one run from then on: c becomes that run's first column, L grows, and stepping goes on with
+ * the joined run.  A left neighbour that is X or the other gap op stops the run.  Runs are treated left to right; a run is
+ * finished when no step is allowed, then comes the next run on its right.  Adjacent equal ops are merged into words exactly
+ * as the projection merges them (a run above 2^28 - 1 columns is full words and then the rest).
+ * It follows that
+ *   * ref_begin, ref_end, ref_score, score, haplotype and pattern are unchanged, and so is the number of =, X, I and D columns;
+ *   * the result consumes exactly P and ref[ref_begin, ref_end), and every = / X column is still true;
+ *   * normalising a normalised transcript changes nothing;
+ *   * the result depends only on (P, ref, ref_begin, words);
+ *   * a transcript wholly inside an insertion (|P| I) is unchanged;
+ *   * the word count grows by at most one word per gap run -- result words <= 2 x source words -- and may shrink, when runs
+ *     join or a passed = run is used up.
+ * Worked cases (ref, needle, ref_begin: source -> result).
+ *  1. GATTCGCAAAAGTCCATG, TTCGCAAAGTCCA, 2: 8=1D5= -> 5=1D8= (and 6=1D7=, 5=1D8= give the same): collapse case 1, whose two
+ *     haplotypes now agree.
+ *  2. GGAC (ACT)x5 GGTC, AC (ACT)x4 GG, 2: one unit deleted in any of the five places -> 2=3D14=.  A tandem repeat of unit 3.
+ *  3. GATCCGT, ATCCCG, 1: 4=1I1= or 3=1I2= -> 2=1I3=.  An insertion.
+ *  4. GACGTCGTA, ACGTCGTCGTA, 1: 7=3I1= -> 1=3I7=.  The run stops with one column on its left.
+ *  5. CAAAAG, AAAG, 1: 3=1D1= -> 1=1D3=.  The first column is pinned.
+ *  6. CAAAAAAG, AAAAG, 1: 2=1D1=1D2=, 1=1D2=1D2= and 4=2D1= -> 1=2D4=.  Two runs join and go on as one.
+ *  7. GACGTTA, ACGATTA, 1: 3=1X1I2= unchanged.  An X stops a run.
+ *
+ *   * Accepted: any result of spm_hip_jst_alns_project or of this call.  The call reads the reference text of the tree and
+ *     the needles of the set behind the projection: both must be alive DURING the call.  The result outlives them and its
+ *     source.  A tree indexed again since the search is accepted: the reference text belongs to no index generation.
+ *   * Record i of the host view belongs to record i of the source's host view, record i of the device view to record i of
+ *     the source's device view.  Every field but cigar_off / cigar_len equals the source's.  The pool holds one transcript per
+ *     distinct source slot, in source pool order; equal source cigar_off gives equal result cigar_off.  Two calls give
+ *     byte-identical host views.
+ *   * spm_hip_jst_ref_alns_stats on the result answers the counts (n_alns, n_projected = slots, n_ops = words of this pool)
+ *     with zero times; spm_hip_jst_ref_alns_normalize_stats on a handle this call did not make is SPM_E_INVALID.
+ *   * SPM_E_INVALID with a message: NULL arguments, unknown flag bits, a handle that names no tree.
+ *   * A slot whose transcript lies outside the source pool, whose words do not consume exactly its needle and its reference
+ *     range, or whose range lies outside the reference is COUNTED on the device and fails the whole call with SPM_E_INVALID,
+ *     never a fault: every needle, reference and pool index is tested against its size before it is read.
+ *   * More than 2^32 - 1 result words: SPM_E_UNSUPPORTED, decided before any result word is written.
+ *   * No records: an empty result and SPM_OK.
+ * flags: must be 0 */
+typedef struct spm_jst_normalize_stats { /* 96 bytes */
+    float ms_total;            /* device: the five stages below (HIP events) */
+    float ms_slots;            /* one representative record per distinct source slot */
+    float ms_normalize;        /* the rule, one lane per slot */
+    float ms_offsets;          /* where every slot's words go; their total */
+    float ms_gather;           /* one record per source record */
+    float ms_compact;          /* the slots' words into the pool */
+    float ms_host;             /* wall clock of the whole call, host view included */
+    float reserved;
+    uint64_t n_alns;           /* records = the source's count */
+    uint64_t n_slots;          /* distinct source slots */
+    uint64_t n_ops_in;         /* words of the source's pool */
+    uint64_t n_ops;            /* words of this pool */
+    uint64_t n_changed;        /* slots whose words differ from the source's */
+    uint64_t n_steps;          /* steps left, summed over all runs of all slots */
+    uint64_t n_joined;         /* joins of two runs */
+    uint64_t n_pinned;         /* stops that only the first-column rule caused (a run that joins another may stop twice) */
+} spm_jst_normalize_stats;
+
+int spm_hip_jst_ref_alns_normalize(spm_jst_ref_alns *a, uint32_t flags, spm_jst_ref_alns **out);
+int spm_hip_jst_ref_alns_normalize_stats(const spm_jst_ref_alns *a, spm_jst_normalize_stats *out);
 
 /* ---- selection of pan-genome hits: one record per haplotype locus, the best stratum per (haplotype, needle) -------------
  * spm_hip_hits_select for the 24-byte records of spm_hip_jst_search.  The locus is (haplotype, pattern).  For a record

@@ -197,6 +197,27 @@ class JstCollapseStats(C.Structure):
     ]
 
 
+class JstNormalizeStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_slots", C.c_float),
+        ("ms_normalize", C.c_float),
+        ("ms_offsets", C.c_float),
+        ("ms_gather", C.c_float),
+        ("ms_compact", C.c_float),
+        ("ms_host", C.c_float),
+        ("reserved", C.c_float),
+        ("n_alns", C.c_uint64),
+        ("n_slots", C.c_uint64),
+        ("n_ops_in", C.c_uint64),
+        ("n_ops", C.c_uint64),
+        ("n_changed", C.c_uint64),
+        ("n_steps", C.c_uint64),
+        ("n_joined", C.c_uint64),
+        ("n_pinned", C.c_uint64),
+    ]
+
+
 ALIGN_BEGIN_ONLY = 1
 
 
@@ -324,6 +345,8 @@ def lib():
                                                   C.POINTER(C.c_uint64)]),
         "spm_hip_jst_ref_alns_stats": (C.c_int, [vp, C.POINTER(JstProjectStats)]),
         "spm_hip_jst_ref_alns_destroy": (None, [vp]),
+        "spm_hip_jst_ref_alns_normalize": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_ref_alns_normalize_stats": (C.c_int, [vp, C.POINTER(JstNormalizeStats)]),
         "spm_hip_jst_ref_alns_collapse": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
         "spm_hip_jst_ref_loci_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRefLocus)), C.POINTER(C.c_uint64), C.POINTER(u32p),
                                                 C.POINTER(C.c_uint64), C.POINTER(u32p), C.POINTER(C.POINTER(C.c_int32)),
@@ -375,6 +398,7 @@ EXPORTS = [
     "spm_hip_jst_alns_destroy",
     "spm_hip_jst_alns_project", "spm_hip_jst_ref_alns_view", "spm_hip_jst_ref_alns_device", "spm_hip_jst_ref_alns_stats",
     "spm_hip_jst_ref_alns_destroy",
+    "spm_hip_jst_ref_alns_normalize", "spm_hip_jst_ref_alns_normalize_stats",
     "spm_hip_jst_ref_alns_collapse", "spm_hip_jst_ref_loci_view", "spm_hip_jst_ref_loci_device", "spm_hip_jst_ref_loci_map",
     "spm_hip_jst_ref_loci_stats", "spm_hip_jst_ref_loci_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",

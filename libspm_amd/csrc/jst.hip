@@ -6,4 +6,5 @@
 #include "jst_locate.hpp"
 #include "transcript_slots.hpp"
 #include "jst_project.hpp"
+#include "jst_normalize.hpp"
 #include "jst_collapse.hpp"

@@ -207,6 +207,12 @@ struct spm_jst_ref_alns
     spm_jst_project_stats stats{};
     uint32_t n_patterns = 0; // what spm_hip_jst_ref_alns_collapse plans its keys from: the needles of the set ...
     uint64_t n_ref = 0;      // ... and the reference length (the collapse reads neither tree nor set)
+    // what spm_hip_jst_ref_alns_normalize reads: the tree (its reference text) and the needle set behind these records --
+    // host bookkeeping only; both must be alive during that call, not after it
+    spm_jst *jst = nullptr;
+    const spm_patterns *patterns = nullptr;
+    bool normalized = false; // made by spm_hip_jst_ref_alns_normalize, which then filled norm_stats
+    spm_jst_normalize_stats norm_stats{};
 };
 
 extern "C" void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a)
@@ -259,6 +265,8 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
     R->stats.n_alns = n;
     R->n_patterns = ps->n;
     R->n_ref = J->ref->n;
+    R->jst = J;
+    R->patterns = ps;
     hipStream_t st = ctx->stream;
     float ms_rep = 0, ms_count = 0, ms_emit = 0, ms_gather = 0;
     uint64_t n_slots = 0;

@@ -1,7 +1,7 @@
 // transcript_slots.hpp -- the distinct transcript slots of a "records + CIGAR pool" object, numbered in pool order.  gfx950.
-// Included by jst.hip ahead of jst_project.hpp and jst_collapse.hpp, which both begin with this stage: the collapse is right
-// only if it numbers the slots of the projection's records the way the projection numbered its own, so the stage is written
-// once.
+// Included by jst.hip ahead of jst_project.hpp, jst_normalize.hpp and jst_collapse.hpp, which all begin with this stage: the
+// collapse is right only if it numbers the slots of the projection's records the way the projection numbered its own, so the
+// stage is written once.
 //   slot_rep_kernel      one lane per record: atomicMin of the record index into rep[cigar_off] -- the smallest record index
 //                        represents its slot; a record its caller's predicate calls unusable is counted, not entered
 //   (hipcub exclusive sum of rep[w] != none over the pool: the number of every slot, in pool order)

@@ -638,13 +638,18 @@ class JstAlignments(_RecordPool):
             raise capi.SpmError("JstAlignments.project: the tree or the needle set of these alignments has been closed")
         r = C.c_void_p()
         self._call("project", 0, C.byref(r))
-        return JstRefAlignments(self.ctx, r)
+        return JstRefAlignments(self.ctx, r, self._jst, self._pats)
 
 
 class JstRefAlignments(_RecordPool):
     """Result of JstAlignments.project(): JST_REF_ALN_DTYPE records matched to the source's records, and the pool of CIGAR
     words (len << 4 | op) against the reference -- one transcript per distinct transcript slot of the source."""
     _PREFIX, _REC, _DTYPE, _STATS = "jst_ref_alns", capi.JstRefAln, JST_REF_ALN_DTYPE, capi.JstProjectStats
+
+    def __init__(self, ctx, h, jst=None, pats=None):
+        # the tree and the needle set behind these records: normalize() reads the reference text and the needles
+        super().__init__(ctx, h)
+        self._jst, self._pats = jst, pats
 
     def device(self):
         """(records, n, ops, n_ops): device pointers; record i matched to record i of the source's device()."""
@@ -656,6 +661,24 @@ class JstRefAlignments(_RecordPool):
 
     def stats(self) -> capi.JstProjectStats:
         return self._stats()
+
+    def normalize(self) -> "JstRefAlignments":
+        """These records with every indel at its leftmost equivalent place (spm_hip_jst_ref_alns_normalize): the same
+        records in the same order, every field but cigar_off / cigar_len unchanged, one transcript per distinct slot.
+        collapse() of the result merges the haplotypes that differ only in which copy of a repeat an indel touches.  The
+        tree and the needle set must be open during the call (the tree may have been indexed again); the result stays
+        valid after they and this object are closed."""
+        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
+            raise capi.SpmError("JstRefAlignments.normalize: the tree or the needle set of these alignments has been closed")
+        r = C.c_void_p()
+        self._call("normalize", 0, C.byref(r))
+        return JstRefAlignments(self.ctx, r, self._jst, self._pats)
+
+    def normalize_stats(self) -> capi.JstNormalizeStats:
+        """Stage times and counts of the normalize() call that made this object (an error for any other)."""
+        s = capi.JstNormalizeStats()
+        self._call("normalize_stats", C.byref(s))
+        return s
 
     def collapse(self) -> "JstRefLoci":
         """One record per distinct reference alignment (spm_hip_jst_ref_alns_collapse): records that agree in needle,
