@@ -79,6 +79,24 @@ struct jst_ref_locus
     bool operator==(jst_ref_locus const &) const noexcept = default;
 };
 
+// what a mapper reports per read (journaled_sequence_tree::locate_reads; spm_jst_read in spm_hip.h): where the read's loci
+// stand in the loci vector, how many it has on which strand, the primary one -- smallest (haplotype_errors, index) -- and how
+// many share the best and the next stratum
+struct jst_read
+{
+    std::uint32_t first_locus, n_loci, n_forward, primary;
+    std::int32_t best, best_ref_score;
+    std::uint32_t n_best, n_next;
+    bool operator==(jst_read const &) const noexcept = default;
+};
+
+struct jst_read_loci
+{
+    std::vector<jst_ref_locus> loci; // of locate_reference_loci_normalized
+    std::vector<jst_read> reads;     // one per read, in read order
+    bool operator==(jst_read_loci const &) const noexcept = default;
+};
+
 struct jst_search_stats
 {
     std::uint64_t haplotype_symbols{}; // sum of haplotype lengths (what per-haplotype scans would read)
@@ -346,8 +364,7 @@ public:
         spm_ctx * ctx = hip::default_context();
         spm_jst_hits * hh = device_search(needles, window, block, 0, stats);
         spm_select_opts o{};
-        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
-                  (selection.across ? SPM_SELECT_ACROSS : 0u);
+        o.flags = hip::select_flags(selection, true);
         o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
         o.strata = selection.strata.value_or(0u);
         spm_jst_hits * sel = nullptr;
@@ -374,16 +391,22 @@ public:
     {
         if (selection.across && !selection.strata)
             hip::fatal("journaled_sequence_tree::search (hit_selection::across needs strata)", hip::default_context());
+        if (selection.strands && !selection.strata)
+            hip::fatal("journaled_sequence_tree::search (hit_selection::strands needs strata)", hip::default_context());
+        std::uint32_t const shift = selection.strands ? 1u : 0u; // the minimum's unit: the needle, or the read = needle >> 1
         std::sort(hits.begin(), hits.end(), [](jst_hit const & a, jst_hit const & b) {
             return std::tuple{a.haplotype, a.needle, a.position} < std::tuple{b.haplotype, b.needle, b.position};
         });
         auto const same = [&](std::size_t i, std::size_t j) {
             return hits[i].haplotype == hits[j].haplotype && hits[i].needle == hits[j].needle;
         };
-        std::vector<std::int64_t> best(selection.across ? needle_len.size() : hits.size(), INT64_MAX); // per needle / group head
+        auto const same_unit = [&](std::size_t i, std::size_t j) {
+            return hits[i].haplotype == hits[j].haplotype && hits[i].needle >> shift == hits[j].needle >> shift;
+        };
+        std::vector<std::int64_t> best(selection.across ? needle_len.size() : hits.size(), INT64_MAX); // per unit / group head
         std::vector<std::size_t> slot(hits.size());
         for (std::size_t i = 0; i < hits.size(); ++i) {
-            slot[i] = selection.across ? hits[i].needle : i && same(i, i - 1) ? slot[i - 1] : i;
+            slot[i] = selection.across ? hits[i].needle >> shift : i && same_unit(i, i - 1) ? slot[i - 1] : i;
             best[slot[i]] = std::min<std::int64_t>(best[slot[i]], hits[i].errors);
         }
         std::vector<jst_hit> out;
@@ -719,6 +742,68 @@ public:
         return collapse_host(locate_reference_normalized_host(needles, window, needle_ranks, reports_begin, selection, block, stats));
     }
 
+    // ---- the normalised loci of a selection and, per read, their summary (the contract of spm_hip_jst_ref_loci_reads in
+    // spm_hip.h).  strands: 2 for needles compiled with both_strands (read = needle >> 1), else 1.  Device route: the
+    // normalised-loci chain plus spm_hip_jst_ref_loci_reads.  Host route: the host loci and a plain loop.  Both return the same.
+    jst_read_loci locate_reads(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                               bool reports_begin, std::uint32_t strands, std::uint32_t n_reads,
+                               hip::hit_selection const & selection, std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_reads_device(needles, window, strands, n_reads, selection, block, stats);
+        return locate_reads_host(needles, window, needle_ranks, reports_begin, strands, n_reads, selection, block, stats);
+    }
+
+    jst_read_loci locate_reads_device(spm_patterns * needles, std::size_t window, std::uint32_t strands, std::uint32_t n_reads,
+                                      hip::hit_selection const & selection, std::size_t block = 0,
+                                      jst_search_stats * stats = nullptr) const
+    {
+        jst_read_loci out;
+        out.loci = loci_of(device_alns(needles, window, selection, block, stats).get(), true, strands, n_reads, &out.reads);
+        return out;
+    }
+
+    jst_read_loci locate_reads_host(spm_patterns * needles, std::size_t window,
+                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                    std::uint32_t strands, std::uint32_t n_reads, hip::hit_selection const & selection,
+                                    std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        jst_read_loci out;
+        out.loci = locate_reference_loci_normalized_host(needles, window, needle_ranks, reports_begin, selection, block, stats);
+        out.reads = reads_host(out.loci, strands, n_reads);
+        return out;
+    }
+
+    // the summary as a plain loop over loci in their order (needle first: the loci of a read are contiguous)
+    static std::vector<jst_read> reads_host(std::vector<jst_ref_locus> const & loci, std::uint32_t strands, std::uint32_t n_reads)
+    {
+        if (strands != 1 && strands != 2)
+            hip::fatal("journaled_sequence_tree::locate_reads (strands is 1 or 2)", hip::default_context());
+        std::vector<jst_read> out;
+        std::size_t i = 0;
+        for (std::uint32_t r = 0; r < n_reads; ++r) {
+            jst_read R{static_cast<std::uint32_t>(i), 0, 0, 0xFFFFFFFFu, -1, -1, 0, 0};
+            std::size_t const lo = i;
+            for (; i < loci.size() && loci[i].needle / strands == r; ++i) {
+                R.n_loci += 1;
+                R.n_forward += loci[i].needle % strands == 0;
+                if (R.primary == 0xFFFFFFFFu || loci[i].haplotype_errors < R.best) {
+                    R.primary = static_cast<std::uint32_t>(i);
+                    R.best = loci[i].haplotype_errors;
+                    R.best_ref_score = loci[i].aln.errors();
+                }
+            }
+            for (std::size_t j = lo; j < i; ++j) {
+                R.n_best += loci[j].haplotype_errors == R.best;
+                R.n_next += static_cast<std::int64_t>(loci[j].haplotype_errors) == static_cast<std::int64_t>(R.best) + 1;
+            }
+            out.push_back(R);
+        }
+        if (i != loci.size())
+            hip::fatal("journaled_sequence_tree::locate_reads (a locus names a needle outside the reads)", hip::default_context());
+        return out;
+    }
+
     // The normalisation on the host, in column form: one op per column, a gap run moved one step at a time by the rule of
     // spm_hip.h.  i and r -- the needle symbols and reference positions the columns before the run consume -- are counted
     // anew for every step.
@@ -935,8 +1020,7 @@ private:
         spm_ctx * ctx = hip::default_context();
         spm_jst_hits * hh = device_search(needles, window, block, 0, stats); // (need not be alignable)
         spm_select_opts o{};
-        o.flags = (selection.loci ? SPM_SELECT_LOCI : 0u) | (selection.strata ? SPM_SELECT_BEST : 0u) |
-                  (selection.across ? SPM_SELECT_ACROSS : 0u);
+        o.flags = hip::select_flags(selection, true);
         o.window = selection.window.value_or(SPM_SELECT_WINDOW_K);
         o.strata = selection.strata.value_or(0u);
         spm_jst_hits * sel = nullptr;
@@ -1017,7 +1101,9 @@ private:
     }
 
     // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
-    static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false)
+    // ... and, where asked for, the summary of n_reads reads over them (spm_hip_jst_ref_loci_reads)
+    static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false, std::uint32_t strands = 1,
+                                              std::uint32_t n_reads = 0, std::vector<jst_read> * reads = nullptr)
     {
         spm_ctx * ctx = hip::default_context();
         spm_jst_ref_alns * r = projected(a, normalized);
@@ -1043,6 +1129,20 @@ private:
             for (std::uint32_t m = 0; m < rec[i].n_haplotypes; ++m)
                 x.members.emplace_back(members[rec[i].member_off + m], scores[rec[i].member_off + m]);
             out.push_back(std::move(x));
+        }
+        if (reads != nullptr) {
+            spm_jst_reads * rd = nullptr;
+            if (spm_hip_jst_ref_loci_reads(l, strands, n_reads, 0, &rd) != SPM_OK)
+                hip::fatal("spm_hip_jst_ref_loci_reads", ctx);
+            std::unique_ptr<spm_jst_reads, decltype(&spm_hip_jst_reads_destroy)> rd_owner{rd, &spm_hip_jst_reads_destroy};
+            spm_jst_read const * rr = nullptr;
+            std::uint64_t nr = 0;
+            if (spm_hip_jst_reads_view(rd, &rr, &nr) != SPM_OK)
+                hip::fatal("spm_hip_jst_reads_view", ctx);
+            reads->clear();
+            for (std::uint64_t i = 0; i < nr; ++i)
+                reads->push_back({rr[i].first_locus, rr[i].n_loci, rr[i].n_forward, rr[i].primary, rr[i].best,
+                                  rr[i].best_ref_score, rr[i].n_best, rr[i].n_next});
         }
         return out;
     }

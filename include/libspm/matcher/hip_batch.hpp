@@ -41,6 +41,24 @@ public:
         build(needles, max_error_counts);
     }
 
+    // n READS searched on both strands: size() is 2n, callbacks report needle_index = 2 * read + strand
+    // (hip::read_of / hip::strand_of), needle 2r + 1 is the reverse complement of read r and shares its max_error_count
+    template <std::ranges::input_range needles_t>
+        requires std::ranges::input_range<std::ranges::range_reference_t<needles_t>>
+    batch_matcher(hip::both_strands_t, needles_t && reads, std::size_t max_error_count = 0)
+    {
+        std::vector<std::uint16_t> ks;
+        for ([[maybe_unused]] auto && n : reads)
+            ks.push_back(static_cast<std::uint16_t>(max_error_count));
+        build(reads, ks, true);
+    }
+    template <std::ranges::input_range needles_t>
+        requires std::ranges::input_range<std::ranges::range_reference_t<needles_t>>
+    batch_matcher(hip::both_strands_t, needles_t && reads, std::vector<std::uint16_t> max_error_counts)
+    {
+        build(reads, max_error_counts, true);
+    }
+
     std::size_t size() const noexcept { return _lengths.size(); }
     bool filterable() const noexcept { return spm_hip_patterns_filterable(_patterns.get()) != 0; }
 
@@ -220,7 +238,7 @@ private:
 
 private:
     template <typename needles_t>
-    void build(needles_t && needles, std::vector<std::uint16_t> const & ks)
+    void build(needles_t && needles, std::vector<std::uint16_t> const & ks, bool stranded = false)
     {
         std::vector<std::uint8_t> cat;
         std::vector<std::uint32_t> offsets{0};
@@ -236,10 +254,21 @@ private:
         _errors.resize(_lengths.size(), 0);
         spm_patterns * p = nullptr;
         std::uint8_t const dummy = 0;
-        if (spm_hip_patterns_create(hip::default_context(), algo_v, cat.empty() ? &dummy : cat.data(), offsets.data(),
-                                    static_cast<std::uint32_t>(_lengths.size()), _errors.data(), _sigma, &p) != SPM_OK)
-            hip::fatal("spm_hip_patterns_create", hip::default_context());
+        auto const create = stranded ? spm_hip_patterns_create_stranded : spm_hip_patterns_create;
+        if (create(hip::default_context(), algo_v, cat.empty() ? &dummy : cat.data(), offsets.data(),
+                   static_cast<std::uint32_t>(_lengths.size()), _errors.data(), _sigma, &p) != SPM_OK)
+            hip::fatal(stranded ? "spm_hip_patterns_create_stranded" : "spm_hip_patterns_create", hip::default_context());
         _patterns = hip::patterns_ptr{p, hip::patterns_deleter{}};
+        if (stranded) { // needle 2r and 2r + 1 have read r's length and errors
+            std::vector<std::uint32_t> lengths;
+            std::vector<std::uint16_t> errors;
+            for (std::size_t r = 0; r < _lengths.size(); ++r) {
+                lengths.insert(lengths.end(), 2, _lengths[r]);
+                errors.insert(errors.end(), 2, _errors[r]);
+            }
+            _lengths = std::move(lengths);
+            _errors = std::move(errors);
+        }
     }
 
     constexpr friend std::size_t tag_invoke(std::tag_t<window_size>, batch_matcher const & me) noexcept

@@ -136,13 +136,56 @@ struct hit_selection
     std::optional<std::uint32_t> window{};
     std::optional<std::uint32_t> strata{};
     bool across{false};
+    bool strands{false}; // SPM_SELECT_STRANDS: the needles are reads on both strands (both_strands); best per READ; needs `strata`
 };
+
+// the SPM_SELECT_* bits of a selection; `pan_genome`: the call takes SPM_SELECT_ACROSS
+inline std::uint32_t select_flags(hit_selection const & sel, bool pan_genome) noexcept
+{
+    return (sel.loci ? SPM_SELECT_LOCI : 0u) | (sel.strata ? SPM_SELECT_BEST : 0u) |
+           (pan_genome && sel.across ? SPM_SELECT_ACROSS : 0u) | (sel.strands ? SPM_SELECT_STRANDS : 0u);
+}
+
+// ---- reads on both strands.  batch_matcher{both_strands, reads, k} compiles n reads into 2n needles
+// (spm_hip_patterns_create_stranded): needle 2r is read r, needle 2r + 1 its reverse complement, both with read r's k.
+struct both_strands_t
+{
+    explicit both_strands_t() = default;
+};
+inline constexpr both_strands_t both_strands{};
+constexpr std::size_t read_of(std::size_t needle_index) noexcept { return needle_index >> 1; }
+constexpr std::size_t strand_of(std::size_t needle_index) noexcept { return needle_index & 1; } // 0 forward, 1 reverse
+
+// complement by rank (dna4 ACGT, dna5 ACGNT, dna15 ABCDGHKMNRSTVWY): what the library applies to a stranded set
+inline std::uint8_t complement_rank(std::uint32_t sigma, std::uint8_t r) noexcept
+{
+    static constexpr std::uint8_t c5[5] = {4, 2, 1, 3, 0};
+    static constexpr std::uint8_t c15[15] = {11, 12, 4, 5, 2, 3, 7, 6, 8, 14, 10, 0, 1, 13, 9};
+    if (r >= sigma)
+        return r;
+    return sigma == 4 ? static_cast<std::uint8_t>(3 - r) : sigma == 5 ? c5[r] : c15[r];
+}
+
+// the reverse complement of a range over spm::dna4, dna5 or dna15, as a vector of the same symbols
+template <std::ranges::input_range range_t>
+    requires requires { std::ranges::range_value_t<range_t>::alphabet_size; }
+std::vector<std::ranges::range_value_t<range_t>> reverse_complement(range_t && sequence)
+{
+    using symbol_t = std::ranges::range_value_t<range_t>;
+    constexpr std::uint32_t sigma = static_cast<std::uint32_t>(symbol_t::alphabet_size);
+    static_assert(sigma == 4 || sigma == 5 || sigma == 15, "a complement is defined for dna4, dna5 and dna15");
+    std::vector<symbol_t> out;
+    for (auto && s : sequence)
+        out.push_back(symbol_t{complement_rank(sigma, spm::detail::rank_byte(s))});
+    std::reverse(out.begin(), out.end());
+    return out;
+}
 
 // the selected hits of a completed scan in callback order; failures are fatal like every other call of the mirror
 inline hits_ptr select_hits(spm_ctx * ctx, spm_hits * hits, hit_selection const & sel, spm_hit const *& rec, std::uint64_t & n) noexcept
 {
     spm_select_opts o{};
-    o.flags = (sel.loci ? SPM_SELECT_LOCI : 0u) | (sel.strata ? SPM_SELECT_BEST : 0u);
+    o.flags = select_flags(sel, false);
     o.window = sel.window.value_or(SPM_SELECT_WINDOW_K);
     o.strata = sel.strata.value_or(0u);
     spm_hits * s = nullptr;

@@ -167,6 +167,24 @@ uint64_t spm_hip_patterns_window_size(const spm_patterns *p, uint32_t pattern);
 /* 1 if the set admits the lossless seed filter (dna4, every needle long enough for its k). */
 int spm_hip_patterns_filterable(const spm_patterns *p);
 
+/* ---- stranded needle sets: n reads searched on both strands ---------------------------------------------------------
+ * The arguments of spm_hip_patterns_create, read as n_reads READS.  The result is an ordinary set of 2 * n_reads needles:
+ * pattern 2r is read r, pattern 2r + 1 its reverse complement, both with k[r].  The interleaving is the contract --
+ * read = pattern >> 1, strand = pattern & 1 -- and every other call (window_size, state blobs, scan, segments, the pan-genome
+ * search, align, project, normalise, collapse) sees nothing but 2n needles.  The CIGAR of the reverse-complement needle
+ * against the forward text is what SAM stores for a reverse-strand read.
+ *   * Complement by rank: dna4 ACGT 3 - r; dna5 ACGNT {4,2,1,3,0}; dna15 ABCDGHKMNRSTVWY {11,12,4,5,2,3,7,6,8,14,10,0,1,13,9}.
+ *     A rank >= sigma (it matches nothing) is kept as it is, at its mirrored place.  Any other sigma: SPM_E_UNSUPPORTED.
+ *   * 2 * n_reads, or twice the summed lengths, above 2^32 - 1: SPM_E_UNSUPPORTED, decided before any allocation.
+ *   * All four algo values are accepted. */
+int spm_hip_patterns_create_stranded(spm_ctx *ctx, int algo, const uint8_t *ranks_concat, const uint32_t *offsets,
+                                     uint32_t n_reads, const uint16_t *k, uint32_t sigma, spm_patterns **out);
+uint32_t spm_hip_patterns_strands(const spm_patterns *p);   /* 1, or 2 for a stranded set */
+uint32_t spm_hip_patterns_count(const spm_patterns *p);     /* needles in the set (2 * n_reads when stranded) */
+/* The symbols of needle `pattern`, copied from the set's host copy: SAM SEQ of a reverse-strand hit.  Any set.  *len is
+ * always written (0 for a pattern outside the set, which is SPM_E_INVALID); cap < *len is SPM_E_INVALID and copies nothing. */
+int spm_hip_patterns_needle(const spm_patterns *p, uint32_t pattern, uint8_t *out, uint32_t cap, uint32_t *len);
+
 /* What spm_hip_patterns_create spent where (host wall clock, ms) and what it built.  The reference's constructors are
  * O(|P|) per needle (myers_matcher.hpp:40-43); a set of 100 000 needles is built by `threads` host threads here
  * (SPM_HIP_BUILD_THREADS; default: the hardware concurrency, at most 16). */
@@ -307,6 +325,12 @@ void spm_hip_alns_destroy(spm_alns *a);
  *                     taken over that pattern's INPUT records, over the whole result (not per segment).  LOCI never removes
  *                     a pattern's minimum -- the leftmost minimal record inside its window always survives -- so the minimum
  *                     before LOCI is the minimum after it.
+ *   SPM_SELECT_STRANDS  with BEST, for stranded needle sets (spm_hip_patterns_create_stranded): the minimum is taken per READ =
+ *                     pattern >> 1, over the input records of both its patterns.  "A perfect forward hit beats a 3-error
+ *                     reverse hit elsewhere."  LOCI is unchanged: records of different patterns never see each other, so a
+ *                     palindromic read yields two records per place, and both stay.  Without BEST: SPM_E_INVALID.  With a
+ *                     needle set at hand (the scan's, or patterns != NULL) that is not stranded: SPM_E_INVALID; a raw buffer
+ *                     with patterns == NULL is taken by the index convention.  Order, views, stats, re-selection: as ever.
  *   neither flag      a sorted copy.
  * The result is a new spm_hits with a hit block of its own.  BOTH its host view and its device view are in (pattern, pos)
  * order (positions compare as in spm_hip_hits_view) -- the one device view with a defined order.  It copies the source's
@@ -322,6 +346,7 @@ void spm_hip_alns_destroy(spm_alns *a);
  * sharding of the multi-GPU exchange below the order is: gatherv first, spm_hip_records_select on the root second. */
 #define SPM_SELECT_LOCI 1u
 #define SPM_SELECT_BEST 2u
+#define SPM_SELECT_STRANDS 8u   /* with SPM_SELECT_BEST: the minimum is taken per READ = pattern >> 1, over both strands */
 #define SPM_SELECT_WINDOW_K 0xFFFFFFFFu
 typedef struct spm_select_opts {
     uint32_t flags;    /* SPM_SELECT_* */
@@ -688,6 +713,43 @@ int spm_hip_jst_ref_loci_map(spm_jst_ref_loci *l, const uint32_t **host_map, con
 int spm_hip_jst_ref_loci_stats(const spm_jst_ref_loci *l, spm_jst_collapse_stats *out);
 void spm_hip_jst_ref_loci_destroy(spm_jst_ref_loci *l);
 
+/* ---- the loci of every read: what a mapper reports per read ----------------------------------------------------------------
+ * One spm_jst_read per read 0 .. n_reads - 1, in read order, from the loci of a collapse.  strands says how patterns name
+ * reads: read = pattern / strands (2: a stranded set, forward = pattern 2r; 1: a plain set, every locus is forward).  The loci
+ * of a read are contiguous in the loci order, forward before reverse, leftmost first, and the PRIMARY locus is the one with
+ * the smallest (score, locus index).  MAPQ is a policy over (n_best, n_next) and is deliberately not computed.
+ * The result is a pure function of the loci records: byte-identical across runs, host and device view alike.  It outlives
+ * the loci handle.
+ *   * SPM_E_INVALID: strands not 1 or 2, flags != 0, NULL arguments, strands * n_reads above 2^32 - 1.
+ *   * A locus whose pattern is >= strands * n_reads (or whose score is negative) is COUNTED on the device and fails the whole
+ *     call with SPM_E_INVALID, never a fault.
+ *   * No loci: every read unmapped.  n_reads == 0: an empty result.  Both SPM_OK. */
+typedef struct spm_jst_read {        /* 32 bytes */
+    uint32_t first_locus;            /* index of the read's first locus in the loci order; no loci: where it would stand */
+    uint32_t n_loci;                 /* loci of the read, both strands (they are contiguous: patterns strands * r ..) */
+    uint32_t n_forward;              /* of those, on pattern strands * r */
+    uint32_t primary;                /* the locus with the smallest (score, locus index); 0xFFFFFFFF: unmapped */
+    int32_t best;                    /* its score (haplotype distance); -1 unmapped */
+    int32_t best_ref_score;          /* its ref_score (SAM NM); -1 unmapped */
+    uint32_t n_best;                 /* loci of the read with score == best */
+    uint32_t n_next;                 /* ... with score == best + 1 */
+} spm_jst_read;
+typedef struct spm_jst_reads spm_jst_reads;
+typedef struct spm_jst_reads_stats { /* 48 bytes */
+    float ms_total;                  /* device: the three passes (HIP events) */
+    float ms_host;                   /* wall clock of the whole call, host view included */
+    uint64_t n_reads;
+    uint64_t n_loci;
+    uint64_t n_mapped;               /* reads with at least one locus */
+    uint64_t n_unique;               /* reads with n_best == 1 */
+    uint64_t n_multi;                /* reads with n_best > 1 */
+} spm_jst_reads_stats;
+int spm_hip_jst_ref_loci_reads(spm_jst_ref_loci *l, uint32_t strands, uint32_t n_reads, uint32_t flags, spm_jst_reads **out);
+int spm_hip_jst_reads_view(spm_jst_reads *r, const spm_jst_read **records, uint64_t *n);
+int spm_hip_jst_reads_device(spm_jst_reads *r, const void **records, uint64_t *n);
+int spm_hip_jst_reads_stats(const spm_jst_reads *r, spm_jst_reads_stats *out);
+void spm_hip_jst_reads_destroy(spm_jst_reads *r);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps
@@ -775,6 +837,9 @@ int spm_hip_jst_ref_alns_normalize_stats(const spm_jst_ref_alns *a, spm_jst_norm
  *                      (haplotype, pattern) ...
  *   SPM_SELECT_ACROSS  ... or, with this flag, over the input records of the same pattern on ALL haplotypes ("the best place
  *                      of this read anywhere in the pan-genome").  ACROSS without BEST is SPM_E_INVALID.
+ *   SPM_SELECT_STRANDS with BEST: the minimum's pattern becomes the READ = pattern >> 1 -- over (haplotype, read), or with
+ *                      ACROSS over the read on all haplotypes.  Refusals as in spm_hip_hits_select (the strands of a search's
+ *                      needle set are remembered by its result and by every selection of it).  LOCI is unchanged.
  *   neither flag       a sorted copy.
  * Without ACROSS the records of haplotype h in the result are exactly what spm_hip_scan + spm_hip_hits_select with the same
  * opts return on the materialised haplotype h.  The rule reads only the SET of records: the result is bit-identical across

@@ -197,6 +197,23 @@ class JstCollapseStats(C.Structure):
     ]
 
 
+class JstRead(C.Structure):
+    _fields_ = [("first_locus", C.c_uint32), ("n_loci", C.c_uint32), ("n_forward", C.c_uint32), ("primary", C.c_uint32),
+                ("best", C.c_int32), ("best_ref_score", C.c_int32), ("n_best", C.c_uint32), ("n_next", C.c_uint32)]
+
+
+class JstReadsStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_reads", C.c_uint64),
+        ("n_loci", C.c_uint64),
+        ("n_mapped", C.c_uint64),
+        ("n_unique", C.c_uint64),
+        ("n_multi", C.c_uint64),
+    ]
+
+
 class JstNormalizeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -241,6 +258,7 @@ class SelectStats(C.Structure):
 
 SELECT_LOCI, SELECT_BEST = 1, 2
 SELECT_ACROSS = 4   # pan-genome selections only, with SELECT_BEST
+SELECT_STRANDS = 8  # with SELECT_BEST: the minimum is taken per read = pattern >> 1, over both strands of a stranded set
 SELECT_WINDOW_K = 0xFFFFFFFF
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
 
@@ -284,6 +302,10 @@ def lib():
         "spm_hip_text_device_ptr": (vp, [vp]),
         "spm_hip_text_destroy": (None, [vp]),
         "spm_hip_patterns_create": (C.c_int, [vp, C.c_int, u8p, u32p, C.c_uint32, u16p, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_patterns_create_stranded": (C.c_int, [vp, C.c_int, u8p, u32p, C.c_uint32, u16p, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_patterns_strands": (C.c_uint32, [vp]),
+        "spm_hip_patterns_count": (C.c_uint32, [vp]),
+        "spm_hip_patterns_needle": (C.c_int, [vp, C.c_uint32, u8p, C.c_uint32, u32p]),
         "spm_hip_patterns_destroy": (None, [vp]),
         "spm_hip_patterns_window_size": (C.c_uint64, [vp, C.c_uint32]),
         "spm_hip_patterns_filterable": (C.c_int, [vp]),
@@ -356,6 +378,11 @@ def lib():
         "spm_hip_jst_ref_loci_map": (C.c_int, [vp, C.POINTER(u32p), C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_ref_loci_stats": (C.c_int, [vp, C.POINTER(JstCollapseStats)]),
         "spm_hip_jst_ref_loci_destroy": (None, [vp]),
+        "spm_hip_jst_ref_loci_reads": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+        "spm_hip_jst_reads_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRead)), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_reads_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_reads_stats": (C.c_int, [vp, C.POINTER(JstReadsStats)]),
+        "spm_hip_jst_reads_destroy": (None, [vp]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -384,6 +411,7 @@ EXPORTS = [
     "spm_hip_text_wrap", "spm_hip_text_generate", "spm_hip_text_generate_repeats", "spm_hip_text_pack", "spm_hip_text_is_packed",
     "spm_hip_text_download", "spm_hip_text_length",
     "spm_hip_text_device_ptr", "spm_hip_text_destroy", "spm_hip_patterns_create", "spm_hip_patterns_destroy",
+    "spm_hip_patterns_create_stranded", "spm_hip_patterns_strands", "spm_hip_patterns_count", "spm_hip_patterns_needle",
     "spm_hip_patterns_window_size", "spm_hip_patterns_filterable", "spm_hip_patterns_build_stats", "spm_hip_patterns_state_stride",
     "spm_hip_patterns_state_init", "spm_hip_scan", "spm_hip_scan_segments", "spm_hip_hits_view", "spm_hip_hits_device",
     "spm_hip_hits_copy_device", "spm_hip_hits_copy_fused", "spm_hip_hits_copy_fused_device", "spm_hip_hits_stats", "spm_hip_hits_checksum", "spm_hip_hits_destroy",
@@ -401,6 +429,8 @@ EXPORTS = [
     "spm_hip_jst_ref_alns_normalize", "spm_hip_jst_ref_alns_normalize_stats",
     "spm_hip_jst_ref_alns_collapse", "spm_hip_jst_ref_loci_view", "spm_hip_jst_ref_loci_device", "spm_hip_jst_ref_loci_map",
     "spm_hip_jst_ref_loci_stats", "spm_hip_jst_ref_loci_destroy",
+    "spm_hip_jst_ref_loci_reads", "spm_hip_jst_reads_view", "spm_hip_jst_reads_device", "spm_hip_jst_reads_stats",
+    "spm_hip_jst_reads_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

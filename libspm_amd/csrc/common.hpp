@@ -135,6 +135,7 @@ struct spm_jst_hits // (jst.hip: searches; jst_select.hip: selections)
     bool alignable = false;
     spm_jst *jst = nullptr;
     const struct spm_patterns *patterns = nullptr;
+    uint32_t pat_strands = 0; // the set's strands as the search found them (the set may be gone when a selection asks); 0: no set
     uint64_t generation = 0;
     spm_hits *seg = nullptr; // the search's segment hits, owned (nullptr: the search had nothing to scan)
     // what a selection plans its sort key from: set by the search (the tree's bounds), or by the range kernel of

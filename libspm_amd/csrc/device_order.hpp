@@ -1,6 +1,6 @@
 // device_order.hpp -- the host side of "order the records, then compact them", written once for the drivers that do it
 // (select.hip, jst_select.hip, jst_locate.hpp, transcript_slots.hpp -- the slot stage of jst_project.hpp, jst_normalize.hpp and
-// jst_collapse.hpp -- and those three): the hipcub radix sort of (64-bit key, 32-bit index) pairs over the key's low bits, the hipcub exclusive sum
+// jst_collapse.hpp -- those three, and jst_reads.hpp): the hipcub radix sort of (64-bit key, 32-bit index) pairs over the key's low bits, the hipcub exclusive sum
 // over any input iterator, the read-back of a call's counts, and the events a call times its stages with.  HIP, host code only: hipcub instantiates for the callers' own iterator types what
 // a direct call would.  Every function returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
 #pragma once

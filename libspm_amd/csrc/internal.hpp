@@ -24,6 +24,7 @@ struct spm_patterns : spm_hip::seed_index // (the seed index: passes, entries, s
     spm_ctx *ctx = nullptr;
     int algo = 0;
     uint32_t n = 0;
+    uint32_t strands = 1; // 2: made by spm_hip_patterns_create_stranded -- pattern 2r is read r, 2r + 1 its reverse complement
     uint32_t sigma = 4;
     std::vector<uint8_t> ranks;
     std::vector<uint32_t> offsets;

@@ -8,3 +8,4 @@
 #include "jst_project.hpp"
 #include "jst_normalize.hpp"
 #include "jst_collapse.hpp"
+#include "jst_reads.hpp"

@@ -1156,6 +1156,7 @@ extern "C" int spm_hip_jst_search(spm_jst *J, const spm_patterns *patterns, cons
     o.flags &= ~SPM_SCAN_ALIGNABLE;
     R->jst = J;
     R->patterns = patterns;
+    R->pat_strands = patterns->strands;
     R->generation = J->generation;
     R->sel_n_hap = J->H;
     R->sel_n_patterns = std::max<uint64_t>(patterns->n, 1);

@@ -18,6 +18,7 @@ struct jsel_source // what the two entry points know about their records
     uint64_t n = 0;
     uint64_t n_hap = 1, n_patterns = 1, max_pos = 0;
     const spm_patterns *ps = nullptr; // may be null (records)
+    uint32_t strands = 0;             // of the needle set the records stem from (0: no set is known)
     spm_jst *jst = nullptr;           // the tree and index generation of the search the records stem from (records: none):
     uint64_t generation = 0;          // what spm_hip_jst_selection_align locates the kept records in
 };
@@ -38,7 +39,7 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
         return SPM_OK;
     }
     const bool numbered = plan.best && !plan.across; // minima indexed by group number: at most n groups
-    const uint64_t n_min = !plan.best ? 0 : plan.across ? S.n_patterns : (uint64_t)n;
+    const uint64_t n_min = plan.min_slots;
 
     // the scratch: keys and indices twice (the sort's in and out), scores in arrival and in sorted order, flags, offsets,
     // group numbers, minima, counts, the compacted records (their count is known only after the read-back)
@@ -76,6 +77,7 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
     P.loci = plan.loci;
     P.best = plan.best;
     P.across = plan.across;
+    P.shift = plan.strands ? 1u : 0u;
     P.window = plan.window;
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr; // (WINDOW_K: the set is alive, jsel_make)
     P.halo = plan.halo;
@@ -143,6 +145,11 @@ int jsel_make(spm_ctx *ctx, const jsel_source &S, const spm_select_opts *opts, c
         SPM_SET_ERR(ctx, "%s: %s", who, plan.why);
         return plan.status;
     }
+    if (plan.strands && S.strands != 0 && S.strands != 2) {
+        // (a raw buffer without a set is taken by the index convention: read = pattern >> 1)
+        SPM_SET_ERR(ctx, "%s: SPM_SELECT_STRANDS on a needle set that spm_hip_patterns_create_stranded did not make", who);
+        return SPM_E_INVALID;
+    }
     if (plan.across && S.n_patterns > kJselAcrossPatterns) {
         // (ACROSS keeps one minimum per pattern index; only a raw buffer without a set can name indices this large)
         SPM_SET_ERR(ctx, "%s: SPM_SELECT_ACROSS takes pattern indices below 2^24, the records name %llu", who,
@@ -156,6 +163,7 @@ int jsel_make(spm_ctx *ctx, const jsel_source &S, const spm_select_opts *opts, c
     R->patterns = S.ps;
     R->jst = S.jst;
     R->generation = S.generation;
+    R->pat_strands = S.strands;
     R->sel_n_hap = S.n_hap;
     R->sel_n_patterns = S.n_patterns;
     R->sel_max_pos = S.max_pos;
@@ -190,6 +198,7 @@ extern "C" int spm_hip_jst_hits_select(spm_jst_hits *h, const spm_select_opts *o
     S.ps = h->patterns;
     S.jst = h->jst;
     S.generation = h->generation;
+    S.strands = h->pat_strands;
     S.n_hap = std::max<uint64_t>(h->sel_n_hap, 1);
     S.n_patterns = std::max<uint64_t>(h->sel_n_patterns, 1);
     S.max_pos = h->sel_max_pos;
@@ -212,6 +221,7 @@ extern "C" int spm_hip_jst_records_select(spm_ctx *ctx, const void *device_recor
     S.d_recs = static_cast<const spm_jst_hit *>(device_records);
     S.n = n;
     S.ps = patterns;
+    S.strands = patterns ? patterns->strands : 0;
     S.n_patterns = patterns ? std::max<uint64_t>(patterns->n, 1) : 1;
     {
         // refuse what the plan refuses whatever the records hold, before anything is launched

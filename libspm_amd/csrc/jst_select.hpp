@@ -7,6 +7,8 @@
 //   jst_select_minima_kernel   BEST: the minimal score of every group, into an array indexed by the group's number (the
 //                              exclusive sum of the head flags) -- or, with ACROSS, by the pattern;
 //   jst_select_compact_kernel  the stratum test and the stable compaction of the kept records, three 8-byte words each.
+// With SPM_SELECT_STRANDS the minimum's group is group >> shift, (haplotype, read) -- or with ACROSS the read -- since the
+// strand is the group's lowest bit; LOCI's group stays (haplotype, pattern).
 // Also here: jst_select_params, the keys and range kernels, the group numbering (jsel_gid, jsel_min_slot), sel_final.
 // Staging, walks, min-scan and the flag functor are select_walk.hpp's, shared with select.hpp.
 #pragma once
@@ -32,13 +34,14 @@ struct jst_select_params
     unsigned long long pos_mask = 0;
     uint32_t pat_mask = 0;                    // group & pat_mask = pattern
     uint32_t loci = 0, best = 0, across = 0;
+    uint32_t shift = 0;                       // BEST's minimum is taken per group >> shift (1: SPM_SELECT_STRANDS, per read)
     uint32_t window = 0;                      // SPM_SELECT_WINDOW_K: k_tab[pattern]
     const int32_t *k_tab = nullptr;
     uint32_t halo = 0;                        // <= kSelHaloCap
     long long strata = 0;
     // out
     uint8_t *keep = nullptr;                  // [n] LOCI's verdict
-    uint8_t *head = nullptr;                  // [n] 1 where a group begins
+    uint8_t *head = nullptr;                  // [n] 1 where a group >> shift begins
     int32_t *score = nullptr;                 // [n] scores in sorted order
     const uint32_t *gid = nullptr;            // [n] exclusive sum of head (BEST without ACROSS)
     int32_t *minima = nullptr;                // BEST: minimal score per group number / per pattern (preset to INT_MAX)
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(kSelTile) void jst_select_loci_kernel(const jst_sel
             P.head[i] = 1;
         else {
             const unsigned long long kp = i - 1 >= T.lds0 ? s_key[i - 1 - T.lds0] : P.keys[i - 1];
-            P.head[i] = jsel_group(P, kp) != grp ? 1 : 0;
+            P.head[i] = (jsel_group(P, kp) >> P.shift) != (grp >> P.shift) ? 1 : 0;
         }
         const unsigned long long w = !P.loci                            ? 0ull
                                      : P.window == SPM_SELECT_WINDOW_K ? (unsigned long long)max(P.k_tab[(uint32_t)grp & P.pat_mask], 0)
@@ -152,7 +155,7 @@ __device__ __forceinline__ uint32_t jsel_gid(const jst_select_params &P, uint32_
 // where the minimum that record i is measured against lives
 __device__ __forceinline__ uint32_t jsel_min_slot(const jst_select_params &P, uint32_t i)
 {
-    return P.across ? (uint32_t)jsel_group(P, P.keys[i]) & P.pat_mask : jsel_gid(P, i);
+    return P.across ? ((uint32_t)jsel_group(P, P.keys[i]) & P.pat_mask) >> P.shift : jsel_gid(P, i);
 }
 
 // BEST: the last lane of every run of one group in a wave (sel_run_min) issues the one atomicMin of that wave and group.  A
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(256) void jst_select_minima_kernel(const jst_select
     unsigned long long grp = ~0ull;
     int32_t sc = 0x7FFFFFFF;
     if (valid) {
-        grp = jsel_group(P, P.keys[i]);
+        grp = jsel_group(P, P.keys[i]) >> P.shift;
         sc = P.score[i];
     }
     bool run_ends;

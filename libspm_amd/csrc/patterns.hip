@@ -3,6 +3,7 @@
 // MI355X only; no CPU scan path exists in this library: if HIP fails the call fails.
 #include "internal.hpp"
 #include "index_build.hpp"
+#include "strands.hpp"
 #include "tables_build.hpp"
 
 // Every table of a needle set lives in ONE device allocation and travels in one stream of pinned chunks: the sources are laid
@@ -232,6 +233,48 @@ extern "C" int spm_hip_patterns_create(spm_ctx *ctx, int algo, const uint8_t *ra
                 ps->build.anchor_sixteenths, ps->build.ms_total, ps->build.ms_tables, ps->build.ms_index, ps->build.ms_upload,
                 ps->build.threads);
     *out = ps.release();
+    return SPM_OK;
+}
+
+// n reads as 2n needles (strands.hpp lays them out), then the ordinary create path: nothing but `strands` tells the set apart
+extern "C" int spm_hip_patterns_create_stranded(spm_ctx *ctx, int algo, const uint8_t *ranks_concat, const uint32_t *offsets,
+                                                uint32_t n_reads, const uint16_t *k, uint32_t sigma, spm_patterns **out)
+{
+    if (!ctx || !out || (n_reads && (!offsets || !ranks_concat)) || sigma < 2 || sigma > 255 || algo < 0 ||
+        algo > SPM_ALGO_HORSPOOL) {
+        SPM_SET_ERR(ctx, "spm_hip_patterns_create_stranded: invalid argument");
+        return SPM_E_INVALID;
+    }
+    const stranded_set S = build_stranded(ranks_concat, offsets, n_reads, k, sigma);
+    if (S.status != SPM_OK) {
+        SPM_SET_ERR(ctx, "spm_hip_patterns_create_stranded: %s", S.why);
+        return S.status;
+    }
+    static const uint8_t none = 0; // (the create path wants a pointer even where no needle has a symbol)
+    spm_patterns *ps = nullptr;
+    SPM_TRY(spm_hip_patterns_create(ctx, algo, S.ranks.empty() ? &none : S.ranks.data(), S.offsets.data(), 2 * n_reads,
+                                    S.k.empty() ? nullptr : S.k.data(), sigma, &ps));
+    ps->strands = 2;
+    *out = ps;
+    return SPM_OK;
+}
+
+extern "C" uint32_t spm_hip_patterns_strands(const spm_patterns *p) { return p ? p->strands : 0; }
+
+extern "C" uint32_t spm_hip_patterns_count(const spm_patterns *p) { return p ? p->n : 0; }
+
+extern "C" int spm_hip_patterns_needle(const spm_patterns *p, uint32_t pattern, uint8_t *out, uint32_t cap, uint32_t *len)
+{
+    if (len)
+        *len = 0;
+    if (!p || !len || pattern >= p->n)
+        return SPM_E_INVALID;
+    const uint32_t m = p->offsets[pattern + 1] - p->offsets[pattern];
+    *len = m;
+    if (cap < m || (m && !out))
+        return SPM_E_INVALID;
+    if (m)
+        memcpy(out, p->ranks.data() + p->offsets[pattern], m);
     return SPM_OK;
 }
 

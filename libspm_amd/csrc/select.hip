@@ -65,7 +65,7 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     scratch_layout L;
     const size_t o_keys0 = L.take((size_t)n * 8), o_keys1 = L.take((size_t)n * 8), o_idx0 = L.take((size_t)n * 4),
                  o_idx1 = L.take((size_t)n * 4), o_keep = L.take(n), o_score = L.take((size_t)n * 4),
-                 o_offs = L.take((size_t)n * 4), o_min = L.take(plan.best ? S.n_patterns * 4 : 0),
+                 o_offs = L.take((size_t)n * 4), o_min = L.take(plan.min_slots * 4),
                  o_segs = L.take(n_segs ? (n_segs + 1) * 8 : 0), o_counts = L.take(16), o_tmp = L.take(tmp_bytes);
     SPM_TRY(ensure_scratch(ctx, L.bytes()));
     void *base = ctx->d_scratch;
@@ -83,6 +83,7 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     P.bias = S.bias;
     P.loci = plan.loci;
     P.best = plan.best;
+    P.shift = plan.strands ? 1u : 0u;
     P.window = plan.window;
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr;
     P.halo = plan.halo;
@@ -101,7 +102,7 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     }
     SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, 16, ctx->stream));
     if (plan.best)
-        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, S.n_patterns, ctx->stream));
+        SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, plan.min_slots, ctx->stream));
 
     // order
     const unsigned grid = (n + 255u) / 256u;
@@ -138,6 +139,11 @@ int select_make(spm_ctx *ctx, const select_source &S, const spm_select_opts *opt
     if (plan.status != SPM_OK) {
         SPM_SET_ERR(ctx, "%s: %s", who, plan.why);
         return plan.status;
+    }
+    if (plan.strands && S.ps && S.ps->strands != 2) {
+        // (a raw buffer without a set is taken by the index convention: read = pattern >> 1)
+        SPM_SET_ERR(ctx, "%s: SPM_SELECT_STRANDS on a needle set that spm_hip_patterns_create_stranded did not make", who);
+        return SPM_E_INVALID;
     }
     SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<spm_hits, void (*)(spm_hits *)> H(new spm_hits, spm_hip_hits_destroy);

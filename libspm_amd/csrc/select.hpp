@@ -6,6 +6,8 @@
 //                          scores with a halo on either side is staged in LDS; also the per-pattern score minima;
 //   select_compact_kernel  the stratum test, and the stable compaction of the kept records into the new hit block through an
 //                          exclusive scan of the keep flags (the order IS the contract: no slot atomics).
+// With SPM_SELECT_STRANDS the minimum is per read = pattern >> shift: the strand is the pattern's lowest bit, so
+// a read's two strands are adjacent runs of the sorted order.  shift = 0 is the selection per pattern, expression for expression.
 // Also here: select_params, the keys and range kernels, sel_final.  Staging, walks, min-scan, flag functor: select_walk.hpp.
 #pragma once
 
@@ -29,6 +31,7 @@ struct select_params
     unsigned long long bias = 0;
     uint32_t loci = 0;
     uint32_t best = 0;
+    uint32_t shift = 0;                       // BEST's minimum is taken per pattern >> shift (1: SPM_SELECT_STRANDS, per read)
     uint32_t window = 0;                      // SPM_SELECT_WINDOW_K: k_tab[pattern]
     const int32_t *k_tab = nullptr;
     uint32_t halo = 0;                        // <= kSelHaloCap
@@ -40,7 +43,7 @@ struct select_params
     // out
     uint8_t *keep = nullptr;                  // [n] LOCI's verdict
     int32_t *score = nullptr;                 // [n] scores in sorted order
-    int32_t *minima = nullptr;                // [n_patterns] minimal score of every pattern (BEST only; preset to INT_MAX)
+    int32_t *minima = nullptr;                // [min_slots] minimal score per pattern >> shift (BEST only; preset to INT_MAX)
     unsigned long long *counts = nullptr;     // [0] records LOCI kept, [1] records of the result
 };
 
@@ -137,19 +140,21 @@ __global__ __launch_bounds__(kSelTile) void select_loci_kernel(const select_para
         P.keep[i] = kept ? 1 : 0;
     }
     sel_count_kept(kept, &P.counts[0]);
-    // per-pattern minima: the last lane of every run issues the one atomicMin of that wave and pattern
+    // per-pattern minima: the last lane of every run issues the one atomicMin of that wave and pattern (with a shift: of
+    // that read, whose two strands are adjacent runs of the sorted order)
     if (P.best) {
         bool run_ends;
-        const int32_t m = sel_run_min(pat, sc, run_ends);
+        const uint32_t grp = pat >> P.shift;
+        const int32_t m = sel_run_min(grp, sc, run_ends);
         if (valid && (run_ends || i + 1 >= T.n))
-            atomicMin(&P.minima[pat], m);
+            atomicMin(&P.minima[grp], m);
     }
 }
 
-// the final flag of sorted record i: the minimum it is measured against is its pattern's
+// the final flag of sorted record i: the minimum it is measured against is its pattern's (its read's)
 __device__ __forceinline__ uint32_t sel_final(const select_params &P, uint32_t i)
 {
-    return sel_final_flag(P, i, [&](uint32_t r) { return sel_pattern(P, P.keys[r]); });
+    return sel_final_flag(P, i, [&](uint32_t r) { return sel_pattern(P, P.keys[r]) >> P.shift; });
 }
 
 // offs: exclusive scan of the final flags.  A kept record travels as one 16-byte load and one 16-byte store.

@@ -1,7 +1,8 @@
 // select_plan.hpp -- what one hit selection (spm_hip_hits_select / spm_hip_records_select) decides on the host, as pure
 // functions (plain C++17, no HIP: select.hip and tests/cpp/select_plan_cases.cpp both compile it): the window a needle
 // gets, the bit budget of the sort key, the halo the selection kernel stages in LDS, and the two refusals that are made
-// before anything is launched.  select.hip keeps the HIP calls and acts on the answers.  Also here: plan_jst_select for
+// before anything is launched (SPM_SELECT_STRANDS: the flag needs BEST, the minima table is per read).  select.hip keeps the
+// HIP calls and acts on the answers.  Also here: plan_jst_select for
 // pan-genome selections (front and back shared with plan_select) and plan_jst_locate for spm_hip_jst_selection_align's sort.
 #pragma once
 
@@ -50,6 +51,8 @@ struct select_plan
     uint32_t max_window = 0;   // the largest window any needle gets
     uint32_t halo = 0;
     bool loci = false, best = false;
+    bool strands = false;      // SPM_SELECT_STRANDS: BEST's minimum is per read = pattern >> 1
+    uint64_t min_slots = 0;    // entries of the minima table BEST needs (0 without BEST)
 };
 
 // a refusal: status and why are set, and nothing else of P means anything
@@ -70,11 +73,22 @@ template <class Plan> bool plan_select_front(Plan &P, const spm_select_opts &o, 
     P.best = (o.flags & SPM_SELECT_BEST) != 0;
     if ((o.flags & SPM_SELECT_ACROSS) && !P.best)
         return plan_refuse(P, SPM_E_INVALID, "SPM_SELECT_ACROSS needs SPM_SELECT_BEST");
+    P.strands = (o.flags & SPM_SELECT_STRANDS) != 0;
+    if (P.strands && !P.best)
+        return plan_refuse(P, SPM_E_INVALID, "SPM_SELECT_STRANDS needs SPM_SELECT_BEST");
     if (P.loci && o.window == SPM_SELECT_WINDOW_K && !have_k)
         return plan_refuse(P, SPM_E_INVALID, "SPM_SELECT_WINDOW_K needs the needle set");
     if (n_records > 0xFFFFFFFFull)
         return plan_refuse(P, SPM_E_UNSUPPORTED, "more than 2^32 - 1 records");
     return true;
+}
+
+// Entries of a minima table indexed by pattern, or under SPM_SELECT_STRANDS by read = pattern >> 1: the patterns
+// 0 .. n_patterns - 1 name the reads 0 .. (n_patterns - 1) >> 1.
+inline uint64_t select_minima_slots(uint64_t n_patterns, bool strands)
+{
+    const uint64_t n = std::max<uint64_t>(n_patterns, 1);
+    return strands ? ((n - 1) >> 1) + 1 : n;
 }
 
 // ... and the back, once the key's fields are sized: above 64 bits refused with `too_wide`; the window(s) and the halo
@@ -100,8 +114,9 @@ inline select_plan plan_select(const spm_select_opts &o, uint64_t n_records, uin
                                bool have_k, bool myers_set, uint32_t max_k)
 {
     select_plan P;
-    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST, n_records, have_k))
+    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_STRANDS, n_records, have_k))
         return P;
+    P.min_slots = P.best ? select_minima_slots(n_patterns, P.strands) : 0;
     P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
     P.pos_bits = bits_for(max_rel_pos);
     P.key_bits = P.pat_bits + P.pos_bits;
@@ -122,6 +137,8 @@ struct jst_select_plan
     uint32_t max_window = 0;
     uint32_t halo = 0;
     bool loci = false, best = false, across = false;
+    bool strands = false;      // SPM_SELECT_STRANDS: the minimum's group is (haplotype, read), or with ACROSS the read
+    uint64_t min_slots = 0;    // entries of the minima table: per read or pattern with ACROSS, else one per record at most
 };
 
 // n_haplotypes / n_patterns: what the records can name (>= 1 each); max_pos: the largest position a record can hold (for a
@@ -130,11 +147,14 @@ inline jst_select_plan plan_jst_select(const spm_select_opts &o, uint64_t n_reco
                                        uint64_t max_pos, bool have_k, bool myers_set, uint32_t max_k)
 {
     jst_select_plan P;
-    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_ACROSS, n_records, have_k))
+    if (!plan_select_front(P, o, SPM_SELECT_LOCI | SPM_SELECT_BEST | SPM_SELECT_ACROSS | SPM_SELECT_STRANDS, n_records, have_k))
         return P;
     P.across = (o.flags & SPM_SELECT_ACROSS) != 0;
+    P.min_slots = !P.best ? 0 : P.across ? select_minima_slots(n_patterns, P.strands) : n_records;
     P.hap_bits = bits_for(n_haplotypes ? n_haplotypes - 1 : 0);
     P.pat_bits = bits_for(n_patterns ? n_patterns - 1 : 0);
+    if (P.strands) // the strand is the lowest bit of the group: it must be a pattern bit even where only pattern 0 occurs
+        P.pat_bits = std::max(P.pat_bits, 1u);
     P.pos_bits = bits_for(max_pos);
     P.key_bits = P.hap_bits + P.pat_bits + P.pos_bits;
     plan_select_back(P, o, myers_set, max_k, "haplotype, pattern index and position do not fit one 64-bit sort key");

@@ -75,9 +75,11 @@ class Context:
         return Text(self, h, 4)
 
     # ---- needles ----
-    def patterns(self, algo: int, needles, k=0, sigma: int = 4) -> "PatternSet":
+    def patterns(self, algo: int, needles, k=0, sigma: int = 4, both_strands: bool = False) -> "PatternSet":
         """needles: a sequence of rank arrays, or -- reads of one length -- a 2-D uint8 array, one needle per row (what the C ABI
-        takes anyway: ranks back to back + offsets; 100 000 rows cost a reshape instead of 100 000 Python objects)."""
+        takes anyway: ranks back to back + offsets; 100 000 rows cost a reshape instead of 100 000 Python objects).
+        both_strands: the needles are n READS and the set holds 2n needles (spm_hip_patterns_create_stranded): pattern 2r is
+        read r, pattern 2r + 1 its reverse complement, both with k[r]."""
         if isinstance(needles, np.ndarray) and needles.ndim == 2:
             mat = np.ascontiguousarray(needles, dtype=np.uint8)
             n_needles = mat.shape[0]
@@ -95,11 +97,10 @@ class Context:
         else:
             ks = np.ascontiguousarray(k, dtype=np.uint16)
         h = C.c_void_p()
-        _check(capi.lib().spm_hip_patterns_create(self._h, algo, cat.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(needles),
-                                                  ks.ctypes.data_as(C.POINTER(C.c_uint16)), sigma, C.byref(h)),
-               self._h)
-        return PatternSet(self, h, algo, len(needles))
+        create = capi.lib().spm_hip_patterns_create_stranded if both_strands else capi.lib().spm_hip_patterns_create
+        _check(create(self._h, algo, cat.ctypes.data_as(C.POINTER(C.c_uint8)), offs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                      len(needles), ks.ctypes.data_as(C.POINTER(C.c_uint16)), sigma, C.byref(h)), self._h)
+        return PatternSet(self, h, algo, (2 if both_strands else 1) * len(needles))
 
 
 class Text:
@@ -145,6 +146,25 @@ class Text:
 class PatternSet:
     def __init__(self, ctx, h, algo, n):
         self.ctx, self._h, self.algo, self.n = ctx, h, algo, n
+
+    def __len__(self):
+        """needles in the set: 2n for n reads on both strands"""
+        return int(capi.lib().spm_hip_patterns_count(self._h))
+
+    @property
+    def strands(self) -> int:
+        """2 for a set made with both_strands (read = pattern >> 1, strand = pattern & 1), else 1"""
+        return int(capi.lib().spm_hip_patterns_strands(self._h))
+
+    def needle(self, p: int) -> np.ndarray:
+        """The ranks of needle p, from the set's host copy: SAM SEQ of a reverse-strand hit when p is odd in a stranded set."""
+        n = C.c_uint32()
+        capi.lib().spm_hip_patterns_needle(self._h, p, None, 0, C.byref(n))
+        out = np.empty(n.value, dtype=np.uint8)
+        rc = capi.lib().spm_hip_patterns_needle(self._h, p, out.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n))
+        if rc != 0:
+            raise capi.SpmError(f"spm_hip_patterns_needle: no needle {p} in a set of {len(self)}")
+        return out
 
     def window_size(self, p: int = 0) -> int:
         return int(capi.lib().spm_hip_patterns_window_size(self._h, p))
@@ -225,11 +245,12 @@ class Hits:
                self.ctx._h)
         return Alignments(self.ctx, a)
 
-    def select(self, loci: bool = True, window: int | None = None, best: int | None = None) -> "Hits":
+    def select(self, loci: bool = True, window: int | None = None, best: int | None = None, strands: bool = False) -> "Hits":
         """A new, smaller Hits (spm_hip_hits_select): one record per locus (loci; window=None: every needle's own k) and,
-        with best=s, only the records within s errors of their needle's minimum.  Host AND device view of the result are
-        sorted by (pattern, pos); it stays valid after this object is closed."""
-        opts = _select_opts(loci, window, best)
+        with best=s, only the records within s errors of their needle's minimum -- with strands=True (a set made with
+        both_strands) of their READ's minimum over both strands.  Host AND device view of the result are sorted by
+        (pattern, pos); it stays valid after this object is closed."""
+        opts = _select_opts(loci, window, best, strands=strands)
         h = C.c_void_p()
         _check(capi.lib().spm_hip_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
         return Hits(self.ctx, h, self._text, self._pats)
@@ -364,18 +385,19 @@ def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | 
     return (hits, st_out) if want_state else hits
 
 
-def _select_opts(loci, window, best, across=False) -> capi.SelectOpts:
+def _select_opts(loci, window, best, across=False, strands=False) -> capi.SelectOpts:
     flags = ((capi.SELECT_LOCI if loci else 0) | (capi.SELECT_BEST if best is not None else 0)
-             | (capi.SELECT_ACROSS if across else 0))
+             | (capi.SELECT_ACROSS if across else 0) | (capi.SELECT_STRANDS if strands else 0))
     return capi.SelectOpts(flags=flags, window=capi.SELECT_WINDOW_K if window is None else int(window),
                            strata=0 if best is None else int(best), reserved=0)
 
 
 def select_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet | None = None, *, loci: bool = True,
-                   window: int | None = None, best: int | None = None) -> Hits:
+                   window: int | None = None, best: int | None = None, strands: bool = False) -> Hits:
     """Hits.select() on a device buffer of n HIT_DTYPE records that no Hits owns -- what a gatherv delivers on the root
-    (spm_hip_records_select).  pats may be None when window is explicit.  The result cannot be aligned."""
-    opts = _select_opts(loci, window, best)
+    (spm_hip_records_select).  pats may be None when window is explicit.  The result cannot be aligned.  strands: as
+    Hits.select; without pats the records are taken by the index convention read = pattern >> 1."""
+    opts = _select_opts(loci, window, best, strands=strands)
     h = C.c_void_p()
     _check(capi.lib().spm_hip_records_select(ctx._h, C.c_void_p(device_ptr), n, pats._h if pats is not None else None,
                                              C.byref(opts), C.byref(h)), ctx._h)
@@ -421,6 +443,8 @@ JST_ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4")
                           ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("reserved", "<u4")])
 JST_REF_ALN_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"),
                               ("score", "<i4"), ("ref_score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4")])
+JST_READ_DTYPE = np.dtype([("first_locus", "<u4"), ("n_loci", "<u4"), ("n_forward", "<u4"), ("primary", "<u4"),
+                           ("best", "<i4"), ("best_ref_score", "<i4"), ("n_best", "<u4"), ("n_next", "<u4")])
 JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
                                 ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
                                 ("member_off", "<u4"), ("n_haplotypes", "<u4")])
@@ -565,15 +589,16 @@ class JstHits:
         return JstAlignments(self.ctx, a, self._jst, self._pats)
 
     def select(self, loci: bool = True, window: int | None = None, best: int | None = None,
-               across: bool = False) -> "JstHits":
+               across: bool = False, strands: bool = False) -> "JstHits":
         """A new, smaller JstHits (spm_hip_jst_hits_select): one record per locus of every haplotype (loci; window=None:
         every needle's own k) and, with best=s, only the records within s errors of the minimum of their (haplotype,
         needle) -- with across=True, of their needle on all haplotypes.  The device view of the result is sorted by
         (haplotype, pattern, pos), its host view as every view(); it stays valid after this object is closed.  align()
-        does not take it; align_selected() aligns the records it kept."""
+        does not take it; align_selected() aligns the records it kept.  strands=True (a set made with both_strands): the
+        minimum is taken per READ = pattern >> 1 over both strands."""
         if self._pats is not None and not self._pats._h:
             raise capi.SpmError("JstHits.select: the needle set of these hits has been closed")
-        opts = _select_opts(loci, window, best, across)
+        opts = _select_opts(loci, window, best, across, strands)
         h = C.c_void_p()
         _check(capi.lib().spm_hip_jst_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
         return JstHits(self.ctx, h, self._jst, self._pats)
@@ -597,10 +622,11 @@ class JstHits:
 
 
 def select_jst_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet | None = None, *, loci: bool = True,
-                       window: int | None = None, best: int | None = None, across: bool = False) -> JstHits:
+                       window: int | None = None, best: int | None = None, across: bool = False,
+                       strands: bool = False) -> JstHits:
     """JstHits.select() on a device buffer of n JST_HIT_DTYPE records that no JstHits owns -- what a gatherv of the block
     shards delivers on the root (spm_hip_jst_records_select).  pats may be None when window is explicit."""
-    opts = _select_opts(loci, window, best, across)
+    opts = _select_opts(loci, window, best, across, strands)
     h = C.c_void_p()
     _check(capi.lib().spm_hip_jst_records_select(ctx._h, C.c_void_p(device_ptr), n, pats._h if pats is not None else None,
                                                  C.byref(opts), C.byref(h)), ctx._h)
@@ -745,3 +771,50 @@ class JstRefLoci(_RecordPool):
 
     def stats(self) -> capi.JstCollapseStats:
         return self._stats()
+
+    def reads(self, n_reads: int, strands: int = 1) -> "JstReads":
+        """One JST_READ_DTYPE record per read 0 .. n_reads - 1 (spm_hip_jst_ref_loci_reads): where its loci stand, how many
+        it has on which strand, its primary locus -- the smallest (score, locus index) -- and how many loci share the best
+        and the next stratum.  strands=2: the loci stem from a set made with both_strands (read = pattern >> 1).  The result
+        stays valid after this object is closed."""
+        r = C.c_void_p()
+        self._call("reads", strands, n_reads, 0, C.byref(r))
+        return JstReads(self.ctx, r)
+
+
+class JstReads:
+    """Result of JstRefLoci.reads(): one JST_READ_DTYPE record per read, in read order, in both views."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def __len__(self):
+        return self.device()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n = C.POINTER(capi.JstRead)(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_reads_view(self._h, C.byref(rec), C.byref(n)), self.ctx._h)
+        return _as_array(rec, n.value, capi.JstRead, JST_READ_DTYPE)
+
+    def device(self):
+        """(pointer, count) of the records in HBM"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_reads_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return int(p.value or 0), int(n.value)
+
+    def stats(self) -> capi.JstReadsStats:
+        s = capi.JstReadsStats()
+        _check(capi.lib().spm_hip_jst_reads_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_jst_reads_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
