@@ -97,6 +97,26 @@ struct jst_read_loci
     bool operator==(jst_read_loci const &) const noexcept = default;
 };
 
+// what a mapper reports per pair of mates (journaled_sequence_tree::locate_pairs; spm_jst_pair in spm_hip.h): reads 2p and
+// 2p + 1 are the mates of pair p.  The best concordant combination of a forward locus of one mate and a reverse locus of the
+// other (FR orientation, min_tlen <= fragment <= max_tlen) by (sum of haplotype_errors, index, index); without one, the
+// mates' own primaries
+struct jst_pair
+{
+    std::uint32_t locus1, locus2; // indices into the loci vector; 0xFFFFFFFF: unmapped
+    std::int32_t tlen, best;      // SAM TLEN of mate 1 (0: not a proper pair); the error sum (-1: none)
+    std::uint32_t n_pairs, n_best, n_next;
+    std::uint16_t flag1, flag2;   // SAM FLAG of the two primary lines
+    bool operator==(jst_pair const &) const noexcept = default;
+};
+
+struct jst_pair_loci
+{
+    jst_read_loci mapped;         // the loci and the summary of every read
+    std::vector<jst_pair> pairs;  // one per pair, in pair order
+    bool operator==(jst_pair_loci const &) const noexcept = default;
+};
+
 struct jst_search_stats
 {
     std::uint64_t haplotype_symbols{}; // sum of haplotype lengths (what per-haplotype scans would read)
@@ -804,6 +824,101 @@ public:
         return out;
     }
 
+    // ---- the mates of paired-end reads (the contract of spm_hip_jst_ref_loci_pairs in spm_hip.h): needles compiled with
+    // both_strands from n_reads reads, n_reads even, reads 2p and 2p + 1 the mates of pair p.  Device route: the chain of
+    // locate_reads plus spm_hip_jst_ref_loci_pairs.  Host route: the host loci, the host summary and a plain loop over all
+    // combinations.  Both return the same.
+    jst_pair_loci locate_pairs(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                               bool reports_begin, std::uint32_t n_reads, std::uint32_t min_tlen, std::uint32_t max_tlen,
+                               hip::hit_selection const & selection, std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return locate_pairs_device(needles, window, n_reads, min_tlen, max_tlen, selection, block, stats);
+        return locate_pairs_host(needles, window, needle_ranks, reports_begin, n_reads, min_tlen, max_tlen, selection, block, stats);
+    }
+
+    jst_pair_loci locate_pairs_device(spm_patterns * needles, std::size_t window, std::uint32_t n_reads, std::uint32_t min_tlen,
+                                      std::uint32_t max_tlen, hip::hit_selection const & selection, std::size_t block = 0,
+                                      jst_search_stats * stats = nullptr) const
+    {
+        jst_pair_loci out;
+        spm_jst_pair_opts const opts{min_tlen, max_tlen, 0, 0};
+        out.mapped.loci = loci_of(device_alns(needles, window, selection, block, stats).get(), true, 2, n_reads, &out.mapped.reads,
+                                  &opts, &out.pairs);
+        return out;
+    }
+
+    jst_pair_loci locate_pairs_host(spm_patterns * needles, std::size_t window,
+                                    std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
+                                    std::uint32_t n_reads, std::uint32_t min_tlen, std::uint32_t max_tlen,
+                                    hip::hit_selection const & selection, std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        jst_pair_loci out;
+        out.mapped = locate_reads_host(needles, window, needle_ranks, reports_begin, 2, n_reads, selection, block, stats);
+        out.pairs = pairs_host(out.mapped, min_tlen, max_tlen);
+        return out;
+    }
+
+    // the rule as a plain loop: per pair, every forward locus of one mate against every reverse locus of the other
+    static std::vector<jst_pair> pairs_host(jst_read_loci const & mapped, std::uint32_t min_tlen, std::uint32_t max_tlen)
+    {
+        if (min_tlen < 1 || min_tlen > max_tlen || max_tlen > 0x7FFFFFFFu || mapped.reads.size() % 2 != 0)
+            hip::fatal("journaled_sequence_tree::locate_pairs (1 <= min_tlen <= max_tlen <= 2^31 - 1, an even number of reads)",
+                       hip::default_context());
+        std::vector<jst_ref_locus> const & loci = mapped.loci;
+        auto const clamp = [](std::uint64_t x) { return static_cast<std::uint32_t>(std::min<std::uint64_t>(x, 0xFFFFFFFFu)); };
+        std::vector<jst_pair> out;
+        for (std::size_t p = 0; p < mapped.reads.size() / 2; ++p) {
+            jst_read const mate[2] = {mapped.reads[2 * p], mapped.reads[2 * p + 1]};
+            std::int64_t best = -1;
+            std::uint32_t best_a = 0, best_b = 0;
+            std::uint64_t n_pairs = 0, n_best = 0, n_next = 0;
+            for (int pass = 0; pass < 2; ++pass) // the minimum, then the counts against it
+                for (int m = 0; m < 2; ++m) {
+                    jst_read const &F = mate[m], &V = mate[m ^ 1];
+                    for (std::uint32_t a = F.first_locus; a < F.first_locus + F.n_forward; ++a)
+                        for (std::uint32_t b = V.first_locus + V.n_forward; b < V.first_locus + V.n_loci; ++b) {
+                            alignment const &A = loci[a].aln, &B = loci[b].aln;
+                            if (A.begin_position() > B.begin_position() || A.end_position() > B.end_position())
+                                continue;
+                            std::size_t const t = B.end_position() - A.begin_position();
+                            if (t < min_tlen || t > max_tlen)
+                                continue;
+                            std::int64_t const sum = static_cast<std::int64_t>(loci[a].haplotype_errors) + loci[b].haplotype_errors;
+                            if (pass == 0) { // (a ascends, then b: the first of equal sums stays)
+                                if (best < 0 || sum < best) {
+                                    best = sum;
+                                    best_a = a;
+                                    best_b = b;
+                                }
+                            } else {
+                                n_pairs += 1;
+                                n_best += sum == best;
+                                n_next += sum == best + 1;
+                            }
+                        }
+                }
+            bool const proper = best >= 0;
+            jst_pair P{mate[0].primary, mate[1].primary, 0, -1, 0, 0, 0, 0, 0};
+            if (proper) {
+                bool const mate1_forward = (loci[best_a].needle & 2u) == 0;
+                auto const t = static_cast<std::int32_t>(loci[best_b].aln.end_position() - loci[best_a].aln.begin_position());
+                P = {mate1_forward ? best_a : best_b, mate1_forward ? best_b : best_a, mate1_forward ? t : -t,
+                     static_cast<std::int32_t>(best), clamp(n_pairs), clamp(n_best), clamp(n_next), 0, 0};
+            }
+            bool const un1 = P.locus1 == 0xFFFFFFFFu, un2 = P.locus2 == 0xFFFFFFFFu;
+            bool const rev1 = !un1 && (loci[P.locus1].needle & 1u), rev2 = !un2 && (loci[P.locus2].needle & 1u);
+            auto const flag = [&](bool second, bool self_un, bool other_un, bool self_rev, bool other_rev) {
+                return static_cast<std::uint16_t>(0x1u | (proper ? 0x2u : 0u) | (self_un ? 0x4u : 0u) | (other_un ? 0x8u : 0u) |
+                                                  (self_rev ? 0x10u : 0u) | (other_rev ? 0x20u : 0u) | (second ? 0x80u : 0x40u));
+            };
+            P.flag1 = flag(false, un1, un2, rev1, rev2);
+            P.flag2 = flag(true, un2, un1, rev2, rev1);
+            out.push_back(P);
+        }
+        return out;
+    }
+
     // The normalisation on the host, in column form: one op per column, a gap run moved one step at a time by the rule of
     // spm_hip.h.  i and r -- the needle symbols and reference positions the columns before the run consume -- are counted
     // anew for every step.
@@ -1101,9 +1216,11 @@ private:
     }
 
     // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
-    // ... and, where asked for, the summary of n_reads reads over them (spm_hip_jst_ref_loci_reads)
+    // ... and, where asked for, the summary of n_reads reads over them (spm_hip_jst_ref_loci_reads) and the pairs of their
+    // mates (spm_hip_jst_ref_loci_pairs)
     static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false, std::uint32_t strands = 1,
-                                              std::uint32_t n_reads = 0, std::vector<jst_read> * reads = nullptr)
+                                              std::uint32_t n_reads = 0, std::vector<jst_read> * reads = nullptr,
+                                              spm_jst_pair_opts const * pair_opts = nullptr, std::vector<jst_pair> * pairs = nullptr)
     {
         spm_ctx * ctx = hip::default_context();
         spm_jst_ref_alns * r = projected(a, normalized);
@@ -1143,6 +1260,20 @@ private:
             for (std::uint64_t i = 0; i < nr; ++i)
                 reads->push_back({rr[i].first_locus, rr[i].n_loci, rr[i].n_forward, rr[i].primary, rr[i].best,
                                   rr[i].best_ref_score, rr[i].n_best, rr[i].n_next});
+            if (pairs != nullptr) {
+                spm_jst_pairs * pr = nullptr;
+                if (spm_hip_jst_ref_loci_pairs(l, rd, pair_opts, &pr) != SPM_OK)
+                    hip::fatal("spm_hip_jst_ref_loci_pairs", ctx);
+                std::unique_ptr<spm_jst_pairs, decltype(&spm_hip_jst_pairs_destroy)> pr_owner{pr, &spm_hip_jst_pairs_destroy};
+                spm_jst_pair const * pp = nullptr;
+                std::uint64_t np = 0;
+                if (spm_hip_jst_pairs_view(pr, &pp, &np) != SPM_OK)
+                    hip::fatal("spm_hip_jst_pairs_view", ctx);
+                pairs->clear();
+                for (std::uint64_t i = 0; i < np; ++i)
+                    pairs->push_back({pp[i].locus1, pp[i].locus2, pp[i].tlen, pp[i].best, pp[i].n_pairs, pp[i].n_best, pp[i].n_next,
+                                      pp[i].flag1, pp[i].flag2});
+            }
         }
         return out;
     }

@@ -750,6 +750,80 @@ int spm_hip_jst_reads_device(spm_jst_reads *r, const void **records, uint64_t *n
 int spm_hip_jst_reads_stats(const spm_jst_reads *r, spm_jst_reads_stats *out);
 void spm_hip_jst_reads_destroy(spm_jst_reads *r);
 
+/* ---- the mates of paired-end reads: one proper pair per read pair --------------------------------------------------------------
+ * One spm_jst_pair per pair p = 0 .. n_reads / 2 - 1, in pair order, from the loci of a collapse and their read summary made
+ * with strands == 2.  Reads 2p (mate 1) and 2p + 1 (mate 2) are the mates of pair p: the loci of the pair are the contiguous
+ * patterns 4p (mate 1 forward), 4p + 1 (mate 1 reverse), 4p + 2 (mate 2 forward), 4p + 3 (mate 2 reverse), and each of the
+ * four sub-runs is ascending in ref_begin.  The forward loci of a read are its first n_forward loci, its reverse loci the rest.
+ *
+ * Concordance (FR orientation only).  Forward locus a of one mate and reverse locus b of the OTHER mate are concordant iff
+ *     a.ref_begin <= b.ref_begin,  a.ref_end <= b.ref_end  and  min_tlen <= b.ref_end - a.ref_begin <= max_tlen.
+ * Both directions count: mate 1 forward with mate 2 reverse, and mate 2 forward with mate 1 reverse.  A locus inside an
+ * insertion (ref_begin == ref_end, the anchor) takes part as it is.
+ * The best pair is the minimum of (a.score + b.score, index of a, index of b) over the concordant combinations; the sum is
+ * taken in 64 bits.  n_pairs counts the concordant combinations, n_best those whose sum equals the best, n_next those whose
+ * sum equals the best + 1; all three are accumulated in 64 bits and clamped to 0xFFFFFFFF in the record.
+ * No concordant combination: locus1 and locus2 are the mates' own primaries from the read summary (0xFFFFFFFF: unmapped),
+ * tlen is 0, best is -1, the counts are 0.  MAPQ is a policy over (n_best, n_next) and is deliberately not computed.
+ * flag1 / flag2 are the SAM FLAG of the two primary lines:
+ *     0x1 always   0x2 proper pair   0x4 this mate has no locus   0x8 the other mate has no locus
+ *     0x10 this mate's reported locus is a reverse pattern   0x20 the other mate's is   0x40 mate 1 / 0x80 mate 2
+ * No secondary or supplementary bits are emitted.
+ * The result is a pure function of the loci and opts: byte-identical across runs, host and device view alike.  It outlives
+ * both source handles.
+ *
+ * Worked cases, reads of 30 symbols, min_tlen 100, max_tlen 300.
+ *  1. The pair of the primaries is not the primary pair.  Mate 1 has one forward locus [1000,1030), score 0.  Mate 2 has the
+ *     reverse loci [1170,1200) with score 1 and [7000,7030) with score 0: its own primary is the distant copy.  Only the first
+ *     is concordant (fragment 200): locus2 is the locus at 1170, tlen +200, best 1, n_pairs 1, n_best 1, flag1 0x63, flag2 0x93.
+ *  2. Mate 1 on the reverse strand.  Mate 2 forward at [500,530), mate 1 reverse at [720,750): tlen -250 (mate 2's line: +250),
+ *     flag1 0x53, flag2 0xA3.
+ *  3. Bounds and shapes.  a = [1000,1030) forward: b = [1070,1100) gives 100, concordant; [1069,1099) gives 99, not;
+ *     [1270,1300) gives 300, concordant; [1271,1301) gives 301, not.  b = [990,1120) begins left of a (a dovetail) and
+ *     a = [1000,1200), b = [1050,1150) ends right of b (a containment): neither is concordant.  Two forward loci of one mate
+ *     and two reverse loci of the other, same strand on both mates, or only one mate mapped: never a proper pair; the record
+ *     carries the primaries, tlen 0, and flags without 0x2.
+ *
+ *   * SPM_E_INVALID with a message: NULL arguments; unknown flag bits or a nonzero reserved; min_tlen == 0, min_tlen >
+ *     max_tlen, max_tlen > 2^31 - 1; a reads handle of another context, one not made with strands == 2, one with an odd
+ *     number of reads, one made from a different number of loci.
+ *   * Everything else about the agreement of the two handles is tested on the device before it is used as an index -- the run
+ *     of a read lies inside the loci, the patterns at the head and the tail of its sub-runs name the read, its primary lies
+ *     inside the run, every locus lies in the run of its own read -- and a concordant combination whose score sum does not fit
+ *     in 31 bits is unusable: either is COUNTED and fails the whole call with SPM_E_INVALID, never a fault.
+ *   * Zero reads: an empty result.  No loci: every pair unmapped, flag1 0x4D, flag2 0x8D.  Both SPM_OK. */
+typedef struct spm_jst_pair_opts {   /* 16 bytes */
+    uint32_t min_tlen, max_tlen;     /* 1 <= min_tlen <= max_tlen <= 2^31 - 1 */
+    uint32_t flags;                  /* must be 0 (FR orientation) */
+    uint32_t reserved;               /* must be 0 */
+} spm_jst_pair_opts;
+typedef struct spm_jst_pair {        /* 32 bytes */
+    uint32_t locus1, locus2;         /* locus reported for mate 1 / mate 2; 0xFFFFFFFF: unmapped */
+    int32_t tlen;                    /* SAM TLEN of mate 1 (mate 2: its negative): + (b.ref_end - a.ref_begin) when mate 1 is
+                                        the forward locus, - when it is the reverse one; 0 when not a proper pair */
+    int32_t best;                    /* score sum of the best concordant pair; -1: none */
+    uint32_t n_pairs, n_best, n_next;
+    uint16_t flag1, flag2;           /* SAM FLAG of the two primary lines */
+} spm_jst_pair;
+typedef struct spm_jst_pairs spm_jst_pairs;
+typedef struct spm_jst_pairs_stats { /* 72 bytes */
+    float ms_total;                  /* device: the three passes (HIP events) */
+    float ms_host;                   /* wall clock of the whole call, host view included */
+    uint64_t n_pairs;                /* read pairs */
+    uint64_t n_proper;               /* pairs with a concordant combination */
+    uint64_t n_unique;               /* ... with n_best == 1 */
+    uint64_t n_multi;                /* ... with n_best > 1 */
+    uint64_t n_discordant;           /* both mates mapped, not proper */
+    uint64_t n_one_mate;             /* exactly one mate mapped */
+    uint64_t n_unmapped;             /* neither */
+    uint64_t max_window;             /* the longest partner window any forward locus walked: the walk is linear in it */
+} spm_jst_pairs_stats;
+int spm_hip_jst_ref_loci_pairs(spm_jst_ref_loci *l, spm_jst_reads *r, const spm_jst_pair_opts *opts, spm_jst_pairs **out);
+int spm_hip_jst_pairs_view(spm_jst_pairs *p, const spm_jst_pair **records, uint64_t *n);
+int spm_hip_jst_pairs_device(spm_jst_pairs *p, const void **records, uint64_t *n);
+int spm_hip_jst_pairs_stats(const spm_jst_pairs *p, spm_jst_pairs_stats *out);
+void spm_hip_jst_pairs_destroy(spm_jst_pairs *p);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

@@ -214,6 +214,30 @@ class JstReadsStats(C.Structure):
     ]
 
 
+class JstPairOpts(C.Structure):
+    _fields_ = [("min_tlen", C.c_uint32), ("max_tlen", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JstPair(C.Structure):
+    _fields_ = [("locus1", C.c_uint32), ("locus2", C.c_uint32), ("tlen", C.c_int32), ("best", C.c_int32),
+                ("n_pairs", C.c_uint32), ("n_best", C.c_uint32), ("n_next", C.c_uint32), ("flag1", C.c_uint16), ("flag2", C.c_uint16)]
+
+
+class JstPairsStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_pairs", C.c_uint64),
+        ("n_proper", C.c_uint64),
+        ("n_unique", C.c_uint64),
+        ("n_multi", C.c_uint64),
+        ("n_discordant", C.c_uint64),
+        ("n_one_mate", C.c_uint64),
+        ("n_unmapped", C.c_uint64),
+        ("max_window", C.c_uint64),
+    ]
+
+
 class JstNormalizeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -383,6 +407,11 @@ def lib():
         "spm_hip_jst_reads_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_reads_stats": (C.c_int, [vp, C.POINTER(JstReadsStats)]),
         "spm_hip_jst_reads_destroy": (None, [vp]),
+        "spm_hip_jst_ref_loci_pairs": (C.c_int, [vp, vp, C.POINTER(JstPairOpts), C.POINTER(vp)]),
+        "spm_hip_jst_pairs_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstPair)), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_pairs_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_pairs_stats": (C.c_int, [vp, C.POINTER(JstPairsStats)]),
+        "spm_hip_jst_pairs_destroy": (None, [vp]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -431,6 +460,8 @@ EXPORTS = [
     "spm_hip_jst_ref_loci_stats", "spm_hip_jst_ref_loci_destroy",
     "spm_hip_jst_ref_loci_reads", "spm_hip_jst_reads_view", "spm_hip_jst_reads_device", "spm_hip_jst_reads_stats",
     "spm_hip_jst_reads_destroy",
+    "spm_hip_jst_ref_loci_pairs", "spm_hip_jst_pairs_view", "spm_hip_jst_pairs_device", "spm_hip_jst_pairs_stats",
+    "spm_hip_jst_pairs_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

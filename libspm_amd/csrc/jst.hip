@@ -9,3 +9,4 @@
 #include "jst_normalize.hpp"
 #include "jst_collapse.hpp"
 #include "jst_reads.hpp"
+#include "jst_pairs.hpp"

@@ -171,6 +171,8 @@ struct spm_jst_reads
     spm_ctx *ctx = nullptr;
     spm_jst_read *d_reads = nullptr;
     uint64_t n = 0;
+    uint32_t strands = 1; // what the summary was made with, and from how many loci (spm_hip_jst_ref_loci_pairs asks)
+    uint64_t n_loci = 0;
     std::vector<spm_jst_read> host;
     spm_jst_reads_stats stats{};
 };
@@ -214,6 +216,8 @@ extern "C" int spm_hip_jst_ref_loci_reads(spm_jst_ref_loci *l, uint32_t strands,
     std::unique_ptr<spm_jst_reads, void (*)(spm_jst_reads *)> R(new spm_jst_reads, spm_hip_jst_reads_destroy);
     R->ctx = ctx;
     R->n = n_reads;
+    R->strands = strands;
+    R->n_loci = l->n;
     R->stats.n_reads = n_reads;
     R->stats.n_loci = l->n;
     if (n_reads) {

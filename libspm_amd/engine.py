@@ -445,6 +445,8 @@ JST_REF_ALN_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("haplot
                               ("score", "<i4"), ("ref_score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4")])
 JST_READ_DTYPE = np.dtype([("first_locus", "<u4"), ("n_loci", "<u4"), ("n_forward", "<u4"), ("primary", "<u4"),
                            ("best", "<i4"), ("best_ref_score", "<i4"), ("n_best", "<u4"), ("n_next", "<u4")])
+JST_PAIR_DTYPE = np.dtype([("locus1", "<u4"), ("locus2", "<u4"), ("tlen", "<i4"), ("best", "<i4"), ("n_pairs", "<u4"),
+                           ("n_best", "<u4"), ("n_next", "<u4"), ("flag1", "<u2"), ("flag2", "<u2")])
 JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
                                 ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
                                 ("member_off", "<u4"), ("n_haplotypes", "<u4")])
@@ -781,6 +783,16 @@ class JstRefLoci(_RecordPool):
         self._call("reads", strands, n_reads, 0, C.byref(r))
         return JstReads(self.ctx, r)
 
+    def pairs(self, reads: "JstReads", min_tlen: int, max_tlen: int) -> "JstPairs":
+        """One JST_PAIR_DTYPE record per pair of mates -- reads 2p and 2p + 1 of `reads`, this object's reads(n, strands=2)
+        (spm_hip_jst_ref_loci_pairs): the best concordant combination of a forward locus of one mate and a reverse locus
+        of the other with min_tlen <= fragment length <= max_tlen, how many there are, the SAM TLEN and FLAGs; without one,
+        the mates' own primaries.  The result stays valid after this object and `reads` are closed."""
+        opts = capi.JstPairOpts(min_tlen=int(min_tlen), max_tlen=int(max_tlen), flags=0, reserved=0)
+        p = C.c_void_p()
+        self._call("pairs", reads._h, C.byref(opts), C.byref(p))
+        return JstPairs(self.ctx, p)
+
 
 class JstReads:
     """Result of JstRefLoci.reads(): one JST_READ_DTYPE record per read, in read order, in both views."""
@@ -811,6 +823,44 @@ class JstReads:
         if self._h:
             if self.ctx._h:
                 capi.lib().spm_hip_jst_reads_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JstPairs:
+    """Result of JstRefLoci.pairs(): one JST_PAIR_DTYPE record per pair of mates, in pair order, in both views."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def __len__(self):
+        return self.device()[1]
+
+    def view(self) -> np.ndarray:
+        rec, n = C.POINTER(capi.JstPair)(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_pairs_view(self._h, C.byref(rec), C.byref(n)), self.ctx._h)
+        return _as_array(rec, n.value, capi.JstPair, JST_PAIR_DTYPE)
+
+    def device(self):
+        """(pointer, count) of the records in HBM"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(capi.lib().spm_hip_jst_pairs_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return int(p.value or 0), int(n.value)
+
+    def stats(self) -> capi.JstPairsStats:
+        s = capi.JstPairsStats()
+        _check(capi.lib().spm_hip_jst_pairs_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_jst_pairs_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
