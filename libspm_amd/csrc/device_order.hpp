@@ -1,9 +1,17 @@
-// device_order.hpp -- the host side of "order the records, then compact them", written once for the drivers that do it
-// (select.hip, jst_select.hip, jst_locate.hpp, transcript_slots.hpp -- the slot stage of jst_project.hpp, jst_normalize.hpp and
-// jst_collapse.hpp -- those three, and jst_reads.hpp): the hipcub radix sort of (64-bit key, 32-bit index) pairs over the key's low bits, the hipcub exclusive sum
-// over any input iterator, the read-back of a call's counts, and the events a call times its stages with.  HIP, host code only: hipcub instantiates for the callers' own iterator types what
-// a direct call would.  Every function returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
+// device_order.hpp -- the host side of "order the records, then compact them", written once for the drivers that do it:
+// select.hip, jst_select.hip, jst_locate.hpp, transcript_slots.hpp (the slot stage of jst_project.hpp, jst_normalize.hpp
+// and jst_collapse.hpp), those three themselves, jst_reads.hpp and jst_pairs.hpp.  Here are
+//   the launch of a one-lane-per-item kernel on the context's stream,
+//   the hipcub radix sort of (64-bit key, 32-bit index) pairs over the key's low bits,
+//   the hipcub exclusive sum over any input iterator,
+//   the read-back of a call's counts,
+//   the events a call times its stages with,
+//   the handle of a result that is records alone (no pool).
+// HIP, host code only: hipcub instantiates for the callers' own iterator types what a direct call would.  Every function
+// returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
 #pragma once
+
+#include <vector>
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -12,6 +20,16 @@
 
 namespace spm_hip
 {
+
+// ---- kernel(args...) with one lane per item, in workgroups of Block lanes; n_items > 0.  The arguments are converted to
+// the kernel's own parameter types, as a direct call would convert them ----
+template <unsigned Block = 256, class... Params, class... Args>
+hipError_t launch_1d(spm_ctx *ctx, void (*kernel)(Params...), uint64_t n_items, Args &&...args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n_items + Block - 1) / Block)), dim3(Block), 0, ctx->stream,
+                       static_cast<Params>(args)...);
+    return hipGetLastError();
+}
 
 // ---- the sort: keys_in/idx_in -> keys_out/idx_out, stable, by bits [0, key_bits) of the key ----
 inline hipError_t sort_pairs_tmp_bytes(spm_ctx *ctx, size_t n, uint32_t key_bits, size_t *tmp_bytes)
@@ -77,6 +95,46 @@ template <int N> struct hip_events
         return r;
     }
     hipEvent_t operator[](int i) const { return e[i]; }
+};
+
+// ---- what a "records only" result handle is made of, and what its C accessors answer.  The handle derives from this ----
+template <class Rec, class Stats> struct device_records
+{
+    spm_ctx *ctx = nullptr;
+    Rec *d = nullptr; // [n]
+    uint64_t n = 0;
+    std::vector<Rec> host;
+    Stats stats{};
+
+    // h: the deriving handle (or null); work of the context's stream may still read its records
+    template <class Handle> static void destroy(Handle *h)
+    {
+        if (!h)
+            return;
+        if (h->ctx && h->d)
+            hipStreamSynchronize(h->ctx->stream);
+        hipFree(h->d);
+        delete h;
+    }
+    int view(const Rec **records, uint64_t *n_out) const { return out<Rec>(host.data(), records, n_out); }
+    int device(const void **records, uint64_t *n_out) const { return out<void>(d, records, n_out); }
+    int stats_out(Stats *s) const
+    {
+        if (!s)
+            return SPM_E_INVALID;
+        *s = stats;
+        return SPM_OK;
+    }
+
+  private:
+    template <class P> int out(const P *from, const P **records, uint64_t *n_out) const
+    {
+        if (!records || !n_out)
+            return SPM_E_INVALID;
+        *records = from;
+        *n_out = n;
+        return SPM_OK;
+    }
 };
 
 } // namespace spm_hip

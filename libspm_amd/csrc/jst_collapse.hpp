@@ -23,8 +23,9 @@
 //   jst_col_member_kernel   one lane per sorted record: n_records, score, n_haplotypes (integer atomics: any order gives the
 //                           same bytes), the member heads their haplotype, smallest score and the locus's member_off
 // The walk is quadratic in the group times the transcript length; groups are the distinct contexts over one read locus, a
-// handful.  max_run in the stats shows an input where they are not.  The scratch is laid out with scratch_layout.hpp; sorts,
-// sums, the read-back and the events are device_order.hpp's.  Every table index is tested against its size before it is read.
+// handful.  max_run in the stats shows an input where they are not.  The scratch is laid out with scratch_layout.hpp;
+// launches, sorts, sums, the read-back and the events are device_order.hpp's; what makes a record unusable (ref_aln_unusable)
+// and the slot clamp are transcript_slots.hpp's.  Every table index is tested against its size before it is read.
 #pragma once
 
 #include "jst_collapse_core.hpp"
@@ -73,22 +74,6 @@ struct jst_collapse_params
     slot_tables slots() const { return slot_tables{rep, sid, slot_rec, n_ops, cap, counts}; } // (what the slot stage takes)
 };
 
-// what makes a record unusable: tested before any of its fields indexes a table.  P: the kernels' parameters, or the three
-// limits alone -- the predicate the slot stage takes
-template <class Limits> __device__ __forceinline__ bool jcol_bad(const Limits &P, const spm_jst_ref_aln &a)
-{
-    return a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops || a.pattern >= P.n_patterns ||
-           a.ref_begin > a.ref_end || a.ref_end > P.n_ref;
-}
-
-struct jcol_unusable
-{
-    uint64_t n_ops;
-    uint32_t n_patterns;
-    uint64_t n_ref;
-    __device__ __forceinline__ bool operator()(const spm_jst_ref_aln &a) const { return jcol_bad(*this, a); }
-};
-
 __device__ __forceinline__ jst_locus_key jcol_key(const spm_jst_ref_aln &a)
 {
     jst_locus_key k;
@@ -100,23 +85,13 @@ __device__ __forceinline__ jst_locus_key jcol_key(const spm_jst_ref_aln &a)
     return k;
 }
 
-__device__ __forceinline__ uint32_t jcol_n_slots(const jst_collapse_params &P)
-{
-    return (uint32_t)min(P.counts[kColCntSlots], (unsigned long long)P.cap);
-}
-
-__device__ __forceinline__ void jcol_count_bad(const jst_collapse_params &P, bool bad)
-{
-    count_flagged(&P.counts[kColCntBad], bad);
-}
-
 __global__ __launch_bounds__(256) void jst_col_key_kernel(const jst_collapse_params P)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s >= P.cap)
         return;
     unsigned long long key = ~0ull;
-    if (s < jcol_n_slots(P)) {
+    if (s < slot_count(P.counts, P.cap)) {
         const uint32_t r = P.slot_rec[s];
         if (r < P.n) {
             const spm_jst_ref_aln a = P.recs[r];
@@ -138,7 +113,7 @@ struct jcol_view
         spm_jst_ref_aln a{};
         if (r < P.n)
             a = P.recs[r];
-        if (r >= P.n || jcol_bad(P, a)) { // (never of a counted slot; an empty transcript reads no word)
+        if (r >= P.n || ref_aln_unusable(P, a)) { // (never of a counted slot; an empty transcript reads no word)
             a = spm_jst_ref_aln{};
         }
         return a;
@@ -150,7 +125,7 @@ struct jcol_view
 __global__ __launch_bounds__(256) void jst_col_walk_kernel(const jst_collapse_params P)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t n_slots = jcol_n_slots(P);
+    const uint32_t n_slots = slot_count(P.counts, P.cap);
     if (i >= n_slots)
         return;
     const unsigned long long key = P.key[i];
@@ -172,7 +147,7 @@ __global__ __launch_bounds__(256) void jst_col_walk_kernel(const jst_collapse_pa
 __global__ __launch_bounds__(256) void jst_col_number_kernel(const jst_collapse_params P)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t n_slots = jcol_n_slots(P);
+    const uint32_t n_slots = slot_count(P.counts, P.cap);
     if (i >= n_slots)
         return;
     const uint32_t lo = P.glo[i], rank = P.rank[i];
@@ -200,7 +175,7 @@ __global__ __launch_bounds__(256) void jst_col_reckey_kernel(const jst_collapse_
     if (i < P.n) {
         const spm_jst_ref_aln a = P.recs[i];
         uint32_t locus = kSlotNone;
-        if (!jcol_bad(P, a)) {
+        if (!ref_aln_unusable(P, a)) {
             const uint32_t s = P.sid[a.cigar_off];
             const uint32_t r = s < P.cap ? P.slot_rec[s] : kSlotNone;
             // a record must say what the representative of its slot says: the content was compared through that one
@@ -212,7 +187,7 @@ __global__ __launch_bounds__(256) void jst_col_reckey_kernel(const jst_collapse_
         P.rkey_in[i] = bad ? ~0ull : ((unsigned long long)locus << 32) | a.haplotype;
         P.ridx_in[i] = (uint32_t)i;
     }
-    jcol_count_bad(P, bad);
+    count_flagged(&P.counts[kColCntBad], bad);
 }
 
 __global__ __launch_bounds__(256) void jst_col_mhead_kernel(const jst_collapse_params P)
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(256) void jst_col_locus_kernel(const jst_collapse_p
         bad = r >= P.n;
         if (!bad) {
             a = P.recs[r];
-            bad = jcol_bad(P, a) || a.cigar_len != P.loc_len[l] || off + a.cigar_len > O.n_ops;
+            bad = ref_aln_unusable(P, a) || a.cigar_len != P.loc_len[l] || off + a.cigar_len > O.n_ops;
         }
         spm_jst_ref_locus o{};
         o.score = 0x7FFFFFFF;
@@ -270,7 +245,7 @@ __global__ __launch_bounds__(256) void jst_col_locus_kernel(const jst_collapse_p
         }
         O.loci[l] = o;
     }
-    jcol_count_bad(P, bad);
+    count_flagged(&P.counts[kColCntBad], bad);
 }
 
 __global__ __launch_bounds__(256) void jst_col_member_kernel(const jst_collapse_params P, const jst_collapse_out O)
@@ -303,7 +278,7 @@ __global__ __launch_bounds__(256) void jst_col_member_kernel(const jst_collapse_
             }
         }
     }
-    jcol_count_bad(P, bad);
+    count_flagged(&P.counts[kColCntBad], bad);
 }
 
 } // namespace spm_hip
@@ -384,19 +359,39 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, cap, slot_key_bits, &b[3]));
         SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n32, rec_key_bits, &b[4]));
         const size_t tmp_bytes = *std::max_element(b, b + 5);
+        jst_collapse_params P{};
+        // (what the sorts and the sums write; the kernels read them through P's pointers to const)
+        unsigned long long *d_key = nullptr, *d_loff = nullptr, *d_rkey = nullptr;
+        uint32_t *d_idx = nullptr, *d_lsum = nullptr, *d_ridx = nullptr, *d_msum = nullptr;
+        uint8_t *d_tmp = nullptr;
         scratch_layout L;
-        const size_t c4 = (size_t)cap * 4, c8 = (size_t)cap * 8;
-        const size_t o_rep = L.take(n_src_ops * 4), o_sid = L.take(n_src_ops * 4), o_srec = L.take(c4), o_key0 = L.take(c8),
-                     o_key1 = L.take(c8), o_idx0 = L.take(c4), o_idx1 = L.take(c4), o_rank = L.take(c4), o_glo = L.take(c4),
-                     o_first = L.take(cap), o_lsum = L.take(c4), o_sloc = L.take(c4), o_lrec = L.take(c4), o_llen = L.take(c4),
-                     o_loff = L.take(c8), o_rkey0 = L.take(n * 8), o_rkey1 = L.take(n * 8), o_ridx0 = L.take(n * 4),
-                     o_ridx1 = L.take(n * 4), o_mhead = L.take(n), o_msum = L.take(n * 4), o_counts = L.take(kColCnts * 8),
-                     o_tmp = L.take(tmp_bytes);
+        L.take(P.rep, n_src_ops);
+        L.take(P.sid, n_src_ops);
+        L.take(P.slot_rec, cap);
+        L.take(P.key_in, cap);
+        L.take(d_key, cap);
+        L.take(P.idx_in, cap);
+        L.take(d_idx, cap);
+        L.take(P.rank, cap);
+        L.take(P.glo, cap);
+        L.take(P.is_first, cap);
+        L.take(d_lsum, cap);
+        L.take(P.slot_locus, cap);
+        L.take(P.loc_rec, cap);
+        L.take(P.loc_len, cap);
+        L.take(d_loff, cap);
+        L.take(P.rkey_in, n);
+        L.take(d_rkey, n);
+        L.take(P.ridx_in, n);
+        L.take(d_ridx, n);
+        L.take(P.mhead, n);
+        L.take(d_msum, n);
+        L.take(P.counts, kColCnts);
+        L.take(d_tmp, tmp_bytes);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
+        L.bind(ctx->d_scratch);
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_map, n * 4));
 
-        jst_collapse_params P{};
         P.recs = a->d_recs;
         P.n = n32;
         P.ops = a->d_ops;
@@ -405,69 +400,40 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         P.ref_bits = plan.ref_bits;
         P.n_ops = n_src_ops;
         P.cap = cap;
-        P.rep = L.at<uint32_t>(base, o_rep);
-        P.sid = L.at<uint32_t>(base, o_sid);
-        P.slot_rec = L.at<uint32_t>(base, o_srec);
-        P.key_in = L.at<unsigned long long>(base, o_key0);
-        unsigned long long *d_key = L.at<unsigned long long>(base, o_key1);
         P.key = d_key;
-        P.idx_in = L.at<uint32_t>(base, o_idx0);
-        uint32_t *d_idx = L.at<uint32_t>(base, o_idx1);
         P.idx = d_idx;
-        P.rank = L.at<uint32_t>(base, o_rank);
-        P.glo = L.at<uint32_t>(base, o_glo);
-        P.is_first = L.at<uint8_t>(base, o_first);
-        uint32_t *d_lsum = L.at<uint32_t>(base, o_lsum);
         P.lsum = d_lsum;
-        P.slot_locus = L.at<uint32_t>(base, o_sloc);
-        P.loc_rec = L.at<uint32_t>(base, o_lrec);
-        P.loc_len = L.at<uint32_t>(base, o_llen);
-        unsigned long long *d_loff = L.at<unsigned long long>(base, o_loff);
         P.loc_off = d_loff;
-        P.rkey_in = L.at<unsigned long long>(base, o_rkey0);
-        unsigned long long *d_rkey = L.at<unsigned long long>(base, o_rkey1);
         P.rkey = d_rkey;
-        P.ridx_in = L.at<uint32_t>(base, o_ridx0);
-        uint32_t *d_ridx = L.at<uint32_t>(base, o_ridx1);
         P.ridx = d_ridx;
-        P.mhead = L.at<uint8_t>(base, o_mhead);
-        uint32_t *d_msum = L.at<uint32_t>(base, o_msum);
         P.msum = d_msum;
         P.map = R->d_map;
-        unsigned long long *d_counts = P.counts = L.at<unsigned long long>(base, o_counts);
-        void *d_tmp = L.at<uint8_t>(base, o_tmp);
-        const unsigned g_rec = (unsigned)((n + 255) / 256), g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- slots: one representative per distinct slot of the source pool, numbered in pool order ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kColCnts * 8, st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kColCnts * 8, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), jcol_unusable{P.n_ops, P.n_patterns, P.n_ref}, d_tmp, tmp_bytes));
+        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), ref_aln_unusable_op{{P.n_ops, P.n_patterns, P.n_ref}},
+                                              d_tmp, tmp_bytes));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- order: groups of one (pattern, ref_begin), the rule inside a group, the locus of every slot ----
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.is_first, 0, cap, st));
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.loc_len, 0, c4, st));
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.slot_locus, 0xFF, c4, st));
-        hipLaunchKernelGGL(jst_col_key_kernel, dim3(g_slot), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.loc_len, 0, (size_t)cap * 4, st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.slot_locus, 0xFF, (size_t)cap * 4, st));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_key_kernel, cap, P));
         SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, P.key_in, d_key, P.idx_in, d_idx, cap, slot_key_bits));
-        hipLaunchKernelGGL(jst_col_walk_kernel, dim3(g_slot), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_walk_kernel, cap, P));
         SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(byte_op{P.is_first}), d_lsum, cap));
-        hipLaunchKernelGGL(jst_col_number_kernel, dim3(g_slot), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_number_kernel, cap, P));
         SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{P.loc_len}), d_loff, cap));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         // ---- records: (locus, haplotype) order, the member heads ----
-        hipLaunchKernelGGL(jst_col_reckey_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_reckey_kernel, n, P));
         SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, P.rkey_in, d_rkey, P.ridx_in, d_ridx, n32, rec_key_bits));
-        hipLaunchKernelGGL(jst_col_mhead_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_mhead_kernel, n, P));
         SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(byte_op{P.mhead}), d_msum, n32));
-        hipLaunchKernelGGL(jst_col_total_kernel, dim3(1), dim3(64), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d<64>(ctx, jst_col_total_kernel, 1, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
         // the one read-back that sizes the pools
-        SPM_HIP_CHECK(ctx, read_counts(ctx, d_counts, kColCnts));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kColCnts));
         unsigned long long *c = ctx->h_counters;
         const unsigned long long n_slots = c[kColCntSlots], n_bad = c[kColCntBad], n_loci = c[kColCntLoci],
                                  n_members = c[kColCntMembers], total = c[kColCntWords];
@@ -488,10 +454,8 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         jst_collapse_out O{R->d_loci, (uint32_t)n_loci, R->d_ops, total, R->d_members, R->d_member_scores, (uint32_t)n_members};
         // ---- emit: the loci and their transcripts, then what the records add to them ----
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
-        hipLaunchKernelGGL(jst_col_locus_kernel, dim3((unsigned)((n_loci + 255) / 256)), dim3(256), 0, st, P, O);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(jst_col_member_kernel, dim3(g_rec), dim3(256), 0, st, P, O);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_locus_kernel, n_loci, P, O));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_col_member_kernel, n, P, O));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
         // ---- the host view: a plain download; the host map goes through the slot tables ----
         slot_host_map slot(n_src_ops);
@@ -500,7 +464,7 @@ extern "C" int spm_hip_jst_ref_alns_collapse(spm_jst_ref_alns *a, uint32_t flags
         R->host_ops.resize(total);
         R->host_members.resize(n_members);
         R->host_member_scores.resize(n_members);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kColCnts * 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, kColCnts * 8, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, slot.download(ctx, P.slots()));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(sloc.data(), P.slot_locus, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d_loci, n_loci * sizeof(spm_jst_ref_locus), hipMemcpyDeviceToHost, st));

@@ -18,10 +18,12 @@
 //   jst_locate_emit_kernel  heads write the compact spm_hit list (already in pool order), every record uid[arrival] = u
 //   jst_aln_gather_kernel   one lane per kept record i: record i + seg_alns[uid[i]] -> the 40-byte spm_jst_aln i
 // Between emit and gather: jst_align_segments; the end: jst_alns_download / _close (jst.hpp's, shared with spm_hip_jst_hits_align).
-// The scratch is laid out with scratch_layout.hpp; the sort, the sum and the events are device_order.hpp's.
+// The scratch is laid out with scratch_layout.hpp; the launches, the sort, the sum and the events are device_order.hpp's; the
+// count of the flagged lanes is wave.hpp's.
 #pragma once
 
 #include "select_plan.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -123,9 +125,7 @@ __global__ __launch_bounds__(256) void jst_locate_kernel(const jst_locate_params
         P.idx[i] = (uint32_t)i;
         P.score[i] = sc;
     }
-    const unsigned long long bad = __ballot(valid && !ok);
-    if ((threadIdx.x & 63) == 0 && bad)
-        atomicAdd(&P.counts[1], (unsigned long long)__popcll(bad));
+    count_flagged(&P.counts[1], valid && !ok);
 }
 
 // One lane per sorted record: 1 where a run of equal keys begins.  Records of one run name the same segment hit, so their
@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256) void jst_locate_heads_kernel(const unsigned lo
         head[i] = first ? 1 : 0;
         bad = !first && score[idx[i]] != score[idx[i - 1]];
     }
-    const unsigned long long m = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicAdd(&counts[1], (unsigned long long)__popcll(m));
+    count_flagged(&counts[1], bad);
 }
 
 struct jloc_head_op
@@ -292,27 +290,30 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n32, plan.key_bits, &sort_bytes));
         SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jloc_head_op{nullptr}), n32, &scan_bytes));
         const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+        jst_locate_params P{};
+        unsigned long long *keys = nullptr; // (sorted; P.keys and P.idx are the sort's input)
+        uint32_t *idx = nullptr, *offs = nullptr;
+        uint8_t *head = nullptr, *d_tmp = nullptr;
+        spm_hit *d_list = nullptr;
         scratch_layout L;
-        const size_t o_keys0 = L.take(n * 8), o_keys1 = L.take(n * 8), o_idx0 = L.take(n * 4), o_idx1 = L.take(n * 4),
-                     o_score = L.take(n * 4), o_head = L.take(n), o_offs = L.take(n * 4), o_counts = L.take(16),
-                     o_tmp = L.take(tmp_bytes), o_list = L.take(n * sizeof(spm_hit));
+        L.take(P.keys, n);
+        L.take(keys, n);
+        L.take(P.idx, n);
+        L.take(idx, n);
+        L.take(P.score, n);
+        L.take(head, n);
+        L.take(offs, n);
+        L.take(P.counts, 2);
+        L.take(d_tmp, tmp_bytes);
+        L.take(d_list, n);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
-        unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0), *keys = L.at<unsigned long long>(base, o_keys1);
-        uint32_t *idx_in = L.at<uint32_t>(base, o_idx0), *idx = L.at<uint32_t>(base, o_idx1);
-        int32_t *score = L.at<int32_t>(base, o_score);
-        uint8_t *head = L.at<uint8_t>(base, o_head);
-        uint32_t *offs = L.at<uint32_t>(base, o_offs);
-        unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
-        void *d_tmp = L.at<uint8_t>(base, o_tmp);
-        spm_hit *d_list = L.at<spm_hit>(base, o_list);
+        L.bind(ctx->d_scratch);
         dev_scratch tmp;
         uint32_t *d_uid = nullptr;
         spm_aln *d_seg_alns = nullptr;
         SPM_HIP_CHECK(ctx, tmp.alloc(&d_uid, n * 4));
         SPM_HIP_CHECK(ctx, hipMalloc(&A->d_recs, n * sizeof(spm_jst_aln)));
 
-        jst_locate_params P{};
         P.recs = reinterpret_cast<const unsigned long long *>(h->d);
         P.n = n32;
         P.hap_start = J->d_hap_start;
@@ -330,28 +331,18 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         P.n_patterns = ps->n;
         P.report_begin = myers ? 0 : 1;
         P.ctx_bits = plan.ctx_bits;
-        P.keys = keys_in;
-        P.idx = idx_in;
-        P.score = score;
-        P.counts = d_counts;
-        const unsigned grid = (unsigned)((n + 255) / 256);
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 16, st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, 16, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(jst_locate_kernel, dim3(grid), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, keys_in, keys, idx_in, idx, n32, plan.key_bits));
-        hipLaunchKernelGGL(jst_locate_heads_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
-                           (const uint32_t *)idx, (const int32_t *)score, n32, head, d_counts);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_locate_kernel, n, P));
+        SPM_HIP_CHECK(ctx, sort_pairs(ctx, d_tmp, tmp_bytes, P.keys, keys, P.idx, idx, n32, plan.key_bits));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_locate_heads_kernel, n, keys, idx, P.score, n32, head, P.counts));
         SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<uint32_t>(jloc_head_op{head}), offs, n32));
-        hipLaunchKernelGGL(jst_locate_emit_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keys,
-                           (const uint32_t *)idx, (const int32_t *)score, (const uint8_t *)head, (const uint32_t *)offs, n32,
-                           plan.ctx_bits, d_list, d_uid, d_counts);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_locate_emit_kernel, n, keys, idx, P.score, head, offs, n32, plan.ctx_bits, d_list, d_uid,
+                                     P.counts));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // the one read-back: {distinct, errors}; the context tables travel with it, once per index generation
         unsigned long long *c = ctx->h_counters;
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, 16, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, 16, hipMemcpyDeviceToHost, st));
         SPM_TRY(J->fetch_ctx_tables());
         SPM_HIP_CHECK(ctx, hipStreamSynchronize(st));
         J->h_generation = J->generation;
@@ -384,10 +375,8 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
                                    &d_seg_alns));
         // ---- the gather: record i of the selection's device view -> alignment record i ----
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-        hipLaunchKernelGGL(jst_aln_gather_kernel, dim3(grid), dim3(256), 0, st, P.recs, (const uint32_t *)d_uid,
-                           (const spm_aln *)d_seg_alns, n32, (uint32_t)nk, P.report_begin,
-                           reinterpret_cast<unsigned long long *>(A->d_recs));
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_aln_gather_kernel, n, P.recs, d_uid, d_seg_alns, n32, nk, P.report_begin,
+                                     reinterpret_cast<unsigned long long *>(A->d_recs)));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
         SPM_TRY(jst_alns_download(ctx, A.get()));
         hipEventElapsedTime(&ms_locate, ev[0], ev[1]);

@@ -8,13 +8,14 @@
 //   jst_norm_walk_kernel     one lane per slot: jst_normalize_walk of jst_normalize_core.hpp with the slot's slice of a scratch
 //                            buffer of twice the source pool as its stack, [2 cigar_off, 2 (cigar_off + cigar_len)); the words
 //                            of the result, whether they differ from the source's, steps, joins, pinned runs
-//   (hipcub exclusive sum of the word counts, 64 bits; jst_norm_total_kernel)
+//   (hipcub exclusive sum of the word counts, 64 bits; slot_total_kernel)
 //   jst_norm_gather_kernel   one lane per record i: its own record + offset and length of its slot -> spm_jst_ref_aln i; a
 //                            record that disagrees with the representative of its slot is counted
 //   (the one read-back that sizes the pool: {slots, errors, words, changed, steps, joined, pinned})
 //   jst_norm_compact_kernel  one lane per slot: its slice -> its place in the pool
-// The scratch is laid out with scratch_layout.hpp; the sums, the read-back and the events are device_order.hpp's.  Every
-// needle, reference and pool index is tested against its size before it is read.
+// The scratch is laid out with scratch_layout.hpp; the launches, the sums, the read-back and the events are
+// device_order.hpp's; what makes a record unusable (ref_aln_unusable), the slot clamp and the total kernel are
+// transcript_slots.hpp's.  Every needle, reference and pool index is tested against its size before it is read.
 #pragma once
 
 #include "jst_normalize_core.hpp"
@@ -54,22 +55,6 @@ struct jst_normalize_params
     slot_tables slots() const { return slot_tables{rep, sid, slot_rec, n_ops, cap, counts}; } // (what the slot stage takes)
 };
 
-// what makes a record unusable: tested before any of its fields indexes a table (the three limits are the kernels'
-// parameters', or stand alone as the predicate the slot stage takes)
-template <class Limits> __device__ __forceinline__ bool jnorm_bad(const Limits &P, const spm_jst_ref_aln &a)
-{
-    return a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops || a.pattern >= P.n_patterns ||
-           a.ref_begin > a.ref_end || a.ref_end > P.n_ref;
-}
-
-struct jnorm_unusable
-{
-    uint64_t n_ops;
-    uint32_t n_patterns;
-    uint64_t n_ref;
-    __device__ __forceinline__ bool operator()(const spm_jst_ref_aln &a) const { return jnorm_bad(*this, a); }
-};
-
 // a slot's slice of the stack buffer
 struct jnorm_slice
 {
@@ -80,23 +65,18 @@ struct jnorm_slice
     __device__ __forceinline__ void put(uint64_t k, uint32_t v) { w[k] = v; }
 };
 
-__device__ __forceinline__ uint32_t jnorm_n_slots(const jst_normalize_params &P)
-{
-    return (uint32_t)min(P.counts[kNormCntSlots], (unsigned long long)P.cap);
-}
-
 __global__ __launch_bounds__(256) void jst_norm_walk_kernel(const jst_normalize_params P)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     bool bad = false, changed = false;
     unsigned long long steps = 0, joined = 0, pinned = 0;
-    if (s < jnorm_n_slots(P)) {
+    if (s < slot_count(P.counts, P.cap)) {
         const uint32_t ri = P.slot_rec[s];
         spm_jst_ref_aln a{};
         bad = ri >= P.n;
         if (!bad) {
             a = P.recs[ri];
-            bad = jnorm_bad(P, a);
+            bad = ref_aln_unusable(P, a);
         }
         const int32_t m = bad ? 0 : P.m[a.pattern];
         bad = bad || m <= 0;
@@ -128,14 +108,6 @@ __global__ __launch_bounds__(256) void jst_norm_walk_kernel(const jst_normalize_
         atomicAdd(&P.counts[kNormCntPinned], pinned);
 }
 
-__global__ void jst_norm_total_kernel(const jst_normalize_params P)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint32_t n_slots = jnorm_n_slots(P);
-        P.counts[kNormCntWords] = n_slots ? P.slot_off[n_slots - 1] + P.slot_words[n_slots - 1] : 0ull;
-    }
-}
-
 __global__ __launch_bounds__(256) void jst_norm_gather_kernel(const jst_normalize_params P)
 {
     const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
@@ -143,7 +115,7 @@ __global__ __launch_bounds__(256) void jst_norm_gather_kernel(const jst_normaliz
     if (i < P.n) {
         spm_jst_ref_aln o = P.recs[i];
         bad = true;
-        if (!jnorm_bad(P, o)) {
+        if (!ref_aln_unusable(P, o)) {
             const uint32_t s = P.sid[o.cigar_off];
             const uint32_t r = s < P.cap ? P.slot_rec[s] : kSlotNone;
             if (r < P.n) {
@@ -169,14 +141,14 @@ __global__ __launch_bounds__(256) void jst_norm_compact_kernel(const jst_normali
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     bool bad = false;
-    if (s < jnorm_n_slots(P)) {
+    if (s < slot_count(P.counts, P.cap)) {
         const uint32_t ri = P.slot_rec[s];
         const unsigned long long off = P.slot_off[s];
         const uint32_t nw = P.slot_words[s];
         bad = ri >= P.n || off + nw > pool_words;
         if (!bad) {
             const spm_jst_ref_aln a = P.recs[ri];
-            bad = jnorm_bad(P, a) || nw > 2 * (uint64_t)a.cigar_len;
+            bad = ref_aln_unusable(P, a) || nw > 2 * (uint64_t)a.cigar_len;
             if (!bad) {
                 const uint32_t *src = P.stack + 2 * (uint64_t)a.cigar_off;
                 for (uint32_t w = 0; w < nw; ++w)
@@ -241,19 +213,22 @@ extern "C" int spm_hip_jst_ref_alns_normalize(spm_jst_ref_alns *a, uint32_t flag
         SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(widen_op{nullptr}), cap,
                                                                        &b_wide));
         const size_t tmp_bytes = std::max(b_flag, b_wide);
+        jst_normalize_params P{};
+        unsigned long long *d_off = nullptr; // (P.slot_off, writable for the sum)
+        uint8_t *d_tmp = nullptr;
         scratch_layout L;
-        const size_t o_rep = L.take(n_src_ops * 4), o_sid = L.take(n_src_ops * 4), o_rec = L.take((size_t)cap * 4),
-                     o_stack = L.take(n_src_ops * 8), o_words = L.take((size_t)cap * 4), o_off = L.take((size_t)cap * 8),
-                     o_counts = L.take(kNormCnts * 8), o_tmp = L.take(tmp_bytes);
+        L.take(P.rep, n_src_ops);
+        L.take(P.sid, n_src_ops);
+        L.take(P.slot_rec, cap);
+        L.take(P.stack, 2 * n_src_ops);
+        L.take(P.slot_words, cap);
+        L.take(d_off, cap);
+        L.take(P.counts, kNormCnts);
+        L.take(d_tmp, tmp_bytes);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
-        uint32_t *d_words = L.at<uint32_t>(base, o_words);
-        unsigned long long *d_off = L.at<unsigned long long>(base, o_off);
-        unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
-        void *d_tmp = L.at<uint8_t>(base, o_tmp);
+        L.bind(ctx->d_scratch);
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_recs, n * sizeof(spm_jst_ref_aln)));
 
-        jst_normalize_params P{};
         P.recs = a->d_recs;
         P.n = n32;
         P.ops = a->d_ops;
@@ -265,37 +240,27 @@ extern "C" int spm_hip_jst_ref_alns_normalize(spm_jst_ref_alns *a, uint32_t flag
         P.m = ps->d_m;
         P.n_patterns = std::min(ps->n, a->n_patterns);
         P.cap = cap;
-        P.rep = L.at<uint32_t>(base, o_rep);
-        P.sid = L.at<uint32_t>(base, o_sid);
-        P.slot_rec = L.at<uint32_t>(base, o_rec);
-        P.stack = L.at<uint32_t>(base, o_stack);
-        P.slot_words = d_words;
         P.slot_off = d_off;
-        P.counts = d_counts;
         P.out = R->d_recs;
-        const unsigned g_rec = (unsigned)((n + 255) / 256), g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- slots: one representative per distinct slot of the source pool, numbered in pool order ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kNormCnts * 8, st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kNormCnts * 8, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), jnorm_unusable{P.n_ops, P.n_patterns, P.n_ref}, d_tmp,
-                                              tmp_bytes));
+        SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), ref_aln_unusable_op{{P.n_ops, P.n_patterns, P.n_ref}},
+                                              d_tmp, tmp_bytes));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- normalise: the rule on every slot, in its slice of the stack buffer ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_words, 0, (size_t)cap * 4, st));
-        hipLaunchKernelGGL(jst_norm_walk_kernel, dim3(g_slot), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.slot_words, 0, (size_t)cap * 4, st));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_norm_walk_kernel, cap, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         // ---- offsets: where every slot's words go, and how many there are ----
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{d_words}), d_off, cap));
-        hipLaunchKernelGGL(jst_norm_total_kernel, dim3(1), dim3(64), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{P.slot_words}), d_off, cap));
+        SPM_HIP_CHECK(ctx, launch_1d<64>(ctx, slot_total_kernel, 1, P.counts, cap, P.slot_off, P.slot_words, kNormCntWords));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
         // ---- gather: one record per source record (it needs the offsets, not the pool) ----
-        hipLaunchKernelGGL(jst_norm_gather_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_norm_gather_kernel, n, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
         // the one read-back that sizes the pool: {slots, errors, words, changed, steps, joined, pinned}
-        SPM_HIP_CHECK(ctx, read_counts(ctx, d_counts, kNormCnts));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kNormCnts));
         unsigned long long *c = ctx->h_counters;
         const unsigned long long n_slots = c[kNormCntSlots], n_bad = c[kNormCntBad], total = c[kNormCntWords];
         if (n_bad || n_slots == 0 || n_slots > cap || total > 2 * n_src_ops) {
@@ -318,18 +283,16 @@ extern "C" int spm_hip_jst_ref_alns_normalize(spm_jst_ref_alns *a, uint32_t flag
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_ops, std::max<uint64_t>(total, 1) * 4));
         // ---- compact: the slices into the pool ----
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
-        hipLaunchKernelGGL(jst_norm_compact_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, P, R->d_ops,
-                           (uint64_t)total);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_norm_compact_kernel, n_slots, P, R->d_ops, total));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[6], st));
         // ---- the host view: record i of the source's host view through the slot tables ----
         slot_host_map slot(n_src_ops);
         std::vector<uint32_t> words(n_slots);
         std::vector<unsigned long long> woff(n_slots);
         R->host_ops.resize(total);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kNormCnts * 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, kNormCnts * 8, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, slot.download(ctx, P.slots()));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), d_words, n_slots * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), P.slot_words, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(woff.data(), d_off, n_slots * 8, hipMemcpyDeviceToHost, st));
         if (total)
             SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host_ops.data(), R->d_ops, total * 4, hipMemcpyDeviceToHost, st));

@@ -1,15 +1,16 @@
 // jst_pairs.hpp -- the mates of paired-end reads (spm_hip_jst_ref_loci_pairs; contract in spm_hip.h, scheme in DESIGN.md 4.9,
-// the rule in jst_pairs_core.hpp).  gfx950.  Included by jst.hip behind jst_reads.hpp, whose spm_jst_reads and segmented scan it
-// uses.  The loci of pair p are the contiguous patterns 4p .. 4p + 3, and the read summary holds the bounds of the four
+// the rule in jst_pairs_core.hpp).  gfx950.  Included by jst.hip behind jst_reads.hpp, whose spm_jst_reads it reads.  The
+// loci of pair p are the contiguous patterns 4p .. 4p + 3, and the read summary holds the bounds of the four
 // sub-runs, so pairing is a walk of a window of the other mate's reverse run, found by a lower bound:
 //   jst_pairs_best_kernel   one lane per locus.  A lane on a forward locus a walks its partner window, keeps its best partner
-//                           in partner[a] and packs (uint32) sum << 32 | a; the segmented scan of jreads_run_scan, keyed on the
-//                           pair, leaves every run's minimal key in the run's last lane: one 64-bit atomicMin per wave and run.
-//                           Reverse lanes take part with the empty key.  The longest window goes to max_window;
+//                           in partner[a] and packs (uint32) sum << 32 | a; the segmented scan of wave.hpp (wave_run_scan),
+//                           keyed on the pair, leaves every run's minimal key in the run's last lane: one 64-bit atomicMin
+//                           per wave and run.  Reverse lanes take part with the empty key.  The longest window goes to
+//                           max_window;
 //   jst_pairs_count_kernel  the same lanes, the same walk: n_pairs / n_best / n_next against the settled minimum, summed in
 //                           64 bits by the same scan: three atomicAdd per wave and run;
 //   jst_pairs_emit_kernel   one lane per pair: unpacks the key, reads partner, writes the record and the flags, falls back
-//                           to the read summary's primaries, counts the statistics by ballot.
+//                           to the read summary's primaries, counts each statistic with count_flagged.
 // Every record of the read summary is tested against the loci before it is used as an index (jst_pairs_read_ok,
 // jst_pairs_covers); what disagrees is counted and fails the call.  Minima and sums do not depend on the order the atomics
 // land in: the records are byte-identical across runs.
@@ -21,6 +22,7 @@
 #include "device_order.hpp"
 #include "jst_pairs_core.hpp"
 #include "scratch_layout.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -75,28 +77,18 @@ __device__ __forceinline__ int jpairs_lane(const jst_pairs_params &P, uint32_t i
     return kPairsLaneForward;
 }
 
-struct jpairs_sums
+// what jst_pairs_count_kernel carries through the scan over a pair's run, in 64 bits
+struct jpairs_count_run
 {
-    unsigned long long a, b, c;
-    bool ends;
-};
-
-// jreads_run_scan over three 64-bit sums: the last lane of every run of equal `pair` (ends) holds the run's sums.  All lanes call.
-__device__ __forceinline__ jpairs_sums jpairs_run_sums(uint32_t pair, unsigned long long a, unsigned long long b, unsigned long long c)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long a2 = __shfl_up(a, d), b2 = __shfl_up(b, d), c2 = __shfl_up(c, d);
-        const uint32_t p2 = __shfl_up(pair, d);
-        if (lane >= (uint32_t)d && p2 == pair) {
-            a += a2;
-            b += b2;
-            c += c2;
-        }
+    run_sum<unsigned long long> n_pairs, n_best, n_next;
+    __device__ __forceinline__ jpairs_count_run up(int d) const { return {n_pairs.up(d), n_best.up(d), n_next.up(d)}; }
+    __device__ __forceinline__ void join(const jpairs_count_run &l, bool take)
+    {
+        n_pairs.join(l.n_pairs, take);
+        n_best.join(l.n_best, take);
+        n_next.join(l.n_next, take);
     }
-    const uint32_t p_next = __shfl_down(pair, 1);
-    return jpairs_sums{a, b, c, lane == 63 || p_next != pair};
-}
+};
 
 __global__ __launch_bounds__(256) void jst_pairs_best_kernel(const jst_pairs_params P)
 {
@@ -119,13 +111,11 @@ __global__ __launch_bounds__(256) void jst_pairs_best_kernel(const jst_pairs_par
             }
         }
     }
-    const jreads_run R = jreads_run_scan(pair, key, 0u, 0u);
-    if (pair != kPairsNoPair && R.ends && R.key != kJstPairsNoKey)
-        atomicMin(&P.minkey[pair], R.key);
-    for (int d = 32; d; d >>= 1) {
-        const uint32_t w2 = __shfl_xor(window, d);
-        window = w2 > window ? w2 : window;
-    }
+    run_min<unsigned long long> R{key};
+    const bool ends = wave_run_scan(pair, R);
+    if (pair != kPairsNoPair && ends && R.v != kJstPairsNoKey)
+        atomicMin(&P.minkey[pair], R.v);
+    window = wave_max(window);
     if ((threadIdx.x & 63) == 0 && window)
         atomicMax(&P.counts[kPairsCntMaxWindow], (unsigned long long)window);
     if (bad) // (a fault of the input, not a path to be fast on)
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(256) void jst_pairs_count_kernel(const jst_pairs_pa
 {
     const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
     uint32_t pair = kPairsNoPair;
-    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    jpairs_count_run S{{0}, {0}, {0}};
     if (i < P.n) {
         uint32_t lo = 0, hi = 0;
         const int what = jpairs_lane(P, (uint32_t)i, pair, lo, hi);
@@ -147,20 +137,20 @@ __global__ __launch_bounds__(256) void jst_pairs_count_kernel(const jst_pairs_pa
             if (key != kJstPairsNoKey) {
                 const jst_pairs_walked W = jst_pairs_walk(P.loci, (uint32_t)i, lo, hi, P.min_tlen, P.max_tlen,
                                                           (long long)jst_pairs_key_sum(key));
-                c0 = W.n_pairs;
-                c1 = W.n_best;
-                c2 = W.n_next;
+                S.n_pairs.v = W.n_pairs;
+                S.n_best.v = W.n_best;
+                S.n_next.v = W.n_next;
             }
         }
     }
-    const jpairs_sums S = jpairs_run_sums(pair, c0, c1, c2);
-    if (pair != kPairsNoPair && S.ends) {
-        if (S.a)
-            atomicAdd(&P.sums[3ull * pair], S.a);
-        if (S.b)
-            atomicAdd(&P.sums[3ull * pair + 1], S.b);
-        if (S.c)
-            atomicAdd(&P.sums[3ull * pair + 2], S.c);
+    const bool ends = wave_run_scan(pair, S);
+    if (pair != kPairsNoPair && ends) {
+        if (S.n_pairs.v)
+            atomicAdd(&P.sums[3ull * pair], S.n_pairs.v);
+        if (S.n_best.v)
+            atomicAdd(&P.sums[3ull * pair + 1], S.n_best.v);
+        if (S.n_next.v)
+            atomicAdd(&P.sums[3ull * pair + 2], S.n_next.v);
     }
 }
 
@@ -190,36 +180,24 @@ __global__ __launch_bounds__(256) void jst_pairs_emit_kernel(const jst_pairs_par
         }
         P.pairs[p] = O;
     }
-    const bool what[7] = {bad, proper, unique, multi, discordant, one_mate, unmapped};
-    for (int c = 0; c < 7; ++c) { // (kPairsCntBad .. kPairsCntUnmapped, in the enum's order)
-        const unsigned long long m = __ballot(what[c]);
-        if ((threadIdx.x & 63) == 0 && m)
-            atomicAdd(&P.counts[c], (unsigned long long)__popcll(m));
-    }
+    count_flagged(&P.counts[kPairsCntBad], bad);
+    count_flagged(&P.counts[kPairsCntProper], proper);
+    count_flagged(&P.counts[kPairsCntUnique], unique);
+    count_flagged(&P.counts[kPairsCntMulti], multi);
+    count_flagged(&P.counts[kPairsCntDiscordant], discordant);
+    count_flagged(&P.counts[kPairsCntOneMate], one_mate);
+    count_flagged(&P.counts[kPairsCntUnmapped], unmapped);
 }
 
 } // namespace spm_hip
 
-struct spm_jst_pairs
+struct spm_jst_pairs : spm_hip::device_records<spm_jst_pair, spm_jst_pairs_stats>
 {
-    spm_ctx *ctx = nullptr;
-    spm_jst_pair *d_pairs = nullptr;
-    uint64_t n = 0;
-    std::vector<spm_jst_pair> host;
-    spm_jst_pairs_stats stats{};
 };
 static_assert(sizeof(spm_jst_pair_opts) == 16 && sizeof(spm_jst_pair) == 32 && sizeof(spm_jst_pairs_stats) == 72,
               "spm_hip.h states these sizes");
 
-extern "C" void spm_hip_jst_pairs_destroy(spm_jst_pairs *p)
-{
-    if (!p)
-        return;
-    if (p->ctx && p->d_pairs)
-        hipStreamSynchronize(p->ctx->stream);
-    hipFree(p->d_pairs);
-    delete p;
-}
+extern "C" void spm_hip_jst_pairs_destroy(spm_jst_pairs *p) { spm_jst_pairs::destroy(p); }
 
 extern "C" int spm_hip_jst_ref_loci_pairs(spm_jst_ref_loci *l, spm_jst_reads *r, const spm_jst_pair_opts *opts, spm_jst_pairs **out)
 {
@@ -276,36 +254,30 @@ extern "C" int spm_hip_jst_ref_loci_pairs(spm_jst_ref_loci *l, spm_jst_reads *r,
         P.loci = l->d_loci;
         P.n = l->d_loci ? (uint32_t)l->n : 0u;
         scratch_layout L;
-        const size_t o_min = L.take((size_t)n_pairs * 8), o_sums = L.take((size_t)n_pairs * 24), o_partner = L.take((size_t)P.n * 4),
-                     o_counts = L.take(kPairsCnts * 8);
+        L.take(P.minkey, n_pairs);
+        L.take(P.sums, 3 * (size_t)n_pairs);
+        L.take(P.partner, P.n);
+        L.take(P.counts, kPairsCnts);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
-        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_pairs, (size_t)n_pairs * sizeof(spm_jst_pair)));
-        P.reads = r->d_reads;
+        L.bind(ctx->d_scratch);
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d, (size_t)n_pairs * sizeof(spm_jst_pair)));
+        P.reads = r->d;
         P.n_reads = n_reads;
         P.min_tlen = opts->min_tlen;
         P.max_tlen = opts->max_tlen;
-        P.minkey = L.at<unsigned long long>(base, o_min);
-        P.sums = L.at<unsigned long long>(base, o_sums);
-        P.partner = L.at<uint32_t>(base, o_partner);
-        P.pairs = R->d_pairs;
-        P.counts = L.at<unsigned long long>(base, o_counts);
+        P.pairs = R->d;
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.minkey, 0xFF, (size_t)n_pairs * 8, st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.sums, 0, (size_t)n_pairs * 24, st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kPairsCnts * 8, st));
         if (P.n) {
-            const unsigned g_loci = (unsigned)(((uint64_t)P.n + 255) / 256);
-            hipLaunchKernelGGL(jst_pairs_best_kernel, dim3(g_loci), dim3(256), 0, st, P);
-            SPM_HIP_CHECK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(jst_pairs_count_kernel, dim3(g_loci), dim3(256), 0, st, P);
-            SPM_HIP_CHECK(ctx, hipGetLastError());
+            SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_pairs_best_kernel, P.n, P));
+            SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_pairs_count_kernel, P.n, P));
         }
-        hipLaunchKernelGGL(jst_pairs_emit_kernel, dim3((unsigned)(((uint64_t)n_pairs + 255) / 256)), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_pairs_emit_kernel, n_pairs, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         R->host.resize(n_pairs);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d_pairs, (size_t)n_pairs * sizeof(spm_jst_pair), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d, (size_t)n_pairs * sizeof(spm_jst_pair), hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kPairsCnts)); // (synchronises: the host view has arrived too)
         const unsigned long long *c = ctx->h_counters;
         if (c[kPairsCntBad]) {
@@ -336,26 +308,15 @@ extern "C" int spm_hip_jst_ref_loci_pairs(spm_jst_ref_loci *l, spm_jst_reads *r,
 
 extern "C" int spm_hip_jst_pairs_view(spm_jst_pairs *p, const spm_jst_pair **records, uint64_t *n)
 {
-    if (!p || !records || !n)
-        return SPM_E_INVALID;
-    *records = p->host.data();
-    *n = p->n;
-    return SPM_OK;
+    return p ? p->view(records, n) : SPM_E_INVALID;
 }
 
 extern "C" int spm_hip_jst_pairs_device(spm_jst_pairs *p, const void **records, uint64_t *n)
 {
-    if (!p || !records || !n)
-        return SPM_E_INVALID;
-    *records = p->d_pairs;
-    *n = p->n;
-    return SPM_OK;
+    return p ? p->device(records, n) : SPM_E_INVALID;
 }
 
 extern "C" int spm_hip_jst_pairs_stats(const spm_jst_pairs *p, spm_jst_pairs_stats *out)
 {
-    if (!p || !out)
-        return SPM_E_INVALID;
-    *out = p->stats;
-    return SPM_OK;
+    return p ? p->stats_out(out) : SPM_E_INVALID;
 }

@@ -8,11 +8,11 @@
 //   jst_proj_count_kernel    one lane per slot: the block of its haplotype that holds `begin` (binary search down column h of
 //                            hap_start), the journal walked from jst_first_ref / a_lo up to begin, then jst_project_compose
 //                            with a counting sink: words, ref_begin, ref_end, ref_score
-//   (hipcub exclusive sum of the word counts, 64 bits; jst_proj_total_kernel; the one read-back that sizes the pool)
+//   (hipcub exclusive sum of the word counts, 64 bits; slot_total_kernel; the one read-back that sizes the pool)
 //   jst_proj_emit_kernel     the same walk with a writing sink
 //   jst_proj_gather_kernel   one lane per record i: its own record + the result of its slot -> spm_jst_ref_aln i
-// The scratch is laid out with scratch_layout.hpp; the sums, the first read-back and the events are device_order.hpp's; the
-// ballot-and-count of the flagged lanes is transcript_slots.hpp's.
+// The scratch is laid out with scratch_layout.hpp; the launches, the sums, the first read-back and the events are
+// device_order.hpp's; the slot clamp and the total kernel are transcript_slots.hpp's, the count of the flagged lanes wave.hpp's.
 // The walk starts from the tables of the index and runs forward as far as the transcript reaches: it assumes neither that a
 // carried deletion ends inside its block nor that begin and end lie in the same block.
 #pragma once
@@ -115,7 +115,7 @@ __device__ __forceinline__ bool jproj_run(const jst_project_params &P, uint32_t 
 __global__ __launch_bounds__(256) void jst_proj_count_kernel(const jst_project_params P)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
+    const uint32_t n_slots = slot_count(P.counts, P.cap);
     bool bad = false, inside = false;
     if (s < n_slots) {
         jst_proj_count_sink S;
@@ -132,19 +132,11 @@ __global__ __launch_bounds__(256) void jst_proj_count_kernel(const jst_project_p
     count_flagged(&P.counts[kProjCntInside], inside);
 }
 
-__global__ void jst_proj_total_kernel(const jst_project_params P)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
-        P.counts[kProjCntWords] = n_slots ? P.slot_off[n_slots - 1] + P.slot_words[n_slots - 1] : 0ull;
-    }
-}
-
 // pool_words: the size of out_ops, which the host allocated from the total the count stage found
 __global__ __launch_bounds__(256) void jst_proj_emit_kernel(const jst_project_params P, uint64_t pool_words)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t n_slots = (uint32_t)min(P.counts[kProjCntSlots], (unsigned long long)P.cap);
+    const uint32_t n_slots = slot_count(P.counts, P.cap);
     bool bad = false, changed = false;
     if (s < n_slots) {
         const unsigned long long off = P.slot_off[s];
@@ -285,19 +277,23 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<unsigned long long>(ctx, counted<unsigned long long>(widen_op{nullptr}), cap,
                                                                        &b_wide));
         const size_t tmp_bytes = std::max(b_flag, b_wide);
+        jst_project_params P{};
+        unsigned long long *d_off = nullptr; // (P.slot_off, writable for the sum)
+        uint8_t *d_tmp = nullptr;
         scratch_layout L;
-        const size_t o_rep = L.take(n_src_ops * 4), o_sid = L.take(n_src_ops * 4), o_rec = L.take((size_t)cap * 4),
-                     o_range = L.take((size_t)cap * 16), o_words = L.take((size_t)cap * 4), o_score = L.take((size_t)cap * 4),
-                     o_off = L.take((size_t)cap * 8), o_counts = L.take(kProjCnts * 8), o_tmp = L.take(tmp_bytes);
+        L.take(P.rep, n_src_ops);
+        L.take(P.sid, n_src_ops);
+        L.take(P.slot_rec, cap);
+        L.take(P.slot_range, 2 * (size_t)cap);
+        L.take(P.slot_words, cap);
+        L.take(P.slot_score, cap);
+        L.take(d_off, cap);
+        L.take(P.counts, kProjCnts);
+        L.take(d_tmp, tmp_bytes);
         SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
-        uint32_t *d_words = L.at<uint32_t>(base, o_words);
-        unsigned long long *d_off = L.at<unsigned long long>(base, o_off);
-        unsigned long long *d_counts = L.at<unsigned long long>(base, o_counts);
-        void *d_tmp = L.at<uint8_t>(base, o_tmp);
+        L.bind(ctx->d_scratch);
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_recs, n * sizeof(spm_jst_ref_aln)));
 
-        jst_project_params P{};
         P.J = J->dev();
         P.recs = a->d_recs;
         P.n = n32;
@@ -308,32 +304,22 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         P.n_patterns = ps->n;
         P.n_ops = n_src_ops;
         P.cap = cap;
-        P.rep = L.at<uint32_t>(base, o_rep);
-        P.sid = L.at<uint32_t>(base, o_sid);
-        P.slot_rec = L.at<uint32_t>(base, o_rec);
-        P.counts = d_counts;
-        P.slot_range = L.at<unsigned long long>(base, o_range);
-        P.slot_words = d_words;
-        P.slot_score = L.at<int32_t>(base, o_score);
         P.slot_off = d_off;
         P.out_ops = nullptr;
         P.out = R->d_recs;
-        const unsigned g_rec = (unsigned)((n + 255) / 256), g_slot = (unsigned)(((uint64_t)cap + 255) / 256);
         // ---- representatives: one per distinct slot of the source pool, numbered in pool order ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, kProjCnts * 8, st));
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kProjCnts * 8, st));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         SPM_HIP_CHECK(ctx, slot_stage_enqueue(ctx, P.recs, n32, P.slots(), jproj_unusable{n_src_ops}, d_tmp, tmp_bytes));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         // ---- count: the projection of every slot with a counting sink, then where its words go ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(d_words, 0, (size_t)cap * 4, st));
-        hipLaunchKernelGGL(jst_proj_count_kernel, dim3(g_slot), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{d_words}), d_off, cap));
-        hipLaunchKernelGGL(jst_proj_total_kernel, dim3(1), dim3(64), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.slot_words, 0, (size_t)cap * 4, st));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_proj_count_kernel, cap, P));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp_bytes, counted<unsigned long long>(widen_op{P.slot_words}), d_off, cap));
+        SPM_HIP_CHECK(ctx, launch_1d<64>(ctx, slot_total_kernel, 1, P.counts, cap, P.slot_off, P.slot_words, kProjCntWords));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
         // the one read-back that sizes the pool: {slots, errors, inside an insertion, -, words}
-        SPM_HIP_CHECK(ctx, read_counts(ctx, d_counts, kProjCnts));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kProjCnts));
         unsigned long long *c = ctx->h_counters;
         n_slots = c[kProjCntSlots];
         const unsigned long long n_bad = c[kProjCntBad], total = c[kProjCntWords];
@@ -353,11 +339,9 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         P.out_ops = R->d_ops;
         // ---- emit, gather ----
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
-        hipLaunchKernelGGL(jst_proj_emit_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, P, (uint64_t)total);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_proj_emit_kernel, n_slots, P, total));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
-        hipLaunchKernelGGL(jst_proj_gather_kernel, dim3(g_rec), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_proj_gather_kernel, n, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
         // ---- the host view: record i of the source's host view through the slot tables ----
         slot_host_map slot(n_src_ops);
@@ -365,9 +349,9 @@ extern "C" int spm_hip_jst_alns_project(spm_jst_alns *a, uint32_t flags, spm_jst
         std::vector<int32_t> score(n_slots);
         std::vector<unsigned long long> range(2 * n_slots), woff(n_slots);
         R->host_ops.resize(total);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, d_counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(c, P.counts, kProjCnts * 8, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, slot.download(ctx, P.slots()));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), d_words, n_slots * 4, hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(words.data(), P.slot_words, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(score.data(), P.slot_score, n_slots * 4, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(range.data(), P.slot_range, n_slots * 16, hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(woff.data(), d_off, n_slots * 8, hipMemcpyDeviceToHost, st));

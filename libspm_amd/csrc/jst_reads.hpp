@@ -2,15 +2,16 @@
 // rule in jst_reads_core.hpp).  gfx950.  Included by jst.hip behind jst_collapse.hpp, whose spm_jst_ref_loci it reads.
 // The loci of a collapse are ordered by pattern, so the loci of one read are one contiguous run.  Work is proportional to
 // loci + reads, and a read with 10^5 loci is 10^5 lanes, not a loop:
-//   jst_reads_min_kernel    one lane per locus: a segmented scan over the wave (the sel_run_min idiom of select_walk.hpp, here
-//                           over a 64-bit key and two counts) leaves, in the last lane of every run of one read, the run's
+//   jst_reads_min_kernel    one lane per locus: the segmented scan over the wave (wave_run_scan of wave.hpp, here over a
+//                           64-bit key and two counts) leaves, in the last lane of every run of one read, the run's
 //                           minimal key (uint32) score << 32 | locus and its n_loci / n_forward: one atomicMin and two
 //                           atomicAdd per wave and run.  The head of a read's run writes first_locus.  Unusable loci are
 //                           counted and index nothing;
-//   jst_reads_count_kernel  one lane per locus, the same scan: n_best / n_next against the settled minimum;
+//   jst_reads_count_kernel  one lane per locus, the same scan over two counts: n_best / n_next against the settled minimum;
 //   jst_reads_emit_kernel   one lane per read: unpacks the key, reads the primary's ref_score, finds where a read without
 //                           loci would stand (a lower bound over the patterns), counts mapped / unique / multi reads.
 // Minima and counts do not depend on the order the atomics land in: the records are byte-identical across runs.
+// The handle is a device_records (device_order.hpp), as are the launches, the events and the read-back.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "device_order.hpp"
 #include "jst_reads_core.hpp"
 #include "scratch_layout.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -37,30 +39,31 @@ struct jst_reads_params
     unsigned long long *counts = nullptr; // [kReadsCnts]
 };
 
-struct jreads_run
+// what jst_reads_min_kernel carries through the scan over a read's run: the minimal key, and n_loci / n_forward
+struct jreads_min_run
 {
-    unsigned long long key;
-    uint32_t a, b;
-    bool ends;
+    run_min<unsigned long long> key;
+    run_sum<uint32_t> n_loci, n_forward;
+    __device__ __forceinline__ jreads_min_run up(int d) const { return {key.up(d), n_loci.up(d), n_forward.up(d)}; }
+    __device__ __forceinline__ void join(const jreads_min_run &l, bool take)
+    {
+        key.join(l.key, take);
+        n_loci.join(l.n_loci, take);
+        n_forward.join(l.n_forward, take);
+    }
 };
 
-// Lanes of one read are contiguous.  Inclusive segmented scan over the wave: the last lane of every run of equal `read`
-// (ends) holds the run's minimal key and the sums of a and b.  All lanes call.
-__device__ __forceinline__ jreads_run jreads_run_scan(uint32_t read, unsigned long long key, uint32_t a, uint32_t b)
+// ... and jst_reads_count_kernel: n_best / n_next
+struct jreads_count_run
 {
-    const uint32_t lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long k2 = __shfl_up(key, d);
-        const uint32_t a2 = __shfl_up(a, d), b2 = __shfl_up(b, d), r2 = __shfl_up(read, d);
-        if (lane >= (uint32_t)d && r2 == read) {
-            key = k2 < key ? k2 : key;
-            a += a2;
-            b += b2;
-        }
+    run_sum<uint32_t> n_best, n_next;
+    __device__ __forceinline__ jreads_count_run up(int d) const { return {n_best.up(d), n_next.up(d)}; }
+    __device__ __forceinline__ void join(const jreads_count_run &l, bool take)
+    {
+        n_best.join(l.n_best, take);
+        n_next.join(l.n_next, take);
     }
-    const uint32_t r_next = __shfl_down(read, 1);
-    return jreads_run{key, a, b, lane == 63 || r_next != read};
-}
+};
 
 // the read of locus i, or kReadsNoRead for an unusable one; score: its score
 __device__ __forceinline__ uint32_t jreads_read_of(const jst_reads_params &P, uint32_t i, uint32_t &pattern, int32_t &score)
@@ -89,16 +92,15 @@ __global__ __launch_bounds__(256) void jst_reads_min_kernel(const jst_reads_para
                 P.reads[read].first_locus = (uint32_t)i;
         }
     }
-    const jreads_run R = jreads_run_scan(read, key, cnt, fwd);
-    if (read != kReadsNoRead && R.ends) {
-        atomicMin(&P.minkey[read], R.key);
-        atomicAdd(&P.reads[read].n_loci, R.a);
-        if (R.b)
-            atomicAdd(&P.reads[read].n_forward, R.b);
+    jreads_min_run R{{key}, {cnt}, {fwd}};
+    const bool ends = wave_run_scan(read, R);
+    if (read != kReadsNoRead && ends) {
+        atomicMin(&P.minkey[read], R.key.v);
+        atomicAdd(&P.reads[read].n_loci, R.n_loci.v);
+        if (R.n_forward.v)
+            atomicAdd(&P.reads[read].n_forward, R.n_forward.v);
     }
-    const unsigned long long bad_mask = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && bad_mask)
-        atomicAdd(&P.counts[kReadsCntBad], (unsigned long long)__popcll(bad_mask));
+    count_flagged(&P.counts[kReadsCntBad], bad);
 }
 
 __global__ __launch_bounds__(256) void jst_reads_count_kernel(const jst_reads_params P)
@@ -115,12 +117,13 @@ __global__ __launch_bounds__(256) void jst_reads_count_kernel(const jst_reads_pa
             is_next = c == 1;
         }
     }
-    const jreads_run R = jreads_run_scan(read, 0ull, is_best, is_next);
-    if (read != kReadsNoRead && R.ends) {
-        if (R.a)
-            atomicAdd(&P.reads[read].n_best, R.a);
-        if (R.b)
-            atomicAdd(&P.reads[read].n_next, R.b);
+    jreads_count_run R{{is_best}, {is_next}};
+    const bool ends = wave_run_scan(read, R);
+    if (read != kReadsNoRead && ends) {
+        if (R.n_best.v)
+            atomicAdd(&P.reads[read].n_best, R.n_best.v);
+        if (R.n_next.v)
+            atomicAdd(&P.reads[read].n_next, R.n_next.v);
     }
 }
 
@@ -153,40 +156,21 @@ __global__ __launch_bounds__(256) void jst_reads_emit_kernel(const jst_reads_par
         }
         P.reads[r] = R;
     }
-    const unsigned long long m0 = __ballot(mapped), m1 = __ballot(unique), m2 = __ballot(multi);
-    if ((threadIdx.x & 63) == 0) {
-        if (m0)
-            atomicAdd(&P.counts[kReadsCntMapped], (unsigned long long)__popcll(m0));
-        if (m1)
-            atomicAdd(&P.counts[kReadsCntUnique], (unsigned long long)__popcll(m1));
-        if (m2)
-            atomicAdd(&P.counts[kReadsCntMulti], (unsigned long long)__popcll(m2));
-    }
+    count_flagged(&P.counts[kReadsCntMapped], mapped);
+    count_flagged(&P.counts[kReadsCntUnique], unique);
+    count_flagged(&P.counts[kReadsCntMulti], multi);
 }
 
 } // namespace spm_hip
 
-struct spm_jst_reads
+struct spm_jst_reads : spm_hip::device_records<spm_jst_read, spm_jst_reads_stats>
 {
-    spm_ctx *ctx = nullptr;
-    spm_jst_read *d_reads = nullptr;
-    uint64_t n = 0;
     uint32_t strands = 1; // what the summary was made with, and from how many loci (spm_hip_jst_ref_loci_pairs asks)
     uint64_t n_loci = 0;
-    std::vector<spm_jst_read> host;
-    spm_jst_reads_stats stats{};
 };
 static_assert(sizeof(spm_jst_read) == 32 && sizeof(spm_jst_reads_stats) == 48, "spm_hip.h states these sizes");
 
-extern "C" void spm_hip_jst_reads_destroy(spm_jst_reads *r)
-{
-    if (!r)
-        return;
-    if (r->ctx && r->d_reads)
-        hipStreamSynchronize(r->ctx->stream);
-    hipFree(r->d_reads);
-    delete r;
-}
+extern "C" void spm_hip_jst_reads_destroy(spm_jst_reads *r) { spm_jst_reads::destroy(r); }
 
 extern "C" int spm_hip_jst_ref_loci_reads(spm_jst_ref_loci *l, uint32_t strands, uint32_t n_reads, uint32_t flags,
                                           spm_jst_reads **out)
@@ -224,35 +208,30 @@ extern "C" int spm_hip_jst_ref_loci_reads(spm_jst_ref_loci *l, uint32_t strands,
         hipStream_t st = ctx->stream;
         hip_events<2> ev;
         SPM_HIP_CHECK(ctx, ev.create());
-        scratch_layout L;
-        const size_t o_min = L.take((size_t)n_reads * 8), o_counts = L.take(kReadsCnts * 8);
-        SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        void *base = ctx->d_scratch;
-        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_reads, (size_t)n_reads * sizeof(spm_jst_read)));
         jst_reads_params P{};
+        scratch_layout L;
+        L.take(P.minkey, n_reads);
+        L.take(P.counts, kReadsCnts);
+        SPM_TRY(ensure_scratch(ctx, L.bytes()));
+        L.bind(ctx->d_scratch);
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d, (size_t)n_reads * sizeof(spm_jst_read)));
         P.loci = l->d_loci;
         P.n = l->d_loci ? (uint32_t)l->n : 0u;
         P.strands = strands;
         P.n_reads = n_reads;
-        P.minkey = L.at<unsigned long long>(base, o_min);
-        P.reads = R->d_reads;
-        P.counts = L.at<unsigned long long>(base, o_counts);
+        P.reads = R->d;
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.minkey, 0xFF, (size_t)n_reads * 8, st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.reads, 0, (size_t)n_reads * sizeof(spm_jst_read), st));
         SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kReadsCnts * 8, st));
         if (P.n) {
-            const unsigned g_loci = (unsigned)(((uint64_t)P.n + 255) / 256);
-            hipLaunchKernelGGL(jst_reads_min_kernel, dim3(g_loci), dim3(256), 0, st, P);
-            SPM_HIP_CHECK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(jst_reads_count_kernel, dim3(g_loci), dim3(256), 0, st, P);
-            SPM_HIP_CHECK(ctx, hipGetLastError());
+            SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_reads_min_kernel, P.n, P));
+            SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_reads_count_kernel, P.n, P));
         }
-        hipLaunchKernelGGL(jst_reads_emit_kernel, dim3((unsigned)(((uint64_t)n_reads + 255) / 256)), dim3(256), 0, st, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_reads_emit_kernel, n_reads, P));
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
         R->host.resize(n_reads);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d_reads, (size_t)n_reads * sizeof(spm_jst_read), hipMemcpyDeviceToHost, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->host.data(), R->d, (size_t)n_reads * sizeof(spm_jst_read), hipMemcpyDeviceToHost, st));
         SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kReadsCnts)); // (synchronises: the host view has arrived too)
         const unsigned long long *c = ctx->h_counters;
         if (c[kReadsCntBad]) {
@@ -277,26 +256,15 @@ extern "C" int spm_hip_jst_ref_loci_reads(spm_jst_ref_loci *l, uint32_t strands,
 
 extern "C" int spm_hip_jst_reads_view(spm_jst_reads *r, const spm_jst_read **records, uint64_t *n)
 {
-    if (!r || !records || !n)
-        return SPM_E_INVALID;
-    *records = r->host.data();
-    *n = r->n;
-    return SPM_OK;
+    return r ? r->view(records, n) : SPM_E_INVALID;
 }
 
 extern "C" int spm_hip_jst_reads_device(spm_jst_reads *r, const void **records, uint64_t *n)
 {
-    if (!r || !records || !n)
-        return SPM_E_INVALID;
-    *records = r->d_reads;
-    *n = r->n;
-    return SPM_OK;
+    return r ? r->device(records, n) : SPM_E_INVALID;
 }
 
 extern "C" int spm_hip_jst_reads_stats(const spm_jst_reads *r, spm_jst_reads_stats *out)
 {
-    if (!r || !out)
-        return SPM_E_INVALID;
-    *out = r->stats;
-    return SPM_OK;
+    return r ? r->stats_out(out) : SPM_E_INVALID;
 }

@@ -50,25 +50,29 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
     SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(flag_op{P}), n, &scan_bytes));
     SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(jsel_head_op{nullptr}), n, &head_bytes));
     const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, head_bytes));
+    unsigned long long *keys_in = nullptr, *d_out = nullptr; // (d_out: the kept records as 8-byte words, three each)
+    uint32_t *idx_in = nullptr, *offs = nullptr, *gid = nullptr;
+    int32_t *score_in = nullptr;
+    uint8_t *tmp = nullptr;
     scratch_layout L;
-    const size_t o_keys0 = L.take((size_t)n * 8), o_keys1 = L.take((size_t)n * 8), o_idx0 = L.take((size_t)n * 4),
-                 o_idx1 = L.take((size_t)n * 4), o_sc0 = L.take((size_t)n * 4), o_sc1 = L.take((size_t)n * 4), o_keep = L.take(n),
-                 o_head = L.take(n), o_offs = L.take((size_t)n * 4), o_gid = L.take(numbered ? (size_t)n * 4 : 0),
-                 o_min = L.take(n_min * 4), o_counts = L.take(16), o_tmp = L.take(tmp_bytes),
-                 o_out = L.take((size_t)n * sizeof(spm_jst_hit));
+    L.take(keys_in, n);
+    L.take(P.keys, n);
+    L.take(idx_in, n);
+    L.take(P.idx, n);
+    L.take(score_in, n);
+    L.take(P.score, n);
+    L.take(P.keep, n);
+    L.take(P.head, n);
+    L.take(offs, n);
+    L.take(gid, numbered ? n : 0);
+    L.take(P.minima, n_min);
+    L.take(P.counts, 2);
+    L.take(tmp, tmp_bytes);
+    L.take(d_out, 3 * (size_t)n);
     SPM_TRY(ensure_scratch(ctx, L.bytes()));
-    void *base = ctx->d_scratch;
-    unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0);
-    uint32_t *idx_in = L.at<uint32_t>(base, o_idx0);
-    int32_t *score_in = L.at<int32_t>(base, o_sc0);
-    uint32_t *offs = L.at<uint32_t>(base, o_offs);
-    uint32_t *gid = L.at<uint32_t>(base, o_gid);
-    void *tmp = L.at<uint8_t>(base, o_tmp);
-    unsigned long long *d_out = L.at<unsigned long long>(base, o_out);
+    L.bind(ctx->d_scratch);
 
     P.recs = reinterpret_cast<const unsigned long long *>(S.d_recs);
-    P.keys = L.at<unsigned long long>(base, o_keys1);
-    P.idx = L.at<uint32_t>(base, o_idx1);
     P.score_in = score_in;
     P.n = n;
     P.pos_bits = plan.pos_bits;
@@ -82,36 +86,27 @@ int jsel_run(spm_ctx *ctx, const jsel_source &S, const jst_select_plan &plan, ui
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr; // (WINDOW_K: the set is alive, jsel_make)
     P.halo = plan.halo;
     P.strata = strata;
-    P.keep = L.at<uint8_t>(base, o_keep);
-    P.head = L.at<uint8_t>(base, o_head);
-    P.score = L.at<int32_t>(base, o_sc1);
     P.gid = numbered ? gid : nullptr;
-    P.minima = plan.best ? L.at<int32_t>(base, o_min) : nullptr;
-    P.counts = L.at<unsigned long long>(base, o_counts);
+    if (!plan.best)
+        P.minima = nullptr;
     SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, 16, ctx->stream));
     if (plan.best)
         SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, n_min, ctx->stream));
 
     // order
-    const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256);
-    hipLaunchKernelGGL(jst_select_keys_kernel, dim3(grid), dim3(256), 0, ctx->stream, P.recs, keys_in, idx_in, score_in, n,
-                       plan.pos_bits, plan.pat_bits);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_select_keys_kernel, n, P.recs, keys_in, idx_in, score_in, n, plan.pos_bits, plan.pat_bits));
     SPM_HIP_CHECK(ctx, sort_pairs(ctx, tmp, tmp_bytes, keys_in, P.keys, idx_in, P.idx, n, plan.key_bits));
     SPM_HIP_CHECK(ctx, hipEventRecord(R->sel_ev[1], ctx->stream));
 
     // select
-    hipLaunchKernelGGL(jst_select_loci_kernel, dim3((unsigned)(((uint64_t)n + kSelTile - 1) / kSelTile)), dim3(kSelTile), 0, ctx->stream, P);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d<kSelTile>(ctx, jst_select_loci_kernel, n, P));
     if (plan.best) {
         if (numbered)
             SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(jsel_head_op{P.head}), gid, n));
-        hipLaunchKernelGGL(jst_select_minima_kernel, dim3(grid), dim3(256), 0, ctx->stream, P);
-        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_select_minima_kernel, n, P));
     }
     SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(flag_op{P}), offs, n));
-    hipLaunchKernelGGL(jst_select_compact_kernel, dim3(grid), dim3(256), 0, ctx->stream, P, (const uint32_t *)offs, d_out);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_select_compact_kernel, n, P, offs, d_out));
     SPM_HIP_CHECK(ctx, hipEventRecord(R->sel_ev[2], ctx->stream));
 
     // the one read-back: how many records LOCI kept, how many the result has

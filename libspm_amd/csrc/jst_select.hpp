@@ -10,7 +10,8 @@
 // With SPM_SELECT_STRANDS the minimum's group is group >> shift, (haplotype, read) -- or with ACROSS the read -- since the
 // strand is the group's lowest bit; LOCI's group stays (haplotype, pattern).
 // Also here: jst_select_params, the keys and range kernels, the group numbering (jsel_gid, jsel_min_slot), sel_final.
-// Staging, walks, min-scan and the flag functor are select_walk.hpp's, shared with select.hpp.
+// Staging, walks and the flag functor are select_walk.hpp's, shared with select.hpp; the kept count and the segmented
+// min-scan are wave.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(kSelTile) void jst_select_loci_kernel(const jst_sel
                 [&](unsigned long long k) { return jsel_group(P, k); }, score_of, [](unsigned long long) { return true; });
         P.keep[i] = kept ? 1 : 0;
     }
-    sel_count_kept(kept, &P.counts[0]);
+    count_flagged(&P.counts[0], kept);
 }
 
 // the number of record i's group among the groups of the sorted list
@@ -158,7 +159,7 @@ __device__ __forceinline__ uint32_t jsel_min_slot(const jst_select_params &P, ui
     return P.across ? ((uint32_t)jsel_group(P, P.keys[i]) & P.pat_mask) >> P.shift : jsel_gid(P, i);
 }
 
-// BEST: the last lane of every run of one group in a wave (sel_run_min) issues the one atomicMin of that wave and group.  A
+// BEST: the last lane of every run of one group in a wave (wave_run_scan) issues the one atomicMin of that wave and group.  A
 // table of n_haplotypes x n_patterns minima would not fit; the groups that occur are numbered instead, and there are at
 // most n of them.
 __global__ __launch_bounds__(256) void jst_select_minima_kernel(const jst_select_params P)
@@ -171,10 +172,10 @@ __global__ __launch_bounds__(256) void jst_select_minima_kernel(const jst_select
         grp = jsel_group(P, P.keys[i]) >> P.shift;
         sc = P.score[i];
     }
-    bool run_ends;
-    const int32_t m = sel_run_min(grp, sc, run_ends);
+    run_min<int32_t> m{sc};
+    const bool run_ends = wave_run_scan(grp, m);
     if (valid && (run_ends || i + 1 >= P.n))
-        atomicMin(&P.minima[jsel_min_slot(P, (uint32_t)i)], m);
+        atomicMin(&P.minima[jsel_min_slot(P, (uint32_t)i)], m.v);
 }
 
 // the final flag of sorted record i

@@ -62,21 +62,25 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     SPM_HIP_CHECK(ctx, sort_pairs_tmp_bytes(ctx, n, plan.key_bits, &sort_bytes));
     SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(flag_op{P}), n, &scan_bytes));
     const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+    unsigned long long *keys_in = nullptr, *d_segs = nullptr;
+    uint32_t *idx_in = nullptr, *offs = nullptr;
+    uint8_t *tmp = nullptr;
     scratch_layout L;
-    const size_t o_keys0 = L.take((size_t)n * 8), o_keys1 = L.take((size_t)n * 8), o_idx0 = L.take((size_t)n * 4),
-                 o_idx1 = L.take((size_t)n * 4), o_keep = L.take(n), o_score = L.take((size_t)n * 4),
-                 o_offs = L.take((size_t)n * 4), o_min = L.take(plan.min_slots * 4),
-                 o_segs = L.take(n_segs ? (n_segs + 1) * 8 : 0), o_counts = L.take(16), o_tmp = L.take(tmp_bytes);
+    L.take(keys_in, n);
+    L.take(P.keys, n);
+    L.take(idx_in, n);
+    L.take(P.idx, n);
+    L.take(P.keep, n);
+    L.take(P.score, n);
+    L.take(offs, n);
+    L.take(P.minima, plan.min_slots);
+    L.take(d_segs, n_segs ? n_segs + 1 : 0);
+    L.take(P.counts, 2);
+    L.take(tmp, tmp_bytes);
     SPM_TRY(ensure_scratch(ctx, L.bytes()));
-    void *base = ctx->d_scratch;
-    unsigned long long *keys_in = L.at<unsigned long long>(base, o_keys0);
-    uint32_t *idx_in = L.at<uint32_t>(base, o_idx0);
-    uint32_t *offs = L.at<uint32_t>(base, o_offs);
-    void *tmp = L.at<uint8_t>(base, o_tmp);
+    L.bind(ctx->d_scratch);
 
     P.recs = S.d_recs;
-    P.keys = L.at<unsigned long long>(base, o_keys1);
-    P.idx = L.at<uint32_t>(base, o_idx1);
     P.n = n;
     P.pos_bits = plan.pos_bits;
     P.pos_mask = plan.pos_bits >= 64 ? ~0ull : (1ull << plan.pos_bits) - 1;
@@ -88,12 +92,9 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
     P.k_tab = plan.window == SPM_SELECT_WINDOW_K && S.ps ? S.ps->d_k : nullptr;
     P.halo = plan.halo;
     P.strata = strata;
-    P.keep = L.at<uint8_t>(base, o_keep);
-    P.score = L.at<int32_t>(base, o_score);
-    P.minima = plan.best ? L.at<int32_t>(base, o_min) : nullptr;
-    P.counts = L.at<unsigned long long>(base, o_counts);
+    if (!plan.best)
+        P.minima = nullptr;
     if (n_segs) {
-        unsigned long long *d_segs = L.at<unsigned long long>(base, o_segs);
         SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, S.segs->data(), (n_segs + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         P.segs = d_segs;
         P.n_segs = n_segs;
@@ -105,20 +106,14 @@ int select_run(spm_ctx *ctx, const select_source &S, const select_plan &plan, ui
         SPM_HIP_CHECK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.minima), 0x7FFFFFFF, plan.min_slots, ctx->stream));
 
     // order
-    const unsigned grid = (n + 255u) / 256u;
-    hipLaunchKernelGGL(select_keys_kernel, dim3(grid), dim3(256), 0, ctx->stream, S.d_recs, keys_in, idx_in, n, plan.pos_bits,
-                       (unsigned long long)S.bias);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, select_keys_kernel, n, S.d_recs, keys_in, idx_in, n, plan.pos_bits, S.bias));
     SPM_HIP_CHECK(ctx, sort_pairs(ctx, tmp, tmp_bytes, keys_in, P.keys, idx_in, P.idx, n, plan.key_bits));
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[1], ctx->stream));
 
     // select
-    hipLaunchKernelGGL(select_loci_kernel, dim3((n + kSelTile - 1) / kSelTile), dim3(kSelTile), 0, ctx->stream, P);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d<kSelTile>(ctx, select_loci_kernel, n, P));
     SPM_HIP_CHECK(ctx, exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(flag_op{P}), offs, n));
-    hipLaunchKernelGGL(select_compact_kernel, dim3(grid), dim3(256), 0, ctx->stream, P, (const uint32_t *)offs, H->d_hits,
-                       H->d_count + kCntHits);
-    SPM_HIP_CHECK(ctx, hipGetLastError());
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, select_compact_kernel, n, P, offs, H->d_hits, H->d_count + kCntHits));
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[2], ctx->stream));
 
     // the one read-back: how many records LOCI kept, how many the result has

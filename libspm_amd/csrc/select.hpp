@@ -8,7 +8,8 @@
 //                          exclusive scan of the keep flags (the order IS the contract: no slot atomics).
 // With SPM_SELECT_STRANDS the minimum is per read = pattern >> shift: the strand is the pattern's lowest bit, so
 // a read's two strands are adjacent runs of the sorted order.  shift = 0 is the selection per pattern, expression for expression.
-// Also here: select_params, the keys and range kernels, sel_final.  Staging, walks, min-scan, flag functor: select_walk.hpp.
+// Also here: select_params, the keys and range kernels, sel_final.  Staging, walks, flag functor: select_walk.hpp; the kept count
+// and the segmented min-scan: wave.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -139,15 +140,15 @@ __global__ __launch_bounds__(kSelTile) void select_loci_kernel(const select_para
         }
         P.keep[i] = kept ? 1 : 0;
     }
-    sel_count_kept(kept, &P.counts[0]);
+    count_flagged(&P.counts[0], kept);
     // per-pattern minima: the last lane of every run issues the one atomicMin of that wave and pattern (with a shift: of
     // that read, whose two strands are adjacent runs of the sorted order)
     if (P.best) {
-        bool run_ends;
         const uint32_t grp = pat >> P.shift;
-        const int32_t m = sel_run_min(grp, sc, run_ends);
+        run_min<int32_t> m{sc};
+        const bool run_ends = wave_run_scan(grp, m);
         if (valid && (run_ends || i + 1 >= T.n))
-            atomicMin(&P.minima[grp], m);
+            atomicMin(&P.minima[grp], m.v);
     }
 }
 

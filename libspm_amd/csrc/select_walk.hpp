@@ -1,7 +1,8 @@
 // select_walk.hpp -- the device pieces that the two selections share (select.hpp: 16-byte spm_hit; jst_select.hpp: 24-byte
-// spm_jst_hit).  gfx950.  Holds the tile staging and the two window walks of LOCI, the kept count, the
-// wave-level segmented min-scan of BEST, and the final flag with its functor.  __device__ __forceinline__ templates over
-// functors, no class hierarchy: every kernel stays in its own header and passes what differs --
+// spm_jst_hit).  gfx950.  Holds the tile staging and the two window walks of LOCI, and the final flag with its
+// functor; the kept count and the segmented min-scan of BEST are wave.hpp's (count_flagged, wave_run_scan over a run_min).
+// __device__ __forceinline__ templates over functors, no class hierarchy: every kernel stays in its own header and passes
+// what differs --
 //   group_of(key)  the group whose records see each other: the pattern, or (haplotype, pattern)
 //   score_of(j)    the score of sorted entry j, from global memory (staging, and a walk that leaves the halo)
 //   allowed(rel)   may a neighbour at this position suppress?  (the plain selection's segment range; pan-genome: always)
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "select_plan.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -83,31 +85,6 @@ __device__ __forceinline__ bool sel_walk_keeps(const unsigned long long *s_key, 
             return false;
     }
     return true;
-}
-
-// records LOCI kept: one atomic per wave
-__device__ __forceinline__ void sel_count_kept(bool kept, unsigned long long *counter)
-{
-    const unsigned long long kept_mask = __ballot(kept);
-    if ((threadIdx.x & 63) == 0 && kept_mask)
-        atomicAdd(counter, (unsigned long long)__popcll(kept_mask));
-}
-
-// BEST: lanes of one group are contiguous (sorted input), so a segmented min-scan over the wave leaves the minimum of every
-// run of equal `grp` in the run's last lane (run_ends: the wave's last lane, or the next lane's grp differs).  All lanes call.
-template <class Group> __device__ __forceinline__ int32_t sel_run_min(Group grp, int32_t score, bool &run_ends)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    int32_t m = score;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t m2 = __shfl_up(m, d);
-        const Group g2 = __shfl_up(grp, d);
-        if (lane >= (uint32_t)d && g2 == grp)
-            m = m2 < m ? m2 : m;
-    }
-    const Group g_next = __shfl_down(grp, 1);
-    run_ends = lane == 63 || g_next != grp;
-    return m;
 }
 
 // What the exclusive sum adds up and the compaction tests again: LOCI's verdict, and with BEST the stratum test against

@@ -7,12 +7,17 @@
 //   (hipcub exclusive sum of rep[w] != none over the pool: the number of every slot, in pool order)
 //   slot_compact_kernel  one lane per pool word: slot number -> representative record; the last lane writes the slot count
 // and on the host: the temp bytes the sum needs, the stage enqueued in that order, and the downloaded numbering for the loop
-// that sends the records of a host view to their slots.  The sum is device_order.hpp's.
+// that sends the records of a host view to their slots.  The sum and the launches are device_order.hpp's, the count of the
+// flagged lanes is wave.hpp's.
+// Also what the callers would otherwise each write again: slot_count (the clamp every later kernel runs under),
+// ref_aln_unusable (the collapse's and the normalisation's test of a projected record), slot_total_kernel (the words of all
+// slots, for the projection and the normalisation).
 #pragma once
 
 #include <vector>
 
 #include "device_order.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -32,13 +37,32 @@ struct slot_tables
     unsigned long long *counts; // the caller's counters; kSlotCnt* are this stage's
 };
 
-// one atomicAdd per wave: the lanes of it that raise `flag`
-__device__ __forceinline__ void count_flagged(unsigned long long *counter, bool flag)
+// the slots the stage counted, as far as the per-slot tables hold them: what every later kernel of a caller runs over
+__device__ __forceinline__ uint32_t slot_count(const unsigned long long *counts, uint32_t cap)
 {
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicAdd(counter, (unsigned long long)__popcll(m));
+    return (uint32_t)min(counts[kSlotCntSlots], (unsigned long long)cap);
 }
+
+// What makes a projected record (the collapse's and the normalisation's input) unusable: tested before any of its fields
+// indexes a table.  Limits: ref_aln_limits, or a kernel's parameter block, which holds the same three fields.
+struct ref_aln_limits
+{
+    uint64_t n_ops;      // words of the source's pool
+    uint32_t n_patterns; // needles of the set
+    uint64_t n_ref;      // symbols of the reference
+};
+
+template <class Limits> __device__ __forceinline__ bool ref_aln_unusable(const Limits &P, const spm_jst_ref_aln &a)
+{
+    return a.cigar_len == 0 || (uint64_t)a.cigar_off + a.cigar_len > P.n_ops || a.pattern >= P.n_patterns ||
+           a.ref_begin > a.ref_end || a.ref_end > P.n_ref;
+}
+
+struct ref_aln_unusable_op // the predicate as the slot stage takes it
+{
+    ref_aln_limits lim;
+    __device__ __forceinline__ bool operator()(const spm_jst_ref_aln &a) const { return ref_aln_unusable(lim, a); }
+};
 
 // unusable(record): true if the record must not index a table -- tested before any of its fields does
 template <class Rec, class Unusable>
@@ -66,6 +90,16 @@ __global__ __launch_bounds__(256) void slot_compact_kernel(const slot_tables T)
         T.slot_rec[s] = r;
     if (w == T.n_ops - 1)
         T.counts[kSlotCntSlots] = (unsigned long long)s + (r != kSlotNone ? 1ull : 0ull);
+}
+
+// one lane: the words of all slots -- slot_off is the exclusive sum of slot_words -- into the caller's counter `words`
+__global__ void slot_total_kernel(unsigned long long *counts, uint32_t cap, const unsigned long long *slot_off,
+                                  const uint32_t *slot_words, uint32_t words)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint32_t n_slots = slot_count(counts, cap);
+        counts[words] = n_slots ? slot_off[n_slots - 1] + slot_words[n_slots - 1] : 0ull;
+    }
 }
 
 // what the exclusive sums of the callers add up: "this word starts a slot", a table of bytes, a table of words widened
@@ -97,18 +131,14 @@ template <class Rec, class Unusable>
 hipError_t slot_stage_enqueue(spm_ctx *ctx, const Rec *recs, uint32_t n, const slot_tables &T, Unusable unusable, void *tmp,
                               size_t tmp_bytes)
 {
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMemsetAsync(T.rep, 0xFF, T.n_ops * 4, st);
+    hipError_t e = hipMemsetAsync(T.rep, 0xFF, T.n_ops * 4, ctx->stream);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((slot_rep_kernel<Rec, Unusable>), dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, recs, n, T,
-                       unusable);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_1d(ctx, slot_rep_kernel<Rec, Unusable>, n, recs, n, T, unusable)) != hipSuccess)
         return e;
     if ((e = exclusive_sum(ctx, tmp, tmp_bytes, counted<uint32_t>(slot_flag_op{T.rep}), T.sid, T.n_ops)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(slot_compact_kernel, dim3((unsigned)((T.n_ops + 255) / 256)), dim3(256), 0, st, T);
-    return hipGetLastError();
+    return launch_1d(ctx, slot_compact_kernel, T.n_ops, T);
 }
 
 // the numbering on the host: download() enqueues the copy (the caller synchronises), of() answers for one record

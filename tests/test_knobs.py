@@ -9,7 +9,7 @@ NOT_KNOBS = {"SPM_HIP_CHECK", "SPM_HIP_H"}  # an error-check macro and the C hea
 
 
 def _tokens(pattern, *globs):
-    files = [f for g in globs for f in glob.glob(os.path.join(ROOT, g), recursive=True)]
+    files = [f for g in globs for f in glob.glob(os.path.join(ROOT, g), recursive=True) if os.path.isfile(f)]
     return {t for f in files for t in re.findall(pattern, open(f, encoding="utf-8").read())} - NOT_KNOBS
 
 
