@@ -117,6 +117,26 @@ struct jst_pair_loci
     bool operator==(jst_pair_loci const &) const noexcept = default;
 };
 
+// mate rescue (journaled_sequence_tree::locate_pairs_rescued; spm_jst_rescue in spm_hip.h): one record per job -- a mapped
+// mate of a pair without a proper combination, whose partner was searched beside it in the reference with up to k edits --
+// ordered by (pair, mate rescued)
+struct jst_rescue
+{
+    std::uint32_t pair, needle, anchor; // the pair, the needle that was aligned, the anchor's index into the loci vector
+    alignment aln;                      // against the reference; errors() is the reference distance.  NONE: empty, errors -1
+    std::int32_t tlen;                  // SAM TLEN of mate 1; 0 unless RESCUED
+    std::uint16_t flag, status;         // SAM FLAG of the rescued mate's line; spm_rescue_status
+    bool operator==(jst_rescue const &) const noexcept = default;
+};
+
+struct jst_rescued_pair_loci
+{
+    jst_pair_loci located;              // what locate_pairs returns
+    std::vector<jst_rescue> rescues;
+    std::vector<std::uint32_t> ops;     // the pool of CIGAR words as the device returned it
+    bool operator==(jst_rescued_pair_loci const &) const noexcept = default;
+};
+
 struct jst_search_stats
 {
     std::uint64_t haplotype_symbols{}; // sum of haplotype lengths (what per-haplotype scans would read)
@@ -848,6 +868,25 @@ public:
         return out;
     }
 
+    // ---- locate_pairs plus mate rescue (the contract of spm_hip_jst_pairs_rescue in spm_hip.h): every pair without a proper
+    // combination gets one job per mapped mate, searched in the tree's reference with up to k edits.  Device route only: the
+    // search and the alignment are the device's (there is no second traceback on the host).
+    jst_rescued_pair_loci locate_pairs_rescued(spm_patterns * needles, std::size_t window, std::uint32_t n_reads,
+                                               std::uint32_t min_tlen, std::uint32_t max_tlen, std::uint32_t k,
+                                               hip::hit_selection const & selection, std::size_t block = 0,
+                                               jst_search_stats * stats = nullptr) const
+    {
+        if (!device_ready())
+            hip::fatal("journaled_sequence_tree::locate_pairs_rescued (tree not representable on the device)", hip::default_context());
+        jst_rescued_pair_loci out;
+        spm_jst_pair_opts const opts{min_tlen, max_tlen, 0, 0};
+        rescue_request const rescue{spm_jst_rescue_opts{min_tlen, max_tlen, k, 0, 0}, _device->reference.get(), needles, &out.rescues,
+                                    &out.ops};
+        out.located.mapped.loci = loci_of(device_alns(needles, window, selection, block, stats).get(), true, 2, n_reads,
+                                          &out.located.mapped.reads, &opts, &out.located.pairs, &rescue);
+        return out;
+    }
+
     jst_pair_loci locate_pairs_host(spm_patterns * needles, std::size_t window,
                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
                                     std::uint32_t n_reads, std::uint32_t min_tlen, std::uint32_t max_tlen,
@@ -1215,12 +1254,23 @@ private:
         return out;
     }
 
+    // what loci_of needs for the mate rescue behind the pairs: the bounds and k, the reference, the needles, where the answer goes
+    struct rescue_request
+    {
+        spm_jst_rescue_opts opts;
+        spm_text const * reference;
+        spm_patterns const * needles;
+        std::vector<jst_rescue> * rescues;
+        std::vector<std::uint32_t> * ops;
+    };
+
     // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
     // ... and, where asked for, the summary of n_reads reads over them (spm_hip_jst_ref_loci_reads) and the pairs of their
     // mates (spm_hip_jst_ref_loci_pairs)
     static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false, std::uint32_t strands = 1,
                                               std::uint32_t n_reads = 0, std::vector<jst_read> * reads = nullptr,
-                                              spm_jst_pair_opts const * pair_opts = nullptr, std::vector<jst_pair> * pairs = nullptr)
+                                              spm_jst_pair_opts const * pair_opts = nullptr, std::vector<jst_pair> * pairs = nullptr,
+                                              rescue_request const * rescue = nullptr)
     {
         spm_ctx * ctx = hip::default_context();
         spm_jst_ref_alns * r = projected(a, normalized);
@@ -1273,6 +1323,25 @@ private:
                 for (std::uint64_t i = 0; i < np; ++i)
                     pairs->push_back({pp[i].locus1, pp[i].locus2, pp[i].tlen, pp[i].best, pp[i].n_pairs, pp[i].n_best, pp[i].n_next,
                                       pp[i].flag1, pp[i].flag2});
+                if (rescue != nullptr) {
+                    spm_jst_rescues * rs = nullptr;
+                    if (spm_hip_jst_pairs_rescue(l, rd, pr, rescue->reference, rescue->needles, &rescue->opts, &rs) != SPM_OK)
+                        hip::fatal("spm_hip_jst_pairs_rescue", ctx);
+                    std::unique_ptr<spm_jst_rescues, decltype(&spm_hip_jst_rescues_destroy)> rs_owner{rs, &spm_hip_jst_rescues_destroy};
+                    spm_jst_rescue const * rr2 = nullptr;
+                    std::uint32_t const * rops = nullptr;
+                    std::uint64_t n_rescues = 0, n_rops = 0;
+                    if (spm_hip_jst_rescues_view(rs, &rr2, &n_rescues, &rops, &n_rops) != SPM_OK)
+                        hip::fatal("spm_hip_jst_rescues_view", ctx);
+                    rescue->rescues->clear();
+                    rescue->ops->assign(rops, rops + n_rops);
+                    for (std::uint64_t i = 0; i < n_rescues; ++i)
+                        rescue->rescues->push_back({rr2[i].pair, rr2[i].pattern, rr2[i].anchor,
+                                                    alignment{static_cast<std::size_t>(rr2[i].ref_begin),
+                                                              static_cast<std::size_t>(rr2[i].ref_end), rr2[i].score,
+                                                              rops + rr2[i].cigar_off, rr2[i].cigar_len},
+                                                    rr2[i].tlen, rr2[i].flag, rr2[i].status});
+                }
             }
         }
         return out;

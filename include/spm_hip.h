@@ -824,6 +824,98 @@ int spm_hip_jst_pairs_device(spm_jst_pairs *p, const void **records, uint64_t *n
 int spm_hip_jst_pairs_stats(const spm_jst_pairs *p, spm_jst_pairs_stats *out);
 void spm_hip_jst_pairs_destroy(spm_jst_pairs *p);
 
+/* ---- mate rescue: a missing mate re-aligned beside its partner -------------------------------------------------------------
+ * A pair whose record lacks 0x2 gives one JOB per mapped mate: one-mate pairs one, discordant pairs two; proper pairs and
+ * pairs with no mate mapped none.  The ANCHOR A of a job is the locus the pair record reports for that mate (locus1 / locus2,
+ * its primary; only the primary is used).  The job looks for the OTHER mate Y on the opposite strand: needle
+ *     q = 4 pair + 2 (mate of Y) + (1 - strand bit of A's pattern)
+ * of `patterns`, the stranded Myers set that produced the loci.  Jobs -- and records -- are ordered by (pair, mate rescued).
+ * Window and ends, N the length of `reference`, ends exclusive as ref_end is:
+ *     A forward:  lo = A.ref_begin,                    window [lo, min(lo + max_tlen, N)),
+ *                 ends e in [max(lo + min_tlen, A.ref_end), min(lo + max_tlen, N)]
+ *     A reverse:  lo = max(0, A.ref_end - max_tlen),   window [lo, A.ref_end),   ends e in (lo, A.ref_end]
+ * No alignment begins left of lo (the lo of spm_hip_hits_align); an empty range finds nothing.
+ * Search: unit-cost semi-global edit distance of q in the window (a needle rank >= sigma matches nothing).  d(e) is the
+ * distance of the best alignment that ends at e and begins at or right of lo; the candidate is the minimum of (d, e) over
+ * the admissible ends with d <= k.  A needle of m <= k symbols is not searched: status NONE, counted in n_short (and in
+ * n_none).  Needles above 256 symbols: SPM_E_UNSUPPORTED.
+ * Alignment: begin and transcript of (q, e, d, lo) are those of spm_hip_hits_align over `reference` -- the largest begin;
+ * diagonal, then I, then D -- computed by the same kernels.
+ * Classification: the concordance predicate of the pairing on (A, rescued alignment), POST HOC.  A forward anchor's
+ * candidate is concordant by construction.  A reverse anchor's candidate can fail on its begin -- it begins right of A's
+ * begin (a dovetail), or the fragment is shorter than min_tlen: it is kept with its alignment, status NOT_CONCORDANT, tlen 0,
+ * and NO second-best end is tried.
+ * Limits.  The search is against the REFERENCE, not the haplotypes: a mate that carries non-reference alleles pays for them
+ * in edits, and k has to cover that; score is a reference distance (SAM NM), not a haplotype distance, and is never mixed
+ * with the anchor's score.  FR orientation only (no RF, no FF).  No MAPQ.
+ * flag is the SAM FLAG of the rescued mate's line: 0x1; 0x2 when RESCUED; 0x4 when NONE; 0x10 the needle is a reverse
+ * pattern (not for NONE); 0x20 the anchor is; 0x40 / 0x80 the rescued mate is mate 1 / mate 2.
+ * The result is a pure function of its inputs: byte-identical across runs, host and device view alike.  It outlives all
+ * five inputs.
+ *
+ * Worked cases, reads of 30 symbols, min_tlen 100, max_tlen 300, N = 10000.
+ *  1. Mate 1 forward at [1000,1030), mate 2 unmapped: one job, needle 4p + 3, window [1000,1300), ends 1100 .. 1300.  The best
+ *     end is 1200 with 4 edits, its begin 1170: RESCUED, tlen +200, flag 0x93.
+ *  2. Mate 2 reverse at [720,750), mate 1 unmapped: needle 4p + 0, window [450,750), ends 451 .. 750.  Candidate [500,530):
+ *     RESCUED, tlen +250, flag 0x63.  Candidate [700,730): 50 < min_tlen, NOT_CONCORDANT, tlen 0, flag 0x61.  Candidate
+ *     [725,750) with min_tlen 20: it begins right of 720 (a dovetail), NOT_CONCORDANT.
+ *  3. Clipping.  A forward at [9800,9830): window [9800,10000), ends 9900 .. 10000.  A forward at [9950,9980): ends 10050 ..
+ *     are beyond N: nothing is found.  A reverse at [170,200): lo = 0, ends 1 .. 200.
+ *  4. A discordant pair (both mapped): two jobs, the first rescues mate 1 (anchor locus2), the second mate 2 (anchor locus1).
+ *
+ *   * SPM_E_INVALID with a message, decided on the host before any launch: NULL arguments; nonzero flags or reserved;
+ *     min_tlen == 0, min_tlen > max_tlen, max_tlen > 2^31 - 1; handles of different contexts; a reads handle not made with
+ *     strands == 2; pairs->n != reads->n / 2; a reads handle made from a different number of loci; a needle set that is not a
+ *     stranded Myers set with n == 2 n_reads; a text sigma other than the set's.
+ *   * SPM_E_UNSUPPORTED, likewise: a MYERS_PREFIX set; a needle above 256 symbols.
+ *   * A pair record that disagrees with the read summary, the loci or the reference -- an index outside the loci, a pattern
+ *     that does not name the mate and the strand the flags state, ref_end > N, a locus that is not the read's primary -- is
+ *     COUNTED on the device, each test before the value is used as an index, and fails the call with SPM_E_INVALID.
+ *   * Zero pairs, or zero jobs: an empty result and SPM_OK. */
+typedef struct spm_jst_rescue_opts { /* 20 bytes */
+    uint32_t min_tlen, max_tlen;     /* 1 <= min_tlen <= max_tlen <= 2^31 - 1: the rule of the pairing */
+    uint32_t k;                      /* the most edits a rescued mate may have against the reference */
+    uint32_t flags;                  /* must be 0 */
+    uint32_t reserved;               /* must be 0 */
+} spm_jst_rescue_opts;
+enum spm_rescue_status { SPM_RESCUE_RESCUED = 0, SPM_RESCUE_NONE = 1, SPM_RESCUE_NOT_CONCORDANT = 2 };
+typedef struct spm_jst_rescue {      /* 48 bytes */
+    uint64_t ref_begin, ref_end;     /* the rescued alignment; 0, 0 for NONE */
+    uint32_t pair;
+    uint32_t pattern;                /* the needle that was aligned */
+    uint32_t anchor;                 /* the anchor's locus index */
+    int32_t score;                   /* edits against the reference; -1 for NONE */
+    uint32_t cigar_off, cigar_len;   /* into this result's ops pool: cigar_off is the exclusive prefix sum of 2 score + 1 over
+                                        the found jobs in job order; 0, 0 for NONE */
+    int32_t tlen;                    /* SAM TLEN of mate 1 as the pairing defines it; 0 unless RESCUED */
+    uint16_t flag;                   /* SAM FLAG of the rescued mate's line */
+    uint16_t status;                 /* spm_rescue_status */
+} spm_jst_rescue;
+typedef struct spm_jst_rescues spm_jst_rescues;
+typedef struct spm_jst_rescues_stats { /* 80 bytes */
+    float ms_total;                  /* device: the four stages below (HIP events) */
+    float ms_jobs;                   /* the job list */
+    float ms_search;                 /* the bounded search, one wave per job */
+    float ms_align;                  /* begins and transcripts of the found jobs */
+    float ms_emit;                   /* classification and records */
+    float ms_host;                   /* wall clock of the whole call */
+    uint64_t n_pairs;
+    uint64_t n_jobs;                 /* = n_rescued + n_none + n_not_concordant */
+    uint64_t n_rescued;
+    uint64_t n_none;
+    uint64_t n_not_concordant;
+    uint64_t n_short;                /* of n_none: needles of m <= k symbols, not searched */
+    uint64_t max_window;             /* the longest window of any job */
+} spm_jst_rescues_stats;
+int spm_hip_jst_pairs_rescue(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs, const spm_text *reference,
+                             const spm_patterns *patterns, const spm_jst_rescue_opts *opts, spm_jst_rescues **out);
+/* ops and n_ops may be NULL */
+int spm_hip_jst_rescues_view(spm_jst_rescues *r, const spm_jst_rescue **records, uint64_t *n, const uint32_t **ops,
+                             uint64_t *n_ops);
+int spm_hip_jst_rescues_device(spm_jst_rescues *r, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops);
+int spm_hip_jst_rescues_stats(const spm_jst_rescues *r, spm_jst_rescues_stats *out);
+void spm_hip_jst_rescues_destroy(spm_jst_rescues *r);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

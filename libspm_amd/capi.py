@@ -238,6 +238,42 @@ class JstPairsStats(C.Structure):
     ]
 
 
+class JstRescueOpts(C.Structure):
+    _fields_ = [("min_tlen", C.c_uint32), ("max_tlen", C.c_uint32), ("k", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class JstRescue(C.Structure):
+    _fields_ = [("ref_begin", C.c_uint64), ("ref_end", C.c_uint64), ("pair", C.c_uint32), ("pattern", C.c_uint32),
+                ("anchor", C.c_uint32), ("score", C.c_int32), ("cigar_off", C.c_uint32), ("cigar_len", C.c_uint32),
+                ("tlen", C.c_int32), ("flag", C.c_uint16), ("status", C.c_uint16)]
+
+
+# the numpy view of JstRescue (spm_jst_rescue, 48 bytes)
+JST_RESCUE_DTYPE = [("ref_begin", "<u8"), ("ref_end", "<u8"), ("pair", "<u4"), ("pattern", "<u4"), ("anchor", "<u4"),
+                    ("score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("tlen", "<i4"), ("flag", "<u2"),
+                    ("status", "<u2")]
+RESCUE_RESCUED, RESCUE_NONE, RESCUE_NOT_CONCORDANT = 0, 1, 2
+
+
+class JstRescuesStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_jobs", C.c_float),
+        ("ms_search", C.c_float),
+        ("ms_align", C.c_float),
+        ("ms_emit", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_pairs", C.c_uint64),
+        ("n_jobs", C.c_uint64),
+        ("n_rescued", C.c_uint64),
+        ("n_none", C.c_uint64),
+        ("n_not_concordant", C.c_uint64),
+        ("n_short", C.c_uint64),
+        ("max_window", C.c_uint64),
+    ]
+
+
 class JstNormalizeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -412,6 +448,12 @@ def lib():
         "spm_hip_jst_pairs_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_pairs_stats": (C.c_int, [vp, C.POINTER(JstPairsStats)]),
         "spm_hip_jst_pairs_destroy": (None, [vp]),
+        "spm_hip_jst_pairs_rescue": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(JstRescueOpts), C.POINTER(vp)]),
+        "spm_hip_jst_rescues_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRescue)), C.POINTER(C.c_uint64), C.POINTER(u32p),
+                                               C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_rescues_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_jst_rescues_stats": (C.c_int, [vp, C.POINTER(JstRescuesStats)]),
+        "spm_hip_jst_rescues_destroy": (None, [vp]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -462,6 +504,8 @@ EXPORTS = [
     "spm_hip_jst_reads_destroy",
     "spm_hip_jst_ref_loci_pairs", "spm_hip_jst_pairs_view", "spm_hip_jst_pairs_device", "spm_hip_jst_pairs_stats",
     "spm_hip_jst_pairs_destroy",
+    "spm_hip_jst_pairs_rescue", "spm_hip_jst_rescues_view", "spm_hip_jst_rescues_device", "spm_hip_jst_rescues_stats",
+    "spm_hip_jst_rescues_destroy",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

@@ -10,3 +10,4 @@
 #include "jst_collapse.hpp"
 #include "jst_reads.hpp"
 #include "jst_pairs.hpp"
+#include "jst_rescue.hpp"

@@ -447,6 +447,7 @@ JST_READ_DTYPE = np.dtype([("first_locus", "<u4"), ("n_loci", "<u4"), ("n_forwar
                            ("best", "<i4"), ("best_ref_score", "<i4"), ("n_best", "<u4"), ("n_next", "<u4")])
 JST_PAIR_DTYPE = np.dtype([("locus1", "<u4"), ("locus2", "<u4"), ("tlen", "<i4"), ("best", "<i4"), ("n_pairs", "<u4"),
                            ("n_best", "<u4"), ("n_next", "<u4"), ("flag1", "<u2"), ("flag2", "<u2")])
+JST_RESCUE_DTYPE = np.dtype(capi.JST_RESCUE_DTYPE)
 JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
                                 ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
                                 ("member_off", "<u4"), ("n_haplotypes", "<u4")])
@@ -857,6 +858,19 @@ class JstPairs:
         _check(capi.lib().spm_hip_jst_pairs_stats(self._h, C.byref(s)), self.ctx._h)
         return s
 
+    def rescue(self, loci: "JstRefLoci", reads: "JstReads", reference: "Text", patterns: "PatternSet", k: int, min_tlen: int,
+               max_tlen: int) -> "JstRescues":
+        """Mate rescue (spm_hip_jst_pairs_rescue): for every pair here without a proper combination, one job per mapped
+        mate -- the other mate, on the opposite strand, searched with at most k edits in the stretch of `reference` the
+        fragment bounds allow beside that mate's locus, and aligned as Hits.align() aligns.  loci, reads: what these pairs
+        were made from; patterns: the both_strands Myers set behind them.  One JST_RESCUE_DTYPE record per job, ordered by
+        (pair, mate rescued).  The result stays valid after every input is closed."""
+        opts = capi.JstRescueOpts(min_tlen=int(min_tlen), max_tlen=int(max_tlen), k=int(k), flags=0, reserved=0)
+        r = C.c_void_p()
+        _check(capi.lib().spm_hip_jst_pairs_rescue(loci._h, reads._h, self._h, reference._h, patterns._h, C.byref(opts),
+                                                   C.byref(r)), self.ctx._h)
+        return JstRescues(self.ctx, r)
+
     def close(self):
         if self._h:
             if self.ctx._h:
@@ -868,3 +882,25 @@ class JstPairs:
             self.close()
         except Exception:
             pass
+
+
+class JstRescues(_RecordPool):
+    """Result of JstPairs.rescue(): one JST_RESCUE_DTYPE record per job, ordered by (pair, mate rescued), and the pool of
+    CIGAR words (len << 4 | op) the found ones point into."""
+    _PREFIX, _REC, _DTYPE, _STATS = "jst_rescues", capi.JstRescue, JST_RESCUE_DTYPE, capi.JstRescuesStats
+
+    def view(self):
+        """(records, ops)"""
+        r = self._raw()
+        return _as_array(r[0], r[1], self._REC, self._DTYPE), _as_array(r[2], r[3], C.c_uint32, np.uint32)
+
+    def device(self):
+        """(records, n, ops, n_ops): device pointers"""
+        return self._device()
+
+    def cigar(self, i: int) -> str:
+        records, ops = self.view()
+        return self._cigar(i, records, ops)
+
+    def stats(self) -> capi.JstRescuesStats:
+        return self._stats()
