@@ -55,7 +55,7 @@ struct jst_dev
     uint32_t n_groups;    // ceil(n_hap / kJstGroup)
     uint64_t L, n_blocks; // all blocks of the reference
     uint64_t jb, je;      // indexed blocks
-    const uint64_t *a_lo; // [n_blocks + 1]: first allele with pos >= j * L
+    const uint64_t *a_lo; // [n_blocks + 1]: first allele with pos >= j * L; row n_blocks = n_alleles
     uint64_t *hap_start;  // [(n_blocks + 1) * n_hap]
 };
 
@@ -70,7 +70,9 @@ __global__ void jst_alo_kernel(const uint64_t *pos, uint64_t n_alleles, uint64_t
     if (j > n_blocks)
         return;
     const uint64_t key = j * L;
-    uint64_t lo = 0, hi = n_alleles;
+    // row n_blocks closes the last block: an insertion behind the last reference symbol (pos == n_ref) belongs to it,
+    // also where the block length divides n_ref and n_blocks * L == n_ref
+    uint64_t lo = j == n_blocks ? n_alleles : 0, hi = n_alleles;
     while (lo < hi) {
         const uint64_t mid = (lo + hi) >> 1;
         if (pos[mid] < key)

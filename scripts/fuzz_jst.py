@@ -4,7 +4,10 @@ insertions, deletions, replacements, multi-allelic sites) / coverage / needles /
 search (context buffer + segmented scan + fan-out, spm_hip_jst_*) against what SURVEY 8(f)-2 defines it to be -- the union
 over haplotypes of a linear scan of each materialised haplotype (numpy application of the alleles, brute-force engine).
 
-    python scripts/fuzz_jst.py [--seconds 240] [--seed 1]
+    python scripts/fuzz_jst.py [--seconds 240] [--seed 1] [--geometry grid|touching]
+
+--geometry touching draws the alleles from tests/jst_edges.random_touching_alleles instead: positions with repeats anywhere
+in [0, n_ref], so that alleles touch, share positions, sit at both ends of the reference and overlap on disjoint haplotypes.
 """
 import argparse
 import importlib.util
@@ -25,7 +28,17 @@ def helpers():
     return m
 
 
-def one_case(spm, ctx, H, seed):
+def touching():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import jst_edges
+    return jst_edges
+
+
+def one_case(spm, ctx, H, seed, geometry="grid"):
+    if geometry == "touching":
+        r, n = touching().touching_case(spm, ctx, seed)
+        one_case.records += n
+        return r
     rng = np.random.default_rng(seed)
     n_ref = int(rng.choice([6_000, 20_000, 50_000]))
     n_hap = int(rng.choice([1, 2, 7, 33, 64, 65, 130]))
@@ -75,6 +88,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--geometry", choices=["grid", "touching"], default="grid")
     args = ap.parse_args()
     import torch
     torch.zeros(1, device="cuda")
@@ -84,7 +98,7 @@ def main():
     t_end = time.time() + args.seconds
     seed, n, bad, skipped = args.seed, 0, 0, 0
     while time.time() < t_end:
-        r = one_case(spm, ctx, H, seed)
+        r = one_case(spm, ctx, H, seed, args.geometry)
         bad += r == "bad"
         skipped += r == "skipped"
         n += 1
