@@ -154,7 +154,7 @@ int scan_impl(spm_ctx *ctx, const spm_text *text, uint64_t begin, uint64_t end, 
               const uint32_t *d_seg_owned = nullptr, const std::function<int(spm_hits *)> *after_launch = nullptr);
 
 // ---- alignment of Myers hits (align.hip): the work list, the kernel classes, stage A and stage B.  Shared by
-// spm_hip_hits_align (hits of a scan) and, through jst_align_segments (jst.hpp), by spm_hip_jst_hits_align (segment hits of
+// spm_hip_hits_align (hits of a scan) and, through jst_align_segments (jst_hits_align.hpp), by spm_hip_jst_hits_align (segment hits of
 // a journaled-sequence search) and spm_hip_jst_selection_align (the distinct segment hits of a selection's records). ----
 struct align_work
 {

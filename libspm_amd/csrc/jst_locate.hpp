@@ -1,5 +1,5 @@
 // jst_locate.hpp -- begins and alignments of the records a pan-genome SELECTION kept (spm_hip_jst_selection_align; contract
-// in spm_hip.h, scheme in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst.hpp: it needs spm_jst and spm_jst_alns.
+// in spm_hip.h, scheme in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_hits_align.hpp: it needs spm_jst and spm_jst_alns.
 //
 // jst_fanout_kernel is a bijection from (segment hit ending on an owned symbol, member haplotype of its context) to
 // haplotype record.  A selection keeps records, not segment hits, so the map is inverted per kept record from the tables of
@@ -17,7 +17,7 @@
 //   (hipcub exclusive sum of the head flags: the number u of every distinct segment hit)
 //   jst_locate_emit_kernel  heads write the compact spm_hit list (already in pool order), every record uid[arrival] = u
 //   jst_aln_gather_kernel   one lane per kept record i: record i + seg_alns[uid[i]] -> the 40-byte spm_jst_aln i
-// Between emit and gather: jst_align_segments; the end: jst_alns_download / _close (jst.hpp's, shared with spm_hip_jst_hits_align).
+// Between emit and gather: jst_align_segments; the end: jst_alns_download / _close (jst_hits_align.hpp's, shared with spm_hip_jst_hits_align).
 // The scratch is laid out with scratch_layout.hpp; the launches, the sort, the sum and the events are device_order.hpp's; the
 // count of the flagged lanes is wave.hpp's.
 #pragma once
@@ -35,11 +35,8 @@ struct jst_locate_params
     uint32_t n;
     // the index (all of it bounds-checked against the sizes below before it is read)
     const uint64_t *hap_start; // [(n_blocks + 1) * n_hap]
-    const uint16_t *local_id;  // [(je - jb) * n_hap]
-    const uint64_t *ctx_base;  // [(je - jb) * n_groups + 1]
-    const uint64_t *ctx_off;   // [n_ctx + 1]
-    const uint32_t *ctx_owned; // [n_ctx]
-    uint64_t jb, je, n_ctx;
+    jst_ctx_tables T;          // (ctx_block is not read: the cell follows from the block and the haplotype)
+    uint64_t jb, je;
     uint32_t n_hap, n_groups, window;
     const int32_t *m;          // needle lengths [n_patterns]
     uint32_t n_patterns;
@@ -102,18 +99,18 @@ __global__ __launch_bounds__(256) void jst_locate_kernel(const jst_locate_params
         }
         if (ok) {
             const uint64_t jr = j - P.jb;
-            const uint16_t v = P.local_id[jr * P.n_hap + h];
+            const uint16_t v = P.T.local_id[jr * P.n_hap + h];
             const uint64_t cb = jr * P.n_groups + h / kJstGroup;
             ok = v != kJstNone;
             if (ok) {
-                const uint64_t c = P.ctx_base[cb] + (uint64_t)(v & 0x7FFFu);
-                ok = c < P.ctx_base[cb + 1] && c < P.n_ctx;
+                const uint64_t c = P.T.ctx_base[cb] + (uint64_t)(v & 0x7FFFu);
+                ok = c < P.T.ctx_base[cb + 1] && c < P.T.n_ctx;
                 if (ok) {
                     const uint64_t a = P.hap_start[j * P.n_hap + h];
                     const uint64_t ctx_lo = a - min((uint64_t)(P.window ? P.window - 1 : 0), a);
-                    const uint64_t off = P.ctx_off[c], len_c = P.ctx_off[c + 1] - off;
+                    const uint64_t off = P.T.ctx_off[c], len_c = P.T.ctx_off[c + 1] - off;
                     // the last symbol inside the context and not in its left context; the reported position inside it
-                    ok = pos >= ctx_lo && last >= ctx_lo && last - ctx_lo < len_c && last - ctx_lo >= P.ctx_owned[c];
+                    ok = pos >= ctx_lo && last >= ctx_lo && last - ctx_lo < len_c && last - ctx_lo >= P.T.ctx_owned[c];
                     const uint64_t at = off + (pos - ctx_lo);
                     ok = ok && (P.ctx_bits >= 64 || (at >> P.ctx_bits) == 0);
                     if (ok)
@@ -317,13 +314,9 @@ extern "C" int spm_hip_jst_selection_align(spm_jst_hits *h, uint32_t flags, spm_
         P.recs = reinterpret_cast<const unsigned long long *>(h->d);
         P.n = n32;
         P.hap_start = J->d_hap_start;
-        P.local_id = J->d_local_id;
-        P.ctx_base = J->d_ctx_base;
-        P.ctx_off = J->d_ctx_off;
-        P.ctx_owned = J->d_ctx_owned;
+        P.T = J->ctx_tables();
         P.jb = J->jb;
         P.je = J->je;
-        P.n_ctx = J->n_ctx;
         P.n_hap = J->H;
         P.n_groups = (J->H + kJstGroup - 1) / kJstGroup;
         P.window = J->window;

@@ -1,5 +1,5 @@
 // jst_project.hpp -- pan-genome alignments in reference coordinates (spm_hip_jst_alns_project; contract in spm_hip.h, scheme
-// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp (it needs spm_jst, spm_jst_alns and jst_first_ref)
+// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp (it needs spm_jst, spm_jst_alns and jst_walk_core.hpp's jst_first_ref)
 // and transcript_slots.hpp (the slot stage it begins with).
 //
 // Records that share a transcript slot share a context: they carry the same alleles over it and lie on the same reference

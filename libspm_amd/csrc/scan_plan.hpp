@@ -34,7 +34,7 @@ enum scan_counter : int
     kCntUnreadSurvMax = 9, // largest survivor demand of a pass
     kCntBandsSelected = 10, // entries of the list band_select_kernel kept (sets with surplus seeds)
     kCntRunHeads = 11,      // entries of the list of run heads (band_runs_kernel)
-    kCntFanOut = 12,        // records of the journaled-sequence fan-out launched behind the scan (jst.hpp)
+    kCntFanOut = 12,        // records of the journaled-sequence fan-out launched behind the scan (jst_search.hpp)
     kCntStateOnly = 13,     // where a state-only brute-force pass counts the hits it does not report
     kCntTicket = 15,        // the device-side fused copy: workgroups that have read the block (the last one clears it)
 };

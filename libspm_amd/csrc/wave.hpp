@@ -2,6 +2,7 @@
 // kernels of the result chain (select.hpp, jst_select.hpp, jst_locate.hpp, transcript_slots.hpp and the stages behind it,
 // jst_reads.hpp, jst_pairs.hpp).  gfx950.  Shuffles and one ballot: no LDS, no barrier.  All 64 lanes call every function here.
 //   count_flagged   one atomicAdd per wave for the lanes that raise a flag
+//   wave_reserve    one atomicAdd per wave for the output slots its lanes ask for (the fan-outs of jst_fanout.hpp)
 //   wave_run_scan   segmented inclusive scan over runs of equal id: the last lane of a run holds the run's combined value
 //   run_min, run_sum   the values the callers carry through it, alone or as the members of a struct of their own (scalar
 //                   members only: an array member sends the scan through scratch memory)
@@ -19,6 +20,24 @@ __device__ __forceinline__ void count_flagged(unsigned long long *counter, bool 
     const unsigned long long m = __ballot(flag);
     if ((threadIdx.x & 63) == 0 && m)
         atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// One atomicAdd per wave for slots in an output array: every lane asks for n of them (0: none) and receives the number of its
+// first, the lanes' slots in lane order -- the exclusive prefix of n over the lanes on top of what the counter held.
+__device__ __forceinline__ unsigned long long wave_reserve(unsigned long long *counter, uint32_t n)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t incl = n;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o);
+        if ((int)lane >= o)
+            incl += up;
+    }
+    const uint32_t total = __shfl(incl, 63);
+    unsigned long long base = 0;
+    if (lane == 0 && total)
+        base = atomicAdd(counter, (unsigned long long)total);
+    return __shfl(base, 0) + (incl - n);
 }
 
 // Lanes of one id are contiguous.  Inclusive segmented scan over the wave: the last lane of every run of equal `id` (the

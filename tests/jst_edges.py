@@ -163,8 +163,25 @@ def deleted_tree():
     return _tree(2050, DEG_REF, 1, [("all deleted", 0, DEG_REF, np.zeros(0, np.uint8), (0,))])
 
 
+# The 96-symbol, 3-haplotype tree of tests/cpp/jst_walk_core_cases.cpp (edge_tree(96, 3)): the same formula for the reference
+# and the same table, written out in both places.  WALK_STATS is what that program computes for block length 16 and window 8
+# from the brute-force haplotypes and the host-side walk, and asserts; tests/test_gpu_jst_edges.py asserts it of the device.
+WALK_REF, WALK_BLOCK, WALK_WINDOW = 96, 16, 8
+WALK_ROWS = [(0, 0, [3, 2, 1], (0,)), (0, 3, [], (1,)), (10, 1, [2], (0,)), (15, 34, [], (2,)), (28, 8, [], (1,)),
+             (30, 4, [], (0,)), (34, 1, [1], (0,)), (46, 0, [0, 1, 2, 3] * 3, (1,)), (60, 4, [], (1,)),
+             (64, 0, [0, 1, 2, 3], (1,)), (64, 1, [2], (1,)), (64, 6, [], (2,)), (70, 0, [1, 1], (2,)), (78, 5, [], (2,)),
+             (92, 14, [], (2,)), (95, 1, [0], (0, 1)), (96, 0, [2, 2, 0, 1, 3], (0, 1)), (96, 0, [3], (2,))]
+WALK_STATS = {"contexts": 16, "unique_contexts": 15, "context_symbols": 315, "haplotype_symbols": 252}
+
+
+def walk_tree():
+    """(ref, alleles, pool, cov, n_hap) of the tree above"""
+    ref = np.array([((i * 2654435761) & 0xFFFFFFFF) >> 30 for i in range(WALK_REF)], dtype=np.uint8)
+    return (ref,) + table(WALK_ROWS, 3) + (3,)
+
+
 WIDE_HAP = 1030
-WIDE_SITE = 2200     # no other allele within 100 positions
+WIDE_SITE = 2200    # no other allele within 100 positions
 
 
 def wide_tree():

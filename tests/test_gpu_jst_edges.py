@@ -203,6 +203,21 @@ def test_haplotypes_without_room_for_a_needle(spm, ctx):
     _close(jst, ps, ref_text)
 
 
+def test_index_statistics_equal_the_host_walk(spm, ctx):
+    """The device index of the 96-symbol tree counts what tests/cpp/jst_walk_core_cases.cpp counts on the host, from the
+    brute-force haplotypes and the same walk functions (tests/test_jst_walk_cpp.py runs that program): both sides assert
+    jst_edges.WALK_STATS."""
+    ref, alleles, pool, cov, n_hap = E.walk_tree()
+    assert E.legal(len(ref), alleles, cov)
+    ref_text = ctx.upload(ref)
+    jst = spm.Jst(ctx, ref_text, alleles, pool, cov, n_hap)
+    st = jst.index(E.WALK_WINDOW, E.WALK_BLOCK)
+    got = {k: int(getattr(st, k)) for k in E.WALK_STATS}
+    print(got)
+    assert got == E.WALK_STATS and st.n_blocks == E.WALK_REF // E.WALK_BLOCK
+    _close(jst, ref_text)
+
+
 def test_search_on_the_wide_tree(spm, ctx):
     t, ref_text, jst, ps, window = _open(spm, ctx, "wide", "myers")
     needles, plants, k, _myers = _set("wide", "myers")
