@@ -21,9 +21,11 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <string>
 #include <string_view>
 #include <tuple>
 #include <unordered_map>
@@ -135,6 +137,42 @@ struct jst_rescued_pair_loci
     std::vector<jst_rescue> rescues;
     std::vector<std::uint32_t> ops;     // the pool of CIGAR words as the device returned it
     bool operator==(jst_rescued_pair_loci const &) const noexcept = default;
+};
+
+// SAM lines (journaled_sequence_tree::map_sam; spm_hip_jst_ref_loci_sam in spm_hip.h): the text, and one record per line
+struct jst_sam_line
+{
+    std::uint64_t offset;               // first byte of the line in the text
+    std::uint32_t len, read, source;    // bytes with the \n; the read; locus index, rescue index or 0xFFFFFFFF
+    std::uint16_t flag;
+    std::uint8_t mapq, kind;            // spm_sam_kind
+    bool operator==(jst_sam_line const &) const noexcept = default;
+};
+
+struct jst_sam
+{
+    std::string text;
+    std::vector<jst_sam_line> lines;
+    bool operator==(jst_sam const &) const noexcept = default;
+};
+
+struct jst_sam_options
+{
+    std::string rname;
+    std::string symbols{"ACGT"};
+    std::vector<std::string> names;     // one per read (paired: per pair); empty: decimal indices
+    bool cigar_m{false}, secondary{false};
+    bool default_tables{true};          // false: the two tables below
+    std::array<std::uint8_t, 4> mapq_unique{60, 40, 30, 20}, mapq_multi{3, 1, 1, 0};
+};
+
+// what stands between the loci and the lines of map_sam: nothing (single-end), the pairing, the pairing and the mate rescue
+struct jst_sam_pairing
+{
+    bool paired{false};
+    std::uint32_t min_tlen{1}, max_tlen{1};
+    bool rescue{false};
+    std::uint32_t k{0};
 };
 
 struct jst_search_stats
@@ -887,6 +925,234 @@ public:
         return out;
     }
 
+    // ---- the SAM lines of a mapping (the contract of spm_hip_jst_ref_loci_sam in spm_hip.h), behind locate_reads, locate_pairs
+    // or locate_pairs_rescued as `pairing` says.  Device route: the same chain plus spm_hip_jst_ref_loci_sam.  Host route: the
+    // host structs those calls return and a plain std::string formatter (sam_host).  Both return the same.
+    jst_sam map_sam(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                    bool reports_begin, std::uint32_t strands, std::uint32_t n_reads, jst_sam_pairing const & pairing,
+                    jst_sam_options const & options, hip::hit_selection const & selection, std::size_t block = 0,
+                    jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return map_sam_device(needles, window, strands, n_reads, pairing, options, selection, block, stats);
+        return map_sam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options, selection, block, stats);
+    }
+
+    jst_sam map_sam_device(spm_patterns * needles, std::size_t window, std::uint32_t strands, std::uint32_t n_reads,
+                           jst_sam_pairing const & pairing, jst_sam_options const & options, hip::hit_selection const & selection,
+                           std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (!device_ready())
+            hip::fatal("journaled_sequence_tree::map_sam_device (tree not representable on the device)", hip::default_context());
+        jst_sam out;
+        std::vector<jst_read> reads;
+        std::vector<jst_pair> pairs;
+        std::vector<jst_rescue> rescues;
+        std::vector<std::uint32_t> rescue_ops;
+        spm_jst_pair_opts const opts{pairing.min_tlen, pairing.max_tlen, 0, 0};
+        rescue_request const rescue{spm_jst_rescue_opts{pairing.min_tlen, pairing.max_tlen, pairing.k, 0, 0}, _device->reference.get(),
+                                    needles, &rescues, &rescue_ops};
+        sam_request const sam{&options, needles, &out};
+        loci_of(device_alns(needles, window, selection, block, stats).get(), true, pairing.paired ? 2 : strands, n_reads, &reads,
+                pairing.paired ? &opts : nullptr, pairing.paired ? &pairs : nullptr,
+                pairing.paired && pairing.rescue ? &rescue : nullptr, &sam);
+        return out;
+    }
+
+    jst_sam map_sam_host(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                         bool reports_begin, std::uint32_t strands, std::uint32_t n_reads, jst_sam_pairing const & pairing,
+                         jst_sam_options const & options, hip::hit_selection const & selection, std::size_t block = 0,
+                         jst_search_stats * stats = nullptr) const
+    {
+        if (pairing.paired && pairing.rescue) { // (the rescue search itself has one route: the device's)
+            jst_rescued_pair_loci const R = locate_pairs_rescued(needles, window, n_reads, pairing.min_tlen, pairing.max_tlen, pairing.k,
+                                                                 selection, block, stats);
+            return sam_host(R.located.mapped, &R.located.pairs, &R.rescues, needle_ranks, 2, options);
+        }
+        if (pairing.paired) {
+            jst_pair_loci const P = locate_pairs(needles, window, needle_ranks, reports_begin, n_reads, pairing.min_tlen, pairing.max_tlen,
+                                                 selection, block, stats);
+            return sam_host(P.mapped, &P.pairs, nullptr, needle_ranks, 2, options);
+        }
+        return sam_host(locate_reads(needles, window, needle_ranks, reports_begin, strands, n_reads, selection, block, stats), nullptr,
+                        nullptr, needle_ranks, strands, options);
+    }
+
+    // The rule of spm_hip.h as a plain formatter over the host structs: which line a read reports, MAPQ from the tables, the
+    // mate fields, the secondary lines, every field with std::to_string.
+    static jst_sam sam_host(jst_read_loci const & mapped, std::vector<jst_pair> const * pairs, std::vector<jst_rescue> const * rescues,
+                            std::vector<std::vector<std::uint8_t>> const & needle_ranks, std::uint32_t strands,
+                            jst_sam_options const & o)
+    {
+        constexpr std::uint32_t none = 0xFFFFFFFFu;
+        std::vector<jst_ref_locus> const & loci = mapped.loci;
+        std::size_t const n_reads = mapped.reads.size();
+        bool const paired = pairs != nullptr;
+        if ((paired && (strands != 2 || pairs->size() * 2 != n_reads)) || (rescues != nullptr && !paired) ||
+            needle_ranks.size() != static_cast<std::size_t>(strands) * n_reads ||
+            (!o.names.empty() && o.names.size() != (paired ? pairs->size() : n_reads)))
+            hip::fatal("journaled_sequence_tree::map_sam (pairs, rescues, needles or names do not belong to these reads)",
+                       hip::default_context());
+        std::array<std::uint8_t, 4> const unique = o.default_tables ? std::array<std::uint8_t, 4>{60, 40, 30, 20} : o.mapq_unique;
+        std::array<std::uint8_t, 4> const multi = o.default_tables ? std::array<std::uint8_t, 4>{3, 1, 1, 0} : o.mapq_multi;
+        auto const mapq = [&](std::uint32_t n_best, std::uint32_t n_next) -> std::uint8_t {
+            if (n_best == 0)
+                return 0;
+            return n_best == 1 ? unique[std::min<std::uint32_t>(n_next, 3)] : multi[std::min<std::uint32_t>(n_best, 5) - 2];
+        };
+        auto const cigar_text = [&](std::vector<std::uint32_t> const & words) {
+            std::string text;
+            std::uint64_t run = 0;
+            for (std::size_t w = 0; w < words.size(); ++w) {
+                std::uint32_t const op = words[w] & 15u;
+                bool const is_m = o.cigar_m && (op == SPM_CIGAR_EQ || op == SPM_CIGAR_X);
+                run += words[w] >> 4;
+                if (is_m && w + 1 < words.size() && ((words[w + 1] & 15u) == SPM_CIGAR_EQ || (words[w + 1] & 15u) == SPM_CIGAR_X))
+                    continue;
+                text += std::to_string(run);
+                text += is_m ? 'M' : op == SPM_CIGAR_EQ ? '=' : op == SPM_CIGAR_X ? 'X' : op == SPM_CIGAR_INS ? 'I' : 'D';
+                run = 0;
+            }
+            return text;
+        };
+        auto const seq_text = [&](std::uint32_t needle) {
+            std::string text;
+            for (std::uint8_t const r : needle_ranks[needle])
+                text += r < o.symbols.size() ? o.symbols[r] : 'N';
+            return text;
+        };
+        struct reported
+        {
+            std::uint8_t kind{SPM_SAM_UNMAPPED}, mapq{0};
+            std::uint32_t source{0xFFFFFFFFu}, x0{0}, x1{0};
+            std::uint16_t flag{0};
+            std::uint64_t pos{0};
+            bool reverse{false};
+            std::int32_t tlen{0};
+        };
+        std::vector<reported> rep(n_reads);
+        auto const of_locus = [&](std::uint32_t i, std::uint16_t flag, std::uint32_t n_best, std::uint32_t n_next) {
+            reported R;
+            R.kind = SPM_SAM_LOCUS;
+            R.source = i;
+            R.flag = flag;
+            R.x0 = n_best;
+            R.x1 = n_next;
+            R.mapq = mapq(n_best, n_next);
+            R.pos = loci[i].aln.begin_position() + 1;
+            R.reverse = strands == 2 && (loci[i].needle & 1u);
+            return R;
+        };
+        if (!paired) {
+            for (std::size_t r = 0; r < n_reads; ++r) {
+                jst_read const & M = mapped.reads[r];
+                rep[r].flag = 0x4;
+                if (M.primary != none)
+                    rep[r] = of_locus(M.primary, strands == 2 && (loci[M.primary].needle & 1u) ? 0x10 : 0, M.n_best, M.n_next);
+            }
+        } else {
+            std::vector<std::size_t> used(pairs->size(), static_cast<std::size_t>(-1));
+            for (std::size_t j = 0; rescues != nullptr && j < rescues->size(); ++j) {
+                jst_rescue const & U = (*rescues)[j];
+                if (U.status != SPM_RESCUE_RESCUED)
+                    continue;
+                std::size_t & u = used[U.pair];
+                if (u == static_cast<std::size_t>(-1) || U.aln.errors() < (*rescues)[u].aln.errors())
+                    u = j;
+            }
+            for (std::size_t p = 0; p < pairs->size(); ++p) {
+                jst_pair const & P = (*pairs)[p];
+                std::uint32_t const locus[2] = {P.locus1, P.locus2};
+                std::uint16_t const flag[2] = {P.flag1, P.flag2};
+                std::int32_t tlen = P.tlen;
+                if (used[p] != static_cast<std::size_t>(-1)) {
+                    jst_rescue const & U = (*rescues)[used[p]];
+                    std::size_t const y = (U.needle >> 1) & 1u, a = y ^ 1u;
+                    jst_read const & A = mapped.reads[2 * p + a];
+                    reported & Y = rep[2 * p + y];
+                    Y.kind = SPM_SAM_RESCUE;
+                    Y.source = static_cast<std::uint32_t>(used[p]);
+                    Y.flag = U.flag;
+                    Y.pos = U.aln.begin_position() + 1;
+                    Y.reverse = (U.flag & 0x10) != 0;
+                    Y.x0 = A.n_best;
+                    Y.x1 = A.n_next;
+                    Y.mapq = mapq(A.n_best, A.n_next);
+                    auto const fixed = static_cast<std::uint16_t>(((flag[a] | 0x2) & ~0x28) | (Y.reverse ? 0x20 : 0));
+                    rep[2 * p + a] = of_locus(U.anchor, fixed, A.n_best, A.n_next);
+                    tlen = U.tlen;
+                } else {
+                    bool const proper = (P.flag1 & 0x2) != 0;
+                    for (std::size_t x = 0; x < 2; ++x) {
+                        jst_read const & M = mapped.reads[2 * p + x];
+                        rep[2 * p + x].flag = flag[x];
+                        if (locus[x] != none)
+                            rep[2 * p + x] = of_locus(locus[x], flag[x], proper ? P.n_best : M.n_best, proper ? P.n_next : M.n_next);
+                    }
+                }
+                rep[2 * p].tlen = rep[2 * p].kind == SPM_SAM_UNMAPPED ? 0 : tlen;
+                rep[2 * p + 1].tlen = rep[2 * p + 1].kind == SPM_SAM_UNMAPPED ? 0 : -tlen;
+            }
+        }
+        jst_sam out;
+        auto const emit = [&](std::size_t r, std::uint8_t kind, std::uint32_t source, std::uint16_t flag, std::uint8_t q,
+                              reported const & own, std::int32_t tlen) {
+            reported const * other = paired ? &rep[r ^ 1u] : nullptr;
+            std::uint64_t const mate_pos = other != nullptr && other->kind != SPM_SAM_UNMAPPED ? other->pos : 0;
+            bool const is_mapped = kind != SPM_SAM_UNMAPPED;
+            std::uint64_t pos = mate_pos;
+            std::string cigar = "*", seq, tags;
+            if (kind == SPM_SAM_LOCUS || kind == SPM_SAM_SECONDARY_LINE) {
+                jst_ref_locus const & X = loci[source];
+                pos = X.aln.begin_position() + 1;
+                cigar = cigar_text(X.aln.cigar());
+                seq = kind == SPM_SAM_LOCUS ? seq_text(X.needle) : "*";
+                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + "\tXH:i:" + std::to_string(X.haplotype_errors) + "\tXN:i:" +
+                       std::to_string(X.members.size());
+            } else if (kind == SPM_SAM_RESCUE) {
+                jst_rescue const & X = (*rescues)[source];
+                pos = X.aln.begin_position() + 1;
+                cigar = cigar_text(X.aln.cigar());
+                seq = seq_text(X.needle);
+                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + "\tXR:i:1";
+            } else {
+                seq = seq_text(static_cast<std::uint32_t>(strands * r));
+            }
+            if (kind == SPM_SAM_LOCUS || kind == SPM_SAM_RESCUE)
+                tags += "\tX0:i:" + std::to_string(own.x0) + "\tX1:i:" + std::to_string(own.x1);
+            std::size_t const name = paired ? r / 2 : r;
+            std::string line = o.names.empty() ? std::to_string(name) : o.names[name];
+            line += "\t" + std::to_string(flag) + "\t" + (is_mapped || mate_pos ? o.rname : std::string("*")) + "\t" + std::to_string(pos) +
+                    "\t" + std::to_string(q) + "\t" + cigar + "\t";
+            if (!paired || (!is_mapped && !mate_pos))
+                line += "*\t0";
+            else
+                line += "=\t" + std::to_string(mate_pos ? mate_pos : pos);
+            line += "\t" + std::to_string(tlen) + "\t" + seq + "\t*" + tags + "\n";
+            out.lines.push_back({out.text.size(), static_cast<std::uint32_t>(line.size()), static_cast<std::uint32_t>(r), source, flag, q,
+                                 kind});
+            out.text += line;
+        };
+        for (std::size_t r = 0; r < n_reads; ++r) {
+            reported const & own = rep[r];
+            emit(r, own.kind, own.source, own.flag, own.mapq, own, own.tlen);
+            if (!o.secondary)
+                continue;
+            jst_read const & M = mapped.reads[r];
+            for (std::uint32_t i = M.first_locus; i < M.first_locus + M.n_loci; ++i) {
+                if (own.kind == SPM_SAM_LOCUS && i == own.source)
+                    continue;
+                std::uint32_t flag = 0x100u | (strands == 2 && (loci[i].needle & 1u) ? 0x10u : 0u);
+                if (paired) {
+                    reported const & other = rep[r ^ 1u];
+                    flag |= 0x1u | (r & 1u ? 0x80u : 0x40u) | (other.kind == SPM_SAM_UNMAPPED ? 0x8u : other.reverse ? 0x20u : 0u);
+                }
+                emit(r, SPM_SAM_SECONDARY_LINE, i, static_cast<std::uint16_t>(flag), 255, own, 0);
+            }
+        }
+        return out;
+    }
+
     jst_pair_loci locate_pairs_host(spm_patterns * needles, std::size_t window,
                                     std::vector<std::vector<std::uint8_t>> const & needle_ranks, bool reports_begin,
                                     std::uint32_t n_reads, std::uint32_t min_tlen, std::uint32_t max_tlen,
@@ -1264,13 +1530,60 @@ private:
         std::vector<std::uint32_t> * ops;
     };
 
+    // what loci_of needs for the SAM lines behind everything else it was asked for: the options, the needles, where the answer goes
+    struct sam_request
+    {
+        jst_sam_options const * options;
+        spm_patterns const * needles;
+        jst_sam * out;
+    };
+
+    // spm_hip_jst_ref_loci_sam over the handles loci_of holds (pr, rs: nullptr where there are none), and its host view
+    static void sam_of(spm_jst_ref_loci * l, spm_jst_reads * rd, spm_jst_pairs * pr, spm_jst_rescues * rs, sam_request const & req)
+    {
+        spm_ctx * ctx = hip::default_context();
+        jst_sam_options const & o = *req.options;
+        std::string blob;
+        std::vector<std::uint64_t> off{0};
+        for (std::string const & name : o.names) {
+            blob += name;
+            off.push_back(blob.size());
+        }
+        spm_sam_opts opts{};
+        opts.rname = o.rname.c_str();
+        opts.symbols = o.symbols.c_str();
+        if (!o.names.empty()) {
+            opts.names = blob.data();
+            opts.name_off = off.data();
+            opts.n_names = o.names.size();
+        }
+        std::copy(o.mapq_unique.begin(), o.mapq_unique.end(), opts.mapq_unique);
+        std::copy(o.mapq_multi.begin(), o.mapq_multi.end(), opts.mapq_multi);
+        opts.mapq_defaults = o.default_tables ? 1 : 0;
+        opts.flags = (o.cigar_m ? SPM_SAM_CIGAR_M : 0u) | (o.secondary ? SPM_SAM_SECONDARY : 0u);
+        spm_sam * s = nullptr;
+        if (spm_hip_jst_ref_loci_sam(l, rd, pr, rs, req.needles, &opts, &s) != SPM_OK)
+            hip::fatal("spm_hip_jst_ref_loci_sam", ctx);
+        std::unique_ptr<spm_sam, decltype(&spm_hip_sam_destroy)> owner{s, &spm_hip_sam_destroy};
+        char const * text = nullptr;
+        spm_sam_line const * lines = nullptr;
+        std::uint64_t n_bytes = 0, n_lines = 0;
+        if (spm_hip_sam_view(s, &text, &n_bytes, &lines, &n_lines) != SPM_OK)
+            hip::fatal("spm_hip_sam_view", ctx);
+        req.out->text.assign(text, text + n_bytes);
+        req.out->lines.clear();
+        for (std::uint64_t i = 0; i < n_lines; ++i)
+            req.out->lines.push_back({lines[i].offset, lines[i].len, lines[i].read, lines[i].source, lines[i].flag, lines[i].mapq,
+                                      lines[i].kind});
+    }
+
     // the loci of device alignments: projection, collapse, the host view as it comes (it is in locus order)
     // ... and, where asked for, the summary of n_reads reads over them (spm_hip_jst_ref_loci_reads) and the pairs of their
     // mates (spm_hip_jst_ref_loci_pairs)
     static std::vector<jst_ref_locus> loci_of(spm_jst_alns * a, bool normalized = false, std::uint32_t strands = 1,
                                               std::uint32_t n_reads = 0, std::vector<jst_read> * reads = nullptr,
                                               spm_jst_pair_opts const * pair_opts = nullptr, std::vector<jst_pair> * pairs = nullptr,
-                                              rescue_request const * rescue = nullptr)
+                                              rescue_request const * rescue = nullptr, sam_request const * sam = nullptr)
     {
         spm_ctx * ctx = hip::default_context();
         spm_jst_ref_alns * r = projected(a, normalized);
@@ -1341,7 +1654,13 @@ private:
                                                               static_cast<std::size_t>(rr2[i].ref_end), rr2[i].score,
                                                               rops + rr2[i].cigar_off, rr2[i].cigar_len},
                                                     rr2[i].tlen, rr2[i].flag, rr2[i].status});
+                    if (sam != nullptr)
+                        sam_of(l, rd, pr, rs, *sam);
+                } else if (sam != nullptr) {
+                    sam_of(l, rd, pr, nullptr, *sam);
                 }
+            } else if (sam != nullptr) {
+                sam_of(l, rd, nullptr, nullptr, *sam);
             }
         }
         return out;

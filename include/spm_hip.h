@@ -717,7 +717,7 @@ void spm_hip_jst_ref_loci_destroy(spm_jst_ref_loci *l);
  * One spm_jst_read per read 0 .. n_reads - 1, in read order, from the loci of a collapse.  strands says how patterns name
  * reads: read = pattern / strands (2: a stranded set, forward = pattern 2r; 1: a plain set, every locus is forward).  The loci
  * of a read are contiguous in the loci order, forward before reverse, leftmost first, and the PRIMARY locus is the one with
- * the smallest (score, locus index).  MAPQ is a policy over (n_best, n_next) and is deliberately not computed.
+ * the smallest (score, locus index).  MAPQ is a policy over (n_best, n_next): spm_hip_jst_ref_loci_sam applies it.
  * The result is a pure function of the loci records: byte-identical across runs, host and device view alike.  It outlives
  * the loci handle.
  *   * SPM_E_INVALID: strands not 1 or 2, flags != 0, NULL arguments, strands * n_reads above 2^32 - 1.
@@ -764,7 +764,7 @@ void spm_hip_jst_reads_destroy(spm_jst_reads *r);
  * taken in 64 bits.  n_pairs counts the concordant combinations, n_best those whose sum equals the best, n_next those whose
  * sum equals the best + 1; all three are accumulated in 64 bits and clamped to 0xFFFFFFFF in the record.
  * No concordant combination: locus1 and locus2 are the mates' own primaries from the read summary (0xFFFFFFFF: unmapped),
- * tlen is 0, best is -1, the counts are 0.  MAPQ is a policy over (n_best, n_next) and is deliberately not computed.
+ * tlen is 0, best is -1, the counts are 0.  MAPQ is a policy over (n_best, n_next): spm_hip_jst_ref_loci_sam applies it.
  * flag1 / flag2 are the SAM FLAG of the two primary lines:
  *     0x1 always   0x2 proper pair   0x4 this mate has no locus   0x8 the other mate has no locus
  *     0x10 this mate's reported locus is a reverse pattern   0x20 the other mate's is   0x40 mate 1 / 0x80 mate 2
@@ -847,7 +847,7 @@ void spm_hip_jst_pairs_destroy(spm_jst_pairs *p);
  * and NO second-best end is tried.
  * Limits.  The search is against the REFERENCE, not the haplotypes: a mate that carries non-reference alleles pays for them
  * in edits, and k has to cover that; score is a reference distance (SAM NM), not a haplotype distance, and is never mixed
- * with the anchor's score.  FR orientation only (no RF, no FF).  No MAPQ.
+ * with the anchor's score.  FR orientation only (no RF, no FF).  MAPQ: see spm_hip_jst_ref_loci_sam.
  * flag is the SAM FLAG of the rescued mate's line: 0x1; 0x2 when RESCUED; 0x4 when NONE; 0x10 the needle is a reverse
  * pattern (not for NONE); 0x20 the anchor is; 0x40 / 0x80 the rescued mate is mate 1 / mate 2.
  * The result is a pure function of its inputs: byte-identical across runs, host and device view alike.  It outlives all
@@ -915,6 +915,129 @@ int spm_hip_jst_rescues_view(spm_jst_rescues *r, const spm_jst_rescue **records,
 int spm_hip_jst_rescues_device(spm_jst_rescues *r, const void **records, uint64_t *n, const void **ops, uint64_t *n_ops);
 int spm_hip_jst_rescues_stats(const spm_jst_rescues *r, spm_jst_rescues_stats *out);
 void spm_hip_jst_rescues_destroy(spm_jst_rescues *r);
+
+/* ---- SAM lines and MAPQ: what a mapper's user takes away -------------------------------------------------------------------
+ * One call turns (loci, read summary, optionally pairs and rescues, needle set) into SAM text in HBM plus one fixed-size
+ * spm_sam_line per line.  Lines are ordered by read; within a read the REPORTED line comes first, then (with
+ * SPM_SAM_SECONDARY) its secondary lines in locus order.  Single-end: pairs == NULL, the reads handle may have strands 1 or 2.
+ * Paired: reads 2p and 2p + 1 are the mates of pair p, strands == 2.
+ *
+ * MAPQ is a policy over (n_best, n_next), given by two tables of the opts:
+ *     mapq(n_best, n_next) = 0                               for n_best == 0
+ *                            mapq_unique[min(n_next, 3)]     for n_best == 1
+ *                            mapq_multi[min(n_best, 5) - 2]  otherwise
+ * (the counts arrive clamped to 0xFFFFFFFF; min takes care of that).  With mapq_defaults != 0 the tables of the opts are not
+ * read: mapq_multi = {3, 1, 1, 0}, which is floor(-10 log10(1 - 1/n)) for n = 2, 3, 4, >= 5, and mapq_unique = {60, 40, 30,
+ * 20}, which is a CONVENTION, not a derivation: a unique best placement is the surer the fewer placements stand one edit
+ * behind it, and these four numbers say so in the range mappers commonly print.  They are the caller's to override.
+ * Which counts a line uses.  Single-end: the read's.  Mates of a proper pair: the pair record's, on both lines.  Mates of a
+ * pair that is neither proper nor rescued: each mate's own read counts.  A rescued pair: both lines take the ANCHOR read's
+ * counts (the rescued mate was searched only beside the anchor: its placement is as sure as the anchor's).  Unmapped lines:
+ * MAPQ 0.  Secondary lines: 255 (SAM: unavailable).
+ *
+ * Which line a read reports, in paired mode with rescues.  Only records with status RESCUED are used.  A discordant pair can
+ * have two: the one with the smaller score is used, on a tie the first in record order (it rescues mate 1).  The rescued
+ * mate's reported line is the rescue alignment: ref_begin, ref_end, score as NM, its transcript in the rescues' pool, flag as
+ * the record has it.  The anchor's line is its locus with flag (pair flag | 0x2) & ~0x8 and 0x20 set iff the rescue's flag has
+ * 0x10.  Both carry the rescue's tlen (negated on mate 2's line, as the pairing defines).  Without a used rescue the lines
+ * are locus1 / locus2 with flag1 / flag2 and the pair's tlen.
+ * Mate fields.  Both mates have a reported line: RNEXT "=", PNEXT the mate's POS.  This mate mapped, the other not: "=", own
+ * POS, TLEN 0.  This mate unmapped, the other mapped: RNAME and POS are the mate's, RNEXT "=", PNEXT the mate's POS, MAPQ 0,
+ * CIGAR "*".  Neither: "* 0 0 * * 0 0".  Single-end: RNEXT "*", PNEXT 0, TLEN 0.
+ * Secondary lines (SPM_SAM_SECONDARY).  Every locus of the read that is not its reported line, in locus order; for a mate
+ * whose line came from a rescue that is all of its loci.  FLAG 0x100, 0x10 for a reverse pattern; paired also 0x1, 0x40 or
+ * 0x80, 0x20 iff the mate's reported line is reverse, 0x8 iff the mate has none; never 0x2.  TLEN 0, mate fields as above (a
+ * secondary's "own POS" is its own), SEQ "*".
+ * Fields of a mapped line.  QNAME: the caller's name (one per read, paired: one per pair, shared by the mates), without
+ * names the decimal index of the read / pair.  FLAG.  RNAME of the opts.  POS = ref_begin + 1.  MAPQ.  CIGAR: the words as
+ * <len><op> with I D = X; with SPM_SAM_CIGAR_M maximal runs of adjacent = / X words become one M of the summed length.  SEQ:
+ * the needle locus.pattern through `symbols` (sigma characters; a rank >= sigma prints N) -- the reverse pattern already is
+ * the reverse complement, which is what SAM wants.  QUAL "*".  Tags in this order: NM:i:<ref_score> XH:i:<score, the haplotype
+ * distance> XN:i:<n_haplotypes>, and on reported lines X0:i:<n_best> X1:i:<n_next>, the counts the MAPQ used.  A rescued
+ * mate's line has NM:i:<score> XR:i:1 X0 X1.  An unmapped line has SEQ = the forward read and no tags.  A locus inside an
+ * insertion (ref_begin == ref_end, all I) is printed as it is.  Every line ends in \n.
+ *
+ * Worked cases (rname "chr", default tables, no names).
+ *  1. Single-end read 7, primary locus [99,131) on pattern 15 (reverse), words 20= 1X 11=, ref_score 1, score 0, 2 haplotypes,
+ *     n_best 1, n_next 1:   7 16 chr 100 40 20=1X11= * 0 0 <SEQ> * NM:i:1 XH:i:0 XN:i:2 X0:i:1 X1:i:1   (CIGAR_M: 32M).
+ *  2. Case 1 of the pairing (flag1 0x63, flag2 0x93, tlen +200, loci [1000,1030) and [1170,1200), n_best 1, n_next 0), pair 0:
+ *     0 99 chr 1001 60 30= = 1171 200 ...   and   0 147 chr 1171 60 30= = 1001 -200 ...
+ *  3. Case 1 of the rescue (mate 1 at [1000,1030), flag1 0x49; mate 2 rescued at [1170,1200), 4 edits, flag 0x93, tlen +200; the
+ *     anchor read has n_best 2):  anchor flag (0x49 | 0x2) & ~0x8 | 0x20 = 0x63, both MAPQ 3, and mate 2's line ends in
+ *     NM:i:4 XR:i:1 X0:i:2 X1:i:0.
+ *  4. One mate only (flag1 0x49, flag2 0x85, mate 1 at [500,530)):  0 73 chr 501 60 30= = 501 0 ...   and
+ *     0 133 chr 501 0 * = 501 0 <SEQ> *.
+ *
+ *   * SPM_E_INVALID with a message, decided on the host before any launch: NULL arguments; unknown flags, a nonzero
+ *     reserved, a mapq_defaults above 1; rescues without pairs; handles of different contexts; a reads handle made from
+ *     another number of loci; pairs with a reads handle whose strands is not 2, or whose count is not reads / 2; a needle set
+ *     whose n is not strands x n_reads; strlen(symbols) != the set's sigma;
+ *     an rname or a name that is empty, longer than 254 bytes or contains a byte outside '!' .. '~' ('@' is allowed, "*"
+ *     alone is not); n_names not the number of reads (single-end) / pairs (paired); names without name_off or the other way
+ *     round; a name_off that does not ascend from 0.
+ *   * SPM_E_UNSUPPORTED, likewise: a MYERS_PREFIX set; reads + (with SPM_SAM_SECONDARY) loci above 2^32 - 1, the bound on
+ *     the number of lines.
+ *   * Everything else about the agreement of the inputs is tested on the device before a value is used as an index: the run
+ *     of a read lies inside the loci and names the read, a pair's loci lie in the runs of its mates, rescue records are
+ *     ordered by (pair, mate rescued), a rescue names a pair inside the pairs and an anchor that is that pair's locus, a
+ *     transcript lies inside its pool, the query length of a transcript (= + X + I) equals the needle's length.  A failure is
+ *     COUNTED and fails the call with SPM_E_INVALID, never a fault.
+ *   * Zero reads: an empty result and SPM_OK.
+ * The result is a pure function of its inputs: byte-identical across runs, host and device view equal.  It outlives all
+ * inputs (the strings of the opts are copied). */
+#define SPM_SAM_CIGAR_M 1u      /* = and X words print as M, adjacent ones merged */
+#define SPM_SAM_SECONDARY 2u    /* a line for every locus that is not its read's reported line */
+typedef struct spm_sam_opts {       /* 64 bytes */
+    const char *rname;              /* NUL-terminated */
+    const char *symbols;            /* NUL-terminated, sigma characters: the letter of every rank */
+    const char *names;              /* the names back to back, or NULL: decimal indices */
+    const uint64_t *name_off;       /* n_names + 1 offsets into names, name_off[0] == 0; NULL with names == NULL */
+    uint64_t n_names;               /* reads (single-end) or pairs (paired); 0 with names == NULL */
+    uint8_t mapq_unique[4];         /* n_best == 1: by min(n_next, 3) */
+    uint8_t mapq_multi[4];          /* n_best >= 2: by min(n_best, 5) - 2 */
+    uint32_t mapq_defaults;         /* 1: use the default tables, the two above are not read; 0: use them */
+    uint32_t flags;                 /* SPM_SAM_* */
+    uint64_t reserved;              /* must be 0 */
+} spm_sam_opts;
+enum spm_sam_kind { SPM_SAM_UNMAPPED = 0, SPM_SAM_LOCUS = 1, SPM_SAM_RESCUE = 2, SPM_SAM_SECONDARY_LINE = 3 };
+typedef struct spm_sam_line {       /* 24 bytes: what a BAM writer needs of a line besides the pools */
+    uint64_t offset;                /* first byte of the line in the text */
+    uint32_t len;                   /* bytes, the \n included */
+    uint32_t read;
+    uint32_t source;                /* locus index (LOCUS, SECONDARY_LINE), rescue index (RESCUE), 0xFFFFFFFF (UNMAPPED) */
+    uint16_t flag;
+    uint8_t mapq;
+    uint8_t kind;                   /* spm_sam_kind */
+} spm_sam_line;
+typedef struct spm_sam spm_sam;
+typedef struct spm_sam_stats {      /* 72 bytes */
+    float ms_total;                 /* device: the four stages below (HIP events) */
+    float ms_lines;                 /* first rescue of every pair, the reported lines, the line records */
+    float ms_measure;               /* the length of every line, the offsets */
+    float ms_write;                 /* the text, one wave per line */
+    float ms_stats;                 /* offsets into the records, the counts */
+    float ms_host;                  /* wall clock of the whole call (the views are downloaded when first asked for) */
+    uint64_t n_lines;               /* = n_reported + n_secondary + n_unmapped */
+    uint64_t n_bytes;
+    uint64_t n_reported;            /* lines of kind LOCUS or RESCUE */
+    uint64_t n_secondary;
+    uint64_t n_unmapped;
+    uint64_t n_rescue_lines;        /* of n_reported: kind RESCUE */
+} spm_sam_stats;
+int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs /* NULL: single-end */,
+                             spm_jst_rescues *rescues /* NULL; needs pairs */, const spm_patterns *patterns,
+                             const spm_sam_opts *opts, spm_sam **out);
+/* text is NOT NUL-terminated; every pointer may be NULL */
+int spm_hip_sam_view(spm_sam *s, const char **text, uint64_t *n_bytes, const spm_sam_line **lines, uint64_t *n_lines);
+int spm_hip_sam_device(spm_sam *s, const void **text, uint64_t *n_bytes, const void **lines, uint64_t *n_lines);
+int spm_hip_sam_stats(const spm_sam *s, spm_sam_stats *out);
+void spm_hip_sam_destroy(spm_sam *s);
+/* host only, no device needed.  The header: "@HD\tVN:1.6\tSO:unknown\n@SQ\tSN:<rname>\tLN:<ref_len>\n", not NUL-terminated.
+ * *len is what it needs; cap too small: SPM_E_OVERFLOW and nothing is written.  A bad rname: SPM_E_INVALID. */
+int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len);
+/* the MAPQ of (n_best, n_next) under the tables of opts (only the three mapq members are read); -1: NULL opts or
+ * mapq_defaults above 1 */
+int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint32_t n_next);
 
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to

@@ -274,6 +274,41 @@ class JstRescuesStats(C.Structure):
     ]
 
 
+class SamOpts(C.Structure):
+    _fields_ = [("rname", C.c_char_p), ("symbols", C.c_char_p), ("names", C.c_void_p), ("name_off", C.c_void_p),
+                ("n_names", C.c_uint64), ("mapq_unique", C.c_uint8 * 4), ("mapq_multi", C.c_uint8 * 4),
+                ("mapq_defaults", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class SamLine(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint32), ("read", C.c_uint32), ("source", C.c_uint32),
+                ("flag", C.c_uint16), ("mapq", C.c_uint8), ("kind", C.c_uint8)]
+
+
+# the numpy view of SamLine (spm_sam_line, 24 bytes)
+SAM_LINE_DTYPE = [("offset", "<u8"), ("len", "<u4"), ("read", "<u4"), ("source", "<u4"), ("flag", "<u2"), ("mapq", "u1"),
+                  ("kind", "u1")]
+SAM_CIGAR_M, SAM_SECONDARY = 1, 2
+SAM_UNMAPPED, SAM_LOCUS, SAM_RESCUE, SAM_SECONDARY_LINE = 0, 1, 2, 3
+
+
+class SamStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_lines", C.c_float),
+        ("ms_measure", C.c_float),
+        ("ms_write", C.c_float),
+        ("ms_stats", C.c_float),
+        ("ms_host", C.c_float),
+        ("n_lines", C.c_uint64),
+        ("n_bytes", C.c_uint64),
+        ("n_reported", C.c_uint64),
+        ("n_secondary", C.c_uint64),
+        ("n_unmapped", C.c_uint64),
+        ("n_rescue_lines", C.c_uint64),
+    ]
+
+
 class JstNormalizeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -454,6 +489,14 @@ def lib():
         "spm_hip_jst_rescues_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_rescues_stats": (C.c_int, [vp, C.POINTER(JstRescuesStats)]),
         "spm_hip_jst_rescues_destroy": (None, [vp]),
+        "spm_hip_jst_ref_loci_sam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(SamOpts), C.POINTER(vp)]),
+        "spm_hip_sam_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(SamLine)),
+                                       C.POINTER(C.c_uint64)]),
+        "spm_hip_sam_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_sam_stats": (C.c_int, [vp, C.POINTER(SamStats)]),
+        "spm_hip_sam_destroy": (None, [vp]),
+        "spm_hip_sam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "spm_hip_sam_mapq": (C.c_int, [C.POINTER(SamOpts), C.c_uint32, C.c_uint32]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -506,6 +549,8 @@ EXPORTS = [
     "spm_hip_jst_pairs_destroy",
     "spm_hip_jst_pairs_rescue", "spm_hip_jst_rescues_view", "spm_hip_jst_rescues_device", "spm_hip_jst_rescues_stats",
     "spm_hip_jst_rescues_destroy",
+    "spm_hip_jst_ref_loci_sam", "spm_hip_sam_view", "spm_hip_sam_device", "spm_hip_sam_stats", "spm_hip_sam_destroy",
+    "spm_hip_sam_header", "spm_hip_sam_mapq",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

@@ -1,0 +1,588 @@
+// jst_sam.hpp -- SAM lines and MAPQ (spm_hip_jst_ref_loci_sam; contract in spm_hip.h, scheme in DESIGN.md 4.11, the rule in
+// jst_sam_core.hpp).  gfx950.  Included by jst.hip behind jst_rescue.hpp, whose handles it reads.
+//   jst_sam_first_rescue_kernel   one lane per rescue record: the ordering test against the record before it, and the first
+//                                 record of every pair scattered into first_rescue[pair];
+//   jst_sam_lines_kernel<kEmit>   one lane per read: the agreement tests, the reported line of the read (both mates of a pair
+//                                 derive the pair's plan: it is a function of the records alone) and, first, the number of
+//                                 its lines; an exclusive sum later, the same lanes write the line records;
+//   jst_sam_measure_kernel        one lane per line: the record resolved against its sources (every index tested), the byte
+//                                 length of the line by the measuring sink;
+//   jst_sam_write_kernel          one wave per line, four lines per workgroup: the same composition into the wave sink --
+//                                 byte i of a field goes to lane i, numbers one digit per lane, CIGAR one word per lane with
+//                                 a wave prefix sum over the words' text lengths and a segmented sum for the M runs.  Byte
+//                                 stores straight to HBM: consecutive lanes store consecutive bytes.  No atomics;
+//   jst_sam_stats_kernel          one lane per line: offset and length into the record, the counts by count_flagged.
+#pragma once
+
+#include <string>
+
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "device_order.hpp"
+#include "jst_sam_core.hpp"
+#include "scratch_layout.hpp"
+#include "wave.hpp"
+
+namespace spm_hip
+{
+
+enum {
+    kSamCntBad = 0,
+    kSamCntLines,
+    kSamCntBytes,
+    kSamCntReported,
+    kSamCntSecondary,
+    kSamCntUnmapped,
+    kSamCntRescue,
+    kSamCnts
+};
+
+struct jst_sam_params
+{
+    jst_sam_src S;
+    uint32_t *first_rescue = nullptr; // [n_pairs], what S.first_rescue reads
+    uint32_t *cnt = nullptr;          // [n_reads] lines of every read
+    uint32_t *offs = nullptr;         // [n_reads] their exclusive sum
+    spm_sam_line *lines = nullptr;    // [cap_lines]
+    jst_sam_aux *aux = nullptr;       // [cap_lines]
+    uint32_t *len = nullptr;          // [cap_lines] bytes of every line, 0 beyond the last
+    uint64_t *off64 = nullptr;        // [cap_lines] their exclusive sum
+    uint32_t cap_lines = 0;           // the host's bound on the number of lines
+    uint32_t n_lines = 0;             // write and stats: what the lines stage counted
+    char *text = nullptr;
+    uint64_t n_bytes = 0;
+    unsigned long long *counts = nullptr; // [kSamCnts]
+};
+
+// one atomicAdd per wave: the sum of v over its lanes
+__device__ __forceinline__ void count_summed(unsigned long long *counter, unsigned long long v)
+{
+    for (int d = 32; d; d >>= 1)
+        v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0 && v)
+        atomicAdd(counter, v);
+}
+
+__global__ __launch_bounds__(256) void jst_sam_first_rescue_kernel(const jst_sam_params P)
+{
+    const unsigned long long j = blockIdx.x * 256ull + threadIdx.x;
+    bool bad = false;
+    if (j < P.S.n_rescues) {
+        const spm_jst_rescue R = P.S.rescues[j];
+        bool first = true;
+        bad = !jst_sam_rescue_names_pair(R, P.S.n_pairs);
+        if (j > 0) {
+            const spm_jst_rescue before = P.S.rescues[j - 1];
+            bad = bad || !jst_sam_rescues_ordered(before, R);
+            first = before.pair != R.pair;
+        }
+        if (!bad && first)
+            P.first_rescue[R.pair] = (uint32_t)j;
+    }
+    count_flagged(&P.counts[kSamCntBad], bad);
+}
+
+template <bool kEmit> __global__ __launch_bounds__(256) void jst_sam_lines_kernel(const jst_sam_params P)
+{
+    const unsigned long long r = blockIdx.x * 256ull + threadIdx.x;
+    bool bad = false;
+    uint32_t n = 0;
+    if (r < P.S.n_reads) {
+        jst_sam_reported own, other;
+        int32_t tlen = 0;
+        if (P.S.pairs) {
+            const jst_sam_pair_plan plan = jst_sam_plan_pair(P.S, (uint32_t)(r / 2));
+            bad = !plan.ok;
+            own = plan.mate[r & 1];
+            other = plan.mate[(r & 1) ^ 1];
+            tlen = (r & 1) ? (int32_t)(0u - (uint32_t)plan.tlen) : plan.tlen;
+        } else {
+            bool ok = true;
+            own = jst_sam_plan_single(P.S, (uint32_t)r, ok);
+            bad = !ok;
+        }
+        if (!bad) {
+            n = jst_sam_line_count(P.S.reads[r], own, P.S.flags);
+            if (kEmit) {
+                const uint32_t at = P.offs[r];
+                if (at <= P.cap_lines)
+                    jst_sam_read_lines(P.S, (uint32_t)r, own, P.S.pairs ? &other : nullptr, tlen, P.lines + at, P.aux + at, P.cap_lines - at);
+            }
+        }
+        if (!kEmit)
+            P.cnt[r] = n;
+    }
+    if (!kEmit) {
+        count_flagged(&P.counts[kSamCntBad], bad);
+        count_summed(&P.counts[kSamCntLines], n);
+    }
+}
+
+__global__ __launch_bounds__(256) void jst_sam_measure_kernel(const jst_sam_params P)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    const unsigned long long n_lines = P.counts[kSamCntLines]; // (the lines stage is complete: stream order)
+    bool bad = false;
+    uint64_t n = 0;
+    if (i < P.cap_lines) {
+        if (i < n_lines) {
+            jst_sam_fields F;
+            bad = !jst_sam_resolve(P.S, P.lines[i], P.aux[i], F, true);
+            if (!bad) {
+                jst_sam_measure M;
+                jst_sam_compose(P.S, F, M);
+                n = M.n;
+                bad = n > 0xFFFFFFFFull;
+            }
+            n = bad ? 0 : n;
+        }
+        P.len[i] = (uint32_t)n;
+    }
+    count_flagged(&P.counts[kSamCntBad], bad);
+    count_summed(&P.counts[kSamCntBytes], n);
+}
+
+// The wave sink: the composition of one line, byte i of a field to lane i.  cur is wave-uniform.  No store lands outside
+// [cur at construction, end): the line's own bytes.
+struct jst_sam_wave_sink
+{
+    char *to;
+    uint64_t cur, end;
+    uint32_t lane;
+
+    __device__ __forceinline__ void store(uint64_t at, char c)
+    {
+        if (at < end)
+            to[at] = c;
+    }
+    __device__ __forceinline__ void text(uint64_t lit, uint32_t n_lit)
+    {
+        if (lane < n_lit)
+            store(cur + lane, (char)(lit >> (8 * lane)));
+        cur += n_lit;
+    }
+    // literal, sign and digits are at most 8 + 1 + 20 characters: one pass of the wave, lane i writes character i
+    __device__ __forceinline__ void num(uint64_t lit, uint32_t n_lit, uint64_t v, bool negative)
+    {
+        const uint32_t head = n_lit + (negative ? 1u : 0u), len = jst_sam_dec_len(v);
+        if (lane < n_lit)
+            store(cur + lane, (char)(lit >> (8 * lane)));
+        else if (lane < head)
+            store(cur + lane, '-');
+        else if (lane < head + len)
+            store(cur + lane, jst_sam_dec_char(v, len, lane - head));
+        cur += head + len;
+    }
+    __device__ __forceinline__ void bytes(const char *p, uint64_t n)
+    {
+        for (uint64_t i = lane; i < n; i += kWave)
+            store(cur + i, p[i]);
+        cur += n;
+    }
+    __device__ __forceinline__ void seq(const uint8_t *ranks, uint32_t m, const char *symbols, uint32_t sigma)
+    {
+        for (uint32_t i = lane; i < m; i += kWave)
+            store(cur + i, jst_sam_seq_char(ranks[i], symbols, sigma));
+        cur += m;
+    }
+    // lane w of a pass takes word w.  A word that ends a printed item -- every word, or with `merge` the last word of a
+    // maximal run of = / X words -- holds the item's length (a segmented sum over the wave, plus what the pass before left
+    // open) and writes <len><op> at the wave prefix sum of the items' text lengths.
+    __device__ __forceinline__ void cigar(const uint32_t *words, uint32_t n, bool merge)
+    {
+        uint64_t carry = 0; // the length of the M run the passes so far left open
+        bool open = false;
+        for (uint32_t base = 0; base < n; base += kWave) {
+            const uint32_t w = base + lane;
+            const bool live = w < n;
+            const uint32_t word = live ? words[w] : 0u;
+            const bool has_next = live && w + 1 < n;
+            const uint32_t next = has_next ? words[w + 1] : 0u;
+            const bool is_m = live && merge && jst_sam_op_is_m(word);
+            const bool next_m = has_next && merge && jst_sam_op_is_m(next);
+            const int left_m = __shfl_up(is_m ? 1 : 0, 1);
+            const bool prev_m = lane == 0 ? open : left_m != 0;
+            const bool start = !(is_m && prev_m);
+            const uint32_t id = (uint32_t)__popcll(__ballot(start) & (~0ull >> (63 - lane)));
+            run_sum<uint64_t> v{live ? (uint64_t)(word >> 4) : 0ull};
+            if (lane == 0 && !start)
+                v.v += carry;
+            wave_run_scan(id, v);
+            const bool last = live && !(is_m && next_m);
+            const char op = jst_sam_op_char(word & 15u, merge);
+            const uint32_t len = last ? jst_sam_word_len(v.v) : 0u;
+            uint32_t incl = len;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(incl, o);
+                if ((int)lane >= o)
+                    incl += up;
+            }
+            const uint32_t total = __shfl(incl, 63);
+            const uint64_t at = cur + (incl - len);
+            for (uint32_t i = 0; i < len; ++i)
+                store(at + i, jst_sam_word_char(v.v, op, len, i));
+            open = __shfl((live && !last) ? 1 : 0, 63) != 0;
+            carry = __shfl(v.v, 63);
+            cur += total;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void jst_sam_write_kernel(const jst_sam_params P)
+{
+    const uint32_t wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const unsigned long long i = blockIdx.x * 4ull + wv;
+    if (i >= P.n_lines)
+        return; // (whole waves: i is uniform across the wave, and no workgroup barrier follows)
+    jst_sam_fields F;
+    if (!jst_sam_resolve(P.S, P.lines[i], P.aux[i], F, false))
+        return; // (the measure stage resolved this record and counted a failure: the host does not get here)
+    const uint64_t begin = P.off64[i], end = begin + P.len[i];
+    jst_sam_wave_sink out{P.text, begin, end < P.n_bytes ? end : P.n_bytes, lane};
+    jst_sam_compose(P.S, F, out);
+}
+
+__global__ __launch_bounds__(256) void jst_sam_stats_kernel(const jst_sam_params P)
+{
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    uint32_t kind = ~0u;
+    if (i < P.n_lines) {
+        kind = P.lines[i].kind;
+        P.lines[i].offset = P.off64[i];
+        P.lines[i].len = P.len[i];
+    }
+    count_flagged(&P.counts[kSamCntReported], kind == SPM_SAM_LOCUS || kind == SPM_SAM_RESCUE);
+    count_flagged(&P.counts[kSamCntSecondary], kind == SPM_SAM_SECONDARY_LINE);
+    count_flagged(&P.counts[kSamCntUnmapped], kind == SPM_SAM_UNMAPPED);
+    count_flagged(&P.counts[kSamCntRescue], kind == SPM_SAM_RESCUE);
+}
+
+struct sam_cnt_op
+{
+    const uint32_t *cnt;
+    __host__ __device__ uint32_t operator()(uint32_t i) const { return cnt[i]; }
+};
+struct sam_len_op
+{
+    const uint32_t *len;
+    __host__ __device__ uint64_t operator()(uint32_t i) const { return len[i]; }
+};
+
+} // namespace spm_hip
+
+struct spm_sam
+{
+    spm_ctx *ctx = nullptr;
+    char *d_text = nullptr;
+    spm_sam_line *d_lines = nullptr;
+    uint64_t n_bytes = 0, n_lines = 0;
+    bool have_host = false; // the views are downloaded when first asked for
+    std::vector<char> host_text;
+    std::vector<spm_sam_line> host_lines;
+    spm_sam_stats stats{};
+};
+static_assert(sizeof(spm_sam_opts) == 64 && sizeof(spm_sam_line) == 24 && sizeof(spm_sam_stats) == 72 && sizeof(spm_hip::jst_sam_aux) == 24,
+              "spm_hip.h states these sizes");
+
+extern "C" void spm_hip_sam_destroy(spm_sam *s)
+{
+    if (!s)
+        return;
+    if (s->ctx && (s->d_text || s->d_lines))
+        hipStreamSynchronize(s->ctx->stream);
+    hipFree(s->d_text);
+    hipFree(s->d_lines);
+    delete s;
+}
+
+extern "C" int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint32_t n_next)
+{
+    if (!opts || opts->mapq_defaults > 1)
+        return -1;
+    return spm_hip::jst_sam_mapq(spm_hip::jst_sam_tables_of(*opts), n_best, n_next);
+}
+
+extern "C" int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len)
+{
+    if (!rname || !len || (!buf && cap))
+        return SPM_E_INVALID;
+    if (!spm_hip::jst_sam_name_ok(rname, strlen(rname))) {
+        SPM_SET_ERR((spm_ctx *)nullptr, "spm_hip_sam_header: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'");
+        return SPM_E_INVALID;
+    }
+    const std::string h = std::string("@HD\tVN:1.6\tSO:unknown\n@SQ\tSN:") + rname + "\tLN:" + std::to_string(ref_len) + "\n";
+    *len = h.size();
+    if (h.size() > cap)
+        return SPM_E_OVERFLOW;
+    memcpy(buf, h.data(), h.size());
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                        const spm_patterns *ps, const spm_sam_opts *opts, spm_sam **out)
+{
+    using namespace spm_hip;
+    static const char *const who = "spm_hip_jst_ref_loci_sam";
+    if (!l || !out)
+        return SPM_E_INVALID;
+    *out = nullptr;
+    spm_ctx *ctx = l->ctx;
+    const auto t_call = clk::now();
+    if (!r || !ps || !opts || !opts->rname || !opts->symbols) {
+        SPM_SET_ERR(ctx, "%s: NULL %s", who, !r ? "reads handle" : !ps ? "patterns" : !opts ? "opts" : !opts->rname ? "rname" : "symbols");
+        return SPM_E_INVALID;
+    }
+    if ((opts->flags & ~(SPM_SAM_CIGAR_M | SPM_SAM_SECONDARY)) || opts->reserved || opts->mapq_defaults > 1) {
+        SPM_SET_ERR(ctx, "%s: unknown flag bits 0x%x, reserved %llu (must be 0) or mapq_defaults %u (0 or 1)", who, opts->flags,
+                    (unsigned long long)opts->reserved, opts->mapq_defaults);
+        return SPM_E_INVALID;
+    }
+    if (rs && !pr) {
+        SPM_SET_ERR(ctx, "%s: rescues without pairs", who);
+        return SPM_E_INVALID;
+    }
+    if (r->ctx != ctx || ps->ctx != ctx || (pr && pr->ctx != ctx) || (rs && rs->ctx != ctx)) {
+        SPM_SET_ERR(ctx, "%s: the %s belongs to another context", who,
+                    r->ctx != ctx ? "reads handle" : ps->ctx != ctx ? "needle set" : (pr && pr->ctx != ctx) ? "pairs handle" : "rescues handle");
+        return SPM_E_INVALID;
+    }
+    if (r->n_loci != l->n) {
+        SPM_SET_ERR(ctx, "%s: the reads handle was made from %llu loci, these are %llu", who, (unsigned long long)r->n_loci,
+                    (unsigned long long)l->n);
+        return SPM_E_INVALID;
+    }
+    if (pr && (r->strands != 2 || (r->n & 1) || pr->n != r->n / 2)) {
+        SPM_SET_ERR(ctx, "%s: %llu pairs do not belong to %llu reads made with strands == %u (mates need 2)", who, (unsigned long long)pr->n,
+                    (unsigned long long)r->n, r->strands);
+        return SPM_E_INVALID;
+    }
+    if (ps->algo == SPM_ALGO_MYERS_PREFIX) {
+        SPM_SET_ERR(ctx, "%s: a MYERS_PREFIX needle set has no alignments to print (not supported)", who);
+        return SPM_E_UNSUPPORTED;
+    }
+    if ((uint64_t)ps->n != (uint64_t)r->strands * r->n) {
+        SPM_SET_ERR(ctx, "%s: %u needles are not the set of %llu reads on %u strand(s)", who, ps->n, (unsigned long long)r->n, r->strands);
+        return SPM_E_INVALID;
+    }
+    if (strlen(opts->symbols) != ps->sigma) {
+        SPM_SET_ERR(ctx, "%s: symbols has %zu characters, the needle set sigma %u", who, strlen(opts->symbols), ps->sigma);
+        return SPM_E_INVALID;
+    }
+    const size_t rname_len = strlen(opts->rname);
+    if (!jst_sam_name_ok(opts->rname, rname_len)) {
+        SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
+        return SPM_E_INVALID;
+    }
+    const uint64_t n_named = pr ? pr->n : r->n;
+    if (!opts->names != !opts->name_off || (!opts->names && opts->n_names) || (opts->names && opts->n_names != n_named)) {
+        SPM_SET_ERR(ctx, "%s: %llu names (names %s, name_off %s) for %llu %s", who, (unsigned long long)opts->n_names,
+                    opts->names ? "given" : "NULL", opts->name_off ? "given" : "NULL", (unsigned long long)n_named, pr ? "pairs" : "reads");
+        return SPM_E_INVALID;
+    }
+    if (opts->names) {
+        if (opts->name_off[0] != 0) {
+            SPM_SET_ERR(ctx, "%s: name_off does not ascend from 0", who);
+            return SPM_E_INVALID;
+        }
+        for (uint64_t i = 0; i < n_named; ++i) {
+            if (opts->name_off[i + 1] < opts->name_off[i]) {
+                SPM_SET_ERR(ctx, "%s: name_off does not ascend at name %llu", who, (unsigned long long)i);
+                return SPM_E_INVALID;
+            }
+            if (!jst_sam_name_ok(opts->names + opts->name_off[i], opts->name_off[i + 1] - opts->name_off[i])) {
+                SPM_SET_ERR(ctx, "%s: name %llu is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who,
+                            (unsigned long long)i);
+                return SPM_E_INVALID;
+            }
+        }
+    }
+    const bool secondary = (opts->flags & SPM_SAM_SECONDARY) != 0;
+    if (l->n > 0xFFFFFFFFull || r->n + (secondary ? l->n : 0) > 0xFFFFFFFFull || (rs && rs->n > 0xFFFFFFFFull)) {
+        SPM_SET_ERR(ctx, "%s: %llu reads and %llu loci: more than 2^32 - 1 lines", who, (unsigned long long)r->n, (unsigned long long)l->n);
+        return SPM_E_UNSUPPORTED;
+    }
+    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<spm_sam, void (*)(spm_sam *)> R(new spm_sam, spm_hip_sam_destroy);
+    R->ctx = ctx;
+    const uint32_t n_reads = (uint32_t)r->n;
+    if (n_reads) {
+        hipStream_t st = ctx->stream;
+        hip_events<8> ev;
+        SPM_HIP_CHECK(ctx, ev.create());
+        SPM_TRY(spm_align_tables(ps)); // the needles' ranks on the device (built once per set)
+        jst_sam_params P{};
+        jst_sam_src &S = P.S;
+        S.loci = l->d_loci;
+        S.n_loci = l->d_loci ? (uint32_t)l->n : 0u;
+        S.ops = l->d_ops;
+        S.n_ops = l->d_ops ? l->n_ops : 0;
+        S.reads = r->d;
+        S.n_reads = n_reads;
+        S.strands = r->strands;
+        S.pairs = pr ? pr->d : nullptr;
+        S.n_pairs = pr ? (uint32_t)pr->n : 0u;
+        S.rescues = rs ? rs->d : nullptr;
+        S.n_rescues = rs && rs->d ? (uint32_t)rs->n : 0u;
+        S.rescue_ops = rs ? rs->d_ops : nullptr;
+        S.n_rescue_ops = rs && rs->d_ops ? rs->n_ops : 0;
+        S.ranks = ps->d_al_ranks;
+        S.offsets = ps->d_al_offsets;
+        S.m = ps->d_m;
+        S.n_needles = ps->n;
+        S.sigma = ps->sigma;
+        S.rname_len = (uint32_t)rname_len;
+        S.tables = jst_sam_tables_of(*opts);
+        S.flags = opts->flags;
+        P.cap_lines = n_reads + (secondary ? S.n_loci : 0u);
+        // ---- the strings of the opts, copied: rname, symbols, names, name_off in one allocation ----
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t names_bytes = opts->names ? (size_t)opts->name_off[n_named] : 0;
+        const size_t b_rname = al(rname_len + 1), b_sym = al(ps->sigma + 1), b_off = al(opts->names ? (n_named + 1) * 8 : 0);
+        std::vector<uint8_t> img(b_rname + b_sym + b_off + al(names_bytes + 1), 0);
+        memcpy(img.data(), opts->rname, rname_len);
+        memcpy(img.data() + b_rname, opts->symbols, ps->sigma);
+        if (opts->names) {
+            memcpy(img.data() + b_rname + b_sym, opts->name_off, (n_named + 1) * 8);
+            memcpy(img.data() + b_rname + b_sym + b_off, opts->names, names_bytes);
+        }
+        dev_scratch keep;
+        char *d_img = nullptr;
+        SPM_HIP_CHECK(ctx, keep.alloc(&d_img, img.size()));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, st));
+        S.rname = d_img;
+        S.symbols = d_img + b_rname;
+        if (opts->names) {
+            S.name_off = reinterpret_cast<const uint64_t *>(d_img + b_rname + b_sym);
+            S.names = d_img + b_rname + b_sym + b_off;
+        }
+        // ---- scratch ----
+        size_t tmp32 = 0, tmp64 = 0;
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(sam_cnt_op{nullptr}), n_reads, &tmp32));
+        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint64_t>(ctx, counted<uint64_t>(sam_len_op{nullptr}), P.cap_lines, &tmp64));
+        uint8_t *d_tmp = nullptr;
+        scratch_layout L;
+        L.take(P.first_rescue, S.n_pairs);
+        L.take(P.cnt, n_reads);
+        L.take(P.offs, n_reads);
+        L.take(P.aux, P.cap_lines);
+        L.take(P.len, P.cap_lines);
+        L.take(P.off64, P.cap_lines);
+        L.take(P.counts, kSamCnts);
+        L.take(d_tmp, std::max(tmp32, tmp64));
+        SPM_TRY(ensure_scratch(ctx, L.bytes()));
+        L.bind(ctx->d_scratch);
+        S.first_rescue = rs ? P.first_rescue : nullptr;
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_lines, (size_t)P.cap_lines * sizeof(spm_sam_line)));
+        P.lines = R->d_lines;
+        // ---- lines ----
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kSamCnts * 8, st));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
+        if (rs) {
+            SPM_HIP_CHECK(ctx, hipMemsetAsync(P.first_rescue, 0xFF, (size_t)S.n_pairs * 4, st));
+            if (S.n_rescues)
+                SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_first_rescue_kernel, S.n_rescues, P));
+        }
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<false>, n_reads, P));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp32, counted<uint32_t>(sam_cnt_op{P.cnt}), P.offs, n_reads));
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<true>, n_reads, P));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
+        // ---- measure ----
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_measure_kernel, P.cap_lines, P));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+        const unsigned long long *c = ctx->h_counters;
+        if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
+            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools or the "
+                             "needle set; nothing was written", who, c[kSamCntBad]);
+            return SPM_E_INVALID;
+        }
+        P.n_lines = (uint32_t)c[kSamCntLines];
+        P.n_bytes = c[kSamCntBytes];
+        R->n_lines = P.n_lines;
+        R->n_bytes = P.n_bytes;
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_text, std::max<uint64_t>(P.n_bytes, 1)));
+        P.text = R->d_text;
+        // ---- write ----
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
+        hipLaunchKernelGGL(jst_sam_write_kernel, dim3((P.n_lines + 3) / 4), dim3(256), 0, st, P);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
+        // ---- stats ----
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_stats_kernel, P.n_lines, P));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+        R->stats.n_lines = P.n_lines;
+        R->stats.n_bytes = P.n_bytes;
+        R->stats.n_reported = c[kSamCntReported];
+        R->stats.n_secondary = c[kSamCntSecondary];
+        R->stats.n_unmapped = c[kSamCntUnmapped];
+        R->stats.n_rescue_lines = c[kSamCntRescue];
+        hipEventElapsedTime(&R->stats.ms_lines, ev[0], ev[1]);
+        hipEventElapsedTime(&R->stats.ms_measure, ev[1], ev[2]);
+        hipEventElapsedTime(&R->stats.ms_write, ev[3], ev[4]);
+        hipEventElapsedTime(&R->stats.ms_stats, ev[4], ev[5]);
+        R->stats.ms_total = R->stats.ms_lines + R->stats.ms_measure + R->stats.ms_write + R->stats.ms_stats;
+    }
+    R->stats.ms_host = ms_since(t_call);
+    if (spm_trace_on())
+        fprintf(stderr, "[spm_hip] jst sam: %u reads -> %llu lines (%llu reported, %llu of them rescues, %llu secondary, %llu unmapped), "
+                        "%llu bytes: device %.3f ms (lines %.3f, measure %.3f, write %.3f, stats %.3f), %.3f ms in all\n", n_reads,
+                (unsigned long long)R->stats.n_lines, (unsigned long long)R->stats.n_reported, (unsigned long long)R->stats.n_rescue_lines,
+                (unsigned long long)R->stats.n_secondary, (unsigned long long)R->stats.n_unmapped, (unsigned long long)R->stats.n_bytes,
+                R->stats.ms_total, R->stats.ms_lines, R->stats.ms_measure, R->stats.ms_write, R->stats.ms_stats, R->stats.ms_host);
+    *out = R.release();
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_sam_view(spm_sam *s, const char **text, uint64_t *n_bytes, const spm_sam_line **lines, uint64_t *n_lines)
+{
+    if (!s)
+        return SPM_E_INVALID;
+    if (!s->have_host && (s->n_bytes || s->n_lines)) {
+        spm_ctx *ctx = s->ctx;
+        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        s->host_text.resize(s->n_bytes);
+        s->host_lines.resize(s->n_lines);
+        if (s->n_bytes)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(s->host_text.data(), s->d_text, s->n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (s->n_lines)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(s->host_lines.data(), s->d_lines, s->n_lines * sizeof(spm_sam_line), hipMemcpyDeviceToHost,
+                                              ctx->stream));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    s->have_host = true;
+    if (text)
+        *text = s->host_text.data();
+    if (n_bytes)
+        *n_bytes = s->n_bytes;
+    if (lines)
+        *lines = s->host_lines.data();
+    if (n_lines)
+        *n_lines = s->n_lines;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_sam_device(spm_sam *s, const void **text, uint64_t *n_bytes, const void **lines, uint64_t *n_lines)
+{
+    if (!s)
+        return SPM_E_INVALID;
+    if (text)
+        *text = s->d_text;
+    if (n_bytes)
+        *n_bytes = s->n_bytes;
+    if (lines)
+        *lines = s->d_lines;
+    if (n_lines)
+        *n_lines = s->n_lines;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_sam_stats(const spm_sam *s, spm_sam_stats *out)
+{
+    if (!s || !out)
+        return SPM_E_INVALID;
+    *out = s->stats;
+    return SPM_OK;
+}

@@ -448,6 +448,7 @@ JST_READ_DTYPE = np.dtype([("first_locus", "<u4"), ("n_loci", "<u4"), ("n_forwar
 JST_PAIR_DTYPE = np.dtype([("locus1", "<u4"), ("locus2", "<u4"), ("tlen", "<i4"), ("best", "<i4"), ("n_pairs", "<u4"),
                            ("n_best", "<u4"), ("n_next", "<u4"), ("flag1", "<u2"), ("flag2", "<u2")])
 JST_RESCUE_DTYPE = np.dtype(capi.JST_RESCUE_DTYPE)
+SAM_LINE_DTYPE = np.dtype(capi.SAM_LINE_DTYPE)
 JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
                                 ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
                                 ("member_off", "<u4"), ("n_haplotypes", "<u4")])
@@ -793,6 +794,114 @@ class JstRefLoci(_RecordPool):
         p = C.c_void_p()
         self._call("pairs", reads._h, C.byref(opts), C.byref(p))
         return JstPairs(self.ctx, p)
+
+    def sam(self, reads: "JstReads", patterns: "PatternSet", rname: str, *, pairs: "JstPairs | None" = None,
+            rescues: "JstRescues | None" = None, names=None, symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False,
+            mapq_unique=None, mapq_multi=None) -> "Sam":
+        """SAM lines of these loci (spm_hip_jst_ref_loci_sam), written on the device: per read its reported line and, with
+        secondary, one line per other locus.  reads: this object's reads(); patterns: the needle set behind the loci; pairs
+        (and rescues): paired-end mode, reads 2p and 2p + 1 are mates.  names: one per read (paired: per pair), str or bytes;
+        None prints the index.  mapq_unique / mapq_multi: four values each; None (both): the default tables.  The result
+        stays valid after every input is closed."""
+        opts = sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi)
+        keep = None
+        if names is not None:
+            raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+            off = np.zeros(len(raw) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
+            blob = C.create_string_buffer(b"".join(raw), int(off[-1]) + 1)
+            keep = (blob, off)
+            opts.names, opts.name_off, opts.n_names = C.addressof(blob), off.ctypes.data, len(raw)
+        s = C.c_void_p()
+        self._call("sam", reads._h, pairs._h if pairs is not None else None, rescues._h if rescues is not None else None,
+                   patterns._h, C.byref(opts), C.byref(s))
+        del keep
+        return Sam(self.ctx, s, rname)
+
+
+def sam_opts(rname, symbols: str = "ACGT", *, cigar_m: bool = False, secondary: bool = False, mapq_unique=None,
+             mapq_multi=None) -> capi.SamOpts:
+    """spm_sam_opts without names.  mapq_unique, mapq_multi: both None for the default tables, else both given."""
+    if (mapq_unique is None) != (mapq_multi is None):
+        raise ValueError("mapq_unique and mapq_multi: give both tables or neither")
+    enc = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+    opts = capi.SamOpts(rname=enc(rname), symbols=enc(symbols), n_names=0, mapq_defaults=1 if mapq_unique is None else 0,
+                        flags=(capi.SAM_CIGAR_M if cigar_m else 0) | (capi.SAM_SECONDARY if secondary else 0), reserved=0)
+    if mapq_unique is not None:
+        opts.mapq_unique = (C.c_uint8 * 4)(*[int(x) for x in mapq_unique])
+        opts.mapq_multi = (C.c_uint8 * 4)(*[int(x) for x in mapq_multi])
+    return opts
+
+
+def sam_mapq(n_best: int, n_next: int, mapq_unique=None, mapq_multi=None) -> int:
+    """The MAPQ of (n_best, n_next) under the given tables (None: the defaults).  Needs no device."""
+    opts = sam_opts("x", mapq_unique=mapq_unique, mapq_multi=mapq_multi)
+    return int(capi.lib().spm_hip_sam_mapq(C.byref(opts), min(int(n_best), 0xFFFFFFFF), min(int(n_next), 0xFFFFFFFF)))
+
+
+def sam_header(rname, ref_len: int) -> bytes:
+    """The @HD and @SQ lines (spm_hip_sam_header).  Needs no device."""
+    rname = rname.encode() if isinstance(rname, str) else bytes(rname)
+    need = C.c_uint64()
+    rc = capi.lib().spm_hip_sam_header(rname, int(ref_len), None, 0, C.byref(need))
+    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
+        raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_header refused rname {rname!r}")
+    buf = C.create_string_buffer(need.value)
+    rc = capi.lib().spm_hip_sam_header(rname, int(ref_len), buf, need.value, C.byref(need))
+    if rc != 0:
+        raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_header")
+    return buf.raw[:need.value]
+
+
+class Sam:
+    """Result of JstRefLoci.sam(): the SAM text and one SAM_LINE_DTYPE record per line, in line order."""
+
+    def __init__(self, ctx, h, rname):
+        self.ctx, self._h, self.rname = ctx, h, rname
+
+    def _view(self):
+        t, rec = C.c_void_p(), C.POINTER(capi.SamLine)()
+        nb, nl = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_sam_view(self._h, C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl)), self.ctx._h)
+        return t, nb.value, rec, nl.value
+
+    def __len__(self):
+        return self.device()[3]
+
+    def text(self) -> bytes:
+        t, nb, _rec, _nl = self._view()
+        return C.string_at(t, nb) if nb else b""
+
+    def lines(self) -> np.ndarray:
+        _t, _nb, rec, nl = self._view()
+        return _as_array(rec, nl, capi.SamLine, SAM_LINE_DTYPE)
+
+    def device(self):
+        """(text, n_bytes, lines, n_lines): device pointers and counts"""
+        t, rec = C.c_void_p(), C.c_void_p()
+        nb, nl = C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_sam_device(self._h, C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl)), self.ctx._h)
+        return int(t.value or 0), int(nb.value), int(rec.value or 0), int(nl.value)
+
+    def stats(self) -> capi.SamStats:
+        s = capi.SamStats()
+        _check(capi.lib().spm_hip_sam_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def header(self, ref_len: int) -> bytes:
+        return sam_header(self.rname, ref_len)
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_sam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class JstReads:
