@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cctype>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -173,6 +174,30 @@ struct jst_sam_pairing
     std::uint32_t min_tlen{1}, max_tlen{1};
     bool rescue{false};
     std::uint32_t k{0};
+};
+
+// A BAM file of a mapping (journaled_sequence_tree::map_bam; spm_hip_jst_ref_loci_bam in spm_hip.h): the complete file (header
+// section, record blocks, EOF block), the uncompressed record stream, and one record per BAM record as for map_sam, whose
+// offset / len locate it in that stream
+struct jst_bam_options
+{
+    jst_sam_options sam;
+    std::uint64_t ref_len{0};           // 1 .. 2^31 - 1
+    std::uint32_t block_data{0};        // uncompressed bytes per BGZF block, 0: 65280
+};
+
+struct jst_bam
+{
+    std::string file, records;
+    std::vector<jst_sam_line> lines;
+    std::uint64_t header_file_bytes{0}; // where the first record block starts
+    bool operator==(jst_bam const &) const noexcept = default;
+    // the BGZF virtual file offset of record i
+    std::uint64_t virtual_offset(std::size_t i, std::uint32_t block_data = 0) const
+    {
+        std::uint64_t const D = block_data ? block_data : 65280u, u = lines[i].offset;
+        return (header_file_bytes + (u / D) * (D + 31)) << 16 | (u % D);
+    }
 };
 
 struct jst_search_stats
@@ -978,6 +1003,168 @@ public:
                         nullptr, needle_ranks, strands, options);
     }
 
+    // ---- the same mapping as a BAM file (the contract of spm_hip_jst_ref_loci_bam in spm_hip.h).  Device route: the chain plus
+    // that call.  Host route: map_sam_host's lines, each converted to a record from its TEXT FIELDS (bam_of_sam, a plain
+    // SAM-to-BAM converter that shares no code with the device's composition), framed by spm_hip_bgzf_frame_host.  Both return
+    // the same bytes.
+    jst_bam map_bam(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                    bool reports_begin, std::uint32_t strands, std::uint32_t n_reads, jst_sam_pairing const & pairing,
+                    jst_bam_options const & options, hip::hit_selection const & selection, std::size_t block = 0,
+                    jst_search_stats * stats = nullptr) const
+    {
+        if (device_ready())
+            return map_bam_device(needles, window, strands, n_reads, pairing, options, selection, block, stats);
+        return map_bam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options, selection, block, stats);
+    }
+
+    jst_bam map_bam_device(spm_patterns * needles, std::size_t window, std::uint32_t strands, std::uint32_t n_reads,
+                           jst_sam_pairing const & pairing, jst_bam_options const & options, hip::hit_selection const & selection,
+                           std::size_t block = 0, jst_search_stats * stats = nullptr) const
+    {
+        if (!device_ready())
+            hip::fatal("journaled_sequence_tree::map_bam_device (tree not representable on the device)", hip::default_context());
+        jst_bam out;
+        std::vector<jst_read> reads;
+        std::vector<jst_pair> pairs;
+        std::vector<jst_rescue> rescues;
+        std::vector<std::uint32_t> rescue_ops;
+        spm_jst_pair_opts const opts{pairing.min_tlen, pairing.max_tlen, 0, 0};
+        rescue_request const rescue{spm_jst_rescue_opts{pairing.min_tlen, pairing.max_tlen, pairing.k, 0, 0}, _device->reference.get(),
+                                    needles, &rescues, &rescue_ops};
+        sam_request const bam{&options.sam, needles, nullptr, &options, &out};
+        loci_of(device_alns(needles, window, selection, block, stats).get(), true, pairing.paired ? 2 : strands, n_reads, &reads,
+                pairing.paired ? &opts : nullptr, pairing.paired ? &pairs : nullptr,
+                pairing.paired && pairing.rescue ? &rescue : nullptr, &bam);
+        return out;
+    }
+
+    jst_bam map_bam_host(spm_patterns * needles, std::size_t window, std::vector<std::vector<std::uint8_t>> const & needle_ranks,
+                         bool reports_begin, std::uint32_t strands, std::uint32_t n_reads, jst_sam_pairing const & pairing,
+                         jst_bam_options const & options, hip::hit_selection const & selection, std::size_t block = 0,
+                         jst_search_stats * stats = nullptr) const
+    {
+        return bam_of_sam(map_sam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options.sam, selection,
+                                       block, stats),
+                          options);
+    }
+
+    // SAM lines to a BAM file, from the text alone and the SAM specification (section 4.2): every field parsed back out of its
+    // line.  Tags are written as the contract of spm_hip.h types them: NM XH XR int32, XN X0 X1 uint32.  QUAL is absent.
+    static jst_bam bam_of_sam(jst_sam const & sam, jst_bam_options const & o)
+    {
+        spm_ctx const * const ctx = nullptr; // (no device is needed: the host-only calls leave their message without a context)
+        auto const put = [](std::string & to, std::uint64_t v, int bytes) {
+            for (int i = 0; i < bytes; ++i)
+                to.push_back(static_cast<char>((v >> (8 * i)) & 0xFF));
+        };
+        auto const reg2bin = [](std::int64_t beg, std::int64_t end) -> std::uint32_t {
+            --end;
+            int const shifts[5] = {14, 17, 20, 23, 26};
+            std::uint32_t const firsts[5] = {4681, 585, 73, 9, 1};
+            for (int i = 0; i < 5; ++i)
+                if ((beg >> shifts[i]) == (end >> shifts[i]))
+                    return static_cast<std::uint32_t>(firsts[i] + (beg >> shifts[i]));
+            return 0;
+        };
+        std::string const seq_letters = "=ACMGRSVTWYHKDBN", cigar_ops = "MIDNSHP=X";
+        jst_bam out;
+        for (std::size_t i = 0; i < sam.lines.size(); ++i) {
+            std::string const line = sam.text.substr(sam.lines[i].offset, sam.lines[i].len - 1); // (without the \n)
+            std::vector<std::string> f;
+            for (std::size_t at = 0;;) {
+                std::size_t const tab = line.find('\t', at);
+                f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+                if (tab == std::string::npos)
+                    break;
+                at = tab + 1;
+            }
+            if (f.size() < 11)
+                hip::fatal("journaled_sequence_tree::map_bam (a SAM line of fewer than 11 fields)", ctx);
+            std::int64_t const pos = std::stoll(f[3]) - 1, pnext = std::stoll(f[7]) - 1;
+            std::string cigar;
+            std::uint64_t span = 0, n_items = 0;
+            if (f[5] != "*")
+                for (std::size_t at = 0; at < f[5].size();) {
+                    std::size_t used = 0;
+                    std::uint64_t const n = std::stoull(f[5].substr(at), &used);
+                    std::size_t const op = cigar_ops.find(f[5][at + used]);
+                    if (op == std::string::npos)
+                        hip::fatal("journaled_sequence_tree::map_bam (an unknown CIGAR operation)", ctx);
+                    put(cigar, n << 4 | op, 4);
+                    span += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? n : 0;
+                    ++n_items;
+                    at += used + 1;
+                }
+            std::string seq;
+            std::uint32_t const l_seq = f[9] == "*" ? 0u : static_cast<std::uint32_t>(f[9].size());
+            for (std::uint32_t j = 0; j < l_seq; j += 2) {
+                auto const code = [&](char c) {
+                    std::size_t const at = seq_letters.find(static_cast<char>(std::toupper(static_cast<unsigned char>(c))));
+                    return at == std::string::npos ? 15u : static_cast<unsigned>(at);
+                };
+                seq.push_back(static_cast<char>(code(f[9][j]) << 4 | (j + 1 < l_seq ? code(f[9][j + 1]) : 0u)));
+            }
+            std::string rec;
+            put(rec, f[2] == "*" ? 0xFFFFFFFFu : 0u, 4);
+            put(rec, static_cast<std::uint32_t>(pos), 4);
+            put(rec, f[0].size() + 1, 1);
+            put(rec, std::stoul(f[4]), 1);
+            put(rec, pos < 0 ? 4680u : reg2bin(pos, pos + static_cast<std::int64_t>(std::max<std::uint64_t>(span, 1))), 2);
+            put(rec, n_items, 2);
+            put(rec, std::stoul(f[1]), 2);
+            put(rec, l_seq, 4);
+            put(rec, f[6] == "*" ? 0xFFFFFFFFu : 0u, 4); // ("=" is the one reference)
+            put(rec, static_cast<std::uint32_t>(pnext), 4);
+            put(rec, static_cast<std::uint32_t>(std::stoll(f[8])), 4);
+            rec += f[0];
+            rec.push_back('\0');
+            rec += cigar;
+            rec += seq;
+            rec.append(l_seq, static_cast<char>(0xFF));
+            for (std::size_t t = 11; t < f.size(); ++t) {
+                std::string const tag = f[t].substr(0, 2);
+                bool const is_signed = tag == "NM" || tag == "XH" || tag == "XR";
+                rec += tag;
+                rec.push_back(is_signed ? 'i' : 'I');
+                put(rec, is_signed ? static_cast<std::uint32_t>(std::stoll(f[t].substr(5))) : static_cast<std::uint32_t>(std::stoull(f[t].substr(5))), 4);
+            }
+            out.lines.push_back({out.records.size(), static_cast<std::uint32_t>(rec.size() + 4), sam.lines[i].read, sam.lines[i].source,
+                                 sam.lines[i].flag, sam.lines[i].mapq, sam.lines[i].kind});
+            put(out.records, rec.size(), 4);
+            out.records += rec;
+        }
+        // the header: BAM\1, l_text, the SAM header, one reference; framed on its own, then the records and the EOF block
+        std::uint64_t n_text = 0;
+        if (spm_hip_sam_header(o.sam.rname.c_str(), o.ref_len, nullptr, 0, &n_text) != SPM_E_OVERFLOW || o.ref_len == 0 ||
+            o.ref_len > 0x7FFFFFFFull)
+            hip::fatal("journaled_sequence_tree::map_bam (rname or ref_len)", ctx);
+        std::string text(n_text, '\0'), plain = std::string("BAM\1", 4);
+        if (spm_hip_sam_header(o.sam.rname.c_str(), o.ref_len, text.data(), n_text, &n_text) != SPM_OK)
+            hip::fatal("spm_hip_sam_header", ctx);
+        put(plain, n_text, 4);
+        plain += text;
+        put(plain, 1, 4);
+        put(plain, o.sam.rname.size() + 1, 4);
+        plain += o.sam.rname;
+        plain.push_back('\0');
+        put(plain, o.ref_len, 4);
+        auto const frame = [&](std::string const & data, bool eof) {
+            spm_bgzf_opts const z{o.block_data, eof ? SPM_BGZF_EOF : 0u, 0};
+            std::uint64_t need = 0;
+            int rc = spm_hip_bgzf_frame_host(data.data(), data.size(), &z, nullptr, 0, &need);
+            std::string framed(need, '\0');
+            if (rc == SPM_E_OVERFLOW)
+                rc = spm_hip_bgzf_frame_host(data.data(), data.size(), &z, framed.data(), need, &need);
+            if (rc != SPM_OK)
+                hip::fatal("spm_hip_bgzf_frame_host", ctx);
+            return framed;
+        };
+        out.file = frame(plain, false);
+        out.header_file_bytes = out.file.size();
+        out.file += frame(out.records, true);
+        return out;
+    }
+
     // The rule of spm_hip.h as a plain formatter over the host structs: which line a read reports, MAPQ from the tables, the
     // mate fields, the secondary lines, every field with std::to_string.
     static jst_sam sam_host(jst_read_loci const & mapped, std::vector<jst_pair> const * pairs, std::vector<jst_rescue> const * rescues,
@@ -1536,6 +1723,8 @@ private:
         jst_sam_options const * options;
         spm_patterns const * needles;
         jst_sam * out;
+        jst_bam_options const * bam_options = nullptr; // map_bam: the BAM call instead, into bam_out
+        jst_bam * bam_out = nullptr;
     };
 
     // spm_hip_jst_ref_loci_sam over the handles loci_of holds (pr, rs: nullptr where there are none), and its host view
@@ -1561,6 +1750,28 @@ private:
         std::copy(o.mapq_multi.begin(), o.mapq_multi.end(), opts.mapq_multi);
         opts.mapq_defaults = o.default_tables ? 1 : 0;
         opts.flags = (o.cigar_m ? SPM_SAM_CIGAR_M : 0u) | (o.secondary ? SPM_SAM_SECONDARY : 0u);
+        if (req.bam_out != nullptr) {
+            spm_bam_opts const bopts{opts, req.bam_options->ref_len, req.bam_options->block_data, 0};
+            spm_bam * b = nullptr;
+            if (spm_hip_jst_ref_loci_bam(l, rd, pr, rs, req.needles, &bopts, &b) != SPM_OK)
+                hip::fatal("spm_hip_jst_ref_loci_bam", ctx);
+            std::unique_ptr<spm_bam, decltype(&spm_hip_bam_destroy)> owner{b, &spm_hip_bam_destroy};
+            void const * file = nullptr;
+            void const * records = nullptr;
+            spm_sam_line const * lines = nullptr;
+            std::uint64_t n_file = 0, n_records = 0, n_lines = 0;
+            spm_bam_stats st{};
+            if (spm_hip_bam_view(b, &file, &n_file, &records, &n_records, &lines, &n_lines) != SPM_OK || spm_hip_bam_stats(b, &st) != SPM_OK)
+                hip::fatal("spm_hip_bam_view", ctx);
+            req.bam_out->file.assign(static_cast<char const *>(file), n_file);
+            req.bam_out->records.assign(static_cast<char const *>(records), n_records);
+            req.bam_out->header_file_bytes = st.header_file_bytes;
+            req.bam_out->lines.clear();
+            for (std::uint64_t i = 0; i < n_lines; ++i)
+                req.bam_out->lines.push_back({lines[i].offset, lines[i].len, lines[i].read, lines[i].source, lines[i].flag,
+                                              lines[i].mapq, lines[i].kind});
+            return;
+        }
         spm_sam * s = nullptr;
         if (spm_hip_jst_ref_loci_sam(l, rd, pr, rs, req.needles, &opts, &s) != SPM_OK)
             hip::fatal("spm_hip_jst_ref_loci_sam", ctx);

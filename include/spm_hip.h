@@ -1039,6 +1039,144 @@ int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t 
  * mapq_defaults above 1 */
 int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint32_t n_next);
 
+/* ---- BGZF framing of a device buffer: what makes SAM text in HBM a .sam.gz that samtools and tabix read --------------------
+ * One call frames n bytes at device_src (any alignment, owned by no handle; read before the call returns) into BGZF blocks in
+ * a new device buffer.  Every block is one gzip member with one STORED deflate block -- the uncompressed BGZF that `samtools
+ * view -u` writes; nothing is compressed.  A block of d data bytes is d + 31 bytes:
+ *     1f 8b 08 04 | MTIME 00 00 00 00 | XFL 00 | OS ff | XLEN 06 00 | 42 43 02 00 | BSIZE = d + 30, u16       18 bytes
+ *     01 (BFINAL, BTYPE 00) | LEN = d, u16 | NLEN = ~d, u16                                                   5 bytes
+ *     the data                                                                                                d bytes
+ *     CRC32 of the data, u32 | ISIZE = d, u32                                                                 8 bytes
+ * all little-endian.  With D = block_data, blocks 0 .. nb - 2 hold D bytes and the last one the rest; there is no empty data
+ * block: n == 0 gives no block at all.  SPM_BGZF_EOF appends the 28 bytes of the end-of-file block,
+ *     1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00.
+ * The byte at uncompressed offset u lies at file offset (u / D) * (D + 31) + 23 + u % D, its BGZF virtual offset is
+ * ((u / D) * (D + 31)) << 16 | (u % D).  CRC32 is the standard one (reflected 0xEDB88320, initial value and final xor ~0;
+ * crc32("123456789") = 0xCBF43926).
+ * Worked case, the 6 bytes "abcdef", block_data 4, SPM_BGZF_EOF: 35 + 33 + 28 = 96 bytes,
+ *     1f8b08040000000000ff0600424302002200 01 0400 fbff 61626364 11cd82ed 04000000
+ *     1f8b08040000000000ff0600424302002000 01 0200 fdff 6566     704982fd 02000000   and the EOF block.
+ *
+ *   * SPM_E_INVALID with a message, decided on the host before any launch: NULL ctx, opts or out; NULL device_src with n > 0;
+ *     block_data above 65280; flag bits other than SPM_BGZF_EOF; a nonzero reserved.
+ *   * SPM_E_UNSUPPORTED, likewise: more than 2^31 - 2 blocks (the host-only calls: a framed size beyond 64 bits).
+ *   * n == 0: SPM_OK with the EOF block, or with nothing (the views are NULL, 0).
+ * The result is a pure function of the bytes and the opts: equal to spm_hip_bgzf_frame_host of the same bytes, host and device
+ * view equal.  It outlives the source. */
+#define SPM_BGZF_EOF 1u             /* append the end-of-file block */
+#define SPM_BGZF_BLOCK_DATA 65280u  /* the default and the most a block holds: htslib's 0xff00 */
+typedef struct spm_bgzf_opts {      /* 16 bytes */
+    uint32_t block_data;            /* uncompressed bytes per block, 1 .. 65280; 0: 65280 */
+    uint32_t flags;                 /* SPM_BGZF_* */
+    uint64_t reserved;              /* must be 0 */
+} spm_bgzf_opts;
+typedef struct spm_bgzf spm_bgzf;
+typedef struct spm_bgzf_stats {     /* 32 bytes */
+    float ms_frame;                 /* device: the frame stage (HIP events) */
+    float ms_host;                  /* wall clock of the whole call (the view is downloaded when first asked for) */
+    uint64_t n_in;
+    uint64_t n_out;                 /* = n_in + 31 * n_blocks (+ 28 with SPM_BGZF_EOF) */
+    uint64_t n_blocks;              /* data blocks; the EOF block is not counted */
+} spm_bgzf_stats;
+int spm_hip_bgzf_frame(spm_ctx *ctx, const void *device_src, uint64_t n, const spm_bgzf_opts *opts, spm_bgzf **out);
+/* every pointer may be NULL */
+int spm_hip_bgzf_view(spm_bgzf *z, const void **bytes, uint64_t *n);
+int spm_hip_bgzf_device(spm_bgzf *z, const void **bytes, uint64_t *n);
+int spm_hip_bgzf_stats(const spm_bgzf *z, spm_bgzf_stats *out);
+void spm_hip_bgzf_destroy(spm_bgzf *z);
+/* host only, no device needed.  The same container by a serial framer over the same geometry and CRC functions.  *len is what
+ * it needs; cap too small: SPM_E_OVERFLOW and nothing is written.  The opts are checked as above. */
+int spm_hip_bgzf_frame_host(const void *src, uint64_t n, const spm_bgzf_opts *opts, void *dst, uint64_t cap, uint64_t *len);
+int spm_hip_bgzf_framed_size(uint64_t n, const spm_bgzf_opts *opts, uint64_t *len);
+
+/* ---- BAM records in BGZF blocks: the same alignments as spm_hip_jst_ref_loci_sam, as the file its users store ---------------
+ * One call turns (loci, read summary, optionally pairs and rescues, needle set) into a complete BAM file in HBM: the header
+ * section (framed on the host into blocks of its own, so that records start at a block border, as htslib writes them), the
+ * record stream framed by the kernel of spm_hip_bgzf_frame, the EOF block.  Which records exist, in which order, with which
+ * FLAG, MAPQ, mate fields and counts is the rule of spm_hip_jst_ref_loci_sam, line for line: record i is line i, and
+ * `samtools view -h` of the file prints spm_hip_sam_header + that call's text, with XN X0 X1 typed as unsigned.
+ * The handle has three views, each on the host (downloaded when first asked for) and on the device: the file; the
+ * uncompressed record stream; one spm_sam_line per record whose offset / len locate the record (len = block_size + 4) in that
+ * stream.  The record at stream offset u has the BGZF virtual file offset
+ *     (header_file_bytes + (u / D) * (D + 31)) << 16 | (u % D)            D = block_data, 65280 by default
+ * which is what a .bai or .csi would be built from (none is written).
+ *
+ * A record is little-endian; block_size counts what follows it:
+ *     block_size i32 | refID i32 | pos i32 | l_read_name u8 | mapq u8 | bin u16 | n_cigar_op u16 | flag u16 | l_seq u32 |
+ *     next_refID i32 | next_pos i32 | tlen i32 | read_name NUL-terminated | cigar u32[n_cigar_op] | seq u8[(l_seq+1)/2] |
+ *     qual u8[l_seq] | tags
+ * refID: RNAME printed 0, "*" -1.  pos: POS - 1 (POS 0: -1).  next_refID: "=" 0, "*" -1.  next_pos: PNEXT - 1.  read_name: the
+ * QNAME bytes, l_read_name counts the NUL.  cigar: the transcript's words as they are (len << 4 | op with I 1, D 2, = 7, X 8 is
+ * BAM's encoding); with SPM_SAM_CIGAR_M every maximal run of = / X words is one word sum << 4 | 0 and n_cigar_op counts items; a
+ * line with CIGAR "*" has n_cigar_op 0.  seq: two symbols per byte, the first in the high nibble, the code of a letter its place
+ * in "=ACMGRSVTWYHKDBN" in either case, any other letter or a rank >= sigma 15; a secondary (SEQ "*") has l_seq 0; with odd l_seq
+ * the last low nibble is 0.  qual: l_seq bytes ff.  bin: the specification's reg2bin(pos, pos + max(span, 1)) with span the
+ * reference symbols of the transcript (= X D), 0 on an unmapped record -- a locus inside an insertion takes end = pos + 1; pos -1
+ * gives 4680.  tags, in the text's order, SEVEN BYTES EACH whatever the value, on purpose (a record's length does not depend on
+ * its values): NM XH XR are type i (int32), XN X0 X1 type I (uint32: the counts arrive clamped to 0xFFFFFFFF).  An unmapped record
+ * has none.
+ *
+ * Worked records (the worked SAM cases above; rname "chr", default tables, no names), in hex, fields separated by spaces:
+ *  1. Case 1 (read 7 reverse at [99,131), words 20= 1X 11=, MAPQ 40) with a SEQ of 32 A, without SPM_SAM_CIGAR_M, 133 bytes:
+ *       81000000 00000000 63000000 02 28 4912 0300 1000 20000000 ffffffff ffffffff 00000000 3700
+ *       47010000 18000000 b7000000  11 x 16  ff x 32  4e4d69 01000000  584869 00000000  584e49 02000000  583049 01000000
+ *       583149 01000000          and with SPM_SAM_CIGAR_M, 125 bytes:  79000000 ... 0100 1000 ... 3700  00020000  11 x 16 ...
+ *  2. The unmapped mate of case 4 (flag 133 beside a mate at POS 501) with the SEQ ACG, 43 bytes:
+ *       27000000 00000000 f4010000 02 00 4912 0000 8500 03000000 00000000 f4010000 00000000 3000  1240  ffffff
+ *  3. A secondary of pair 0's mate 2 at [7000,7004), words 4=, flag 401, mate at POS 1001, 1 haplotype, 63 bytes:
+ *       3b000000 00000000 581b0000 02 ff 4912 0100 9101 00000000 00000000 e8030000 00000000 3000  47000000
+ *       4e4d69 00000000  584869 00000000  584e49 01000000
+ *
+ *   * Everything spm_hip_jst_ref_loci_sam refuses, with the same codes; the sam member of the opts is that call's opts.
+ *   * SPM_E_INVALID: ref_len == 0; block_data above 65280; a nonzero reserved.  SPM_E_UNSUPPORTED: ref_len above 2^31 - 1; more
+ *     than 2^31 - 2 record blocks.
+ *     Where several refusals apply to one call, which of them is reported is not specified.
+ *   * Counted on the device like every other disagreement of the inputs, and failing the call with SPM_E_INVALID and nothing
+ *     written: a record of more than 65535 CIGAR items; an item of length 0, or a merged run above 2^28 - 1; a mapped record
+ *     that ends beyond ref_len.
+ *   * Zero reads: the header section and the EOF block, which is a valid empty BAM.
+ * A pure function of its inputs: byte-identical across runs, host and device views equal.  It outlives all inputs. */
+typedef struct spm_bam_opts {       /* 80 bytes */
+    spm_sam_opts sam;               /* as for spm_hip_jst_ref_loci_sam: the same flags, the same MAPQ tables */
+    uint64_t ref_len;               /* 1 .. 2^31 - 1: l_ref and the @SQ line's LN */
+    uint32_t block_data;            /* as in spm_bgzf_opts */
+    uint32_t reserved;              /* must be 0 */
+} spm_bam_opts;
+typedef struct spm_bam spm_bam;
+typedef struct spm_bam_stats {      /* 104 bytes */
+    float ms_total;                 /* device: the five stages below (HIP events) */
+    float ms_lines;                 /* shared with spm_hip_jst_ref_loci_sam */
+    float ms_measure;               /* the length and shape of every record, the offsets */
+    float ms_write;                 /* the record stream, one wave per record */
+    float ms_frame;                 /* the record stream into BGZF blocks behind the header section, the EOF block */
+    float ms_stats;                 /* offsets into the line records, the counts */
+    float ms_host;                  /* wall clock of the whole call (the views are downloaded when first asked for) */
+    uint32_t reserved;
+    uint64_t n_records;             /* = n_reported + n_secondary + n_unmapped */
+    uint64_t n_record_bytes;        /* the uncompressed record stream */
+    uint64_t n_file_bytes;          /* = header_file_bytes + n_record_bytes + 31 * n_record_blocks + 28 */
+    uint64_t header_file_bytes;     /* the framed header section: where the first record block starts */
+    uint64_t n_record_blocks;
+    uint64_t n_reported;            /* as in spm_sam_stats */
+    uint64_t n_secondary;
+    uint64_t n_unmapped;
+    uint64_t n_rescue_lines;
+} spm_bam_stats;
+int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs /* NULL: single-end */,
+                             spm_jst_rescues *rescues /* NULL; needs pairs */, const spm_patterns *patterns,
+                             const spm_bam_opts *opts, spm_bam **out);
+/* every pointer may be NULL */
+int spm_hip_bam_view(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
+                     const spm_sam_line **lines, uint64_t *n_lines);
+int spm_hip_bam_device(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
+                       const void **lines, uint64_t *n_lines);
+int spm_hip_bam_stats(const spm_bam *b, spm_bam_stats *out);
+void spm_hip_bam_destroy(spm_bam *b);
+/* host only, no device needed.  The FRAMED header section: "BAM\1", l_text, the bytes of spm_hip_sam_header, n_ref = 1, l_name,
+ * the name with its NUL, l_ref, in BGZF blocks of block_data (0: 65280) without an EOF block.  *len is what it needs; cap too
+ * small: SPM_E_OVERFLOW and nothing is written.  rname, ref_len and block_data are checked as above. */
+int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

@@ -292,6 +292,44 @@ SAM_CIGAR_M, SAM_SECONDARY = 1, 2
 SAM_UNMAPPED, SAM_LOCUS, SAM_RESCUE, SAM_SECONDARY_LINE = 0, 1, 2, 3
 
 
+class BamOpts(C.Structure):
+    _fields_ = [("sam", SamOpts), ("ref_len", C.c_uint64), ("block_data", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BamStats(C.Structure):
+    _fields_ = [
+        ("ms_total", C.c_float),
+        ("ms_lines", C.c_float),
+        ("ms_measure", C.c_float),
+        ("ms_write", C.c_float),
+        ("ms_frame", C.c_float),
+        ("ms_stats", C.c_float),
+        ("ms_host", C.c_float),
+        ("reserved", C.c_uint32),
+        ("n_records", C.c_uint64),
+        ("n_record_bytes", C.c_uint64),
+        ("n_file_bytes", C.c_uint64),
+        ("header_file_bytes", C.c_uint64),
+        ("n_record_blocks", C.c_uint64),
+        ("n_reported", C.c_uint64),
+        ("n_secondary", C.c_uint64),
+        ("n_unmapped", C.c_uint64),
+        ("n_rescue_lines", C.c_uint64),
+    ]
+
+
+class BgzfOpts(C.Structure):
+    _fields_ = [("block_data", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class BgzfStats(C.Structure):
+    _fields_ = [("ms_frame", C.c_float), ("ms_host", C.c_float), ("n_in", C.c_uint64), ("n_out", C.c_uint64),
+                ("n_blocks", C.c_uint64)]
+
+
+BGZF_EOF, BGZF_BLOCK_DATA = 1, 65280
+
+
 class SamStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -497,6 +535,21 @@ def lib():
         "spm_hip_sam_destroy": (None, [vp]),
         "spm_hip_sam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "spm_hip_sam_mapq": (C.c_int, [C.POINTER(SamOpts), C.c_uint32, C.c_uint32]),
+        "spm_hip_jst_ref_loci_bam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(BamOpts), C.POINTER(vp)]),
+        "spm_hip_bam_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.POINTER(SamLine)), C.POINTER(C.c_uint64)]),
+        "spm_hip_bam_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
+                                         C.POINTER(C.c_uint64)]),
+        "spm_hip_bam_stats": (C.c_int, [vp, C.POINTER(BamStats)]),
+        "spm_hip_bam_destroy": (None, [vp]),
+        "spm_hip_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_frame": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(vp)]),
+        "spm_hip_bgzf_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_stats": (C.c_int, [vp, C.POINTER(BgzfStats)]),
+        "spm_hip_bgzf_destroy": (None, [vp]),
+        "spm_hip_bgzf_frame_host": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfOpts), vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_framed_size": (C.c_int, [C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(C.c_uint64)]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -551,6 +604,10 @@ EXPORTS = [
     "spm_hip_jst_rescues_destroy",
     "spm_hip_jst_ref_loci_sam", "spm_hip_sam_view", "spm_hip_sam_device", "spm_hip_sam_stats", "spm_hip_sam_destroy",
     "spm_hip_sam_header", "spm_hip_sam_mapq",
+    "spm_hip_jst_ref_loci_bam", "spm_hip_bam_view", "spm_hip_bam_device", "spm_hip_bam_stats", "spm_hip_bam_destroy",
+    "spm_hip_bam_header",
+    "spm_hip_bgzf_frame", "spm_hip_bgzf_view", "spm_hip_bgzf_device", "spm_hip_bgzf_stats", "spm_hip_bgzf_destroy",
+    "spm_hip_bgzf_frame_host", "spm_hip_bgzf_framed_size",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

@@ -219,6 +219,11 @@ void spm_warm_filter_kernels();
 void spm_warm_hits_kernels();
 void spm_warm_jst_kernels();
 void spm_warm_align_kernels();
+void spm_warm_bgzf_kernels();
+
+// ---- the frame stage of BGZF (bgzf.hip) on the context's stream: n bytes at d_src into d_dst, which has room for
+// bgzf_framed_size(n, D, eof) bytes (bgzf_core.hpp) ----
+hipError_t bgzf_frame_enqueue(spm_ctx *ctx, const void *d_src, uint64_t n, uint32_t D, bool eof, void *d_dst);
 
 // deferred scans (SPM_SCAN_DEFER): read the counters back, and repeat the scan if it needs attention   (scan.hip)
 int spm_complete_deferred(spm_hits *h);

@@ -1,0 +1,413 @@
+// jst_bam.hpp -- BAM records in BGZF blocks (spm_hip_jst_ref_loci_bam; contract in spm_hip.h, scheme in DESIGN.md 4.12, the
+// composition in jst_bam_core.hpp).  gfx950.  Included by jst.hip behind jst_sam.hpp, whose front (the host's refusals, the lines
+// stage) and stats kernel it uses, and bgzf.hip, whose frame stage it enqueues.
+//   jst_bam_measure_kernel   one lane per record: resolved against its sources with the query length checked, its shape (item
+//                            count, bin; what a record cannot hold is counted as a disagreement), its length by the measuring
+//                            sink;
+//   jst_bam_write_kernel     one wave per record, four records per workgroup, into the uncompressed stream: the 36 fixed bytes
+//                            one per lane, name bytes strided, CIGAR one word per lane through wave_cigar_walk (the text sink's
+//                            scheme, the items' size counted in words), SEQ two ranks per lane and byte, QUAL a fill, a tag
+//                            seven lanes.  Byte stores: a record starts wherever the one before it ended.  No atomics.
+#pragma once
+
+#include "bgzf_core.hpp"
+#include "jst_bam_core.hpp"
+#include "jst_sam.hpp"
+
+namespace spm_hip
+{
+
+struct jst_bam_params
+{
+    jst_sam_params P;               // text, n_bytes: the record stream
+    const uint8_t *codes = nullptr; // [256] rank -> 4-bit code
+    uint32_t *shape = nullptr;      // [cap_lines] n_items | bin << 16
+    uint64_t ref_len = 0;
+};
+
+__global__ __launch_bounds__(256) void jst_bam_measure_kernel(const jst_bam_params B)
+{
+    const jst_sam_params &P = B.P;
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    const unsigned long long n_lines = P.counts[kSamCntLines]; // (the lines stage is complete: stream order)
+    bool bad = false;
+    uint64_t n = 0;
+    if (i < P.cap_lines) {
+        jst_bam_shape H;
+        if (i < n_lines) {
+            jst_sam_fields F;
+            bad = !jst_sam_resolve(P.S, P.lines[i], P.aux[i], F, true) || !jst_bam_shape_of(P.S, F, B.ref_len, H);
+            if (!bad) {
+                jst_bam_measure M;
+                jst_bam_compose(P.S, F, H, B.codes, 0, M);
+                n = M.n;
+                bad = n > 0x7FFFFFFFull; // (block_size is an int32)
+            }
+            n = bad ? 0 : n;
+        }
+        P.len[i] = (uint32_t)n;
+        B.shape[i] = H.n_items | H.bin << 16;
+    }
+    count_flagged(&P.counts[kSamCntBad], bad);
+    count_summed(&P.counts[kSamCntBytes], n);
+}
+
+// The wave sink: byte i of a field to lane i.  cur is wave-uniform.  No store lands outside [cur at construction, end): the
+// record's own bytes.
+struct jst_bam_wave_sink
+{
+    uint8_t *to;
+    uint64_t cur, end;
+    uint32_t lane;
+
+    __device__ __forceinline__ void store(uint64_t at, uint8_t c)
+    {
+        if (at < end)
+            to[at] = c;
+    }
+    __device__ __forceinline__ void fixed(const uint32_t *w)
+    {
+        if (lane < kBamFixed)
+            store(cur + lane, jst_bam_le_byte(w[lane >> 2], lane & 3));
+        cur += kBamFixed;
+    }
+    __device__ __forceinline__ void bytes(const char *p, uint64_t n)
+    {
+        for (uint64_t i = lane; i < n; i += kWave)
+            store(cur + i, (uint8_t)p[i]);
+        cur += n;
+    }
+    __device__ __forceinline__ void num(uint64_t v) // at most 20 digits
+    {
+        const uint32_t len = jst_sam_dec_len(v);
+        if (lane < len)
+            store(cur + lane, (uint8_t)jst_sam_dec_char(v, len, lane));
+        cur += len;
+    }
+    __device__ __forceinline__ void fill(uint8_t c, uint64_t n)
+    {
+        for (uint64_t i = lane; i < n; i += kWave)
+            store(cur + i, c);
+        cur += n;
+    }
+    __device__ __forceinline__ void cigar(const uint32_t *words, uint32_t n, bool merge)
+    {
+        const uint64_t begin = cur;
+        cur = begin + 4 * wave_cigar_walk(
+                              words, n, merge, lane, [](uint64_t, uint32_t) { return 1u; },
+                              [&](uint64_t at, uint64_t run, uint32_t word, uint32_t) {
+                                  const uint32_t item = jst_bam_item_word(run, word, merge);
+                                  for (uint32_t i = 0; i < 4; ++i)
+                                      store(begin + 4 * at + i, jst_bam_le_byte(item, i));
+                              });
+    }
+    __device__ __forceinline__ void seq(const uint8_t *ranks, uint32_t m, const uint8_t *codes)
+    {
+        const uint32_t n = jst_bam_seq_len(m);
+        for (uint32_t i = lane; i < n; i += kWave)
+            store(cur + i, jst_bam_seq_byte(ranks, m, codes, i));
+        cur += n;
+    }
+    __device__ __forceinline__ void tag(uint32_t head, uint32_t v)
+    {
+        if (lane < kBamTag)
+            store(cur + lane, jst_bam_tag_byte(head, v, lane));
+        cur += kBamTag;
+    }
+};
+
+__global__ __launch_bounds__(256) void jst_bam_write_kernel(const jst_bam_params B)
+{
+    const jst_sam_params &P = B.P;
+    const uint32_t wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const unsigned long long i = blockIdx.x * 4ull + wv;
+    if (i >= P.n_lines)
+        return; // (whole waves: i is uniform across the wave, and no workgroup barrier follows)
+    jst_sam_fields F;
+    if (!jst_sam_resolve(P.S, P.lines[i], P.aux[i], F, false))
+        return; // (the measure stage resolved this record and counted a failure: the host does not get here)
+    const uint32_t len = P.len[i], shape = B.shape[i];
+    if (len < 4)
+        return;
+    jst_bam_shape H;
+    H.n_items = shape & 0xFFFFu;
+    H.bin = shape >> 16;
+    const uint64_t begin = P.off64[i], end = begin + len;
+    jst_bam_wave_sink out{reinterpret_cast<uint8_t *>(P.text), begin, end < P.n_bytes ? end : P.n_bytes, lane};
+    jst_bam_compose(P.S, F, H, B.codes, len - 4, out);
+}
+
+} // namespace spm_hip
+
+struct spm_bam
+{
+    spm_ctx *ctx = nullptr;
+    uint8_t *d_file = nullptr, *d_records = nullptr;
+    spm_sam_line *d_lines = nullptr;
+    uint64_t n_file = 0, n_record_bytes = 0, n_lines = 0;
+    bool have_host = false; // the views are downloaded when first asked for
+    std::vector<uint8_t> host_file, host_records;
+    std::vector<spm_sam_line> host_lines;
+    spm_bam_stats stats{};
+};
+static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");
+
+extern "C" void spm_hip_bam_destroy(spm_bam *b)
+{
+    if (!b)
+        return;
+    if (b->ctx && (b->d_file || b->d_records || b->d_lines))
+        hipStreamSynchronize(b->ctx->stream);
+    hipFree(b->d_file);
+    hipFree(b->d_records);
+    hipFree(b->d_lines);
+    delete b;
+}
+
+// the plain header: BAM\1, l_text, the text of spm_hip_sam_header, n_ref = 1, l_name, the name with its NUL, l_ref
+static int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t ref_len, std::vector<uint8_t> &h)
+{
+    if (ref_len == 0) {
+        SPM_SET_ERR(ctx, "%s: ref_len is 0", who);
+        return SPM_E_INVALID;
+    }
+    if (ref_len > spm_hip::kBamMaxRefLen) {
+        SPM_SET_ERR(ctx, "%s: ref_len %llu is above 2^31 - 1, the longest reference a BAM record can name (not supported)", who,
+                    (unsigned long long)ref_len);
+        return SPM_E_UNSUPPORTED;
+    }
+    uint64_t n_text = 0;
+    int rc = spm_hip_sam_header(rname, ref_len, nullptr, 0, &n_text);
+    if (rc != SPM_E_OVERFLOW) {
+        if (ctx && rc == SPM_E_INVALID)
+            SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
+        return rc == SPM_OK ? SPM_E_INVALID : rc;
+    }
+    const uint32_t l_name = (uint32_t)strlen(rname) + 1;
+    h.assign(4 + 4 + n_text + 4 + 4 + l_name + 4, 0);
+    auto put32 = [&h](size_t at, uint32_t v) {
+        for (int i = 0; i < 4; ++i)
+            h[at + i] = (uint8_t)(v >> (8 * i));
+    };
+    memcpy(h.data(), "BAM\1", 4);
+    put32(4, (uint32_t)n_text);
+    SPM_TRY(spm_hip_sam_header(rname, ref_len, reinterpret_cast<char *>(h.data()) + 8, n_text, &n_text));
+    put32(8 + n_text, 1);
+    put32(12 + n_text, l_name);
+    memcpy(h.data() + 16 + n_text, rname, l_name - 1);
+    put32(16 + n_text + l_name, (uint32_t)ref_len);
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len)
+{
+    static const char *const who = "spm_hip_bam_header";
+    if (!rname || !len || (!buf && cap)) {
+        SPM_SET_ERR((spm_ctx *)nullptr, "%s: NULL %s", who, !rname ? "rname" : !len ? "len" : "buf with cap > 0");
+        return SPM_E_INVALID;
+    }
+    if (block_data > spm_hip::kBgzfBlockData) {
+        SPM_SET_ERR((spm_ctx *)nullptr, "%s: block_data %u above 65280", who, block_data);
+        return SPM_E_INVALID;
+    }
+    std::vector<uint8_t> plain;
+    SPM_TRY(bam_plain_header(who, nullptr, rname, ref_len, plain));
+    const spm_bgzf_opts o{block_data, 0, 0};
+    return spm_hip_bgzf_frame_host(plain.data(), plain.size(), &o, buf, cap, len);
+}
+
+extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                        const spm_patterns *ps, const spm_bam_opts *opts, spm_bam **out)
+{
+    using namespace spm_hip;
+    static const char *const who = "spm_hip_jst_ref_loci_bam";
+    if (!l || !out)
+        return SPM_E_INVALID;
+    *out = nullptr;
+    spm_ctx *ctx = l->ctx;
+    const auto t_call = clk::now();
+    if (!opts) {
+        SPM_SET_ERR(ctx, "%s: NULL opts", who);
+        return SPM_E_INVALID;
+    }
+    size_t rname_len = 0;
+    uint64_t n_named = 0;
+    SPM_TRY(sam_check_args(who, ctx, l, r, pr, rs, ps, &opts->sam, rname_len, n_named));
+    if (opts->block_data > kBgzfBlockData) {
+        SPM_SET_ERR(ctx, "%s: block_data %u above 65280", who, opts->block_data);
+        return SPM_E_INVALID;
+    }
+    if (opts->reserved) {
+        SPM_SET_ERR(ctx, "%s: reserved is %u (must be 0)", who, opts->reserved);
+        return SPM_E_INVALID;
+    }
+    std::vector<uint8_t> plain, header;
+    SPM_TRY(bam_plain_header(who, ctx, opts->sam.rname, opts->ref_len, plain));
+    const uint32_t D = bgzf_block_data(opts->block_data);
+    header.resize(bgzf_framed_size(plain.size(), D, false));
+    bgzf_frame_serial(plain.data(), plain.size(), D, false, header.data());
+    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<spm_bam, void (*)(spm_bam *)> R(new spm_bam, spm_hip_bam_destroy);
+    R->ctx = ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t n_reads = (uint32_t)r->n;
+    sam_front F;
+    jst_bam_params B;
+    uint8_t codes[256];
+    dev_scratch keep;
+    if (n_reads) {
+        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, &opts->sam, rname_len, n_named, F, &R->d_lines));
+        B.P = F.P;
+        jst_sam_params &P = B.P;
+        hip_events<8> &ev = F.ev;
+        // ---- measure (its time, ev[1] .. ev[2], takes in the two allocations and the 256-byte upload below) ----
+        jst_bam_rank_codes(opts->sam.symbols, ps->sigma, codes);
+        uint8_t *d_codes = nullptr;
+        SPM_HIP_CHECK(ctx, keep.alloc(&d_codes, 256));
+        SPM_HIP_CHECK(ctx, keep.alloc(&B.shape, (size_t)P.cap_lines * 4));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_codes, codes, 256, hipMemcpyHostToDevice, st));
+        B.codes = d_codes;
+        B.ref_len = opts->ref_len;
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_bam_measure_kernel, P.cap_lines, B));
+        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, F.d_tmp, F.tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+        const unsigned long long *c = ctx->h_counters;
+        if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
+            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
+                             "needle set or ref_len, or do not fit a BAM record; nothing was written", who, c[kSamCntBad]);
+            return SPM_E_INVALID;
+        }
+        P.n_lines = (uint32_t)c[kSamCntLines];
+        P.n_bytes = c[kSamCntBytes];
+    }
+    const uint64_t n_records = B.P.n_bytes;
+    if (bgzf_n_blocks(n_records, D) > kBgzfMaxBlocks) {
+        SPM_SET_ERR(ctx, "%s: %llu record bytes in blocks of %u are more than 2^31 - 2 blocks (not supported)", who,
+                    (unsigned long long)n_records, D);
+        return SPM_E_UNSUPPORTED;
+    }
+    R->n_lines = B.P.n_lines;
+    R->n_record_bytes = n_records;
+    R->n_file = header.size() + bgzf_framed_size(n_records, D, true);
+    SPM_HIP_CHECK(ctx, hipMalloc(&R->d_file, R->n_file));
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->d_file, header.data(), header.size(), hipMemcpyHostToDevice, st));
+    hip_events<2> ev_frame;
+    SPM_HIP_CHECK(ctx, ev_frame.create());
+    if (n_reads) {
+        jst_sam_params &P = B.P;
+        hip_events<8> &ev = F.ev;
+        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_records, std::max<uint64_t>(n_records, 1)));
+        P.text = reinterpret_cast<char *>(R->d_records);
+        // ---- write ----
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
+        hipLaunchKernelGGL(jst_bam_write_kernel, dim3((P.n_lines + 3) / 4), dim3(256), 0, st, B);
+        SPM_HIP_CHECK(ctx, hipGetLastError());
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
+    }
+    // ---- frame: the record stream behind the header section, then EOF ----
+    SPM_HIP_CHECK(ctx, hipEventRecord(ev_frame[0], st));
+    SPM_HIP_CHECK(ctx, bgzf_frame_enqueue(ctx, R->d_records, n_records, D, true, R->d_file + header.size()));
+    SPM_HIP_CHECK(ctx, hipEventRecord(ev_frame[1], st));
+    R->stats.header_file_bytes = header.size();
+    R->stats.n_record_blocks = bgzf_n_blocks(n_records, D);
+    R->stats.n_file_bytes = R->n_file;
+    R->stats.n_record_bytes = n_records;
+    if (n_reads) {
+        jst_sam_params &P = B.P;
+        hip_events<8> &ev = F.ev;
+        // ---- stats ----
+        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_stats_kernel, P.n_lines, P));
+        SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
+        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+        const unsigned long long *c = ctx->h_counters;
+        R->stats.n_records = P.n_lines;
+        R->stats.n_reported = c[kSamCntReported];
+        R->stats.n_secondary = c[kSamCntSecondary];
+        R->stats.n_unmapped = c[kSamCntUnmapped];
+        R->stats.n_rescue_lines = c[kSamCntRescue];
+        hipEventElapsedTime(&R->stats.ms_lines, ev[0], ev[1]);
+        hipEventElapsedTime(&R->stats.ms_measure, ev[1], ev[2]);
+        hipEventElapsedTime(&R->stats.ms_write, ev[3], ev[4]);
+        hipEventElapsedTime(&R->stats.ms_stats, ev_frame[1], ev[5]);
+    } else {
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st)); // (header and EOF are in place; `header` goes out of scope)
+    }
+    hipEventElapsedTime(&R->stats.ms_frame, ev_frame[0], ev_frame[1]);
+    R->stats.ms_total = R->stats.ms_lines + R->stats.ms_measure + R->stats.ms_write + R->stats.ms_frame + R->stats.ms_stats;
+    R->stats.ms_host = ms_since(t_call);
+    if (spm_trace_on())
+        fprintf(stderr, "[spm_hip] jst bam: %u reads -> %llu records (%llu reported, %llu of them rescues, %llu secondary, %llu unmapped), "
+                        "%llu bytes in %llu blocks, file %llu bytes: device %.3f ms (lines %.3f, measure %.3f, write %.3f, frame %.3f, "
+                        "stats %.3f), %.3f ms in all\n", n_reads, (unsigned long long)R->stats.n_records,
+                (unsigned long long)R->stats.n_reported, (unsigned long long)R->stats.n_rescue_lines, (unsigned long long)R->stats.n_secondary,
+                (unsigned long long)R->stats.n_unmapped, (unsigned long long)n_records, (unsigned long long)R->stats.n_record_blocks,
+                (unsigned long long)R->n_file, R->stats.ms_total, R->stats.ms_lines, R->stats.ms_measure, R->stats.ms_write,
+                R->stats.ms_frame, R->stats.ms_stats, R->stats.ms_host);
+    *out = R.release();
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_bam_view(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
+                                const spm_sam_line **lines, uint64_t *n_lines)
+{
+    if (!b)
+        return SPM_E_INVALID;
+    if (!b->have_host) {
+        spm_ctx *ctx = b->ctx;
+        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        b->host_file.resize(b->n_file);
+        b->host_records.resize(b->n_record_bytes);
+        b->host_lines.resize(b->n_lines);
+        if (b->n_file)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_file.data(), b->d_file, b->n_file, hipMemcpyDeviceToHost, ctx->stream));
+        if (b->n_record_bytes)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_records.data(), b->d_records, b->n_record_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (b->n_lines)
+            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_lines.data(), b->d_lines, b->n_lines * sizeof(spm_sam_line), hipMemcpyDeviceToHost,
+                                              ctx->stream));
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    b->have_host = true;
+    if (file)
+        *file = b->host_file.data();
+    if (n_file)
+        *n_file = b->n_file;
+    if (records)
+        *records = b->host_records.data();
+    if (n_record_bytes)
+        *n_record_bytes = b->n_record_bytes;
+    if (lines)
+        *lines = b->host_lines.data();
+    if (n_lines)
+        *n_lines = b->n_lines;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_bam_device(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
+                                  const void **lines, uint64_t *n_lines)
+{
+    if (!b)
+        return SPM_E_INVALID;
+    if (file)
+        *file = b->d_file;
+    if (n_file)
+        *n_file = b->n_file;
+    if (records)
+        *records = b->d_records;
+    if (n_record_bytes)
+        *n_record_bytes = b->n_record_bytes;
+    if (lines)
+        *lines = b->d_lines;
+    if (n_lines)
+        *n_lines = b->n_lines;
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_bam_stats(const spm_bam *b, spm_bam_stats *out)
+{
+    if (!b || !out)
+        return SPM_E_INVALID;
+    *out = b->stats;
+    return SPM_OK;
+}

@@ -143,6 +143,50 @@ __global__ __launch_bounds__(256) void jst_sam_measure_kernel(const jst_sam_para
     count_summed(&P.counts[kSamCntBytes], n);
 }
 
+// The items of a transcript across a wave, for the sinks that write them (the text's <len><op>, a BAM record's words).  Lane w
+// of a pass takes word w.  A word that ends an item -- every word, or with `merge` the last word of a maximal run of = / X
+// words -- holds the item's length (a segmented sum over the wave, plus what the pass before left open), asks len_of(run, word)
+// for the item's size in the sink's units and gets put(at, run, word, size) with `at` the wave prefix sum of the sizes in
+// front of it.  -> the size of all items.  words, n, merge and the return value are wave-uniform.
+template <class LenOf, class Put>
+__device__ __forceinline__ uint64_t wave_cigar_walk(const uint32_t *words, uint32_t n, bool merge, uint32_t lane, LenOf len_of, Put put)
+{
+    uint64_t carry = 0, done = 0; // the length of the M run the passes so far left open; the size of the items so far
+    bool open = false;
+    for (uint32_t base = 0; base < n; base += kWave) {
+        const uint32_t w = base + lane;
+        const bool live = w < n;
+        const uint32_t word = live ? words[w] : 0u;
+        const bool has_next = live && w + 1 < n;
+        const uint32_t next = has_next ? words[w + 1] : 0u;
+        const bool is_m = live && merge && jst_sam_op_is_m(word);
+        const bool next_m = has_next && merge && jst_sam_op_is_m(next);
+        const int left_m = __shfl_up(is_m ? 1 : 0, 1);
+        const bool prev_m = lane == 0 ? open : left_m != 0;
+        const bool start = !(is_m && prev_m);
+        const uint32_t id = (uint32_t)__popcll(__ballot(start) & (~0ull >> (63 - lane)));
+        run_sum<uint64_t> v{live ? (uint64_t)(word >> 4) : 0ull};
+        if (lane == 0 && !start)
+            v.v += carry;
+        wave_run_scan(id, v);
+        const bool last = live && !(is_m && next_m);
+        const uint32_t len = last ? len_of(v.v, word) : 0u;
+        uint32_t incl = len;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_up(incl, o);
+            if ((int)lane >= o)
+                incl += up;
+        }
+        const uint32_t total = __shfl(incl, 63);
+        if (last)
+            put(done + (incl - len), v.v, word, len);
+        open = __shfl((live && !last) ? 1 : 0, 63) != 0;
+        carry = __shfl(v.v, 63);
+        done += total;
+    }
+    return done;
+}
+
 // The wave sink: the composition of one line, byte i of a field to lane i.  cur is wave-uniform.  No store lands outside
 // [cur at construction, end): the line's own bytes.
 struct jst_sam_wave_sink
@@ -186,46 +230,16 @@ struct jst_sam_wave_sink
             store(cur + i, jst_sam_seq_char(ranks[i], symbols, sigma));
         cur += m;
     }
-    // lane w of a pass takes word w.  A word that ends a printed item -- every word, or with `merge` the last word of a
-    // maximal run of = / X words -- holds the item's length (a segmented sum over the wave, plus what the pass before left
-    // open) and writes <len><op> at the wave prefix sum of the items' text lengths.
     __device__ __forceinline__ void cigar(const uint32_t *words, uint32_t n, bool merge)
     {
-        uint64_t carry = 0; // the length of the M run the passes so far left open
-        bool open = false;
-        for (uint32_t base = 0; base < n; base += kWave) {
-            const uint32_t w = base + lane;
-            const bool live = w < n;
-            const uint32_t word = live ? words[w] : 0u;
-            const bool has_next = live && w + 1 < n;
-            const uint32_t next = has_next ? words[w + 1] : 0u;
-            const bool is_m = live && merge && jst_sam_op_is_m(word);
-            const bool next_m = has_next && merge && jst_sam_op_is_m(next);
-            const int left_m = __shfl_up(is_m ? 1 : 0, 1);
-            const bool prev_m = lane == 0 ? open : left_m != 0;
-            const bool start = !(is_m && prev_m);
-            const uint32_t id = (uint32_t)__popcll(__ballot(start) & (~0ull >> (63 - lane)));
-            run_sum<uint64_t> v{live ? (uint64_t)(word >> 4) : 0ull};
-            if (lane == 0 && !start)
-                v.v += carry;
-            wave_run_scan(id, v);
-            const bool last = live && !(is_m && next_m);
-            const char op = jst_sam_op_char(word & 15u, merge);
-            const uint32_t len = last ? jst_sam_word_len(v.v) : 0u;
-            uint32_t incl = len;
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t up = __shfl_up(incl, o);
-                if ((int)lane >= o)
-                    incl += up;
-            }
-            const uint32_t total = __shfl(incl, 63);
-            const uint64_t at = cur + (incl - len);
-            for (uint32_t i = 0; i < len; ++i)
-                store(at + i, jst_sam_word_char(v.v, op, len, i));
-            open = __shfl((live && !last) ? 1 : 0, 63) != 0;
-            carry = __shfl(v.v, 63);
-            cur += total;
-        }
+        const uint64_t begin = cur;
+        cur = begin + wave_cigar_walk(
+                          words, n, merge, lane, [](uint64_t run, uint32_t) { return jst_sam_word_len(run); },
+                          [&](uint64_t at, uint64_t run, uint32_t word, uint32_t len) {
+                              const char op = jst_sam_op_char(word & 15u, merge);
+                              for (uint32_t i = 0; i < len; ++i)
+                                  store(begin + at + i, jst_sam_word_char(run, op, len, i));
+                          });
     }
 };
 
@@ -319,16 +333,22 @@ extern "C" int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf
     return SPM_OK;
 }
 
-extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
-                                        const spm_patterns *ps, const spm_sam_opts *opts, spm_sam **out)
+// ---- the front that spm_hip_jst_ref_loci_sam and spm_hip_jst_ref_loci_bam share: what is refused on the host, and the lines
+// stage with everything it needs on the device ----
+struct sam_front
+{
+    spm_hip::jst_sam_params P{};
+    dev_scratch keep;          // the strings of the opts on the device
+    std::vector<uint8_t> img;  // ... and on the host, until the copy has been waited for
+    spm_hip::hip_events<8> ev; // [0], [1]: around the lines stage; the rest are the caller's
+    uint8_t *d_tmp = nullptr;  // the scans' temporary storage, in the context's scratch behind the arrays of P
+    size_t tmp64 = 0;
+};
+
+static int sam_check_args(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                          const spm_patterns *ps, const spm_sam_opts *opts, size_t &rname_len, uint64_t &n_named)
 {
     using namespace spm_hip;
-    static const char *const who = "spm_hip_jst_ref_loci_sam";
-    if (!l || !out)
-        return SPM_E_INVALID;
-    *out = nullptr;
-    spm_ctx *ctx = l->ctx;
-    const auto t_call = clk::now();
     if (!r || !ps || !opts || !opts->rname || !opts->symbols) {
         SPM_SET_ERR(ctx, "%s: NULL %s", who, !r ? "reads handle" : !ps ? "patterns" : !opts ? "opts" : !opts->rname ? "rname" : "symbols");
         return SPM_E_INVALID;
@@ -369,12 +389,12 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         SPM_SET_ERR(ctx, "%s: symbols has %zu characters, the needle set sigma %u", who, strlen(opts->symbols), ps->sigma);
         return SPM_E_INVALID;
     }
-    const size_t rname_len = strlen(opts->rname);
+    rname_len = strlen(opts->rname);
     if (!jst_sam_name_ok(opts->rname, rname_len)) {
         SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
         return SPM_E_INVALID;
     }
-    const uint64_t n_named = pr ? pr->n : r->n;
+    n_named = pr ? pr->n : r->n;
     if (!opts->names != !opts->name_off || (!opts->names && opts->n_names) || (opts->names && opts->n_names != n_named)) {
         SPM_SET_ERR(ctx, "%s: %llu names (names %s, name_off %s) for %llu %s", who, (unsigned long long)opts->n_names,
                     opts->names ? "given" : "NULL", opts->name_off ? "given" : "NULL", (unsigned long long)n_named, pr ? "pairs" : "reads");
@@ -402,91 +422,127 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         SPM_SET_ERR(ctx, "%s: %llu reads and %llu loci: more than 2^32 - 1 lines", who, (unsigned long long)r->n, (unsigned long long)l->n);
         return SPM_E_UNSUPPORTED;
     }
+    return SPM_OK;
+}
+
+// n_reads > 0.  *d_lines: the line records, allocated here, the caller's to free
+static int sam_lines_stage(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                           const spm_patterns *ps, const spm_sam_opts *opts, size_t rname_len, uint64_t n_named, sam_front &F,
+                           spm_sam_line **d_lines)
+{
+    using namespace spm_hip;
+    (void)who;
+    const bool secondary = (opts->flags & SPM_SAM_SECONDARY) != 0;
+    const uint32_t n_reads = (uint32_t)r->n;
+    hipStream_t st = ctx->stream;
+    SPM_HIP_CHECK(ctx, F.ev.create());
+    SPM_TRY(spm_align_tables(ps)); // the needles' ranks on the device (built once per set)
+    jst_sam_params &P = F.P;
+    jst_sam_src &S = P.S;
+    S.loci = l->d_loci;
+    S.n_loci = l->d_loci ? (uint32_t)l->n : 0u;
+    S.ops = l->d_ops;
+    S.n_ops = l->d_ops ? l->n_ops : 0;
+    S.reads = r->d;
+    S.n_reads = n_reads;
+    S.strands = r->strands;
+    S.pairs = pr ? pr->d : nullptr;
+    S.n_pairs = pr ? (uint32_t)pr->n : 0u;
+    S.rescues = rs ? rs->d : nullptr;
+    S.n_rescues = rs && rs->d ? (uint32_t)rs->n : 0u;
+    S.rescue_ops = rs ? rs->d_ops : nullptr;
+    S.n_rescue_ops = rs && rs->d_ops ? rs->n_ops : 0;
+    S.ranks = ps->d_al_ranks;
+    S.offsets = ps->d_al_offsets;
+    S.m = ps->d_m;
+    S.n_needles = ps->n;
+    S.sigma = ps->sigma;
+    S.rname_len = (uint32_t)rname_len;
+    S.tables = jst_sam_tables_of(*opts);
+    S.flags = opts->flags;
+    P.cap_lines = n_reads + (secondary ? S.n_loci : 0u);
+    // ---- the strings of the opts, copied: rname, symbols, names, name_off in one allocation ----
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t names_bytes = opts->names ? (size_t)opts->name_off[n_named] : 0;
+    const size_t b_rname = al(rname_len + 1), b_sym = al(ps->sigma + 1), b_off = al(opts->names ? (n_named + 1) * 8 : 0);
+    std::vector<uint8_t> &img = F.img;
+    img.assign(b_rname + b_sym + b_off + al(names_bytes + 1), 0);
+    memcpy(img.data(), opts->rname, rname_len);
+    memcpy(img.data() + b_rname, opts->symbols, ps->sigma);
+    if (opts->names) {
+        memcpy(img.data() + b_rname + b_sym, opts->name_off, (n_named + 1) * 8);
+        memcpy(img.data() + b_rname + b_sym + b_off, opts->names, names_bytes);
+    }
+    dev_scratch &keep = F.keep;
+    char *d_img = nullptr;
+    SPM_HIP_CHECK(ctx, keep.alloc(&d_img, img.size()));
+    SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, st));
+    S.rname = d_img;
+    S.symbols = d_img + b_rname;
+    if (opts->names) {
+        S.name_off = reinterpret_cast<const uint64_t *>(d_img + b_rname + b_sym);
+        S.names = d_img + b_rname + b_sym + b_off;
+    }
+    // ---- scratch ----
+    size_t tmp32 = 0;
+    size_t &tmp64 = F.tmp64;
+    SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(sam_cnt_op{nullptr}), n_reads, &tmp32));
+    SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint64_t>(ctx, counted<uint64_t>(sam_len_op{nullptr}), P.cap_lines, &tmp64));
+    uint8_t *&d_tmp = F.d_tmp;
+    scratch_layout L;
+    L.take(P.first_rescue, S.n_pairs);
+    L.take(P.cnt, n_reads);
+    L.take(P.offs, n_reads);
+    L.take(P.aux, P.cap_lines);
+    L.take(P.len, P.cap_lines);
+    L.take(P.off64, P.cap_lines);
+    L.take(P.counts, kSamCnts);
+    L.take(d_tmp, std::max(tmp32, tmp64));
+    SPM_TRY(ensure_scratch(ctx, L.bytes()));
+    L.bind(ctx->d_scratch);
+    S.first_rescue = rs ? P.first_rescue : nullptr;
+    SPM_HIP_CHECK(ctx, hipMalloc(d_lines, (size_t)P.cap_lines * sizeof(spm_sam_line)));
+    P.lines = *d_lines;
+    // ---- lines ----
+    SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kSamCnts * 8, st));
+    SPM_HIP_CHECK(ctx, hipEventRecord(F.ev[0], st));
+    if (rs) {
+        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.first_rescue, 0xFF, (size_t)S.n_pairs * 4, st));
+        if (S.n_rescues)
+            SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_first_rescue_kernel, S.n_rescues, P));
+    }
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<false>, n_reads, P));
+    SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp32, counted<uint32_t>(sam_cnt_op{P.cnt}), P.offs, n_reads));
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<true>, n_reads, P));
+    SPM_HIP_CHECK(ctx, hipEventRecord(F.ev[1], st));
+    return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                        const spm_patterns *ps, const spm_sam_opts *opts, spm_sam **out)
+{
+    using namespace spm_hip;
+    static const char *const who = "spm_hip_jst_ref_loci_sam";
+    if (!l || !out)
+        return SPM_E_INVALID;
+    *out = nullptr;
+    spm_ctx *ctx = l->ctx;
+    const auto t_call = clk::now();
+    size_t rname_len = 0;
+    uint64_t n_named = 0;
+    SPM_TRY(sam_check_args(who, ctx, l, r, pr, rs, ps, opts, rname_len, n_named));
     SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<spm_sam, void (*)(spm_sam *)> R(new spm_sam, spm_hip_sam_destroy);
     R->ctx = ctx;
     const uint32_t n_reads = (uint32_t)r->n;
     if (n_reads) {
         hipStream_t st = ctx->stream;
-        hip_events<8> ev;
-        SPM_HIP_CHECK(ctx, ev.create());
-        SPM_TRY(spm_align_tables(ps)); // the needles' ranks on the device (built once per set)
-        jst_sam_params P{};
-        jst_sam_src &S = P.S;
-        S.loci = l->d_loci;
-        S.n_loci = l->d_loci ? (uint32_t)l->n : 0u;
-        S.ops = l->d_ops;
-        S.n_ops = l->d_ops ? l->n_ops : 0;
-        S.reads = r->d;
-        S.n_reads = n_reads;
-        S.strands = r->strands;
-        S.pairs = pr ? pr->d : nullptr;
-        S.n_pairs = pr ? (uint32_t)pr->n : 0u;
-        S.rescues = rs ? rs->d : nullptr;
-        S.n_rescues = rs && rs->d ? (uint32_t)rs->n : 0u;
-        S.rescue_ops = rs ? rs->d_ops : nullptr;
-        S.n_rescue_ops = rs && rs->d_ops ? rs->n_ops : 0;
-        S.ranks = ps->d_al_ranks;
-        S.offsets = ps->d_al_offsets;
-        S.m = ps->d_m;
-        S.n_needles = ps->n;
-        S.sigma = ps->sigma;
-        S.rname_len = (uint32_t)rname_len;
-        S.tables = jst_sam_tables_of(*opts);
-        S.flags = opts->flags;
-        P.cap_lines = n_reads + (secondary ? S.n_loci : 0u);
-        // ---- the strings of the opts, copied: rname, symbols, names, name_off in one allocation ----
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t names_bytes = opts->names ? (size_t)opts->name_off[n_named] : 0;
-        const size_t b_rname = al(rname_len + 1), b_sym = al(ps->sigma + 1), b_off = al(opts->names ? (n_named + 1) * 8 : 0);
-        std::vector<uint8_t> img(b_rname + b_sym + b_off + al(names_bytes + 1), 0);
-        memcpy(img.data(), opts->rname, rname_len);
-        memcpy(img.data() + b_rname, opts->symbols, ps->sigma);
-        if (opts->names) {
-            memcpy(img.data() + b_rname + b_sym, opts->name_off, (n_named + 1) * 8);
-            memcpy(img.data() + b_rname + b_sym + b_off, opts->names, names_bytes);
-        }
-        dev_scratch keep;
-        char *d_img = nullptr;
-        SPM_HIP_CHECK(ctx, keep.alloc(&d_img, img.size()));
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, st));
-        S.rname = d_img;
-        S.symbols = d_img + b_rname;
-        if (opts->names) {
-            S.name_off = reinterpret_cast<const uint64_t *>(d_img + b_rname + b_sym);
-            S.names = d_img + b_rname + b_sym + b_off;
-        }
-        // ---- scratch ----
-        size_t tmp32 = 0, tmp64 = 0;
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint32_t>(ctx, counted<uint32_t>(sam_cnt_op{nullptr}), n_reads, &tmp32));
-        SPM_HIP_CHECK(ctx, exclusive_sum_tmp_bytes<uint64_t>(ctx, counted<uint64_t>(sam_len_op{nullptr}), P.cap_lines, &tmp64));
-        uint8_t *d_tmp = nullptr;
-        scratch_layout L;
-        L.take(P.first_rescue, S.n_pairs);
-        L.take(P.cnt, n_reads);
-        L.take(P.offs, n_reads);
-        L.take(P.aux, P.cap_lines);
-        L.take(P.len, P.cap_lines);
-        L.take(P.off64, P.cap_lines);
-        L.take(P.counts, kSamCnts);
-        L.take(d_tmp, std::max(tmp32, tmp64));
-        SPM_TRY(ensure_scratch(ctx, L.bytes()));
-        L.bind(ctx->d_scratch);
-        S.first_rescue = rs ? P.first_rescue : nullptr;
-        SPM_HIP_CHECK(ctx, hipMalloc(&R->d_lines, (size_t)P.cap_lines * sizeof(spm_sam_line)));
-        P.lines = R->d_lines;
-        // ---- lines ----
-        SPM_HIP_CHECK(ctx, hipMemsetAsync(P.counts, 0, kSamCnts * 8, st));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        if (rs) {
-            SPM_HIP_CHECK(ctx, hipMemsetAsync(P.first_rescue, 0xFF, (size_t)S.n_pairs * 4, st));
-            if (S.n_rescues)
-                SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_first_rescue_kernel, S.n_rescues, P));
-        }
-        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<false>, n_reads, P));
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp32, counted<uint32_t>(sam_cnt_op{P.cnt}), P.offs, n_reads));
-        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_lines_kernel<true>, n_reads, P));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
+        sam_front F;
+        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, opts, rname_len, n_named, F, &R->d_lines));
+        jst_sam_params &P = F.P;
+        hip_events<8> &ev = F.ev;
+        uint8_t *d_tmp = F.d_tmp;
+        const size_t tmp64 = F.tmp64;
         // ---- measure ----
         SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_measure_kernel, P.cap_lines, P));
         SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));

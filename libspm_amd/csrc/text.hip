@@ -94,6 +94,7 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
     spm_warm_hits_kernels();
     spm_warm_jst_kernels();
     spm_warm_align_kernels();
+    spm_warm_bgzf_kernels();
     *out = ctx.release();
     return SPM_OK;
 }

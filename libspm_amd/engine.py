@@ -74,6 +74,16 @@ class Context:
                self._h)
         return Text(self, h, 4)
 
+    # ---- containers ----
+    def bgzf(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """BGZF framing (stored blocks, nothing compressed) of n bytes at device_ptr, any alignment, on the device
+        (spm_hip_bgzf_frame).  block_data: uncompressed bytes per block, 0 for 65280; eof: append the end-of-file block.  The
+        source is read before the call returns."""
+        opts = bgzf_opts(block_data, eof)
+        z = C.c_void_p()
+        _check(capi.lib().spm_hip_bgzf_frame(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
+        return Bgzf(self, z)
+
     # ---- needles ----
     def patterns(self, algo: int, needles, k=0, sigma: int = 4, both_strands: bool = False) -> "PatternSet":
         """needles: a sequence of rank arrays, or -- reads of one length -- a 2-D uint8 array, one needle per row (what the C ABI
@@ -804,19 +814,40 @@ class JstRefLoci(_RecordPool):
         None prints the index.  mapq_unique / mapq_multi: four values each; None (both): the default tables.  The result
         stays valid after every input is closed."""
         opts = sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi)
-        keep = None
-        if names is not None:
-            raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
-            off = np.zeros(len(raw) + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
-            blob = C.create_string_buffer(b"".join(raw), int(off[-1]) + 1)
-            keep = (blob, off)
-            opts.names, opts.name_off, opts.n_names = C.addressof(blob), off.ctypes.data, len(raw)
+        keep = _set_names(opts, names)
         s = C.c_void_p()
         self._call("sam", reads._h, pairs._h if pairs is not None else None, rescues._h if rescues is not None else None,
                    patterns._h, C.byref(opts), C.byref(s))
         del keep
         return Sam(self.ctx, s, rname)
+
+
+    def bam(self, reads: "JstReads", patterns: "PatternSet", rname: str, ref_len: int, *, pairs: "JstPairs | None" = None,
+            rescues: "JstRescues | None" = None, names=None, symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False,
+            mapq_unique=None, mapq_multi=None, block_data: int = 0) -> "Bam":
+        """The alignments of sam() as a complete BAM file in device memory (spm_hip_jst_ref_loci_bam): header, records in BGZF
+        blocks of block_data uncompressed bytes (0: 65280; stored, nothing is compressed), EOF block.  ref_len: the length of
+        the reference, 1 .. 2^31 - 1.  Every other argument as for sam().  The result stays valid after every input is closed."""
+        opts = capi.BamOpts(sam=sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique,
+                                         mapq_multi=mapq_multi), ref_len=int(ref_len), block_data=int(block_data), reserved=0)
+        keep = _set_names(opts.sam, names)
+        b = C.c_void_p()
+        self._call("bam", reads._h, pairs._h if pairs is not None else None, rescues._h if rescues is not None else None,
+                   patterns._h, C.byref(opts), C.byref(b))
+        del keep
+        return Bam(self.ctx, b, int(block_data) or capi.BGZF_BLOCK_DATA)
+
+
+def _set_names(opts: "capi.SamOpts", names):
+    """names (str or bytes, or None) into opts -> what has to stay alive across the call"""
+    if names is None:
+        return None
+    raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+    off = np.zeros(len(raw) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
+    blob = C.create_string_buffer(b"".join(raw), int(off[-1]) + 1)
+    opts.names, opts.name_off, opts.n_names = C.addressof(blob), off.ctypes.data, len(raw)
+    return blob, off
 
 
 def sam_opts(rname, symbols: str = "ACGT", *, cigar_m: bool = False, secondary: bool = False, mapq_unique=None,
@@ -891,10 +922,148 @@ class Sam:
     def header(self, ref_len: int) -> bytes:
         return sam_header(self.rname, ref_len)
 
+    def bgzf(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """The text, framed where it lies in device memory (Context.bgzf).  With ref_len the header is framed on the host, as
+        blocks of its own in front: bytes() is a .sam.gz."""
+        text, n_bytes, _lines, _n = self.device()
+        z = self.ctx.bgzf(text, n_bytes, block_data=block_data, eof=eof)
+        if ref_len is not None:
+            z.prefix = bgzf_frame_host(self.header(ref_len), block_data, eof=False)
+        return z
+
     def close(self):
         if self._h:
             if self.ctx._h:
                 capi.lib().spm_hip_sam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_header(rname, ref_len: int, block_data: int = 0) -> bytes:
+    """The framed header section of a BAM file (spm_hip_bam_header).  Needs no device."""
+    rname = rname.encode() if isinstance(rname, str) else bytes(rname)
+    need = C.c_uint64()
+    rc = capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), None, 0, C.byref(need))
+    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
+        _check(rc if rc else -1, None)
+    buf = C.create_string_buffer(need.value)
+    _check(capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), buf, need.value, C.byref(need)), None)
+    return buf.raw[:need.value]
+
+
+class Bam:
+    """Result of JstRefLoci.bam(): the file, the uncompressed record stream and one SAM_LINE_DTYPE record per BAM record
+    (offset / len: the record in the stream), in record order."""
+
+    def __init__(self, ctx, h, block_data):
+        self.ctx, self._h, self.block_data = ctx, h, block_data
+
+    def _view(self):
+        f, r, rec = C.c_void_p(), C.c_void_p(), C.POINTER(capi.SamLine)()
+        nf, nr, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_bam_view(self._h, C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl)),
+               self.ctx._h)
+        return f, nf.value, r, nr.value, rec, nl.value
+
+    def __len__(self):
+        return self.device()[5]
+
+    def bytes(self) -> bytes:
+        f, nf, _r, _nr, _rec, _nl = self._view()
+        return C.string_at(f, nf) if nf else b""
+
+    def records(self) -> bytes:
+        _f, _nf, r, nr, _rec, _nl = self._view()
+        return C.string_at(r, nr) if nr else b""
+
+    def lines(self) -> np.ndarray:
+        _f, _nf, _r, _nr, rec, nl = self._view()
+        return _as_array(rec, nl, capi.SamLine, SAM_LINE_DTYPE)
+
+    def voffsets(self) -> np.ndarray:
+        """the BGZF virtual file offset of every record"""
+        u = self.lines()["offset"].astype(np.uint64)
+        D = np.uint64(self.block_data)
+        return ((np.uint64(self.stats().header_file_bytes) + (u // D) * (D + np.uint64(31))) << np.uint64(16)) | (u % D)
+
+    def device(self):
+        """(file, n_file, records, n_record_bytes, lines, n_lines): device pointers and counts"""
+        f, r, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nf, nr, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(capi.lib().spm_hip_bam_device(self._h, C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl)),
+               self.ctx._h)
+        return int(f.value or 0), int(nf.value), int(r.value or 0), int(nr.value), int(rec.value or 0), int(nl.value)
+
+    def stats(self) -> capi.BamStats:
+        s = capi.BamStats()
+        _check(capi.lib().spm_hip_bam_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_bam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bgzf_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfOpts:
+    return capi.BgzfOpts(block_data=int(block_data), flags=capi.BGZF_EOF if eof else 0, reserved=0)
+
+
+def bgzf_frame_host(data, block_data: int = 0, eof: bool = True) -> bytes:
+    """The container of Context.bgzf by the serial host framer (spm_hip_bgzf_frame_host).  Needs no device."""
+    data = bytes(data)
+    opts = bgzf_opts(block_data, eof)
+    need = C.c_uint64()
+    src = C.create_string_buffer(data, len(data) + 1)
+    rc = capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), None, 0, C.byref(need))
+    if rc == 0 and need.value == 0:
+        return b""
+    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
+        _check(rc, None)
+    dst = C.create_string_buffer(need.value)
+    _check(capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), dst, need.value, C.byref(need)), None)
+    return dst.raw[:need.value]
+
+
+class Bgzf:
+    """Result of Context.bgzf() / Sam.bgzf(): BGZF blocks in device memory.  prefix: bytes framed on the host that belong in
+    front of them (Sam.bgzf with ref_len: the header's blocks); bytes() has them, device() is the device part alone."""
+
+    def __init__(self, ctx, h, prefix: bytes = b""):
+        self.ctx, self._h, self.prefix = ctx, h, prefix
+
+    def bytes(self) -> bytes:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(capi.lib().spm_hip_bgzf_view(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return self.prefix + (C.string_at(p, n.value) if n.value else b"")
+
+    def device(self):
+        """(bytes, n): device pointer and count"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(capi.lib().spm_hip_bgzf_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return int(p.value or 0), int(n.value)
+
+    def stats(self) -> capi.BgzfStats:
+        s = capi.BgzfStats()
+        _check(capi.lib().spm_hip_bgzf_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                capi.lib().spm_hip_bgzf_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
