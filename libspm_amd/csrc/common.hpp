@@ -62,7 +62,7 @@ struct spm_ctx
     ulonglong2 *d_band_tab = nullptr; // {key, value} per slot (filter.hpp: band_value)
     uint64_t band_slots = 0;
     bool band_dirty = false;
-    uint32_t *d_table_poison = nullptr; // device flag: the table holds slots a scan left behind (filter.hpp: resolve_params)
+    uint32_t *d_table_poison = nullptr; // device flag: the table holds slots a scan left behind (filter_params.hpp: resolve_params)
     // pinned staging of needle-set uploads: two halves, so the host fills one while the other travels (patterns.hip)
     uint8_t *h_stage = nullptr;
     size_t stage_half = 0;
@@ -178,7 +178,7 @@ inline void hits_adopt(spm_hits &h, spm_hits &from)
             return _rc;                                                                                                \
     } while (0)
 
-struct pass_entry // key directory of one pass of the seed filter, in L2 (filter.hpp: resolve_kernel)
+struct pass_entry // key directory of one pass of the seed filter, in L2 (filter_resolve.hpp: resolve_kernel)
 {
     const uint4 *ht; // {key, first entry, entries, -}, open addressing; an empty slot has .z == 0
     uint32_t ht_mask;

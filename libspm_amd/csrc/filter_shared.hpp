@@ -1,5 +1,5 @@
 // filter_shared.hpp -- what the host-side index build (index_build.hpp, compilable by plain g++) and the seed-filter
-// kernels (filter.hpp) must agree on: seed plan, key hashes, table layouts, entry codes.
+// kernels (filter.hpp and its filter_*.hpp stages) must agree on: seed plan, key hashes, table layouts, entry codes.
 #pragma once
 
 #include "hd.hpp"
@@ -17,7 +17,7 @@ constexpr double kMaxSurvivorShare = 0.08;
 
 // Seeds of one needle: n pieces of q symbols at offsets j*q.  k+1 pieces guarantee one intact piece per occurrence;
 // needles with many errors get k+2 (two intact pieces on nearby diagonals), which lets the verification stage count seed
-// hits per diagonal band and skip bands with a single one (candidate merging, filter.hpp).
+// hits per diagonal band and skip bands with a single one (candidate merging, filter_resolve.hpp).
 constexpr uint32_t kMergeMinK = 8;
 struct seed_plan
 {

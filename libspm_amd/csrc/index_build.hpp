@@ -1,5 +1,5 @@
 // index_build.hpp -- host side of the seed filter: which windows of which needles are indexed, and the tables the
-// kernels of filter.hpp read.  PURE HOST C++17 (no HIP): spm_hip.hip includes it for the product, index_host.cpp compiles
+// kernels of filter.hpp and its filter_*.hpp stages read.  PURE HOST C++17 (no HIP): spm_hip.hip includes it for the product, index_host.cpp compiles
 // it with plain g++ for the sanitizer build and the host self-check.
 //
 // This header is the planner -- build_filter_index, a sequence of named stages -- and the name everybody includes for the

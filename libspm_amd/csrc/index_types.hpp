@@ -211,7 +211,7 @@ struct index_kv // one indexed window on its way into the tables: the entry {val
     uint32_t key, val, sig, meta;
 };
 
-// key of the window seed[r, r + H) and the entry fields that go with it (filter.hpp: seed_sig_ok, kRngSingle)
+// key of the window seed[r, r + H) and the entry fields that go with it (filter_resolve.hpp: seed_sig_ok, kRngSingle)
 inline index_kv make_kv(const needle_view &nv, const seed_key &it, uint32_t H)
 {
     const uint32_t p = it.p, o = it.o, r = it.r, q = it.q;

@@ -1,6 +1,7 @@
 // internal.hpp -- what the translation units of libspm_hip.so share: the compiled needle set, the arguments of one scan, and
 // the entry points of the engines.  (patterns.hip: needle sets; text.hip: context + haystacks; scan.hip: the scan driver;
-// scan_brute.hip / scan_filter.hip: the engines, each with its kernels; hits.hip: results; jst.hip: journaled sequences;
+// scan_brute.hip / scan_filter.hip: the engines, the seed filter's kernels in filter_stream / filter_dense / filter_resolve /
+// filter_verify.hip (filter_launch.hpp); hits.hip: results; jst.hip: journaled sequences;
 // comm.hip: the multi-GPU exchange.)
 #pragma once
 

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void jst_bam_measure_kernel(const jst_bam_para
         B.shape[i] = H.n_items | H.bin << 16;
     }
     count_flagged(&P.counts[kSamCntBad], bad);
-    count_summed(&P.counts[kSamCntBytes], n);
+    wave_count_add(&P.counts[kSamCntBytes], (unsigned long long)n);
 }
 
 // The wave sink: byte i of a field to lane i.  cur is wave-uniform.  No store lands outside [cur at construction, end): the

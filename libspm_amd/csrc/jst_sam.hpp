@@ -55,15 +55,6 @@ struct jst_sam_params
     unsigned long long *counts = nullptr; // [kSamCnts]
 };
 
-// one atomicAdd per wave: the sum of v over its lanes
-__device__ __forceinline__ void count_summed(unsigned long long *counter, unsigned long long v)
-{
-    for (int d = 32; d; d >>= 1)
-        v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0 && v)
-        atomicAdd(counter, v);
-}
-
 __global__ __launch_bounds__(256) void jst_sam_first_rescue_kernel(const jst_sam_params P)
 {
     const unsigned long long j = blockIdx.x * 256ull + threadIdx.x;
@@ -115,7 +106,7 @@ template <bool kEmit> __global__ __launch_bounds__(256) void jst_sam_lines_kerne
     }
     if (!kEmit) {
         count_flagged(&P.counts[kSamCntBad], bad);
-        count_summed(&P.counts[kSamCntLines], n);
+        wave_count_add(&P.counts[kSamCntLines], (unsigned long long)n);
     }
 }
 
@@ -140,7 +131,7 @@ __global__ __launch_bounds__(256) void jst_sam_measure_kernel(const jst_sam_para
         P.len[i] = (uint32_t)n;
     }
     count_flagged(&P.counts[kSamCntBad], bad);
-    count_summed(&P.counts[kSamCntBytes], n);
+    wave_count_add(&P.counts[kSamCntBytes], (unsigned long long)n);
 }
 
 // The items of a transcript across a wave, for the sinks that write them (the text's <len><op>, a BAM record's words).  Lane w
@@ -171,7 +162,7 @@ __device__ __forceinline__ uint64_t wave_cigar_walk(const uint32_t *words, uint3
         wave_run_scan(id, v);
         const bool last = live && !(is_m && next_m);
         const uint32_t len = last ? len_of(v.v, word) : 0u;
-        uint32_t incl = len;
+        uint32_t incl = len; // (flat: through wave_prefix_incl the two write kernels are scheduled differently)
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t up = __shfl_up(incl, o);
             if ((int)lane >= o)

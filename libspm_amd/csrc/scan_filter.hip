@@ -1,149 +1,7 @@
-// scan_filter.hip -- the seed-filter engine (filter.hpp): buffer sizing and the launches of one scan.
+// scan_filter.hip -- the seed-filter engine (filter.hpp): buffer sizing and the launches of one scan.  The kernels live in
+// the units of filter_launch.hpp, one per stage.
 // MI355X only; no CPU scan path exists in this library: if HIP fails the call fails.
-#include "internal.hpp"
-#include "filter.hpp"
-
-namespace
-{
-// raise the kernel's dynamic LDS limit to what this launch asks for, then launch it
-template <typename K, typename... Args>
-void launch(K kernel, dim3 grid, uint32_t threads, size_t lds, hipStream_t s, Args... args)
-{
-    hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, args...);
-}
-
-using filter_kernel = void (*)(filter_params);
-using packed_kernel = void (*)(filter_params, const uint4 *);
-
-// The streaming kernel of each pass the index build (index_tables.hpp build_one_index, index_dense.hpp build_dense_index) can
-// produce; nullptr for any other combination.
-// Sparse passes on the 1-byte text, seed_filter_kernel<S, U, HV, SIG, KM>: U 1-KiB chunks per group (8 from stride 4 on,
-// 2 at strides 1 and 2); KM = keys shorter than 16 symbols, which only strides 1 and 2 carry.
-//   dna4, fingerprint table (HV 2): strides 4..16 (strides 1 and 2 use presence bits, unless anchored);
-//   dna4, Bloom cascade (HV 1): every stride -- SPM_HIP_FILTER_HASH=1, or a fingerprint table that could not be built;
-//   dna5 / dna15: fingerprint table only, every stride.
-template <int S, int U, bool KM>
-filter_kernel sparse_kernel(uint32_t hv, uint32_t sigma)
-{
-    if (hv == 2 && sigma == 5)
-        return seed_filter_kernel<S, U, 2, 5, KM>;
-    if (hv == 2 && sigma == 15)
-        return seed_filter_kernel<S, U, 2, 15, KM>;
-    if (hv == 1 && sigma == 4)
-        return seed_filter_kernel<S, U, 1, 4, KM>;
-    if constexpr (S >= 4)
-        if (hv == 2 && sigma == 4)
-            return seed_filter_kernel<S, U, 2, 4, KM>;
-    return nullptr;
-}
-
-filter_kernel select_filter_kernel(const filter_index &F, uint32_t sigma, bool km)
-{
-    if (F.dense) { // the dense pass: anchors = a union of n_pat dimer patterns
-        switch (F.n_pat) {
-        case 0:
-        case 1: return seed_filter_dense_kernel<4, 1>;
-        case 2: return seed_filter_dense_kernel<4, 2>;
-        case 3: return seed_filter_dense_kernel<4, 3>;
-        default: return nullptr;
-        }
-    }
-    if (F.hash_variant == 4) { // presence bits + L2 buckets as level 1 of a sparse dna4 pass
-        if (F.stride == 1)
-            return km ? seed_filter_dense_kernel<4, 1, 1, true> : seed_filter_dense_kernel<4, 1, 1, false>;
-        if (F.stride == 2)
-            return km ? seed_filter_dense_kernel<4, 1, 2, true> : seed_filter_dense_kernel<4, 1, 2, false>;
-        return nullptr;
-    }
-    switch (F.stride) {
-    case 16: return km ? nullptr : sparse_kernel<16, 8, false>(F.hash_variant, sigma);
-    case 8: return km ? nullptr : sparse_kernel<8, 8, false>(F.hash_variant, sigma);
-    case 4: return km ? nullptr : sparse_kernel<4, 8, false>(F.hash_variant, sigma);
-    case 2: return km ? sparse_kernel<2, 2, true>(F.hash_variant, sigma) : sparse_kernel<2, 2, false>(F.hash_variant, sigma);
-    case 1:
-        // anchored pass: few windows per lane are looked up, so a lane can hold more text
-        if (F.anchor_cm != 0 && F.hash_variant == 2 && sigma == 4 && !km)
-            return seed_filter_kernel<1, 4, 2, 4, false, true>;
-        return km ? sparse_kernel<1, 2, true>(F.hash_variant, sigma) : sparse_kernel<1, 2, false>(F.hash_variant, sigma);
-    default: return nullptr;
-    }
-}
-
-// sparse dna4 passes with the fingerprint table over the 2-bit shadow, seed_filter_packed_kernel<S, U2, 2, false>: strides
-// 4..16 (stride 1 has 16 windows per word, and 4 words already fill the 32-bit survivor mask twice over; stride 2 uses
-// presence bits)
-packed_kernel select_packed_kernel(uint32_t stride, bool km)
-{
-    if (km)
-        return nullptr;
-    switch (stride) {
-    case 16: return seed_filter_packed_kernel<16, 4, 2, false>;
-    case 8: return seed_filter_packed_kernel<8, 4, 2, false>;
-    case 4: return seed_filter_packed_kernel<4, 2, 2, false>;
-    default: return nullptr;
-    }
-}
-
-template <int NWN>
-void launch_verify_nw(const verify_params &V, dim3 grid, hipStream_t s)
-{
-    // LDS holds (sigma+1)*NWN words per thread; keep the block within ~128 KiB
-    uint32_t threads = 256;
-    const size_t per_thread = (size_t)(V.sigma + 1) * NWN * 4 + 2 * 16; // match masks + the hits of one 16-symbol block
-    while (threads > 64 && per_thread * threads > 128 * 1024)
-        threads >>= 1;
-    const size_t lds = per_thread * threads + (size_t)(threads / 64) * kHitStage * sizeof(spm_hit);
-    launch(verify_kernel<NWN>, grid, threads, lds, s, V);
-}
-
-template <int G>
-void launch_verify_wave_g(verify_params V, const uint32_t *peq_bot, uint32_t max_m, dim3 grid, hipStream_t s)
-{
-    // One wave per workgroup: a scan leaves a few thousand long bands, i.e. far fewer busy waves than the GPU has SIMDs,
-    // and each is a serial chain ~1500 steps long.  With four-wave workgroups filled in order, the dispatcher packed the
-    // busy waves four to a SIMD on a third of the CUs and left the rest idle.
-    grid.x *= 4;
-    const uint32_t n_slots = 2 * V.max_k + 1 + V.max_span;
-    // text window of one candidate: cold start |P| + k symbols before the first end position, then the end positions
-    V.wave_text = ((max_m + V.max_k + n_slots + 16 + 15) & ~15u) + 16;
-    const size_t per_group = ((n_slots * 2 + 15) & ~15u) + V.wave_text;
-    launch(verify_wave_kernel<G, 1>, grid, 64, (64 / G) * per_group, s, V, peq_bot);
-}
-
-// long needles: one 32-row block per lane, G = lanes per band >= blocks of the longest needle
-void launch_verify_wave(uint32_t n_blocks, const verify_params &V, const uint32_t *peq_bot, uint32_t max_m, dim3 grid,
-                        hipStream_t s)
-{
-    if (n_blocks <= 8)
-        launch_verify_wave_g<8>(V, peq_bot, max_m, grid, s);
-    else if (n_blocks <= 16)
-        launch_verify_wave_g<16>(V, peq_bot, max_m, grid, s);
-    else if (n_blocks <= 32)
-        launch_verify_wave_g<32>(V, peq_bot, max_m, grid, s);
-    else
-        launch_verify_wave_g<64>(V, peq_bot, max_m, grid, s);
-}
-
-// nwn = 32-bit words that can hold needle rows = ceil(max |P| / 32), rounded up to an instantiated width
-void launch_verify(uint32_t nwn, const verify_params &V, dim3 grid, hipStream_t s)
-{
-    switch (nwn) {
-    case 1: launch_verify_nw<1>(V, grid, s); break;
-    case 2: launch_verify_nw<2>(V, grid, s); break;
-    case 3: launch_verify_nw<3>(V, grid, s); break;
-    case 4: launch_verify_nw<4>(V, grid, s); break;
-    case 5: launch_verify_nw<5>(V, grid, s); break;
-    case 6: launch_verify_nw<6>(V, grid, s); break;
-    case 7: launch_verify_nw<7>(V, grid, s); break;
-    case 8: launch_verify_nw<8>(V, grid, s); break;
-    case 16: launch_verify_nw<16>(V, grid, s); break;
-    case 32: launch_verify_nw<32>(V, grid, s); break;
-    default: launch_verify_nw<64>(V, grid, s); break;
-    }
-}
-
-} // namespace
+#include "filter_launch.hpp"
 
 // persistent band table of the context: empty between scans (the verification gives every slot back), so a scan pays
 // for the bands it has, not for a memset of the table
@@ -172,8 +30,6 @@ int ensure_band_table(spm_ctx *ctx, uint64_t slots)
 
 namespace
 {
-static_assert(sizeof(survivor) == kSurvivorBytes && sizeof(band_rec) == kBandRecBytes, "scan_plan.hpp sizes the lists");
-
 struct filter_run // one run_filter: the request, its sizes, the scratch buffer laid out for them, and the launches in order
 {
     const scan_args &A;
@@ -239,79 +95,9 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
         P.ovf_spans = ovf;
         P.ovf_cap = kOvfCap;
         for (size_t fi = 0; fi < ps->fidx.size(); ++fi) {
-            const filter_index &F = ps->fidx[fi];
-            P.stride = F.stride;
-            P.key_len = F.key_len;
-            P.key_mask = F.key_len >= 16 ? 0xFFFFFFFFu : ((1u << (2 * F.key_len)) - 1);
-            P.bitmap_words = F.hash_variant == 2 ? 1024 : F.bitmap_words;
-            P.lds_words = F.lds_words;
-            P.chd_slot_mask = F.chd_slot_mask;
-            P.chd_bucket_shift = F.chd_bucket_shift;
-            P.chd_disp_off = F.chd_disp_off;
-            P.n_probes = F.n_probes;
-            P.bitmap = F.d_bitmap;
-            P.pass = (uint32_t)fi;
-            P.anchor_c = F.anchor_c;
-            P.anchor_cm = F.anchor_cm;
-            P.n_pat = F.n_pat;
-            for (uint32_t i = 0; i < kDensePatterns; ++i) {
-                P.pat_c[i] = F.pat_c[i];
-                P.pat_cm[i] = F.pat_cm[i];
-            }
-            P.bucket_shift = F.bucket_shift;
-            P.buckets = reinterpret_cast<const uint4 *>(F.d_buckets);
             if (fi > 0) // each pass draws its spans from a fresh head
                 SPM_HIP_CHECK(ctx, hipMemsetAsync(H->d_count + kCntSpanHead, 0, sizeof(unsigned long long), ctx->stream));
-            const bool km = F.key_len < 16; // (masked keys)
-            const bool bits = F.hash_variant == 4; // presence bits + L2 buckets as level 1 of a sparse pass: the dense kernel's machinery
-            const bool use_packed = F.hash_variant == 2 && A.text->d_packed && ps->sigma == 4 && F.stride >= 2 &&
-                                    !(A.opts.flags & SPM_SCAN_IGNORE_PACKED);
-            // measured best: 8 waves per CU on the 1-byte text when HBM binds, 16 on the 2-bit shadow and at stride 1 with
-            // 16-symbol keys (LDS-bound: C4 25.8 vs 29.1 ms; the other stride-1/2 variants need more than 128 VGPRs)
-            // stride 2: two chunks per group (16 windows per lane) need < 128 VGPRs, so 16 waves per CU hide the LDS round trips
-            // (C5: 0.53 -> 0.46 ms; four chunks per group hold 167 VGPRs at 8 waves)
-            const bool wide_ok = use_packed || F.stride == 2 || (F.stride == 1 && !km && ps->sigma == 4);
-            const uint32_t threads = (F.dense || bits || wide_ok) ? 1024 : 512;
-            // + the workgroup's span-dequeue slot (4 words) + one survivor-chunk record per wave (+ dense: one queue per wave)
-            const size_t lds = (size_t)F.lds_words * 4 + 16 + 16 * kCandRec * 4 + ((F.dense || bits) ? 16 * sizeof(dense_queue) : 0);
-            const uint32_t wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 2048 / threads));
-            const uint32_t grid = ctx->n_cu * wg_per_cu;
-            const uint64_t n_waves = (uint64_t)grid * (threads / 64);
-            const span_plan span = plan_span(stream_geometry_of(P.lo, P.hi, 1024).n_chunks, n_waves, 1024);
-            P.span_chunks = span.span_chunks;
-            P.span_unit = 1024;
-            // candidates a span may produce before it gives up and is re-scanned by the brute-force kernel: one per 4 symbols
-            // costs the verification about what the re-scan would
-            const int sb = A.tune.span_budget;
-            P.span_budget = sb > 0 ? (uint32_t)sb : (uint32_t)std::max<uint64_t>(256, (uint64_t)span.span_chunks * 1024 / 4);
-            P.dynamic = span.dynamic;
-            P.hash_variant = F.hash_variant;
-            H->stats.span_symbols = P.span_chunks * P.span_unit;
-            if (use_packed) {
-                // p-chunks of 4096 symbols: recompute the span geometry in those units
-                filter_params Q = P;
-                const span_plan pspan = plan_span(stream_geometry_of(Q.lo, Q.hi, 4096).n_chunks, n_waves, 4096);
-                Q.span_chunks = pspan.span_chunks;
-                Q.span_unit = 4096;
-                if (sb <= 0)
-                    Q.span_budget = (uint32_t)std::max<uint64_t>(256, (uint64_t)pspan.span_chunks * 4096 / 4);
-                Q.dynamic = pspan.dynamic;
-                H->stats.span_symbols = Q.span_chunks * Q.span_unit;
-                const packed_kernel k = select_packed_kernel(F.stride, km);
-                if (!k) {
-                    SPM_SET_ERR(ctx, "internal: no packed filter kernel for stride %u, key length %u", F.stride, F.key_len);
-                    return SPM_E_UNSUPPORTED;
-                }
-                launch(k, dim3(grid), threads, lds, ctx->stream, Q, reinterpret_cast<const uint4 *>(A.text->d_packed));
-            } else {
-                const filter_kernel k = select_filter_kernel(F, ps->sigma, km);
-                if (!k) {
-                    SPM_SET_ERR(ctx, "internal: no filter kernel for stride %u, key length %u, sigma %u, hash variant %u, %u patterns",
-                                F.stride, F.key_len, ps->sigma, F.hash_variant, F.n_pat);
-                    return SPM_E_UNSUPPORTED;
-                }
-                launch(k, dim3(grid), threads, lds, ctx->stream, P);
-            }
+            SPM_TRY(launch_stream_pass(A, P, (uint32_t)fi)); // (the pass's tables, geometry and span plan: filter_stream.hip)
             SPM_HIP_CHECK(ctx, hipGetLastError());
             H->stats.main_launches++;
         }
@@ -390,14 +176,7 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
         // grid: what earlier scans of this needle set produced (a full grid of idle workgroups costs ~30 us on a 2.6 ms scan);
         // a scan that produces more simply loops
         const uint64_t surv_expect = ps->cand_hint ? 2 * ps->cand_hint : Z.surv_cap;
-        // (5 workgroups per CU are resident at once -- LDS queues, 84 VGPRs --: a larger grid only adds a second, partly filled
-        // round.  A lane takes ~4 survivors in turn: measured on C5, whose survivors are few and cheap, 0.137 -> 0.10 ms;
-        // c3r 1.33 -> 1.25 ms with the cap alone.)
-        const uint64_t rmax = (uint64_t)ctx->n_cu * 5;
-        // (a short survivor list: one survivor per lane, its latency is the kernel's; a long one: four per lane)
-        const uint64_t per_wg = (surv_expect + 255) / 256 <= rmax ? 256 : 1024;
-        const uint32_t rgrid = (uint32_t)std::min<uint64_t>(rmax, std::max<uint64_t>(ctx->n_cu / 2, (surv_expect + per_wg - 1) / per_wg));
-        hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, R);
+        ::launch_resolve(R, surv_expect, (uint32_t)ctx->n_cu, ctx->stream);
         SPM_HIP_CHECK(ctx, hipGetLastError());
         return SPM_OK;
     }
@@ -417,15 +196,16 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
         V.seen = seen;
         V.band_counter = kCntBandSlots;
         band_rec *kept = bands + Z.band_cap; // the second half of the band list: the bands a pre-pass keeps
+        const uint32_t n_cu = (uint32_t)ctx->n_cu;
         if (runs) {
-            hipLaunchKernelGGL(band_runs_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, bands, kept, H->d_count + kCntRunHeads);
+            launch_band_runs(V, bands, kept, H->d_count + kCntRunHeads, n_cu, ctx->stream);
             SPM_HIP_CHECK(ctx, hipGetLastError());
             V.runs = 1;
             V.bands = kept;
             V.band_counter = kCntRunHeads;
         }
         if (Z.overlap) {
-            hipLaunchKernelGGL(band_select_kernel, dim3(ctx->n_cu * 2), dim3(256), 0, ctx->stream, V, kept, H->d_count + kCntBandsSelected);
+            launch_band_select(V, kept, H->d_count + kCntBandsSelected, n_cu, ctx->stream);
             SPM_HIP_CHECK(ctx, hipGetLastError());
             V.bands = kept;
             V.band_counter = kCntBandsSelected;
@@ -434,17 +214,15 @@ struct filter_run // one run_filter: the request, its sizes, the scratch buffer 
         if (exact_hits) {
             // (the resolve kernel reported the hits)
         } else if (Z.use_wave) {
-            // one verification is a ~1400-step serial chain: enough waves that every band gets its own right away
-            launch_verify_wave(Z.nwn, V, ps->d_peq_bot, ps->max_m, dim3(ctx->n_cu * 16), ctx->stream);
+            launch_verify_wave(Z.nwn, V, ps->d_peq_bot, ps->max_m, n_cu, ctx->stream);
         } else {
             const uint32_t nwn = Z.nwn > 8 ? ps->NW : Z.nwn; // power of two beyond 8 words
             const uint64_t band_expect = ps->band_hint ? 2 * ps->band_hint : Z.band_cap;
-            const uint32_t vgrid = (uint32_t)std::min<uint64_t>((uint64_t)ctx->n_cu * 4, std::max<uint64_t>(ctx->n_cu / 2, (band_expect + 255) / 256));
-            launch_verify(nwn, V, dim3(vgrid), ctx->stream);
+            launch_verify(nwn, V, band_expect, n_cu, ctx->stream);
         }
         SPM_HIP_CHECK(ctx, hipGetLastError());
         if (runs) {
-            hipLaunchKernelGGL(band_release_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, V, bands, (uint32_t)kCntBandSlots);
+            launch_band_release(V, bands, n_cu, ctx->stream);
             SPM_HIP_CHECK(ctx, hipGetLastError());
         }
         return SPM_OK;
@@ -460,7 +238,7 @@ int run_filter(const scan_args &A, const retry_state &R, filter_result &out)
     filter_run F{A, R, ctx, A.ps, H, size_filter(*A.ps, A.tune, A.end - A.begin, (uint64_t)ctx->n_cu, H->cap, R)};
     const filter_sizes &Z = F.Z;
     SPM_TRY(F.lay_out());
-    // runs of adjacent bands (filter.hpp, band_runs_kernel): when earlier scans of this set left a long band list -- a
+    // runs of adjacent bands (filter_verify.hpp, band_runs_kernel): when earlier scans of this set left a long band list -- a
     // repeat-rich text --, sets without surplus seeds, lane-per-band verification
     const bool runs = !Z.overlap && !F.exact_hits && !Z.use_wave && Z.Bw <= 32 && !R.need_seen && A.tune.verify_runs != 0 &&
                       A.ps->band_hint >= (uint64_t)std::max(0, A.tune.verify_runs_min_bands);
@@ -474,11 +252,4 @@ int run_filter(const scan_args &A, const retry_state &R, filter_result &out)
     SPM_TRY(F.launch_bands(runs));
     SPM_HIP_CHECK(ctx, hipEventRecord(H->ev[3], ctx->stream));
     return SPM_OK;
-}
-
-
-void spm_warm_filter_kernels()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, (const void *)resolve_kernel);
 }

@@ -271,7 +271,7 @@ inline span_plan plan_span(uint64_t n_chunks, uint64_t n_waves, uint32_t unit)
 }
 
 // ---- sizes of one filter run: survivor list, band list, band table, band width, dedupe set, scratch layout ----
-constexpr uint32_t kChunkMin = 32; // first chunk of list slots a wave draws (filter.hpp)
+constexpr uint32_t kChunkMin = 32; // first chunk of list slots a wave draws (filter.hpp: chunk_grow)
 constexpr size_t kSurvivorBytes = 16, kBandRecBytes = 16; // sizeof(survivor), sizeof(band_rec): scan_filter.hip asserts it
 
 struct filter_sizes

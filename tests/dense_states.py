@@ -1,4 +1,4 @@
-"""Key sets and texts that put the dense pass (libspm_amd/csrc/filter.hpp: dense_group / dense_drain) into every state of
+"""Key sets and texts that put the dense pass (libspm_amd/csrc/filter_dense.hpp: dense_group / dense_drain) into every state of
 its presence bits, fingerprint buckets and per-wave queue (a helper module of tests/test_dense_states.py and
 tests/test_gpu_dense_states.py, not a test file).
 

@@ -1,4 +1,4 @@
-"""GPU: the dense pass (libspm_amd/csrc/index_dense.hpp build_dense_index, filter.hpp seed_filter_dense_kernel) -- ONE pass
+"""GPU: the dense pass (libspm_amd/csrc/index_dense.hpp build_dense_index, filter_dense.hpp seed_filter_dense_kernel) -- ONE pass
 over the text for a needle set of any size: anchored windows -> presence bits in LDS -> fingerprint buckets in L2 ->
 survivors.  Forced here for small sets (SPM_HIP_FILTER_DENSE=2); whatever the needles look like, the hits equal the
 brute-force engine's and the CPU oracle's.

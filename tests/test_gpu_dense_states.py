@@ -1,4 +1,4 @@
-"""GPU: the dense pass (filter.hpp seed_filter_dense_kernel: dense_group / dense_drain) with its presence bits, fingerprint
+"""GPU: the dense pass (filter_dense.hpp seed_filter_dense_kernel: dense_group / dense_drain) with its presence bits, fingerprint
 buckets and per-wave queue in every state, on key sets built for it (tests/dense_states.py; tests/test_dense_states.py
 checks the builder against the product's tables on the CPU).
 

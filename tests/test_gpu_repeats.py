@@ -232,7 +232,7 @@ def test_segmented_scan_falls_back_span_by_span(spm, ctx, oracle, budget):
 @pytest.mark.parametrize("ppm,every", [(50000, 8), (120000, 4)])
 def test_band_runs_verify_adjacent_bands_once(spm, ctx, oracle, ppm, every):
     """Runs of adjacent bands (a repeat stretch that a needle nearly matches is hit on a hundred diagonals in a row) are
-    verified by their head with ONE cold start (filter.hpp: band_runs_kernel).  Forced here for a short band list; a
+    verified by their head with ONE cold start (filter_verify.hpp: band_runs_kernel).  Forced here for a short band list; a
     5 %-shaped 64 MiB text (and a 12 % one): hits == the scan without runs == the CPU oracle, nothing reported twice."""
     n = 1 << 26
     text = ctx.generate_repeats(SEED_TEXT, 0, n, ppm)
