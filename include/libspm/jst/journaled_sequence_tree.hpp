@@ -184,6 +184,7 @@ struct jst_bam_options
     jst_sam_options sam;
     std::uint64_t ref_len{0};           // 1 .. 2^31 - 1
     std::uint32_t block_data{0};        // uncompressed bytes per BGZF block, 0: 65280
+    bool deflate{false};                // the blocks compressed (spm_hip_bam_deflate / spm_hip_bgzf_deflate_host), not stored
 };
 
 struct jst_bam
@@ -191,11 +192,14 @@ struct jst_bam
     std::string file, records;
     std::vector<jst_sam_line> lines;
     std::uint64_t header_file_bytes{0}; // where the first record block starts
+    std::vector<std::uint64_t> block_offsets; // with jst_bam_options::deflate only: the file offset of every record block, then their end
     bool operator==(jst_bam const &) const noexcept = default;
     // the BGZF virtual file offset of record i
     std::uint64_t virtual_offset(std::size_t i, std::uint32_t block_data = 0) const
     {
         std::uint64_t const D = block_data ? block_data : 65280u, u = lines[i].offset;
+        if (!block_offsets.empty())
+            return block_offsets[u / D] << 16 | (u % D);
         return (header_file_bytes + (u / D) * (D + 31)) << 16 | (u % D);
     }
 };
@@ -1150,18 +1154,30 @@ public:
         put(plain, o.ref_len, 4);
         auto const frame = [&](std::string const & data, bool eof) {
             spm_bgzf_opts const z{o.block_data, eof ? SPM_BGZF_EOF : 0u, 0};
+            spm_bgzf_deflate_opts const dz{o.block_data, eof ? SPM_BGZF_EOF : 0u, 1, 0};
             std::uint64_t need = 0;
-            int rc = spm_hip_bgzf_frame_host(data.data(), data.size(), &z, nullptr, 0, &need);
+            int rc = o.deflate ? spm_hip_bgzf_deflate_bound(data.size(), &dz, &need)
+                               : spm_hip_bgzf_frame_host(data.data(), data.size(), &z, nullptr, 0, &need);
             std::string framed(need, '\0');
-            if (rc == SPM_E_OVERFLOW)
+            if (o.deflate && rc == SPM_OK)
+                rc = spm_hip_bgzf_deflate_host(data.data(), data.size(), &dz, framed.data(), need, &need);
+            else if (rc == SPM_E_OVERFLOW)
                 rc = spm_hip_bgzf_frame_host(data.data(), data.size(), &z, framed.data(), need, &need);
             if (rc != SPM_OK)
-                hip::fatal("spm_hip_bgzf_frame_host", ctx);
+                hip::fatal(o.deflate ? "spm_hip_bgzf_deflate_host" : "spm_hip_bgzf_frame_host", ctx);
+            framed.resize(need);
             return framed;
         };
         out.file = frame(plain, false);
         out.header_file_bytes = out.file.size();
         out.file += frame(out.records, true);
+        if (o.deflate) { // the record blocks, found by their BSIZE fields
+            std::uint64_t at = out.header_file_bytes;
+            for (std::uint64_t const end = out.file.size() - 28; at < end;
+                 at += (static_cast<std::uint8_t>(out.file[at + 16]) | static_cast<std::uint64_t>(static_cast<std::uint8_t>(out.file[at + 17])) << 8) + 1)
+                out.block_offsets.push_back(at);
+            out.block_offsets.push_back(at);
+        }
         return out;
     }
 
@@ -1766,6 +1782,23 @@ private:
             req.bam_out->file.assign(static_cast<char const *>(file), n_file);
             req.bam_out->records.assign(static_cast<char const *>(records), n_records);
             req.bam_out->header_file_bytes = st.header_file_bytes;
+            req.bam_out->block_offsets.clear();
+            if (req.bam_options->deflate) {
+                spm_bgzf_deflate_opts const dz{req.bam_options->block_data, SPM_BGZF_EOF, 1, 0};
+                spm_bgzf * z = nullptr;
+                if (spm_hip_bam_deflate(b, &dz, &z) != SPM_OK)
+                    hip::fatal("spm_hip_bam_deflate", ctx);
+                std::unique_ptr<spm_bgzf, decltype(&spm_hip_bgzf_destroy)> deflated{z, &spm_hip_bgzf_destroy};
+                std::uint64_t const * offsets = nullptr;
+                std::uint64_t n_blocks = 0;
+                spm_bgzf_deflate_stats ds{};
+                if (spm_hip_bgzf_view(z, &file, &n_file) != SPM_OK || spm_hip_bgzf_blocks(z, &offsets, &n_blocks) != SPM_OK ||
+                    spm_hip_bgzf_deflate_stats(z, &ds) != SPM_OK)
+                    hip::fatal("spm_hip_bgzf_view", ctx);
+                req.bam_out->file.assign(static_cast<char const *>(file), n_file);
+                req.bam_out->header_file_bytes = ds.n_prefix_bytes;
+                req.bam_out->block_offsets.assign(offsets, offsets + n_blocks + 1);
+            }
             req.bam_out->lines.clear();
             for (std::uint64_t i = 0; i < n_lines; ++i)
                 req.bam_out->lines.push_back({lines[i].offset, lines[i].len, lines[i].read, lines[i].source, lines[i].flag,

@@ -1089,6 +1089,68 @@ void spm_hip_bgzf_destroy(spm_bgzf *z);
 int spm_hip_bgzf_frame_host(const void *src, uint64_t n, const spm_bgzf_opts *opts, void *dst, uint64_t cap, uint64_t *len);
 int spm_hip_bgzf_framed_size(uint64_t n, const spm_bgzf_opts *opts, uint64_t *len);
 
+/* ---- BGZF blocks with real deflate: LZ77 matches and the fixed Huffman code, per block, on the device -------------------
+ * spm_hip_bgzf_deflate is spm_hip_bgzf_frame with the blocks compressed: the same container (BC field, BSIZE = total - 1,
+ * CRC32, ISIZE, the same split of n bytes into blocks of block_data, the same EOF block), and the payload of a block is ONE
+ * deflate block with BFINAL 1 -- fixed Huffman (BTYPE 01) if that is strictly smaller than the stored form (d + 5 bytes), else
+ * the stored block (BTYPE 00) spm_hip_bgzf_frame writes.  So no block is longer than d + 31 and no file longer than the
+ * stored file, and BSIZE always fits.  What `samtools view -b` writes, where spm_hip_bgzf_frame is `-u`.
+ *
+ * The token rule (the output is a pure function of the bytes and the opts: spm_hip_bgzf_deflate_host gives the same bytes):
+ *   * Lane t of 256 owns the positions [t c, min((t + 1) c, d)) of a block, c = max(64, ceil(d / 256)).  No token crosses a
+ *     chunk border; a match's source lies anywhere earlier in the block and may overlap its target.
+ *   * Two candidates per position i.  Near: i - 1.  Far: the largest j with hash4(j) == hash4(i) among the positions of earlier
+ *     segments of 256 positions, hash4 = (the four bytes at the position as a little-endian word * 2654435761 mod 2^32) >> 18;
+ *     positions with fewer than four bytes behind them in the block have no far candidate and are not hashed.
+ *   * Greedy, left to right: at i both candidates are extended, no further than 258 symbols, the chunk's end, or (far) a
+ *     distance of 32768.  The longer wins, the near one on a tie.  A match if its length is >= 4, or >= 3 at distance 1; else
+ *     the literal.
+ *   * Bits: 1 (BFINAL), 1 0 (BTYPE 01), the lanes' tokens in lane order in the RFC 1951 fixed code, the end-of-block code
+ *     (seven zeros), zero padding to the byte.
+ * Worked cases, block_data 0, SPM_BGZF_EOF (each inflated with zlib; the EOF block follows):
+ *   the 6 bytes "abcdef" (six literals, 58 bits), 34 bytes where the stored block takes 37:
+ *                                     1f8b08040000000000ff0600424302002100 4b4c4a4e494d0300 ef398e4b 06000000
+ *   300 bytes 'a' (lane 0: literal, match 63 at 1; lanes 1 .. 3: match 64 at 1; lane 4: match 44 at 1; 93 bits), 38 bytes:
+ *                                     1f8b08040000000000ff0600424302002500 4ba410500a28059402520000 09199789 2c010000
+ * A record at offset u of the uncompressed stream has the BGZF virtual offset offsets[u / D] << 16 | u % D, with the offsets
+ * of spm_hip_bgzf_blocks.
+ *
+ *   * SPM_E_INVALID with a message, decided on the host before any launch: NULL ctx, opts or out; NULL device_src with n > 0;
+ *     block_data above 65280; flag bits other than SPM_BGZF_EOF; a level other than 1; a nonzero reserved.
+ *   * SPM_E_UNSUPPORTED, likewise: more than 2^31 - 2 blocks.
+ *   * n == 0: SPM_OK with the EOF block, or with nothing.
+ * The result is a spm_bgzf: view, device, stats (n_out the real size) and destroy work on it.  It outlives the source. */
+typedef struct spm_bgzf_deflate_opts { /* 16 bytes */
+    uint32_t block_data;            /* uncompressed bytes per block, 1 .. 65280; 0: 65280 */
+    uint32_t flags;                 /* SPM_BGZF_EOF */
+    uint32_t level;                 /* must be 1: fixed Huffman */
+    uint32_t reserved;              /* must be 0 */
+} spm_bgzf_deflate_opts;
+typedef struct spm_bgzf_deflate_stats { /* 72 bytes */
+    float ms_parse;                 /* device (HIP events): candidates, parse, bits and CRC of every block */
+    float ms_scan;                  /* device: the blocks' file offsets */
+    float ms_place;                 /* device: the blocks at their place, the EOF block */
+    float ms_host;                  /* wall clock of the whole call */
+    uint64_t n_in;
+    uint64_t n_out;                 /* the file's bytes, prefix and EOF block included */
+    uint64_t n_blocks;              /* data blocks of the device part */
+    uint64_t n_stored_blocks;       /* of them, those that did not shrink */
+    uint64_t n_matches;             /* tokens of the blocks that came out fixed */
+    uint64_t n_literals;
+    uint64_t n_prefix_bytes;        /* bytes in front of the first data block (spm_hip_bam_deflate: the header's blocks) */
+} spm_bgzf_deflate_stats;
+int spm_hip_bgzf_deflate(spm_ctx *ctx, const void *device_src, uint64_t n, const spm_bgzf_deflate_opts *opts, spm_bgzf **out);
+/* n_blocks + 1 file offsets: of every data block, then the end of the data blocks.  On the host (made when first asked for)
+ * and on the device.  Also for a handle of spm_hip_bgzf_frame, where they are b * (D + 31).  Every out pointer may be NULL. */
+int spm_hip_bgzf_blocks(spm_bgzf *z, const uint64_t **offsets, uint64_t *n_blocks);
+int spm_hip_bgzf_blocks_device(spm_bgzf *z, const void **offsets, uint64_t *n_blocks);
+/* of a handle of spm_hip_bgzf_frame: every block stored, no tokens, ms_place the frame stage */
+int spm_hip_bgzf_deflate_stats(const spm_bgzf *z, spm_bgzf_deflate_stats *out);
+/* host only, no device needed: the same bytes by the serial rendering of the same rule.  *len is what it needs
+ * (spm_hip_bgzf_deflate_bound is enough: the stored size); cap too small: SPM_E_OVERFLOW and nothing is written. */
+int spm_hip_bgzf_deflate_host(const void *src, uint64_t n, const spm_bgzf_deflate_opts *opts, void *dst, uint64_t cap, uint64_t *len);
+int spm_hip_bgzf_deflate_bound(uint64_t n, const spm_bgzf_deflate_opts *opts, uint64_t *len);
+
 /* ---- BAM records in BGZF blocks: the same alignments as spm_hip_jst_ref_loci_sam, as the file its users store ---------------
  * One call turns (loci, read summary, optionally pairs and rescues, needle set) into a complete BAM file in HBM: the header
  * section (framed on the host into blocks of its own, so that records start at a block border, as htslib writes them), the
@@ -1176,6 +1238,12 @@ void spm_hip_bam_destroy(spm_bam *b);
  * the name with its NUL, l_ref, in BGZF blocks of block_data (0: 65280) without an EOF block.  *len is what it needs; cap too
  * small: SPM_E_OVERFLOW and nothing is written.  rname, ref_len and block_data are checked as above. */
 int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len);
+/* The file of a BAM handle with its blocks deflated (spm_hip_bgzf_deflate's rule and refusals; b NULL: SPM_E_INVALID): the
+ * plain header section deflated on the host into blocks of its own, the handle's device record stream deflated by the kernels
+ * behind it, the EOF block with SPM_BGZF_EOF.  The result's view and device hold the whole file; the offsets of
+ * spm_hip_bgzf_blocks are absolute file offsets of the record blocks, n_prefix_bytes is where the first one starts.  The
+ * result needs the BAM handle no longer once the call returns. */
+int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out);
 
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to

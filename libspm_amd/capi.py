@@ -330,6 +330,16 @@ class BgzfStats(C.Structure):
 BGZF_EOF, BGZF_BLOCK_DATA = 1, 65280
 
 
+class BgzfDeflateOpts(C.Structure):
+    _fields_ = [("block_data", C.c_uint32), ("flags", C.c_uint32), ("level", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BgzfDeflateStats(C.Structure):
+    _fields_ = [("ms_parse", C.c_float), ("ms_scan", C.c_float), ("ms_place", C.c_float), ("ms_host", C.c_float),
+                ("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
+                ("n_matches", C.c_uint64), ("n_literals", C.c_uint64), ("n_prefix_bytes", C.c_uint64)]
+
+
 class SamStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_float),
@@ -550,6 +560,13 @@ def lib():
         "spm_hip_bgzf_destroy": (None, [vp]),
         "spm_hip_bgzf_frame_host": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfOpts), vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "spm_hip_bgzf_framed_size": (C.c_int, [C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_deflate": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(vp)]),
+        "spm_hip_bgzf_blocks": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_blocks_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_deflate_stats": (C.c_int, [vp, C.POINTER(BgzfDeflateStats)]),
+        "spm_hip_bgzf_deflate_host": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "spm_hip_bgzf_deflate_bound": (C.c_int, [C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(C.c_uint64)]),
+        "spm_hip_bam_deflate": (C.c_int, [vp, C.POINTER(BgzfDeflateOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
         "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
@@ -608,6 +625,8 @@ EXPORTS = [
     "spm_hip_bam_header",
     "spm_hip_bgzf_frame", "spm_hip_bgzf_view", "spm_hip_bgzf_device", "spm_hip_bgzf_stats", "spm_hip_bgzf_destroy",
     "spm_hip_bgzf_frame_host", "spm_hip_bgzf_framed_size",
+    "spm_hip_bgzf_deflate", "spm_hip_bgzf_blocks", "spm_hip_bgzf_blocks_device", "spm_hip_bgzf_deflate_stats",
+    "spm_hip_bgzf_deflate_host", "spm_hip_bgzf_deflate_bound", "spm_hip_bam_deflate",
     "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
     "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
     "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",

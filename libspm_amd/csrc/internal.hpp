@@ -225,6 +225,10 @@ void spm_warm_bgzf_kernels();
 // ---- the frame stage of BGZF (bgzf.hip) on the context's stream: n bytes at d_src into d_dst, which has room for
 // bgzf_framed_size(n, D, eof) bytes (bgzf_core.hpp) ----
 hipError_t bgzf_frame_enqueue(spm_ctx *ctx, const void *d_src, uint64_t n, uint32_t D, bool eof, void *d_dst);
+// ---- the deflate stages (bgzf.hip): n bytes at d_src as deflated blocks behind `prefix`, bytes that are blocks already, into a
+// new handle whose offsets count from the prefix's first byte.  The opts have passed spm_hip_bgzf_deflate's checks. ----
+int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t n, const spm_bgzf_deflate_opts *opts,
+                     const std::vector<uint8_t> &prefix, spm_bgzf **out);
 
 // deferred scans (SPM_SCAN_DEFER): read the counters back, and repeat the scan if it needs attention   (scan.hip)
 int spm_complete_deferred(spm_hits *h);

@@ -148,6 +148,7 @@ struct spm_bam
     bool have_host = false; // the views are downloaded when first asked for
     std::vector<uint8_t> host_file, host_records;
     std::vector<spm_sam_line> host_lines;
+    std::vector<uint8_t> plain_header; // the header section before its framing: what spm_hip_bam_deflate compresses again
     spm_bam_stats stats{};
 };
 static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");
@@ -287,6 +288,7 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
                     (unsigned long long)n_records, D);
         return SPM_E_UNSUPPORTED;
     }
+    R->plain_header = plain;
     R->n_lines = B.P.n_lines;
     R->n_record_bytes = n_records;
     R->n_file = header.size() + bgzf_framed_size(n_records, D, true);
@@ -346,6 +348,35 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
                 R->stats.ms_frame, R->stats.ms_stats, R->stats.ms_host);
     *out = R.release();
     return SPM_OK;
+}
+
+extern "C" int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out)
+{
+    static const char *const who = "spm_hip_bam_deflate";
+    if (out)
+        *out = nullptr;
+    if (!b)
+        return SPM_E_INVALID;
+    spm_ctx *ctx = b->ctx;
+    if (!opts || !out) {
+        SPM_SET_ERR(ctx, "%s: NULL %s", who, !opts ? "opts" : "out");
+        return SPM_E_INVALID;
+    }
+    // the header section through the host deflater, without an EOF block: that call holds the opts to the rule
+    spm_bgzf_deflate_opts o = *opts;
+    o.flags &= ~SPM_BGZF_EOF;
+    uint64_t need = 0, len = 0;
+    int rc = spm_hip_bgzf_deflate_bound(b->plain_header.size(), &o, &need);
+    std::vector<uint8_t> header(need);
+    if (rc == SPM_OK)
+        rc = spm_hip_bgzf_deflate_host(b->plain_header.data(), b->plain_header.size(), &o, header.data(), need, &len);
+    if (rc != SPM_OK) {
+        SPM_SET_ERR(ctx, "%s: block_data %u above 65280, flags 0x%x other than SPM_BGZF_EOF, level %u other than 1 or reserved %u", who,
+                    opts->block_data, opts->flags, opts->level, opts->reserved);
+        return rc;
+    }
+    header.resize(len);
+    return bgzf_deflate_run(who, ctx, b->d_records, b->n_record_bytes, opts, header, out);
 }
 
 extern "C" int spm_hip_bam_view(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,

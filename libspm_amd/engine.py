@@ -82,7 +82,15 @@ class Context:
         opts = bgzf_opts(block_data, eof)
         z = C.c_void_p()
         _check(capi.lib().spm_hip_bgzf_frame(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
-        return Bgzf(self, z)
+        return Bgzf(self, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
+
+    def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
+        block; a block that would not shrink stays stored).  The same arguments; the bytes are those of bgzf_deflate_host."""
+        opts = bgzf_deflate_opts(block_data, eof)
+        z = C.c_void_p()
+        _check(capi.lib().spm_hip_bgzf_deflate(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
+        return Bgzf(self, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
 
     # ---- needles ----
     def patterns(self, algo: int, needles, k=0, sigma: int = 4, both_strands: bool = False) -> "PatternSet":
@@ -931,6 +939,14 @@ class Sam:
             z.prefix = bgzf_frame_host(self.header(ref_len), block_data, eof=False)
         return z
 
+    def bgzf_deflate(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """bgzf() with the blocks compressed (Context.bgzf_deflate); the header's blocks come from the host deflater."""
+        text, n_bytes, _lines, _n = self.device()
+        z = self.ctx.bgzf_deflate(text, n_bytes, block_data=block_data, eof=eof)
+        if ref_len is not None:
+            z.prefix = bgzf_deflate_host(self.header(ref_len), block_data, eof=False)
+        return z
+
     def close(self):
         if self._h:
             if self.ctx._h:
@@ -991,6 +1007,15 @@ class Bam:
         D = np.uint64(self.block_data)
         return ((np.uint64(self.stats().header_file_bytes) + (u // D) * (D + np.uint64(31))) << np.uint64(16)) | (u % D)
 
+    def deflate(self, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """The file with its blocks compressed (spm_hip_bam_deflate): the header section deflated on the host, the record
+        stream on the device where it lies, in blocks of block_data uncompressed bytes.  block_offsets() are the record
+        blocks' file offsets; voffsets(self.lines()["offset"]) the records' virtual offsets."""
+        opts = bgzf_deflate_opts(block_data, eof)
+        z = C.c_void_p()
+        _check(capi.lib().spm_hip_bam_deflate(self._h, C.byref(opts), C.byref(z)), self.ctx._h)
+        return Bgzf(self.ctx, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
+
     def device(self):
         """(file, n_file, records, n_record_bytes, lines, n_lines): device pointers and counts"""
         f, r, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -1037,12 +1062,53 @@ def bgzf_frame_host(data, block_data: int = 0, eof: bool = True) -> bytes:
     return dst.raw[:need.value]
 
 
-class Bgzf:
-    """Result of Context.bgzf() / Sam.bgzf(): BGZF blocks in device memory.  prefix: bytes framed on the host that belong in
-    front of them (Sam.bgzf with ref_len: the header's blocks); bytes() has them, device() is the device part alone."""
+def bgzf_deflate_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfDeflateOpts:
+    return capi.BgzfDeflateOpts(block_data=int(block_data), flags=capi.BGZF_EOF if eof else 0, level=1, reserved=0)
 
-    def __init__(self, ctx, h, prefix: bytes = b""):
-        self.ctx, self._h, self.prefix = ctx, h, prefix
+
+def bgzf_deflate_host(data, block_data: int = 0, eof: bool = True) -> bytes:
+    """The bytes of Context.bgzf_deflate by the serial host deflater (spm_hip_bgzf_deflate_host).  Needs no device."""
+    data = bytes(data)
+    opts = bgzf_deflate_opts(block_data, eof)
+    cap = C.c_uint64()
+    _check(capi.lib().spm_hip_bgzf_deflate_bound(len(data), C.byref(opts), C.byref(cap)), None)
+    src = C.create_string_buffer(data, len(data) + 1)
+    dst = C.create_string_buffer(cap.value + 1)
+    need = C.c_uint64()
+    _check(capi.lib().spm_hip_bgzf_deflate_host(src, len(data), C.byref(opts), dst, cap.value, C.byref(need)), None)
+    return dst.raw[:need.value]
+
+
+class Bgzf:
+    """Result of Context.bgzf() / Sam.bgzf(), their bgzf_deflate() and Bam.deflate(): BGZF blocks in device memory.  prefix: bytes
+    framed on the host that belong in front of them (Sam.bgzf with ref_len: the header's blocks); bytes() has them, device()
+    is the device part alone.  block_data: the uncompressed bytes of a full block."""
+
+    def __init__(self, ctx, h, prefix: bytes = b"", block_data: int = capi.BGZF_BLOCK_DATA):
+        self.ctx, self._h, self.prefix, self.block_data = ctx, h, prefix, block_data
+
+    def block_offsets(self) -> np.ndarray:
+        """n_blocks + 1 offsets into bytes(): of every data block of the device part, then their end (spm_hip_bgzf_blocks)"""
+        p, n = C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(capi.lib().spm_hip_bgzf_blocks(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return np.ctypeslib.as_array(p, shape=(n.value + 1,)).astype(np.uint64) + np.uint64(len(self.prefix))
+
+    def block_offsets_device(self):
+        """(offsets, n_blocks): the same offsets on the device, without the prefix's length"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(capi.lib().spm_hip_bgzf_blocks_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        return int(p.value or 0), int(n.value)
+
+    def voffsets(self, stream_offsets) -> np.ndarray:
+        """the BGZF virtual file offset of the bytes at these offsets of the uncompressed stream"""
+        u = np.asarray(stream_offsets).astype(np.uint64)
+        D = np.uint64(self.block_data)
+        return (self.block_offsets()[(u // D).astype(np.int64)] << np.uint64(16)) | (u % D)
+
+    def deflate_stats(self) -> capi.BgzfDeflateStats:
+        s = capi.BgzfDeflateStats()
+        _check(capi.lib().spm_hip_bgzf_deflate_stats(self._h, C.byref(s)), self.ctx._h)
+        return s
 
     def bytes(self) -> bytes:
         p, n = C.c_void_p(), C.c_uint64()
