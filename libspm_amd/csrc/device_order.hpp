@@ -2,13 +2,14 @@
 // select.hip, jst_select.hip, jst_locate.hpp, transcript_slots.hpp (the slot stage of jst_project.hpp, jst_normalize.hpp
 // and jst_collapse.hpp), those three themselves, jst_reads.hpp and jst_pairs.hpp.  Here are
 //   the launch of a one-lane-per-item kernel on the context's stream,
-//   the hipcub radix sort of (64-bit key, 32-bit index) pairs over the key's low bits,
+//   the radix sort of (64-bit key, 32-bit index) pairs over the key's low bits: declared here, compiled once in
+//   device_order.hip (hipcub's sort is 234 kernels; defined inline here, every unit that included this header compiled them),
 //   the hipcub exclusive sum over any input iterator,
 //   the read-back of a call's counts,
 //   the events a call times its stages with,
 //   the handle of a result that is records alone (no pool).
-// HIP, host code only: hipcub instantiates for the callers' own iterator types what a direct call would.  Every function
-// returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
+// HIP, host code only: the sums are templates, so hipcub instantiates for the callers' own iterator types what a direct call
+// would.  Every function returns the first hipError_t that is not hipSuccess, for the caller's SPM_HIP_CHECK.
 #pragma once
 
 #include <vector>
@@ -31,22 +32,12 @@ hipError_t launch_1d(spm_ctx *ctx, void (*kernel)(Params...), uint64_t n_items, 
     return hipGetLastError();
 }
 
-// ---- the sort: keys_in/idx_in -> keys_out/idx_out, stable, by bits [0, key_bits) of the key ----
-inline hipError_t sort_pairs_tmp_bytes(spm_ctx *ctx, size_t n, uint32_t key_bits, size_t *tmp_bytes)
-{
-    *tmp_bytes = 0;
-    return hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, (const unsigned long long *)nullptr,
-                                              (unsigned long long *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, n, 0,
-                                              (int)key_bits, ctx->stream);
-}
-
-inline hipError_t sort_pairs(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const unsigned long long *keys_in,
-                             unsigned long long *keys_out, const uint32_t *idx_in, uint32_t *idx_out, size_t n,
-                             uint32_t key_bits)
-{
-    return hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, (int)key_bits,
-                                              ctx->stream);
-}
+// ---- the sort: keys_in/idx_in -> keys_out/idx_out, stable, by bits [0, key_bits) of the key (device_order.hip) ----
+#pragma GCC visibility push(hidden) // calls between the library's own units, not part of its surface
+hipError_t sort_pairs_tmp_bytes(spm_ctx *ctx, size_t n, uint32_t key_bits, size_t *tmp_bytes);
+hipError_t sort_pairs(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
+                      const uint32_t *idx_in, uint32_t *idx_out, size_t n, uint32_t key_bits);
+#pragma GCC visibility pop
 
 // ---- the exclusive sum of n items of `in` into out[0..n) ----
 template <class Out, class Iter> hipError_t exclusive_sum_tmp_bytes(spm_ctx *ctx, Iter in, size_t n, size_t *tmp_bytes)

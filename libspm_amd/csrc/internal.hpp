@@ -1,8 +1,10 @@
 // internal.hpp -- what the translation units of libspm_hip.so share: the compiled needle set, the arguments of one scan, and
 // the entry points of the engines.  (patterns.hip: needle sets; text.hip: context + haystacks; scan.hip: the scan driver;
 // scan_brute.hip / scan_filter.hip: the engines, the seed filter's kernels in filter_stream / filter_dense / filter_resolve /
-// filter_verify.hip (filter_launch.hpp); hits.hip: results; jst.hip: journaled sequences;
-// comm.hip: the multi-GPU exchange.)
+// filter_verify.hip (filter_launch.hpp); hits.hip: results; align.hip: alignments of hits; select.hip: selection of hits;
+// device_order.hip: the pair sort of the drivers that order records (device_order.hpp); jst.hip: journaled sequences, with
+// jst_align.hip, jst_ref.hip, jst_reads.hip and jst_sam.hip behind it (map in jst.hpp) and jst_select.hip beside it;
+// bgzf.hip: BGZF framing and deflate; comm.hip: the multi-GPU exchange.)
 #pragma once
 
 #include <algorithm>
@@ -221,6 +223,13 @@ void spm_warm_hits_kernels();
 void spm_warm_jst_kernels();
 void spm_warm_align_kernels();
 void spm_warm_bgzf_kernels();
+#pragma GCC visibility push(hidden) // (the units behind the tree, and the pair sort: calls inside the library, like filter_launch.hpp's)
+void spm_warm_jst_align_kernels();
+void spm_warm_jst_ref_kernels();
+void spm_warm_jst_reads_kernels();
+void spm_warm_jst_sam_kernels();
+void spm_warm_device_order_kernels(spm_ctx *ctx); // (hipcub's kernels have no name to ask for: it sorts one pair in ctx's scratch)
+#pragma GCC visibility pop
 
 // ---- the frame stage of BGZF (bgzf.hip) on the context's stream: n bytes at d_src into d_dst, which has room for
 // bgzf_framed_size(n, D, eof) bytes (bgzf_core.hpp) ----

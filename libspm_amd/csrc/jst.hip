@@ -1,18 +1,12 @@
-// jst.hip -- journaled-sequence (pan-genome) search, config C5.
+// jst.hip -- journaled-sequence (pan-genome) search, config C5: the tree, its index and the search.  What is done with the
+// hits is in the units behind it (map in jst.hpp).
 // MI355X only; no CPU scan path exists in this library: if HIP fails the call fails.
-#include "internal.hpp"
-#include "synth.hpp"
 #include "jst.hpp"
 #include "jst_index.hpp"
 #include "jst_search.hpp"
-#include "jst_hits_align.hpp"
-#include "jst_locate.hpp"
-#include "transcript_slots.hpp"
-#include "jst_project.hpp"
-#include "jst_normalize.hpp"
-#include "jst_collapse.hpp"
-#include "jst_reads.hpp"
-#include "jst_pairs.hpp"
-#include "jst_rescue.hpp"
-#include "jst_sam.hpp"
-#include "jst_bam.hpp"
+
+void spm_warm_jst_kernels()
+{
+    hipFuncAttributes a;
+    (void)hipFuncGetAttributes(&a, (const void *)spm_hip::jst_fanout_kernel);
+}

@@ -18,119 +18,33 @@
 //      last symbol lies in the owned part is fanned out to the haplotypes of its group.
 // By the window property (a hit depends only on the window_size symbols ending at it) this is exact; work on the
 // device is proportional to the distinct sequence content, not to haplotypes x length.
-// Here: the tree object spm_jst (create, destroy, extract, length, stats) and the variant generator of C5.  Behind it in jst.hip:
+// Here: the C-ABI calls of the tree object spm_jst (create, destroy, extract, length, stats) and the variant generator of C5.
+// Everything behind the tree is one translation unit per group of stages; every kernel and every C-ABI call is defined in
+// exactly one of them, and a stage reads the stages before it through their handles alone (jst_handles.hpp):
+//   jst.hip         tree, index, search
+//     jst.hpp             this header
+//     jst_index.hpp       spm_hip_jst_index: the build kernels and the build as named stages
+//     jst_search.hpp      spm_hip_jst_search, jst_fanout_kernel and the accessors of the records
+//   jst_align.hip   alignments of hits in haplotype coordinates (both call align.hip's align_run through jst_align_segments)
+//     jst_hits_align.hpp  spm_hip_jst_hits_align, jst_aln_fanout_kernel, and what the call shares with jst_locate.hpp
+//     jst_locate.hpp      spm_hip_jst_selection_align
+//   jst_ref.hip     alignments in reference coordinates (all three begin with the slot stage)
+//     transcript_slots.hpp, jst_project.hpp, jst_normalize.hpp, jst_collapse.hpp
+//   jst_reads.hip   per-read and per-pair summaries over loci
+//     jst_reads.hpp, jst_pairs.hpp, jst_rescue.hpp
+//   jst_sam.hip     output (BAM reuses the SAM front and kernels)
+//     jst_sam.hpp, jst_bam.hpp
+// and under all of them
+//   jst_handles.hpp     the tree and every stage's result handle
 //   jst_walk_core.hpp   what a cell owns and what its context spells (steps 1-3 and the spelling of 4), host and device alike
-//   jst_fanout.hpp      the context tables as one set; the fan-out of step 4, for hits and for alignments
-//   jst_index.hpp       spm_hip_jst_index: the build kernels and the build as named stages
-//   jst_search.hpp      spm_hip_jst_search and the accessors of its records
-//   jst_hits_align.hpp  spm_hip_jst_hits_align, spm_jst_alns, and what they share with jst_locate.hpp
+//   jst_ctx_tables.hpp  the context tables of the index as one set
+//   jst_fanout.hpp      the walk of step 4's fan-out, shared by the kernel for hits and the kernel for alignments
+// (jst_select.hip, the selection of hits, is a unit of its own beside these.)
 #pragma once
 
-#include "device_order.hpp"
-#include "scratch_layout.hpp"
-#include "jst_fanout.hpp"
-
-// the ctypes binding (libspm_amd/capi.py) mirrors these layouts
-static_assert(sizeof(spm_jst_allele) == 24 && sizeof(spm_jst_hit) == 24 && sizeof(spm_jst_stats) == 104, "C ABI layout");
-static_assert(sizeof(spm_jst_aln) == 40 && sizeof(spm_jst_align_stats) == 80, "C ABI layout");
-
-struct spm_jst
-{
-    spm_ctx *ctx = nullptr;
-    const spm_text *ref = nullptr;
-    std::vector<spm_jst_allele> al;
-    std::vector<uint8_t> alt;
-    std::vector<uint64_t> cov;
-    uint32_t H = 0, cw = 0, max_rlen = 0;
-    uint64_t max_hap_len = 0; // reference length plus all inserted symbols: no haplotype position lies beyond it
-    // device allele table
-    uint64_t *d_pos = nullptr, *d_aoff = nullptr, *d_cov = nullptr;
-    uint32_t *d_rlen = nullptr, *d_alen = nullptr;
-    uint8_t *d_alt = nullptr;
-    // index
-    bool indexed = false;
-    uint32_t window = 0;
-    uint64_t L = 0, n_blocks = 0, jb = 0, je = 0;
-    uint64_t *d_alo = nullptr, *d_hap_start = nullptr;
-    uint16_t *d_local_id = nullptr;
-    uint64_t n_ctx = 0, ctx_bytes = 0;
-    uint64_t *d_ctx_off = nullptr, *d_ctx_base = nullptr, *d_byte_base = nullptr;
-    uint32_t *d_ctx_block = nullptr, *d_ctx_owned = nullptr;
-    spm_text *ctx_text = nullptr;
-    spm_jst_stats stats{};
-    // (record buffers of the searches are recycled through the context: a 200 MB hipMalloc / hipFree pair per search
-    // cost ~0.3 ms)
-    unsigned long long *d_fan_count = nullptr;
-    uint64_t seg_hit_hint = 0; // most segment hits a search has seen (sizes the grid of the fan-out launched behind the scan)
-    hipEvent_t fan_ev[2] = {nullptr, nullptr};
-    // alignment of hits (spm_hip_jst_hits_align): every spm_hip_jst_index starts a new generation -- results of earlier
-    // searches point into buffers it freed -- and the context tables are fetched to the host once per generation
-    uint64_t generation = 0, h_generation = ~0ull;
-    std::vector<uint64_t> h_ctx_off;   // [n_ctx + 1]
-    std::vector<uint32_t> h_ctx_owned; // [n_ctx]
-
-    spm_hip::jst_dev dev() const
-    {
-        spm_hip::jst_dev J{};
-        J.ref = ref->d;
-        J.n_ref = ref->n;
-        J.pos = d_pos;
-        J.rlen = d_rlen;
-        J.alen = d_alen;
-        J.aoff = d_aoff;
-        J.alt = d_alt;
-        J.cov = d_cov;
-        J.n_alleles = al.size();
-        J.cw = cw;
-        J.n_hap = H;
-        J.n_groups = (H + spm_hip::kJstGroup - 1) / spm_hip::kJstGroup;
-        J.max_rlen = max_rlen;
-        J.window = window;
-        J.L = L;
-        J.n_blocks = n_blocks;
-        J.jb = jb;
-        J.je = je;
-        J.a_lo = d_alo;
-        J.hap_start = d_hap_start;
-        return J;
-    }
-    spm_hip::jst_ctx_tables ctx_tables() const
-    {
-        return spm_hip::jst_ctx_tables{d_ctx_off, n_ctx, d_ctx_block, d_ctx_owned, d_ctx_base, d_local_id};
-    }
-    // The context tables on the host, for the alignment entry points: enqueued once per index generation.  The caller
-    // synchronises the stream and then sets h_generation = generation.
-    int fetch_ctx_tables()
-    {
-        if (h_generation == generation)
-            return SPM_OK;
-        h_ctx_off.resize(n_ctx + 1);
-        h_ctx_owned.resize(n_ctx);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(h_ctx_off.data(), d_ctx_off, (n_ctx + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_ctx)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(h_ctx_owned.data(), d_ctx_owned, n_ctx * 4, hipMemcpyDeviceToHost, ctx->stream));
-        return SPM_OK;
-    }
-    void free_index()
-    {
-        hipFree(d_alo);
-        hipFree(d_hap_start);
-        hipFree(d_local_id);
-        hipFree(d_ctx_off);
-        hipFree(d_ctx_base);
-        hipFree(d_byte_base);
-        hipFree(d_ctx_block);
-        hipFree(d_ctx_owned);
-        d_alo = d_hap_start = d_ctx_off = d_ctx_base = d_byte_base = nullptr;
-        d_local_id = nullptr;
-        d_ctx_block = d_ctx_owned = nullptr;
-        if (ctx_text)
-            spm_hip_text_destroy(ctx_text);
-        ctx_text = nullptr;
-        indexed = false;
-        ++generation;
-    }
-};
+#include "internal.hpp"
+#include "jst_handles.hpp"
+#include "synth.hpp"
 
 extern "C" int spm_hip_jst_create(spm_ctx *ctx, const spm_text *reference, const spm_jst_allele *alleles,
                                   uint64_t n_alleles, const uint8_t *alt_pool, uint64_t alt_pool_len,

@@ -1,6 +1,6 @@
 // jst_bam.hpp -- BAM records in BGZF blocks (spm_hip_jst_ref_loci_bam; contract in spm_hip.h, scheme in DESIGN.md 4.12, the
-// composition in jst_bam_core.hpp).  gfx950.  Included by jst.hip behind jst_sam.hpp, whose front (the host's refusals, the lines
-// stage) and stats kernel it uses, and bgzf.hip, whose frame stage it enqueues.
+// composition in jst_bam_core.hpp).  gfx950.  Unit: jst_sam.hip, with jst_sam.hpp, whose front (the host's refusals, the lines
+// stage) and stats kernel it uses; it enqueues the frame stage of bgzf.hip (internal.hpp).
 //   jst_bam_measure_kernel   one lane per record: resolved against its sources with the query length checked, its shape (item
 //                            count, bin; what a record cannot hold is counted as a disagreement), its length by the measuring
 //                            sink;
@@ -138,20 +138,6 @@ __global__ __launch_bounds__(256) void jst_bam_write_kernel(const jst_bam_params
 }
 
 } // namespace spm_hip
-
-struct spm_bam
-{
-    spm_ctx *ctx = nullptr;
-    uint8_t *d_file = nullptr, *d_records = nullptr;
-    spm_sam_line *d_lines = nullptr;
-    uint64_t n_file = 0, n_record_bytes = 0, n_lines = 0;
-    bool have_host = false; // the views are downloaded when first asked for
-    std::vector<uint8_t> host_file, host_records;
-    std::vector<spm_sam_line> host_lines;
-    std::vector<uint8_t> plain_header; // the header section before its framing: what spm_hip_bam_deflate compresses again
-    spm_bam_stats stats{};
-};
-static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");
 
 extern "C" void spm_hip_bam_destroy(spm_bam *b)
 {

@@ -1,6 +1,6 @@
 // jst_collapse.hpp -- projected pan-genome alignments collapsed to one record per locus (spm_hip_jst_ref_alns_collapse;
-// contract in spm_hip.h, scheme in DESIGN.md 4.6b).  gfx950.  Included by jst.hip behind jst_project.hpp: it needs
-// spm_jst_ref_alns.
+// contract in spm_hip.h, scheme in DESIGN.md 4.6b).  gfx950.  Unit: jst_ref.hip.  It reads a spm_jst_ref_alns and makes
+// the spm_jst_ref_loci (jst_handles.hpp) that every later stage reads.
 //
 // Records that share a projected slot share their content, so the content is compared once per distinct slot of the source
 // pool, and the records are ordered afterwards:
@@ -28,9 +28,13 @@
 // and the slot clamp are transcript_slots.hpp's.  Every table index is tested against its size before it is read.
 #pragma once
 
+#include "internal.hpp"
+#include "device_order.hpp"
 #include "jst_collapse_core.hpp"
-
-static_assert(sizeof(spm_jst_ref_locus) == 48 && sizeof(spm_jst_collapse_stats) == 80, "C ABI layout");
+#include "jst_handles.hpp"
+#include "scratch_layout.hpp"
+#include "transcript_slots.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {
@@ -282,19 +286,6 @@ __global__ __launch_bounds__(256) void jst_col_member_kernel(const jst_collapse_
 }
 
 } // namespace spm_hip
-
-struct spm_jst_ref_loci
-{
-    spm_ctx *ctx = nullptr;
-    spm_jst_ref_locus *d_loci = nullptr;
-    uint32_t *d_ops = nullptr, *d_members = nullptr, *d_map = nullptr;
-    int32_t *d_member_scores = nullptr;
-    uint64_t n = 0, n_ops = 0, n_members = 0, n_alns = 0;
-    std::vector<spm_jst_ref_locus> host;
-    std::vector<uint32_t> host_ops, host_members, host_map; // host_map[i]: the locus of record i of the source's HOST view
-    std::vector<int32_t> host_member_scores;
-    spm_jst_collapse_stats stats{};
-};
 
 extern "C" void spm_hip_jst_ref_loci_destroy(spm_jst_ref_loci *l)
 {

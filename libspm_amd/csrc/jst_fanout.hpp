@@ -1,25 +1,15 @@
 // jst_fanout.hpp -- from what was found in the context buffer of a pan-genome index to one record per haplotype that shares
-// the context (scheme in jst.hpp).  gfx950.  The context tables of the index as one set, the body the two
-// fan-out kernels share, and the kernels: jst_fanout_kernel (segment hits -> spm_jst_hit, behind every search) and
-// jst_aln_fanout_kernel (segment alignments -> spm_jst_aln, spm_hip_jst_hits_align).
+// the context (scheme in jst.hpp).  gfx950.  The body the two fan-out kernels share (jst_fan_out) and what
+// it reads an item as.  The kernels sit with their launches, each in its unit: jst_fanout_kernel (segment hits -> spm_jst_hit,
+// behind every search) in jst_search.hpp, jst_aln_fanout_kernel (segment alignments -> spm_jst_aln) in jst_hits_align.hpp.
 #pragma once
 
+#include "jst_ctx_tables.hpp"
 #include "jst_walk_core.hpp"
 #include "wave.hpp"
 
 namespace spm_hip
 {
-
-// The context tables of an index (spm_jst::ctx_tables()): written by the build (jst_index.hpp), read by everything behind it.
-struct jst_ctx_tables
-{
-    uint64_t *ctx_off;         // [n_ctx + 1] where context c starts in the context buffer; row n_ctx = its length
-    uint64_t n_ctx;
-    uint32_t *ctx_block;       // [n_ctx] (block - jb, haplotype group) cell of the context
-    uint32_t *ctx_owned;       // [n_ctx] offset of the first owned symbol
-    const uint64_t *ctx_base;  // [cells + 1] exclusive scan of the cells' context counts
-    const uint16_t *local_id;  // [(je - jb) * n_hap]: context of the haplotype inside its cell | 0x8000 for the representative
-};
 
 // the context ids of 8 consecutive haplotypes of one block: one 16-byte load when the row allows it
 __device__ __forceinline__ void jst_load_ids8(const uint16_t *p, uint32_t n_valid, uint16_t (&v)[8])
@@ -123,93 +113,4 @@ __device__ __forceinline__ void jst_fan_out(const jst_dev &J, const jst_ctx_tabl
     }
 }
 
-struct jst_fan_params
-{
-    const spm_hit *hits;
-    uint64_t n_hits;                         // segment hits, if the host knows their number ...
-    const unsigned long long *n_hits_dev;    // ... else where the scan counts them (launched before the host has read it)
-    uint64_t hit_cap;                        //     and the capacity of `hits`
-    jst_ctx_tables T;
-    const int32_t *m; // needle lengths
-    uint32_t report_begin;
-    spm_jst_hit *out;
-    unsigned long long *out_count;
-    uint64_t out_cap;
-};
-
-// One thread per segment hit: drop it if its last symbol lies in the left context, else report it for every haplotype
-// of the context's group, in haplotype coordinates.  Output slots are drawn with one atomic per wave (a per-record
-// atomic on the single counter cost 0.6 ms for 10^6 records).
-__global__ void jst_fanout_kernel(jst_dev J, jst_fan_params F)
-{
-    uint64_t n_hits = F.n_hits;
-    if (F.n_hits_dev) {
-        const unsigned long long n = *F.n_hits_dev;
-        n_hits = n < F.hit_cap ? n : F.hit_cap;
-    }
-    jst_fan_out<spm_hit>(
-        J, F.T, n_hits, F.out_count, F.out_cap,
-        [&](uint64_t t, spm_hit &hit, jst_fan_item &it) {
-            hit = F.hits[t];
-            it.probe = F.report_begin ? hit.pos : hit.pos - 1;
-            it.last = F.report_begin ? hit.pos + (uint64_t)F.m[hit.pattern] - 1 : hit.pos - 1;
-            it.at = hit.pos;
-            return true;
-        },
-        [&](const spm_hit &hit, unsigned long long slot, uint32_t h, uint64_t ctx_lo, uint64_t local) {
-            spm_jst_hit o;
-            o.pos = ctx_lo + local;
-            o.haplotype = h;
-            o.pattern = hit.pattern;
-            o.score = hit.score;
-            o.reserved = 0;
-            F.out[slot] = o;
-        });
-}
-
-struct jst_alnfan_params
-{
-    const spm_aln *segs; // one alignment per segment hit, context-buffer coordinates (stage A / stage B of align.hpp)
-    uint64_t n_segs;
-    jst_ctx_tables T;
-    spm_jst_aln *out;
-    unsigned long long *out_count;
-    uint64_t out_cap;
-};
-
-// The alignment fan-out: one thread per segment alignment.  It is dropped if its last symbol lies in the left context; else
-// every haplotype of the context's group gets a record with its own coordinates and the SHARED transcript (cigar_off /
-// cigar_len of the segment alignment).
-__global__ __launch_bounds__(256) void jst_aln_fanout_kernel(jst_dev J, jst_alnfan_params F)
-{
-    jst_fan_out<spm_aln>(
-        J, F.T, F.n_segs, F.out_count, F.out_cap,
-        [&](uint64_t t, spm_aln &al, jst_fan_item &it) {
-            al = F.segs[t];
-            it.probe = it.last = al.end - 1; // the alignment's last symbol: a symbol of its own context
-            it.at = al.end;
-            it.span = al.end - al.begin;
-            return al.end > 0 && al.begin <= al.end;
-        },
-        [&](const spm_aln &al, unsigned long long slot, uint32_t h, uint64_t ctx_lo, uint64_t local_end) {
-            spm_jst_aln o;
-            o.end = ctx_lo + local_end;
-            o.begin = o.end - (al.end - al.begin);
-            o.haplotype = h;
-            o.pattern = al.pattern;
-            o.score = al.score;
-            o.cigar_off = al.cigar_off;
-            o.cigar_len = al.cigar_len;
-            o.reserved = 0;
-            F.out[slot] = o;
-        });
-}
-
 } // namespace spm_hip
-
-void spm_warm_jst_kernels()
-{
-    hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, (const void *)spm_hip::jst_fanout_kernel);
-    (void)hipFuncGetAttributes(&a, (const void *)spm_hip::jst_aln_fanout_kernel);
-}

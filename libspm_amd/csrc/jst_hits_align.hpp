@@ -1,25 +1,56 @@
 // jst_hits_align.hpp -- begins and alignments of the hits of a pan-genome search (spm_hip_jst_hits_align; contract in
 // spm_hip.h, scheme in DESIGN.md 4.6), the result object spm_jst_alns, and what the call shares with
 // spm_hip_jst_selection_align (jst_locate.hpp): jst_align_segments (distinct segment hits -> their alignments on the device)
-// and jst_alns_download / jst_alns_close (host view, statistics).  gfx950.  Included by jst.hip behind jst.hpp: it needs spm_jst.
+// and jst_alns_download / jst_alns_close (host view, statistics).  gfx950.  Unit: jst_align.hip.  The fan-out of the
+// alignments, jst_aln_fanout_kernel, is here, over the walker of jst_fanout.hpp.
 #pragma once
 
-struct spm_jst_alns
+#include "internal.hpp"
+#include "jst_fanout.hpp"
+#include "jst_handles.hpp"
+
+namespace spm_hip
 {
-    spm_ctx *ctx = nullptr;
-    spm_jst_aln *d_recs = nullptr; // arrival order of the fan-out
-    uint32_t *d_ops = nullptr;
-    uint64_t n = 0, n_ops = 0;
-    std::vector<spm_jst_aln> host; // (haplotype, pos, pattern): the order of spm_hip_jst_hits_view
-    std::vector<uint32_t> host_ops;
-    spm_jst_align_stats stats{};
-    // what spm_hip_jst_alns_project needs to know about the call that made these alignments (jst_project.hpp): the tree and
-    // its index generation, the needle set, and whether there are transcripts at all
-    spm_jst *jst = nullptr;
-    const spm_patterns *patterns = nullptr;
-    uint64_t generation = 0;
-    bool begin_only = false;
+
+struct jst_alnfan_params
+{
+    const spm_aln *segs; // one alignment per segment hit, context-buffer coordinates (stage A / stage B of align.hpp)
+    uint64_t n_segs;
+    jst_ctx_tables T;
+    spm_jst_aln *out;
+    unsigned long long *out_count;
+    uint64_t out_cap;
 };
+
+// The alignment fan-out: one thread per segment alignment.  It is dropped if its last symbol lies in the left context; else
+// every haplotype of the context's group gets a record with its own coordinates and the SHARED transcript (cigar_off /
+// cigar_len of the segment alignment).
+__global__ __launch_bounds__(256) void jst_aln_fanout_kernel(jst_dev J, jst_alnfan_params F)
+{
+    jst_fan_out<spm_aln>(
+        J, F.T, F.n_segs, F.out_count, F.out_cap,
+        [&](uint64_t t, spm_aln &al, jst_fan_item &it) {
+            al = F.segs[t];
+            it.probe = it.last = al.end - 1; // the alignment's last symbol: a symbol of its own context
+            it.at = al.end;
+            it.span = al.end - al.begin;
+            return al.end > 0 && al.begin <= al.end;
+        },
+        [&](const spm_aln &al, unsigned long long slot, uint32_t h, uint64_t ctx_lo, uint64_t local_end) {
+            spm_jst_aln o;
+            o.end = ctx_lo + local_end;
+            o.begin = o.end - (al.end - al.begin);
+            o.haplotype = h;
+            o.pattern = al.pattern;
+            o.score = al.score;
+            o.cigar_off = al.cigar_off;
+            o.cigar_len = al.cigar_len;
+            o.reserved = 0;
+            F.out[slot] = o;
+        });
+}
+
+} // namespace spm_hip
 
 extern "C" void spm_hip_jst_alns_destroy(spm_jst_alns *a)
 {

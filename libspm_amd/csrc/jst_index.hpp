@@ -1,5 +1,5 @@
-// jst_index.hpp -- building the pan-genome index (spm_hip_jst_index; scheme in jst.hpp).  gfx950.  Included by
-// jst.hip behind jst.hpp: it needs spm_jst.  What a cell owns and what its context spells is jst_walk_core.hpp's; the kernels
+// jst_index.hpp -- building the pan-genome index (spm_hip_jst_index; scheme in jst.hpp).  gfx950.  Unit:
+// jst.hip.  What a cell owns and what its context spells is jst_walk_core.hpp's; the kernels
 // here only spread those functions over the cells.  The build, stage by stage:
 //   starts   a_lo, the cells' length deltas, their column-wise prefix, hap_start            (synchronises: errors surface here)
 //   group    the haplotypes of every (block, haplotype group) cell grouped by context signature (jst_dedupe_kernel)
@@ -10,6 +10,10 @@
 #pragma once
 
 #include <hipcub/hipcub.hpp>
+
+#include "internal.hpp"
+#include "jst_handles.hpp"
+#include "wave.hpp"
 
 namespace spm_hip
 {

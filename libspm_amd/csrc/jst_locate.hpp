@@ -1,5 +1,5 @@
 // jst_locate.hpp -- begins and alignments of the records a pan-genome SELECTION kept (spm_hip_jst_selection_align; contract
-// in spm_hip.h, scheme in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_hits_align.hpp: it needs spm_jst and spm_jst_alns.
+// in spm_hip.h, scheme in DESIGN.md 4.6).  gfx950.  Unit: jst_align.hip, with jst_hits_align.hpp, whose host helpers it calls.
 //
 // jst_fanout_kernel is a bijection from (segment hit ending on an owned symbol, member haplotype of its context) to
 // haplotype record.  A selection keeps records, not segment hits, so the map is inverted per kept record from the tables of
@@ -22,6 +22,11 @@
 // count of the flagged lanes is wave.hpp's.
 #pragma once
 
+#include "internal.hpp"
+#include "device_order.hpp"
+#include "jst_handles.hpp"
+#include "jst_hits_align.hpp"
+#include "scratch_layout.hpp"
 #include "select_plan.hpp"
 #include "wave.hpp"
 

@@ -1,6 +1,6 @@
 // jst_normalize.hpp -- projected pan-genome alignments with every gap run at its leftmost equivalent place
-// (spm_hip_jst_ref_alns_normalize; contract in spm_hip.h, scheme in DESIGN.md 4.6c).  gfx950.  Included by jst.hip behind
-// jst_project.hpp: it needs spm_jst_ref_alns.
+// (spm_hip_jst_ref_alns_normalize; contract in spm_hip.h, scheme in DESIGN.md 4.6c).  gfx950.  Unit: jst_ref.hip.  It reads
+// and makes a spm_jst_ref_alns (jst_handles.hpp).
 //
 // Records that share a transcript slot share needle, reference range and words, so the rule is applied once per distinct slot
 // of the source pool and gathered:
@@ -18,9 +18,14 @@
 // transcript_slots.hpp's.  Every needle, reference and pool index is tested against its size before it is read.
 #pragma once
 
+#include "internal.hpp"
+#include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_normalize_core.hpp"
+#include "scratch_layout.hpp"
+#include "transcript_slots.hpp"
+#include "wave.hpp"
 
-static_assert(sizeof(spm_jst_normalize_stats) == 96, "C ABI layout");
 static_assert(SPM_CIGAR_INS == spm_hip::kNormIns && SPM_CIGAR_DEL == spm_hip::kNormDel && SPM_CIGAR_EQ == spm_hip::kNormEq &&
                   SPM_CIGAR_X == spm_hip::kNormX, "the core header's op values are the ABI's");
 

@@ -1,5 +1,5 @@
 // jst_pairs.hpp -- the mates of paired-end reads (spm_hip_jst_ref_loci_pairs; contract in spm_hip.h, scheme in DESIGN.md 4.9,
-// the rule in jst_pairs_core.hpp).  gfx950.  Included by jst.hip behind jst_reads.hpp, whose spm_jst_reads it reads.  The
+// the rule in jst_pairs_core.hpp).  gfx950.  Unit: jst_reads.hip.  It reads the loci and the read summary (jst_handles.hpp).  The
 // loci of pair p are the contiguous patterns 4p .. 4p + 3, and the read summary holds the bounds of the four
 // sub-runs, so pairing is a walk of a window of the other mate's reverse run, found by a lower bound:
 //   jst_pairs_best_kernel   one lane per locus.  A lane on a forward locus a walks its partner window, keeps its best partner
@@ -18,8 +18,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "internal.hpp"
 #include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_pairs_core.hpp"
 #include "scratch_layout.hpp"
 #include "wave.hpp"
@@ -190,12 +191,6 @@ __global__ __launch_bounds__(256) void jst_pairs_emit_kernel(const jst_pairs_par
 }
 
 } // namespace spm_hip
-
-struct spm_jst_pairs : spm_hip::device_records<spm_jst_pair, spm_jst_pairs_stats>
-{
-};
-static_assert(sizeof(spm_jst_pair_opts) == 16 && sizeof(spm_jst_pair) == 32 && sizeof(spm_jst_pairs_stats) == 72,
-              "spm_hip.h states these sizes");
 
 extern "C" void spm_hip_jst_pairs_destroy(spm_jst_pairs *p) { spm_jst_pairs::destroy(p); }
 

@@ -1,6 +1,6 @@
 // jst_project.hpp -- pan-genome alignments in reference coordinates (spm_hip_jst_alns_project; contract in spm_hip.h, scheme
-// in DESIGN.md 4.6).  gfx950.  Included by jst.hip behind jst_locate.hpp (it needs spm_jst, spm_jst_alns and jst_walk_core.hpp's jst_first_ref)
-// and transcript_slots.hpp (the slot stage it begins with).
+// in DESIGN.md 4.6).  gfx950.  Unit: jst_ref.hip.  It reads spm_jst and spm_jst_alns (jst_handles.hpp), walks with
+// jst_walk_core.hpp's jst_first_ref and begins with the slot stage of transcript_slots.hpp.
 //
 // Records that share a transcript slot share a context: they carry the same alleles over it and lie on the same reference
 // positions.  So the projection is computed once per distinct slot of the source pool and gathered:
@@ -17,9 +17,14 @@
 // carried deletion ends inside its block nor that begin and end lie in the same block.
 #pragma once
 
+#include "internal.hpp"
+#include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_project_core.hpp"
+#include "scratch_layout.hpp"
+#include "transcript_slots.hpp"
+#include "wave.hpp"
 
-static_assert(sizeof(spm_jst_ref_aln) == 40 && sizeof(spm_jst_project_stats) == 64, "C ABI layout");
 static_assert(SPM_CIGAR_INS == spm_hip::kProjIns && SPM_CIGAR_DEL == spm_hip::kProjDel && SPM_CIGAR_EQ == spm_hip::kProjEq &&
                   SPM_CIGAR_X == spm_hip::kProjX, "the core header's op values are the ABI's");
 
@@ -187,25 +192,6 @@ __global__ __launch_bounds__(256) void jst_proj_gather_kernel(const jst_project_
 }
 
 } // namespace spm_hip
-
-struct spm_jst_ref_alns
-{
-    spm_ctx *ctx = nullptr;
-    spm_jst_ref_aln *d_recs = nullptr; // record i belongs to record i of the source's device view
-    uint32_t *d_ops = nullptr;
-    uint64_t n = 0, n_ops = 0;
-    std::vector<spm_jst_ref_aln> host; // record i belongs to record i of the source's host view
-    std::vector<uint32_t> host_ops;
-    spm_jst_project_stats stats{};
-    uint32_t n_patterns = 0; // what spm_hip_jst_ref_alns_collapse plans its keys from: the needles of the set ...
-    uint64_t n_ref = 0;      // ... and the reference length (the collapse reads neither tree nor set)
-    // what spm_hip_jst_ref_alns_normalize reads: the tree (its reference text) and the needle set behind these records --
-    // host bookkeeping only; both must be alive during that call, not after it
-    spm_jst *jst = nullptr;
-    const spm_patterns *patterns = nullptr;
-    bool normalized = false; // made by spm_hip_jst_ref_alns_normalize, which then filled norm_stats
-    spm_jst_normalize_stats norm_stats{};
-};
 
 extern "C" void spm_hip_jst_ref_alns_destroy(spm_jst_ref_alns *a)
 {

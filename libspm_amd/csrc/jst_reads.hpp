@@ -1,5 +1,5 @@
 // jst_reads.hpp -- the loci of every read (spm_hip_jst_ref_loci_reads; contract in spm_hip.h, scheme in DESIGN.md 4.8, the
-// rule in jst_reads_core.hpp).  gfx950.  Included by jst.hip behind jst_collapse.hpp, whose spm_jst_ref_loci it reads.
+// rule in jst_reads_core.hpp).  gfx950.  Unit: jst_reads.hip.  It reads the collapse's spm_jst_ref_loci (jst_handles.hpp).
 // The loci of a collapse are ordered by pattern, so the loci of one read are one contiguous run.  Work is proportional to
 // loci + reads, and a read with 10^5 loci is 10^5 lanes, not a loop:
 //   jst_reads_min_kernel    one lane per locus: the segmented scan over the wave (wave_run_scan of wave.hpp, here over a
@@ -16,8 +16,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "internal.hpp"
 #include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_reads_core.hpp"
 #include "scratch_layout.hpp"
 #include "wave.hpp"
@@ -162,13 +163,6 @@ __global__ __launch_bounds__(256) void jst_reads_emit_kernel(const jst_reads_par
 }
 
 } // namespace spm_hip
-
-struct spm_jst_reads : spm_hip::device_records<spm_jst_read, spm_jst_reads_stats>
-{
-    uint32_t strands = 1; // what the summary was made with, and from how many loci (spm_hip_jst_ref_loci_pairs asks)
-    uint64_t n_loci = 0;
-};
-static_assert(sizeof(spm_jst_read) == 32 && sizeof(spm_jst_reads_stats) == 48, "spm_hip.h states these sizes");
 
 extern "C" void spm_hip_jst_reads_destroy(spm_jst_reads *r) { spm_jst_reads::destroy(r); }
 

@@ -1,5 +1,5 @@
 // jst_rescue.hpp -- mate rescue (spm_hip_jst_pairs_rescue; contract in spm_hip.h, scheme in DESIGN.md 4.10, the rule in
-// jst_rescue_core.hpp).  gfx950.  Included by jst.hip behind jst_pairs.hpp, whose spm_jst_pairs it reads.
+// jst_rescue_core.hpp).  gfx950.  Unit: jst_reads.hip.  It reads the loci, the read summary and the pairs (jst_handles.hpp).
 //   jst_rescue_jobs_kernel<kEmit>   one lane per pair: reads the pair record, both read records and the anchor loci, tests
 //                                   them (jst_rescue_pair_ok: every index before it is one) and, first, counts the pair's 0, 1
 //                                   or 2 jobs; an exclusive sum later, the same lanes write the job descriptors in pair order;
@@ -19,8 +19,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "internal.hpp"
 #include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_rescue_core.hpp"
 #include "scratch_layout.hpp"
 #include "wave.hpp"
@@ -212,15 +213,6 @@ template <int NW> hipError_t rescue_search_launch(spm_ctx *ctx, const jst_rescue
 }
 
 } // namespace spm_hip
-
-struct spm_jst_rescues : spm_hip::device_records<spm_jst_rescue, spm_jst_rescues_stats>
-{
-    uint32_t *d_ops = nullptr;
-    uint64_t n_ops = 0;
-    std::vector<uint32_t> host_ops;
-};
-static_assert(sizeof(spm_jst_rescue_opts) == 20 && sizeof(spm_jst_rescue) == 48 && sizeof(spm_jst_rescues_stats) == 80,
-              "spm_hip.h states these sizes");
 
 extern "C" void spm_hip_jst_rescues_destroy(spm_jst_rescues *r)
 {

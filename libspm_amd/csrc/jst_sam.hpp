@@ -1,5 +1,5 @@
 // jst_sam.hpp -- SAM lines and MAPQ (spm_hip_jst_ref_loci_sam; contract in spm_hip.h, scheme in DESIGN.md 4.11, the rule in
-// jst_sam_core.hpp).  gfx950.  Included by jst.hip behind jst_rescue.hpp, whose handles it reads.
+// jst_sam_core.hpp).  gfx950.  Unit: jst_sam.hip.  It reads the handles of the loci, reads, pairs and rescues (jst_handles.hpp).
 //   jst_sam_first_rescue_kernel   one lane per rescue record: the ordering test against the record before it, and the first
 //                                 record of every pair scattered into first_rescue[pair];
 //   jst_sam_lines_kernel<kEmit>   one lane per read: the agreement tests, the reported line of the read (both mates of a pair
@@ -18,8 +18,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "internal.hpp"
 #include "device_order.hpp"
+#include "jst_handles.hpp"
 #include "jst_sam_core.hpp"
 #include "scratch_layout.hpp"
 #include "wave.hpp"
@@ -276,19 +277,7 @@ struct sam_len_op
 
 } // namespace spm_hip
 
-struct spm_sam
-{
-    spm_ctx *ctx = nullptr;
-    char *d_text = nullptr;
-    spm_sam_line *d_lines = nullptr;
-    uint64_t n_bytes = 0, n_lines = 0;
-    bool have_host = false; // the views are downloaded when first asked for
-    std::vector<char> host_text;
-    std::vector<spm_sam_line> host_lines;
-    spm_sam_stats stats{};
-};
-static_assert(sizeof(spm_sam_opts) == 64 && sizeof(spm_sam_line) == 24 && sizeof(spm_sam_stats) == 72 && sizeof(spm_hip::jst_sam_aux) == 24,
-              "spm_hip.h states these sizes");
+static_assert(sizeof(spm_hip::jst_sam_aux) == 24, "spm_hip.h states this size");
 
 extern "C" void spm_hip_sam_destroy(spm_sam *s)
 {

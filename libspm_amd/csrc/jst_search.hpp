@@ -1,7 +1,61 @@
 // jst_search.hpp -- the pan-genome search (spm_hip_jst_search) and the accessors of its records (scheme in jst.hpp, DESIGN.md
-// 4.5).  gfx950.  Included by jst.hip behind jst.hpp: it needs spm_jst.  Search = the segmented scan of the context buffer by
-// the ordinary engines + jst_fanout_kernel (jst_fanout.hpp).
+// 4.5).  gfx950.  Unit: jst.hip.  Search = the segmented scan of the context buffer by the ordinary engines +
+// jst_fanout_kernel, here, over the walker of jst_fanout.hpp.
 #pragma once
+
+#include "internal.hpp"
+#include "jst_fanout.hpp"
+#include "jst_handles.hpp"
+#include "scratch_layout.hpp"
+
+namespace spm_hip
+{
+
+struct jst_fan_params
+{
+    const spm_hit *hits;
+    uint64_t n_hits;                         // segment hits, if the host knows their number ...
+    const unsigned long long *n_hits_dev;    // ... else where the scan counts them (launched before the host has read it)
+    uint64_t hit_cap;                        //     and the capacity of `hits`
+    jst_ctx_tables T;
+    const int32_t *m; // needle lengths
+    uint32_t report_begin;
+    spm_jst_hit *out;
+    unsigned long long *out_count;
+    uint64_t out_cap;
+};
+
+// One thread per segment hit: drop it if its last symbol lies in the left context, else report it for every haplotype
+// of the context's group, in haplotype coordinates.  Output slots are drawn with one atomic per wave (a per-record
+// atomic on the single counter cost 0.6 ms for 10^6 records).
+__global__ void jst_fanout_kernel(jst_dev J, jst_fan_params F)
+{
+    uint64_t n_hits = F.n_hits;
+    if (F.n_hits_dev) {
+        const unsigned long long n = *F.n_hits_dev;
+        n_hits = n < F.hit_cap ? n : F.hit_cap;
+    }
+    jst_fan_out<spm_hit>(
+        J, F.T, n_hits, F.out_count, F.out_cap,
+        [&](uint64_t t, spm_hit &hit, jst_fan_item &it) {
+            hit = F.hits[t];
+            it.probe = F.report_begin ? hit.pos : hit.pos - 1;
+            it.last = F.report_begin ? hit.pos + (uint64_t)F.m[hit.pattern] - 1 : hit.pos - 1;
+            it.at = hit.pos;
+            return true;
+        },
+        [&](const spm_hit &hit, unsigned long long slot, uint32_t h, uint64_t ctx_lo, uint64_t local) {
+            spm_jst_hit o;
+            o.pos = ctx_lo + local;
+            o.haplotype = h;
+            o.pattern = hit.pattern;
+            o.score = hit.score;
+            o.reserved = 0;
+            F.out[slot] = o;
+        });
+}
+
+} // namespace spm_hip
 
 extern "C" void spm_hip_jst_hits_destroy(spm_jst_hits *h)
 {

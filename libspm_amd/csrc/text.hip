@@ -93,8 +93,13 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
     spm_warm_filter_kernels();
     spm_warm_hits_kernels();
     spm_warm_jst_kernels();
+    spm_warm_jst_align_kernels();
+    spm_warm_jst_ref_kernels();
+    spm_warm_jst_reads_kernels();
+    spm_warm_jst_sam_kernels();
     spm_warm_align_kernels();
     spm_warm_bgzf_kernels();
+    spm_warm_device_order_kernels(ctx.get());
     *out = ctx.release();
     return SPM_OK;
 }

@@ -1,7 +1,7 @@
 // transcript_slots.hpp -- the distinct transcript slots of a "records + CIGAR pool" object, numbered in pool order.  gfx950.
-// Included by jst.hip ahead of jst_project.hpp, jst_normalize.hpp and jst_collapse.hpp, which all begin with this stage: the
-// collapse is right only if it numbers the slots of the projection's records the way the projection numbered its own, so the
-// stage is written once.
+// Unit: jst_ref.hip, where jst_project.hpp, jst_normalize.hpp and jst_collapse.hpp include it: all three begin with this
+// stage, and the collapse is right only if it numbers the slots of the projection's records the way the projection numbered
+// its own, so the stage is written once and its two kernels that are no templates are compiled once.
 //   slot_rep_kernel      one lane per record: atomicMin of the record index into rep[cigar_off] -- the smallest record index
 //                        represents its slot; a record its caller's predicate calls unusable is counted, not entered
 //   (hipcub exclusive sum of rep[w] != none over the pool: the number of every slot, in pool order)

@@ -7,7 +7,8 @@ The listings are taken in pairs, but kernels are matched by mangled name across 
 kernel may move from one unit to another.  (Where a unit was split, name the parent's listing once per child listing: a
 file given twice counts once.)  Per kernel the
 comparison drops comments and debug directives and renames local labels (.LBB3_7, .Ltmp12, ..) in order of appearance,
-since their numbers depend on what else the unit holds.  It prints one line per kernel: `identical`, or the instruction
+since their numbers depend on what else the unit holds; for the same reason an unnamed string constant (.str.9) is compared
+by what it holds, not by its number.  It prints one line per kernel: `identical`, or the instruction
 counts parent -> child, VGPR, SGPR, LDS, scratch and the lines removed / added.  Exit status 1 if any kernel differs or is
 missing on either side."""
 import difflib
@@ -20,6 +21,12 @@ from kernel_regs import demangled, kernel_table  # noqa: E402
 
 _DEBUG = re.compile(r"\.(loc|file|cfi_\w+|ident|addrsig\w*)\b")
 _LABEL = re.compile(r"\.L[\w$.]+")
+_STRING = re.compile(r"(?<![\w.])\.str(?:\.\d+)?(?![\w.])")
+
+
+def string_constants(txt):
+    """{symbol: its directive} of the unit's unnamed string constants (.str, .str.1, ..): numbered like the local labels."""
+    return dict(re.findall(r"^(\.str(?:\.\d+)?):\n\s*(\.asci[iz]\s.*)$", txt, re.M))
 
 
 def kernel_body(txt, name):
@@ -27,11 +34,12 @@ def kernel_body(txt, name):
     m = re.search(rf"^{re.escape(name)}:.*?$(.*?)^(\.Lfunc_end\d+:|\s*\.amdhsa_kernel )", txt, re.S | re.M)
     if not m:
         return None
-    lines, labels = [], {}
+    lines, labels, strings = [], {}, string_constants(txt)
     for line in m.group(1).split("\n"):
         line = line.split(";")[0].strip()
         if not line or _DEBUG.match(line):
             continue
+        line = _STRING.sub(lambda s: "{" + strings.get(s.group(0), s.group(0)) + "}", line)  # the constant for its number
         lines.append(_LABEL.sub(lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), line))
     return lines
 

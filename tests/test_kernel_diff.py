@@ -51,6 +51,18 @@ def test_label_names_comments_and_debug_lines_do_not_count():
     assert text.count(": identical") == 2
 
 
+def test_string_constants_count_by_what_they_hold_not_by_their_number():
+    # a kernel that moved to a smaller unit: its string constant has another number there; another string is a difference
+    def with_string(sym, text):
+        body = _body(".LBB0_1", 2)[:-1] + [f"\ts_add_u32 s0, s0, {sym}@rel32@lo+4", "\ts_endpgm"]
+        rodata = f"\t.type\t{sym},@object\n{sym}:\n\t.asciz\t\"{text}\"\n\t.size\t{sym}, {len(text) + 1}\n"
+        return _listing([(A[0], body, 3)]) + ".str:\n\t.asciz\t\"other\"\n" * (sym != ".str") + rodata
+    n, bad, text = _run(with_string(".str.9", "\\tNM:i:"), with_string(".str", "\\tNM:i:"))
+    assert (n, bad) == (1, 0), text
+    n, bad, text = _run(with_string(".str.9", "\\tNM:i:"), with_string(".str", "\\tMD:Z:"))
+    assert (n, bad) == (1, 1) and "-1 / +1 lines" in text, text
+
+
 def test_one_changed_instruction_is_reported_for_its_kernel_alone():
     child = _listing([(A[0], _body(".LBB0_1", 2), 3), (A[1], _body(".LBB1_1", 5), 4)])
     n, bad, text = _run(PARENT, child)
