@@ -249,10 +249,6 @@ class JstRescue(C.Structure):
                 ("tlen", C.c_int32), ("flag", C.c_uint16), ("status", C.c_uint16)]
 
 
-# the numpy view of JstRescue (spm_jst_rescue, 48 bytes)
-JST_RESCUE_DTYPE = [("ref_begin", "<u8"), ("ref_end", "<u8"), ("pair", "<u4"), ("pattern", "<u4"), ("anchor", "<u4"),
-                    ("score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("tlen", "<i4"), ("flag", "<u2"),
-                    ("status", "<u2")]
 RESCUE_RESCUED, RESCUE_NONE, RESCUE_NOT_CONCORDANT = 0, 1, 2
 
 
@@ -285,9 +281,6 @@ class SamLine(C.Structure):
                 ("flag", C.c_uint16), ("mapq", C.c_uint8), ("kind", C.c_uint8)]
 
 
-# the numpy view of SamLine (spm_sam_line, 24 bytes)
-SAM_LINE_DTYPE = [("offset", "<u8"), ("len", "<u4"), ("read", "<u4"), ("source", "<u4"), ("flag", "<u2"), ("mapq", "u1"),
-                  ("kind", "u1")]
 SAM_CIGAR_M, SAM_SECONDARY = 1, 2
 SAM_UNMAPPED, SAM_LOCUS, SAM_RESCUE, SAM_SECONDARY_LINE = 0, 1, 2, 3
 
@@ -406,6 +399,166 @@ SELECT_WINDOW_K = 0xFFFFFFFF
 CIGAR_INS, CIGAR_DEL, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8
 
 
+E_OVERFLOW = -5  # SPM_E_OVERFLOW: the caller's buffer is too small, and the length it needs has been written
+
+# (restype, argtypes) of every function that include/spm_hip.h declares: lib() binds these, EXPORTS names them
+_vp, _u8p, _u32p, _u16p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)
+SIGNATURES = {
+    "spm_hip_init": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
+    "spm_hip_destroy": (None, [_vp]),
+    "spm_hip_last_error": (C.c_char_p, [_vp]),
+    "spm_hip_synchronize": (C.c_int, [_vp]),
+    "spm_hip_text_upload": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_text_wrap": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_text_generate": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
+    "spm_hip_text_generate_repeats": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_text_pack": (C.c_int, [_vp, _vp]),
+    "spm_hip_text_is_packed": (C.c_int, [_vp]),
+    "spm_hip_text_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u8p]),
+    "spm_hip_text_length": (C.c_uint64, [_vp]),
+    "spm_hip_text_device_ptr": (_vp, [_vp]),
+    "spm_hip_text_destroy": (None, [_vp]),
+    "spm_hip_patterns_create": (C.c_int, [_vp, C.c_int, _u8p, _u32p, C.c_uint32, _u16p, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_patterns_create_stranded": (C.c_int, [_vp, C.c_int, _u8p, _u32p, C.c_uint32, _u16p, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_patterns_strands": (C.c_uint32, [_vp]),
+    "spm_hip_patterns_count": (C.c_uint32, [_vp]),
+    "spm_hip_patterns_needle": (C.c_int, [_vp, C.c_uint32, _u8p, C.c_uint32, _u32p]),
+    "spm_hip_patterns_destroy": (None, [_vp]),
+    "spm_hip_patterns_window_size": (C.c_uint64, [_vp, C.c_uint32]),
+    "spm_hip_patterns_filterable": (C.c_int, [_vp]),
+    "spm_hip_patterns_build_stats": (C.c_int, [_vp, C.POINTER(BuildStats)]),
+    "spm_hip_patterns_state_stride": (C.c_size_t, [_vp]),
+    "spm_hip_patterns_state_init": (C.c_int, [_vp, _vp]),
+    "spm_hip_scan": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(ScanOpts), _vp, _vp, C.POINTER(_vp)]),
+    "spm_hip_scan_segments": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.POINTER(ScanOpts),
+                                        C.POINTER(_vp)]),
+    "spm_hip_hits_view": (C.c_int, [_vp, C.POINTER(C.POINTER(Hit)), C.POINTER(C.c_uint64)]),
+    "spm_hip_hits_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_hits_copy_device": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_hits_copy_fused": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_hits_copy_fused_device": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "spm_hip_hits_stats": (C.c_int, [_vp, C.POINTER(ScanStats)]),
+    "spm_hip_hits_checksum": (C.c_uint64, [_vp]),
+    "spm_hip_hits_destroy": (None, [_vp]),
+    "spm_hip_hits_align": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_alns_view": (C.c_int, [_vp, C.POINTER(C.POINTER(Aln)), C.POINTER(C.c_uint64), C.POINTER(_u32p),
+                                    C.POINTER(C.c_uint64)]),
+    "spm_hip_alns_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_alns_stats": (C.c_int, [_vp, C.POINTER(AlignStats)]),
+    "spm_hip_alns_destroy": (None, [_vp]),
+    "spm_hip_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
+    "spm_hip_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
+    "spm_hip_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),
+    "spm_hip_synth_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, _u8p]),
+    "spm_hip_synth_repeat_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, _u8p]),
+    "spm_hip_synth_repeat_text": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _u8p]),
+    "spm_hip_mix64": (C.c_uint64, [C.c_uint64]),
+    "spm_hip_host_selftest": (C.c_int, [C.c_int, _u8p, _u32p, C.c_uint32, _u16p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "spm_hip_version": (C.c_char_p, []),
+    "spm_hip_jst_create": (C.c_int, [_vp, _vp, C.POINTER(JstAllele), C.c_uint64, _u8p, C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_destroy": (None, [_vp]),
+    "spm_hip_jst_haplotype_length": (C.c_uint64, [_vp, C.c_uint32]),
+    "spm_hip_jst_extract": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _u8p]),
+    "spm_hip_jst_index": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spm_hip_jst_search": (C.c_int, [_vp, _vp, C.POINTER(ScanOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_stats": (C.c_int, [_vp, C.POINTER(JstStats)]),
+    "spm_hip_jst_hits_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstHit)), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_hits_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_hits_copy_device": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_hits_destroy": (None, [_vp]),
+    "spm_hip_jst_hits_align": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_selection_align": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_alns_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstAln)), C.POINTER(C.c_uint64), C.POINTER(_u32p),
+                                        C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_alns_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp),
+                                          C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_alns_stats": (C.c_int, [_vp, C.POINTER(JstAlignStats)]),
+    "spm_hip_jst_alns_destroy": (None, [_vp]),
+    "spm_hip_jst_alns_project": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_ref_alns_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstRefAln)), C.POINTER(C.c_uint64), C.POINTER(_u32p),
+                                            C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_ref_alns_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp),
+                                              C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_ref_alns_stats": (C.c_int, [_vp, C.POINTER(JstProjectStats)]),
+    "spm_hip_jst_ref_alns_destroy": (None, [_vp]),
+    "spm_hip_jst_ref_alns_normalize": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_ref_alns_normalize_stats": (C.c_int, [_vp, C.POINTER(JstNormalizeStats)]),
+    "spm_hip_jst_ref_alns_collapse": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_ref_loci_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstRefLocus)), C.POINTER(C.c_uint64), C.POINTER(_u32p),
+                                            C.POINTER(C.c_uint64), C.POINTER(_u32p), C.POINTER(C.POINTER(C.c_int32)),
+                                            C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_ref_loci_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp),
+                                              C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_ref_loci_map": (C.c_int, [_vp, C.POINTER(_u32p), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_ref_loci_stats": (C.c_int, [_vp, C.POINTER(JstCollapseStats)]),
+    "spm_hip_jst_ref_loci_destroy": (None, [_vp]),
+    "spm_hip_jst_ref_loci_reads": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_jst_reads_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstRead)), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_reads_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_reads_stats": (C.c_int, [_vp, C.POINTER(JstReadsStats)]),
+    "spm_hip_jst_reads_destroy": (None, [_vp]),
+    "spm_hip_jst_ref_loci_pairs": (C.c_int, [_vp, _vp, C.POINTER(JstPairOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_pairs_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstPair)), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_pairs_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_pairs_stats": (C.c_int, [_vp, C.POINTER(JstPairsStats)]),
+    "spm_hip_jst_pairs_destroy": (None, [_vp]),
+    "spm_hip_jst_pairs_rescue": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(JstRescueOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_rescues_view": (C.c_int, [_vp, C.POINTER(C.POINTER(JstRescue)), C.POINTER(C.c_uint64), C.POINTER(_u32p),
+                                           C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_rescues_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_jst_rescues_stats": (C.c_int, [_vp, C.POINTER(JstRescuesStats)]),
+    "spm_hip_jst_rescues_destroy": (None, [_vp]),
+    "spm_hip_jst_ref_loci_sam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(SamOpts), C.POINTER(_vp)]),
+    "spm_hip_sam_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(SamLine)),
+                                   C.POINTER(C.c_uint64)]),
+    "spm_hip_sam_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_sam_stats": (C.c_int, [_vp, C.POINTER(SamStats)]),
+    "spm_hip_sam_destroy": (None, [_vp]),
+    "spm_hip_sam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_sam_mapq": (C.c_int, [C.POINTER(SamOpts), C.c_uint32, C.c_uint32]),
+    "spm_hip_jst_ref_loci_bam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BamOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.POINTER(SamLine)), C.POINTER(C.c_uint64)]),
+    "spm_hip_bam_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp),
+                                     C.POINTER(C.c_uint64)]),
+    "spm_hip_bam_stats": (C.c_int, [_vp, C.POINTER(BamStats)]),
+    "spm_hip_bam_destroy": (None, [_vp]),
+    "spm_hip_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_frame": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(_vp)]),
+    "spm_hip_bgzf_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_stats": (C.c_int, [_vp, C.POINTER(BgzfStats)]),
+    "spm_hip_bgzf_destroy": (None, [_vp]),
+    "spm_hip_bgzf_frame_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(BgzfOpts), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_framed_size": (C.c_int, [C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_deflate": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(_vp)]),
+    "spm_hip_bgzf_blocks": (C.c_int, [_vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_blocks_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_deflate_stats": (C.c_int, [_vp, C.POINTER(BgzfDeflateStats)]),
+    "spm_hip_bgzf_deflate_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_bgzf_deflate_bound": (C.c_int, [C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(C.c_uint64)]),
+    "spm_hip_bam_deflate": (C.c_int, [_vp, C.POINTER(BgzfDeflateOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),
+    "spm_hip_comm_unique_id": (C.c_int, [_vp]),
+    "spm_hip_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "spm_hip_comm_destroy": (None, [_vp]),
+    "spm_hip_gatherv_hits": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "spm_hip_gatherv_jst_hits": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64)]),
+    "spm_hip_gatherv_plan": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "spm_hip_comm_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_int)]),
+    "spm_hip_jst_synth_variants": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                             C.POINTER(JstAllele), C.POINTER(C.c_uint64), _u8p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+}
+EXPORTS = list(SIGNATURES)
+
+
 def build(force: bool = False) -> str:
     """Compile libspm_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".cpp"))]
@@ -428,206 +581,9 @@ def lib():
         raise SpmError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). libspm_amd has no CPU fallback.")
     L = C.CDLL(SO_PATH)
-    vp, u8p, u32p, u16p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)
-    sig = {
-        "spm_hip_init": (C.c_int, [C.c_int, vp, C.POINTER(vp)]),
-        "spm_hip_destroy": (None, [vp]),
-        "spm_hip_last_error": (C.c_char_p, [vp]),
-        "spm_hip_synchronize": (C.c_int, [vp]),
-        "spm_hip_text_upload": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_text_wrap": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_text_generate": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
-        "spm_hip_text_generate_repeats": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_text_pack": (C.c_int, [vp, vp]),
-        "spm_hip_text_is_packed": (C.c_int, [vp]),
-        "spm_hip_text_download": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u8p]),
-        "spm_hip_text_length": (C.c_uint64, [vp]),
-        "spm_hip_text_device_ptr": (vp, [vp]),
-        "spm_hip_text_destroy": (None, [vp]),
-        "spm_hip_patterns_create": (C.c_int, [vp, C.c_int, u8p, u32p, C.c_uint32, u16p, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_patterns_create_stranded": (C.c_int, [vp, C.c_int, u8p, u32p, C.c_uint32, u16p, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_patterns_strands": (C.c_uint32, [vp]),
-        "spm_hip_patterns_count": (C.c_uint32, [vp]),
-        "spm_hip_patterns_needle": (C.c_int, [vp, C.c_uint32, u8p, C.c_uint32, u32p]),
-        "spm_hip_patterns_destroy": (None, [vp]),
-        "spm_hip_patterns_window_size": (C.c_uint64, [vp, C.c_uint32]),
-        "spm_hip_patterns_filterable": (C.c_int, [vp]),
-        "spm_hip_patterns_build_stats": (C.c_int, [vp, C.POINTER(BuildStats)]),
-        "spm_hip_patterns_state_stride": (C.c_size_t, [vp]),
-        "spm_hip_patterns_state_init": (C.c_int, [vp, vp]),
-        "spm_hip_scan": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(ScanOpts), vp, vp, C.POINTER(vp)]),
-        "spm_hip_scan_segments": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.c_uint64, vp, C.POINTER(ScanOpts),
-                                            C.POINTER(vp)]),
-        "spm_hip_hits_view": (C.c_int, [vp, C.POINTER(C.POINTER(Hit)), C.POINTER(C.c_uint64)]),
-        "spm_hip_hits_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_hits_copy_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_hits_copy_fused": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_hits_copy_fused_device": (C.c_int, [vp, vp, C.c_uint64]),
-        "spm_hip_hits_stats": (C.c_int, [vp, C.POINTER(ScanStats)]),
-        "spm_hip_hits_checksum": (C.c_uint64, [vp]),
-        "spm_hip_hits_destroy": (None, [vp]),
-        "spm_hip_hits_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(Aln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
-                                        C.POINTER(C.c_uint64)]),
-        "spm_hip_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_alns_stats": (C.c_int, [vp, C.POINTER(AlignStats)]),
-        "spm_hip_alns_destroy": (None, [vp]),
-        "spm_hip_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
-        "spm_hip_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
-        "spm_hip_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
-        "spm_hip_synth_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
-                                               C.c_uint32, u8p]),
-        "spm_hip_synth_repeat_pattern": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                      C.c_uint32, C.c_uint32, C.c_uint32, u8p]),
-        "spm_hip_synth_repeat_text": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u8p]),
-        "spm_hip_mix64": (C.c_uint64, [C.c_uint64]),
-        "spm_hip_host_selftest": (C.c_int, [C.c_int, u8p, u32p, C.c_uint32, u16p, C.c_uint32, C.POINTER(C.c_uint64)]),
-        "spm_hip_version": (C.c_char_p, []),
-        "spm_hip_jst_create": (C.c_int, [vp, vp, C.POINTER(JstAllele), C.c_uint64, u8p, C.c_uint64,
-                                         C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_destroy": (None, [vp]),
-        "spm_hip_jst_haplotype_length": (C.c_uint64, [vp, C.c_uint32]),
-        "spm_hip_jst_extract": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint64, u8p]),
-        "spm_hip_jst_index": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
-        "spm_hip_jst_search": (C.c_int, [vp, vp, C.POINTER(ScanOpts), C.POINTER(vp)]),
-        "spm_hip_jst_stats": (C.c_int, [vp, C.POINTER(JstStats)]),
-        "spm_hip_jst_hits_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstHit)), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_hits_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_hits_copy_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_hits_destroy": (None, [vp]),
-        "spm_hip_jst_hits_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_selection_align": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstAln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
-                                            C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
-                                              C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_alns_stats": (C.c_int, [vp, C.POINTER(JstAlignStats)]),
-        "spm_hip_jst_alns_destroy": (None, [vp]),
-        "spm_hip_jst_alns_project": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_ref_alns_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRefAln)), C.POINTER(C.c_uint64), C.POINTER(u32p),
-                                                C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_ref_alns_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
-                                                  C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_ref_alns_stats": (C.c_int, [vp, C.POINTER(JstProjectStats)]),
-        "spm_hip_jst_ref_alns_destroy": (None, [vp]),
-        "spm_hip_jst_ref_alns_normalize": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_ref_alns_normalize_stats": (C.c_int, [vp, C.POINTER(JstNormalizeStats)]),
-        "spm_hip_jst_ref_alns_collapse": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_ref_loci_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRefLocus)), C.POINTER(C.c_uint64), C.POINTER(u32p),
-                                                C.POINTER(C.c_uint64), C.POINTER(u32p), C.POINTER(C.POINTER(C.c_int32)),
-                                                C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_ref_loci_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
-                                                  C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_ref_loci_map": (C.c_int, [vp, C.POINTER(u32p), C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_ref_loci_stats": (C.c_int, [vp, C.POINTER(JstCollapseStats)]),
-        "spm_hip_jst_ref_loci_destroy": (None, [vp]),
-        "spm_hip_jst_ref_loci_reads": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
-        "spm_hip_jst_reads_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRead)), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_reads_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_reads_stats": (C.c_int, [vp, C.POINTER(JstReadsStats)]),
-        "spm_hip_jst_reads_destroy": (None, [vp]),
-        "spm_hip_jst_ref_loci_pairs": (C.c_int, [vp, vp, C.POINTER(JstPairOpts), C.POINTER(vp)]),
-        "spm_hip_jst_pairs_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstPair)), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_pairs_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_pairs_stats": (C.c_int, [vp, C.POINTER(JstPairsStats)]),
-        "spm_hip_jst_pairs_destroy": (None, [vp]),
-        "spm_hip_jst_pairs_rescue": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(JstRescueOpts), C.POINTER(vp)]),
-        "spm_hip_jst_rescues_view": (C.c_int, [vp, C.POINTER(C.POINTER(JstRescue)), C.POINTER(C.c_uint64), C.POINTER(u32p),
-                                               C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_rescues_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_jst_rescues_stats": (C.c_int, [vp, C.POINTER(JstRescuesStats)]),
-        "spm_hip_jst_rescues_destroy": (None, [vp]),
-        "spm_hip_jst_ref_loci_sam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(SamOpts), C.POINTER(vp)]),
-        "spm_hip_sam_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(SamLine)),
-                                       C.POINTER(C.c_uint64)]),
-        "spm_hip_sam_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_sam_stats": (C.c_int, [vp, C.POINTER(SamStats)]),
-        "spm_hip_sam_destroy": (None, [vp]),
-        "spm_hip_sam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_sam_mapq": (C.c_int, [C.POINTER(SamOpts), C.c_uint32, C.c_uint32]),
-        "spm_hip_jst_ref_loci_bam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(BamOpts), C.POINTER(vp)]),
-        "spm_hip_bam_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64),
-                                       C.POINTER(C.POINTER(SamLine)), C.POINTER(C.c_uint64)]),
-        "spm_hip_bam_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp),
-                                         C.POINTER(C.c_uint64)]),
-        "spm_hip_bam_stats": (C.c_int, [vp, C.POINTER(BamStats)]),
-        "spm_hip_bam_destroy": (None, [vp]),
-        "spm_hip_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_frame": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(vp)]),
-        "spm_hip_bgzf_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_stats": (C.c_int, [vp, C.POINTER(BgzfStats)]),
-        "spm_hip_bgzf_destroy": (None, [vp]),
-        "spm_hip_bgzf_frame_host": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfOpts), vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_framed_size": (C.c_int, [C.c_uint64, C.POINTER(BgzfOpts), C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_deflate": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(vp)]),
-        "spm_hip_bgzf_blocks": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_blocks_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_deflate_stats": (C.c_int, [vp, C.POINTER(BgzfDeflateStats)]),
-        "spm_hip_bgzf_deflate_host": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-        "spm_hip_bgzf_deflate_bound": (C.c_int, [C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(C.c_uint64)]),
-        "spm_hip_bam_deflate": (C.c_int, [vp, C.POINTER(BgzfDeflateOpts), C.POINTER(vp)]),
-        "spm_hip_jst_hits_select": (C.c_int, [vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
-        "spm_hip_jst_records_select": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(SelectOpts), C.POINTER(vp)]),
-        "spm_hip_jst_hits_select_stats": (C.c_int, [vp, C.POINTER(SelectStats)]),
-        "spm_hip_comm_unique_id": (C.c_int, [vp]),
-        "spm_hip_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
-        "spm_hip_comm_destroy": (None, [vp]),
-        "spm_hip_gatherv_hits": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-        "spm_hip_gatherv_jst_hits": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64),
-                                               C.POINTER(C.c_uint64)]),
-        "spm_hip_gatherv_plan": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
-        "spm_hip_comm_selftest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_int)]),
-        "spm_hip_jst_synth_variants": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
-                                                 C.POINTER(JstAllele), C.POINTER(C.c_uint64), u8p,
-                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
     _lib = L
     return L
-
-
-EXPORTS = [
-    "spm_hip_init", "spm_hip_destroy", "spm_hip_last_error", "spm_hip_synchronize", "spm_hip_text_upload",
-    "spm_hip_text_wrap", "spm_hip_text_generate", "spm_hip_text_generate_repeats", "spm_hip_text_pack", "spm_hip_text_is_packed",
-    "spm_hip_text_download", "spm_hip_text_length",
-    "spm_hip_text_device_ptr", "spm_hip_text_destroy", "spm_hip_patterns_create", "spm_hip_patterns_destroy",
-    "spm_hip_patterns_create_stranded", "spm_hip_patterns_strands", "spm_hip_patterns_count", "spm_hip_patterns_needle",
-    "spm_hip_patterns_window_size", "spm_hip_patterns_filterable", "spm_hip_patterns_build_stats", "spm_hip_patterns_state_stride",
-    "spm_hip_patterns_state_init", "spm_hip_scan", "spm_hip_scan_segments", "spm_hip_hits_view", "spm_hip_hits_device",
-    "spm_hip_hits_copy_device", "spm_hip_hits_copy_fused", "spm_hip_hits_copy_fused_device", "spm_hip_hits_stats", "spm_hip_hits_checksum", "spm_hip_hits_destroy",
-    "spm_hip_hits_align", "spm_hip_alns_view", "spm_hip_alns_device", "spm_hip_alns_stats", "spm_hip_alns_destroy",
-    "spm_hip_hits_select", "spm_hip_records_select", "spm_hip_hits_select_stats",
-    "spm_hip_synth_pattern",
-    "spm_hip_synth_repeat_pattern", "spm_hip_synth_repeat_text", "spm_hip_mix64", "spm_hip_host_selftest", "spm_hip_version",
-    "spm_hip_jst_create", "spm_hip_jst_destroy", "spm_hip_jst_haplotype_length", "spm_hip_jst_extract",
-    "spm_hip_jst_index", "spm_hip_jst_search", "spm_hip_jst_stats", "spm_hip_jst_hits_view", "spm_hip_jst_hits_device",
-    "spm_hip_jst_hits_copy_device", "spm_hip_jst_hits_destroy", "spm_hip_jst_synth_variants",
-    "spm_hip_jst_hits_align", "spm_hip_jst_selection_align", "spm_hip_jst_alns_view", "spm_hip_jst_alns_device", "spm_hip_jst_alns_stats",
-    "spm_hip_jst_alns_destroy",
-    "spm_hip_jst_alns_project", "spm_hip_jst_ref_alns_view", "spm_hip_jst_ref_alns_device", "spm_hip_jst_ref_alns_stats",
-    "spm_hip_jst_ref_alns_destroy",
-    "spm_hip_jst_ref_alns_normalize", "spm_hip_jst_ref_alns_normalize_stats",
-    "spm_hip_jst_ref_alns_collapse", "spm_hip_jst_ref_loci_view", "spm_hip_jst_ref_loci_device", "spm_hip_jst_ref_loci_map",
-    "spm_hip_jst_ref_loci_stats", "spm_hip_jst_ref_loci_destroy",
-    "spm_hip_jst_ref_loci_reads", "spm_hip_jst_reads_view", "spm_hip_jst_reads_device", "spm_hip_jst_reads_stats",
-    "spm_hip_jst_reads_destroy",
-    "spm_hip_jst_ref_loci_pairs", "spm_hip_jst_pairs_view", "spm_hip_jst_pairs_device", "spm_hip_jst_pairs_stats",
-    "spm_hip_jst_pairs_destroy",
-    "spm_hip_jst_pairs_rescue", "spm_hip_jst_rescues_view", "spm_hip_jst_rescues_device", "spm_hip_jst_rescues_stats",
-    "spm_hip_jst_rescues_destroy",
-    "spm_hip_jst_ref_loci_sam", "spm_hip_sam_view", "spm_hip_sam_device", "spm_hip_sam_stats", "spm_hip_sam_destroy",
-    "spm_hip_sam_header", "spm_hip_sam_mapq",
-    "spm_hip_jst_ref_loci_bam", "spm_hip_bam_view", "spm_hip_bam_device", "spm_hip_bam_stats", "spm_hip_bam_destroy",
-    "spm_hip_bam_header",
-    "spm_hip_bgzf_frame", "spm_hip_bgzf_view", "spm_hip_bgzf_device", "spm_hip_bgzf_stats", "spm_hip_bgzf_destroy",
-    "spm_hip_bgzf_frame_host", "spm_hip_bgzf_framed_size",
-    "spm_hip_bgzf_deflate", "spm_hip_bgzf_blocks", "spm_hip_bgzf_blocks_device", "spm_hip_bgzf_deflate_stats",
-    "spm_hip_bgzf_deflate_host", "spm_hip_bgzf_deflate_bound", "spm_hip_bam_deflate",
-    "spm_hip_jst_hits_select", "spm_hip_jst_records_select", "spm_hip_jst_hits_select_stats",
-    "spm_hip_comm_unique_id", "spm_hip_comm_init", "spm_hip_comm_destroy", "spm_hip_gatherv_hits",
-    "spm_hip_gatherv_jst_hits", "spm_hip_gatherv_plan", "spm_hip_comm_selftest",
-]

@@ -12,9 +12,23 @@ import numpy as np
 
 from . import capi
 
-HIT_DTYPE = np.dtype([("pos", "<u8"), ("pattern", "<u4"), ("score", "<i4")])
-ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("pattern", "<u4"), ("score", "<i4"), ("cigar_off", "<u4"),
-                      ("cigar_len", "<u4")])
+
+def _dtype(struct) -> np.dtype:
+    """The numpy view of a record of the C ABI: capi's ctypes.Structure is the one statement of its layout."""
+    return np.dtype(struct)
+
+
+HIT_DTYPE = _dtype(capi.Hit)
+ALN_DTYPE = _dtype(capi.Aln)
+ALLELE_DTYPE = _dtype(capi.JstAllele)
+JST_HIT_DTYPE = _dtype(capi.JstHit)
+JST_ALN_DTYPE = _dtype(capi.JstAln)
+JST_REF_ALN_DTYPE = _dtype(capi.JstRefAln)
+JST_REF_LOCUS_DTYPE = _dtype(capi.JstRefLocus)
+JST_READ_DTYPE = _dtype(capi.JstRead)
+JST_PAIR_DTYPE = _dtype(capi.JstPair)
+JST_RESCUE_DTYPE = _dtype(capi.JstRescue)
+SAM_LINE_DTYPE = _dtype(capi.SamLine)
 _CIGAR_CHAR = {capi.CIGAR_INS: "I", capi.CIGAR_DEL: "D", capi.CIGAR_EQ: "=", capi.CIGAR_X: "X"}
 
 
@@ -22,6 +36,90 @@ def _check(rc, ctx_handle):
     if rc != 0:
         msg = capi.lib().spm_hip_last_error(ctx_handle)
         raise capi.SpmError(f"libspm_hip error {rc}: {msg.decode() if msg else ''}")
+
+
+def _as_array(ptr, n, ctype, dtype):
+    if n == 0:
+        return np.zeros(0, dtype=dtype)
+    buf = (ctype * n).from_address(C.addressof(ptr.contents))
+    return np.frombuffer(buf, dtype=dtype).copy()
+
+
+def _size_then_fill(call, refuse=lambda rc: _check(rc, None)) -> bytes:
+    """The bytes of a host-only call that writes into its caller's buffer: call(dst, cap, len) -> rc, once without a buffer,
+    which answers E_OVERFLOW and the length, then with a buffer of that length.  refuse(rc) raises for any other first
+    answer; where it returns (rc 0: there is nothing to write), the result is empty."""
+    need = C.c_uint64()
+    rc = call(None, 0, C.byref(need))
+    if rc != capi.E_OVERFLOW:
+        refuse(rc)
+        return b""
+    buf = C.create_string_buffer(need.value)
+    _check(call(buf, need.value, C.byref(need)), None)
+    return buf.raw[:need.value]
+
+
+def _block_data(block_data) -> int:
+    """the uncompressed bytes of a full BGZF block: 0 asks for the most a block may hold"""
+    return int(block_data) or capi.BGZF_BLOCK_DATA
+
+
+def _voffsets(stream_offsets, block_data, block_offset) -> np.ndarray:
+    """BGZF virtual file offsets of bytes of the uncompressed stream: the file offset of the block that holds the byte << 16
+    | the byte's offset in that block's data.  block_offset(i): the file offsets of the blocks i (an array)."""
+    u = np.asarray(stream_offsets).astype(np.uint64)
+    D = np.uint64(block_data)
+    return (block_offset(u // D) << np.uint64(16)) | (u % D)
+
+
+def _require_open(obj, method, whose, tree=True):
+    """obj.<method> reads the needle set behind obj and, with tree, the tree: neither may have been closed.  An object
+    that was given none has nothing to check."""
+    needed = (obj._jst, obj._pats) if tree else (obj._pats,)
+    if any(x is not None and not x._h for x in needed):
+        what = "the tree or the needle set" if tree else "the needle set"
+        raise capi.SpmError(f"{type(obj).__name__}.{method}: {what} of {whose} has been closed")
+
+
+class _Handle:
+    """An object of the C type spm_hip_<_PREFIX>_* and the context it was made in.  The calls that take the handle first go
+    through _call and what is built on it; a method on a path that bench.py times spells its call out."""
+    _PREFIX = None
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+
+    def _call(self, name, *args):
+        _check(getattr(capi.lib(), f"spm_hip_{self._PREFIX}_{name}")(self._h, *args), self.ctx._h)
+
+    def _stats(self, struct, name="stats"):
+        s = struct()
+        self._call(name, C.byref(s))
+        return s
+
+    def _span(self, name):
+        """(pointer, count), both as int"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._call(name, C.byref(p), C.byref(n))
+        return int(p.value or 0), int(n.value)
+
+    def _new(self, name, *args) -> C.c_void_p:
+        """the handle that a call puts into its last argument"""
+        h = C.c_void_p()
+        self._call(name, *args, C.byref(h))
+        return h
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
+                getattr(capi.lib(), f"spm_hip_{self._PREFIX}_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -75,22 +173,21 @@ class Context:
         return Text(self, h, 4)
 
     # ---- containers ----
+    def _bgzf(self, frame, opts, device_ptr, n) -> "Bgzf":
+        z = C.c_void_p()
+        _check(frame(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
+        return Bgzf(self, z, block_data=_block_data(opts.block_data))
+
     def bgzf(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """BGZF framing (stored blocks, nothing compressed) of n bytes at device_ptr, any alignment, on the device
         (spm_hip_bgzf_frame).  block_data: uncompressed bytes per block, 0 for 65280; eof: append the end-of-file block.  The
         source is read before the call returns."""
-        opts = bgzf_opts(block_data, eof)
-        z = C.c_void_p()
-        _check(capi.lib().spm_hip_bgzf_frame(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
-        return Bgzf(self, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
+        return self._bgzf(capi.lib().spm_hip_bgzf_frame, bgzf_opts(block_data, eof), device_ptr, n)
 
     def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
         block; a block that would not shrink stays stored).  The same arguments; the bytes are those of bgzf_deflate_host."""
-        opts = bgzf_deflate_opts(block_data, eof)
-        z = C.c_void_p()
-        _check(capi.lib().spm_hip_bgzf_deflate(self._h, C.c_void_p(device_ptr), int(n), C.byref(opts), C.byref(z)), self._h)
-        return Bgzf(self, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
+        return self._bgzf(capi.lib().spm_hip_bgzf_deflate, bgzf_deflate_opts(block_data, eof), device_ptr, n)
 
     # ---- needles ----
     def patterns(self, algo: int, needles, k=0, sigma: int = 4, both_strands: bool = False) -> "PatternSet":
@@ -121,9 +218,12 @@ class Context:
         return PatternSet(self, h, algo, (2 if both_strands else 1) * len(needles))
 
 
-class Text:
+class Text(_Handle):
+    _PREFIX = "text"
+
     def __init__(self, ctx, h, sigma):
-        self.ctx, self._h, self.sigma = ctx, h, sigma
+        super().__init__(ctx, h)
+        self.sigma = sigma
         self._keepalive = None
 
     def __len__(self):
@@ -148,22 +248,13 @@ class Text:
                                                 out.ctypes.data_as(C.POINTER(C.c_uint8))), self.ctx._h)
         return out
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
-                capi.lib().spm_hip_text_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class PatternSet(_Handle):
+    _PREFIX = "patterns"
 
-
-class PatternSet:
     def __init__(self, ctx, h, algo, n):
-        self.ctx, self._h, self.algo, self.n = ctx, h, algo, n
+        super().__init__(ctx, h)
+        self.algo, self.n = algo, n
 
     def __len__(self):
         """needles in the set: 2n for n reads on both strands"""
@@ -193,35 +284,24 @@ class PatternSet:
 
     def build_stats(self) -> capi.BuildStats:
         """What spm_hip_patterns_create spent where (host ms) and what it built (passes, keys, dense, anchors)."""
-        st = capi.BuildStats()
-        _check(capi.lib().spm_hip_patterns_build_stats(self._h, C.byref(st)), self.ctx._h)
-        return st
+        return self._stats(capi.BuildStats, "build_stats")
 
     def state_stride(self) -> int:
         return int(capi.lib().spm_hip_patterns_state_stride(self._h))
 
     def initial_state(self) -> np.ndarray:
         st = np.zeros(self.state_stride() * max(1, self.n), dtype=np.uint8)
-        _check(capi.lib().spm_hip_patterns_state_init(self._h, st.ctypes.data), self.ctx._h)
+        self._call("state_init", st.ctypes.data)
         return st
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
-                capi.lib().spm_hip_patterns_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Hits(_Handle):
+    _PREFIX = "hits"
 
-
-class Hits:
     def __init__(self, ctx, h, text=None, pats=None):
         # the scan's haystack and needle set: align() reads both, so they live at least as long as the hits
-        self.ctx, self._h, self._text, self._pats = ctx, h, text, pats
+        super().__init__(ctx, h)
+        self._text, self._pats = text, pats
 
     def view(self) -> np.ndarray:
         """Hits sorted by (pattern, pos): per pattern, the order the reference's callback fires in."""
@@ -258,10 +338,7 @@ class Hits:
 
     def align(self, begin_only: bool = False) -> "Alignments":
         """Begin + CIGAR transcript of every hit (spm_hip_hits_align); record i belongs to view() record i."""
-        a = C.c_void_p()
-        _check(capi.lib().spm_hip_hits_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
-               self.ctx._h)
-        return Alignments(self.ctx, a)
+        return Alignments(self.ctx, self._new("align", capi.ALIGN_BEGIN_ONLY if begin_only else 0))
 
     def select(self, loci: bool = True, window: int | None = None, best: int | None = None, strands: bool = False) -> "Hits":
         """A new, smaller Hits (spm_hip_hits_select): one record per locus (loci; window=None: every needle's own k) and,
@@ -269,14 +346,10 @@ class Hits:
         both_strands) of their READ's minimum over both strands.  Host AND device view of the result are sorted by
         (pattern, pos); it stays valid after this object is closed."""
         opts = _select_opts(loci, window, best, strands=strands)
-        h = C.c_void_p()
-        _check(capi.lib().spm_hip_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
-        return Hits(self.ctx, h, self._text, self._pats)
+        return Hits(self.ctx, self._new("select", C.byref(opts)), self._text, self._pats)
 
     def select_stats(self) -> capi.SelectStats:
-        s = capi.SelectStats()
-        _check(capi.lib().spm_hip_hits_select_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats(capi.SelectStats, "select_stats")
 
     def stats(self) -> capi.ScanStats:
         s = capi.ScanStats()
@@ -286,37 +359,11 @@ class Hits:
     def checksum(self) -> int:
         return int(capi.lib().spm_hip_hits_checksum(self._h))
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
-                capi.lib().spm_hip_hits_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _as_array(ptr, n, ctype, dtype):
-    if n == 0:
-        return np.zeros(0, dtype=dtype)
-    buf = (ctype * n).from_address(C.addressof(ptr.contents))
-    return np.frombuffer(buf, dtype=dtype).copy()
-
-
-class _RecordPool:
-    """What the results made of records + a pool of CIGAR words (len << 4 | op) share: a handle of the C type
-    spm_hip_<_PREFIX>_*, whose view hands out _REC records (numpy: _DTYPE) and the pool they point into, and whose
-    statistics are a _STATS.  The subclasses declare the four and keep what is their own."""
-    _PREFIX = _REC = _DTYPE = _STATS = None
-
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
-
-    def _call(self, name, *args):
-        _check(getattr(capi.lib(), f"spm_hip_{self._PREFIX}_{name}")(self._h, *args), self.ctx._h)
+class _RecordPool(_Handle):
+    """What the results made of records + a pool of CIGAR words (len << 4 | op) share: a view that hands out _REC records
+    (numpy: _DTYPE) and the pool they point into.  The subclasses declare the three and keep what is their own."""
+    _REC = _DTYPE = None
 
     def _raw(self):
         rec, ops = C.POINTER(self._REC)(), C.POINTER(C.c_uint32)()
@@ -348,28 +395,11 @@ class _RecordPool:
         words = o[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]
         return "".join(f"{int(w) >> 4}{_CIGAR_CHAR[int(w) & 15]}" for w in words)
 
-    def _stats(self):
-        s = self._STATS()
-        self._call("stats", C.byref(s))
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:  # the C objects point at their context: once it is gone there is nothing left to release
-                getattr(capi.lib(), f"spm_hip_{self._PREFIX}_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class Alignments(_RecordPool):
     """Result of Hits.align(): ALN_DTYPE records in the order of Hits.view(), and the pool of CIGAR words
     (len << 4 | op) they point into."""
-    _PREFIX, _REC, _DTYPE, _STATS = "alns", capi.Aln, ALN_DTYPE, capi.AlignStats
+    _PREFIX, _REC, _DTYPE = "alns", capi.Aln, ALN_DTYPE
 
     def device(self):
         """(records, n, ops, n_ops): device pointers, records in device hit order."""
@@ -380,7 +410,7 @@ class Alignments(_RecordPool):
         return self._cigar(i, records, ops)
 
     def stats(self) -> capi.AlignStats:
-        return self._stats()
+        return self._stats(capi.AlignStats)
 
 
 def scan(ctx: Context, text: Text, pats: PatternSet, begin: int = 0, end: int | None = None, *,
@@ -454,24 +484,6 @@ def synth_repeat_text(seed: int, repeat_ppm: int, begin: int, n: int) -> np.ndar
     return out
 
 
-ALLELE_DTYPE = np.dtype([("pos", "<u8"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("alt_off", "<u8")])
-JST_HIT_DTYPE = np.dtype([("pos", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"), ("score", "<i4"),
-                          ("reserved", "<u4")])
-JST_ALN_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"), ("score", "<i4"),
-                          ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("reserved", "<u4")])
-JST_REF_ALN_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("haplotype", "<u4"), ("pattern", "<u4"),
-                              ("score", "<i4"), ("ref_score", "<i4"), ("cigar_off", "<u4"), ("cigar_len", "<u4")])
-JST_READ_DTYPE = np.dtype([("first_locus", "<u4"), ("n_loci", "<u4"), ("n_forward", "<u4"), ("primary", "<u4"),
-                           ("best", "<i4"), ("best_ref_score", "<i4"), ("n_best", "<u4"), ("n_next", "<u4")])
-JST_PAIR_DTYPE = np.dtype([("locus1", "<u4"), ("locus2", "<u4"), ("tlen", "<i4"), ("best", "<i4"), ("n_pairs", "<u4"),
-                           ("n_best", "<u4"), ("n_next", "<u4"), ("flag1", "<u2"), ("flag2", "<u2")])
-JST_RESCUE_DTYPE = np.dtype(capi.JST_RESCUE_DTYPE)
-SAM_LINE_DTYPE = np.dtype(capi.SAM_LINE_DTYPE)
-JST_REF_LOCUS_DTYPE = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"),
-                                ("score", "<i4"), ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"),
-                                ("member_off", "<u4"), ("n_haplotypes", "<u4")])
-
-
 def synth_variants(seed_text: int, seed_var: int, ref_begin: int, n_ref: int, n_haplotypes: int):
     """The synthetic variants of config C5: (alleles, alt_pool, coverage) as numpy arrays."""
     na, npool = C.c_uint64(0), C.c_uint64(0)
@@ -491,11 +503,12 @@ def synth_variants(seed_text: int, seed_var: int, ref_begin: int, n_ref: int, n_
     return alleles[:na.value], pool[:npool.value], cov[:na.value]
 
 
-class Jst:
+class Jst(_Handle):
     """Journaled sequence tree in HBM: a reference Text + alleles + per-allele haplotype coverage."""
+    _PREFIX = "jst"
 
     def __init__(self, ctx: Context, reference: Text, alleles, alt_pool, coverage, n_haplotypes: int):
-        self.ctx, self.reference, self.n_haplotypes = ctx, reference, n_haplotypes
+        self.reference, self.n_haplotypes = reference, n_haplotypes
         al = np.ascontiguousarray(alleles, dtype=ALLELE_DTYPE)
         pool = np.ascontiguousarray(alt_pool, dtype=np.uint8)
         cw = (n_haplotypes + 63) // 64
@@ -507,19 +520,18 @@ class Jst:
                                              len(al), pool.ctypes.data_as(C.POINTER(C.c_uint8)), pool.size,
                                              cov.ctypes.data_as(C.POINTER(C.c_uint64)), n_haplotypes, C.byref(h)),
                ctx._h)
-        self._h = h
+        super().__init__(ctx, h)
 
     def haplotype_length(self, h: int) -> int:
         return int(capi.lib().spm_hip_jst_haplotype_length(self._h, h))
 
     def extract(self, h: int, begin: int, n: int) -> np.ndarray:
         out = np.empty(n, dtype=np.uint8)
-        _check(capi.lib().spm_hip_jst_extract(self._h, h, begin, n, out.ctypes.data_as(C.POINTER(C.c_uint8))),
-               self.ctx._h)
+        self._call("extract", h, begin, n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         return out
 
     def index(self, window: int, block_len: int = 0, block_begin: int = 0, block_end: int = 0):
-        _check(capi.lib().spm_hip_jst_index(self._h, window, block_len, block_begin, block_end), self.ctx._h)
+        self._call("index", window, block_len, block_begin, block_end)
         return self.stats()
 
     def stats(self) -> capi.JstStats:
@@ -545,23 +557,14 @@ class Jst:
         finally:
             h.close()
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class JstHits(_Handle):
+    _PREFIX = "jst_hits"
 
-
-class JstHits:
     def __init__(self, ctx, h, jst=None, pats=None):
         # the search's tree and needle set: align() reads both, so they live at least as long as the hits
-        self.ctx, self._h, self._jst, self._pats = ctx, h, jst, pats
+        super().__init__(ctx, h)
+        self._jst, self._pats = jst, pats
 
     def __len__(self):
         return self.device()[1]
@@ -569,9 +572,7 @@ class JstHits:
     def device(self):
         """(pointer, count) of the records in HBM: arrival order for a search, (haplotype, pattern, pos) order for a
         selection."""
-        p, n = C.c_void_p(), C.c_uint64(0)
-        _check(capi.lib().spm_hip_jst_hits_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(p.value or 0), int(n.value)
+        return self._span("device")
 
     def view(self) -> np.ndarray:
         rec = C.POINTER(capi.JstHit)()
@@ -590,11 +591,8 @@ class JstHits:
     def align(self, begin_only: bool = False) -> "JstAlignments":
         """Begin + CIGAR transcript of every record (spm_hip_jst_hits_align), one alignment per segment hit shared by the
         haplotypes of its context; record i belongs to view() record i.  Needs search_device(..., alignable=True)."""
-        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
-            raise capi.SpmError("JstHits.align: the tree or the needle set of this search has been closed")
-        a = C.c_void_p()
-        _check(capi.lib().spm_hip_jst_hits_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
-               self.ctx._h)
+        _require_open(self, "align", "this search")
+        a = self._new("align", capi.ALIGN_BEGIN_ONLY if begin_only else 0)
         return JstAlignments(self.ctx, a, self._jst, self._pats)
 
     def align_selected(self, begin_only: bool = False) -> "JstAlignments":
@@ -603,8 +601,7 @@ class JstHits:
         belongs to view() record i of this selection, and record i of its device() to record i of this selection's
         device(), in (haplotype, pattern, pos) order.  The search need not have been alignable and may be closed; the tree
         and the needle set must be open, and the tree not indexed again since the search."""
-        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
-            raise capi.SpmError("JstHits.align_selected: the tree or the needle set of this selection has been closed")
+        _require_open(self, "align_selected", "this selection")
         a = C.c_void_p()
         _check(capi.lib().spm_hip_jst_selection_align(self._h, capi.ALIGN_BEGIN_ONLY if begin_only else 0, C.byref(a)),
                self.ctx._h)
@@ -618,29 +615,12 @@ class JstHits:
         (haplotype, pattern, pos), its host view as every view(); it stays valid after this object is closed.  align()
         does not take it; align_selected() aligns the records it kept.  strands=True (a set made with both_strands): the
         minimum is taken per READ = pattern >> 1 over both strands."""
-        if self._pats is not None and not self._pats._h:
-            raise capi.SpmError("JstHits.select: the needle set of these hits has been closed")
+        _require_open(self, "select", "these hits", tree=False)
         opts = _select_opts(loci, window, best, across, strands)
-        h = C.c_void_p()
-        _check(capi.lib().spm_hip_jst_hits_select(self._h, C.byref(opts), C.byref(h)), self.ctx._h)
-        return JstHits(self.ctx, h, self._jst, self._pats)
+        return JstHits(self.ctx, self._new("select", C.byref(opts)), self._jst, self._pats)
 
     def select_stats(self) -> capi.SelectStats:
-        s = capi.SelectStats()
-        _check(capi.lib().spm_hip_jst_hits_select_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_hits_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats(capi.SelectStats, "select_stats")
 
 
 def select_jst_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet | None = None, *, loci: bool = True,
@@ -658,7 +638,7 @@ def select_jst_records(ctx: Context, device_ptr: int, n: int, pats: PatternSet |
 class JstAlignments(_RecordPool):
     """Result of JstHits.align(): JST_ALN_DTYPE records in the order of JstHits.view(), and the pool of CIGAR words
     (len << 4 | op) they point into -- one transcript per segment hit, shared by the haplotypes of its context."""
-    _PREFIX, _REC, _DTYPE, _STATS = "jst_alns", capi.JstAln, JST_ALN_DTYPE, capi.JstAlignStats
+    _PREFIX, _REC, _DTYPE = "jst_alns", capi.JstAln, JST_ALN_DTYPE
 
     def __init__(self, ctx, h, jst=None, pats=None):
         # the tree and the needle set behind these alignments: project() reads both
@@ -675,24 +655,21 @@ class JstAlignments(_RecordPool):
         return self._cigar(i, records, ops)
 
     def stats(self) -> capi.JstAlignStats:
-        return self._stats()
+        return self._stats(capi.JstAlignStats)
 
     def project(self) -> "JstRefAlignments":
         """These alignments in REFERENCE coordinates (spm_hip_jst_alns_project): ref_begin, ref_end, ref_score and a
         transcript against the reference, computed once per shared transcript slot.  Record i of the result's view()
         belongs to view() record i, record i of its device() to device() record i.  Not for begin_only alignments; the
         tree and the needle set must be open, and the tree not indexed again since the search."""
-        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
-            raise capi.SpmError("JstAlignments.project: the tree or the needle set of these alignments has been closed")
-        r = C.c_void_p()
-        self._call("project", 0, C.byref(r))
-        return JstRefAlignments(self.ctx, r, self._jst, self._pats)
+        _require_open(self, "project", "these alignments")
+        return JstRefAlignments(self.ctx, self._new("project", 0), self._jst, self._pats)
 
 
 class JstRefAlignments(_RecordPool):
     """Result of JstAlignments.project(): JST_REF_ALN_DTYPE records matched to the source's records, and the pool of CIGAR
     words (len << 4 | op) against the reference -- one transcript per distinct transcript slot of the source."""
-    _PREFIX, _REC, _DTYPE, _STATS = "jst_ref_alns", capi.JstRefAln, JST_REF_ALN_DTYPE, capi.JstProjectStats
+    _PREFIX, _REC, _DTYPE = "jst_ref_alns", capi.JstRefAln, JST_REF_ALN_DTYPE
 
     def __init__(self, ctx, h, jst=None, pats=None):
         # the tree and the needle set behind these records: normalize() reads the reference text and the needles
@@ -708,7 +685,7 @@ class JstRefAlignments(_RecordPool):
         return self._cigar(i, records, ops)
 
     def stats(self) -> capi.JstProjectStats:
-        return self._stats()
+        return self._stats(capi.JstProjectStats)
 
     def normalize(self) -> "JstRefAlignments":
         """These records with every indel at its leftmost equivalent place (spm_hip_jst_ref_alns_normalize): the same
@@ -716,33 +693,31 @@ class JstRefAlignments(_RecordPool):
         collapse() of the result merges the haplotypes that differ only in which copy of a repeat an indel touches.  The
         tree and the needle set must be open during the call (the tree may have been indexed again); the result stays
         valid after they and this object are closed."""
-        if (self._jst is not None and not self._jst._h) or (self._pats is not None and not self._pats._h):
-            raise capi.SpmError("JstRefAlignments.normalize: the tree or the needle set of these alignments has been closed")
-        r = C.c_void_p()
-        self._call("normalize", 0, C.byref(r))
-        return JstRefAlignments(self.ctx, r, self._jst, self._pats)
+        _require_open(self, "normalize", "these alignments")
+        return JstRefAlignments(self.ctx, self._new("normalize", 0), self._jst, self._pats)
 
     def normalize_stats(self) -> capi.JstNormalizeStats:
         """Stage times and counts of the normalize() call that made this object (an error for any other)."""
-        s = capi.JstNormalizeStats()
-        self._call("normalize_stats", C.byref(s))
-        return s
+        return self._stats(capi.JstNormalizeStats, "normalize_stats")
 
     def collapse(self) -> "JstRefLoci":
         """One record per distinct reference alignment (spm_hip_jst_ref_alns_collapse): records that agree in needle,
         reference range and transcript are merged; the result carries the haplotypes that support each locus and their
         haplotype distances.  Reads only these records and their pool: tree and needle set may be closed, and the result
         stays valid after this object is closed."""
-        r = C.c_void_p()
-        self._call("collapse", 0, C.byref(r))
-        return JstRefLoci(self.ctx, r)
+        return JstRefLoci(self.ctx, self._new("collapse", 0))
+
+
+def _or_null(obj):
+    """the handle of an optional argument"""
+    return obj._h if obj is not None else None
 
 
 class JstRefLoci(_RecordPool):
     """Result of JstRefAlignments.collapse(): JST_REF_LOCUS_DTYPE records in (pattern, ref_begin, ref_end, ref_score,
     cigar_len, transcript words) order, one transcript per locus in `ops`, and per locus the distinct haplotypes that
     support it (`members`, ascending) with the smallest haplotype distance each has there (`member_scores`)."""
-    _PREFIX, _REC, _DTYPE, _STATS = "jst_ref_loci", capi.JstRefLocus, JST_REF_LOCUS_DTYPE, capi.JstCollapseStats
+    _PREFIX, _REC, _DTYPE = "jst_ref_loci", capi.JstRefLocus, JST_REF_LOCUS_DTYPE
 
     def _raw(self):
         rec = C.POINTER(capi.JstRefLocus)()
@@ -792,16 +767,14 @@ class JstRefLoci(_RecordPool):
                 "locus_of": int(mp.value or 0), "n_alns": int(n_alns.value)}
 
     def stats(self) -> capi.JstCollapseStats:
-        return self._stats()
+        return self._stats(capi.JstCollapseStats)
 
     def reads(self, n_reads: int, strands: int = 1) -> "JstReads":
         """One JST_READ_DTYPE record per read 0 .. n_reads - 1 (spm_hip_jst_ref_loci_reads): where its loci stand, how many
         it has on which strand, its primary locus -- the smallest (score, locus index) -- and how many loci share the best
         and the next stratum.  strands=2: the loci stem from a set made with both_strands (read = pattern >> 1).  The result
         stays valid after this object is closed."""
-        r = C.c_void_p()
-        self._call("reads", strands, n_reads, 0, C.byref(r))
-        return JstReads(self.ctx, r)
+        return JstReads(self.ctx, self._new("reads", strands, n_reads, 0))
 
     def pairs(self, reads: "JstReads", min_tlen: int, max_tlen: int) -> "JstPairs":
         """One JST_PAIR_DTYPE record per pair of mates -- reads 2p and 2p + 1 of `reads`, this object's reads(n, strands=2)
@@ -809,9 +782,7 @@ class JstRefLoci(_RecordPool):
         of the other with min_tlen <= fragment length <= max_tlen, how many there are, the SAM TLEN and FLAGs; without one,
         the mates' own primaries.  The result stays valid after this object and `reads` are closed."""
         opts = capi.JstPairOpts(min_tlen=int(min_tlen), max_tlen=int(max_tlen), flags=0, reserved=0)
-        p = C.c_void_p()
-        self._call("pairs", reads._h, C.byref(opts), C.byref(p))
-        return JstPairs(self.ctx, p)
+        return JstPairs(self.ctx, self._new("pairs", reads._h, C.byref(opts)))
 
     def sam(self, reads: "JstReads", patterns: "PatternSet", rname: str, *, pairs: "JstPairs | None" = None,
             rescues: "JstRescues | None" = None, names=None, symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False,
@@ -823,12 +794,9 @@ class JstRefLoci(_RecordPool):
         stays valid after every input is closed."""
         opts = sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi)
         keep = _set_names(opts, names)
-        s = C.c_void_p()
-        self._call("sam", reads._h, pairs._h if pairs is not None else None, rescues._h if rescues is not None else None,
-                   patterns._h, C.byref(opts), C.byref(s))
+        s = self._new("sam", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts))
         del keep
         return Sam(self.ctx, s, rname)
-
 
     def bam(self, reads: "JstReads", patterns: "PatternSet", rname: str, ref_len: int, *, pairs: "JstPairs | None" = None,
             rescues: "JstRescues | None" = None, names=None, symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False,
@@ -839,11 +807,9 @@ class JstRefLoci(_RecordPool):
         opts = capi.BamOpts(sam=sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique,
                                          mapq_multi=mapq_multi), ref_len=int(ref_len), block_data=int(block_data), reserved=0)
         keep = _set_names(opts.sam, names)
-        b = C.c_void_p()
-        self._call("bam", reads._h, pairs._h if pairs is not None else None, rescues._h if rescues is not None else None,
-                   patterns._h, C.byref(opts), C.byref(b))
+        b = self._new("bam", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts))
         del keep
-        return Bam(self.ctx, b, int(block_data) or capi.BGZF_BLOCK_DATA)
+        return Bam(self.ctx, b, _block_data(block_data))
 
 
 def _set_names(opts: "capi.SamOpts", names):
@@ -881,27 +847,25 @@ def sam_mapq(n_best: int, n_next: int, mapq_unique=None, mapq_multi=None) -> int
 def sam_header(rname, ref_len: int) -> bytes:
     """The @HD and @SQ lines (spm_hip_sam_header).  Needs no device."""
     rname = rname.encode() if isinstance(rname, str) else bytes(rname)
-    need = C.c_uint64()
-    rc = capi.lib().spm_hip_sam_header(rname, int(ref_len), None, 0, C.byref(need))
-    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
+
+    def refuse(rc):
         raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_header refused rname {rname!r}")
-    buf = C.create_string_buffer(need.value)
-    rc = capi.lib().spm_hip_sam_header(rname, int(ref_len), buf, need.value, C.byref(need))
-    if rc != 0:
-        raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_header")
-    return buf.raw[:need.value]
+
+    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_sam_header(rname, int(ref_len), buf, cap, need), refuse)
 
 
-class Sam:
+class Sam(_Handle):
     """Result of JstRefLoci.sam(): the SAM text and one SAM_LINE_DTYPE record per line, in line order."""
+    _PREFIX = "sam"
 
     def __init__(self, ctx, h, rname):
-        self.ctx, self._h, self.rname = ctx, h, rname
+        super().__init__(ctx, h)
+        self.rname = rname
 
     def _view(self):
         t, rec = C.c_void_p(), C.POINTER(capi.SamLine)()
         nb, nl = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_sam_view(self._h, C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl)), self.ctx._h)
+        self._call("view", C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl))
         return t, nb.value, rec, nl.value
 
     def __len__(self):
@@ -919,71 +883,52 @@ class Sam:
         """(text, n_bytes, lines, n_lines): device pointers and counts"""
         t, rec = C.c_void_p(), C.c_void_p()
         nb, nl = C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_sam_device(self._h, C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl)), self.ctx._h)
+        self._call("device", C.byref(t), C.byref(nb), C.byref(rec), C.byref(nl))
         return int(t.value or 0), int(nb.value), int(rec.value or 0), int(nl.value)
 
     def stats(self) -> capi.SamStats:
-        s = capi.SamStats()
-        _check(capi.lib().spm_hip_sam_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats(capi.SamStats)
 
     def header(self, ref_len: int) -> bytes:
         return sam_header(self.rname, ref_len)
 
+    def _bgzf(self, frame, frame_host, ref_len, block_data, eof) -> "Bgzf":
+        text, n_bytes, _lines, _n = self.device()
+        z = frame(text, n_bytes, block_data=block_data, eof=eof)
+        if ref_len is not None:
+            z.prefix = frame_host(self.header(ref_len), block_data, eof=False)
+        return z
+
     def bgzf(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """The text, framed where it lies in device memory (Context.bgzf).  With ref_len the header is framed on the host, as
         blocks of its own in front: bytes() is a .sam.gz."""
-        text, n_bytes, _lines, _n = self.device()
-        z = self.ctx.bgzf(text, n_bytes, block_data=block_data, eof=eof)
-        if ref_len is not None:
-            z.prefix = bgzf_frame_host(self.header(ref_len), block_data, eof=False)
-        return z
+        return self._bgzf(self.ctx.bgzf, bgzf_frame_host, ref_len, block_data, eof)
 
     def bgzf_deflate(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """bgzf() with the blocks compressed (Context.bgzf_deflate); the header's blocks come from the host deflater."""
-        text, n_bytes, _lines, _n = self.device()
-        z = self.ctx.bgzf_deflate(text, n_bytes, block_data=block_data, eof=eof)
-        if ref_len is not None:
-            z.prefix = bgzf_deflate_host(self.header(ref_len), block_data, eof=False)
-        return z
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_sam_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._bgzf(self.ctx.bgzf_deflate, bgzf_deflate_host, ref_len, block_data, eof)
 
 
 def bam_header(rname, ref_len: int, block_data: int = 0) -> bytes:
     """The framed header section of a BAM file (spm_hip_bam_header).  Needs no device."""
     rname = rname.encode() if isinstance(rname, str) else bytes(rname)
-    need = C.c_uint64()
-    rc = capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), None, 0, C.byref(need))
-    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
-        _check(rc if rc else -1, None)
-    buf = C.create_string_buffer(need.value)
-    _check(capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), buf, need.value, C.byref(need)), None)
-    return buf.raw[:need.value]
+    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), buf, cap, need),
+                           lambda rc: _check(rc if rc else -1, None))
 
 
-class Bam:
+class Bam(_Handle):
     """Result of JstRefLoci.bam(): the file, the uncompressed record stream and one SAM_LINE_DTYPE record per BAM record
     (offset / len: the record in the stream), in record order."""
+    _PREFIX = "bam"
 
     def __init__(self, ctx, h, block_data):
-        self.ctx, self._h, self.block_data = ctx, h, block_data
+        super().__init__(ctx, h)
+        self.block_data = block_data
 
     def _view(self):
         f, r, rec = C.c_void_p(), C.c_void_p(), C.POINTER(capi.SamLine)()
         nf, nr, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_bam_view(self._h, C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl)),
-               self.ctx._h)
+        self._call("view", C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl))
         return f, nf.value, r, nr.value, rec, nl.value
 
     def __len__(self):
@@ -1003,43 +948,25 @@ class Bam:
 
     def voffsets(self) -> np.ndarray:
         """the BGZF virtual file offset of every record"""
-        u = self.lines()["offset"].astype(np.uint64)
-        D = np.uint64(self.block_data)
-        return ((np.uint64(self.stats().header_file_bytes) + (u // D) * (D + np.uint64(31))) << np.uint64(16)) | (u % D)
+        first, block = np.uint64(self.stats().header_file_bytes), np.uint64(self.block_data + 31)  # stored blocks, no gaps
+        return _voffsets(self.lines()["offset"], self.block_data, lambda i: first + i * block)
 
     def deflate(self, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """The file with its blocks compressed (spm_hip_bam_deflate): the header section deflated on the host, the record
         stream on the device where it lies, in blocks of block_data uncompressed bytes.  block_offsets() are the record
         blocks' file offsets; voffsets(self.lines()["offset"]) the records' virtual offsets."""
         opts = bgzf_deflate_opts(block_data, eof)
-        z = C.c_void_p()
-        _check(capi.lib().spm_hip_bam_deflate(self._h, C.byref(opts), C.byref(z)), self.ctx._h)
-        return Bgzf(self.ctx, z, block_data=int(block_data) or capi.BGZF_BLOCK_DATA)
+        return Bgzf(self.ctx, self._new("deflate", C.byref(opts)), block_data=_block_data(block_data))
 
     def device(self):
         """(file, n_file, records, n_record_bytes, lines, n_lines): device pointers and counts"""
         f, r, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
         nf, nr, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(capi.lib().spm_hip_bam_device(self._h, C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl)),
-               self.ctx._h)
+        self._call("device", C.byref(f), C.byref(nf), C.byref(r), C.byref(nr), C.byref(rec), C.byref(nl))
         return int(f.value or 0), int(nf.value), int(r.value or 0), int(nr.value), int(rec.value or 0), int(nl.value)
 
     def stats(self) -> capi.BamStats:
-        s = capi.BamStats()
-        _check(capi.lib().spm_hip_bam_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_bam_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats(capi.BamStats)
 
 
 def bgzf_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfOpts:
@@ -1050,16 +977,9 @@ def bgzf_frame_host(data, block_data: int = 0, eof: bool = True) -> bytes:
     """The container of Context.bgzf by the serial host framer (spm_hip_bgzf_frame_host).  Needs no device."""
     data = bytes(data)
     opts = bgzf_opts(block_data, eof)
-    need = C.c_uint64()
     src = C.create_string_buffer(data, len(data) + 1)
-    rc = capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), None, 0, C.byref(need))
-    if rc == 0 and need.value == 0:
-        return b""
-    if rc != -5:                                                   # SPM_E_OVERFLOW: the length is known now
-        _check(rc, None)
-    dst = C.create_string_buffer(need.value)
-    _check(capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), dst, need.value, C.byref(need)), None)
-    return dst.raw[:need.value]
+    # (no data and no end-of-file block: the size call answers 0 with a length of 0, and that is the result)
+    return _size_then_fill(lambda dst, cap, need: capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), dst, cap, need))
 
 
 def bgzf_deflate_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfDeflateOpts:
@@ -1079,128 +999,83 @@ def bgzf_deflate_host(data, block_data: int = 0, eof: bool = True) -> bytes:
     return dst.raw[:need.value]
 
 
-class Bgzf:
+class Bgzf(_Handle):
     """Result of Context.bgzf() / Sam.bgzf(), their bgzf_deflate() and Bam.deflate(): BGZF blocks in device memory.  prefix: bytes
     framed on the host that belong in front of them (Sam.bgzf with ref_len: the header's blocks); bytes() has them, device()
     is the device part alone.  block_data: the uncompressed bytes of a full block."""
+    _PREFIX = "bgzf"
 
     def __init__(self, ctx, h, prefix: bytes = b"", block_data: int = capi.BGZF_BLOCK_DATA):
-        self.ctx, self._h, self.prefix, self.block_data = ctx, h, prefix, block_data
+        super().__init__(ctx, h)
+        self.prefix, self.block_data = prefix, block_data
 
     def block_offsets(self) -> np.ndarray:
         """n_blocks + 1 offsets into bytes(): of every data block of the device part, then their end (spm_hip_bgzf_blocks)"""
         p, n = C.POINTER(C.c_uint64)(), C.c_uint64()
-        _check(capi.lib().spm_hip_bgzf_blocks(self._h, C.byref(p), C.byref(n)), self.ctx._h)
+        self._call("blocks", C.byref(p), C.byref(n))
         return np.ctypeslib.as_array(p, shape=(n.value + 1,)).astype(np.uint64) + np.uint64(len(self.prefix))
 
     def block_offsets_device(self):
         """(offsets, n_blocks): the same offsets on the device, without the prefix's length"""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(capi.lib().spm_hip_bgzf_blocks_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(p.value or 0), int(n.value)
+        return self._span("blocks_device")
 
     def voffsets(self, stream_offsets) -> np.ndarray:
         """the BGZF virtual file offset of the bytes at these offsets of the uncompressed stream"""
-        u = np.asarray(stream_offsets).astype(np.uint64)
-        D = np.uint64(self.block_data)
-        return (self.block_offsets()[(u // D).astype(np.int64)] << np.uint64(16)) | (u % D)
+        return _voffsets(stream_offsets, self.block_data, lambda i: self.block_offsets()[i.astype(np.int64)])
 
     def deflate_stats(self) -> capi.BgzfDeflateStats:
-        s = capi.BgzfDeflateStats()
-        _check(capi.lib().spm_hip_bgzf_deflate_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats(capi.BgzfDeflateStats, "deflate_stats")
 
     def bytes(self) -> bytes:
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(capi.lib().spm_hip_bgzf_view(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return self.prefix + (C.string_at(p, n.value) if n.value else b"")
+        p, n = self._span("view")
+        return self.prefix + (C.string_at(p, n) if n else b"")
 
     def device(self):
         """(bytes, n): device pointer and count"""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(capi.lib().spm_hip_bgzf_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(p.value or 0), int(n.value)
+        return self._span("device")
 
     def stats(self) -> capi.BgzfStats:
-        s = capi.BgzfStats()
-        _check(capi.lib().spm_hip_bgzf_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_bgzf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats(capi.BgzfStats)
 
 
-class JstReads:
+class JstReads(_Handle):
     """Result of JstRefLoci.reads(): one JST_READ_DTYPE record per read, in read order, in both views."""
-
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    _PREFIX = "jst_reads"
 
     def __len__(self):
         return self.device()[1]
 
     def view(self) -> np.ndarray:
         rec, n = C.POINTER(capi.JstRead)(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_reads_view(self._h, C.byref(rec), C.byref(n)), self.ctx._h)
+        self._call("view", C.byref(rec), C.byref(n))
         return _as_array(rec, n.value, capi.JstRead, JST_READ_DTYPE)
 
     def device(self):
         """(pointer, count) of the records in HBM"""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_reads_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(p.value or 0), int(n.value)
+        return self._span("device")
 
     def stats(self) -> capi.JstReadsStats:
-        s = capi.JstReadsStats()
-        _check(capi.lib().spm_hip_jst_reads_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
-
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_reads_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats(capi.JstReadsStats)
 
 
-class JstPairs:
+class JstPairs(_Handle):
     """Result of JstRefLoci.pairs(): one JST_PAIR_DTYPE record per pair of mates, in pair order, in both views."""
-
-    def __init__(self, ctx, h):
-        self.ctx, self._h = ctx, h
+    _PREFIX = "jst_pairs"
 
     def __len__(self):
         return self.device()[1]
 
     def view(self) -> np.ndarray:
         rec, n = C.POINTER(capi.JstPair)(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_pairs_view(self._h, C.byref(rec), C.byref(n)), self.ctx._h)
+        self._call("view", C.byref(rec), C.byref(n))
         return _as_array(rec, n.value, capi.JstPair, JST_PAIR_DTYPE)
 
     def device(self):
         """(pointer, count) of the records in HBM"""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(capi.lib().spm_hip_jst_pairs_device(self._h, C.byref(p), C.byref(n)), self.ctx._h)
-        return int(p.value or 0), int(n.value)
+        return self._span("device")
 
     def stats(self) -> capi.JstPairsStats:
-        s = capi.JstPairsStats()
-        _check(capi.lib().spm_hip_jst_pairs_stats(self._h, C.byref(s)), self.ctx._h)
-        return s
+        return self._stats(capi.JstPairsStats)
 
     def rescue(self, loci: "JstRefLoci", reads: "JstReads", reference: "Text", patterns: "PatternSet", k: int, min_tlen: int,
                max_tlen: int) -> "JstRescues":
@@ -1215,23 +1090,11 @@ class JstPairs:
                                                    C.byref(r)), self.ctx._h)
         return JstRescues(self.ctx, r)
 
-    def close(self):
-        if self._h:
-            if self.ctx._h:
-                capi.lib().spm_hip_jst_pairs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class JstRescues(_RecordPool):
     """Result of JstPairs.rescue(): one JST_RESCUE_DTYPE record per job, ordered by (pair, mate rescued), and the pool of
     CIGAR words (len << 4 | op) the found ones point into."""
-    _PREFIX, _REC, _DTYPE, _STATS = "jst_rescues", capi.JstRescue, JST_RESCUE_DTYPE, capi.JstRescuesStats
+    _PREFIX, _REC, _DTYPE = "jst_rescues", capi.JstRescue, JST_RESCUE_DTYPE
 
     def view(self):
         """(records, ops)"""
@@ -1247,4 +1110,4 @@ class JstRescues(_RecordPool):
         return self._cigar(i, records, ops)
 
     def stats(self) -> capi.JstRescuesStats:
-        return self._stats()
+        return self._stats(capi.JstRescuesStats)

@@ -1,6 +1,6 @@
 """What the tests of the C++ side share: the g++ command lines of the stand-alone case programs (plain, and under
-AddressSanitizer + UndefinedBehaviorSanitizer) and of the mirror programs that link libspm_hip.so, and the download of a
-device view.  A plain module, imported by the test files that need it."""
+AddressSanitizer + UndefinedBehaviorSanitizer) and of the mirror programs that link libspm_hip.so, the C99 programs that
+print the header's layouts, and the download of a device view.  A plain module, imported by the test files that need it."""
 import ctypes
 import os
 import pathlib
@@ -35,6 +35,15 @@ def build_mirror(source, out_dir, fixtures=True):
                           ["-o", str(exe), os.path.join(CPP, source), "-L" + LIB, "-l:libspm_hip.so", "-Wl,-rpath," + LIB,
                            "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"] + (["-lz"] if fixtures else []))
     return exe
+
+
+def c_layout(tmp_path, source):
+    """What a C99 program over include/spm_hip.h (its own main, nothing to link) prints about the header's layouts:
+    source -> tmp_path/layout, run; its lines "<name> <value>" -> {name: value}, the values as printed."""
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text(source)
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic"] + WARN + ["-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    return dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
 
 
 def download(ctx, device_ptr, n, dtype):

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from bam_decode import EOF_BLOCK, bam_to_sam, parse_bam_header, parse_bgzf, payload_of, reg2bin
-from cpp_programs import ROOT, build_cases
+from cpp_programs import ROOT, build_cases, c_layout
 
 OK, INVALID, UNSUPPORTED, OVERFLOW = 0, -1, -4, -5
 
@@ -65,12 +65,7 @@ def test_layouts_and_names(spm, tmp_path):
     capi = spm.capi
     assert ctypes.sizeof(capi.BgzfOpts) == 16 and ctypes.sizeof(capi.BgzfStats) == 32
     assert ctypes.sizeof(capi.BamOpts) == 80 and ctypes.sizeof(capi.BamStats) == 104
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert (int(want.pop("sizeof.opts")), int(want.pop("sizeof.stats"))) == (16, 32)
     assert (int(want.pop("sizeof.bamopts")), int(want.pop("sizeof.bamstats"))) == (80, 104)
     assert int(want.pop("flag.values")) == 652801 == capi.BGZF_EOF + 10 * capi.BGZF_BLOCK_DATA

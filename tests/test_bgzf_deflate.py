@@ -4,14 +4,12 @@ must consume exactly what BSIZE says) and by gzip; the conditions that follow fr
 against ctypes; the refusals of the host calls."""
 import ctypes
 import gzip
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bgzf_inflate
-from cpp_programs import ROOT
+from cpp_programs import c_layout
 
 OK, INVALID, UNSUPPORTED, OVERFLOW = 0, -1, -4, -5
 LENGTHS = (0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 65279, 65280, 65281, 200_000)
@@ -163,12 +161,7 @@ CALLS = ("spm_hip_bgzf_deflate", "spm_hip_bgzf_blocks", "spm_hip_bgzf_blocks_dev
 def test_layouts_and_names(spm, tmp_path):
     capi = spm.capi
     assert ctypes.sizeof(capi.BgzfDeflateOpts) == 16 and ctypes.sizeof(capi.BgzfDeflateStats) == 72
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert (int(want.pop("sizeof.opts")), int(want.pop("sizeof.stats"))) == (16, 72)
     types = {"opts": capi.BgzfDeflateOpts, "stats": capi.BgzfDeflateStats}
     seen = dict.fromkeys(types, 0)

@@ -10,18 +10,16 @@ The expected answer never comes from that code alone:
 """
 import ctypes
 import gc
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from cpp_programs import build_mirror
+from cpp_programs import build_mirror, c_layout
 from test_align import ref_begins, replay
 from test_gpu_jst import _apply, _random_alleles
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED_TEXT = 0x5EED0001
 SEED_VAR = 0x5EED0003
 
@@ -49,12 +47,7 @@ int main(void)
 def test_record_layout_matches_the_header(spm, tmp_path):
     assert ctypes.sizeof(spm.capi.JstAln) == 40 == spm.JST_ALN_DTYPE.itemsize
     assert ctypes.sizeof(spm.capi.JstAlignStats) == 80
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert int(want.pop("sizeof.aln")) == 40 and int(want.pop("sizeof.stats")) == 80
     assert int(want.pop("flag")) == spm.capi.SCAN_ALIGNABLE == spm.SCAN_ALIGNABLE == 4
     n_rec = n_st = 0

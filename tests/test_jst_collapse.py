@@ -6,19 +6,16 @@ projection to the NumPy projection and the replayer.  Every GPU row compares rec
 reference byte for byte, and asserts -- with counters the reference computes -- that it holds the case it is named for.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from cpp_programs import download
+from cpp_programs import c_layout, download
 from test_align import replay
 from test_gpu_jst import _apply
 from test_jst_project import (ALL_KINDS, DEL, EQ, INS, X, Journal, _check, _cig, _global_dp, _hap, _make_tree, _open,
                               _plant, _r, _row1_tree, _window, np_project)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 LOCUS = np.dtype([("ref_begin", "<u8"), ("ref_end", "<u8"), ("pattern", "<u4"), ("ref_score", "<i4"), ("score", "<i4"),
                   ("n_records", "<u4"), ("cigar_off", "<u4"), ("cigar_len", "<u4"), ("member_off", "<u4"), ("n_haplotypes", "<u4")])
@@ -52,12 +49,7 @@ def test_record_layout_matches_the_header(spm, tmp_path):
     assert ctypes.sizeof(spm.capi.JstRefLocus) == 48 == spm.JST_REF_LOCUS_DTYPE.itemsize
     assert spm.JST_REF_LOCUS_DTYPE == LOCUS
     assert ctypes.sizeof(spm.capi.JstCollapseStats) == 80
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert int(want.pop("sizeof.locus")) == 48 and int(want.pop("sizeof.stats")) == 80
     n_rec = n_st = 0
     for name, off in want.items():

@@ -7,18 +7,15 @@ device view, replays every transcript against the reference, and asserts -- with
 holds the case it is named for.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from cpp_programs import download
+from cpp_programs import c_layout, download
 from test_align import replay
 from test_jst_collapse import REF_ALN, _alleles, _loci_where, _members, _records, np_collapse
 from test_jst_project import (DEL, EQ, INS, X, _cig, _hap, _make_tree, _open, _plant, _r, _row1_tree, _runs, _window)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---------------------------------------------------------------------------------------------------------------------
 # CPU: layout
@@ -41,12 +38,7 @@ CALLS = ("spm_hip_jst_ref_alns_normalize", "spm_hip_jst_ref_alns_normalize_stats
 
 def test_stats_layout_matches_the_header(spm, tmp_path):
     assert ctypes.sizeof(spm.capi.JstNormalizeStats) == 96
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert int(want.pop("sizeof.stats")) == 96
     for name, off in want.items():
         assert getattr(spm.capi.JstNormalizeStats, name).offset == int(off), name

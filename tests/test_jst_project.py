@@ -7,17 +7,14 @@ The expected answer never comes from the code under test:
       test_align: it consumes exactly P and that stretch, = / X agree with the symbols, runs are merged, cost = ref_score.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from cpp_programs import download
+from cpp_programs import c_layout, download
 from test_align import replay
 from test_gpu_jst import _apply, _random_alleles
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INS, DEL, EQ, X = 1, 2, 7, 8
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -43,12 +40,7 @@ int main(void)
 def test_record_layout_matches_the_header(spm, tmp_path):
     assert ctypes.sizeof(spm.capi.JstRefAln) == 40 == spm.JST_REF_ALN_DTYPE.itemsize
     assert ctypes.sizeof(spm.capi.JstProjectStats) == 64
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert int(want.pop("sizeof.aln")) == 40 and int(want.pop("sizeof.stats")) == 64
     n_rec = n_st = 0
     for name, off in want.items():

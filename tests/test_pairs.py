@@ -12,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from cpp_programs import ROOT, build_cases, build_mirror, download
+from cpp_programs import ROOT, build_cases, build_mirror, c_layout, download
 from test_jst_project import _make_tree, _plant, _window
 from test_strands import np_revcomp
 
@@ -61,12 +61,7 @@ def test_layouts_and_names(spm, tmp_path):
     import inspect
     assert ctypes.sizeof(spm.capi.JstPairOpts) == 16 and ctypes.sizeof(spm.capi.JstPairsStats) == 72
     assert ctypes.sizeof(spm.capi.JstPair) == 32 == spm.JST_PAIR_DTYPE.itemsize and spm.JST_PAIR_DTYPE == PAIR
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert (int(want.pop("sizeof.opts")), int(want.pop("sizeof.pair")), int(want.pop("sizeof.stats"))) == (16, 32, 72)
     seen = {"opts": 0, "pair": 0, "stats": 0}
     for name, off in want.items():

@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from cpp_programs import ROOT, build_cases, build_mirror, download
+from cpp_programs import ROOT, build_cases, build_mirror, c_layout, download
 from test_align import ref_begins, replay
 from test_jst_project import _hap, _make_tree, _window
 from test_pairs import _chain, _free_stretches
@@ -67,13 +67,8 @@ def test_layouts_and_names(spm, tmp_path):
     import inspect
     assert ctypes.sizeof(spm.capi.JstRescueOpts) == 20 and ctypes.sizeof(spm.capi.JstRescuesStats) == 80
     assert ctypes.sizeof(spm.capi.JstRescue) == 48 == spm.JST_RESCUE_DTYPE.itemsize and spm.JST_RESCUE_DTYPE == RESCUE
-    assert np.dtype(spm.capi.JST_RESCUE_DTYPE) == RESCUE
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert np.dtype(spm.capi.JstRescue) == RESCUE
+    want = c_layout(tmp_path, LAYOUT_C)
     assert (int(want.pop("sizeof.opts")), int(want.pop("sizeof.rescue")), int(want.pop("sizeof.stats"))) == (20, 48, 80)
     assert int(want.pop("status.values")) == 210 == RESCUED + 10 * NOTHING + 100 * NOT_CONCORDANT
     assert (spm.capi.RESCUE_RESCUED, spm.capi.RESCUE_NONE, spm.capi.RESCUE_NOT_CONCORDANT) == (RESCUED, NOTHING, NOT_CONCORDANT)

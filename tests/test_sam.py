@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from cpp_programs import ROOT, build_cases
+from cpp_programs import ROOT, build_cases, c_layout
 
 LINE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("read", "<u4"), ("source", "<u4"), ("flag", "<u2"), ("mapq", "u1"), ("kind", "u1")])
 OK, INVALID, OVERFLOW = 0, -1, -5
@@ -50,13 +50,8 @@ def test_layouts_and_names(spm, tmp_path):
     capi = spm.capi
     assert ctypes.sizeof(capi.SamOpts) == 64 and ctypes.sizeof(capi.SamStats) == 72
     assert ctypes.sizeof(capi.SamLine) == 24 == spm.SAM_LINE_DTYPE.itemsize and spm.SAM_LINE_DTYPE == LINE
-    assert np.dtype(capi.SAM_LINE_DTYPE) == LINE
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert np.dtype(capi.SamLine) == LINE
+    want = c_layout(tmp_path, LAYOUT_C)
     assert (int(want.pop("sizeof.opts")), int(want.pop("sizeof.line")), int(want.pop("sizeof.stats"))) == (64, 24, 72)
     assert int(want.pop("kind.values")) == 3210
     assert (capi.SAM_UNMAPPED, capi.SAM_LOCUS, capi.SAM_RESCUE, capi.SAM_SECONDARY_LINE) == (0, 1, 2, 3)

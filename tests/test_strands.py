@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from cpp_programs import ROOT, build_cases, build_mirror, download
+from cpp_programs import ROOT, build_cases, build_mirror, c_layout, download
 from test_align import replay
 from test_jst_project import _hap, _make_tree, _open, _plant, _window
 from test_jst_select import device_order, host_order
@@ -81,12 +81,7 @@ def test_layouts_and_names(spm, tmp_path):
     import inspect
     assert ctypes.sizeof(spm.capi.JstRead) == 32 == spm.JST_READ_DTYPE.itemsize and spm.JST_READ_DTYPE == READ
     assert ctypes.sizeof(spm.capi.JstReadsStats) == 48
-    src = tmp_path / "layout.c"
-    src.write_text(LAYOUT_C)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           "-o", str(exe), str(src)])
-    want = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = c_layout(tmp_path, LAYOUT_C)
     assert int(want.pop("sizeof.read")) == 32 and int(want.pop("sizeof.stats")) == 48
     assert int(want.pop("flag.strands")) == spm.capi.SELECT_STRANDS == spm.SELECT_STRANDS == 8
     n_rec = n_st = 0
