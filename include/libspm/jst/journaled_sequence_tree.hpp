@@ -185,6 +185,8 @@ struct jst_bam_options
     std::uint64_t ref_len{0};           // 1 .. 2^31 - 1
     std::uint32_t block_data{0};        // uncompressed bytes per BGZF block, 0: 65280
     bool deflate{false};                // the blocks compressed (spm_hip_bam_deflate / spm_hip_bgzf_deflate_host), not stored
+    bool sort{false};                   // the records in coordinate order under SO:coordinate (spm_hip_bam_sort)
+    bool index{false};                  // with sort: jst_bam::bai, the .bai of the file (spm_hip_bam_index / spm_hip_bai_build_host)
 };
 
 struct jst_bam
@@ -193,6 +195,7 @@ struct jst_bam
     std::vector<jst_sam_line> lines;
     std::uint64_t header_file_bytes{0}; // where the first record block starts
     std::vector<std::uint64_t> block_offsets; // with jst_bam_options::deflate only: the file offset of every record block, then their end
+    std::string bai;                    // with jst_bam_options::index: the bytes of the file's .bai
     bool operator==(jst_bam const &) const noexcept = default;
     // the BGZF virtual file offset of record i
     std::uint64_t virtual_offset(std::size_t i, std::uint32_t block_data = 0) const
@@ -1016,6 +1019,8 @@ public:
                     jst_bam_options const & options, hip::hit_selection const & selection, std::size_t block = 0,
                     jst_search_stats * stats = nullptr) const
     {
+        if (options.index && !options.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
         if (device_ready())
             return map_bam_device(needles, window, strands, n_reads, pairing, options, selection, block, stats);
         return map_bam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options, selection, block, stats);
@@ -1027,6 +1032,8 @@ public:
     {
         if (!device_ready())
             hip::fatal("journaled_sequence_tree::map_bam_device (tree not representable on the device)", hip::default_context());
+        if (options.index && !options.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
         jst_bam out;
         std::vector<jst_read> reads;
         std::vector<jst_pair> pairs;
@@ -1071,7 +1078,19 @@ public:
             return 0;
         };
         std::string const seq_letters = "=ACMGRSVTWYHKDBN", cigar_ops = "MIDNSHP=X";
+        if (o.index && !o.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", ctx);
         jst_bam out;
+        // the records in read order, and what coordinate order looks at: without a position or not, POS, the reverse strand
+        struct converted
+        {
+            std::string bytes; // block_size and all
+            jst_sam_line line;
+            bool unplaced;
+            std::int64_t pos;
+            bool reverse;
+        };
+        std::vector<converted> recs;
         for (std::size_t i = 0; i < sam.lines.size(); ++i) {
             std::string const line = sam.text.substr(sam.lines[i].offset, sam.lines[i].len - 1); // (without the \n)
             std::vector<std::string> f;
@@ -1132,18 +1151,35 @@ public:
                 rec.push_back(is_signed ? 'i' : 'I');
                 put(rec, is_signed ? static_cast<std::uint32_t>(std::stoll(f[t].substr(5))) : static_cast<std::uint32_t>(std::stoull(f[t].substr(5))), 4);
             }
-            out.lines.push_back({out.records.size(), static_cast<std::uint32_t>(rec.size() + 4), sam.lines[i].read, sam.lines[i].source,
-                                 sam.lines[i].flag, sam.lines[i].mapq, sam.lines[i].kind});
-            put(out.records, rec.size(), 4);
-            out.records += rec;
+            converted c{{}, {0, static_cast<std::uint32_t>(rec.size() + 4), sam.lines[i].read, sam.lines[i].source, sam.lines[i].flag,
+                             sam.lines[i].mapq, sam.lines[i].kind},
+                        f[2] == "*", pos, (std::stoul(f[1]) & 0x10u) != 0};
+            put(c.bytes, rec.size(), 4);
+            c.bytes += rec;
+            recs.push_back(std::move(c));
+        }
+        // coordinate order: the records of the reference first, by position, forward before reverse; ties stay in read order
+        if (o.sort)
+            std::stable_sort(recs.begin(), recs.end(), [](converted const & a, converted const & b) {
+                if (a.unplaced != b.unplaced)
+                    return b.unplaced;
+                if (a.pos != b.pos)
+                    return a.pos < b.pos;
+                return !a.reverse && b.reverse;
+            });
+        for (converted & c : recs) {
+            c.line.offset = out.records.size();
+            out.lines.push_back(c.line);
+            out.records += c.bytes;
         }
         // the header: BAM\1, l_text, the SAM header, one reference; framed on its own, then the records and the EOF block
         std::uint64_t n_text = 0;
-        if (spm_hip_sam_header(o.sam.rname.c_str(), o.ref_len, nullptr, 0, &n_text) != SPM_E_OVERFLOW || o.ref_len == 0 ||
+        auto const header_text = o.sort ? spm_hip_sam_header_sorted : spm_hip_sam_header;
+        if (header_text(o.sam.rname.c_str(), o.ref_len, nullptr, 0, &n_text) != SPM_E_OVERFLOW || o.ref_len == 0 ||
             o.ref_len > 0x7FFFFFFFull)
             hip::fatal("journaled_sequence_tree::map_bam (rname or ref_len)", ctx);
         std::string text(n_text, '\0'), plain = std::string("BAM\1", 4);
-        if (spm_hip_sam_header(o.sam.rname.c_str(), o.ref_len, text.data(), n_text, &n_text) != SPM_OK)
+        if (header_text(o.sam.rname.c_str(), o.ref_len, text.data(), n_text, &n_text) != SPM_OK)
             hip::fatal("spm_hip_sam_header", ctx);
         put(plain, n_text, 4);
         plain += text;
@@ -1177,6 +1213,26 @@ public:
                  at += (static_cast<std::uint8_t>(out.file[at + 16]) | static_cast<std::uint64_t>(static_cast<std::uint8_t>(out.file[at + 17])) << 8) + 1)
                 out.block_offsets.push_back(at);
             out.block_offsets.push_back(at);
+        }
+        if (o.index) { // over the block offsets of the file just written: found above, or the closed form of stored blocks
+            std::uint64_t const D = o.block_data ? o.block_data : 65280u, n_blocks = (out.records.size() + D - 1) / D;
+            std::vector<std::uint64_t> offsets = out.block_offsets;
+            if (!o.deflate) {
+                for (std::uint64_t b = 0; b < n_blocks; ++b)
+                    offsets.push_back(out.header_file_bytes + b * (D + 31));
+                offsets.push_back(out.header_file_bytes + out.records.size() + 31 * n_blocks);
+            }
+            std::vector<spm_sam_line> lines;
+            for (jst_sam_line const & l : out.lines)
+                lines.push_back(spm_sam_line{l.offset, l.len, l.read, l.source, l.flag, l.mapq, l.kind});
+            std::uint64_t need = 0;
+            if (spm_hip_bai_build_host(out.records.data(), out.records.size(), lines.data(), lines.size(), offsets.data(), n_blocks,
+                                       o.block_data, nullptr, 0, &need) != SPM_E_OVERFLOW)
+                hip::fatal("spm_hip_bai_build_host", ctx);
+            out.bai.assign(need, '\0');
+            if (spm_hip_bai_build_host(out.records.data(), out.records.size(), lines.data(), lines.size(), offsets.data(), n_blocks,
+                                       o.block_data, out.bai.data(), need, &need) != SPM_OK)
+                hip::fatal("spm_hip_bai_build_host", ctx);
         }
         return out;
     }
@@ -1772,6 +1828,28 @@ private:
             if (spm_hip_jst_ref_loci_bam(l, rd, pr, rs, req.needles, &bopts, &b) != SPM_OK)
                 hip::fatal("spm_hip_jst_ref_loci_bam", ctx);
             std::unique_ptr<spm_bam, decltype(&spm_hip_bam_destroy)> owner{b, &spm_hip_bam_destroy};
+            if (req.bam_options->sort) { // the handle in coordinate order takes the place of the one in read order
+                spm_bam * sorted = nullptr;
+                if (spm_hip_bam_sort(b, nullptr, &sorted) != SPM_OK)
+                    hip::fatal("spm_hip_bam_sort", ctx);
+                owner.reset(sorted);
+                b = sorted;
+            }
+            spm_bgzf * index_of = nullptr; // the deflated file, where the index is the deflated file's
+            auto const index = [&] {
+                req.bam_out->bai.clear();
+                if (!req.bam_options->index)
+                    return;
+                spm_bai * bai = nullptr;
+                if (spm_hip_bam_index(b, index_of, &bai) != SPM_OK)
+                    hip::fatal("spm_hip_bam_index", ctx);
+                std::unique_ptr<spm_bai, decltype(&spm_hip_bai_destroy)> bai_owner{bai, &spm_hip_bai_destroy};
+                void const * bytes = nullptr;
+                std::uint64_t n = 0;
+                if (spm_hip_bai_view(bai, &bytes, &n) != SPM_OK)
+                    hip::fatal("spm_hip_bai_view", ctx);
+                req.bam_out->bai.assign(static_cast<char const *>(bytes), n);
+            };
             void const * file = nullptr;
             void const * records = nullptr;
             spm_sam_line const * lines = nullptr;
@@ -1798,6 +1876,10 @@ private:
                 req.bam_out->file.assign(static_cast<char const *>(file), n_file);
                 req.bam_out->header_file_bytes = ds.n_prefix_bytes;
                 req.bam_out->block_offsets.assign(offsets, offsets + n_blocks + 1);
+                index_of = z;
+                index();
+            } else {
+                index();
             }
             req.bam_out->lines.clear();
             for (std::uint64_t i = 0; i < n_lines; ++i)

@@ -1245,6 +1245,105 @@ int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data,
  * result needs the BAM handle no longer once the call returns. */
 int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out);
 
+/* ---- coordinate-sorted BAM and its BAI index: what a variant caller, a pile-up and `samtools view chr:a-b` need -----------
+ * spm_hip_bam_sort returns a NEW spm_bam with the records of b in coordinate order: view, device, stats, destroy,
+ * spm_hip_bam_deflate and this call again work on it unchanged.  Its header section says SO:coordinate
+ * (spm_hip_sam_header_sorted / spm_hip_bam_header_sorted are the host-only siblings of the header calls, which keep their
+ * bytes), its line records are those of b, permuted, with their new offset.  The counts and byte totals of its spm_bam_stats
+ * are the new file's; the stage times of the call are spm_hip_bam_sort_stats' (SPM_E_INVALID on a handle no sort made).
+ * The order: refID as unsigned (0, then -1), then pos, then forward before reverse (flag 0x10); ties keep the order of b.  A
+ * placed unmapped mate (refID 0, pos the mate's) therefore stands beside its mate; records with refID -1 go to the end.
+ * Sorting a sorted handle gives byte-identical views.  Zero records: the header section and the EOF block.
+ *   * SPM_E_INVALID: NULL b or out; a nonzero reserved (opts may be NULL).  SPM_E_UNSUPPORTED: more than 2^32 - 1 records
+ *     (cannot occur today).  A handle whose line records do not name records of its stream (they always do) fails with
+ *     SPM_E_INVALID after one read-back, and nothing is returned.
+ *
+ * spm_hip_bam_index builds the BAI (SAM specification 5.2) of the handle's own stored file, or, with `deflated` the result of
+ * spm_hip_bam_deflate(b, ...) in blocks of the same block_data, of that file; spm_hip_bai_build is the raw form over any
+ * device record stream, its spm_sam_line records (offset / len), and the n_blocks + 1 file offsets of its blocks;
+ * spm_hip_bai_build_host the same bytes by a serial walk on the host, no device needed.  The rule:
+ *   * A record's interval is [pos, pos + max(span, 1)), span the reference symbols of its CIGAR (M D N = X); pos + 1 with
+ *     flag 0x4 or without CIGAR -- what the writer binned it with.  Its bin is the record's bin field.
+ *   * The virtual offset of stream offset u is offsets[u / D] << 16 | u % D.  A record begins at that of its offset and ends
+ *     at that of offset + len: a record that ends on a block border ends at the next block's first byte, the stream's last
+ *     one possibly at the EOF block.
+ *   * The file: "BAI\1", n_ref = 1, n_bin, the bins, n_intv, the linear index, n_no_coor (always written), little-endian.
+ *   * A bin's chunks are the maximal runs of CONSECUTIVE records in file order that carry the bin: (begin of the first,
+ *     end of the last).  Bins in ascending number, a bin's chunks in file order, not merged further (htslib also merges
+ *     chunks that meet in one block; a reader finds the same records either way).
+ *   * If the reference has a record, the pseudo-bin 37450 comes last and counts in n_bin: (begin of the first placed record,
+ *     end of the last), (n_mapped, n_unmapped) = the records with refID >= 0 without / with flag 0x4.
+ *   * n_intv = ((max end - 1) >> 14) + 1 over the placed records; ioffset[w] the smallest begin among the records that
+ *     overlap window w, an empty window taking the value of the next one to its right that is not.
+ *   * n_no_coor: the records with refID -1.
+ * Worked cases.  No records: 24 bytes,  42414901 01000000 00000000 00000000 0000000000000000.
+ * Four records of one name byte and at most one CIGAR word, block_data 100, stored blocks from file offset 0 (offsets 0, 131,
+ * 226):  42 bytes at 0, pos 100, 50M (bin 4681);  42 at 42, pos 16380, 10M (crosses 2^14: bin 585);  42 at 84, pos 16390, 10M,
+ * reverse (bin 4682, ends in block 1 at byte 26);  38 at 126, refID -1.  152 bytes:
+ *     42414901 01000000 04000000
+ *     49020000 01000000 2a00000000000000 5400000000000000
+ *     49120000 01000000 0000000000000000 2a00000000000000
+ *     4a120000 01000000 5400000000000000 1a00830000000000
+ *     4a920000 02000000 0000000000000000 1a00830000000000 0300000000000000 0000000000000000
+ *     02000000 0000000000000000 2a00000000000000
+ *     0100000000000000
+ *   * SPM_E_INVALID, decided on the host: NULL b, ctx or out; NULL buffers with nonzero counts; block_data above 65280 (0:
+ *     65280); n_blocks that is not what n_record_bytes in blocks of block_data give; records without lines or lines without
+ *     records; a `deflated` of another context, input length or block size.  SPM_E_UNSUPPORTED: more than 2^32 - 1 records.
+ *   * Counted on the device, tested before a value is used as an index, and failing the call with SPM_E_INVALID and nothing
+ *     written: a record out of coordinate order (key(i) < key(i - 1)); a line that leaves the stream or does not start
+ *     where the one before it ended (the first at 0, the last ending the stream); a block_size that is not len - 4; a name
+ *     and CIGAR that leave the record; a refID other than 0 and -1; a placed record with pos < 0, an end beyond 2^29 (the
+ *     reach of a BAI) or a bin field beyond 37448.
+ * One read-back brings the counts, which give the size, and the error counter.  A pure function of its inputs: host and
+ * device builder agree byte for byte (min into the linear index does not depend on order). */
+typedef struct spm_bam_sort_opts {  /* 8 bytes */
+    uint64_t reserved;              /* must be 0 */
+} spm_bam_sort_opts;
+typedef struct spm_bam_sort_stats { /* 48 bytes */
+    float ms_total;                 /* device: the five stages below (HIP events) */
+    float ms_keys;                  /* the key fields of every record out of the stream */
+    float ms_sort;                  /* the stable radix sort of (key, record index) over key_bits */
+    float ms_place;                 /* the new offsets, the permuted line records */
+    float ms_gather;                /* the records to their new place, one wave per record */
+    float ms_frame;                 /* the new stream into BGZF blocks behind the new header section, the EOF block */
+    float ms_host;                  /* wall clock of the whole call */
+    uint32_t key_bits;              /* what ref_len needs, the strand bit and the refID bit */
+    uint64_t n_records;
+    uint64_t n_record_bytes;
+} spm_bam_sort_stats;
+int spm_hip_bam_sort(spm_bam *b, const spm_bam_sort_opts *opts /* NULL: defaults */, spm_bam **out);
+int spm_hip_bam_sort_stats(const spm_bam *b, spm_bam_sort_stats *out);
+/* host only: spm_hip_sam_header / spm_hip_bam_header with "SO:coordinate" */
+int spm_hip_sam_header_sorted(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len);
+int spm_hip_bam_header_sorted(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len);
+typedef struct spm_bai spm_bai;
+typedef struct spm_bai_stats {      /* 80 bytes */
+    float ms_total;                 /* device: the four stages below (HIP events) */
+    float ms_records;               /* every record's item, the order test, the linear index's minima, the counts */
+    float ms_chunks;                /* runs into chunks, the chunks ordered by bin */
+    float ms_bins;                  /* bin heads, the byte offsets */
+    float ms_write;                 /* the back-fill of the linear index, the bytes */
+    float ms_host;                  /* wall clock of the whole call */
+    uint64_t n_bins;                /* the file's n_bin: the pseudo-bin is counted */
+    uint64_t n_chunks;              /* of the bins that hold records */
+    uint64_t n_intv;
+    uint64_t n_mapped;
+    uint64_t n_unmapped;
+    uint64_t n_no_coor;
+    uint64_t n_bytes;
+} spm_bai_stats;
+int spm_hip_bam_index(spm_bam *b, spm_bgzf *deflated /* NULL: the handle's own stored file */, spm_bai **out);
+int spm_hip_bai_build(spm_ctx *ctx, const void *device_records, uint64_t n_record_bytes, const void *device_lines, uint64_t n_lines,
+                      const void *device_block_offsets, uint64_t n_blocks, uint32_t block_data, spm_bai **out);
+int spm_hip_bai_build_host(const void *records, uint64_t n_record_bytes, const spm_sam_line *lines, uint64_t n_lines,
+                           const uint64_t *block_offsets, uint64_t n_blocks, uint32_t block_data, void *dst, uint64_t cap, uint64_t *len);
+/* every pointer may be NULL */
+int spm_hip_bai_view(spm_bai *z, const void **bytes, uint64_t *n);
+int spm_hip_bai_device(spm_bai *z, const void **bytes, uint64_t *n);
+int spm_hip_bai_stats(const spm_bai *z, spm_bai_stats *out);
+void spm_hip_bai_destroy(spm_bai *z);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

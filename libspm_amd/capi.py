@@ -311,6 +311,23 @@ class BamStats(C.Structure):
     ]
 
 
+class BamSortOpts(C.Structure):
+    _fields_ = [("reserved", C.c_uint64)]
+
+
+class BamSortStats(C.Structure):
+    _fields_ = [("ms_total", C.c_float), ("ms_keys", C.c_float), ("ms_sort", C.c_float), ("ms_place", C.c_float),
+                ("ms_gather", C.c_float), ("ms_frame", C.c_float), ("ms_host", C.c_float), ("key_bits", C.c_uint32),
+                ("n_records", C.c_uint64), ("n_record_bytes", C.c_uint64)]
+
+
+class BaiStats(C.Structure):
+    _fields_ = [("ms_total", C.c_float), ("ms_records", C.c_float), ("ms_chunks", C.c_float), ("ms_bins", C.c_float),
+                ("ms_write", C.c_float), ("ms_host", C.c_float), ("n_bins", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("n_intv", C.c_uint64), ("n_mapped", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_no_coor", C.c_uint64),
+                ("n_bytes", C.c_uint64)]
+
+
 class BgzfOpts(C.Structure):
     _fields_ = [("block_data", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
@@ -541,6 +558,18 @@ SIGNATURES = {
     "spm_hip_bgzf_deflate_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "spm_hip_bgzf_deflate_bound": (C.c_int, [C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(C.c_uint64)]),
     "spm_hip_bam_deflate": (C.c_int, [_vp, C.POINTER(BgzfDeflateOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_sort": (C.c_int, [_vp, C.POINTER(BamSortOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_sort_stats": (C.c_int, [_vp, C.POINTER(BamSortStats)]),
+    "spm_hip_sam_header_sorted": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_bam_header_sorted": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spm_hip_bam_index": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spm_hip_bai_build": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "spm_hip_bai_build_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64,
+                                         C.POINTER(C.c_uint64)]),
+    "spm_hip_bai_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_bai_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_bai_stats": (C.c_int, [_vp, C.POINTER(BaiStats)]),
+    "spm_hip_bai_destroy": (None, [_vp]),
     "spm_hip_jst_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),

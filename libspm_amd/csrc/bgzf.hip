@@ -2,7 +2,8 @@
 // kernel), its view / device / stats / destroy, and the two host-only calls over the serial framer of bgzf_core.hpp,
 // spm_hip_bgzf_frame_host and spm_hip_bgzf_framed_size; spm_hip_bgzf_deflate (bgzf_deflate.hpp has the kernels), the stages
 // behind it for spm_hip_bam_deflate, the blocks' offsets of either kind of handle, and the host-only calls over the serial
-// deflater of bgzf_deflate_core.hpp.
+// deflater of bgzf_deflate_core.hpp.  Behind them bam_index.hpp: spm_hip_bam_sort, spm_hip_bam_index and the calls around them, which
+// read both kinds of handle.
 #include "internal.hpp"
 #include "bgzf.hpp"
 #include "bgzf_deflate.hpp"
@@ -388,10 +389,15 @@ extern "C" int spm_hip_bgzf_deflate_stats(const spm_bgzf *z, spm_bgzf_deflate_st
     return SPM_OK;
 }
 
+// ---- a BAM handle in coordinate order and the BAI index of one: they read the handles above ----
+#include "bam_index.hpp"
+
 void spm_warm_bgzf_kernels()
 {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_frame_kernel);
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel);
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_place_kernel);
+    (void)hipFuncGetAttributes(&a, (const void *)bam_gather_kernel);
+    (void)hipFuncGetAttributes(&a, (const void *)bai_records_kernel);
 }

@@ -4,7 +4,7 @@
 // filter_verify.hip (filter_launch.hpp); hits.hip: results; align.hip: alignments of hits; select.hip: selection of hits;
 // device_order.hip: the pair sort of the drivers that order records (device_order.hpp); jst.hip: journaled sequences, with
 // jst_align.hip, jst_ref.hip, jst_reads.hip and jst_sam.hip behind it (map in jst.hpp) and jst_select.hip beside it;
-// bgzf.hip: BGZF framing and deflate; comm.hip: the multi-GPU exchange.)
+// bgzf.hip: BGZF framing and deflate, and behind them the sorted BAM and its BAI index; comm.hip: the multi-GPU exchange.)
 #pragma once
 
 #include <algorithm>
@@ -238,6 +238,12 @@ hipError_t bgzf_frame_enqueue(spm_ctx *ctx, const void *d_src, uint64_t n, uint3
 // new handle whose offsets count from the prefix's first byte.  The opts have passed spm_hip_bgzf_deflate's checks. ----
 int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t n, const spm_bgzf_deflate_opts *opts,
                      const std::vector<uint8_t> &prefix, spm_bgzf **out);
+
+// ---- the header section of a BAM file before its framing (jst_bam.hpp), for the call that writes one and for spm_hip_bam_sort
+// (bam_index.hpp), which writes it again with SO:coordinate ----
+#pragma GCC visibility push(hidden)
+int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t ref_len, bool sorted, std::vector<uint8_t> &h);
+#pragma GCC visibility pop
 
 // deferred scans (SPM_SCAN_DEFER): read the counters back, and repeat the scan if it needs attention   (scan.hip)
 int spm_complete_deferred(spm_hits *h);

@@ -151,9 +151,11 @@ extern "C" void spm_hip_bam_destroy(spm_bam *b)
     delete b;
 }
 
-// the plain header: BAM\1, l_text, the text of spm_hip_sam_header, n_ref = 1, l_name, the name with its NUL, l_ref
-static int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t ref_len, std::vector<uint8_t> &h)
+// the plain header: BAM\1, l_text, the text of spm_hip_sam_header (sorted: of spm_hip_sam_header_sorted), n_ref = 1, l_name, the
+// name with its NUL, l_ref
+int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t ref_len, bool sorted, std::vector<uint8_t> &h)
 {
+    const auto text = sorted ? spm_hip_sam_header_sorted : spm_hip_sam_header;
     if (ref_len == 0) {
         SPM_SET_ERR(ctx, "%s: ref_len is 0", who);
         return SPM_E_INVALID;
@@ -164,7 +166,7 @@ static int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, ui
         return SPM_E_UNSUPPORTED;
     }
     uint64_t n_text = 0;
-    int rc = spm_hip_sam_header(rname, ref_len, nullptr, 0, &n_text);
+    int rc = text(rname, ref_len, nullptr, 0, &n_text);
     if (rc != SPM_E_OVERFLOW) {
         if (ctx && rc == SPM_E_INVALID)
             SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
@@ -178,7 +180,7 @@ static int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, ui
     };
     memcpy(h.data(), "BAM\1", 4);
     put32(4, (uint32_t)n_text);
-    SPM_TRY(spm_hip_sam_header(rname, ref_len, reinterpret_cast<char *>(h.data()) + 8, n_text, &n_text));
+    SPM_TRY(text(rname, ref_len, reinterpret_cast<char *>(h.data()) + 8, n_text, &n_text));
     put32(8 + n_text, 1);
     put32(12 + n_text, l_name);
     memcpy(h.data() + 16 + n_text, rname, l_name - 1);
@@ -186,9 +188,9 @@ static int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, ui
     return SPM_OK;
 }
 
-extern "C" int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len)
+static int bam_header_framed(const char *who, bool sorted, const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap,
+                             uint64_t *len)
 {
-    static const char *const who = "spm_hip_bam_header";
     if (!rname || !len || (!buf && cap)) {
         SPM_SET_ERR((spm_ctx *)nullptr, "%s: NULL %s", who, !rname ? "rname" : !len ? "len" : "buf with cap > 0");
         return SPM_E_INVALID;
@@ -198,9 +200,19 @@ extern "C" int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t 
         return SPM_E_INVALID;
     }
     std::vector<uint8_t> plain;
-    SPM_TRY(bam_plain_header(who, nullptr, rname, ref_len, plain));
+    SPM_TRY(bam_plain_header(who, nullptr, rname, ref_len, sorted, plain));
     const spm_bgzf_opts o{block_data, 0, 0};
     return spm_hip_bgzf_frame_host(plain.data(), plain.size(), &o, buf, cap, len);
+}
+
+extern "C" int spm_hip_bam_header(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len)
+{
+    return bam_header_framed("spm_hip_bam_header", false, rname, ref_len, block_data, buf, cap, len);
+}
+
+extern "C" int spm_hip_bam_header_sorted(const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap, uint64_t *len)
+{
+    return bam_header_framed("spm_hip_bam_header_sorted", true, rname, ref_len, block_data, buf, cap, len);
 }
 
 extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
@@ -229,7 +241,7 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         return SPM_E_INVALID;
     }
     std::vector<uint8_t> plain, header;
-    SPM_TRY(bam_plain_header(who, ctx, opts->sam.rname, opts->ref_len, plain));
+    SPM_TRY(bam_plain_header(who, ctx, opts->sam.rname, opts->ref_len, false, plain));
     const uint32_t D = bgzf_block_data(opts->block_data);
     header.resize(bgzf_framed_size(plain.size(), D, false));
     bgzf_frame_serial(plain.data(), plain.size(), D, false, header.data());
@@ -275,6 +287,9 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         return SPM_E_UNSUPPORTED;
     }
     R->plain_header = plain;
+    R->rname = opts->sam.rname;
+    R->ref_len = opts->ref_len;
+    R->block_data = D;
     R->n_lines = B.P.n_lines;
     R->n_record_bytes = n_records;
     R->n_file = header.size() + bgzf_framed_size(n_records, D, true);

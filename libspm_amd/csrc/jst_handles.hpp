@@ -8,10 +8,11 @@
 //   spm_jst_reads      jst_reads.hpp                                       read by jst_pairs.hpp .. jst_bam.hpp
 //   spm_jst_pairs      jst_pairs.hpp                                       read by jst_rescue.hpp .. jst_bam.hpp
 //   spm_jst_rescues    jst_rescue.hpp                                      read by jst_sam.hpp, jst_bam.hpp
-//   spm_sam, spm_bam   jst_sam.hpp, jst_bam.hpp
+//   spm_sam, spm_bam   jst_sam.hpp, jst_bam.hpp                              spm_bam read by bam_index.hpp (sort, index)
 // (spm_jst_hits, which jst_select.hip shares, is common.hpp's.)  Host structs only: no kernel, no C-ABI definition.
 #pragma once
 
+#include <string>
 #include <vector>
 
 #include "common.hpp"
@@ -219,5 +220,11 @@ struct spm_bam
     std::vector<spm_sam_line> host_lines;
     std::vector<uint8_t> plain_header; // the header section before its framing: what spm_hip_bam_deflate compresses again
     spm_bam_stats stats{};
+    // what spm_hip_bam_sort writes the new header section from, and spm_hip_bam_index the stored blocks' offsets (bam_index.hpp)
+    std::string rname;
+    uint64_t ref_len = 0;
+    uint32_t block_data = 0; // uncompressed bytes of a full block: never 0
+    bool sorted = false;     // made by spm_hip_bam_sort, which then filled sort_stats
+    spm_bam_sort_stats sort_stats{};
 };
 static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");

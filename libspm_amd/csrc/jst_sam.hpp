@@ -297,7 +297,7 @@ extern "C" int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint3
     return spm_hip::jst_sam_mapq(spm_hip::jst_sam_tables_of(*opts), n_best, n_next);
 }
 
-extern "C" int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len)
+static int sam_header_text(const char *so, const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len)
 {
     if (!rname || !len || (!buf && cap))
         return SPM_E_INVALID;
@@ -305,12 +305,22 @@ extern "C" int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf
         SPM_SET_ERR((spm_ctx *)nullptr, "spm_hip_sam_header: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'");
         return SPM_E_INVALID;
     }
-    const std::string h = std::string("@HD\tVN:1.6\tSO:unknown\n@SQ\tSN:") + rname + "\tLN:" + std::to_string(ref_len) + "\n";
+    const std::string h = std::string("@HD\tVN:1.6\tSO:") + so + "\n@SQ\tSN:" + rname + "\tLN:" + std::to_string(ref_len) + "\n";
     *len = h.size();
     if (h.size() > cap)
         return SPM_E_OVERFLOW;
     memcpy(buf, h.data(), h.size());
     return SPM_OK;
+}
+
+extern "C" int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len)
+{
+    return sam_header_text("unknown", rname, ref_len, buf, cap, len);
+}
+
+extern "C" int spm_hip_sam_header_sorted(const char *rname, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len)
+{
+    return sam_header_text("coordinate", rname, ref_len, buf, cap, len);
 }
 
 // ---- the front that spm_hip_jst_ref_loci_sam and spm_hip_jst_ref_loci_bam share: what is refused on the host, and the lines

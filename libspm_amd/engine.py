@@ -184,6 +184,16 @@ class Context:
         source is read before the call returns."""
         return self._bgzf(capi.lib().spm_hip_bgzf_frame, bgzf_opts(block_data, eof), device_ptr, n)
 
+    def bai(self, records: int, n_record_bytes: int, lines: int, n_lines: int, block_offsets: int, n_blocks: int,
+            block_data: int = 0) -> "Bai":
+        """The BAI index of a coordinate-sorted record stream in device memory (spm_hip_bai_build), the raw form of Bam.index():
+        records / lines / block_offsets are device pointers to the uncompressed stream, its SAM_LINE_DTYPE records (offset and
+        len are read) and the n_blocks + 1 file offsets of its blocks of block_data uncompressed bytes (0: 65280)."""
+        z = C.c_void_p()
+        _check(capi.lib().spm_hip_bai_build(self._h, C.c_void_p(records), int(n_record_bytes), C.c_void_p(lines), int(n_lines),
+                                            C.c_void_p(block_offsets), int(n_blocks), int(block_data), C.byref(z)), self._h)
+        return Bai(self, z)
+
     def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
         block; a block that would not shrink stays stored).  The same arguments; the bytes are those of bgzf_deflate_host."""
@@ -844,14 +854,15 @@ def sam_mapq(n_best: int, n_next: int, mapq_unique=None, mapq_multi=None) -> int
     return int(capi.lib().spm_hip_sam_mapq(C.byref(opts), min(int(n_best), 0xFFFFFFFF), min(int(n_next), 0xFFFFFFFF)))
 
 
-def sam_header(rname, ref_len: int) -> bytes:
-    """The @HD and @SQ lines (spm_hip_sam_header).  Needs no device."""
+def sam_header(rname, ref_len: int, sorted: bool = False) -> bytes:
+    """The @HD and @SQ lines (spm_hip_sam_header; sorted: spm_hip_sam_header_sorted, SO:coordinate).  Needs no device."""
     rname = rname.encode() if isinstance(rname, str) else bytes(rname)
+    call = capi.lib().spm_hip_sam_header_sorted if sorted else capi.lib().spm_hip_sam_header
 
     def refuse(rc):
         raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_header refused rname {rname!r}")
 
-    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_sam_header(rname, int(ref_len), buf, cap, need), refuse)
+    return _size_then_fill(lambda buf, cap, need: call(rname, int(ref_len), buf, cap, need), refuse)
 
 
 class Sam(_Handle):
@@ -909,11 +920,24 @@ class Sam(_Handle):
         return self._bgzf(self.ctx.bgzf_deflate, bgzf_deflate_host, ref_len, block_data, eof)
 
 
-def bam_header(rname, ref_len: int, block_data: int = 0) -> bytes:
-    """The framed header section of a BAM file (spm_hip_bam_header).  Needs no device."""
+def bam_header(rname, ref_len: int, block_data: int = 0, sorted: bool = False) -> bytes:
+    """The framed header section of a BAM file (spm_hip_bam_header; sorted: spm_hip_bam_header_sorted).  Needs no device."""
     rname = rname.encode() if isinstance(rname, str) else bytes(rname)
-    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_bam_header(rname, int(ref_len), int(block_data), buf, cap, need),
+    call = capi.lib().spm_hip_bam_header_sorted if sorted else capi.lib().spm_hip_bam_header
+    return _size_then_fill(lambda buf, cap, need: call(rname, int(ref_len), int(block_data), buf, cap, need),
                            lambda rc: _check(rc if rc else -1, None))
+
+
+def bai_build_host(records, lines, block_offsets, block_data: int = 0) -> bytes:
+    """The BAI index of a coordinate-sorted record stream by the serial host builder (spm_hip_bai_build_host): records the
+    uncompressed stream, lines its SAM_LINE_DTYPE records, block_offsets the n_blocks + 1 file offsets of its blocks of
+    block_data uncompressed bytes (0: 65280).  Needs no device."""
+    records = bytes(records)
+    lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
+    offs = np.ascontiguousarray(block_offsets, dtype=np.uint64)
+    src = C.create_string_buffer(records, len(records) + 1)
+    return _size_then_fill(lambda dst, cap, need: capi.lib().spm_hip_bai_build_host(
+        src, len(records), lines.ctypes.data, len(lines), offs.ctypes.data, max(len(offs), 1) - 1, int(block_data), dst, cap, need))
 
 
 class Bam(_Handle):
@@ -958,6 +982,21 @@ class Bam(_Handle):
         opts = bgzf_deflate_opts(block_data, eof)
         return Bgzf(self.ctx, self._new("deflate", C.byref(opts)), block_data=_block_data(block_data))
 
+    def sort(self) -> "Bam":
+        """A new Bam with these records in coordinate order (spm_hip_bam_sort): reference position, forward before reverse,
+        ties in this object's order, records without a position last; the header says SO:coordinate.  What index() takes."""
+        opts = capi.BamSortOpts(reserved=0)
+        return Bam(self.ctx, self._new("sort", C.byref(opts)), self.block_data)
+
+    def sort_stats(self) -> capi.BamSortStats:
+        """the stage times of the sort() that made this object"""
+        return self._stats(capi.BamSortStats, "sort_stats")
+
+    def index(self, deflated: "Bgzf | None" = None) -> "Bai":
+        """The BAI index of this coordinate-sorted file (spm_hip_bam_index), or, with deflated = self.deflate(block_data) in
+        blocks of this object's block_data, of that file.  An unsorted object is refused."""
+        return Bai(self.ctx, self._new("index", _or_null(deflated)))
+
     def device(self):
         """(file, n_file, records, n_record_bytes, lines, n_lines): device pointers and counts"""
         f, r, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -967,6 +1006,23 @@ class Bam(_Handle):
 
     def stats(self) -> capi.BamStats:
         return self._stats(capi.BamStats)
+
+
+class Bai(_Handle):
+    """Result of Bam.index() and Context.bai(): the bytes of a .bai file in device memory.  (Made by those two calls only, so the
+    package does not export the name; it is libspm_amd.engine.Bai.)"""
+    _PREFIX = "bai"
+
+    def bytes(self) -> bytes:
+        p, n = self._span("view")
+        return C.string_at(p, n) if n else b""
+
+    def device(self):
+        """(bytes, n): device pointer and count"""
+        return self._span("device")
+
+    def stats(self) -> capi.BaiStats:
+        return self._stats(capi.BaiStats)
 
 
 def bgzf_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfOpts:
