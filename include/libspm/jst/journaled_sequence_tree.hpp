@@ -165,6 +165,10 @@ struct jst_sam_options
     bool cigar_m{false}, secondary{false};
     bool default_tables{true};          // false: the two tables below
     std::array<std::uint8_t, 4> mapq_unique{60, 40, 30, 20}, mapq_multi{3, 1, 1, 0};
+    // spm_sam_extras: the base qualities, Phred 0 .. 93 as sequenced, one vector per read (empty: none, QUAL "*"); an MD:Z: tag
+    // behind NM on every line with a CIGAR, against the tree's reference
+    std::vector<std::vector<std::uint8_t>> qualities;
+    bool md{false};
 };
 
 // what stands between the loci and the lines of map_sam: nothing (single-end), the pairing, the pairing and the mate rescue
@@ -984,7 +988,7 @@ public:
         spm_jst_pair_opts const opts{pairing.min_tlen, pairing.max_tlen, 0, 0};
         rescue_request const rescue{spm_jst_rescue_opts{pairing.min_tlen, pairing.max_tlen, pairing.k, 0, 0}, _device->reference.get(),
                                     needles, &rescues, &rescue_ops};
-        sam_request const sam{&options, needles, &out};
+        sam_request const sam{&options, needles, &out, nullptr, nullptr, _device->reference.get()};
         loci_of(device_alns(needles, window, selection, block, stats).get(), true, pairing.paired ? 2 : strands, n_reads, &reads,
                 pairing.paired ? &opts : nullptr, pairing.paired ? &pairs : nullptr,
                 pairing.paired && pairing.rescue ? &rescue : nullptr, &sam);
@@ -999,15 +1003,15 @@ public:
         if (pairing.paired && pairing.rescue) { // (the rescue search itself has one route: the device's)
             jst_rescued_pair_loci const R = locate_pairs_rescued(needles, window, n_reads, pairing.min_tlen, pairing.max_tlen, pairing.k,
                                                                  selection, block, stats);
-            return sam_host(R.located.mapped, &R.located.pairs, &R.rescues, needle_ranks, 2, options);
+            return sam_host(R.located.mapped, &R.located.pairs, &R.rescues, needle_ranks, 2, options, &_reference);
         }
         if (pairing.paired) {
             jst_pair_loci const P = locate_pairs(needles, window, needle_ranks, reports_begin, n_reads, pairing.min_tlen, pairing.max_tlen,
                                                  selection, block, stats);
-            return sam_host(P.mapped, &P.pairs, nullptr, needle_ranks, 2, options);
+            return sam_host(P.mapped, &P.pairs, nullptr, needle_ranks, 2, options, &_reference);
         }
         return sam_host(locate_reads(needles, window, needle_ranks, reports_begin, strands, n_reads, selection, block, stats), nullptr,
-                        nullptr, needle_ranks, strands, options);
+                        nullptr, needle_ranks, strands, options, &_reference);
     }
 
     // ---- the same mapping as a BAM file (the contract of spm_hip_jst_ref_loci_bam in spm_hip.h).  Device route: the chain plus
@@ -1042,7 +1046,7 @@ public:
         spm_jst_pair_opts const opts{pairing.min_tlen, pairing.max_tlen, 0, 0};
         rescue_request const rescue{spm_jst_rescue_opts{pairing.min_tlen, pairing.max_tlen, pairing.k, 0, 0}, _device->reference.get(),
                                     needles, &rescues, &rescue_ops};
-        sam_request const bam{&options.sam, needles, nullptr, &options, &out};
+        sam_request const bam{&options.sam, needles, nullptr, &options, &out, _device->reference.get()};
         loci_of(device_alns(needles, window, selection, block, stats).get(), true, pairing.paired ? 2 : strands, n_reads, &reads,
                 pairing.paired ? &opts : nullptr, pairing.paired ? &pairs : nullptr,
                 pairing.paired && pairing.rescue ? &rescue : nullptr, &bam);
@@ -1060,7 +1064,8 @@ public:
     }
 
     // SAM lines to a BAM file, from the text alone and the SAM specification (section 4.2): every field parsed back out of its
-    // line.  Tags are written as the contract of spm_hip.h types them: NM XH XR int32, XN X0 X1 uint32.  QUAL is absent.
+    // line.  Tags are written as the contract of spm_hip.h types them: NM XH XR int32, XN X0 X1 uint32, a Z tag (MD) as its
+    // string and a NUL.  QUAL "*" is absent (ff), any other is its values.
     static jst_bam bam_of_sam(jst_sam const & sam, jst_bam_options const & o)
     {
         spm_ctx const * const ctx = nullptr; // (no device is needed: the host-only calls leave their message without a context)
@@ -1143,9 +1148,21 @@ public:
             rec.push_back('\0');
             rec += cigar;
             rec += seq;
-            rec.append(l_seq, static_cast<char>(0xFF));
+            if (f[10] == "*") {
+                rec.append(l_seq, static_cast<char>(0xFF));
+            } else {
+                if (f[10].size() != l_seq)
+                    hip::fatal("journaled_sequence_tree::map_bam (QUAL and SEQ of different lengths)", ctx);
+                for (char const c : f[10])
+                    rec.push_back(static_cast<char>(c - 33));
+            }
             for (std::size_t t = 11; t < f.size(); ++t) {
                 std::string const tag = f[t].substr(0, 2);
+                if (f[t].size() >= 5 && f[t][3] == 'Z') {
+                    rec += tag + "Z" + f[t].substr(5);
+                    rec.push_back('\0');
+                    continue;
+                }
                 bool const is_signed = tag == "NM" || tag == "XH" || tag == "XR";
                 rec += tag;
                 rec.push_back(is_signed ? 'i' : 'I');
@@ -1238,10 +1255,10 @@ public:
     }
 
     // The rule of spm_hip.h as a plain formatter over the host structs: which line a read reports, MAPQ from the tables, the
-    // mate fields, the secondary lines, every field with std::to_string.
+    // mate fields, the secondary lines, every field with std::to_string.  reference: the ranks that jst_sam_options::md reads.
     static jst_sam sam_host(jst_read_loci const & mapped, std::vector<jst_pair> const * pairs, std::vector<jst_rescue> const * rescues,
                             std::vector<std::vector<std::uint8_t>> const & needle_ranks, std::uint32_t strands,
-                            jst_sam_options const & o)
+                            jst_sam_options const & o, std::vector<std::uint8_t> const * reference = nullptr)
     {
         constexpr std::uint32_t none = 0xFFFFFFFFu;
         std::vector<jst_ref_locus> const & loci = mapped.loci;
@@ -1252,6 +1269,53 @@ public:
             (!o.names.empty() && o.names.size() != (paired ? pairs->size() : n_reads)))
             hip::fatal("journaled_sequence_tree::map_sam (pairs, rescues, needles or names do not belong to these reads)",
                        hip::default_context());
+        if ((!o.qualities.empty() && o.qualities.size() != n_reads) || (o.md && reference == nullptr))
+            hip::fatal("journaled_sequence_tree::map_sam (one vector of qualities per read; md needs the reference)", hip::default_context());
+        for (std::size_t r = 0; r < o.qualities.size(); ++r)
+            if (o.qualities[r].size() != needle_ranks[strands * r].size() ||
+                std::any_of(o.qualities[r].begin(), o.qualities[r].end(), [](std::uint8_t q) { return q > 93; }))
+                hip::fatal("journaled_sequence_tree::map_sam (a read's qualities: one per symbol, 0 .. 93)", hip::default_context());
+        // QUAL of read r: the values + 33, back to front beside a reverse-complemented SEQ
+        auto const qual_text = [&](std::size_t r, bool reverse) {
+            if (o.qualities.empty())
+                return std::string("*");
+            std::string text;
+            for (std::uint8_t const q : o.qualities[r])
+                text += static_cast<char>(q + 33);
+            if (reverse)
+                std::reverse(text.begin(), text.end());
+            return text;
+        };
+        // MD of a transcript whose first reference position is `begin`: the count of matched positions, broken by every
+        // mismatched position (its reference letter) and every deletion (^ and its letters); an insertion breaks nothing
+        auto const md_tag = [&](std::vector<std::uint32_t> const & words, std::uint64_t begin) {
+            if (!o.md)
+                return std::string();
+            std::string text = "\tMD:Z:";
+            std::uint64_t matched = 0, at = begin;
+            auto const letter = [&](std::uint64_t p) {
+                if (p >= reference->size())
+                    hip::fatal("journaled_sequence_tree::map_sam (an alignment beyond the reference)", hip::default_context());
+                return (*reference)[p] < o.symbols.size() ? o.symbols[(*reference)[p]] : 'N';
+            };
+            for (std::uint32_t const w : words) {
+                std::uint32_t const op = w & 15u, n = w >> 4;
+                if (op == SPM_CIGAR_EQ)
+                    matched += n;
+                for (std::uint32_t i = 0; op == SPM_CIGAR_X && i < n; ++i) {
+                    text += std::to_string(matched) + letter(at + i);
+                    matched = 0;
+                }
+                if (op == SPM_CIGAR_DEL && n) {
+                    text += std::to_string(matched) + "^";
+                    for (std::uint32_t i = 0; i < n; ++i)
+                        text += letter(at + i);
+                    matched = 0;
+                }
+                at += op == SPM_CIGAR_INS ? 0u : n;
+            }
+            return text + std::to_string(matched);
+        };
         std::array<std::uint8_t, 4> const unique = o.default_tables ? std::array<std::uint8_t, 4>{60, 40, 30, 20} : o.mapq_unique;
         std::array<std::uint8_t, 4> const multi = o.default_tables ? std::array<std::uint8_t, 4>{3, 1, 1, 0} : o.mapq_multi;
         auto const mapq = [&](std::uint32_t n_best, std::uint32_t n_next) -> std::uint8_t {
@@ -1360,22 +1424,26 @@ public:
             std::uint64_t const mate_pos = other != nullptr && other->kind != SPM_SAM_UNMAPPED ? other->pos : 0;
             bool const is_mapped = kind != SPM_SAM_UNMAPPED;
             std::uint64_t pos = mate_pos;
-            std::string cigar = "*", seq, tags;
+            std::string cigar = "*", seq, tags, qual = "*";
             if (kind == SPM_SAM_LOCUS || kind == SPM_SAM_SECONDARY_LINE) {
                 jst_ref_locus const & X = loci[source];
                 pos = X.aln.begin_position() + 1;
                 cigar = cigar_text(X.aln.cigar());
                 seq = kind == SPM_SAM_LOCUS ? seq_text(X.needle) : "*";
-                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + "\tXH:i:" + std::to_string(X.haplotype_errors) + "\tXN:i:" +
-                       std::to_string(X.members.size());
+                if (kind == SPM_SAM_LOCUS)
+                    qual = qual_text(r, strands == 2 && (X.needle & 1u));
+                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + md_tag(X.aln.cigar(), X.aln.begin_position()) + "\tXH:i:" +
+                       std::to_string(X.haplotype_errors) + "\tXN:i:" + std::to_string(X.members.size());
             } else if (kind == SPM_SAM_RESCUE) {
                 jst_rescue const & X = (*rescues)[source];
                 pos = X.aln.begin_position() + 1;
                 cigar = cigar_text(X.aln.cigar());
                 seq = seq_text(X.needle);
-                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + "\tXR:i:1";
+                qual = qual_text(r, (X.flag & 0x10) != 0);
+                tags = "\tNM:i:" + std::to_string(X.aln.errors()) + md_tag(X.aln.cigar(), X.aln.begin_position()) + "\tXR:i:1";
             } else {
                 seq = seq_text(static_cast<std::uint32_t>(strands * r));
+                qual = qual_text(r, false);
             }
             if (kind == SPM_SAM_LOCUS || kind == SPM_SAM_RESCUE)
                 tags += "\tX0:i:" + std::to_string(own.x0) + "\tX1:i:" + std::to_string(own.x1);
@@ -1387,7 +1455,7 @@ public:
                 line += "*\t0";
             else
                 line += "=\t" + std::to_string(mate_pos ? mate_pos : pos);
-            line += "\t" + std::to_string(tlen) + "\t" + seq + "\t*" + tags + "\n";
+            line += "\t" + std::to_string(tlen) + "\t" + seq + "\t" + qual + tags + "\n";
             out.lines.push_back({out.text.size(), static_cast<std::uint32_t>(line.size()), static_cast<std::uint32_t>(r), source, flag, q,
                                  kind});
             out.text += line;
@@ -1797,6 +1865,7 @@ private:
         jst_sam * out;
         jst_bam_options const * bam_options = nullptr; // map_bam: the BAM call instead, into bam_out
         jst_bam * bam_out = nullptr;
+        spm_text const * reference = nullptr; // the resident reference ranks: what jst_sam_options::md reads
     };
 
     // spm_hip_jst_ref_loci_sam over the handles loci_of holds (pr, rs: nullptr where there are none), and its host view
@@ -1822,11 +1891,19 @@ private:
         std::copy(o.mapq_multi.begin(), o.mapq_multi.end(), opts.mapq_multi);
         opts.mapq_defaults = o.default_tables ? 1 : 0;
         opts.flags = (o.cigar_m ? SPM_SAM_CIGAR_M : 0u) | (o.secondary ? SPM_SAM_SECONDARY : 0u);
+        std::vector<std::uint8_t> qual; // the qualities back to back in read order
+        for (std::vector<std::uint8_t> const & q : o.qualities)
+            qual.insert(qual.end(), q.begin(), q.end());
+        spm_sam_extras extras{};
+        extras.qual = qual.empty() ? nullptr : qual.data();
+        extras.n_qual = qual.size();
+        extras.reference = o.md ? req.reference : nullptr;
+        extras.flags = o.md ? SPM_SAM_MD : 0u;
         if (req.bam_out != nullptr) {
             spm_bam_opts const bopts{opts, req.bam_options->ref_len, req.bam_options->block_data, 0};
             spm_bam * b = nullptr;
-            if (spm_hip_jst_ref_loci_bam(l, rd, pr, rs, req.needles, &bopts, &b) != SPM_OK)
-                hip::fatal("spm_hip_jst_ref_loci_bam", ctx);
+            if (spm_hip_jst_ref_loci_bam_ex(l, rd, pr, rs, req.needles, &bopts, &extras, &b) != SPM_OK)
+                hip::fatal("spm_hip_jst_ref_loci_bam_ex", ctx);
             std::unique_ptr<spm_bam, decltype(&spm_hip_bam_destroy)> owner{b, &spm_hip_bam_destroy};
             if (req.bam_options->sort) { // the handle in coordinate order takes the place of the one in read order
                 spm_bam * sorted = nullptr;
@@ -1888,8 +1965,8 @@ private:
             return;
         }
         spm_sam * s = nullptr;
-        if (spm_hip_jst_ref_loci_sam(l, rd, pr, rs, req.needles, &opts, &s) != SPM_OK)
-            hip::fatal("spm_hip_jst_ref_loci_sam", ctx);
+        if (spm_hip_jst_ref_loci_sam_ex(l, rd, pr, rs, req.needles, &opts, &extras, &s) != SPM_OK)
+            hip::fatal("spm_hip_jst_ref_loci_sam_ex", ctx);
         std::unique_ptr<spm_sam, decltype(&spm_hip_sam_destroy)> owner{s, &spm_hip_sam_destroy};
         char const * text = nullptr;
         spm_sam_line const * lines = nullptr;

@@ -954,7 +954,7 @@ void spm_hip_jst_rescues_destroy(spm_jst_rescues *r);
  * the needle locus.pattern through `symbols` (sigma characters; a rank >= sigma prints N) -- the reverse pattern already is
  * the reverse complement, which is what SAM wants.  QUAL "*".  Tags in this order: NM:i:<ref_score> XH:i:<score, the haplotype
  * distance> XN:i:<n_haplotypes>, and on reported lines X0:i:<n_best> X1:i:<n_next>, the counts the MAPQ used.  A rescued
- * mate's line has NM:i:<score> XR:i:1 X0 X1.  An unmapped line has SEQ = the forward read and no tags.  A locus inside an
+ * mate's line has NM:i:<score> XR:i:1 X0 X1.  An unmapped line has SEQ = the forward read and no tags.  (QUAL other than "*", and an MD tag: spm_hip_jst_ref_loci_sam_ex below.)  A locus inside an
  * insertion (ref_begin == ref_end, all I) is printed as it is.  Every line ends in \n.
  *
  * Worked cases (rname "chr", default tables, no names).
@@ -1038,6 +1038,60 @@ int spm_hip_sam_header(const char *rname, uint64_t ref_len, char *buf, uint64_t 
 /* the MAPQ of (n_best, n_next) under the tables of opts (only the three mapq members are read); -1: NULL opts or
  * mapq_defaults above 1 */
 int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint32_t n_next);
+
+/* ---- base qualities and the MD tag: what makes the lines usable by a variant caller without the reference at hand ----------
+ * spm_hip_jst_ref_loci_sam_ex and spm_hip_jst_ref_loci_bam_ex are the two calls above and below with one more argument.
+ * extras == NULL, or an all-zero extras, gives the bytes of the call without it; the results are the same handles.
+ *
+ * QUAL.  qual holds Phred values 0 .. 93, the reads back to back in READ order, each as sequenced (forward): read r owns
+ * qual[q_off[r] .. q_off[r] + m[strands * r]) with q_off the exclusive sum of the read lengths.  They are copied in the call.
+ * A line whose SEQ is the forward read prints them in order; a line whose SEQ is the reverse complement (pattern & 1 in a
+ * stranded set, a rescue with flag 0x10) prints them back to front; an unmapped line prints them forward, beside its forward
+ * SEQ; a secondary line (SEQ "*") keeps QUAL "*", and l_seq 0 in BAM.  The text gets value + 33, a BAM record the value.  A
+ * one-base read with Phred 9 prints "*", which a reader takes for "no qualities": the ambiguity is the SAM specification's own
+ * and is left as it is.
+ *
+ * MD (SPM_SAM_MD, with the resident reference ranks).  Every line that prints a CIGAR carries MD:Z: directly behind NM:i:
+ * (kinds LOCUS, RESCUE, SECONDARY_LINE).  The string is computed from the transcript's words as they are; SPM_SAM_CIGAR_M does
+ * not change it.  With c the count of matched reference positions, 0 at first, and a reference cursor that starts at ref_begin:
+ *     = of length L   c += L
+ *     I               nothing: it does not end a match run
+ *     X of length L   for each of its L positions: print c, the reference letter, c = 0 (adjacent mismatches are separated by 0)
+ *     D of length L   print c, '^', the L reference letters, c = 0
+ *     at the end      print c
+ * A reference letter is symbols[rank], N for a rank >= sigma.  The result matches [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*.  In BAM the
+ * tag is 4d 44 5a, the string, 00.
+ * Worked cases (symbols "ACGT"):
+ *     20= 1X 11=             G at the X          20G11
+ *     5= 2X 3= 2D 1X 4=      AC / GT / A         5A0C3^GT0A4
+ *     3X                     ACG                 0A0C0G0
+ *     4= 2I 4=                                   8
+ *     all I (a locus inside an insertion)        0
+ *
+ *   * SPM_E_INVALID with a message that names the member, decided on the host before any launch: unknown flags or a nonzero
+ *     reserved; SPM_SAM_MD without a reference, or a reference without SPM_SAM_MD; a reference of another context, or whose
+ *     sigma is not the needle set's; qual without n_qual or the other way round; n_qual not the sum of the read lengths; a
+ *     value above 93; the BAM call only: a reference whose length is not ref_len.
+ *   * Counted on the device like every other disagreement, failing the call with SPM_E_INVALID and nothing written: a mapped
+ *     line whose [ref_begin, ref_end), or what its transcript spans, does not lie inside the reference; an X column whose
+ *     reference rank equals the read's rank there (the reference is not the one the loci were projected against). */
+#define SPM_SAM_MD 1u
+typedef struct spm_sam_extras {     /* 32 bytes */
+    const uint8_t *qual;            /* host: Phred values 0 .. 93; NULL: QUAL "*" / ff */
+    uint64_t n_qual;                /* the sum of the read lengths; 0 with qual == NULL */
+    const spm_text *reference;      /* the resident reference ranks; needed with SPM_SAM_MD, else NULL */
+    uint32_t flags;                 /* SPM_SAM_MD */
+    uint32_t reserved;              /* must be 0 */
+} spm_sam_extras;
+int spm_hip_jst_ref_loci_sam_ex(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs /* NULL: single-end */,
+                                spm_jst_rescues *rescues /* NULL; needs pairs */, const spm_patterns *patterns,
+                                const spm_sam_opts *opts, const spm_sam_extras *extras /* NULL: none */, spm_sam **out);
+/* host only, no device needed.  The MD string of one transcript of n_words words whose first reference position is ref_begin,
+ * by the serial rendering of the same rule; not NUL-terminated.  *len is what it needs; cap too small: SPM_E_OVERFLOW and
+ * nothing is written.  SPM_E_INVALID: a NULL argument (words may be NULL with n_words 0), or a transcript that leaves
+ * [0, ref_len). */
+int spm_hip_sam_md(const uint32_t *words, uint32_t n_words, const uint8_t *ref_ranks, uint64_t ref_len, uint64_t ref_begin,
+                   const char *symbols, char *buf, uint64_t cap, uint64_t *len);
 
 /* ---- BGZF framing of a device buffer: what makes SAM text in HBM a .sam.gz that samtools and tabix read --------------------
  * One call frames n bytes at device_src (any alignment, owned by no handle; read before the call returns) into BGZF blocks in
@@ -1172,11 +1226,12 @@ int spm_hip_bgzf_deflate_bound(uint64_t n, const spm_bgzf_deflate_opts *opts, ui
  * BAM's encoding); with SPM_SAM_CIGAR_M every maximal run of = / X words is one word sum << 4 | 0 and n_cigar_op counts items; a
  * line with CIGAR "*" has n_cigar_op 0.  seq: two symbols per byte, the first in the high nibble, the code of a letter its place
  * in "=ACMGRSVTWYHKDBN" in either case, any other letter or a rank >= sigma 15; a secondary (SEQ "*") has l_seq 0; with odd l_seq
- * the last low nibble is 0.  qual: l_seq bytes ff.  bin: the specification's reg2bin(pos, pos + max(span, 1)) with span the
+ * the last low nibble is 0.  qual: l_seq bytes ff, or with the qualities of spm_sam_extras the values themselves.  bin: the specification's reg2bin(pos, pos + max(span, 1)) with span the
  * reference symbols of the transcript (= X D), 0 on an unmapped record -- a locus inside an insertion takes end = pos + 1; pos -1
  * gives 4680.  tags, in the text's order, SEVEN BYTES EACH whatever the value, on purpose (a record's length does not depend on
- * its values): NM XH XR are type i (int32), XN X0 X1 type I (uint32: the counts arrive clamped to 0xFFFFFFFF).  An unmapped record
- * has none.
+ * its values): NM XH XR are type i (int32), XN X0 X1 type I (uint32: the counts arrive clamped to 0xFFFFFFFF).  The one
+ * exception is MD (SPM_SAM_MD of spm_sam_extras), type Z, directly behind NM: 4d 44 5a, the string, 00 -- the first tag whose
+ * length depends on its values.  An unmapped record has none.
  *
  * Worked records (the worked SAM cases above; rname "chr", default tables, no names), in hex, fields separated by spaces:
  *  1. Case 1 (read 7 reverse at [99,131), words 20= 1X 11=, MAPQ 40) with a SEQ of 32 A, without SPM_SAM_CIGAR_M, 133 bytes:
@@ -1227,6 +1282,10 @@ typedef struct spm_bam_stats {      /* 104 bytes */
 int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs /* NULL: single-end */,
                              spm_jst_rescues *rescues /* NULL; needs pairs */, const spm_patterns *patterns,
                              const spm_bam_opts *opts, spm_bam **out);
+/* the same with base qualities and the MD tag (spm_sam_extras above; its reference has ref_len symbols) */
+int spm_hip_jst_ref_loci_bam_ex(spm_jst_ref_loci *loci, spm_jst_reads *reads, spm_jst_pairs *pairs /* NULL: single-end */,
+                                spm_jst_rescues *rescues /* NULL; needs pairs */, const spm_patterns *patterns,
+                                const spm_bam_opts *opts, const spm_sam_extras *extras /* NULL: none */, spm_bam **out);
 /* every pointer may be NULL */
 int spm_hip_bam_view(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
                      const spm_sam_line **lines, uint64_t *n_lines);

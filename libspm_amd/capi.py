@@ -282,6 +282,12 @@ class SamLine(C.Structure):
 
 
 SAM_CIGAR_M, SAM_SECONDARY = 1, 2
+SAM_MD = 1  # spm_sam_extras.flags
+
+
+class SamExtras(C.Structure):
+    _fields_ = [("qual", C.c_void_p), ("n_qual", C.c_uint64), ("reference", C.c_void_p), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 SAM_UNMAPPED, SAM_LOCUS, SAM_RESCUE, SAM_SECONDARY_LINE = 0, 1, 2, 3
 
 
@@ -537,6 +543,10 @@ SIGNATURES = {
     "spm_hip_sam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "spm_hip_sam_mapq": (C.c_int, [C.POINTER(SamOpts), C.c_uint32, C.c_uint32]),
     "spm_hip_jst_ref_loci_bam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BamOpts), C.POINTER(_vp)]),
+    "spm_hip_jst_ref_loci_sam_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(SamOpts), C.POINTER(SamExtras), C.POINTER(_vp)]),
+    "spm_hip_jst_ref_loci_bam_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BamOpts), C.POINTER(SamExtras), C.POINTER(_vp)]),
+    "spm_hip_sam_md": (C.c_int, [_u32p, C.c_uint32, _u8p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64,
+                                 C.POINTER(C.c_uint64)]),
     "spm_hip_bam_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64),
                                    C.POINTER(C.POINTER(SamLine)), C.POINTER(C.c_uint64)]),
     "spm_hip_bam_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp),

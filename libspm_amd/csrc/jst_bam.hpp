@@ -6,8 +6,10 @@
 //                            sink;
 //   jst_bam_write_kernel     one wave per record, four records per workgroup, into the uncompressed stream: the 36 fixed bytes
 //                            one per lane, name bytes strided, CIGAR one word per lane through wave_cigar_walk (the text sink's
-//                            scheme, the items' size counted in words), SEQ two ranks per lane and byte, QUAL a fill, a tag
-//                            seven lanes.  Byte stores: a record starts wherever the one before it ended.  No atomics.
+//                            scheme, the items' size counted in words), SEQ two ranks per lane and byte, QUAL a fill or,
+//                            with spm_sam_extras, one value per lane; a tag seven lanes, MD (type Z) the text sink's walk
+//                            between its three head bytes and a NUL.  Byte stores: a record starts wherever the one before
+//                            it ended.  No atomics.
 #pragma once
 
 #include "bgzf_core.hpp"
@@ -114,6 +116,26 @@ struct jst_bam_wave_sink
             store(cur + lane, jst_bam_tag_byte(head, v, lane));
         cur += kBamTag;
     }
+    __device__ __forceinline__ void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
+    {
+        for (uint32_t i = lane; i < jst_sam_qual_len(m); i += kWave)
+            store(cur + i, jst_sam_qual_byte(values, m, reverse, add, i));
+        cur += jst_sam_qual_len(m);
+    }
+    // MD Z, the text sink's string by the same walk, NUL
+    __device__ __forceinline__ void md(const uint32_t *words, uint32_t n, const uint8_t *ref, const char *symbols, uint32_t sigma)
+    {
+        if (lane < 3)
+            store(cur + lane, jst_bam_le_byte(jst_bam_tag_head('M', 'D', 'Z'), lane));
+        const uint64_t begin = cur + 3;
+        uint64_t open = 0;
+        cur = begin + wave_md_walk(words, n, lane, open, [&](uint64_t at, uint64_t c, uint32_t word, uint64_t ref_at, uint64_t len) {
+                  for (uint64_t i = 0; i < len; ++i)
+                      store(begin + at + i, (uint8_t)jst_sam_md_word_char(c, word, ref + ref_at, symbols, sigma, i));
+              });
+        num(open);
+        fill(0, 1);
+    }
 };
 
 __global__ __launch_bounds__(256) void jst_bam_write_kernel(const jst_bam_params B)
@@ -215,11 +237,10 @@ extern "C" int spm_hip_bam_header_sorted(const char *rname, uint64_t ref_len, ui
     return bam_header_framed("spm_hip_bam_header_sorted", true, rname, ref_len, block_data, buf, cap, len);
 }
 
-extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
-                                        const spm_patterns *ps, const spm_bam_opts *opts, spm_bam **out)
+static int bam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs, const spm_patterns *ps,
+                   const spm_bam_opts *opts, const spm_sam_extras *ex, spm_bam **out)
 {
     using namespace spm_hip;
-    static const char *const who = "spm_hip_jst_ref_loci_bam";
     if (!l || !out)
         return SPM_E_INVALID;
     *out = nullptr;
@@ -232,6 +253,8 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
     size_t rname_len = 0;
     uint64_t n_named = 0;
     SPM_TRY(sam_check_args(who, ctx, l, r, pr, rs, ps, &opts->sam, rname_len, n_named));
+    if (ex)
+        SPM_TRY(sam_check_extras(who, ctx, r, ps, ex, &opts->ref_len));
     if (opts->block_data > kBgzfBlockData) {
         SPM_SET_ERR(ctx, "%s: block_data %u above 65280", who, opts->block_data);
         return SPM_E_INVALID;
@@ -255,7 +278,7 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
     uint8_t codes[256];
     dev_scratch keep;
     if (n_reads) {
-        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, &opts->sam, rname_len, n_named, F, &R->d_lines));
+        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, &opts->sam, ex, rname_len, n_named, F, &R->d_lines));
         B.P = F.P;
         jst_sam_params &P = B.P;
         hip_events<8> &ev = F.ev;
@@ -274,7 +297,8 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         const unsigned long long *c = ctx->h_counters;
         if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
             SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
-                             "needle set or ref_len, or do not fit a BAM record; nothing was written", who, c[kSamCntBad]);
+                             "needle set, ref_len or the reference of the extras, or do not fit a BAM record; nothing was written", who,
+                        c[kSamCntBad]);
             return SPM_E_INVALID;
         }
         P.n_lines = (uint32_t)c[kSamCntLines];
@@ -349,6 +373,18 @@ extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, s
                 R->stats.ms_frame, R->stats.ms_stats, R->stats.ms_host);
     *out = R.release();
     return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_loci_bam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                        const spm_patterns *ps, const spm_bam_opts *opts, spm_bam **out)
+{
+    return bam_run("spm_hip_jst_ref_loci_bam", l, r, pr, rs, ps, opts, nullptr, out);
+}
+
+extern "C" int spm_hip_jst_ref_loci_bam_ex(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                           const spm_patterns *ps, const spm_bam_opts *opts, const spm_sam_extras *ex, spm_bam **out)
+{
+    return bam_run("spm_hip_jst_ref_loci_bam_ex", l, r, pr, rs, ps, opts, ex, out);
 }
 
 extern "C" int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out)

@@ -6,6 +6,7 @@
 //
 // Tags are 7 bytes each whatever the value (NM, XH, XR: type i; XN, X0, X1: type I, since the counts arrive clamped to
 // 0xFFFFFFFF): fixed-width ON PURPOSE, so that a record's length does not depend on its values and lane i of a tag is byte i.
+// The one exception is MD (spm_sam_extras), type Z: 4d 44 5a, the string of jst_sam_core.hpp's md, 00.
 #pragma once
 
 #include "hd.hpp"
@@ -150,6 +151,8 @@ SPM_HD inline void jst_bam_fixed(const jst_sam_fields &F, const jst_bam_shape &H
 //   cigar(words, n, merge)     the items as words
 //   seq(ranks, m, codes)       m ranks, two per byte
 //   tag(head, v)               7 bytes
+//   qual(values, m, reverse, add)   as the text's
+//   md(words, n, ref, symbols, sigma)   MD Z, the text's string, NUL
 // block_size: what the measuring sink found, less 4 (the measuring sink itself does not look at it).
 template <class Sink>
 SPM_HD inline void jst_bam_compose(const jst_sam_src &S, const jst_sam_fields &F, const jst_bam_shape &H, const uint8_t *codes,
@@ -168,10 +171,15 @@ SPM_HD inline void jst_bam_compose(const jst_sam_src &S, const jst_sam_fields &F
         out.cigar(F.words, F.n_words, (S.flags & SPM_SAM_CIGAR_M) != 0);
     if (F.seq) {
         out.seq(F.seq, F.m, codes);
-        out.fill(0xff, F.m);
+        if (F.qual)
+            out.qual(F.qual, F.m, F.qual_reverse, 0);
+        else
+            out.fill(0xff, F.m);
     }
     if (F.kind != SPM_SAM_UNMAPPED) {
         out.tag(jst_bam_tag_head('N', 'M', 'i'), (uint32_t)F.nm);
+        if (F.md_ref)
+            out.md(F.words, F.n_words, F.md_ref, S.symbols, S.sigma);
         if (F.kind == SPM_SAM_RESCUE) {
             out.tag(jst_bam_tag_head('X', 'R', 'i'), 1);
         } else {
@@ -201,6 +209,13 @@ struct jst_bam_measure
     }
     SPM_HD void seq(const uint8_t *, uint32_t m, const uint8_t *) { n += jst_bam_seq_len(m); }
     SPM_HD void tag(uint32_t, uint32_t) { n += kBamTag; }
+    SPM_HD void qual(const uint8_t *, uint32_t m, bool, uint8_t) { n += jst_sam_qual_len(m); }
+    SPM_HD void md(const uint32_t *words, uint32_t n_words, const uint8_t *ref, const char *symbols, uint32_t sigma)
+    {
+        jst_sam_measure M;
+        M.md(words, n_words, ref, symbols, sigma);
+        n += 3 + M.n + 1;
+    }
 };
 
 // the serial sink: the bytes one after the other into [to, to + cap); n counts on beyond cap without writing
@@ -252,6 +267,20 @@ struct jst_bam_serial
     {
         for (uint32_t i = 0; i < kBamTag; ++i)
             put(jst_bam_tag_byte(head, v, i));
+    }
+    SPM_HD void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
+    {
+        for (uint32_t i = 0; i < jst_sam_qual_len(m); ++i)
+            put(jst_sam_qual_byte(values, m, reverse, add, i));
+    }
+    SPM_HD void md(const uint32_t *words, uint32_t n_words, const uint8_t *ref, const char *symbols, uint32_t sigma)
+    {
+        for (uint32_t i = 0; i < 3; ++i)
+            put(jst_bam_le_byte(jst_bam_tag_head('M', 'D', 'Z'), i));
+        jst_sam_serial T{reinterpret_cast<char *>(to), cap, n};
+        T.md(words, n_words, ref, symbols, sigma);
+        n = T.n;
+        put(0);
     }
 };
 

@@ -7,10 +7,14 @@
 //                                 its lines; an exclusive sum later, the same lanes write the line records;
 //   jst_sam_measure_kernel        one lane per line: the record resolved against its sources (every index tested), the byte
 //                                 length of the line by the measuring sink;
-//   jst_sam_write_kernel          one wave per line, four lines per workgroup: the same composition into the wave sink --
+//   jst_sam_write_kernel<kExtras> one wave per line, four lines per workgroup: the same composition into the wave sink --
 //                                 byte i of a field goes to lane i, numbers one digit per lane, CIGAR one word per lane with
 //                                 a wave prefix sum over the words' text lengths and a segmented sum for the M runs.  Byte
-//                                 stores straight to HBM: consecutive lanes store consecutive bytes.  No atomics;
+//                                 stores straight to HBM: consecutive lanes store consecutive bytes.  No atomics.  With
+//                                 kExtras (spm_sam_extras): QUAL one value per lane, back to front on a
+//                                 reverse line, and MD one transcript word per lane (wave_md_walk) -- a segmented sum gives
+//                                 every X and D word the matched positions in front of it, two wave prefix sums place its
+//                                 text and find its reference letters;
 //   jst_sam_stats_kernel          one lane per line: offset and length into the record, the counts by count_flagged.
 #pragma once
 
@@ -179,6 +183,48 @@ __device__ __forceinline__ uint64_t wave_cigar_walk(const uint32_t *words, uint3
     return done;
 }
 
+// The breaking words (X, D) of a transcript across a wave, for the sinks that write an MD string.  Lane w of a pass takes word
+// w.  A breaking word closes a run -- the = and I words since the breaking word before it -- and holds the matched positions of
+// that run (a segmented sum over the wave; lane 0's run takes in what the passes so far left open, which is how a count crosses
+// a pass border), its first reference position counted from the transcript's (a wave prefix sum over the words' reference
+// spans, on top of the passes so far), and gets put(at, c, word, ref_at, len) with len = jst_sam_md_word_len(c, word) and `at`
+// the wave prefix sum of the lengths in front of it.  -> the size of all items; `open`: the count behind the last breaking word,
+// which the sink prints.  words, n, open and the return value are wave-uniform.
+template <class Put> __device__ __forceinline__ uint64_t wave_md_walk(const uint32_t *words, uint32_t n, uint32_t lane, uint64_t &open, Put put)
+{
+    uint64_t carry = 0, done = 0, ref_done = 0; // the open run's count; the size of the items so far; reference positions so far
+    for (uint32_t base = 0; base < n; base += kWave) {
+        const uint32_t w = base + lane;
+        const uint32_t word = w < n ? words[w] : 0u; // (a word 0 neither breaks nor counts)
+        const bool brk = jst_sam_md_breaks(word);
+        // lanes of one run share the number of breaking words below them; the breaking word is its run's last lane
+        const uint32_t id = (uint32_t)__popcll(__ballot(brk) & ((1ull << lane) - 1ull));
+        run_sum<uint64_t> v{(uint64_t)jst_sam_md_matched(word)};
+        if (lane == 0)
+            v.v += carry;
+        wave_run_scan(id, v);
+        const uint32_t span = jst_sam_md_ref_span(word);
+        uint64_t ref_incl = span;
+        const uint64_t len = brk ? jst_sam_md_word_len(v.v, word) : 0ull;
+        uint64_t incl = len;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t up = __shfl_up(incl, o), ref_up = __shfl_up(ref_incl, o);
+            if ((int)lane >= o) {
+                incl += up;
+                ref_incl += ref_up;
+            }
+        }
+        if (brk)
+            put(done + (incl - len), v.v, word, ref_done + (ref_incl - span), len);
+        const uint64_t last = __shfl(v.v, 63);
+        carry = __shfl(brk ? 1 : 0, 63) ? 0ull : last;
+        done += __shfl(incl, 63);
+        ref_done += __shfl(ref_incl, 63);
+    }
+    open = carry;
+    return done;
+}
+
 // The wave sink: the composition of one line, byte i of a field to lane i.  cur is wave-uniform.  No store lands outside
 // [cur at construction, end): the line's own bytes.
 struct jst_sam_wave_sink
@@ -233,9 +279,27 @@ struct jst_sam_wave_sink
                                   store(begin + at + i, jst_sam_word_char(run, op, len, i));
                           });
     }
+    __device__ __forceinline__ void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
+    {
+        for (uint32_t i = lane; i < jst_sam_qual_len(m); i += kWave)
+            store(cur + i, (char)jst_sam_qual_byte(values, m, reverse, add, i));
+        cur += jst_sam_qual_len(m);
+    }
+    // every lane writes the bytes of its own breaking word (a long D loops); the count behind the last one follows as a number
+    __device__ __forceinline__ void md(const uint32_t *words, uint32_t n, const uint8_t *ref, const char *symbols, uint32_t sigma)
+    {
+        const uint64_t begin = cur;
+        uint64_t open = 0;
+        cur = begin + wave_md_walk(words, n, lane, open, [&](uint64_t at, uint64_t c, uint32_t word, uint64_t ref_at, uint64_t len) {
+                  for (uint64_t i = 0; i < len; ++i)
+                      store(begin + at + i, jst_sam_md_word_char(c, word, ref + ref_at, symbols, sigma, i));
+              });
+        num(0, 0, open, false);
+    }
 };
 
-__global__ __launch_bounds__(256) void jst_sam_write_kernel(const jst_sam_params P)
+// kExtras: the call has qualities or a reference (spm_sam_extras); without, the composition leaves both kinds of field out
+template <bool kExtras> __global__ __launch_bounds__(256) void jst_sam_write_kernel(const jst_sam_params P)
 {
     const uint32_t wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
     const unsigned long long i = blockIdx.x * 4ull + wv;
@@ -246,7 +310,7 @@ __global__ __launch_bounds__(256) void jst_sam_write_kernel(const jst_sam_params
         return; // (the measure stage resolved this record and counted a failure: the host does not get here)
     const uint64_t begin = P.off64[i], end = begin + P.len[i];
     jst_sam_wave_sink out{P.text, begin, end < P.n_bytes ? end : P.n_bytes, lane};
-    jst_sam_compose(P.S, F, out);
+    jst_sam_compose<kExtras>(P.S, F, out);
 }
 
 __global__ __launch_bounds__(256) void jst_sam_stats_kernel(const jst_sam_params P)
@@ -277,7 +341,7 @@ struct sam_len_op
 
 } // namespace spm_hip
 
-static_assert(sizeof(spm_hip::jst_sam_aux) == 24, "spm_hip.h states this size");
+static_assert(sizeof(spm_hip::jst_sam_aux) == 24 && sizeof(spm_sam_extras) == 32, "spm_hip.h states these sizes");
 
 extern "C" void spm_hip_sam_destroy(spm_sam *s)
 {
@@ -330,6 +394,7 @@ struct sam_front
     spm_hip::jst_sam_params P{};
     dev_scratch keep;          // the strings of the opts on the device
     std::vector<uint8_t> img;  // ... and on the host, until the copy has been waited for
+    std::vector<uint64_t> q_off; // the qualities' offsets, likewise
     spm_hip::hip_events<8> ev; // [0], [1]: around the lines stage; the rest are the caller's
     uint8_t *d_tmp = nullptr;  // the scans' temporary storage, in the context's scratch behind the arrays of P
     size_t tmp64 = 0;
@@ -415,10 +480,59 @@ static int sam_check_args(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, sp
     return SPM_OK;
 }
 
-// n_reads > 0.  *d_lines: the line records, allocated here, the caller's to free
+// What spm_sam_extras adds to the refusals (ex != NULL).  bam_ref_len: the BAM call's ref_len, which the reference has to have.
+static int sam_check_extras(const char *who, spm_ctx *ctx, const spm_jst_reads *r, const spm_patterns *ps, const spm_sam_extras *ex,
+                            const uint64_t *bam_ref_len)
+{
+    if ((ex->flags & ~SPM_SAM_MD) || ex->reserved) {
+        SPM_SET_ERR(ctx, "%s: extras: unknown flags bits 0x%x or reserved %u (must be 0)", who, ex->flags, ex->reserved);
+        return SPM_E_INVALID;
+    }
+    if (((ex->flags & SPM_SAM_MD) != 0) != (ex->reference != nullptr)) {
+        SPM_SET_ERR(ctx, "%s: extras: %s", who, ex->reference ? "a reference without SPM_SAM_MD in flags" : "SPM_SAM_MD in flags without a reference");
+        return SPM_E_INVALID;
+    }
+    if (ex->reference) {
+        if (ex->reference->ctx != ctx) {
+            SPM_SET_ERR(ctx, "%s: extras: the reference belongs to another context", who);
+            return SPM_E_INVALID;
+        }
+        if (ex->reference->sigma != ps->sigma) {
+            SPM_SET_ERR(ctx, "%s: extras: the reference has sigma %u, the needle set sigma %u", who, ex->reference->sigma, ps->sigma);
+            return SPM_E_INVALID;
+        }
+        if (bam_ref_len && ex->reference->n != *bam_ref_len) {
+            SPM_SET_ERR(ctx, "%s: extras: the reference has %llu symbols, ref_len is %llu", who, (unsigned long long)ex->reference->n,
+                        (unsigned long long)*bam_ref_len);
+            return SPM_E_INVALID;
+        }
+    }
+    if ((ex->qual != nullptr) != (ex->n_qual != 0)) {
+        SPM_SET_ERR(ctx, "%s: extras: %s", who, ex->qual ? "qual with n_qual 0" : "n_qual without qual");
+        return SPM_E_INVALID;
+    }
+    if (ex->qual) {
+        uint64_t sum = 0;
+        for (uint64_t i = 0; i < r->n; ++i)
+            sum += (uint64_t)ps->m[r->strands * i];
+        if (ex->n_qual != sum) {
+            SPM_SET_ERR(ctx, "%s: extras: n_qual is %llu, the read lengths add up to %llu", who, (unsigned long long)ex->n_qual,
+                        (unsigned long long)sum);
+            return SPM_E_INVALID;
+        }
+        for (uint64_t i = 0; i < ex->n_qual; ++i)
+            if (ex->qual[i] > 93) {
+                SPM_SET_ERR(ctx, "%s: extras: qual[%llu] is %u, above 93", who, (unsigned long long)i, ex->qual[i]);
+                return SPM_E_INVALID;
+            }
+    }
+    return SPM_OK;
+}
+
+// n_reads > 0.  *d_lines: the line records, allocated here, the caller's to free.  ex: checked, or NULL
 static int sam_lines_stage(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
-                           const spm_patterns *ps, const spm_sam_opts *opts, size_t rname_len, uint64_t n_named, sam_front &F,
-                           spm_sam_line **d_lines)
+                           const spm_patterns *ps, const spm_sam_opts *opts, const spm_sam_extras *ex, size_t rname_len, uint64_t n_named,
+                           sam_front &F, spm_sam_line **d_lines)
 {
     using namespace spm_hip;
     (void)who;
@@ -473,6 +587,24 @@ static int sam_lines_stage(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, s
         S.name_off = reinterpret_cast<const uint64_t *>(d_img + b_rname + b_sym);
         S.names = d_img + b_rname + b_sym + b_off;
     }
+    // ---- the extras: the qualities and their offsets copied, the reference where it is resident ----
+    if (ex && ex->qual) {
+        F.q_off.assign((size_t)n_reads + 1, 0);
+        for (uint32_t i = 0; i < n_reads; ++i)
+            F.q_off[i + 1] = F.q_off[i] + (uint64_t)ps->m[(size_t)r->strands * i];
+        uint64_t *d_q_off = nullptr;
+        uint8_t *d_qual = nullptr;
+        SPM_HIP_CHECK(ctx, keep.alloc(&d_q_off, F.q_off.size() * 8));
+        SPM_HIP_CHECK(ctx, keep.alloc(&d_qual, ex->n_qual));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_q_off, F.q_off.data(), F.q_off.size() * 8, hipMemcpyHostToDevice, st));
+        SPM_HIP_CHECK(ctx, hipMemcpyAsync(d_qual, ex->qual, ex->n_qual, hipMemcpyHostToDevice, st));
+        S.q_off = d_q_off;
+        S.qual = d_qual;
+    }
+    if (ex && ex->reference) {
+        S.ref = ex->reference->d;
+        S.ref_n = ex->reference->n;
+    }
     // ---- scratch ----
     size_t tmp32 = 0;
     size_t &tmp64 = F.tmp64;
@@ -508,11 +640,10 @@ static int sam_lines_stage(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, s
     return SPM_OK;
 }
 
-extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
-                                        const spm_patterns *ps, const spm_sam_opts *opts, spm_sam **out)
+static int sam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs, const spm_patterns *ps,
+                   const spm_sam_opts *opts, const spm_sam_extras *ex, spm_sam **out)
 {
     using namespace spm_hip;
-    static const char *const who = "spm_hip_jst_ref_loci_sam";
     if (!l || !out)
         return SPM_E_INVALID;
     *out = nullptr;
@@ -521,6 +652,8 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
     size_t rname_len = 0;
     uint64_t n_named = 0;
     SPM_TRY(sam_check_args(who, ctx, l, r, pr, rs, ps, opts, rname_len, n_named));
+    if (ex)
+        SPM_TRY(sam_check_extras(who, ctx, r, ps, ex, nullptr));
     SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<spm_sam, void (*)(spm_sam *)> R(new spm_sam, spm_hip_sam_destroy);
     R->ctx = ctx;
@@ -528,7 +661,7 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
     if (n_reads) {
         hipStream_t st = ctx->stream;
         sam_front F;
-        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, opts, rname_len, n_named, F, &R->d_lines));
+        SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, opts, ex, rname_len, n_named, F, &R->d_lines));
         jst_sam_params &P = F.P;
         hip_events<8> &ev = F.ev;
         uint8_t *d_tmp = F.d_tmp;
@@ -540,8 +673,8 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
         const unsigned long long *c = ctx->h_counters;
         if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
-            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools or the "
-                             "needle set; nothing was written", who, c[kSamCntBad]);
+            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
+                             "needle set or the reference of the extras; nothing was written", who, c[kSamCntBad]);
             return SPM_E_INVALID;
         }
         P.n_lines = (uint32_t)c[kSamCntLines];
@@ -552,7 +685,10 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
         P.text = R->d_text;
         // ---- write ----
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
-        hipLaunchKernelGGL(jst_sam_write_kernel, dim3((P.n_lines + 3) / 4), dim3(256), 0, st, P);
+        if (P.S.qual || P.S.ref)
+            hipLaunchKernelGGL(jst_sam_write_kernel<true>, dim3((P.n_lines + 3) / 4), dim3(256), 0, st, P);
+        else
+            hipLaunchKernelGGL(jst_sam_write_kernel<false>, dim3((P.n_lines + 3) / 4), dim3(256), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
         // ---- stats ----
@@ -580,6 +716,18 @@ extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, s
                 R->stats.ms_total, R->stats.ms_lines, R->stats.ms_measure, R->stats.ms_write, R->stats.ms_stats, R->stats.ms_host);
     *out = R.release();
     return SPM_OK;
+}
+
+extern "C" int spm_hip_jst_ref_loci_sam(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                        const spm_patterns *ps, const spm_sam_opts *opts, spm_sam **out)
+{
+    return sam_run("spm_hip_jst_ref_loci_sam", l, r, pr, rs, ps, opts, nullptr, out);
+}
+
+extern "C" int spm_hip_jst_ref_loci_sam_ex(spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs,
+                                           const spm_patterns *ps, const spm_sam_opts *opts, const spm_sam_extras *ex, spm_sam **out)
+{
+    return sam_run("spm_hip_jst_ref_loci_sam_ex", l, r, pr, rs, ps, opts, ex, out);
 }
 
 extern "C" int spm_hip_sam_view(spm_sam *s, const char **text, uint64_t *n_bytes, const spm_sam_line **lines, uint64_t *n_lines)

@@ -6,6 +6,10 @@
 // A line is composed once (jst_sam_compose) and handed, field by field, to a sink: the measuring sink adds up the lengths,
 // the serial sink writes the bytes one after the other, the wave sink of jst_sam.hpp gives byte i of a field to lane i.  All
 // three call the length and byte functions below and nothing else, so what is measured is what is written.
+//
+// Two kinds of field come with spm_sam_extras (scheme in DESIGN.md 4.11a): qual, the read's base qualities as sequenced, printed
+// back to front on a line whose SEQ is the reverse complement; and md, the MD string of a transcript against the resident
+// reference, whose items are the transcript's BREAKING words (X, D), each with the count of matched positions in front of it.
 #pragma once
 
 #include "hd.hpp"
@@ -118,6 +122,78 @@ template <class F> SPM_HD inline void jst_sam_cigar_items(const uint32_t *words,
     }
 }
 
+// ---- QUAL: value i of the read as the line prints it; `reverse`: the line's SEQ is the reverse complement ----
+SPM_HD inline uint32_t jst_sam_qual_len(uint32_t m) { return m; }
+SPM_HD inline uint8_t jst_sam_qual_byte(const uint8_t *values, uint32_t m, bool reverse, uint8_t add, uint32_t i) // i < m
+{
+    return (uint8_t)(values[reverse ? m - 1 - i : i] + add);
+}
+
+// ---- MD: a breaking word (X, D) behind `c` matched positions, as text ----
+//   X of length L: c, then per position the reference letter, "0" between two of them   (5, AC -> 5A0C)
+//   D of length L: c, '^', the L reference letters                                      (3, GT -> 3^GT)
+// = adds to c, I does nothing, the count behind the last breaking word ends the string.
+SPM_HD inline bool jst_sam_md_breaks(uint32_t word)
+{
+    const uint32_t op = word & 15u;
+    return (op == SPM_CIGAR_X || op == SPM_CIGAR_DEL) && (word >> 4) != 0; // (a word of length 0 prints nothing)
+}
+SPM_HD inline uint32_t jst_sam_md_matched(uint32_t word) { return (word & 15u) == SPM_CIGAR_EQ ? word >> 4 : 0u; }
+SPM_HD inline uint32_t jst_sam_md_ref_span(uint32_t word) // reference positions a word consumes
+{
+    const uint32_t op = word & 15u;
+    return (op == SPM_CIGAR_EQ || op == SPM_CIGAR_X || op == SPM_CIGAR_DEL) ? word >> 4 : 0u;
+}
+SPM_HD inline uint64_t jst_sam_md_word_len(uint64_t c, uint32_t word) // jst_sam_md_breaks(word)
+{
+    const uint64_t L = word >> 4;
+    return jst_sam_dec_len(c) + ((word & 15u) == SPM_CIGAR_X ? 2 * L - 1 : L + 1);
+}
+// ref: the reference ranks at the word's first position; i < len == jst_sam_md_word_len(c, word)
+SPM_HD inline char jst_sam_md_word_char(uint64_t c, uint32_t word, const uint8_t *ref, const char *symbols, uint32_t sigma, uint64_t i)
+{
+    const uint32_t digits = jst_sam_dec_len(c);
+    if (i < digits)
+        return jst_sam_dec_char(c, digits, (uint32_t)i);
+    const uint64_t j = i - digits;
+    if ((word & 15u) == SPM_CIGAR_X)
+        return (j & 1u) ? '0' : jst_sam_seq_char(ref[j >> 1], symbols, sigma);
+    return j == 0 ? '^' : jst_sam_seq_char(ref[j - 1], symbols, sigma);
+}
+// Walks the breaking words of a transcript: f(c, word, at) with c the matched positions in front of the word and `at` its first
+// reference position, counted from the transcript's.  -> the count behind the last one.  The serial form of what the wave does
+// with a segmented sum.
+template <class F> SPM_HD inline uint64_t jst_sam_md_items(const uint32_t *words, uint32_t n, F &&f)
+{
+    uint64_t c = 0, at = 0;
+    for (uint32_t w = 0; w < n; ++w) {
+        const uint32_t word = words[w];
+        if (jst_sam_md_breaks(word)) {
+            f(c, word, at);
+            c = 0;
+        } else {
+            c += jst_sam_md_matched(word);
+        }
+        at += jst_sam_md_ref_span(word);
+    }
+    return c;
+}
+// every X column disagrees with the read: ref at the transcript's first reference position, needle at its first query symbol
+SPM_HD inline bool jst_sam_md_agrees(const uint32_t *words, uint32_t n, const uint8_t *ref, const uint8_t *needle)
+{
+    uint64_t r = 0, q = 0;
+    bool ok = true;
+    for (uint32_t w = 0; w < n; ++w) {
+        const uint32_t op = words[w] & 15u, len = words[w] >> 4;
+        if (op == SPM_CIGAR_X)
+            for (uint32_t i = 0; i < len; ++i)
+                ok = ok && ref[r + i] != needle[q + i];
+        q += (op == SPM_CIGAR_EQ || op == SPM_CIGAR_X || op == SPM_CIGAR_INS) ? len : 0u;
+        r += (op == SPM_CIGAR_EQ || op == SPM_CIGAR_X || op == SPM_CIGAR_DEL) ? len : 0u;
+    }
+    return ok;
+}
+
 // ---- names: SAM's [!-~]{1,254}, and "*" alone means "no name" ----
 inline bool jst_sam_name_ok(const char *s, uint64_t len)
 {
@@ -154,6 +230,11 @@ struct jst_sam_src
     uint32_t rname_len = 0;
     jst_sam_mapq_tables tables{};
     uint32_t flags = 0;
+    // spm_sam_extras: read r's qualities are qual[q_off[r] .. q_off[r] + m[strands * r]); the reference ranks, set with SPM_SAM_MD
+    const uint8_t *qual = nullptr;
+    const uint64_t *q_off = nullptr; // [n_reads + 1]
+    const uint8_t *ref = nullptr;
+    uint64_t ref_n = 0;
 };
 
 // what a line carries besides its record: the mate's POS, the signed TLEN, the counts behind the MAPQ
@@ -393,6 +474,9 @@ struct jst_sam_fields
     uint32_t xn = 0, x0 = 0, x1 = 0;
     uint8_t kind = SPM_SAM_UNMAPPED;
     bool rname = false, rnext = false;
+    const uint8_t *qual = nullptr; // nullptr: QUAL *
+    const uint8_t *md_ref = nullptr; // the reference at pos - 1; nullptr: no MD
+    bool qual_reverse = false;
 };
 
 // Does the record of a line agree with its sources?  Every index before it is one; fills F when it does.  check_query: walk
@@ -413,6 +497,8 @@ SPM_HD inline bool jst_sam_resolve(const jst_sam_src &S, const spm_sam_line &L, 
     F.x0 = A.x0;
     F.x1 = A.x1;
     uint32_t pattern = S.strands * L.read; // an unmapped line prints the forward read
+    uint64_t ref_end = 0;
+    bool reverse = false;
     if (L.kind == SPM_SAM_LOCUS || L.kind == SPM_SAM_SECONDARY_LINE) {
         if (L.source >= S.n_loci)
             return false;
@@ -420,6 +506,8 @@ SPM_HD inline bool jst_sam_resolve(const jst_sam_src &S, const spm_sam_line &L, 
         if (X.pattern / S.strands != L.read || X.ref_begin > X.ref_end || !jst_sam_transcript_ok(X.cigar_off, X.cigar_len, S.n_ops))
             return false;
         pattern = X.pattern;
+        reverse = S.strands == 2 && (X.pattern & 1u);
+        ref_end = X.ref_end;
         F.pos = X.ref_begin + 1;
         F.words = S.ops + X.cigar_off;
         F.n_words = X.cigar_len;
@@ -433,6 +521,8 @@ SPM_HD inline bool jst_sam_resolve(const jst_sam_src &S, const spm_sam_line &L, 
         if ((X.pattern >> 1) != L.read || X.ref_begin > X.ref_end || !jst_sam_transcript_ok(X.cigar_off, X.cigar_len, S.n_rescue_ops))
             return false;
         pattern = X.pattern;
+        reverse = (X.flag & 0x10u) != 0;
+        ref_end = X.ref_end;
         F.pos = X.ref_begin + 1;
         F.words = S.rescue_ops + X.cigar_off;
         F.n_words = X.cigar_len;
@@ -441,14 +531,29 @@ SPM_HD inline bool jst_sam_resolve(const jst_sam_src &S, const spm_sam_line &L, 
     if (pattern >= S.n_needles || S.m[pattern] < 0)
         return false;
     F.m = (uint32_t)S.m[pattern];
+    if (mapped && S.ref)
+        F.md_ref = S.ref + (F.pos - 1);
     if (mapped && check_query) { // the query length of the transcript is the needle's
         uint64_t q, r;
         jst_sam_cigar_spans(F.words, F.n_words, q, r);
         if (q != F.m)
             return false;
+        if (S.ref) { // the locus and what the transcript spans lie inside the reference, whose X columns disagree with the read
+            if (ref_end > S.ref_n || F.pos - 1 > S.ref_n || r > S.ref_n - (F.pos - 1))
+                return false;
+            if (!jst_sam_md_agrees(F.words, F.n_words, F.md_ref, S.ranks + S.offsets[pattern]))
+                return false;
+        }
     }
-    if (L.kind != SPM_SAM_SECONDARY_LINE)
+    if (L.kind != SPM_SAM_SECONDARY_LINE) {
         F.seq = S.ranks + S.offsets[pattern];
+        if (S.qual) { // (a read and its reverse complement have one length: what q_off was summed from)
+            if (S.m[S.strands * L.read] != S.m[pattern])
+                return false;
+            F.qual = S.qual + S.q_off[L.read];
+            F.qual_reverse = reverse;
+        }
+    }
     if (!mapped)
         F.pos = mate_has ? A.mate_pos : 0;
     F.rname = mapped || mate_has;
@@ -467,7 +572,11 @@ SPM_HD constexpr uint64_t jst_sam_pack(const char *s, int n) { return n == 0 ? 0
 //   bytes(p, n)                    n characters at p
 //   seq(ranks, m, symbols, sigma)  m ranks as letters
 //   cigar(words, n, merge)
-template <class Sink> SPM_HD inline void jst_sam_compose(const jst_sam_src &S, const jst_sam_fields &F, Sink &out)
+//   qual(values, m, reverse, add)  m values + add, back to front with reverse
+//   md(words, n, ref, symbols, sigma)   the MD string; ref: the reference at the transcript's first position
+// kExtras = false: a composition that knows neither qual nor md, for a call without spm_sam_extras (the write kernel of such a
+// call is then the code it was before the two fields existed).
+template <bool kExtras = true, class Sink> SPM_HD inline void jst_sam_compose(const jst_sam_src &S, const jst_sam_fields &F, Sink &out)
 {
     if (S.names)
         out.bytes(S.names + S.name_off[F.name], S.name_off[F.name + 1] - S.name_off[F.name]);
@@ -496,12 +605,21 @@ template <class Sink> SPM_HD inline void jst_sam_compose(const jst_sam_src &S, c
     if (F.seq) {
         out.text(SPM_SAM_LIT("\t"));
         out.seq(F.seq, F.m, S.symbols, S.sigma);
-        out.text(SPM_SAM_LIT("\t*"));
+        if (kExtras && F.qual) {
+            out.text(SPM_SAM_LIT("\t"));
+            out.qual(F.qual, F.m, F.qual_reverse, 33);
+        } else {
+            out.text(SPM_SAM_LIT("\t*"));
+        }
     } else {
         out.text(SPM_SAM_LIT("\t*\t*"));
     }
     if (F.kind != SPM_SAM_UNMAPPED) {
         out.num(SPM_SAM_LIT("\tNM:i:"), jst_sam_int_abs(F.nm), F.nm < 0);
+        if (kExtras && F.md_ref) {
+            out.text(SPM_SAM_LIT("\tMD:Z:"));
+            out.md(F.words, F.n_words, F.md_ref, S.symbols, S.sigma);
+        }
         if (F.kind == SPM_SAM_RESCUE) {
             out.text(SPM_SAM_LIT("\tXR:i:1"));
         } else {
@@ -529,6 +647,13 @@ struct jst_sam_measure
         uint64_t add = 0;
         jst_sam_cigar_items(words, n_words, merge, [&add](uint64_t run, char) { add += jst_sam_word_len(run); });
         n += add;
+    }
+    SPM_HD void qual(const uint8_t *, uint32_t m, bool, uint8_t) { n += jst_sam_qual_len(m); }
+    SPM_HD void md(const uint32_t *words, uint32_t n_words, const uint8_t *, const char *, uint32_t)
+    {
+        uint64_t add = 0;
+        const uint64_t c = jst_sam_md_items(words, n_words, [&add](uint64_t c, uint32_t word, uint64_t) { add += jst_sam_md_word_len(c, word); });
+        n += add + jst_sam_dec_len(c);
     }
 };
 
@@ -574,6 +699,20 @@ struct jst_sam_serial
             for (uint32_t i = 0; i < len; ++i)
                 put(jst_sam_word_char(run, op, len, i));
         });
+    }
+    SPM_HD void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
+    {
+        for (uint32_t i = 0; i < jst_sam_qual_len(m); ++i)
+            put((char)jst_sam_qual_byte(values, m, reverse, add, i));
+    }
+    SPM_HD void md(const uint32_t *words, uint32_t n_words, const uint8_t *ref, const char *symbols, uint32_t sigma)
+    {
+        const uint64_t c = jst_sam_md_items(words, n_words, [&](uint64_t c, uint32_t word, uint64_t at) {
+            const uint64_t len = jst_sam_md_word_len(c, word);
+            for (uint64_t i = 0; i < len; ++i)
+                put(jst_sam_md_word_char(c, word, ref + at, symbols, sigma, i));
+        });
+        num(0, 0, c, false);
     }
 };
 

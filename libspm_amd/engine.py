@@ -801,11 +801,22 @@ class JstRefLoci(_RecordPool):
         secondary, one line per other locus.  reads: this object's reads(); patterns: the needle set behind the loci; pairs
         (and rescues): paired-end mode, reads 2p and 2p + 1 are mates.  names: one per read (paired: per pair), str or bytes;
         None prints the index.  mapq_unique / mapq_multi: four values each; None (both): the default tables.  The result
-        stays valid after every input is closed."""
+        stays valid after every input is closed.  (With base qualities and the MD tag: sam_ex.)"""
+        return self.sam_ex(reads, patterns, rname, pairs=pairs, rescues=rescues, names=names, symbols=symbols, cigar_m=cigar_m,
+                           secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi)
+
+    def sam_ex(self, reads: "JstReads", patterns: "PatternSet", rname: str, *, qualities=None, md: bool = False,
+               reference: "Text | None" = None, pairs: "JstPairs | None" = None, rescues: "JstRescues | None" = None, names=None,
+               symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False, mapq_unique=None, mapq_multi=None) -> "Sam":
+        """sam() with base qualities and the MD tag (spm_hip_jst_ref_loci_sam_ex).  qualities: Phred values 0 .. 93 as sequenced,
+        a 2-D uint8 array with one row per read or a sequence of arrays, printed as QUAL (back to front on a reverse line);
+        md with reference, the resident ranks the loci were projected against: an MD:Z: tag behind NM on every line with a
+        CIGAR.  With none of the three: the bytes of sam()."""
         opts = sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi)
         keep = _set_names(opts, names)
-        s = self._new("sam", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts))
-        del keep
+        extras, keep_q = sam_extras(qualities, md, reference)
+        s = self._new("sam_ex", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts), _ref_or_null(extras))
+        del keep, keep_q
         return Sam(self.ctx, s, rname)
 
     def bam(self, reads: "JstReads", patterns: "PatternSet", rname: str, ref_len: int, *, pairs: "JstPairs | None" = None,
@@ -813,13 +824,62 @@ class JstRefLoci(_RecordPool):
             mapq_unique=None, mapq_multi=None, block_data: int = 0) -> "Bam":
         """The alignments of sam() as a complete BAM file in device memory (spm_hip_jst_ref_loci_bam): header, records in BGZF
         blocks of block_data uncompressed bytes (0: 65280; stored, nothing is compressed), EOF block.  ref_len: the length of
-        the reference, 1 .. 2^31 - 1.  Every other argument as for sam().  The result stays valid after every input is closed."""
+        the reference, 1 .. 2^31 - 1.  Every other argument as for sam().  The result stays valid after every input is closed.
+        (With base qualities and the MD tag: bam_ex.)"""
+        return self.bam_ex(reads, patterns, rname, ref_len, pairs=pairs, rescues=rescues, names=names, symbols=symbols, cigar_m=cigar_m,
+                           secondary=secondary, mapq_unique=mapq_unique, mapq_multi=mapq_multi, block_data=block_data)
+
+    def bam_ex(self, reads: "JstReads", patterns: "PatternSet", rname: str, ref_len: int, *, qualities=None, md: bool = False,
+               reference: "Text | None" = None, pairs: "JstPairs | None" = None, rescues: "JstRescues | None" = None, names=None,
+               symbols: str = "ACGT", cigar_m: bool = False, secondary: bool = False, mapq_unique=None, mapq_multi=None,
+               block_data: int = 0) -> "Bam":
+        """bam() with base qualities and the MD tag (spm_hip_jst_ref_loci_bam_ex): qualities, md and reference as for sam_ex();
+        the reference has ref_len symbols."""
         opts = capi.BamOpts(sam=sam_opts(rname, symbols, cigar_m=cigar_m, secondary=secondary, mapq_unique=mapq_unique,
                                          mapq_multi=mapq_multi), ref_len=int(ref_len), block_data=int(block_data), reserved=0)
         keep = _set_names(opts.sam, names)
-        b = self._new("bam", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts))
-        del keep
+        extras, keep_q = sam_extras(qualities, md, reference)
+        b = self._new("bam_ex", reads._h, _or_null(pairs), _or_null(rescues), patterns._h, C.byref(opts), _ref_or_null(extras))
+        del keep, keep_q
         return Bam(self.ctx, b, _block_data(block_data))
+
+
+def _ref_or_null(struct):
+    """an optional struct argument by reference"""
+    return C.byref(struct) if struct is not None else None
+
+
+def sam_extras(qualities=None, md: bool = False, reference: "Text | None" = None):
+    """spm_sam_extras of JstRefLoci.sam() / bam() -> (the struct, or None when nothing is asked for; what has to stay alive
+    across the call).  qualities: a 2-D uint8 array, one row per read, or a sequence of arrays, back to back in read order."""
+    if qualities is None and not md and reference is None:
+        return None, None
+    cat = None
+    if qualities is not None:
+        if isinstance(qualities, np.ndarray) and qualities.ndim == 2:
+            cat = np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+        else:
+            rows = [np.ascontiguousarray(q, dtype=np.uint8).reshape(-1) for q in qualities]
+            cat = np.concatenate(rows) if rows else np.zeros(0, np.uint8)
+    extras = capi.SamExtras(qual=cat.ctypes.data if cat is not None and cat.size else None, n_qual=cat.size if cat is not None else 0,
+                            reference=_or_null(reference), flags=capi.SAM_MD if md else 0, reserved=0)
+    return extras, cat
+
+
+def sam_md(words, ref_ranks, ref_begin: int, symbols: str = "ACGT") -> str:
+    """The MD string of one transcript (words: len << 4 | op) whose first reference position is ref_begin, by the serial host
+    rendering of the device's rule (spm_hip_sam_md).  Needs no device."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    ref = np.ascontiguousarray(ref_ranks, dtype=np.uint8)
+    sym = symbols.encode() if isinstance(symbols, str) else bytes(symbols)
+    wp = w.ctypes.data_as(C.POINTER(C.c_uint32)) if w.size else None
+    rp = (ref if ref.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def refuse(rc):
+        raise capi.SpmError(f"libspm_hip error {rc}: spm_hip_sam_md: the transcript leaves the reference [0, {ref.size})")
+
+    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_sam_md(wp, w.size, rp, ref.size, int(ref_begin), sym, buf, cap, need),
+                           refuse).decode()
 
 
 def _set_names(opts: "capi.SamOpts", names):

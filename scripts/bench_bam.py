@@ -9,9 +9,11 @@ device's); and, once, the frame kernel alone over raw buffers of pseudo-random b
 block sizes in RAW_SHAPES).  Every figure is the MEDIAN of --runs calls behind one warm-up call.  Nothing is asserted but that
 two calls return the same bytes, that the file's size is what its statistics say, that gzip reads the framed SAM text back and
 that the framed raw buffers equal the host framer's.  The row runs in a child process of its own under a time limit.
+With --qual and / or --md the calls are spm_hip_jst_ref_loci_bam_ex / _sam_ex with the qualities of bench_sam.phred_profile and /
+or the MD tag; the host route's timer knows neither, so its figure is left out then.
 
     python scripts/bench_bam.py [--pan-log2 27] [--pan-reads 100000] [--runs 5] [--min-tlen 200] [--max-tlen 600] [--k 12]
-                                [--row-timeout 420] [--out profiles/r15/bam.jsonl]
+                                [--qual] [--md] [--row-timeout 420] [--out profiles/r15/bam.jsonl]
 """
 import argparse
 import ctypes
@@ -35,6 +37,7 @@ import libspm_amd as S  # noqa: E402
 sys.dont_write_bytecode = True  # (scripts/ holds programs, not a package: leave no cache directory beside them)
 from bench_pairs import COMP4, med  # noqa: E402
 from bench_rescue import build  # noqa: E402
+from bench_sam import phred_profile  # noqa: E402
 
 BAM_STAGES = ("ms_total", "ms_lines", "ms_measure", "ms_write", "ms_frame", "ms_stats")
 SAM_STAGES = ("ms_total", "ms_lines", "ms_measure", "ms_write", "ms_stats")
@@ -69,7 +72,7 @@ def raw_rows(ctx, runs):
     return out
 
 
-def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
+def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k, qual=False, md=False):
     ctx = S.Context(0)
     ref, jst, ps, reads, out = build(ctx, pan_log2, pan_reads)
     h = jst.search_device(ps, max_hits=1 << 26)
@@ -84,6 +87,8 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
     ref_len = len(ref)
     out.update({"loci": len(lc), "min_tlen": min_tlen, "max_tlen": max_tlen, "k": k, "rescue_jobs": len(rs), "ref_len": ref_len})
     names = [f"pair.{p}/frag" for p in range(len(reads) // 2)]
+    extras = {"qualities": phred_profile(len(reads), reads.shape[1]) if qual else None, "md": md, "reference": ref if md else None}
+    out.update({"qual": qual, "md": md})
     # the views the C++ mirror's host route converts, downloaded once and written where its timer (bench_bam_host.cpp) reads them
     tmp = tempfile.mkdtemp(prefix="bench_bam_")
     t0 = time.perf_counter()
@@ -105,7 +110,7 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
         first = None
         for i in range(runs + 1):
             t0 = time.perf_counter()
-            b = lc.bam(rd, ps, "pan_ref", ref_len, pairs=pairs, rescues=rs, **kw)
+            b = lc.bam_ex(rd, ps, "pan_ref", ref_len, pairs=pairs, rescues=rs, **extras, **kw)
             call.append((time.perf_counter() - t0) * 1e3)
             st = b.stats()
             for x in BAM_STAGES:
@@ -118,7 +123,7 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
             assert raw == first, "two calls returned different bytes"
             counts = {c: int(getattr(st, c)) for c in COUNTS}
             b.close()
-            s = lc.sam(rd, ps, "pan_ref", pairs=pairs, rescues=rs, **kw)
+            s = lc.sam_ex(rd, ps, "pan_ref", pairs=pairs, rescues=rs, **extras, **kw)
             ss = s.stats()
             for x in SAM_STAGES:
                 sam[x].append(getattr(ss, x))
@@ -133,15 +138,18 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
         bits = "".join("1" if kw.get(x) else "0" for x in ("cigar_m", "secondary", "names"))
         with open(os.path.join(tmp, f"bam_{bits}.bin"), "wb") as f:
             f.write(first)
-        r = subprocess.run([exe, tmp, str(reads.shape[1]), str(runs)] + list(bits) + [str(ref_len)], capture_output=True, text=True)
-        assert r.returncode == 0, "the host route and the device disagree: " + r.stdout[-500:] + r.stderr[-500:]
+        host_route = None
+        if not qual and not md:
+            r = subprocess.run([exe, tmp, str(reads.shape[1]), str(runs)] + list(bits) + [str(ref_len)], capture_output=True, text=True)
+            assert r.returncode == 0, "the host route and the device disagree: " + r.stdout[-500:] + r.stderr[-500:]
+            host_route = json.loads(r.stdout.strip().splitlines()[-1])
         out[label] = {"bam": {x: med(v[1:]) for x, v in bam.items()}, "sam_same_run": {x: med(v[1:]) for x, v in sam.items()},
                       "ms_call_host": med(call[1:]), "ms_first_call_host": round(call[0], 3), "ms_download_file": med(view[1:]), **counts,
                       "write_gb_per_s": round(counts["n_record_bytes"] / max(med(bam["ms_write"][1:]), 1e-6) / 1e6, 3),
                       "frame_gb_per_s": round(counts["n_record_bytes"] / max(med(bam["ms_frame"][1:]), 1e-6) / 1e6, 3),
                       "sam_text_bytes": sam_bytes, "ms_frame_sam_text": ms_frame_text,
                       "frame_sam_text_gb_per_s": round(sam_bytes / max(ms_frame_text, 1e-6) / 1e6, 3),
-                      "host_route": json.loads(r.stdout.strip().splitlines()[-1])}
+                      "host_route": host_route}
     shutil.rmtree(tmp, ignore_errors=True)
     for x in (rs, pairs, rd, lc, nz, pr, a, sel, h, ps, jst, ref):
         x.close()
@@ -157,6 +165,8 @@ def main():
     ap.add_argument("--min-tlen", type=int, default=200)
     ap.add_argument("--max-tlen", type=int, default=600)
     ap.add_argument("--k", type=int, default=12)
+    ap.add_argument("--qual", action="store_true", help="with base qualities (bench_sam.phred_profile)")
+    ap.add_argument("--md", action="store_true", help="with the MD tag")
     ap.add_argument("--row-timeout", type=int, default=420, help="seconds the row's child process may take")
     ap.add_argument("--out", default=None, help="also write the line to this file")
     ap.add_argument("--row", action="store_true", help=argparse.SUPPRESS)   # the child's mode: the row's JSON on stdout
@@ -164,10 +174,11 @@ def main():
     if a.runs < 5:
         ap.error("--runs: a median of at least 5 runs")
     if a.row:
-        print(json.dumps(row(a.pan_log2, a.pan_reads, a.runs, a.min_tlen, a.max_tlen, a.k)))
+        print(json.dumps(row(a.pan_log2, a.pan_reads, a.runs, a.min_tlen, a.max_tlen, a.k, a.qual, a.md)))
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--row", "--pan-log2", str(a.pan_log2), "--pan-reads", str(a.pan_reads),
            "--runs", str(a.runs), "--min-tlen", str(a.min_tlen), "--max-tlen", str(a.max_tlen), "--k", str(a.k)]
+    cmd += (["--qual"] if a.qual else []) + (["--md"] if a.md else [])
     r = subprocess.run(["timeout", "-k", "10", str(a.row_timeout)] + cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
