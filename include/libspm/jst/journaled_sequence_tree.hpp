@@ -189,6 +189,7 @@ struct jst_bam_options
     std::uint64_t ref_len{0};           // 1 .. 2^31 - 1
     std::uint32_t block_data{0};        // uncompressed bytes per BGZF block, 0: 65280
     bool deflate{false};                // the blocks compressed (spm_hip_bam_deflate / spm_hip_bgzf_deflate_host), not stored
+    bool dynamic{false};                // with deflate only: a block may take a Huffman code of its own (SPM_BGZF_DYNAMIC)
     bool sort{false};                   // the records in coordinate order under SO:coordinate (spm_hip_bam_sort)
     bool index{false};                  // with sort: jst_bam::bai, the .bai of the file (spm_hip_bam_index / spm_hip_bai_build_host)
 };
@@ -1207,7 +1208,7 @@ public:
         put(plain, o.ref_len, 4);
         auto const frame = [&](std::string const & data, bool eof) {
             spm_bgzf_opts const z{o.block_data, eof ? SPM_BGZF_EOF : 0u, 0};
-            spm_bgzf_deflate_opts const dz{o.block_data, eof ? SPM_BGZF_EOF : 0u, 1, 0};
+            spm_bgzf_deflate_opts const dz{o.block_data, (eof ? SPM_BGZF_EOF : 0u) | (o.dynamic ? SPM_BGZF_DYNAMIC : 0u), 1, 0};
             std::uint64_t need = 0;
             int rc = o.deflate ? spm_hip_bgzf_deflate_bound(data.size(), &dz, &need)
                                : spm_hip_bgzf_frame_host(data.data(), data.size(), &z, nullptr, 0, &need);
@@ -1939,7 +1940,7 @@ private:
             req.bam_out->header_file_bytes = st.header_file_bytes;
             req.bam_out->block_offsets.clear();
             if (req.bam_options->deflate) {
-                spm_bgzf_deflate_opts const dz{req.bam_options->block_data, SPM_BGZF_EOF, 1, 0};
+                spm_bgzf_deflate_opts const dz{req.bam_options->block_data, SPM_BGZF_EOF | (req.bam_options->dynamic ? SPM_BGZF_DYNAMIC : 0u), 1, 0};
                 spm_bgzf * z = nullptr;
                 if (spm_hip_bam_deflate(b, &dz, &z) != SPM_OK)
                     hip::fatal("spm_hip_bam_deflate", ctx);

@@ -1118,6 +1118,7 @@ int spm_hip_sam_md(const uint32_t *words, uint32_t n_words, const uint8_t *ref_r
  * The result is a pure function of the bytes and the opts: equal to spm_hip_bgzf_frame_host of the same bytes, host and device
  * view equal.  It outlives the source. */
 #define SPM_BGZF_EOF 1u             /* append the end-of-file block */
+#define SPM_BGZF_DYNAMIC 4u         /* the deflate calls only: a block may take a Huffman code of its own (see there) */
 #define SPM_BGZF_BLOCK_DATA 65280u  /* the default and the most a block holds: htslib's 0xff00 */
 typedef struct spm_bgzf_opts {      /* 16 bytes */
     uint32_t block_data;            /* uncompressed bytes per block, 1 .. 65280; 0: 65280 */
@@ -1169,15 +1170,49 @@ int spm_hip_bgzf_framed_size(uint64_t n, const spm_bgzf_opts *opts, uint64_t *le
  * A record at offset u of the uncompressed stream has the BGZF virtual offset offsets[u / D] << 16 | u % D, with the offsets
  * of spm_hip_bgzf_blocks.
  *
+ * SPM_BGZF_DYNAMIC lets a block take a Huffman code of its own (BTYPE 10), built on the device by the workgroup that parses
+ * the block.  The tokens are the same; only their coding may change.  Without the flag every call gives the bytes above.
+ * With it, per block of d bytes (again a pure function of the bytes and the opts, and again spm_hip_bgzf_deflate_host's):
+ *   1. Counts: the literal/length symbols 0 .. 285 of the block's tokens, symbol 256 once; the distance symbols 0 .. 29.  An
+ *      alphabet with fewer than two symbols in use gives count 1 to its lowest-numbered unused symbols until it has two (zlib's
+ *      device), so every code the block transmits is complete.
+ *   2. Code lengths: an optimal length-limited prefix code, lengths <= 15 (<= 7 for the code-length code): the sum of count x
+ *      length is minimal.  Which optimal code: package-merge over the symbols in use sorted by (count, symbol); a level's list
+ *      is the symbols merged with the pairwise sums of the level below (an odd last item dropped), a symbol in front of a sum
+ *      of equal weight; the first 2n - 2 items of the last level are taken, and the items their sums are made of.  So a symbol
+ *      with a larger count never has a longer code, and of two with equal counts the lower-numbered never the shorter one.
+ *      Codes are assigned canonically (RFC 1951 3.2.2).
+ *   3. Header: HLIT and HDIST from the highest symbol with a nonzero length.  The HLIT + 257 + HDIST + 1 lengths are ONE
+ *      sequence (a run may cross from the literal/length part into the distance part), run-length coded greedily from the
+ *      left: a run of zeros of 3 or more takes symbol 18 (11 .. 138) or 17 (3 .. 10), each as long as it can be; a run of a
+ *      nonzero length is sent once, then by symbol 16 (3 .. 6) while 3 or more remain; what is left goes as plain lengths.
+ *      Steps 1 and 2 (limit 7) over the counts of these 19 symbols; HCLEN from the last nonzero entry in the RFC's permuted
+ *      order, at least 4.
+ *   4. Bits: 1 (BFINAL), 0 1 (BTYPE 10), HLIT in 5 bits, HDIST in 5, HCLEN in 4, 3 bits per code-length code length, the coded
+ *      sequence with its extra bits, the lanes' tokens in lane order with their extra bits, the code of symbol 256, zero
+ *      padding to the byte.
+ *   5. Choice: with s = d + 5, f the fixed payload's bytes and y the dynamic payload's: stored if neither f nor y is below s;
+ *      else the smaller of f and y, fixed when they are equal.  So no block is longer than without the flag.
+ * Worked cases, block_data 0, no EOF block:
+ *   "ab" 20 times (40 literals; lengths: 'a' 2, 'b' 1, 256 2; distance symbols 0 and 1 padded in with length 1; HLIT 0,
+ *   HDIST 1, HCLEN 14; 105 bits in front of the first token, 167 in all), 47 bytes where the fixed form takes 68:
+ *       1f8b08040000000000ff0600424302002e00 05c181000000008020d6f387b89224499224499264 135ad4bc 28000000
+ *   1000 bytes 'a' (lane 0: literal, match 63 at 1; lanes 1 .. 14: match 64 at 1; lane 15: match 40 at 1; HLIT 20, HDIST 1,
+ *   HCLEN 14), 53 bytes where the fixed form takes 59:
+ *       1f8b08040000000000ff0600424302003400 a5c1010d000000c2a0acf62f61856fc090524a29a594524a29551d 03da389a e8030000
+ *   The 6 bytes "abcdef", a block of one byte and the 300 bytes 'a' above keep their fixed form: the dynamic header alone
+ *   outweighs them.
+ *
  *   * SPM_E_INVALID with a message, decided on the host before any launch: NULL ctx, opts or out; NULL device_src with n > 0;
- *     block_data above 65280; flag bits other than SPM_BGZF_EOF; a level other than 1; a nonzero reserved.
+ *     block_data above 65280; flag bits other than SPM_BGZF_EOF and SPM_BGZF_DYNAMIC (2 stays refused); a level other
+ *     than 1; a nonzero reserved.
  *   * SPM_E_UNSUPPORTED, likewise: more than 2^31 - 2 blocks.
  *   * n == 0: SPM_OK with the EOF block, or with nothing.
  * The result is a spm_bgzf: view, device, stats (n_out the real size) and destroy work on it.  It outlives the source. */
 typedef struct spm_bgzf_deflate_opts { /* 16 bytes */
     uint32_t block_data;            /* uncompressed bytes per block, 1 .. 65280; 0: 65280 */
-    uint32_t flags;                 /* SPM_BGZF_EOF */
-    uint32_t level;                 /* must be 1: fixed Huffman */
+    uint32_t flags;                 /* SPM_BGZF_EOF, SPM_BGZF_DYNAMIC */
+    uint32_t level;                 /* must be 1: the greedy parse */
     uint32_t reserved;              /* must be 0 */
 } spm_bgzf_deflate_opts;
 typedef struct spm_bgzf_deflate_stats { /* 72 bytes */
@@ -1189,7 +1224,7 @@ typedef struct spm_bgzf_deflate_stats { /* 72 bytes */
     uint64_t n_out;                 /* the file's bytes, prefix and EOF block included */
     uint64_t n_blocks;              /* data blocks of the device part */
     uint64_t n_stored_blocks;       /* of them, those that did not shrink */
-    uint64_t n_matches;             /* tokens of the blocks that came out fixed */
+    uint64_t n_matches;             /* tokens of the blocks that were not stored */
     uint64_t n_literals;
     uint64_t n_prefix_bytes;        /* bytes in front of the first data block (spm_hip_bam_deflate: the header's blocks) */
 } spm_bgzf_deflate_stats;
@@ -1200,8 +1235,11 @@ int spm_hip_bgzf_blocks(spm_bgzf *z, const uint64_t **offsets, uint64_t *n_block
 int spm_hip_bgzf_blocks_device(spm_bgzf *z, const void **offsets, uint64_t *n_blocks);
 /* of a handle of spm_hip_bgzf_frame: every block stored, no tokens, ms_place the frame stage */
 int spm_hip_bgzf_deflate_stats(const spm_bgzf *z, spm_bgzf_deflate_stats *out);
+/* the handle's data blocks that came out stored (n[0]), fixed (n[1]) and dynamic (n[2]); they sum to n_blocks.  Of a handle
+ * of spm_hip_bgzf_frame every block is stored.  A NULL argument: SPM_E_INVALID. */
+int spm_hip_bgzf_block_types(const spm_bgzf *z, uint64_t n[3]);
 /* host only, no device needed: the same bytes by the serial rendering of the same rule.  *len is what it needs
- * (spm_hip_bgzf_deflate_bound is enough: the stored size); cap too small: SPM_E_OVERFLOW and nothing is written. */
+ * (spm_hip_bgzf_deflate_bound is enough: the stored size, with SPM_BGZF_DYNAMIC too); cap too small: SPM_E_OVERFLOW and nothing is written. */
 int spm_hip_bgzf_deflate_host(const void *src, uint64_t n, const spm_bgzf_deflate_opts *opts, void *dst, uint64_t cap, uint64_t *len);
 int spm_hip_bgzf_deflate_bound(uint64_t n, const spm_bgzf_deflate_opts *opts, uint64_t *len);
 

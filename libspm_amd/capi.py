@@ -343,7 +343,7 @@ class BgzfStats(C.Structure):
                 ("n_blocks", C.c_uint64)]
 
 
-BGZF_EOF, BGZF_BLOCK_DATA = 1, 65280
+BGZF_EOF, BGZF_DYNAMIC, BGZF_BLOCK_DATA = 1, 4, 65280
 
 
 class BgzfDeflateOpts(C.Structure):
@@ -565,6 +565,7 @@ SIGNATURES = {
     "spm_hip_bgzf_blocks": (C.c_int, [_vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
     "spm_hip_bgzf_blocks_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "spm_hip_bgzf_deflate_stats": (C.c_int, [_vp, C.POINTER(BgzfDeflateStats)]),
+    "spm_hip_bgzf_block_types": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "spm_hip_bgzf_deflate_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(BgzfDeflateOpts), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "spm_hip_bgzf_deflate_bound": (C.c_int, [C.c_uint64, C.POINTER(BgzfDeflateOpts), C.POINTER(C.c_uint64)]),
     "spm_hip_bam_deflate": (C.c_int, [_vp, C.POINTER(BgzfDeflateOpts), C.POINTER(_vp)]),

@@ -178,8 +178,8 @@ static int deflate_check_opts(const char *who, spm_ctx *ctx, const spm_bgzf_defl
 {
     const char *why = !o                                ? "NULL opts"
                       : o->block_data > kBgzfBlockData  ? "block_data above 65280"
-                      : (o->flags & ~SPM_BGZF_EOF)      ? "unknown flag bits"
-                      : o->level != 1                   ? "level is not 1 (fixed Huffman, the one there is)"
+                      : (o->flags & ~(SPM_BGZF_EOF | SPM_BGZF_DYNAMIC)) ? "unknown flag bits"
+                      : o->level != 1                   ? "level is not 1 (the greedy parse, the one there is)"
                       : o->reserved                     ? "reserved is not 0"
                                                         : nullptr;
     if (!why)
@@ -194,7 +194,7 @@ static int deflate_check_opts(const char *who, spm_ctx *ctx, const spm_bgzf_defl
 extern "C" int spm_hip_bgzf_deflate_bound(uint64_t n, const spm_bgzf_deflate_opts *opts, uint64_t *len)
 {
     SPM_TRY(deflate_check_opts("spm_hip_bgzf_deflate_bound", nullptr, opts));
-    const spm_bgzf_opts o{opts->block_data, opts->flags, 0};
+    const spm_bgzf_opts o{opts->block_data, opts->flags & SPM_BGZF_EOF, 0};
     return spm_hip_bgzf_framed_size(n, &o, len);
 }
 
@@ -210,7 +210,7 @@ extern "C" int spm_hip_bgzf_deflate_host(const void *src, uint64_t n, const spm_
     SPM_TRY(spm_hip_bgzf_deflate_bound(n, opts, &bound));
     std::vector<uint8_t> file(bound);
     *len = bgzf_deflate_serial(static_cast<const uint8_t *>(src), n, bgzf_block_data(opts->block_data), (opts->flags & SPM_BGZF_EOF) != 0,
-                               file.data());
+                               file.data(), nullptr, nullptr, (opts->flags & SPM_BGZF_DYNAMIC) != 0);
     if (*len > cap)
         return SPM_E_OVERFLOW;
     if (*len)
@@ -224,7 +224,7 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
 {
     const auto t_call = clk::now();
     const uint32_t D = bgzf_block_data(opts->block_data);
-    const bool eof = (opts->flags & SPM_BGZF_EOF) != 0;
+    const bool eof = (opts->flags & SPM_BGZF_EOF) != 0, dynamic = (opts->flags & SPM_BGZF_DYNAMIC) != 0;
     const uint64_t n_blocks = bgzf_n_blocks(n, D);
     if (n_blocks > kBgzfMaxBlocks) {
         SPM_SET_ERR(ctx, "%s: %llu bytes in blocks of %u are more than 2^31 - 2 blocks (not supported)", who, (unsigned long long)n, D);
@@ -264,7 +264,7 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
         SPM_HIP_CHECK(ctx, keep.alloc(&P.slots, n * 2));
         SPM_HIP_CHECK(ctx, keep.alloc(&P.stage, n_blocks * P.stage_words * 4));
         SPM_HIP_CHECK(ctx, keep.alloc(&P.crc, n_blocks * 4));
-        hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)n_blocks), dim3(kBgzfLanes), 0, st, P);
+        hipLaunchKernelGGL(dynamic ? bgzf_deflate_kernel<true> : bgzf_deflate_kernel<false>, dim3((unsigned)n_blocks), dim3(kBgzfLanes), 0, st, P);
         SPM_HIP_CHECK(ctx, hipGetLastError());
     }
     SPM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
@@ -297,6 +297,7 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
     S.n_matches = ctx->h_counters[1 + kDefCntMatches];
     S.n_literals = ctx->h_counters[1 + kDefCntLiterals];
     S.n_prefix_bytes = prefix.size();
+    Z->n_dynamic_blocks = ctx->h_counters[1 + kDefCntDynamic];
     S.ms_host = ms_since(t_call);
     Z->stats.ms_frame = S.ms_parse + S.ms_scan + S.ms_place;
     Z->stats.ms_host = S.ms_host;
@@ -304,9 +305,9 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
     Z->stats.n_out = Z->n;
     Z->stats.n_blocks = n_blocks;
     if (spm_trace_on())
-        fprintf(stderr, "[spm_hip] bgzf deflate: %llu bytes -> %llu blocks of %u (%llu stored)%s, %llu bytes: parse %.3f, scan %.3f, place "
-                        "%.3f ms, %.3f ms in all\n", (unsigned long long)n, (unsigned long long)n_blocks, D,
-                (unsigned long long)S.n_stored_blocks, eof ? " + EOF" : "", (unsigned long long)Z->n, S.ms_parse, S.ms_scan, S.ms_place,
+        fprintf(stderr, "[spm_hip] bgzf deflate: %llu bytes -> %llu blocks of %u (%llu stored, %llu dynamic)%s, %llu bytes: parse %.3f, scan "
+                        "%.3f, place %.3f ms, %.3f ms in all\n", (unsigned long long)n, (unsigned long long)n_blocks, D,
+                (unsigned long long)S.n_stored_blocks, (unsigned long long)Z->n_dynamic_blocks, eof ? " + EOF" : "", (unsigned long long)Z->n, S.ms_parse, S.ms_scan, S.ms_place,
                 S.ms_host);
     *out = Z.release();
     return SPM_OK;
@@ -389,6 +390,16 @@ extern "C" int spm_hip_bgzf_deflate_stats(const spm_bgzf *z, spm_bgzf_deflate_st
     return SPM_OK;
 }
 
+extern "C" int spm_hip_bgzf_block_types(const spm_bgzf *z, uint64_t n[3])
+{
+    if (!z || !n)
+        return SPM_E_INVALID;
+    n[0] = z->deflate.n_stored_blocks;
+    n[2] = z->n_dynamic_blocks;
+    n[1] = z->deflate.n_blocks - n[0] - n[2];
+    return SPM_OK;
+}
+
 // ---- a BAM handle in coordinate order and the BAI index of one: they read the handles above ----
 #include "bam_index.hpp"
 
@@ -396,7 +407,8 @@ void spm_warm_bgzf_kernels()
 {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_frame_kernel);
-    (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel);
+    (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel<false>);
+    (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel<true>);
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_place_kernel);
     (void)hipFuncGetAttributes(&a, (const void *)bam_gather_kernel);
     (void)hipFuncGetAttributes(&a, (const void *)bai_records_kernel);

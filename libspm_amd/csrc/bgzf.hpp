@@ -183,6 +183,7 @@ struct spm_bgzf
     bool have_host_offsets = false;
     std::vector<uint64_t> host_offsets;
     spm_bgzf_deflate_stats deflate{};
+    uint64_t n_dynamic_blocks = 0; // spm_hip_bgzf_block_types: of the blocks that are not stored, those with a code of their own
 };
 static_assert(sizeof(spm_bgzf_opts) == 16 && sizeof(spm_bgzf_stats) == 32, "spm_hip.h states these sizes");
 static_assert(sizeof(spm_bgzf_deflate_opts) == 16 && sizeof(spm_bgzf_deflate_stats) == 72, "spm_hip.h states these sizes");

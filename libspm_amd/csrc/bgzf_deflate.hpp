@@ -16,7 +16,8 @@
 //                         its payload out of the staging row (dwords funnel-shifted to the destination's alignment), CRC and
 //                         ISIZE; a stored block by bgzf_frame_block, straight from the source; the workgroup behind the last
 //                         writes the EOF block.  No store leaves the block's own bytes.
-// Every loop is bounded by the chunk, 258 or d / 256; no lane waits for another outside a barrier.  No read passes src + n.
+//                         bgzf_deflate_kernel<true> (SPM_BGZF_DYNAMIC) adds the block's own Huffman code: see at the kernel.
+// Every loop is bounded by the chunk, 258, d / 256, an alphabet or the 15 levels of the code build; no lane waits for another outside a barrier.  No read passes src + n.
 #pragma once
 
 #include "bgzf.hpp"
@@ -26,9 +27,9 @@
 namespace spm_hip
 {
 
-enum : uint32_t { kDefCntStored = 0, kDefCntMatches, kDefCntLiterals, kDefCnts };
+enum : uint32_t { kDefCntStored = 0, kDefCntMatches, kDefCntLiterals, kDefCntDynamic, kDefCnts };
 
-// words of a block's staging row: the longest fixed payload (D + 4 bytes) and one word more for the funnel shift
+// words of a block's staging row: the longest coded payload (D + 4 bytes) and one word more for the funnel shift
 inline uint32_t deflate_stage_words(uint32_t D) { return (D + kDefStored - 1 + 3) / 4 + 1; }
 
 struct bgzf_deflate_params
@@ -40,15 +41,44 @@ struct bgzf_deflate_params
     uint32_t stage_words = 0;
     bgzf_lane_plan L{};
     uint16_t *slots = nullptr;           // [n] a position's far candidate, then its token
-    uint32_t *stage = nullptr;           // [n_blocks][stage_words] the payload of a fixed block
+    uint32_t *stage = nullptr;           // [n_blocks][stage_words] the payload of a coded block
     uint32_t *size = nullptr;            // [n_blocks] the block's bytes in the file
-    uint32_t *crc = nullptr;             // [n_blocks] of a fixed block's data
+    uint32_t *crc = nullptr;             // [n_blocks] of a coded block's data
     unsigned long long *offsets = nullptr; // [n_blocks + 1] file offsets behind the scan; [n_blocks] is where the EOF block goes
     unsigned long long *counts = nullptr;  // [kDefCnts]
     uint8_t *dst = nullptr;
 };
 
-__global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_deflate_params P)
+struct huff_barrier
+{
+    __device__ __forceinline__ void operator()() const { __syncthreads(); }
+};
+static_assert(sizeof(huff_work) <= (4u << kDefHashBits), "the code build works in the LDS the hash table left");
+
+// this lane's v summed over the lanes in front of it, and over the workgroup; wave_v is free again behind the call
+__device__ __forceinline__ uint32_t deflate_block_prefix(uint32_t v, uint32_t *wave_v, uint32_t &total)
+{
+    const uint32_t t = threadIdx.x, incl = wave_prefix_incl(v);
+    __syncthreads();
+    if (t % kWave == kWave - 1)
+        wave_v[t / kWave] = incl;
+    __syncthreads();
+    uint32_t before = incl - v;
+    total = 0;
+    for (uint32_t w = 0; w < kBgzfLanes / kWave; ++w) {
+        before += w < t / kWave ? wave_v[w] : 0;
+        total += wave_v[w];
+    }
+    return before;
+}
+
+// Dynamic: the block also sizes its tokens in a Huffman code of its own (SPM_BGZF_DYNAMIC; bgzf_huffman_core.hpp) and takes
+// the smallest of the three forms.  Behind the candidate rounds the table's LDS holds the two histograms (LDS atomics: sums do
+// not depend on the lanes' order) and the work space of huff_block_build, which the workgroup runs as one; the code itself
+// (huff_code, 2 KiB) has LDS of its own, because the payload's words take the table's place.  A second walk of the lane's tokens
+// gives its bits in that code, a second prefix its first bit; lane 0 writes the header in front of its tokens, the last lane
+// the end-of-block code behind its own.  The false instantiation is the fixed coder as it was.
+template <bool Dynamic> __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_deflate_params P)
 {
     __shared__ uint32_t table[1u << kDefHashBits]; // the hash table, then the payload's words
     __shared__ uint32_t wave_v[kBgzfLanes / kWave];
@@ -78,6 +108,12 @@ __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_def
             atomicMax(&table[h], pos + 1);
         __syncthreads(); // (the last one also hands the slots to the lanes that parse them)
     }
+    [[maybe_unused]] huff_work &W = *reinterpret_cast<huff_work *>(table);
+    if constexpr (Dynamic) {
+        for (uint32_t i = t; i < kHufSeq; i += kBgzfLanes)
+            W.count[i] = i == kHufEob;
+        __syncthreads();
+    }
     // ---- parse ----
     const uint32_t c = deflate_chunk(d);
     const uint32_t lo = (uint64_t)t * c < d ? t * c : d, hi = lo + c < d ? lo + c : d;
@@ -87,6 +123,13 @@ __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_def
         uint32_t len, v;
         deflate_token_at(from, i, hi, slots[i], len, v);
         bits += deflate_token_bits(len, v);
+        if constexpr (Dynamic) {
+            uint32_t ls, ds;
+            huff_count_token(len, v, ls, ds);
+            atomicAdd(&W.count[ls], 1u);
+            if (ds < kHufDist)
+                atomicAdd(&W.count[kHufLitLen + ds], 1u);
+        }
         if (len > 1) {
             slots[i] = (uint16_t)len;
             slots[i + 1] = (uint16_t)(v - 1);
@@ -108,29 +151,49 @@ __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_def
         total += wave_v[w];
     }
     const uint32_t fixed = deflate_fixed_bytes(total);
-    if (!deflate_takes_fixed(fixed, d)) { // (the whole workgroup)
+    uint32_t dyn = d + kDefStored, dyn_before = 0;
+    [[maybe_unused]] __shared__ huff_code K;
+    if constexpr (Dynamic) {
+        uint32_t floor_tokens = 0; // literals + 2 matches: what huff_may_win counts
+        deflate_block_prefix(n_literals + 2 * n_matches, wave_v, floor_tokens);
+        const uint32_t other = fixed < d + kDefStored ? fixed : d + kDefStored;
+        if (huff_may_win(floor_tokens, 0, other)) { // (the whole workgroup)
+            huff_block_build(W, K, t, kBgzfLanes, huff_barrier{});
+            uint32_t dyn_bits = 0;
+#pragma unroll 1
+            for (uint32_t i = lo; i < hi;) {
+                const uint32_t len = slots[i];
+                dyn_bits += len ? huff_token_bits(K, len, slots[i + 1] + 1u) : huff_token_bits(K, 1, from[i]);
+                i += len ? len : 1;
+            }
+            uint32_t dyn_total = 0;
+            dyn_before = deflate_block_prefix(dyn_bits, wave_v, dyn_total);
+            dyn = huff_dynamic_bytes(K, dyn_total);
+        }
+    }
+    const uint32_t type = deflate_choose(fixed, dyn, d);
+    if (type == 0) { // (the whole workgroup)
         if (t == 0) {
             P.size[b] = d + kBgzfFrame;
             atomicAdd(&P.counts[kDefCntStored], 1ull);
         }
         return;
     }
+    const bool coded_dyn = Dynamic && type == 2;
+    const uint32_t payload = coded_dyn ? dyn : fixed;
     // ---- the bits, in the LDS the table left ----
-    const uint32_t words = (fixed + 3) / 4;
+    const uint32_t words = (payload + 3) / 4;
     for (uint32_t i = t; i < words; i += kBgzfLanes)
         table[i] = 0;
     __syncthreads();
     {
-        const uint32_t start = kDefHeaderBits + before + incl - bits;
+        const uint32_t start = coded_dyn ? kHufHeaderBits + K.header_bits + dyn_before : kDefHeaderBits + before + incl - bits;
         uint32_t w = t ? start >> 5 : 0, fill = t ? start & 31 : kDefHeaderBits;
-        uint64_t acc = t ? 0 : kDefHeader;
+        uint64_t acc = t ? 0 : coded_dyn ? kHufHeader : kDefHeader;
         bool first = true;
-#pragma unroll 1
-        for (uint32_t i = lo; i < hi;) {
-            const uint32_t len = slots[i];
-            const deflate_code k = len ? deflate_token_code(len, slots[i + 1] + 1u) : deflate_token_code(1, from[i]);
-            acc |= k.bits << fill;
-            fill += k.n;
+        auto put = [&](uint64_t code, uint32_t n) { // n <= 32 bits behind the lane's last
+            acc |= code << fill;
+            fill += n;
             if (fill >= 32) {
                 if (first)
                     atomicOr(&table[w], (uint32_t)acc);
@@ -141,8 +204,27 @@ __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_def
                 acc >>= 32;
                 fill -= 32;
             }
+        };
+        if constexpr (Dynamic)
+            if (coded_dyn && t == 0)
+                huff_put_header(K, put);
+#pragma unroll 1
+        for (uint32_t i = lo; i < hi;) {
+            const uint32_t len = slots[i];
+            if (coded_dyn) {
+                deflate_code ka, kb;
+                huff_token_code(K, len ? len : 1, len ? slots[i + 1] + 1u : from[i], ka, kb);
+                put(ka.bits, ka.n);
+                put(kb.bits, kb.n);
+            } else {
+                const deflate_code k = len ? deflate_token_code(len, slots[i + 1] + 1u) : deflate_token_code(1, from[i]);
+                put(k.bits, k.n);
+            }
             i += len ? len : 1;
         }
+        if constexpr (Dynamic)
+            if (coded_dyn && t == kBgzfLanes - 1)
+                put(K.ll[kHufEob] & 0xffff, K.ll[kHufEob] >> 16);
         if (acc)
             atomicOr(&table[w], (uint32_t)acc);
     }
@@ -152,8 +234,10 @@ __global__ __launch_bounds__(kBgzfLanes) void bgzf_deflate_kernel(const bgzf_def
         stage[i] = table[i];
     const uint32_t crc = bgzf_block_crc<false>(from, d, nullptr, P.L, wave_v);
     if (t == 0) {
-        P.size[b] = fixed + kDefMember;
+        P.size[b] = payload + kDefMember;
         P.crc[b] = crc;
+        if (coded_dyn)
+            atomicAdd(&P.counts[kDefCntDynamic], 1ull);
     }
     wave_count_add(&P.counts[kDefCntMatches], n_matches);
     wave_count_add(&P.counts[kDefCntLiterals], n_literals);

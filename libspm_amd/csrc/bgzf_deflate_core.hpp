@@ -4,7 +4,9 @@
 // spm_hip.h, scheme in DESIGN.md 4.12a.  The container (header, BSIZE, CRC32, ISIZE, EOF block) is bgzf_core.hpp's.
 //
 // A block of d data bytes is ONE deflate block with BFINAL 1: fixed Huffman (BTYPE 01) if that is strictly smaller than the
-// stored form (d + 5 bytes), else the stored block of bgzf_core.hpp.
+// stored form (d + 5 bytes), else the stored block of bgzf_core.hpp.  With `dynamic` (SPM_BGZF_DYNAMIC) the same tokens are also
+// sized in the block's own code (BTYPE 10, bgzf_huffman_core.hpp): stored if neither coded form is below d + 5, else the smaller
+// of the two, fixed when they are equal.
 //
 // Chunks.  Lane t of kBgzfLanes owns the positions [t c, min((t + 1) c, d)), c = deflate_chunk(d) = max(64, ceil(d / 256)).  No
 // token crosses a chunk border; a match's source lies anywhere earlier in the block and may overlap its target.
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "bgzf_core.hpp"
+#include "bgzf_huffman_core.hpp" // the RFC's length and distance symbols, deflate_code, the dynamic code
 
 namespace spm_hip
 {
@@ -45,33 +48,7 @@ SPM_HD inline uint32_t deflate_chunk(uint32_t d)
 }
 SPM_HD inline uint32_t deflate_load4(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 SPM_HD inline uint32_t deflate_hash4(uint32_t w) { return (w * 2654435761u) >> (32 - kDefHashBits); }
-SPM_HD inline uint32_t deflate_log2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); } // v >= 1
 
-// ---- the RFC 1951 tables as arithmetic: the symbol of a length or distance, its extra bits and their value ----
-SPM_HD inline void deflate_len_symbol(uint32_t len, uint32_t &sym, uint32_t &ebits, uint32_t &eval) // 3 .. 258
-{
-    const uint32_t l = len - 3;
-    sym = 285, ebits = 0, eval = 0;
-    if (len == kDefMaxMatch)
-        return;
-    if (l < 8) {
-        sym = 257 + l;
-        return;
-    }
-    ebits = deflate_log2(l) - 2;
-    sym = 261 + 4 * ebits + ((l >> ebits) & 3);
-    eval = l & ((1u << ebits) - 1);
-}
-SPM_HD inline void deflate_dist_symbol(uint32_t dist, uint32_t &sym, uint32_t &ebits, uint32_t &eval) // 1 .. 32768
-{
-    const uint32_t dd = dist - 1;
-    sym = dd, ebits = 0, eval = 0;
-    if (dd < 4)
-        return;
-    ebits = deflate_log2(dd) - 1;
-    sym = 2 * ebits + 2 + ((dd >> ebits) & 1);
-    eval = dd & ((1u << ebits) - 1);
-}
 // the fixed code of a literal/length symbol 0 .. 287, as RFC 1951 prints it (first bit on the left), and its length
 SPM_HD inline uint32_t deflate_litlen_code(uint32_t sym, uint32_t &n)
 {
@@ -90,21 +67,10 @@ SPM_HD inline uint32_t deflate_litlen_code(uint32_t sym, uint32_t &n)
     n = 8;
     return 0xC0 + (sym - 280);
 }
-SPM_HD inline uint32_t deflate_reverse(uint32_t code, uint32_t n) // the first bit of a Huffman code goes into the stream first
-{
-    uint32_t r = 0;
-    for (uint32_t i = 0; i < n; ++i, code >>= 1)
-        r = r << 1 | (code & 1);
-    return r;
-}
 
 // ---- a token: len == 1 is the literal v (a byte), len >= 3 a match of that length at distance v.  Its size in bits, and its
-// bits in stream order from bit 0 (at most 31).  A dynamic-Huffman coder replaces this pair and nothing else. ----
-struct deflate_code
-{
-    uint64_t bits;
-    uint32_t n;
-};
+// bits in stream order from bit 0 (at most 31).  The dynamic coder replaces this pair (huff_token_bits, huff_token_code) and
+// nothing else. ----
 SPM_HD inline uint32_t deflate_token_bits(uint32_t len, uint32_t v)
 {
     if (len == 1)
@@ -171,7 +137,8 @@ struct deflate_token
 };
 struct deflate_counts
 {
-    uint64_t n_stored_blocks = 0, n_matches = 0, n_literals = 0; // tokens of the blocks that came out fixed
+    uint64_t n_stored_blocks = 0, n_matches = 0, n_literals = 0; // tokens of the blocks that were not stored
+    uint64_t n_dynamic_blocks = 0;
 };
 
 // far candidates of every position of a block: cand[i] = position + 1 or 0
@@ -211,12 +178,45 @@ inline uint64_t deflate_parse_serial(const uint8_t *p, uint32_t d, std::vector<d
     }
     return bits;
 }
+// The step-5 choice between the three forms: which deflate block type a block of d bytes takes, given its fixed payload's bytes
+// and its dynamic payload's (any value >= d + 5 where there is none).
+SPM_HD inline uint32_t deflate_choose(uint32_t fixed_bytes, uint32_t dynamic_bytes, uint32_t d)
+{
+    if (dynamic_bytes < d + kDefStored && dynamic_bytes < fixed_bytes)
+        return 2;
+    return deflate_takes_fixed(fixed_bytes, d) ? 1 : 0;
+}
+
 // The deflate payload of a block of d >= 1 bytes into out, which has room for d + 5: returns its length.
-inline uint32_t deflate_block_serial(const uint8_t *p, uint32_t d, uint8_t *out, deflate_counts *counts = nullptr)
+inline uint32_t deflate_block_serial(const uint8_t *p, uint32_t d, uint8_t *out, deflate_counts *counts = nullptr, bool dynamic = false)
 {
     std::vector<deflate_token> tokens;
     const uint32_t fixed = deflate_fixed_bytes(deflate_parse_serial(p, d, tokens));
-    if (!deflate_takes_fixed(fixed, d)) {
+    uint64_t n_matches = 0;
+    for (const deflate_token &k : tokens)
+        n_matches += k.len > 1;
+    uint32_t dyn = d + kDefStored;
+    huff_code K;
+    const uint32_t other = fixed < d + kDefStored ? fixed : d + kDefStored;
+    if (dynamic && huff_may_win(tokens.size() - n_matches, n_matches, other)) {
+        std::vector<huff_work> work(1);
+        huff_work &W = work[0];
+        W.count[kHufEob] = 1;
+        for (const deflate_token &k : tokens) {
+            uint32_t ls, ds;
+            huff_count_token(k.len, k.v, ls, ds);
+            ++W.count[ls];
+            if (ds < kHufDist)
+                ++W.count[kHufLitLen + ds];
+        }
+        huff_block_build(W, K, 0, 1, huff_serial{});
+        uint64_t bits = 0;
+        for (const deflate_token &k : tokens)
+            bits += huff_token_bits(K, k.len, k.v);
+        dyn = huff_dynamic_bytes(K, bits);
+    }
+    const uint32_t type = deflate_choose(fixed, dyn, d);
+    if (type == 0) {
         for (uint32_t i = 0; i < kDefStored; ++i)
             out[i] = bgzf_head_byte(d, 18 + i);
         memcpy(out + kDefStored, p, d);
@@ -224,27 +224,43 @@ inline uint32_t deflate_block_serial(const uint8_t *p, uint32_t d, uint8_t *out,
             ++counts->n_stored_blocks;
         return d + kDefStored;
     }
-    memset(out, 0, fixed);
+    const uint32_t m = type == 2 ? dyn : fixed;
+    memset(out, 0, m);
     uint64_t at = 0;
     auto put = [&](uint64_t bits, uint32_t n) {
         for (uint32_t i = 0; i < n; ++i, ++at)
             out[at >> 3] |= (uint8_t)(((bits >> i) & 1) << (at & 7));
     };
+    if (counts) {
+        counts->n_matches += n_matches;
+        counts->n_literals += tokens.size() - n_matches;
+        counts->n_dynamic_blocks += type == 2;
+    }
+    if (type == 2) {
+        put(kHufHeader, kHufHeaderBits);
+        huff_put_header(K, put);
+        for (const deflate_token &k : tokens) {
+            deflate_code a, b;
+            huff_token_code(K, k.len, k.v, a, b);
+            put(a.bits, a.n);
+            put(b.bits, b.n);
+        }
+        put(K.ll[kHufEob] & 0xffff, K.ll[kHufEob] >> 16);
+        return m;
+    }
     put(kDefHeader, kDefHeaderBits);
     for (const deflate_token &k : tokens) {
         const deflate_code code = deflate_token_code(k.len, k.v);
         put(code.bits, code.n);
-        if (counts)
-            ++(k.len == 1 ? counts->n_literals : counts->n_matches);
     }
     put(0, kDefEobBits);
-    return fixed;
+    return m;
 }
 
 // n bytes of src into dst, which has room for bgzf_framed_size bytes: returns the file's length.  offsets (or null) receives
 // the file offset of every data block and, last, the end of the data blocks.
 inline uint64_t bgzf_deflate_serial(const uint8_t *src, uint64_t n, uint32_t D, bool eof, uint8_t *dst, std::vector<uint64_t> *offsets = nullptr,
-                                    deflate_counts *counts = nullptr)
+                                    deflate_counts *counts = nullptr, bool dynamic = false)
 {
     const uint64_t nb = bgzf_n_blocks(n, D);
     uint64_t at = 0;
@@ -256,7 +272,7 @@ inline uint64_t bgzf_deflate_serial(const uint8_t *src, uint64_t n, uint32_t D, 
         uint8_t *to = dst + at;
         if (offsets)
             offsets->push_back(at);
-        const uint32_t m = deflate_block_serial(from, d, to + 18, counts), size = m + kDefMember;
+        const uint32_t m = deflate_block_serial(from, d, to + 18, counts, dynamic), size = m + kDefMember;
         for (uint32_t i = 0; i < 16; ++i)
             to[i] = bgzf_head_byte(d, i);
         to[16] = deflate_bsize_byte(size, 0);

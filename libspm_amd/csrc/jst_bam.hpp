@@ -408,7 +408,7 @@ extern "C" int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts
     if (rc == SPM_OK)
         rc = spm_hip_bgzf_deflate_host(b->plain_header.data(), b->plain_header.size(), &o, header.data(), need, &len);
     if (rc != SPM_OK) {
-        SPM_SET_ERR(ctx, "%s: block_data %u above 65280, flags 0x%x other than SPM_BGZF_EOF, level %u other than 1 or reserved %u", who,
+        SPM_SET_ERR(ctx, "%s: block_data %u above 65280, flags 0x%x other than SPM_BGZF_EOF | SPM_BGZF_DYNAMIC, level %u other than 1 or reserved %u", who,
                     opts->block_data, opts->flags, opts->level, opts->reserved);
         return rc;
     }

@@ -194,10 +194,11 @@ class Context:
                                             C.c_void_p(block_offsets), int(n_blocks), int(block_data), C.byref(z)), self._h)
         return Bai(self, z)
 
-    def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+    def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
-        block; a block that would not shrink stays stored).  The same arguments; the bytes are those of bgzf_deflate_host."""
-        return self._bgzf(capi.lib().spm_hip_bgzf_deflate, bgzf_deflate_opts(block_data, eof), device_ptr, n)
+        block; a block that would not shrink stays stored).  dynamic: a block may take a Huffman code of its own, built on the
+        device (SPM_BGZF_DYNAMIC), where that is smaller.  The bytes are those of bgzf_deflate_host with the same arguments."""
+        return self._bgzf(capi.lib().spm_hip_bgzf_deflate, bgzf_deflate_opts(block_data, eof, dynamic=dynamic), device_ptr, n)
 
     # ---- needles ----
     def patterns(self, algo: int, needles, k=0, sigma: int = 4, both_strands: bool = False) -> "PatternSet":
@@ -963,11 +964,11 @@ class Sam(_Handle):
     def header(self, ref_len: int) -> bytes:
         return sam_header(self.rname, ref_len)
 
-    def _bgzf(self, frame, frame_host, ref_len, block_data, eof) -> "Bgzf":
+    def _bgzf(self, frame, frame_host, ref_len, block_data, eof, **how) -> "Bgzf":
         text, n_bytes, _lines, _n = self.device()
-        z = frame(text, n_bytes, block_data=block_data, eof=eof)
+        z = frame(text, n_bytes, block_data=block_data, eof=eof, **how)
         if ref_len is not None:
-            z.prefix = frame_host(self.header(ref_len), block_data, eof=False)
+            z.prefix = frame_host(self.header(ref_len), block_data, eof=False, **how)
         return z
 
     def bgzf(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
@@ -975,9 +976,9 @@ class Sam(_Handle):
         blocks of its own in front: bytes() is a .sam.gz."""
         return self._bgzf(self.ctx.bgzf, bgzf_frame_host, ref_len, block_data, eof)
 
-    def bgzf_deflate(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+    def bgzf_deflate(self, ref_len: int | None = None, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
         """bgzf() with the blocks compressed (Context.bgzf_deflate); the header's blocks come from the host deflater."""
-        return self._bgzf(self.ctx.bgzf_deflate, bgzf_deflate_host, ref_len, block_data, eof)
+        return self._bgzf(self.ctx.bgzf_deflate, bgzf_deflate_host, ref_len, block_data, eof, dynamic=dynamic)
 
 
 def bam_header(rname, ref_len: int, block_data: int = 0, sorted: bool = False) -> bytes:
@@ -1035,11 +1036,12 @@ class Bam(_Handle):
         first, block = np.uint64(self.stats().header_file_bytes), np.uint64(self.block_data + 31)  # stored blocks, no gaps
         return _voffsets(self.lines()["offset"], self.block_data, lambda i: first + i * block)
 
-    def deflate(self, block_data: int = 0, eof: bool = True) -> "Bgzf":
+    def deflate(self, block_data: int = 0, eof: bool = True, *, dynamic: bool = False) -> "Bgzf":
         """The file with its blocks compressed (spm_hip_bam_deflate): the header section deflated on the host, the record
         stream on the device where it lies, in blocks of block_data uncompressed bytes.  block_offsets() are the record
-        blocks' file offsets; voffsets(self.lines()["offset"]) the records' virtual offsets."""
-        opts = bgzf_deflate_opts(block_data, eof)
+        blocks' file offsets; voffsets(self.lines()["offset"]) the records' virtual offsets.  dynamic: as in
+        Context.bgzf_deflate, for the header's blocks too."""
+        opts = bgzf_deflate_opts(block_data, eof, dynamic=dynamic)
         return Bgzf(self.ctx, self._new("deflate", C.byref(opts)), block_data=_block_data(block_data))
 
     def sort(self) -> "Bam":
@@ -1098,14 +1100,15 @@ def bgzf_frame_host(data, block_data: int = 0, eof: bool = True) -> bytes:
     return _size_then_fill(lambda dst, cap, need: capi.lib().spm_hip_bgzf_frame_host(src, len(data), C.byref(opts), dst, cap, need))
 
 
-def bgzf_deflate_opts(block_data: int = 0, eof: bool = True) -> capi.BgzfDeflateOpts:
-    return capi.BgzfDeflateOpts(block_data=int(block_data), flags=capi.BGZF_EOF if eof else 0, level=1, reserved=0)
+def bgzf_deflate_opts(block_data: int = 0, eof: bool = True, *, dynamic: bool = False) -> capi.BgzfDeflateOpts:
+    flags = (capi.BGZF_EOF if eof else 0) | (capi.BGZF_DYNAMIC if dynamic else 0)
+    return capi.BgzfDeflateOpts(block_data=int(block_data), flags=flags, level=1, reserved=0)
 
 
-def bgzf_deflate_host(data, block_data: int = 0, eof: bool = True) -> bytes:
+def bgzf_deflate_host(data, block_data: int = 0, eof: bool = True, *, dynamic: bool = False) -> bytes:
     """The bytes of Context.bgzf_deflate by the serial host deflater (spm_hip_bgzf_deflate_host).  Needs no device."""
     data = bytes(data)
-    opts = bgzf_deflate_opts(block_data, eof)
+    opts = bgzf_deflate_opts(block_data, eof, dynamic=dynamic)
     cap = C.c_uint64()
     _check(capi.lib().spm_hip_bgzf_deflate_bound(len(data), C.byref(opts), C.byref(cap)), None)
     src = C.create_string_buffer(data, len(data) + 1)
@@ -1141,6 +1144,12 @@ class Bgzf(_Handle):
 
     def deflate_stats(self) -> capi.BgzfDeflateStats:
         return self._stats(capi.BgzfDeflateStats, "deflate_stats")
+
+    def block_types(self) -> tuple:
+        """(stored, fixed, dynamic): how many data blocks of the device part took each form (spm_hip_bgzf_block_types)"""
+        n = (C.c_uint64 * 3)()
+        self._call("block_types", n)
+        return int(n[0]), int(n[1]), int(n[2])
 
     def bytes(self) -> bytes:
         p, n = self._span("view")

@@ -10,8 +10,12 @@ synthetic records.  Every time is the MEDIAN of --runs calls behind one warm-up 
 return the same bytes, that gzip reads the deflated file back as the stored one, and (up to 25 MB) that the bytes are the host
 deflater's.  The row runs in a child process of its own under a time limit.
 
+--dynamic adds, per row and in the same loop of the same run, the call with SPM_BGZF_DYNAMIC: its file bytes, its three block-type
+counts and its stage times beside those without the flag ("dynamic": {...}); and one more BAM row, "qualities", whose records
+carry Phred-like base qualities (values 2 .. 41, skewed) where the other rows have the ff fill.
+
     python scripts/bench_bgzf_deflate.py [--pan-log2 27] [--pan-reads 100000] [--runs 5] [--min-tlen 200] [--max-tlen 600]
-                                         [--k 12] [--row-timeout 900] [--out profiles/r17/bgzf_deflate.jsonl]
+                                         [--k 12] [--row-timeout 900] [--dynamic] [--out profiles/r17/bgzf_deflate.jsonl]
 """
 import argparse
 import ctypes
@@ -49,9 +53,10 @@ def zlib1_size(data, D=65280):
     return total
 
 
-def compare(ctx, ptr, n, runs, deflate, stored_bytes=None, check=None):
-    """deflate() and the frame kernel over the same n bytes at ptr -> the figures of one row"""
+def compare(ctx, ptr, n, runs, deflate, stored_bytes=None, check=None, dynamic=None):
+    """deflate() and the frame kernel over the same n bytes at ptr -> the figures of one row.  dynamic: the same call with the flag"""
     st = {s: [] for s in STAGES}
+    dyn_st, dyn_first, dyn_types = {s: [] for s in STAGES}, None, None
     call, down, frame, frame_call, frame_down = [], [], [], [], []
     first, counts = None, {}
     for i in range(runs + 1):
@@ -68,6 +73,16 @@ def compare(ctx, ptr, n, runs, deflate, stored_bytes=None, check=None):
         assert raw == first, "two calls returned different bytes"
         counts = {c: int(getattr(ds, c)) for c in COUNTS}
         z.close()
+        if dynamic is not None:
+            z = dynamic()
+            ds = z.deflate_stats()
+            for s in STAGES:
+                dyn_st[s].append(getattr(ds, s))
+            dyn_types = z.block_types()
+            if dyn_first is None:
+                dyn_first = z.bytes()
+                assert gzip.decompress(dyn_first) == gzip.decompress(raw), "the flagged file inflates to other bytes"
+            z.close()
         t0 = time.perf_counter()
         f = ctx.bgzf(ptr, n)
         frame_call.append((time.perf_counter() - t0) * 1e3)
@@ -87,10 +102,13 @@ def compare(ctx, ptr, n, runs, deflate, stored_bytes=None, check=None):
     out["ms_frame_plus_download_host"] = round(out["ms_frame_call_host"] + out["ms_download_stored"], 3)
     out["claim_holds"] = out["ms_deflate_plus_download_host"] < out["ms_frame_plus_download_host"]
     out["deflate_gb_per_s"] = round(n / max(ms_device, 1e-6) / 1e6, 3)
+    if dynamic is not None:
+        out["dynamic"] = {"file_bytes": len(dyn_first), "n_stored": dyn_types[0], "n_fixed": dyn_types[1], "n_dynamic": dyn_types[2],
+                          **{s: med(v[1:]) for s, v in dyn_st.items()}}
     return out
 
 
-def raw_rows(ctx, runs):
+def raw_rows(ctx, runs, dynamic=False):
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
     hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
@@ -113,7 +131,8 @@ def raw_rows(ctx, runs):
             if n <= 25_000_000:
                 assert raw == S.bgzf_deflate_host(data)
 
-        r = compare(ctx, p.value, n, runs, lambda: ctx.bgzf_deflate(p.value, n), check=check)
+        r = compare(ctx, p.value, n, runs, lambda: ctx.bgzf_deflate(p.value, n), check=check,
+                    dynamic=(lambda: ctx.bgzf_deflate(p.value, n, dynamic=True)) if dynamic else None)
         r.update({"kind": kind, "bytes": n, "zlib_level1_file_bytes": zlib1_size(data) + 28})
         out.append(r)
     ctx.synchronize()
@@ -121,7 +140,7 @@ def raw_rows(ctx, runs):
     return out
 
 
-def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
+def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k, dynamic=False):
     ctx = S.Context(0)
     ref, jst, ps, reads, out = build(ctx, pan_log2, pan_reads)
     h = jst.search_device(ps, max_hits=1 << 26)
@@ -136,8 +155,13 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
     ref_len = len(ref)
     out.update({"loci": len(lc), "ref_len": ref_len})
     names = [f"pair.{p}/frag" for p in range(len(reads) // 2)]
-    for label, kw in (("plain", {}), ("cigar_m_secondary_names", {"cigar_m": True, "secondary": True, "names": names})):
-        b = lc.bam(rd, ps, "pan_ref", ref_len, pairs=pairs, rescues=rs, **kw)
+    rows = [("plain", {}), ("cigar_m_secondary_names", {"cigar_m": True, "secondary": True, "names": names})]
+    if dynamic:
+        read_len = len(reads[0])
+        qual = 41 - np.minimum(np.random.default_rng(21).geometric(0.25, (len(reads), read_len)) - 1, 39)
+        rows.append(("qualities", {"qualities": qual.astype(np.uint8)}))
+    for label, kw in rows:
+        b = lc.bam_ex(rd, ps, "pan_ref", ref_len, pairs=pairs, rescues=rs, **kw)
         stored_file = b.bytes()
         stream = b.records()
         d_rec, n_rec = b.device()[2:4]
@@ -145,14 +169,15 @@ def row(pan_log2, pan_reads, runs, min_tlen, max_tlen, k):
         def check(raw, _stored, stored_file=stored_file):
             assert gzip.decompress(raw) == gzip.decompress(stored_file)
 
-        r = compare(ctx, d_rec, n_rec, runs, b.deflate, stored_bytes=len(stored_file), check=check)
+        r = compare(ctx, d_rec, n_rec, runs, b.deflate, stored_bytes=len(stored_file), check=check,
+                    dynamic=(lambda b=b: b.deflate(dynamic=True)) if dynamic else None)
         r.update({"n_records": int(b.stats().n_records), "n_record_bytes": n_rec, "zlib_level1_file_bytes":
                   zlib1_size(gzip.decompress(S.bam_header("pan_ref", ref_len))) + zlib1_size(stream) + 28})
         out[label] = r
         b.close()
     for x in (rs, pairs, rd, lc, nz, pr, a, sel, h, ps, jst, ref):
         x.close()
-    out["raw_buffers"] = raw_rows(ctx, runs)
+    out["raw_buffers"] = raw_rows(ctx, runs, dynamic)
     return out
 
 
@@ -165,16 +190,17 @@ def main():
     ap.add_argument("--max-tlen", type=int, default=600)
     ap.add_argument("--k", type=int, default=12)
     ap.add_argument("--row-timeout", type=int, default=900, help="seconds the row's child process may take")
+    ap.add_argument("--dynamic", action="store_true", help="also time every call with SPM_BGZF_DYNAMIC, and a row with base qualities")
     ap.add_argument("--out", default=None, help="also write the line to this file")
     ap.add_argument("--row", action="store_true", help=argparse.SUPPRESS)   # the child's mode: the row's JSON on stdout
     a = ap.parse_args()
     if a.runs < 5:
         ap.error("--runs: a median of at least 5 runs")
     if a.row:
-        print(json.dumps(row(a.pan_log2, a.pan_reads, a.runs, a.min_tlen, a.max_tlen, a.k)))
+        print(json.dumps(row(a.pan_log2, a.pan_reads, a.runs, a.min_tlen, a.max_tlen, a.k, a.dynamic)))
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--row", "--pan-log2", str(a.pan_log2), "--pan-reads", str(a.pan_reads),
-           "--runs", str(a.runs), "--min-tlen", str(a.min_tlen), "--max-tlen", str(a.max_tlen), "--k", str(a.k)]
+           "--runs", str(a.runs), "--min-tlen", str(a.min_tlen), "--max-tlen", str(a.max_tlen), "--k", str(a.k)] + (["--dynamic"] if a.dynamic else [])
     r = subprocess.run(["timeout", "-k", "10", str(a.row_timeout)] + cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
