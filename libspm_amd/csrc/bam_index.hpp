@@ -1,6 +1,7 @@
 // bam_index.hpp -- a BAM handle in coordinate order, and the BAI index of a sorted one (spm_hip_bam_sort, spm_hip_bam_index,
-// spm_hip_bai_build; contract in spm_hip.h, scheme in DESIGN.md 4.12b, the rule in bam_index_core.hpp).  gfx950.  Included by
-// bgzf.hip, behind the containers it reads.
+// spm_hip_bai_build; contract in spm_hip.h, scheme in DESIGN.md 4.12b, the rule in bam_index_core.hpp).  gfx950.  Unit:
+// bam_index.hip.  It reads the handles of output_handles.hpp; of the other units it calls bam_plain_header, bgzf_frame_enqueue and
+// bgzf_offsets_ready (internal.hpp).
 //   bam_sort_keys_kernel    one lane per record: its key fields out of the stream, the packed key; a record that cannot be read
 //                           is counted;
 //   bam_sort_place_kernel   one lane per record of the new order: its line record with the new offset;
@@ -18,23 +19,13 @@
 //   bai_write_bins_kernel, bai_write_rest_kernel   the bytes.
 #pragma once
 
-#include <string>
+#include <hip/hip_runtime.h>
 
+#include "internal.hpp"
 #include "bam_index_core.hpp"
 #include "device_order.hpp"
-#include "jst_handles.hpp"
+#include "output_handles.hpp"
 #include "wave.hpp"
-
-struct spm_bai
-{
-    spm_ctx *ctx = nullptr;
-    uint8_t *d = nullptr;
-    uint64_t n = 0;
-    bool have_host = false; // the view is downloaded when first asked for
-    std::vector<uint8_t> host;
-    spm_bai_stats stats{};
-};
-static_assert(sizeof(spm_bam_sort_opts) == 8 && sizeof(spm_bam_sort_stats) == 48 && sizeof(spm_bai_stats) == 80, "spm_hip.h states these sizes");
 
 namespace spm_hip
 {
@@ -350,27 +341,16 @@ extern "C" int spm_hip_bam_sort(spm_bam *b, const spm_bam_sort_opts *opts, spm_b
         SPM_SET_ERR(ctx, "%s: %llu records are more than 2^32 - 1 (not supported)", who, (unsigned long long)b->n_lines);
         return SPM_E_UNSUPPORTED;
     }
-    std::vector<uint8_t> plain, header;
-    SPM_TRY(bam_plain_header(who, ctx, b->rname.c_str(), b->ref_len, true, plain));
     const uint32_t D = b->block_data;
-    header.resize(bgzf_framed_size(plain.size(), D, false));
-    bgzf_frame_serial(plain.data(), plain.size(), D, false, header.data());
-    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<spm_bam, void (*)(spm_bam *)> R(new spm_bam, spm_hip_bam_destroy);
-    R->ctx = ctx;
-    R->rname = b->rname;
-    R->ref_len = b->ref_len;
-    R->block_data = D;
-    R->sorted = true;
-    R->plain_header = plain;
-    hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)b->n_lines;
     const uint64_t n_bytes = b->n_record_bytes;
-    R->n_lines = n;
-    R->n_record_bytes = n_bytes;
-    R->n_file = header.size() + bgzf_framed_size(n_bytes, D, true);
-    SPM_HIP_CHECK(ctx, hipMalloc(&R->d_file, R->n_file));
-    SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->d_file, header.data(), header.size(), hipMemcpyHostToDevice, st));
+    bam_file file;
+    bam_ptr R(nullptr, spm_hip_bam_destroy);
+    SPM_TRY(file.open(who, ctx, b->rname.c_str(), b->ref_len, D, true, R));
+    SPM_TRY(file.place(R.get(), n, n_bytes));
+    R->stats = b->stats; // the counts are the source's; the sizes and times are this file's
+    R->stats.ms_lines = R->stats.ms_measure = R->stats.ms_write = R->stats.ms_stats = 0;
+    hipStream_t st = ctx->stream;
     hip_events<6> ev;
     SPM_HIP_CHECK(ctx, ev.create());
     dev_scratch keep;
@@ -419,8 +399,8 @@ extern "C" int spm_hip_bam_sort(spm_bam *b, const spm_bam_sort_opts *opts, spm_b
             SPM_HIP_CHECK(ctx, hipEventRecord(ev[i], st));
     }
     SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
-    // ---- frame: the record stream behind the new header section, then EOF ----
-    SPM_HIP_CHECK(ctx, bgzf_frame_enqueue(ctx, R->d_records, n_bytes, D, true, R->d_file + header.size()));
+    // ---- frame ----
+    SPM_TRY(file.frame(R.get()));
     SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
     SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSortCnts)); // the one read-back: the error counter and the total
     const unsigned long long *c = ctx->h_counters;
@@ -441,15 +421,9 @@ extern "C" int spm_hip_bam_sort(spm_bam *b, const spm_bam_sort_opts *opts, spm_b
     S.key_bits = key_bits;
     S.n_records = n;
     S.n_record_bytes = n_bytes;
-    R->stats = b->stats; // the counts are the source's; the sizes and times are this file's
-    R->stats.ms_lines = R->stats.ms_measure = R->stats.ms_write = R->stats.ms_stats = 0;
     R->stats.ms_frame = S.ms_frame;
     R->stats.ms_total = S.ms_total;
     R->stats.ms_host = S.ms_host;
-    R->stats.header_file_bytes = header.size();
-    R->stats.n_file_bytes = R->n_file;
-    R->stats.n_record_bytes = n_bytes;
-    R->stats.n_record_blocks = bgzf_n_blocks(n_bytes, D);
     if (spm_trace_on())
         fprintf(stderr, "[spm_hip] bam sort: %u records, %llu bytes, %u key bits: device %.3f ms (keys %.3f, sort %.3f, place %.3f, gather "
                         "%.3f, frame %.3f), %.3f ms in all\n", n, (unsigned long long)n_bytes, key_bits, S.ms_total, S.ms_keys, S.ms_sort,
@@ -460,10 +434,7 @@ extern "C" int spm_hip_bam_sort(spm_bam *b, const spm_bam_sort_opts *opts, spm_b
 
 extern "C" int spm_hip_bam_sort_stats(const spm_bam *b, spm_bam_sort_stats *out)
 {
-    if (!b || !out || !b->sorted)
-        return SPM_E_INVALID;
-    *out = b->sort_stats;
-    return SPM_OK;
+    return stats_out(b && b->sorted ? &b->sort_stats : nullptr, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -471,12 +442,8 @@ extern "C" int spm_hip_bam_sort_stats(const spm_bam *b, spm_bam_sort_stats *out)
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" void spm_hip_bai_destroy(spm_bai *z)
 {
-    if (!z)
-        return;
-    if (z->ctx && z->d)
-        hipStreamSynchronize(z->ctx->stream);
-    hipFree(z->d);
-    delete z;
+    if (z)
+        handle_destroy(z, {z->d});
 }
 
 // the stages on the context's stream; B.table is a device pointer or null.  The inputs have passed the host's checks.
@@ -694,18 +661,9 @@ extern "C" int spm_hip_bai_view(spm_bai *z, const void **bytes, uint64_t *n)
 {
     if (!z)
         return SPM_E_INVALID;
-    if (!z->have_host && z->n) {
-        spm_ctx *ctx = z->ctx;
-        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        z->host.resize(z->n);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(z->host.data(), z->d, z->n, hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    z->have_host = true;
-    if (bytes)
-        *bytes = z->host.data();
-    if (n)
-        *n = z->n;
+    SPM_TRY(handle_download(z->ctx, z->have_host, view_part{z->d, z->n, z->host}));
+    out_if(bytes, z->host.data());
+    out_if(n, z->n);
     return SPM_OK;
 }
 
@@ -713,17 +671,9 @@ extern "C" int spm_hip_bai_device(spm_bai *z, const void **bytes, uint64_t *n)
 {
     if (!z)
         return SPM_E_INVALID;
-    if (bytes)
-        *bytes = z->d;
-    if (n)
-        *n = z->n;
+    out_if(bytes, z->d);
+    out_if(n, z->n);
     return SPM_OK;
 }
 
-extern "C" int spm_hip_bai_stats(const spm_bai *z, spm_bai_stats *out)
-{
-    if (!z || !out)
-        return SPM_E_INVALID;
-    *out = z->stats;
-    return SPM_OK;
-}
+extern "C" int spm_hip_bai_stats(const spm_bai *z, spm_bai_stats *out) { return stats_out(z ? &z->stats : nullptr, out); }

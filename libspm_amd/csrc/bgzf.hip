@@ -2,8 +2,7 @@
 // kernel), its view / device / stats / destroy, and the two host-only calls over the serial framer of bgzf_core.hpp,
 // spm_hip_bgzf_frame_host and spm_hip_bgzf_framed_size; spm_hip_bgzf_deflate (bgzf_deflate.hpp has the kernels), the stages
 // behind it for spm_hip_bam_deflate, the blocks' offsets of either kind of handle, and the host-only calls over the serial
-// deflater of bgzf_deflate_core.hpp.  Behind them bam_index.hpp: spm_hip_bam_sort, spm_hip_bam_index and the calls around them, which
-// read both kinds of handle.
+// deflater of bgzf_deflate_core.hpp; spm_hip_bam_deflate, the deflated file of a BAM handle (output_handles.hpp).
 #include "internal.hpp"
 #include "bgzf.hpp"
 #include "bgzf_deflate.hpp"
@@ -27,13 +26,8 @@ hipError_t bgzf_frame_enqueue(spm_ctx *ctx, const void *d_src, uint64_t n, uint3
 
 extern "C" void spm_hip_bgzf_destroy(spm_bgzf *z)
 {
-    if (!z)
-        return;
-    if (z->ctx && z->d)
-        hipStreamSynchronize(z->ctx->stream);
-    hipFree(z->d);
-    hipFree(z->d_offsets_alloc);
-    delete z;
+    if (z)
+        handle_destroy(z, {z->d, z->d_offsets_alloc});
 }
 
 extern "C" int spm_hip_bgzf_framed_size(uint64_t n, const spm_bgzf_opts *opts, uint64_t *len)
@@ -99,10 +93,7 @@ extern "C" int spm_hip_bgzf_frame(spm_ctx *ctx, const void *device_src, uint64_t
     const uint32_t D = bgzf_block_data(opts->block_data);
     const bool eof = (opts->flags & SPM_BGZF_EOF) != 0;
     const uint64_t n_blocks = bgzf_n_blocks(n, D);
-    if (n_blocks > kBgzfMaxBlocks) {
-        SPM_SET_ERR(ctx, "%s: %llu bytes in blocks of %u are more than 2^31 - 2 blocks (not supported)", who, (unsigned long long)n, D);
-        return SPM_E_UNSUPPORTED;
-    }
+    SPM_TRY(bgzf_check_n_blocks(who, ctx, n, D, "bytes"));
     std::unique_ptr<spm_bgzf, void (*)(spm_bgzf *)> Z(new spm_bgzf, spm_hip_bgzf_destroy);
     Z->ctx = ctx;
     Z->n = bgzf_framed_size(n, D, eof);
@@ -139,18 +130,9 @@ extern "C" int spm_hip_bgzf_view(spm_bgzf *z, const void **bytes, uint64_t *n)
 {
     if (!z)
         return SPM_E_INVALID;
-    if (!z->have_host && z->n) {
-        spm_ctx *ctx = z->ctx;
-        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        z->host.resize(z->n);
-        SPM_HIP_CHECK(ctx, hipMemcpyAsync(z->host.data(), z->d, z->n, hipMemcpyDeviceToHost, ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    z->have_host = true;
-    if (bytes)
-        *bytes = z->host.data();
-    if (n)
-        *n = z->n;
+    SPM_TRY(handle_download(z->ctx, z->have_host, view_part{z->d, z->n, z->host}));
+    out_if(bytes, z->host.data());
+    out_if(n, z->n);
     return SPM_OK;
 }
 
@@ -158,20 +140,12 @@ extern "C" int spm_hip_bgzf_device(spm_bgzf *z, const void **bytes, uint64_t *n)
 {
     if (!z)
         return SPM_E_INVALID;
-    if (bytes)
-        *bytes = z->d;
-    if (n)
-        *n = z->n;
+    out_if(bytes, z->d);
+    out_if(n, z->n);
     return SPM_OK;
 }
 
-extern "C" int spm_hip_bgzf_stats(const spm_bgzf *z, spm_bgzf_stats *out)
-{
-    if (!z || !out)
-        return SPM_E_INVALID;
-    *out = z->stats;
-    return SPM_OK;
-}
+extern "C" int spm_hip_bgzf_stats(const spm_bgzf *z, spm_bgzf_stats *out) { return stats_out(z ? &z->stats : nullptr, out); }
 
 // ---- deflated blocks (bgzf_deflate.hpp, bgzf_deflate_core.hpp) ----
 static int deflate_check_opts(const char *who, spm_ctx *ctx, const spm_bgzf_deflate_opts *o)
@@ -226,10 +200,7 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
     const uint32_t D = bgzf_block_data(opts->block_data);
     const bool eof = (opts->flags & SPM_BGZF_EOF) != 0, dynamic = (opts->flags & SPM_BGZF_DYNAMIC) != 0;
     const uint64_t n_blocks = bgzf_n_blocks(n, D);
-    if (n_blocks > kBgzfMaxBlocks) {
-        SPM_SET_ERR(ctx, "%s: %llu bytes in blocks of %u are more than 2^31 - 2 blocks (not supported)", who, (unsigned long long)n, D);
-        return SPM_E_UNSUPPORTED;
-    }
+    SPM_TRY(bgzf_check_n_blocks(who, ctx, n, D, "bytes"));
     std::unique_ptr<spm_bgzf, void (*)(spm_bgzf *)> Z(new spm_bgzf, spm_hip_bgzf_destroy);
     Z->ctx = ctx;
     Z->D = D;
@@ -330,8 +301,29 @@ extern "C" int spm_hip_bgzf_deflate(spm_ctx *ctx, const void *device_src, uint64
     return bgzf_deflate_run(who, ctx, device_src, n, opts, std::vector<uint8_t>(), out);
 }
 
-// the offsets of a framed handle are the closed form: made, and uploaded, when first asked for
-static int bgzf_offsets_ready(spm_bgzf *z, bool on_device)
+// The whole BAM file deflated: the header section by the host deflater, without an EOF block, the record stream behind it.
+extern "C" int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out)
+{
+    static const char *const who = "spm_hip_bam_deflate";
+    if (out)
+        *out = nullptr;
+    if (!b)
+        return SPM_E_INVALID;
+    spm_ctx *ctx = b->ctx;
+    if (!opts || !out) {
+        SPM_SET_ERR(ctx, "%s: NULL %s", who, !opts ? "opts" : "out");
+        return SPM_E_INVALID;
+    }
+    SPM_TRY(deflate_check_opts(who, ctx, opts));
+    const uint32_t D = bgzf_block_data(opts->block_data);
+    std::vector<uint8_t> header(bgzf_framed_size(b->plain_header.size(), D, false)); // (a bound: a block never grows past stored)
+    header.resize(bgzf_deflate_serial(b->plain_header.data(), b->plain_header.size(), D, false, header.data(), nullptr, nullptr,
+                                      (opts->flags & SPM_BGZF_DYNAMIC) != 0));
+    return bgzf_deflate_run(who, ctx, b->d_records, b->n_record_bytes, opts, header, out);
+}
+
+// the offsets of a framed handle are the closed form: made, and uploaded, when first asked for (spm_hip_bam_index asks too)
+int bgzf_offsets_ready(spm_bgzf *z, bool on_device)
 {
     spm_ctx *ctx = z->ctx;
     const uint64_t n_offsets = z->stats.n_blocks + 1;
@@ -363,10 +355,8 @@ extern "C" int spm_hip_bgzf_blocks(spm_bgzf *z, const uint64_t **offsets, uint64
     if (!z)
         return SPM_E_INVALID;
     SPM_TRY(bgzf_offsets_ready(z, false));
-    if (offsets)
-        *offsets = z->host_offsets.data();
-    if (n_blocks)
-        *n_blocks = z->stats.n_blocks;
+    out_if(offsets, z->host_offsets.data());
+    out_if(n_blocks, z->stats.n_blocks);
     return SPM_OK;
 }
 
@@ -375,19 +365,14 @@ extern "C" int spm_hip_bgzf_blocks_device(spm_bgzf *z, const void **offsets, uin
     if (!z)
         return SPM_E_INVALID;
     SPM_TRY(bgzf_offsets_ready(z, true));
-    if (offsets)
-        *offsets = z->d_offsets;
-    if (n_blocks)
-        *n_blocks = z->stats.n_blocks;
+    out_if(offsets, z->d_offsets);
+    out_if(n_blocks, z->stats.n_blocks);
     return SPM_OK;
 }
 
 extern "C" int spm_hip_bgzf_deflate_stats(const spm_bgzf *z, spm_bgzf_deflate_stats *out)
 {
-    if (!z || !out)
-        return SPM_E_INVALID;
-    *out = z->deflate;
-    return SPM_OK;
+    return stats_out(z ? &z->deflate : nullptr, out);
 }
 
 extern "C" int spm_hip_bgzf_block_types(const spm_bgzf *z, uint64_t n[3])
@@ -400,9 +385,6 @@ extern "C" int spm_hip_bgzf_block_types(const spm_bgzf *z, uint64_t n[3])
     return SPM_OK;
 }
 
-// ---- a BAM handle in coordinate order and the BAI index of one: they read the handles above ----
-#include "bam_index.hpp"
-
 void spm_warm_bgzf_kernels()
 {
     hipFuncAttributes a;
@@ -410,6 +392,4 @@ void spm_warm_bgzf_kernels()
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel<false>);
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_deflate_kernel<true>);
     (void)hipFuncGetAttributes(&a, (const void *)bgzf_place_kernel);
-    (void)hipFuncGetAttributes(&a, (const void *)bam_gather_kernel);
-    (void)hipFuncGetAttributes(&a, (const void *)bai_records_kernel);
 }

@@ -1,5 +1,5 @@
 // bgzf.hpp -- BGZF framing of a device buffer (spm_hip_bgzf_frame; contract in spm_hip.h, scheme in DESIGN.md 4.12, geometry
-// and CRC arithmetic in bgzf_core.hpp).  gfx950.  Included by bgzf.hip.
+// and CRC arithmetic in bgzf_core.hpp).  gfx950.  Unit: bgzf.hip.  The handle, spm_bgzf, is output_handles.hpp's.
 //   bgzf_frame_kernel   one workgroup of 256 lanes per block, one pass: lane t takes bgzf_lane_range of the block's data, a
 //                       contiguous chunk whose pieces are 16-byte aligned IN THE SOURCE (dwordx4 loads at any source
 //                       alignment; the bytes in front of the first border go one by one, the fewer than 16 behind the last
@@ -21,6 +21,7 @@
 #include "bgzf_core.hpp"
 #include "common.hpp"
 #include "device_order.hpp"
+#include "output_handles.hpp"
 
 namespace spm_hip
 {
@@ -166,24 +167,3 @@ inline int bgzf_check_opts(const spm_bgzf_opts &o, const char *&why)
 }
 
 } // namespace spm_hip
-
-struct spm_bgzf
-{
-    spm_ctx *ctx = nullptr;
-    uint8_t *d = nullptr;
-    uint64_t n = 0;
-    bool have_host = false; // the view is downloaded when first asked for
-    std::vector<uint8_t> host;
-    spm_bgzf_stats stats{};
-    // the blocks' file offsets (spm_hip_bgzf_blocks): n_blocks + 1 of them.  A deflated handle has them on the device from the
-    // call on (inside d_offsets_alloc); a framed one makes them from the closed form when first asked for
-    uint32_t D = spm_hip::kBgzfBlockData;
-    void *d_offsets_alloc = nullptr;
-    unsigned long long *d_offsets = nullptr;
-    bool have_host_offsets = false;
-    std::vector<uint64_t> host_offsets;
-    spm_bgzf_deflate_stats deflate{};
-    uint64_t n_dynamic_blocks = 0; // spm_hip_bgzf_block_types: of the blocks that are not stored, those with a code of their own
-};
-static_assert(sizeof(spm_bgzf_opts) == 16 && sizeof(spm_bgzf_stats) == 32, "spm_hip.h states these sizes");
-static_assert(sizeof(spm_bgzf_deflate_opts) == 16 && sizeof(spm_bgzf_deflate_stats) == 72, "spm_hip.h states these sizes");

@@ -1,5 +1,5 @@
 // bgzf_deflate.hpp -- BGZF blocks deflated on the device (spm_hip_bgzf_deflate; contract in spm_hip.h, scheme in DESIGN.md
-// 4.12a, the token rule and the fixed-Huffman code in bgzf_deflate_core.hpp).  gfx950.  Included by bgzf.hip behind bgzf.hpp.
+// 4.12a, the token rule and the fixed-Huffman code in bgzf_deflate_core.hpp).  gfx950.  Unit: bgzf.hip, with bgzf.hpp.
 //   bgzf_deflate_kernel   one workgroup of 256 lanes per block.  (1) Far candidates: ceil(d / 256) rounds over a table of 2^14
 //                         words in LDS (64 KiB: two workgroups per CU); in a round lane t looks up position 256 r + t, and behind
 //                         a barrier inserts it with an LDS atomicMax, so the table is "largest position per hash" whatever the

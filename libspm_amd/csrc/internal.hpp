@@ -4,7 +4,8 @@
 // filter_verify.hip (filter_launch.hpp); hits.hip: results; align.hip: alignments of hits; select.hip: selection of hits;
 // device_order.hip: the pair sort of the drivers that order records (device_order.hpp); jst.hip: journaled sequences, with
 // jst_align.hip, jst_ref.hip, jst_reads.hip and jst_sam.hip behind it (map in jst.hpp) and jst_select.hip beside it;
-// bgzf.hip: BGZF framing and deflate, and behind them the sorted BAM and its BAI index; comm.hip: the multi-GPU exchange.)
+// bgzf.hip: BGZF framing and deflate; bam_index.hip: the sorted BAM and its BAI index (the handles of both and of jst_sam.hip:
+// output_handles.hpp); comm.hip: the multi-GPU exchange.)
 #pragma once
 
 #include <algorithm>
@@ -228,6 +229,7 @@ void spm_warm_jst_align_kernels();
 void spm_warm_jst_ref_kernels();
 void spm_warm_jst_reads_kernels();
 void spm_warm_jst_sam_kernels();
+void spm_warm_bam_index_kernels();
 void spm_warm_device_order_kernels(spm_ctx *ctx); // (hipcub's kernels have no name to ask for: it sorts one pair in ctx's scratch)
 #pragma GCC visibility pop
 
@@ -240,9 +242,11 @@ int bgzf_deflate_run(const char *who, spm_ctx *ctx, const void *d_src, uint64_t 
                      const std::vector<uint8_t> &prefix, spm_bgzf **out);
 
 // ---- the header section of a BAM file before its framing (jst_bam.hpp), for the call that writes one and for spm_hip_bam_sort
-// (bam_index.hpp), which writes it again with SO:coordinate ----
+// (bam_index.hpp), which writes it again with SO:coordinate; the blocks' offsets of a spm_bgzf handle made ready on the host
+// and, with on_device, on the device (bgzf.hip), for spm_hip_bam_index over a deflated file ----
 #pragma GCC visibility push(hidden)
 int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t ref_len, bool sorted, std::vector<uint8_t> &h);
+int bgzf_offsets_ready(spm_bgzf *z, bool on_device);
 #pragma GCC visibility pop
 
 // deferred scans (SPM_SCAN_DEFER): read the counters back, and repeat the scan if it needs attention   (scan.hip)

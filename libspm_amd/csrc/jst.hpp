@@ -35,7 +35,7 @@
 //   jst_sam.hip     output (BAM reuses the SAM front and kernels)
 //     jst_sam.hpp, jst_bam.hpp
 // and under all of them
-//   jst_handles.hpp     the tree and every stage's result handle
+//   jst_handles.hpp     the tree and every stage's result handle (spm_sam and spm_bam: output_handles.hpp)
 //   jst_walk_core.hpp   what a cell owns and what its context spells (steps 1-3 and the spelling of 4), host and device alike
 //   jst_ctx_tables.hpp  the context tables of the index as one set
 //   jst_fanout.hpp      the walk of step 4's fan-out, shared by the kernel for hits and the kernel for alignments

@@ -1,6 +1,7 @@
 // jst_bam.hpp -- BAM records in BGZF blocks (spm_hip_jst_ref_loci_bam; contract in spm_hip.h, scheme in DESIGN.md 4.12, the
 // composition in jst_bam_core.hpp).  gfx950.  Unit: jst_sam.hip, with jst_sam.hpp, whose front (the host's refusals, the lines
-// stage) and stats kernel it uses; it enqueues the frame stage of bgzf.hip (internal.hpp).
+// stage), measured and closed steps, stats kernel and wave sink base it uses; the file around its record stream is bam_file's
+// (output_handles.hpp), which enqueues the frame stage of bgzf.hip (internal.hpp).
 //   jst_bam_measure_kernel   one lane per record: resolved against its sources with the query length checked, its shape (item
 //                            count, bin; what a record cannot hold is counted as a disagreement), its length by the measuring
 //                            sink;
@@ -54,30 +55,14 @@ __global__ __launch_bounds__(256) void jst_bam_measure_kernel(const jst_bam_para
     wave_count_add(&P.counts[kSamCntBytes], (unsigned long long)n);
 }
 
-// The wave sink: byte i of a field to lane i.  cur is wave-uniform.  No store lands outside [cur at construction, end): the
-// record's own bytes.
-struct jst_bam_wave_sink
+// The wave sink: the composition of one record, over what it shares with the text's (jst_wave_sink_base).
+struct jst_bam_wave_sink : jst_wave_sink_base<uint8_t>
 {
-    uint8_t *to;
-    uint64_t cur, end;
-    uint32_t lane;
-
-    __device__ __forceinline__ void store(uint64_t at, uint8_t c)
-    {
-        if (at < end)
-            to[at] = c;
-    }
     __device__ __forceinline__ void fixed(const uint32_t *w)
     {
         if (lane < kBamFixed)
             store(cur + lane, jst_bam_le_byte(w[lane >> 2], lane & 3));
         cur += kBamFixed;
-    }
-    __device__ __forceinline__ void bytes(const char *p, uint64_t n)
-    {
-        for (uint64_t i = lane; i < n; i += kWave)
-            store(cur + i, (uint8_t)p[i]);
-        cur += n;
     }
     __device__ __forceinline__ void num(uint64_t v) // at most 20 digits
     {
@@ -116,24 +101,12 @@ struct jst_bam_wave_sink
             store(cur + lane, jst_bam_tag_byte(head, v, lane));
         cur += kBamTag;
     }
-    __device__ __forceinline__ void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
-    {
-        for (uint32_t i = lane; i < jst_sam_qual_len(m); i += kWave)
-            store(cur + i, jst_sam_qual_byte(values, m, reverse, add, i));
-        cur += jst_sam_qual_len(m);
-    }
     // MD Z, the text sink's string by the same walk, NUL
     __device__ __forceinline__ void md(const uint32_t *words, uint32_t n, const uint8_t *ref, const char *symbols, uint32_t sigma)
     {
         if (lane < 3)
             store(cur + lane, jst_bam_le_byte(jst_bam_tag_head('M', 'D', 'Z'), lane));
-        const uint64_t begin = cur + 3;
-        uint64_t open = 0;
-        cur = begin + wave_md_walk(words, n, lane, open, [&](uint64_t at, uint64_t c, uint32_t word, uint64_t ref_at, uint64_t len) {
-                  for (uint64_t i = 0; i < len; ++i)
-                      store(begin + at + i, (uint8_t)jst_sam_md_word_char(c, word, ref + ref_at, symbols, sigma, i));
-              });
-        num(open);
+        num(md_words(cur + 3, words, n, ref, symbols, sigma));
         fill(0, 1);
     }
 };
@@ -155,7 +128,7 @@ __global__ __launch_bounds__(256) void jst_bam_write_kernel(const jst_bam_params
     H.n_items = shape & 0xFFFFu;
     H.bin = shape >> 16;
     const uint64_t begin = P.off64[i], end = begin + len;
-    jst_bam_wave_sink out{reinterpret_cast<uint8_t *>(P.text), begin, end < P.n_bytes ? end : P.n_bytes, lane};
+    jst_bam_wave_sink out{{reinterpret_cast<uint8_t *>(P.text), begin, end < P.n_bytes ? end : P.n_bytes, lane}};
     jst_bam_compose(P.S, F, H, B.codes, len - 4, out);
 }
 
@@ -163,14 +136,8 @@ __global__ __launch_bounds__(256) void jst_bam_write_kernel(const jst_bam_params
 
 extern "C" void spm_hip_bam_destroy(spm_bam *b)
 {
-    if (!b)
-        return;
-    if (b->ctx && (b->d_file || b->d_records || b->d_lines))
-        hipStreamSynchronize(b->ctx->stream);
-    hipFree(b->d_file);
-    hipFree(b->d_records);
-    hipFree(b->d_lines);
-    delete b;
+    if (b)
+        spm_hip::handle_destroy(b, {b->d_file, b->d_records, b->d_lines});
 }
 
 // the plain header: BAM\1, l_text, the text of spm_hip_sam_header (sorted: of spm_hip_sam_header_sorted), n_ref = 1, l_name, the
@@ -191,7 +158,7 @@ int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t 
     int rc = text(rname, ref_len, nullptr, 0, &n_text);
     if (rc != SPM_E_OVERFLOW) {
         if (ctx && rc == SPM_E_INVALID)
-            SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
+            SPM_SET_ERR(ctx, "%s: rname %s", who, kSamNameRule);
         return rc == SPM_OK ? SPM_E_INVALID : rc;
     }
     const uint32_t l_name = (uint32_t)strlen(rname) + 1;
@@ -210,6 +177,14 @@ int bam_plain_header(const char *who, spm_ctx *ctx, const char *rname, uint64_t 
     return SPM_OK;
 }
 
+static int bam_check_block_data(const char *who, spm_ctx *ctx, uint32_t block_data)
+{
+    if (block_data <= spm_hip::kBgzfBlockData)
+        return SPM_OK;
+    SPM_SET_ERR(ctx, "%s: block_data %u above 65280", who, block_data);
+    return SPM_E_INVALID;
+}
+
 static int bam_header_framed(const char *who, bool sorted, const char *rname, uint64_t ref_len, uint32_t block_data, void *buf, uint64_t cap,
                              uint64_t *len)
 {
@@ -217,10 +192,7 @@ static int bam_header_framed(const char *who, bool sorted, const char *rname, ui
         SPM_SET_ERR((spm_ctx *)nullptr, "%s: NULL %s", who, !rname ? "rname" : !len ? "len" : "buf with cap > 0");
         return SPM_E_INVALID;
     }
-    if (block_data > spm_hip::kBgzfBlockData) {
-        SPM_SET_ERR((spm_ctx *)nullptr, "%s: block_data %u above 65280", who, block_data);
-        return SPM_E_INVALID;
-    }
+    SPM_TRY(bam_check_block_data(who, nullptr, block_data));
     std::vector<uint8_t> plain;
     SPM_TRY(bam_plain_header(who, nullptr, rname, ref_len, sorted, plain));
     const spm_bgzf_opts o{block_data, 0, 0};
@@ -255,33 +227,26 @@ static int bam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_j
     SPM_TRY(sam_check_args(who, ctx, l, r, pr, rs, ps, &opts->sam, rname_len, n_named));
     if (ex)
         SPM_TRY(sam_check_extras(who, ctx, r, ps, ex, &opts->ref_len));
-    if (opts->block_data > kBgzfBlockData) {
-        SPM_SET_ERR(ctx, "%s: block_data %u above 65280", who, opts->block_data);
-        return SPM_E_INVALID;
-    }
+    SPM_TRY(bam_check_block_data(who, ctx, opts->block_data));
     if (opts->reserved) {
         SPM_SET_ERR(ctx, "%s: reserved is %u (must be 0)", who, opts->reserved);
         return SPM_E_INVALID;
     }
-    std::vector<uint8_t> plain, header;
-    SPM_TRY(bam_plain_header(who, ctx, opts->sam.rname, opts->ref_len, false, plain));
     const uint32_t D = bgzf_block_data(opts->block_data);
-    header.resize(bgzf_framed_size(plain.size(), D, false));
-    bgzf_frame_serial(plain.data(), plain.size(), D, false, header.data());
-    SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<spm_bam, void (*)(spm_bam *)> R(new spm_bam, spm_hip_bam_destroy);
-    R->ctx = ctx;
+    bam_file file;
+    bam_ptr R(nullptr, spm_hip_bam_destroy);
+    SPM_TRY(file.open(who, ctx, opts->sam.rname, opts->ref_len, D, false, R));
     hipStream_t st = ctx->stream;
     const uint32_t n_reads = (uint32_t)r->n;
     sam_front F;
+    hip_events<8> &ev = F.ev;
     jst_bam_params B;
+    jst_sam_params &P = B.P; // (no reads: no lines and no bytes)
     uint8_t codes[256];
     dev_scratch keep;
     if (n_reads) {
         SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, &opts->sam, ex, rname_len, n_named, F, &R->d_lines));
-        B.P = F.P;
-        jst_sam_params &P = B.P;
-        hip_events<8> &ev = F.ev;
+        P = F.P;
         // ---- measure (its time, ev[1] .. ev[2], takes in the two allocations and the 256-byte upload below) ----
         jst_bam_rank_codes(opts->sam.symbols, ps->sigma, codes);
         uint8_t *d_codes = nullptr;
@@ -291,39 +256,14 @@ static int bam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_j
         B.codes = d_codes;
         B.ref_len = opts->ref_len;
         SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_bam_measure_kernel, P.cap_lines, B));
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, F.d_tmp, F.tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
-        const unsigned long long *c = ctx->h_counters;
-        if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
-            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
-                             "needle set, ref_len or the reference of the extras, or do not fit a BAM record; nothing was written", who,
-                        c[kSamCntBad]);
-            return SPM_E_INVALID;
-        }
-        P.n_lines = (uint32_t)c[kSamCntLines];
-        P.n_bytes = c[kSamCntBytes];
+        SPM_TRY(sam_measured(who, ctx, F, P, ", ref_len or the reference of the extras, or do not fit a BAM record"));
     }
-    const uint64_t n_records = B.P.n_bytes;
-    if (bgzf_n_blocks(n_records, D) > kBgzfMaxBlocks) {
-        SPM_SET_ERR(ctx, "%s: %llu record bytes in blocks of %u are more than 2^31 - 2 blocks (not supported)", who,
-                    (unsigned long long)n_records, D);
-        return SPM_E_UNSUPPORTED;
-    }
-    R->plain_header = plain;
-    R->rname = opts->sam.rname;
-    R->ref_len = opts->ref_len;
-    R->block_data = D;
-    R->n_lines = B.P.n_lines;
-    R->n_record_bytes = n_records;
-    R->n_file = header.size() + bgzf_framed_size(n_records, D, true);
-    SPM_HIP_CHECK(ctx, hipMalloc(&R->d_file, R->n_file));
-    SPM_HIP_CHECK(ctx, hipMemcpyAsync(R->d_file, header.data(), header.size(), hipMemcpyHostToDevice, st));
+    const uint64_t n_records = P.n_bytes;
+    SPM_TRY(bgzf_check_n_blocks(who, ctx, n_records, D, "record bytes"));
+    SPM_TRY(file.place(R.get(), P.n_lines, n_records));
     hip_events<2> ev_frame;
     SPM_HIP_CHECK(ctx, ev_frame.create());
     if (n_reads) {
-        jst_sam_params &P = B.P;
-        hip_events<8> &ev = F.ev;
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_records, std::max<uint64_t>(n_records, 1)));
         P.text = reinterpret_cast<char *>(R->d_records);
         // ---- write ----
@@ -332,33 +272,16 @@ static int bam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_j
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
     }
-    // ---- frame: the record stream behind the header section, then EOF ----
+    // ---- frame ----
     SPM_HIP_CHECK(ctx, hipEventRecord(ev_frame[0], st));
-    SPM_HIP_CHECK(ctx, bgzf_frame_enqueue(ctx, R->d_records, n_records, D, true, R->d_file + header.size()));
+    SPM_TRY(file.frame(R.get()));
     SPM_HIP_CHECK(ctx, hipEventRecord(ev_frame[1], st));
-    R->stats.header_file_bytes = header.size();
-    R->stats.n_record_blocks = bgzf_n_blocks(n_records, D);
-    R->stats.n_file_bytes = R->n_file;
-    R->stats.n_record_bytes = n_records;
     if (n_reads) {
-        jst_sam_params &P = B.P;
-        hip_events<8> &ev = F.ev;
         // ---- stats ----
-        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_stats_kernel, P.n_lines, P));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
-        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
-        const unsigned long long *c = ctx->h_counters;
+        SPM_TRY(sam_closed(ctx, F, P, ev_frame[1], R->stats));
         R->stats.n_records = P.n_lines;
-        R->stats.n_reported = c[kSamCntReported];
-        R->stats.n_secondary = c[kSamCntSecondary];
-        R->stats.n_unmapped = c[kSamCntUnmapped];
-        R->stats.n_rescue_lines = c[kSamCntRescue];
-        hipEventElapsedTime(&R->stats.ms_lines, ev[0], ev[1]);
-        hipEventElapsedTime(&R->stats.ms_measure, ev[1], ev[2]);
-        hipEventElapsedTime(&R->stats.ms_write, ev[3], ev[4]);
-        hipEventElapsedTime(&R->stats.ms_stats, ev_frame[1], ev[5]);
     } else {
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st)); // (header and EOF are in place; `header` goes out of scope)
+        SPM_HIP_CHECK(ctx, hipStreamSynchronize(st)); // (header and EOF are in place; the file's header goes out of scope)
     }
     hipEventElapsedTime(&R->stats.ms_frame, ev_frame[0], ev_frame[1]);
     R->stats.ms_total = R->stats.ms_lines + R->stats.ms_measure + R->stats.ms_write + R->stats.ms_frame + R->stats.ms_stats;
@@ -387,95 +310,36 @@ extern "C" int spm_hip_jst_ref_loci_bam_ex(spm_jst_ref_loci *l, spm_jst_reads *r
     return bam_run("spm_hip_jst_ref_loci_bam_ex", l, r, pr, rs, ps, opts, ex, out);
 }
 
-extern "C" int spm_hip_bam_deflate(spm_bam *b, const spm_bgzf_deflate_opts *opts, spm_bgzf **out)
-{
-    static const char *const who = "spm_hip_bam_deflate";
-    if (out)
-        *out = nullptr;
-    if (!b)
-        return SPM_E_INVALID;
-    spm_ctx *ctx = b->ctx;
-    if (!opts || !out) {
-        SPM_SET_ERR(ctx, "%s: NULL %s", who, !opts ? "opts" : "out");
-        return SPM_E_INVALID;
-    }
-    // the header section through the host deflater, without an EOF block: that call holds the opts to the rule
-    spm_bgzf_deflate_opts o = *opts;
-    o.flags &= ~SPM_BGZF_EOF;
-    uint64_t need = 0, len = 0;
-    int rc = spm_hip_bgzf_deflate_bound(b->plain_header.size(), &o, &need);
-    std::vector<uint8_t> header(need);
-    if (rc == SPM_OK)
-        rc = spm_hip_bgzf_deflate_host(b->plain_header.data(), b->plain_header.size(), &o, header.data(), need, &len);
-    if (rc != SPM_OK) {
-        SPM_SET_ERR(ctx, "%s: block_data %u above 65280, flags 0x%x other than SPM_BGZF_EOF | SPM_BGZF_DYNAMIC, level %u other than 1 or reserved %u", who,
-                    opts->block_data, opts->flags, opts->level, opts->reserved);
-        return rc;
-    }
-    header.resize(len);
-    return bgzf_deflate_run(who, ctx, b->d_records, b->n_record_bytes, opts, header, out);
-}
-
 extern "C" int spm_hip_bam_view(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
                                 const spm_sam_line **lines, uint64_t *n_lines)
 {
+    using namespace spm_hip;
     if (!b)
         return SPM_E_INVALID;
-    if (!b->have_host) {
-        spm_ctx *ctx = b->ctx;
-        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        b->host_file.resize(b->n_file);
-        b->host_records.resize(b->n_record_bytes);
-        b->host_lines.resize(b->n_lines);
-        if (b->n_file)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_file.data(), b->d_file, b->n_file, hipMemcpyDeviceToHost, ctx->stream));
-        if (b->n_record_bytes)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_records.data(), b->d_records, b->n_record_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (b->n_lines)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(b->host_lines.data(), b->d_lines, b->n_lines * sizeof(spm_sam_line), hipMemcpyDeviceToHost,
-                                              ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    b->have_host = true;
-    if (file)
-        *file = b->host_file.data();
-    if (n_file)
-        *n_file = b->n_file;
-    if (records)
-        *records = b->host_records.data();
-    if (n_record_bytes)
-        *n_record_bytes = b->n_record_bytes;
-    if (lines)
-        *lines = b->host_lines.data();
-    if (n_lines)
-        *n_lines = b->n_lines;
+    SPM_TRY(handle_download(b->ctx, b->have_host, view_part{b->d_file, b->n_file, b->host_file},
+                            view_part{b->d_records, b->n_record_bytes, b->host_records}, view_part{b->d_lines, b->n_lines, b->host_lines}));
+    out_if(file, b->host_file.data());
+    out_if(n_file, b->n_file);
+    out_if(records, b->host_records.data());
+    out_if(n_record_bytes, b->n_record_bytes);
+    out_if(lines, b->host_lines.data());
+    out_if(n_lines, b->n_lines);
     return SPM_OK;
 }
 
 extern "C" int spm_hip_bam_device(spm_bam *b, const void **file, uint64_t *n_file, const void **records, uint64_t *n_record_bytes,
                                   const void **lines, uint64_t *n_lines)
 {
+    using namespace spm_hip;
     if (!b)
         return SPM_E_INVALID;
-    if (file)
-        *file = b->d_file;
-    if (n_file)
-        *n_file = b->n_file;
-    if (records)
-        *records = b->d_records;
-    if (n_record_bytes)
-        *n_record_bytes = b->n_record_bytes;
-    if (lines)
-        *lines = b->d_lines;
-    if (n_lines)
-        *n_lines = b->n_lines;
+    out_if(file, b->d_file);
+    out_if(n_file, b->n_file);
+    out_if(records, b->d_records);
+    out_if(n_record_bytes, b->n_record_bytes);
+    out_if(lines, b->d_lines);
+    out_if(n_lines, b->n_lines);
     return SPM_OK;
 }
 
-extern "C" int spm_hip_bam_stats(const spm_bam *b, spm_bam_stats *out)
-{
-    if (!b || !out)
-        return SPM_E_INVALID;
-    *out = b->stats;
-    return SPM_OK;
-}
+extern "C" int spm_hip_bam_stats(const spm_bam *b, spm_bam_stats *out) { return spm_hip::stats_out(b ? &b->stats : nullptr, out); }

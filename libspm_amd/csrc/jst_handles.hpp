@@ -8,8 +8,8 @@
 //   spm_jst_reads      jst_reads.hpp                                       read by jst_pairs.hpp .. jst_bam.hpp
 //   spm_jst_pairs      jst_pairs.hpp                                       read by jst_rescue.hpp .. jst_bam.hpp
 //   spm_jst_rescues    jst_rescue.hpp                                      read by jst_sam.hpp, jst_bam.hpp
-//   spm_sam, spm_bam   jst_sam.hpp, jst_bam.hpp                              spm_bam read by bam_index.hpp (sort, index)
-// (spm_jst_hits, which jst_select.hip shares, is common.hpp's.)  Host structs only: no kernel, no C-ABI definition.
+// (spm_jst_hits, which jst_select.hip shares, is common.hpp's.  The handles of the output stage behind these -- spm_sam, spm_bam,
+// spm_bgzf, spm_bai -- are output_handles.hpp's.)  Host structs only: no kernel, no C-ABI definition.
 #pragma once
 
 #include <string>
@@ -195,36 +195,3 @@ struct spm_jst_rescues : spm_hip::device_records<spm_jst_rescue, spm_jst_rescues
 };
 static_assert(sizeof(spm_jst_rescue_opts) == 20 && sizeof(spm_jst_rescue) == 48 && sizeof(spm_jst_rescues_stats) == 80,
               "spm_hip.h states these sizes");
-
-struct spm_sam
-{
-    spm_ctx *ctx = nullptr;
-    char *d_text = nullptr;
-    spm_sam_line *d_lines = nullptr;
-    uint64_t n_bytes = 0, n_lines = 0;
-    bool have_host = false; // the views are downloaded when first asked for
-    std::vector<char> host_text;
-    std::vector<spm_sam_line> host_lines;
-    spm_sam_stats stats{};
-};
-static_assert(sizeof(spm_sam_opts) == 64 && sizeof(spm_sam_line) == 24 && sizeof(spm_sam_stats) == 72, "spm_hip.h states these sizes");
-
-struct spm_bam
-{
-    spm_ctx *ctx = nullptr;
-    uint8_t *d_file = nullptr, *d_records = nullptr;
-    spm_sam_line *d_lines = nullptr;
-    uint64_t n_file = 0, n_record_bytes = 0, n_lines = 0;
-    bool have_host = false; // the views are downloaded when first asked for
-    std::vector<uint8_t> host_file, host_records;
-    std::vector<spm_sam_line> host_lines;
-    std::vector<uint8_t> plain_header; // the header section before its framing: what spm_hip_bam_deflate compresses again
-    spm_bam_stats stats{};
-    // what spm_hip_bam_sort writes the new header section from, and spm_hip_bam_index the stored blocks' offsets (bam_index.hpp)
-    std::string rname;
-    uint64_t ref_len = 0;
-    uint32_t block_data = 0; // uncompressed bytes of a full block: never 0
-    bool sorted = false;     // made by spm_hip_bam_sort, which then filled sort_stats
-    spm_bam_sort_stats sort_stats{};
-};
-static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");

@@ -1,5 +1,6 @@
 // jst_sam.hpp -- SAM lines and MAPQ (spm_hip_jst_ref_loci_sam; contract in spm_hip.h, scheme in DESIGN.md 4.11, the rule in
-// jst_sam_core.hpp).  gfx950.  Unit: jst_sam.hip.  It reads the handles of the loci, reads, pairs and rescues (jst_handles.hpp).
+// jst_sam_core.hpp).  gfx950.  Unit: jst_sam.hip.  It reads the handles of the loci, reads, pairs and rescues (jst_handles.hpp)
+// and makes a spm_sam (output_handles.hpp).
 //   jst_sam_first_rescue_kernel   one lane per rescue record: the ordering test against the record before it, and the first
 //                                 record of every pair scattered into first_rescue[pair];
 //   jst_sam_lines_kernel<kEmit>   one lane per read: the agreement tests, the reported line of the read (both mates of a pair
@@ -26,6 +27,7 @@
 #include "device_order.hpp"
 #include "jst_handles.hpp"
 #include "jst_sam_core.hpp"
+#include "output_handles.hpp"
 #include "scratch_layout.hpp"
 #include "wave.hpp"
 
@@ -225,19 +227,48 @@ template <class Put> __device__ __forceinline__ uint64_t wave_md_walk(const uint
     return done;
 }
 
-// The wave sink: the composition of one line, byte i of a field to lane i.  cur is wave-uniform.  No store lands outside
-// [cur at construction, end): the line's own bytes.
-struct jst_sam_wave_sink
+// What the two wave sinks share: byte i of a field to lane i.  cur is wave-uniform.  No store lands outside [cur at
+// construction, end): the line's, or the record's, own bytes.
+template <class Byte> struct jst_wave_sink_base
 {
-    char *to;
+    Byte *to;
     uint64_t cur, end;
     uint32_t lane;
 
-    __device__ __forceinline__ void store(uint64_t at, char c)
+    __device__ __forceinline__ void store(uint64_t at, Byte c)
     {
         if (at < end)
             to[at] = c;
     }
+    __device__ __forceinline__ void bytes(const char *p, uint64_t n)
+    {
+        for (uint64_t i = lane; i < n; i += kWave)
+            store(cur + i, (Byte)p[i]);
+        cur += n;
+    }
+    __device__ __forceinline__ void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
+    {
+        for (uint32_t i = lane; i < jst_sam_qual_len(m); i += kWave)
+            store(cur + i, (Byte)jst_sam_qual_byte(values, m, reverse, add, i));
+        cur += jst_sam_qual_len(m);
+    }
+    // the MD string from `begin` on: every lane writes the bytes of its own breaking word (a long D loops).  cur: behind them.
+    // -> the count behind the last breaking word, which the sink prints as a number
+    __device__ __forceinline__ uint64_t md_words(uint64_t begin, const uint32_t *words, uint32_t n, const uint8_t *ref, const char *symbols,
+                                                 uint32_t sigma)
+    {
+        uint64_t open = 0;
+        cur = begin + wave_md_walk(words, n, lane, open, [&](uint64_t at, uint64_t c, uint32_t word, uint64_t ref_at, uint64_t len) {
+                  for (uint64_t i = 0; i < len; ++i)
+                      store(begin + at + i, (Byte)jst_sam_md_word_char(c, word, ref + ref_at, symbols, sigma, i));
+              });
+        return open;
+    }
+};
+
+// The wave sink: the composition of one line.
+struct jst_sam_wave_sink : jst_wave_sink_base<char>
+{
     __device__ __forceinline__ void text(uint64_t lit, uint32_t n_lit)
     {
         if (lane < n_lit)
@@ -256,12 +287,6 @@ struct jst_sam_wave_sink
             store(cur + lane, jst_sam_dec_char(v, len, lane - head));
         cur += head + len;
     }
-    __device__ __forceinline__ void bytes(const char *p, uint64_t n)
-    {
-        for (uint64_t i = lane; i < n; i += kWave)
-            store(cur + i, p[i]);
-        cur += n;
-    }
     __device__ __forceinline__ void seq(const uint8_t *ranks, uint32_t m, const char *symbols, uint32_t sigma)
     {
         for (uint32_t i = lane; i < m; i += kWave)
@@ -279,22 +304,9 @@ struct jst_sam_wave_sink
                                   store(begin + at + i, jst_sam_word_char(run, op, len, i));
                           });
     }
-    __device__ __forceinline__ void qual(const uint8_t *values, uint32_t m, bool reverse, uint8_t add)
-    {
-        for (uint32_t i = lane; i < jst_sam_qual_len(m); i += kWave)
-            store(cur + i, (char)jst_sam_qual_byte(values, m, reverse, add, i));
-        cur += jst_sam_qual_len(m);
-    }
-    // every lane writes the bytes of its own breaking word (a long D loops); the count behind the last one follows as a number
     __device__ __forceinline__ void md(const uint32_t *words, uint32_t n, const uint8_t *ref, const char *symbols, uint32_t sigma)
     {
-        const uint64_t begin = cur;
-        uint64_t open = 0;
-        cur = begin + wave_md_walk(words, n, lane, open, [&](uint64_t at, uint64_t c, uint32_t word, uint64_t ref_at, uint64_t len) {
-                  for (uint64_t i = 0; i < len; ++i)
-                      store(begin + at + i, jst_sam_md_word_char(c, word, ref + ref_at, symbols, sigma, i));
-              });
-        num(0, 0, open, false);
+        num(0, 0, md_words(cur, words, n, ref, symbols, sigma), false);
     }
 };
 
@@ -309,7 +321,7 @@ template <bool kExtras> __global__ __launch_bounds__(256) void jst_sam_write_ker
     if (!jst_sam_resolve(P.S, P.lines[i], P.aux[i], F, false))
         return; // (the measure stage resolved this record and counted a failure: the host does not get here)
     const uint64_t begin = P.off64[i], end = begin + P.len[i];
-    jst_sam_wave_sink out{P.text, begin, end < P.n_bytes ? end : P.n_bytes, lane};
+    jst_sam_wave_sink out{{P.text, begin, end < P.n_bytes ? end : P.n_bytes, lane}};
     jst_sam_compose<kExtras>(P.S, F, out);
 }
 
@@ -345,14 +357,12 @@ static_assert(sizeof(spm_hip::jst_sam_aux) == 24 && sizeof(spm_sam_extras) == 32
 
 extern "C" void spm_hip_sam_destroy(spm_sam *s)
 {
-    if (!s)
-        return;
-    if (s->ctx && (s->d_text || s->d_lines))
-        hipStreamSynchronize(s->ctx->stream);
-    hipFree(s->d_text);
-    hipFree(s->d_lines);
-    delete s;
+    if (s)
+        spm_hip::handle_destroy(s, {s->d_text, s->d_lines});
 }
+
+// what a reference name, and a read name, has to be: the tail of each refusal
+static const char *const kSamNameRule = "is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'";
 
 extern "C" int spm_hip_sam_mapq(const spm_sam_opts *opts, uint32_t n_best, uint32_t n_next)
 {
@@ -366,7 +376,7 @@ static int sam_header_text(const char *so, const char *rname, uint64_t ref_len, 
     if (!rname || !len || (!buf && cap))
         return SPM_E_INVALID;
     if (!spm_hip::jst_sam_name_ok(rname, strlen(rname))) {
-        SPM_SET_ERR((spm_ctx *)nullptr, "spm_hip_sam_header: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'");
+        SPM_SET_ERR((spm_ctx *)nullptr, "%s: rname %s", "spm_hip_sam_header", kSamNameRule);
         return SPM_E_INVALID;
     }
     const std::string h = std::string("@HD\tVN:1.6\tSO:") + so + "\n@SQ\tSN:" + rname + "\tLN:" + std::to_string(ref_len) + "\n";
@@ -446,7 +456,7 @@ static int sam_check_args(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, sp
     }
     rname_len = strlen(opts->rname);
     if (!jst_sam_name_ok(opts->rname, rname_len)) {
-        SPM_SET_ERR(ctx, "%s: rname is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who);
+        SPM_SET_ERR(ctx, "%s: rname %s", who, kSamNameRule);
         return SPM_E_INVALID;
     }
     n_named = pr ? pr->n : r->n;
@@ -466,8 +476,7 @@ static int sam_check_args(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, sp
                 return SPM_E_INVALID;
             }
             if (!jst_sam_name_ok(opts->names + opts->name_off[i], opts->name_off[i + 1] - opts->name_off[i])) {
-                SPM_SET_ERR(ctx, "%s: name %llu is empty, longer than 254 bytes, \"*\" or holds a byte outside '!' .. '~'", who,
-                            (unsigned long long)i);
+                SPM_SET_ERR(ctx, "%s: name %llu %s", who, (unsigned long long)i, kSamNameRule);
                 return SPM_E_INVALID;
             }
         }
@@ -640,6 +649,45 @@ static int sam_lines_stage(const char *who, spm_ctx *ctx, spm_jst_ref_loci *l, s
     return SPM_OK;
 }
 
+// Behind the measure launch of either format: the lines' offsets, the one read-back before anything is written, the refusal
+// (`clause`: what else a record of this format can disagree with), n_lines and n_bytes.  P: the params the format launches with
+static int sam_measured(const char *who, spm_ctx *ctx, sam_front &F, spm_hip::jst_sam_params &P, const char *clause)
+{
+    using namespace spm_hip;
+    SPM_HIP_CHECK(ctx, exclusive_sum(ctx, F.d_tmp, F.tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));
+    SPM_HIP_CHECK(ctx, hipEventRecord(F.ev[2], ctx->stream));
+    SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+    const unsigned long long *c = ctx->h_counters;
+    if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
+        SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
+                         "needle set%s; nothing was written", who, c[kSamCntBad], clause);
+        return SPM_E_INVALID;
+    }
+    P.n_lines = (uint32_t)c[kSamCntLines];
+    P.n_bytes = c[kSamCntBytes];
+    return SPM_OK;
+}
+
+// Behind the last stage that writes (`before`: the event that closed it): the stats kernel, the second read-back, the four
+// counts and the four stage times that spm_sam_stats and spm_bam_stats share by name.
+template <class Stats> static int sam_closed(spm_ctx *ctx, sam_front &F, const spm_hip::jst_sam_params &P, hipEvent_t before, Stats &S)
+{
+    using namespace spm_hip;
+    SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_stats_kernel, P.n_lines, P));
+    SPM_HIP_CHECK(ctx, hipEventRecord(F.ev[5], ctx->stream));
+    SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+    const unsigned long long *c = ctx->h_counters;
+    S.n_reported = c[kSamCntReported];
+    S.n_secondary = c[kSamCntSecondary];
+    S.n_unmapped = c[kSamCntUnmapped];
+    S.n_rescue_lines = c[kSamCntRescue];
+    hipEventElapsedTime(&S.ms_lines, F.ev[0], F.ev[1]);
+    hipEventElapsedTime(&S.ms_measure, F.ev[1], F.ev[2]);
+    hipEventElapsedTime(&S.ms_write, F.ev[3], F.ev[4]);
+    hipEventElapsedTime(&S.ms_stats, before, F.ev[5]);
+    return SPM_OK;
+}
+
 static int sam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_jst_pairs *pr, spm_jst_rescues *rs, const spm_patterns *ps,
                    const spm_sam_opts *opts, const spm_sam_extras *ex, spm_sam **out)
 {
@@ -664,21 +712,9 @@ static int sam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_j
         SPM_TRY(sam_lines_stage(who, ctx, l, r, pr, rs, ps, opts, ex, rname_len, n_named, F, &R->d_lines));
         jst_sam_params &P = F.P;
         hip_events<8> &ev = F.ev;
-        uint8_t *d_tmp = F.d_tmp;
-        const size_t tmp64 = F.tmp64;
         // ---- measure ----
         SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_measure_kernel, P.cap_lines, P));
-        SPM_HIP_CHECK(ctx, exclusive_sum(ctx, d_tmp, tmp64, counted<uint64_t>(sam_len_op{P.len}), P.off64, P.cap_lines));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
-        const unsigned long long *c = ctx->h_counters;
-        if (c[kSamCntBad] || c[kSamCntLines] > P.cap_lines) {
-            SPM_SET_ERR(ctx, "%s: %llu records of the reads, pairs or rescues disagree with each other, these loci, their pools, the "
-                             "needle set or the reference of the extras; nothing was written", who, c[kSamCntBad]);
-            return SPM_E_INVALID;
-        }
-        P.n_lines = (uint32_t)c[kSamCntLines];
-        P.n_bytes = c[kSamCntBytes];
+        SPM_TRY(sam_measured(who, ctx, F, P, " or the reference of the extras"));
         R->n_lines = P.n_lines;
         R->n_bytes = P.n_bytes;
         SPM_HIP_CHECK(ctx, hipMalloc(&R->d_text, std::max<uint64_t>(P.n_bytes, 1)));
@@ -692,19 +728,9 @@ static int sam_run(const char *who, spm_jst_ref_loci *l, spm_jst_reads *r, spm_j
         SPM_HIP_CHECK(ctx, hipGetLastError());
         SPM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
         // ---- stats ----
-        SPM_HIP_CHECK(ctx, launch_1d(ctx, jst_sam_stats_kernel, P.n_lines, P));
-        SPM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
-        SPM_HIP_CHECK(ctx, read_counts(ctx, P.counts, kSamCnts));
+        SPM_TRY(sam_closed(ctx, F, P, ev[4], R->stats));
         R->stats.n_lines = P.n_lines;
         R->stats.n_bytes = P.n_bytes;
-        R->stats.n_reported = c[kSamCntReported];
-        R->stats.n_secondary = c[kSamCntSecondary];
-        R->stats.n_unmapped = c[kSamCntUnmapped];
-        R->stats.n_rescue_lines = c[kSamCntRescue];
-        hipEventElapsedTime(&R->stats.ms_lines, ev[0], ev[1]);
-        hipEventElapsedTime(&R->stats.ms_measure, ev[1], ev[2]);
-        hipEventElapsedTime(&R->stats.ms_write, ev[3], ev[4]);
-        hipEventElapsedTime(&R->stats.ms_stats, ev[4], ev[5]);
         R->stats.ms_total = R->stats.ms_lines + R->stats.ms_measure + R->stats.ms_write + R->stats.ms_stats;
     }
     R->stats.ms_host = ms_since(t_call);
@@ -732,51 +758,27 @@ extern "C" int spm_hip_jst_ref_loci_sam_ex(spm_jst_ref_loci *l, spm_jst_reads *r
 
 extern "C" int spm_hip_sam_view(spm_sam *s, const char **text, uint64_t *n_bytes, const spm_sam_line **lines, uint64_t *n_lines)
 {
+    using namespace spm_hip;
     if (!s)
         return SPM_E_INVALID;
-    if (!s->have_host && (s->n_bytes || s->n_lines)) {
-        spm_ctx *ctx = s->ctx;
-        SPM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        s->host_text.resize(s->n_bytes);
-        s->host_lines.resize(s->n_lines);
-        if (s->n_bytes)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(s->host_text.data(), s->d_text, s->n_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (s->n_lines)
-            SPM_HIP_CHECK(ctx, hipMemcpyAsync(s->host_lines.data(), s->d_lines, s->n_lines * sizeof(spm_sam_line), hipMemcpyDeviceToHost,
-                                              ctx->stream));
-        SPM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    s->have_host = true;
-    if (text)
-        *text = s->host_text.data();
-    if (n_bytes)
-        *n_bytes = s->n_bytes;
-    if (lines)
-        *lines = s->host_lines.data();
-    if (n_lines)
-        *n_lines = s->n_lines;
+    SPM_TRY(handle_download(s->ctx, s->have_host, view_part{s->d_text, s->n_bytes, s->host_text}, view_part{s->d_lines, s->n_lines, s->host_lines}));
+    out_if(text, s->host_text.data());
+    out_if(n_bytes, s->n_bytes);
+    out_if(lines, s->host_lines.data());
+    out_if(n_lines, s->n_lines);
     return SPM_OK;
 }
 
 extern "C" int spm_hip_sam_device(spm_sam *s, const void **text, uint64_t *n_bytes, const void **lines, uint64_t *n_lines)
 {
+    using namespace spm_hip;
     if (!s)
         return SPM_E_INVALID;
-    if (text)
-        *text = s->d_text;
-    if (n_bytes)
-        *n_bytes = s->n_bytes;
-    if (lines)
-        *lines = s->d_lines;
-    if (n_lines)
-        *n_lines = s->n_lines;
+    out_if(text, s->d_text);
+    out_if(n_bytes, s->n_bytes);
+    out_if(lines, s->d_lines);
+    out_if(n_lines, s->n_lines);
     return SPM_OK;
 }
 
-extern "C" int spm_hip_sam_stats(const spm_sam *s, spm_sam_stats *out)
-{
-    if (!s || !out)
-        return SPM_E_INVALID;
-    *out = s->stats;
-    return SPM_OK;
-}
+extern "C" int spm_hip_sam_stats(const spm_sam *s, spm_sam_stats *out) { return spm_hip::stats_out(s ? &s->stats : nullptr, out); }

@@ -5,8 +5,8 @@
 
 REGEX selects kernels by their demangled name (default: all of them).  The units that hold the seed filter's kernels are
 filter_stream, filter_dense, filter_resolve and filter_verify; scan_brute holds the brute-force kernels, jst, select,
-jst_select, align, bgzf, text, patterns, hits and comm their own.  scripts/kernel_diff.py compares two builds kernel by kernel
-and reads the listings through kernel_table() below."""
+jst_select, align, bgzf, bam_index, text, patterns, hits and comm their own.  scripts/kernel_diff.py compares two builds kernel by
+kernel and reads the listings through kernel_table() below."""
 import re
 import subprocess
 import sys
