@@ -192,6 +192,8 @@ struct jst_bam_options
     bool dynamic{false};                // with deflate only: a block may take a Huffman code of its own (SPM_BGZF_DYNAMIC)
     bool sort{false};                   // the records in coordinate order under SO:coordinate (spm_hip_bam_sort)
     bool index{false};                  // with sort: jst_bam::bai, the .bai of the file (spm_hip_bam_index / spm_hip_bai_build_host)
+    bool mark_duplicates{false};        // FLAG 0x400 on duplicate reads and pairs, behind sort and before deflate / index
+                                        // (spm_hip_bam_markdup / spm_hip_bam_markdup_host; default min_qual)
 };
 
 struct jst_bam
@@ -1190,6 +1192,19 @@ public:
             out.lines.push_back(c.line);
             out.records += c.bytes;
         }
+        if (o.mark_duplicates) { // the serial builder over the records just written: one bit of byte 19 per record, and the line's flag
+            std::vector<spm_sam_line> lines;
+            for (jst_sam_line const & l : out.lines)
+                lines.push_back(spm_sam_line{l.offset, l.len, l.read, l.source, l.flag, l.mapq, l.kind});
+            std::vector<std::uint8_t> dup(lines.size(), 0);
+            if (spm_hip_bam_markdup_host(out.records.data(), out.records.size(), lines.data(), lines.size(), o.ref_len, nullptr, dup.data()) != SPM_OK)
+                hip::fatal("spm_hip_bam_markdup_host", ctx);
+            for (std::size_t i = 0; i < dup.size(); ++i) {
+                char & high = out.records[out.lines[i].offset + 19];
+                high = static_cast<char>((static_cast<std::uint8_t>(high) & ~0x4u) | (dup[i] ? 0x4u : 0u));
+                out.lines[i].flag = static_cast<std::uint16_t>((out.lines[i].flag & ~0x400u) | (dup[i] ? 0x400u : 0u));
+            }
+        }
         // the header: BAM\1, l_text, the SAM header, one reference; framed on its own, then the records and the EOF block
         std::uint64_t n_text = 0;
         auto const header_text = o.sort ? spm_hip_sam_header_sorted : spm_hip_sam_header;
@@ -1912,6 +1927,13 @@ private:
                     hip::fatal("spm_hip_bam_sort", ctx);
                 owner.reset(sorted);
                 b = sorted;
+            }
+            if (req.bam_options->mark_duplicates) { // ... and the marked handle the place of that one
+                spm_bam * marked = nullptr;
+                if (spm_hip_bam_markdup(b, nullptr, &marked) != SPM_OK)
+                    hip::fatal("spm_hip_bam_markdup", ctx);
+                owner.reset(marked);
+                b = marked;
             }
             spm_bgzf * index_of = nullptr; // the deflated file, where the index is the deflated file's
             auto const index = [&] {

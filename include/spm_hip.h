@@ -1441,6 +1441,87 @@ int spm_hip_bai_device(spm_bai *z, const void **bytes, uint64_t *n);
 int spm_hip_bai_stats(const spm_bai *z, spm_bai_stats *out);
 void spm_hip_bai_destroy(spm_bai *z);
 
+/* ---- duplicate reads and pairs marked with FLAG 0x400: the step between "sort" and "index" (samtools markdup, Picard) ------
+ * spm_hip_bam_markdup returns a NEW spm_bam that differs from b in bit 0x400 of every record's flag (one byte per record, at
+ * record offset 19, and the flag of the record's line) and in the CRC32 of the re-framed blocks, nothing else: the header
+ * section with its SO:, record order, offsets and lengths, rname, ref_len, block_data, sorted and the sort stats are b's.
+ * view, device, stats, destroy, spm_hip_bam_deflate, spm_hip_bam_sort, spm_hip_bam_index and this call again work on it
+ * unchanged; the stage times and counts of the call are spm_hip_bam_markdup_stats'.  spm_hip_bam_markdup_records is the raw
+ * form over any device record stream and its spm_sam_line records (offset, len, read): dup[i] = 1 iff record i is a duplicate;
+ * spm_hip_bam_markdup_host the same bytes by a serial walk on the host (maps, no sort), no device needed.  The rule, a
+ * function of the record stream and the line records alone:
+ *   * Which records take part.  Read r's PRIMARY RECORD is the one line with lines.read == r whose record's flag has neither
+ *     0x100 nor 0x800; mates are reads 2p and 2p + 1.  r is PLACED if its primary record exists and lacks 0x4.  Secondary and
+ *     unmapped records never take part: their 0x400 comes out clear.
+ *   * The 5' end (u, s) of a placed read: s is flag 0x10; u = pos on the forward strand, u = end - 1 on the reverse strand,
+ *     end = pos + max(span, 1) with span the reference symbols of the CIGAR (M D N = X), the record's end in the BAI rule.
+ *     CIGAR items S and H are refused (the writers make none): unclipped ends are out of scope.
+ *   * A placed read is a PAIR END if its primary flag has 0x1, read r ^ 1 is placed and that read's primary flag has 0x1;
+ *     any other placed read is a FRAGMENT.
+ *   * The score of a record is the sum of its qual bytes v with min_qual <= v <= 93, clamped to 2^24 - 1: the ff fill scores
+ *     0.  A pair's score is the sum of its two mates' scores.
+ *   * Pairs.  The key of pair p is its two ends ordered by (u, s): (u_lo, s_lo, u_hi, s_hi).  Which mate is the lower end is
+ *     NOT part of the key -- a fixed choice: Picard tells F1F2 from F2F1, this rule does not.  Among pairs of equal key the one
+ *     with the highest score stays, ties going to the lowest p; every other pair of that key is a duplicate, on BOTH primary
+ *     records.
+ *   * Fragments.  A fragment whose (u, s) is an end of ANY pair is a duplicate, whether or not that pair is one itself.  Among
+ *     the remaining fragments of equal (u, s) the highest score stays, ties going to the lowest r; the others are duplicates.
+ *   * An incoming 0x400 is ignored and recomputed: marking a marked handle is byte-identical.  Nothing depends on record
+ *     order: sort-then-mark and mark-then-sort have byte-identical views.
+ * Worked cases (ref_len 10000, refID 0, no qualities; POS as SAM prints it):
+ *     read 0   FLAG 0   POS 101  40=   (100, +)   stays
+ *     read 1   FLAG 0   POS 101  30=   (100, +)   duplicate of 0
+ *     read 2   FLAG 16  POS 112  30=   (140, -)   stays
+ *     read 3   FLAG 16  POS 102  40=   (140, -)   duplicate of 2, although POS differs
+ *     read 4   FLAG 16  POS 101  40=   (139, -)   stays
+ *     reads 6, 7     a pair  (1000, +) / (1199, -)   stay
+ *     reads 8, 9     a pair  (1000, +) / (1199, -)   pair 4 is a duplicate, both records
+ *     reads 10, 11   a pair  (1000, +) / (1299, -)   stay
+ *     read 12  its mate 13 unmapped  (1000, +)     duplicate: a pair end sits there
+ *     read 13  flag 0x4, placed beside 12          unchanged
+ *   If read 1 carries 30 values of Phred 30 and read 0 40 values of Phred 10 (below the default min_qual), read 0 is the duplicate.
+ *   * SPM_E_INVALID, decided on the host before any launch: NULL arguments (opts and stats may be NULL); nonzero flags or
+ *     reserved; min_qual above 93; buffers without counts or counts without buffers.  SPM_E_UNSUPPORTED: more than 2^32 - 1
+ *     records; ref_len >= 2^30 (a pair key needs 2 * bits(ref_len) + 2 bits of the 64 the sort takes, and a BAI reaches 2^29).
+ *   * Counted on the device, each test before a value is used as an index, brought back with the counts in ONE read-back,
+ *     and failing the call with SPM_E_INVALID, nothing returned or written, never a fault: a line that leaves the stream; a
+ *     block_size that is not len - 4; a name or CIGAR that leaves the record; an l_seq whose seq and qual leave the record;
+ *     lines.read >= n_lines; two primary records of one read; a placed primary record with a refID other than 0, pos < 0,
+ *     end > ref_len or a CIGAR item S or H.
+ *   * Zero records: the header section and the EOF block.
+ * A pure function of its inputs: host and device agree byte for byte across runs; the result outlives b. */
+typedef struct spm_bam_markdup_opts {  /* 16 bytes */
+    uint32_t min_qual;              /* 0: 15; above 93: SPM_E_INVALID */
+    uint32_t flags;                 /* must be 0 */
+    uint64_t reserved;              /* must be 0 */
+} spm_bam_markdup_opts;
+typedef struct spm_bam_markdup_stats { /* 88 bytes */
+    float ms_total;                 /* device: the five stages below (HIP events) */
+    float ms_keys;                  /* primary records claimed; 5' end and score of every placed one, one wave per record */
+    float ms_sort;                  /* pairs, then ends: by inverted score, then stably by key */
+    float ms_mark;                  /* "my key is my left neighbour's" by read, then by line; the counts */
+    float ms_write;                 /* the stream copied, one byte per record, the line records (0 in the raw form) */
+    float ms_frame;                 /* the stream into BGZF blocks behind the header section (0 in the raw form) */
+    float ms_host;                  /* wall clock of the whole call */
+    uint32_t reserved;
+    uint64_t n_records;
+    uint64_t n_pairs;
+    uint64_t n_fragments;
+    uint64_t n_dup_pairs;
+    uint64_t n_dup_fragments;
+    uint64_t n_dup_records;         /* 2 n_dup_pairs + n_dup_fragments */
+    uint64_t n_fragments_beside_pairs; /* of n_dup_fragments: a pair end sits at their (u, s) */
+} spm_bam_markdup_stats;
+int spm_hip_bam_markdup(spm_bam *b, const spm_bam_markdup_opts *opts /* NULL: defaults */, spm_bam **out);
+/* SPM_E_INVALID on a handle no markdup made */
+int spm_hip_bam_markdup_stats(const spm_bam *b, spm_bam_markdup_stats *out);
+/* dup is a caller-owned device buffer of n_lines bytes, written behind the read-back */
+int spm_hip_bam_markdup_records(spm_ctx *ctx, const void *device_records, uint64_t n_record_bytes, const void *device_lines,
+                                uint64_t n_lines, uint64_t ref_len, const spm_bam_markdup_opts *opts /* NULL: defaults */,
+                                void *device_dup, spm_bam_markdup_stats *stats /* NULL */);
+int spm_hip_bam_markdup_host(const void *records, uint64_t n_record_bytes, const spm_sam_line *lines, uint64_t n_lines,
+                             uint64_t ref_len, const spm_bam_markdup_opts *opts /* NULL: defaults */, uint8_t *dup);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

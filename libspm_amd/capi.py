@@ -327,6 +327,17 @@ class BamSortStats(C.Structure):
                 ("n_records", C.c_uint64), ("n_record_bytes", C.c_uint64)]
 
 
+class BamMarkdupOpts(C.Structure):
+    _fields_ = [("min_qual", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class BamMarkdupStats(C.Structure):
+    _fields_ = [("ms_total", C.c_float), ("ms_keys", C.c_float), ("ms_sort", C.c_float), ("ms_mark", C.c_float),
+                ("ms_write", C.c_float), ("ms_frame", C.c_float), ("ms_host", C.c_float), ("reserved", C.c_uint32),
+                ("n_records", C.c_uint64), ("n_pairs", C.c_uint64), ("n_fragments", C.c_uint64), ("n_dup_pairs", C.c_uint64),
+                ("n_dup_fragments", C.c_uint64), ("n_dup_records", C.c_uint64), ("n_fragments_beside_pairs", C.c_uint64)]
+
+
 class BaiStats(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_records", C.c_float), ("ms_chunks", C.c_float), ("ms_bins", C.c_float),
                 ("ms_write", C.c_float), ("ms_host", C.c_float), ("n_bins", C.c_uint64), ("n_chunks", C.c_uint64),
@@ -581,6 +592,11 @@ SIGNATURES = {
     "spm_hip_bai_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "spm_hip_bai_stats": (C.c_int, [_vp, C.POINTER(BaiStats)]),
     "spm_hip_bai_destroy": (None, [_vp]),
+    "spm_hip_bam_markdup": (C.c_int, [_vp, C.POINTER(BamMarkdupOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_markdup_stats": (C.c_int, [_vp, C.POINTER(BamMarkdupStats)]),
+    "spm_hip_bam_markdup_records": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(BamMarkdupOpts), _vp,
+                                              C.POINTER(BamMarkdupStats)]),
+    "spm_hip_bam_markdup_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(BamMarkdupOpts), _vp]),
     "spm_hip_jst_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),

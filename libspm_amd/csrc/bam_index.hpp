@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void bam_sort_place_kernel(const bam_sort_para
         P.counts[kSortCntBytes] = L.offset + L.len;
 }
 
-// the dword at source offset a (a multiple of 4, below n_bytes); the last dword of the stream may be short
+// the dword at source offset a (src + a on a 4-byte border, a below n_bytes); the last dword of the stream may be short
 __device__ __forceinline__ uint32_t bam_src_dword(const uint8_t *src, uint64_t n_bytes, uint64_t a)
 {
     if (a + 4 <= n_bytes)

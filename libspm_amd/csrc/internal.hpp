@@ -4,8 +4,8 @@
 // filter_verify.hip (filter_launch.hpp); hits.hip: results; align.hip: alignments of hits; select.hip: selection of hits;
 // device_order.hip: the pair sort of the drivers that order records (device_order.hpp); jst.hip: journaled sequences, with
 // jst_align.hip, jst_ref.hip, jst_reads.hip and jst_sam.hip behind it (map in jst.hpp) and jst_select.hip beside it;
-// bgzf.hip: BGZF framing and deflate; bam_index.hip: the sorted BAM and its BAI index (the handles of both and of jst_sam.hip:
-// output_handles.hpp); comm.hip: the multi-GPU exchange.)
+// bgzf.hip: BGZF framing and deflate; bam_index.hip: the sorted BAM, its BAI index and its duplicate marks (the handles of both
+// and of jst_sam.hip: output_handles.hpp); comm.hip: the multi-GPU exchange.)
 #pragma once
 
 #include <algorithm>

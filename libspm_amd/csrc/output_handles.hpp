@@ -1,12 +1,12 @@
 // output_handles.hpp -- the result handles of the output stage, and what their C accessors do, written once:
 //   spm_sam    jst_sam.hpp                          SAM text and its line records
-//   spm_bam    jst_bam.hpp, bam_index.hpp (sort)    a BAM file, its record stream and line records; read by bam_index.hpp
-//                                                   (sort, index) and bgzf.hip (spm_hip_bam_deflate)
+//   spm_bam    jst_bam.hpp, bam_index.hpp (sort),   a BAM file, its record stream and line records; read by bam_index.hpp
+//              bam_markdup.hpp (markdup)            (sort, index), bam_markdup.hpp and bgzf.hip (spm_hip_bam_deflate)
 //   spm_bgzf   bgzf.hip                             framed or deflated blocks and their offsets; read by bam_index.hpp (index)
 //   spm_bai    bam_index.hpp                        the bytes of a BAI index
 // Behind them: the lazy download of a handle's host view, the synchronise-and-free of its device buffers, the copy-out of
-// optional out-parameters and of a stats struct; the BAM file around a record stream that spm_hip_jst_ref_loci_bam and
-// spm_hip_bam_sort both make; the refusal both BGZF calls and the BAM call word alike.  Host code only: no kernel, no C-ABI
+// optional out-parameters and of a stats struct; the BAM file around a record stream that spm_hip_jst_ref_loci_bam,
+// spm_hip_bam_sort and spm_hip_bam_markdup make; the refusal both BGZF calls and the BAM call word alike.  Host code only: no kernel, no C-ABI
 // definition.
 #pragma once
 
@@ -50,9 +50,12 @@ struct spm_bam
     uint32_t block_data = 0; // uncompressed bytes of a full block: never 0
     bool sorted = false;     // made by spm_hip_bam_sort, which then filled sort_stats
     spm_bam_sort_stats sort_stats{};
+    bool marked = false;     // made by spm_hip_bam_markdup (bam_markdup.hpp), which then filled markdup_stats
+    spm_bam_markdup_stats markdup_stats{};
 };
 static_assert(sizeof(spm_bam_opts) == 80 && sizeof(spm_bam_stats) == 104, "spm_hip.h states these sizes");
 static_assert(sizeof(spm_bam_sort_opts) == 8 && sizeof(spm_bam_sort_stats) == 48, "spm_hip.h states these sizes");
+static_assert(sizeof(spm_bam_markdup_opts) == 16 && sizeof(spm_bam_markdup_stats) == 88, "spm_hip.h states these sizes");
 
 struct spm_bgzf
 {

@@ -10,7 +10,7 @@
 //   wave_run_scan   segmented inclusive scan over runs of equal id: the last lane of a run holds the run's combined value
 //   run_min, run_sum   the values the callers carry through it, alone or as the members of a struct of their own (scalar
 //                   members only: an array member sends the scan through scratch memory)
-//   wave_max        the maximum of the wave, in every lane
+//   wave_max, wave_sum   the maximum and the sum of the wave, in every lane
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -127,6 +127,13 @@ template <class T> __device__ __forceinline__ T wave_max(T v)
         const T v2 = __shfl_xor(v, d);
         v = v2 > v ? v2 : v;
     }
+    return v;
+}
+
+template <class T> __device__ __forceinline__ T wave_sum(T v)
+{
+    for (int d = 32; d; d >>= 1)
+        v += __shfl_xor(v, d);
     return v;
 }
 

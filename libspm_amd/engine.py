@@ -194,6 +194,16 @@ class Context:
                                             C.c_void_p(block_offsets), int(n_blocks), int(block_data), C.byref(z)), self._h)
         return Bai(self, z)
 
+    def bam_markdup(self, records: int, n_record_bytes: int, lines: int, n_lines: int, ref_len: int, dup_ptr: int,
+                    min_qual: int = 0) -> capi.BamMarkdupStats:
+        """Duplicate marks of a record stream in device memory (spm_hip_bam_markdup_records), the raw form of Bam.markdup():
+        records / lines are device pointers to the uncompressed stream and its SAM_LINE_DTYPE records (offset, len and read are
+        read), dup_ptr one to n_lines bytes that take 1 where the record is a duplicate.  min_qual: 0 for 15.  -> the counts."""
+        opts, stats = bam_markdup_opts(min_qual), capi.BamMarkdupStats()
+        _check(capi.lib().spm_hip_bam_markdup_records(self._h, C.c_void_p(records), int(n_record_bytes), C.c_void_p(lines), int(n_lines),
+                                                      int(ref_len), C.byref(opts), C.c_void_p(dup_ptr), C.byref(stats)), self._h)
+        return stats
+
     def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
         block; a block that would not shrink stays stored).  dynamic: a block may take a Huffman code of its own, built on the
@@ -1001,6 +1011,23 @@ def bai_build_host(records, lines, block_offsets, block_data: int = 0) -> bytes:
         src, len(records), lines.ctypes.data, len(lines), offs.ctypes.data, max(len(offs), 1) - 1, int(block_data), dst, cap, need))
 
 
+def bam_markdup_opts(min_qual: int = 0) -> capi.BamMarkdupOpts:
+    return capi.BamMarkdupOpts(min_qual=int(min_qual), flags=0, reserved=0)
+
+
+def bam_markdup_host(records, lines, ref_len: int, min_qual: int = 0) -> np.ndarray:
+    """dup[i] = 1 where record i is a duplicate, by the serial host builder (spm_hip_bam_markdup_host): records the uncompressed
+    stream, lines its SAM_LINE_DTYPE records.  Needs no device."""
+    records = bytes(records)
+    lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
+    src = C.create_string_buffer(records, len(records) + 1)
+    dup = np.zeros(len(lines), dtype=np.uint8)
+    opts = bam_markdup_opts(min_qual)
+    _check(capi.lib().spm_hip_bam_markdup_host(src, len(records), lines.ctypes.data, len(lines), int(ref_len), C.byref(opts),
+                                               dup.ctypes.data), None)
+    return dup
+
+
 class Bam(_Handle):
     """Result of JstRefLoci.bam(): the file, the uncompressed record stream and one SAM_LINE_DTYPE record per BAM record
     (offset / len: the record in the stream), in record order."""
@@ -1053,6 +1080,17 @@ class Bam(_Handle):
     def sort_stats(self) -> capi.BamSortStats:
         """the stage times of the sort() that made this object"""
         return self._stats(capi.BamSortStats, "sort_stats")
+
+    def markdup(self, min_qual: int = 0) -> "Bam":
+        """A new Bam whose duplicate reads and pairs carry FLAG 0x400 (spm_hip_bam_markdup; the rule is in spm_hip.h): the same
+        records in the same order, one bit per record apart.  min_qual: the lowest base quality that counts towards a record's
+        score, 0 for 15."""
+        opts = bam_markdup_opts(min_qual)
+        return Bam(self.ctx, self._new("markdup", C.byref(opts)), self.block_data)
+
+    def markdup_stats(self) -> capi.BamMarkdupStats:
+        """the stage times and counts of the markdup() that made this object"""
+        return self._stats(capi.BamMarkdupStats, "markdup_stats")
 
     def index(self, deflated: "Bgzf | None" = None) -> "Bai":
         """The BAI index of this coordinate-sorted file (spm_hip_bam_index), or, with deflated = self.deflate(block_data) in
