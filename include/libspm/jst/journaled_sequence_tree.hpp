@@ -194,6 +194,8 @@ struct jst_bam_options
     bool index{false};                  // with sort: jst_bam::bai, the .bai of the file (spm_hip_bam_index / spm_hip_bai_build_host)
     bool mark_duplicates{false};        // FLAG 0x400 on duplicate reads and pairs, behind sort and before deflate / index
                                         // (spm_hip_bam_markdup / spm_hip_bam_markdup_host; default min_qual)
+    bool pileup{false};                 // with sort: jst_bam::pileup, the per-base counts of the file over the whole reference, behind
+                                        // mark_duplicates (spm_hip_bam_pileup / spm_hip_bam_pileup_host; default options)
 };
 
 struct jst_bam
@@ -203,6 +205,7 @@ struct jst_bam
     std::uint64_t header_file_bytes{0}; // where the first record block starts
     std::vector<std::uint64_t> block_offsets; // with jst_bam_options::deflate only: the file offset of every record block, then their end
     std::string bai;                    // with jst_bam_options::index: the bytes of the file's .bai
+    std::vector<std::uint32_t> pileup;  // with jst_bam_options::pileup: 8 planes (SPM_PILEUP_A ..) x ref_len counts, plane-major
     bool operator==(jst_bam const &) const noexcept = default;
     // the BGZF virtual file offset of record i
     std::uint64_t virtual_offset(std::size_t i, std::uint32_t block_data = 0) const
@@ -1028,6 +1031,8 @@ public:
     {
         if (options.index && !options.sort)
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
+        if (options.pileup && !options.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", hip::default_context());
         if (device_ready())
             return map_bam_device(needles, window, strands, n_reads, pairing, options, selection, block, stats);
         return map_bam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options, selection, block, stats);
@@ -1041,6 +1046,8 @@ public:
             hip::fatal("journaled_sequence_tree::map_bam_device (tree not representable on the device)", hip::default_context());
         if (options.index && !options.sort)
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
+        if (options.pileup && !options.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", hip::default_context());
         jst_bam out;
         std::vector<jst_read> reads;
         std::vector<jst_pair> pairs;
@@ -1088,6 +1095,8 @@ public:
         std::string const seq_letters = "=ACMGRSVTWYHKDBN", cigar_ops = "MIDNSHP=X";
         if (o.index && !o.sort)
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", ctx);
+        if (o.pileup && !o.sort)
+            hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", ctx);
         jst_bam out;
         // the records in read order, and what coordinate order looks at: without a position or not, POS, the reverse strand
         struct converted
@@ -1204,6 +1213,15 @@ public:
                 high = static_cast<char>((static_cast<std::uint8_t>(high) & ~0x4u) | (dup[i] ? 0x4u : 0u));
                 out.lines[i].flag = static_cast<std::uint16_t>((out.lines[i].flag & ~0x400u) | (dup[i] ? 0x400u : 0u));
             }
+        }
+        if (o.pileup) { // the serial builder over the records just written, marks and all
+            std::vector<spm_sam_line> lines;
+            for (jst_sam_line const & l : out.lines)
+                lines.push_back(spm_sam_line{l.offset, l.len, l.read, l.source, l.flag, l.mapq, l.kind});
+            out.pileup.assign(SPM_PILEUP_PLANES * o.ref_len, 0);
+            if (spm_hip_bam_pileup_host(out.records.data(), out.records.size(), lines.data(), lines.size(), o.ref_len, nullptr,
+                                        out.pileup.data()) != SPM_OK)
+                hip::fatal("spm_hip_bam_pileup_host", ctx);
         }
         // the header: BAM\1, l_text, the SAM header, one reference; framed on its own, then the records and the EOF block
         std::uint64_t n_text = 0;
@@ -1934,6 +1952,18 @@ private:
                     hip::fatal("spm_hip_bam_markdup", ctx);
                 owner.reset(marked);
                 b = marked;
+            }
+            req.bam_out->pileup.clear();
+            if (req.bam_options->pileup) { // the counts of the handle as it stands: sorted, and marked where that was asked for
+                spm_pileup * p = nullptr;
+                if (spm_hip_bam_pileup(b, nullptr, &p) != SPM_OK)
+                    hip::fatal("spm_hip_bam_pileup", ctx);
+                std::unique_ptr<spm_pileup, decltype(&spm_hip_pileup_destroy)> pileup_owner{p, &spm_hip_pileup_destroy};
+                std::uint32_t const * counts = nullptr;
+                std::uint64_t n = 0;
+                if (spm_hip_pileup_view(p, &counts, &n) != SPM_OK)
+                    hip::fatal("spm_hip_pileup_view", ctx);
+                req.bam_out->pileup.assign(counts, counts + SPM_PILEUP_PLANES * n);
             }
             spm_bgzf * index_of = nullptr; // the deflated file, where the index is the deflated file's
             auto const index = [&] {

@@ -1522,6 +1522,121 @@ int spm_hip_bam_markdup_records(spm_ctx *ctx, const void *device_records, uint64
 int spm_hip_bam_markdup_host(const void *records, uint64_t n_record_bytes, const spm_sam_line *lines, uint64_t n_lines,
                              uint64_t ref_len, const spm_bam_markdup_opts *opts /* NULL: defaults */, uint8_t *dup);
 
+/* ---- the per-base pileup of a coordinate-sorted BAM handle, and its variant sites (samtools depth / mpileup, the candidate
+ * step of a variant caller): the first consumer of the sorted, duplicate-marked stream ---------------------------------------
+ * spm_hip_bam_pileup counts, for every reference position of a region [begin, end), how many records show A, C, G, T, another
+ * symbol, a deletion, an insertion behind the position, or a base below the quality threshold: counts[plane * n + (pos -
+ * begin)], n = end - begin, uint32, plane-major, the planes in the order SPM_PILEUP_A .. SPM_PILEUP_LOWQ.  The handle form
+ * works on any spm_bam whose records are in coordinate order (an unsorted one is refused by the order test, not by a flag); on
+ * a handle out of spm_hip_bam_markdup the duplicates are left out by the default exclude_flags.  spm_hip_bam_pileup_records is
+ * the raw form over any device record stream and its spm_sam_line records (offset and len are read), spm_hip_bam_pileup_host
+ * the same counts by a serial walk on the host, no device needed.  The rule, a function of the stream, the line records
+ * (offset, len), ref_len, the region and the options alone:
+ *   * Which records take part: flag lacks 0x4, flag & exclude_flags == 0, mapq >= min_mapq, at least one CIGAR item.  Any
+ *     other record is skipped, not refused.
+ *   * The walk.  r = pos, q = 0; for each CIGAR item (op, len):
+ *       M = X (0 7 8)   for j < len, column r + j: the quality byte qual[q + j] below min_baseq adds 1 to LOWQ; otherwise the
+ *                       4-bit SEQ code at q + j adds 1 to its plane (1 A, 2 C, 4 G, 8 T, any other code N).  r += len, q += len.
+ *                       A quality of ff (absent) passes every threshold, as in htslib.
+ *       D (2)           1 to DEL at r .. r + len - 1; r += len.
+ *       N (3)           r += len; nothing is counted.
+ *       I (1)           1 to INS at column r - 1 if r > pos (a leading insertion is dropped); q += len.
+ *       S (4)           q += len.      H P (5 6)   nothing.
+ *     Only columns inside [begin, end) are counted.  A record's end is pos + max(span, 1), the BAI rule.
+ *   * Overlapping mates of a pair are counted twice, once per record, as samtools depth counts them.
+ *   * Depth is A + C + G + T + N + DEL.  INS and LOWQ are outside it.
+ * Worked table (ref_len 1000, refID 0, min_baseq 0, forward records; POS 0-based; qualities ff unless given):
+ *      0   10   4M           ACGT      A@10 C@11 G@12 T@13
+ *      1   10   2=1X1=       ACNT      A@10 C@11 N@12 T@13
+ *      2   11   2M2D2M       CGAA      C@11 G@12 DEL@13,14 A@15 A@16
+ *      3   12   2M3N2M       GTCC      G@12 T@13, nothing at 14..16, C@17 C@18
+ *      4   12   2I3M         TTGTA     the leading I is dropped: G@12 T@13 A@14
+ *      5   12   2S1I3M       AATGTA    S, then I with r == pos, dropped: G@12 T@13 A@14
+ *      6   13   2M2I2M       TAGGAC    T@13 A@14 INS@14 A@15 C@16
+ *      7   13   3M2S         TAACC     T@13 A@14 A@15
+ *      8   14   2H3M1P2M3H   AACAC     A@14 A@15 C@16 A@17 C@18
+ *      9   15   3M           ACG, qual 0 20 ff   A@15 C@16 G@17; min_baseq 1: LOWQ@15 C@16 G@17; min_baseq 93: LOWQ@15,16 G@17
+ *     10   15   3M flag 0x400   AAA    nothing by default; A@15,16,17 with exclude_flags 0x4
+ *     11   unplaced, flag 0x4          nothing
+ *   * SPM_E_INVALID, decided on the host before any launch: NULL arguments (opts may be NULL); nonzero flags or reserved
+ *     fields; min_baseq above 93; begin > end or end > ref_len (end 0: ref_len); buffers without counts or counts without
+ *     buffers.  SPM_E_UNSUPPORTED: more than 2^32 - 1 records; ref_len above 2^31.
+ *   * Counted on the device in one counter, each test before a value is used as an index, brought back in ONE read-back, and
+ *     failing the call with SPM_E_INVALID, nothing returned or written, never a fault: a line that leaves the stream; a
+ *     block_size that is not len - 4; a name, CIGAR, SEQ or QUAL that leaves the record; a record that takes part with a
+ *     refID other than 0, pos < 0 or end > ref_len, a CIGAR op code above 8, or a CIGAR query length that is not l_seq (SEQ *
+ *     beside a CIGAR, what a secondary line of spm_hip_jst_ref_loci_bam carries: leave 0x100 in exclude_flags); records
+ *     out of coordinate order (pos descending among the records of refID 0, or a record of refID 0 behind one of another
+ *     refID).  The order is a precondition, as it is for samtools mpileup and for spm_hip_bai_build; the host builder refuses
+ *     the same inputs.
+ *   * Zero records give all-zero counts, an empty region a view of length 0.
+ * A pure function of its inputs: integer adds commute, host and device agree byte for byte across runs; the result outlives b.
+ *
+ * spm_hip_pileup_sites compares a finished pileup with the resident reference (a dna4 spm_text of ranks, the handle
+ * spm_sam_extras.reference takes; shorter than the pileup's end, another sigma or another context: SPM_E_INVALID) and returns,
+ * in position order, the columns with depth >= min_depth, alt >= min_alt and 1000 * alt >= min_alt_permille * depth, where
+ * alt = depth - counts[plane of the reference base] + INS (a reference rank above 3 takes plane N).  A site's counts[4] are the
+ * four base planes A C G T: N + DEL is depth less their sum, and INS is alt - (depth - counts[ref]).  spm_hip_pileup_sites_host
+ * is the serial twin over host arrays: cap records at dst, *n the number of sites, SPM_E_OVERFLOW with *n set when cap is too small. */
+enum { SPM_PILEUP_A = 0, SPM_PILEUP_C, SPM_PILEUP_G, SPM_PILEUP_T, SPM_PILEUP_N, SPM_PILEUP_DEL, SPM_PILEUP_INS, SPM_PILEUP_LOWQ,
+       SPM_PILEUP_PLANES };
+typedef struct spm_pileup_opts {   /* 32 bytes */
+    uint64_t begin, end;           /* end 0: ref_len; begin <= end <= ref_len else SPM_E_INVALID */
+    uint32_t exclude_flags;        /* 0: 0x704 (UNMAP | SECONDARY | QCFAIL | DUP); 0x4 is always excluded */
+    uint8_t  min_mapq, min_baseq;  /* min_baseq above 93: SPM_E_INVALID */
+    uint16_t reserved0;            /* must be 0 */
+    uint32_t flags, reserved1;     /* must be 0 */
+} spm_pileup_opts;
+typedef struct spm_pileup_stats {  /* 88 bytes */
+    float ms_total;                /* device: the four stages below (HIP events) */
+    float ms_records;              /* every record read and tested, the order test, pos and end */
+    float ms_scan;                 /* the running maximum of end */
+    float ms_tiles;                /* one workgroup per tile: the counters in LDS, the plane segments stored */
+    float ms_summary;              /* n_covered, sum_depth, max_depth, n_evidence from the finished planes */
+    float ms_host;                 /* wall clock of the whole call */
+    uint32_t tile_positions;       /* positions per tile of this build (not part of the ABI's promises) */
+    uint32_t reserved;
+    uint64_t n_records;
+    uint64_t n_taking_part;
+    uint64_t n_evidence;           /* the sum of all planes */
+    uint64_t n_covered;            /* positions with depth > 0 */
+    uint64_t sum_depth;
+    uint64_t max_depth;
+    uint64_t n_tile_visits;        /* records walked by tiles, a record once per tile it reaches into: the scheme's redundancy */
+} spm_pileup_stats;
+typedef struct spm_pileup_site {   /* 32 bytes */
+    uint32_t pos;
+    uint32_t depth;
+    uint32_t alt;
+    uint32_t counts[4];            /* the base planes A C G T */
+    uint8_t ref;                   /* the reference rank at pos */
+    uint8_t reserved[3];
+} spm_pileup_site;
+typedef struct spm_pileup_site_opts { /* 16 bytes */
+    uint32_t min_depth, min_alt, min_alt_permille; /* NULL opts: 1, 2, 200 */
+    uint32_t flags;                /* must be 0 */
+} spm_pileup_site_opts;
+typedef struct spm_pileup spm_pileup;
+typedef struct spm_pileup_sites spm_pileup_sites;
+int spm_hip_bam_pileup(spm_bam *b, const spm_pileup_opts *opts /* NULL: defaults */, spm_pileup **out);
+int spm_hip_bam_pileup_records(spm_ctx *ctx, const void *device_records, uint64_t n_record_bytes, const void *device_lines,
+                               uint64_t n_lines, uint64_t ref_len, const spm_pileup_opts *opts /* NULL: defaults */, spm_pileup **out);
+/* counts: 8 * (end - begin) values, written only when the call succeeds */
+int spm_hip_bam_pileup_host(const void *records, uint64_t n_record_bytes, const spm_sam_line *lines, uint64_t n_lines,
+                            uint64_t ref_len, const spm_pileup_opts *opts /* NULL: defaults */, uint32_t *counts);
+/* the host view is downloaded when first asked for; n_positions = end - begin; every out pointer may be NULL */
+int spm_hip_pileup_view(spm_pileup *p, const uint32_t **counts, uint64_t *n_positions);
+int spm_hip_pileup_device(spm_pileup *p, const void **counts, uint64_t *n_positions);
+int spm_hip_pileup_stats(const spm_pileup *p, spm_pileup_stats *out);
+void spm_hip_pileup_destroy(spm_pileup *p);
+int spm_hip_pileup_sites(spm_pileup *p, const spm_text *reference, const spm_pileup_site_opts *opts /* NULL: defaults */,
+                         spm_pileup_sites **out);
+int spm_hip_pileup_sites_view(spm_pileup_sites *s, const spm_pileup_site **sites, uint64_t *n);
+int spm_hip_pileup_sites_device(spm_pileup_sites *s, const void **sites, uint64_t *n);
+void spm_hip_pileup_sites_destroy(spm_pileup_sites *s);
+int spm_hip_pileup_sites_host(const uint32_t *counts, uint64_t begin, uint64_t n_positions, const uint8_t *ref_ranks, uint64_t ref_len,
+                              const spm_pileup_site_opts *opts /* NULL: defaults */, spm_pileup_site *dst, uint64_t cap, uint64_t *n);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

@@ -338,6 +338,30 @@ class BamMarkdupStats(C.Structure):
                 ("n_dup_fragments", C.c_uint64), ("n_dup_records", C.c_uint64), ("n_fragments_beside_pairs", C.c_uint64)]
 
 
+class PileupOpts(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64), ("exclude_flags", C.c_uint32), ("min_mapq", C.c_uint8),
+                ("min_baseq", C.c_uint8), ("reserved0", C.c_uint16), ("flags", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
+class PileupStats(C.Structure):
+    _fields_ = [("ms_total", C.c_float), ("ms_records", C.c_float), ("ms_scan", C.c_float), ("ms_tiles", C.c_float),
+                ("ms_summary", C.c_float), ("ms_host", C.c_float), ("tile_positions", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_records", C.c_uint64), ("n_taking_part", C.c_uint64), ("n_evidence", C.c_uint64), ("n_covered", C.c_uint64),
+                ("sum_depth", C.c_uint64), ("max_depth", C.c_uint64), ("n_tile_visits", C.c_uint64)]
+
+
+class PileupSite(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("depth", C.c_uint32), ("alt", C.c_uint32), ("counts", C.c_uint32 * 4), ("ref", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+class PileupSiteOpts(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_alt_permille", C.c_uint32), ("flags", C.c_uint32)]
+
+
+PILEUP_PLANES = ("A", "C", "G", "T", "N", "DEL", "INS", "LOWQ")  # SPM_PILEUP_A .. SPM_PILEUP_LOWQ
+
+
 class BaiStats(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_records", C.c_float), ("ms_chunks", C.c_float), ("ms_bins", C.c_float),
                 ("ms_write", C.c_float), ("ms_host", C.c_float), ("n_bins", C.c_uint64), ("n_chunks", C.c_uint64),
@@ -597,6 +621,19 @@ SIGNATURES = {
     "spm_hip_bam_markdup_records": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(BamMarkdupOpts), _vp,
                                               C.POINTER(BamMarkdupStats)]),
     "spm_hip_bam_markdup_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(BamMarkdupOpts), _vp]),
+    "spm_hip_bam_pileup": (C.c_int, [_vp, C.POINTER(PileupOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_pileup_records": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(PileupOpts), C.POINTER(_vp)]),
+    "spm_hip_bam_pileup_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.POINTER(PileupOpts), _vp]),
+    "spm_hip_pileup_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_pileup_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_pileup_stats": (C.c_int, [_vp, C.POINTER(PileupStats)]),
+    "spm_hip_pileup_destroy": (None, [_vp]),
+    "spm_hip_pileup_sites": (C.c_int, [_vp, _vp, C.POINTER(PileupSiteOpts), C.POINTER(_vp)]),
+    "spm_hip_pileup_sites_view": (C.c_int, [_vp, C.POINTER(C.POINTER(PileupSite)), C.POINTER(C.c_uint64)]),
+    "spm_hip_pileup_sites_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_pileup_sites_destroy": (None, [_vp]),
+    "spm_hip_pileup_sites_host": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.POINTER(PileupSiteOpts), _vp, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]),
     "spm_hip_jst_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),

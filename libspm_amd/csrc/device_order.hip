@@ -1,5 +1,6 @@
 // device_order.hip -- the radix sort of device_order.hpp, instantiated once for the library: (64-bit key, 32-bit index) pairs.
-// Every driver that orders records calls these two; no other unit names hipcub's sort.
+// Every driver that orders records calls these two; no other unit names hipcub's sort.  Beside it the two scans over 32-bit
+// values that the pileup takes (bam_pileup.hpp): the running maximum and the exclusive sum.
 #include "internal.hpp"
 #include "device_order.hpp"
 
@@ -20,6 +21,26 @@ hipError_t sort_pairs(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const unsigned 
 {
     return hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, (int)key_bits,
                                               ctx->stream);
+}
+
+hipError_t scan_u32_tmp_bytes(spm_ctx *ctx, size_t n, size_t *tmp_bytes)
+{
+    size_t a = 0, b = 0;
+    hipError_t e = hipcub::DeviceScan::InclusiveScan(nullptr, a, (const uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), n, ctx->stream);
+    if (e == hipSuccess)
+        e = hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, n, ctx->stream);
+    *tmp_bytes = a > b ? a : b;
+    return e;
+}
+
+hipError_t inclusive_max_u32(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n)
+{
+    return hipcub::DeviceScan::InclusiveScan(tmp, tmp_bytes, in, out, hipcub::Max(), n, ctx->stream);
+}
+
+hipError_t exclusive_sum_u32(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n)
+{
+    return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, in, out, n, ctx->stream);
 }
 
 } // namespace spm_hip

@@ -4,6 +4,7 @@
 //   the launch of a one-lane-per-item kernel on the context's stream,
 //   the radix sort of (64-bit key, 32-bit index) pairs over the key's low bits: declared here, compiled once in
 //   device_order.hip (hipcub's sort is 234 kernels; defined inline here, every unit that included this header compiled them),
+//   the running maximum and the exclusive sum over 32-bit values, compiled there too (bam_pileup.hpp),
 //   the hipcub exclusive sum over any input iterator,
 //   the read-back of a call's counts,
 //   the events a call times its stages with,
@@ -37,6 +38,11 @@ hipError_t launch_1d(spm_ctx *ctx, void (*kernel)(Params...), uint64_t n_items, 
 hipError_t sort_pairs_tmp_bytes(spm_ctx *ctx, size_t n, uint32_t key_bits, size_t *tmp_bytes);
 hipError_t sort_pairs(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
                       const uint32_t *idx_in, uint32_t *idx_out, size_t n, uint32_t key_bits);
+// ---- two scans over n 32-bit values, compiled once in device_order.hip: the inclusive running maximum and the exclusive sum;
+// in and out may be the same array.  One temporary size serves both ----
+hipError_t scan_u32_tmp_bytes(spm_ctx *ctx, size_t n, size_t *tmp_bytes);
+hipError_t inclusive_max_u32(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n);
+hipError_t exclusive_sum_u32(spm_ctx *ctx, void *tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, size_t n);
 #pragma GCC visibility pop
 
 // ---- the exclusive sum of n items of `in` into out[0..n) ----

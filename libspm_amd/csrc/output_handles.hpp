@@ -4,6 +4,7 @@
 //              bam_markdup.hpp (markdup)            (sort, index), bam_markdup.hpp and bgzf.hip (spm_hip_bam_deflate)
 //   spm_bgzf   bgzf.hip                             framed or deflated blocks and their offsets; read by bam_index.hpp (index)
 //   spm_bai    bam_index.hpp                        the bytes of a BAI index
+//   spm_pileup, spm_pileup_sites   bam_pileup.hpp   the eight count planes of a region; the site records compacted from them
 // Behind them: the lazy download of a handle's host view, the synchronise-and-free of its device buffers, the copy-out of
 // optional out-parameters and of a stats struct; the BAM file around a record stream that spm_hip_jst_ref_loci_bam,
 // spm_hip_bam_sort and spm_hip_bam_markdup make; the refusal both BGZF calls and the BAM call word alike.  Host code only: no kernel, no C-ABI
@@ -88,6 +89,26 @@ struct spm_bai
     spm_bai_stats stats{};
 };
 static_assert(sizeof(spm_bai_stats) == 80, "spm_hip.h states this size");
+
+struct spm_pileup
+{
+    spm_ctx *ctx = nullptr;
+    uint32_t *d = nullptr; // [8 * n] plane-major
+    uint64_t begin = 0, n = 0;
+    bool have_host = false; // the view is downloaded when first asked for
+    std::vector<uint32_t> host;
+    spm_pileup_stats stats{};
+};
+struct spm_pileup_sites
+{
+    spm_ctx *ctx = nullptr;
+    spm_pileup_site *d = nullptr; // [n]
+    uint64_t n = 0;
+    bool have_host = false; // the view is downloaded when first asked for
+    std::vector<spm_pileup_site> host;
+};
+static_assert(sizeof(spm_pileup_opts) == 32 && sizeof(spm_pileup_stats) == 88, "spm_hip.h states these sizes");
+static_assert(sizeof(spm_pileup_site) == 32 && sizeof(spm_pileup_site_opts) == 16, "spm_hip.h states these sizes");
 
 #pragma GCC visibility push(hidden) // (inline code of the library's own units, not part of its surface)
 namespace spm_hip

@@ -29,6 +29,8 @@ JST_READ_DTYPE = _dtype(capi.JstRead)
 JST_PAIR_DTYPE = _dtype(capi.JstPair)
 JST_RESCUE_DTYPE = _dtype(capi.JstRescue)
 SAM_LINE_DTYPE = _dtype(capi.SamLine)
+PILEUP_SITE_DTYPE = _dtype(capi.PileupSite)
+PILEUP_PLANES = capi.PILEUP_PLANES
 _CIGAR_CHAR = {capi.CIGAR_INS: "I", capi.CIGAR_DEL: "D", capi.CIGAR_EQ: "=", capi.CIGAR_X: "X"}
 
 
@@ -203,6 +205,16 @@ class Context:
         _check(capi.lib().spm_hip_bam_markdup_records(self._h, C.c_void_p(records), int(n_record_bytes), C.c_void_p(lines), int(n_lines),
                                                       int(ref_len), C.byref(opts), C.c_void_p(dup_ptr), C.byref(stats)), self._h)
         return stats
+
+    def bam_pileup(self, records: int, n_record_bytes: int, lines: int, n_lines: int, ref_len: int, begin: int = 0, end=None,
+                   min_mapq: int = 0, min_baseq: int = 0, exclude_flags=None) -> "Pileup":
+        """The pileup of a coordinate-sorted record stream in device memory (spm_hip_bam_pileup_records), the raw form of
+        Bam.pileup(): records / lines are device pointers to the uncompressed stream and its SAM_LINE_DTYPE records (offset and len
+        are read).  The other arguments are Bam.pileup's."""
+        opts, h = pileup_opts(begin, end, min_mapq, min_baseq, exclude_flags), C.c_void_p()
+        _check(capi.lib().spm_hip_bam_pileup_records(self._h, C.c_void_p(records), int(n_record_bytes), C.c_void_p(lines), int(n_lines),
+                                                     int(ref_len), C.byref(opts), C.byref(h)), self._h)
+        return Pileup(self, h, int(begin))
 
     def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
@@ -1028,6 +1040,100 @@ def bam_markdup_host(records, lines, ref_len: int, min_qual: int = 0) -> np.ndar
     return dup
 
 
+def pileup_opts(begin: int = 0, end=None, min_mapq: int = 0, min_baseq: int = 0, exclude_flags=None) -> capi.PileupOpts:
+    """end None (or 0): the reference's length; exclude_flags None (or 0): 0x704, and 0x4 is always excluded"""
+    return capi.PileupOpts(begin=int(begin), end=int(end or 0), exclude_flags=int(exclude_flags or 0), min_mapq=int(min_mapq),
+                           min_baseq=int(min_baseq), reserved0=0, flags=0, reserved1=0)
+
+
+def pileup_site_opts(min_depth: int = 1, min_alt: int = 2, min_alt_permille: int = 200) -> capi.PileupSiteOpts:
+    return capi.PileupSiteOpts(min_depth=int(min_depth), min_alt=int(min_alt), min_alt_permille=int(min_alt_permille), flags=0)
+
+
+def bam_pileup_host(records, lines, ref_len: int, begin: int = 0, end=None, min_mapq: int = 0, min_baseq: int = 0,
+                    exclude_flags=None) -> np.ndarray:
+    """The (8, end - begin) uint32 counts of a coordinate-sorted record stream by the serial host builder
+    (spm_hip_bam_pileup_host), the planes in the order PILEUP_PLANES: records the uncompressed stream, lines its SAM_LINE_DTYPE
+    records.  Needs no device."""
+    records = bytes(records)
+    lines = np.ascontiguousarray(lines, dtype=SAM_LINE_DTYPE)
+    src = C.create_string_buffer(records, len(records) + 1)
+    opts = pileup_opts(begin, end, min_mapq, min_baseq, exclude_flags)
+    n = max((int(end) if end else int(ref_len)) - int(begin), 0)
+    counts = np.zeros((len(PILEUP_PLANES), n), dtype=np.uint32)
+    _check(capi.lib().spm_hip_bam_pileup_host(src, len(records), lines.ctypes.data, len(lines), int(ref_len), C.byref(opts),
+                                              counts.ctypes.data), None)
+    return counts
+
+
+def pileup_sites_host(counts, begin: int, ref_ranks, min_depth: int = 1, min_alt: int = 2, min_alt_permille: int = 200) -> np.ndarray:
+    """The PILEUP_SITE_DTYPE records of an (8, n) pileup that begins at `begin`, against the ranks of the whole reference, by the
+    serial host builder (spm_hip_pileup_sites_host).  Needs no device."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    ref = np.ascontiguousarray(ref_ranks, dtype=np.uint8)
+    assert counts.ndim == 2 and counts.shape[0] == len(PILEUP_PLANES)
+    n = counts.shape[1]
+    opts, need = pileup_site_opts(min_depth, min_alt, min_alt_permille), C.c_uint64()
+    out = np.zeros(n, dtype=PILEUP_SITE_DTYPE)
+    _check(capi.lib().spm_hip_pileup_sites_host(counts.ctypes.data, int(begin), n, ref.ctypes.data, len(ref), C.byref(opts),
+                                                out.ctypes.data, n, C.byref(need)), None)
+    return out[:need.value].copy()
+
+
+class Pileup(_Handle):
+    """Result of Bam.pileup() and Context.bam_pileup(): the eight count planes of a region in device memory, plane-major.  (Made by
+    those two calls only, so the package does not export the name; it is libspm_amd.engine.Pileup.)"""
+    _PREFIX = "pileup"
+
+    def __init__(self, ctx, h, begin: int = 0):
+        super().__init__(ctx, h)
+        self.begin = begin
+
+    def __len__(self):
+        return self.device()[1]
+
+    def counts(self) -> np.ndarray:
+        """(8, n) uint32, the planes in the order PILEUP_PLANES; column j is reference position begin + j"""
+        p, n = self._span("view")
+        if n == 0:
+            return np.zeros((len(PILEUP_PLANES), 0), dtype=np.uint32)
+        buf = (C.c_uint32 * (len(PILEUP_PLANES) * n)).from_address(p)
+        return np.frombuffer(buf, dtype=np.uint32).reshape(len(PILEUP_PLANES), n).copy()
+
+    def depth(self) -> np.ndarray:
+        """A + C + G + T + N + DEL per position"""
+        return self.counts()[:6].sum(axis=0, dtype=np.uint32)
+
+    def device(self):
+        """(counts, n_positions): device pointer and count"""
+        return self._span("device")
+
+    def stats(self) -> capi.PileupStats:
+        return self._stats(capi.PileupStats)
+
+    def sites(self, reference: "Text", min_depth: int = 1, min_alt: int = 2, min_alt_permille: int = 200) -> np.ndarray:
+        """The columns that depart from the resident reference (spm_hip_pileup_sites; the rule is in spm_hip.h), in position
+        order, as PILEUP_SITE_DTYPE records.  reference: the dna4 Text of ranks that sam_extras takes."""
+        opts = pileup_site_opts(min_depth, min_alt, min_alt_permille)
+        s = _PileupSites(self.ctx, self._new("sites", reference._h, C.byref(opts)))
+        try:
+            return s.view()
+        finally:
+            s.close()
+
+
+class _PileupSites(_Handle):
+    _PREFIX = "pileup_sites"
+
+    def view(self) -> np.ndarray:
+        rec, n = C.POINTER(capi.PileupSite)(), C.c_uint64()
+        self._call("view", C.byref(rec), C.byref(n))
+        return _as_array(rec, n.value, capi.PileupSite, PILEUP_SITE_DTYPE)
+
+    def device(self):
+        return self._span("device")
+
+
 class Bam(_Handle):
     """Result of JstRefLoci.bam(): the file, the uncompressed record stream and one SAM_LINE_DTYPE record per BAM record
     (offset / len: the record in the stream), in record order."""
@@ -1091,6 +1197,14 @@ class Bam(_Handle):
     def markdup_stats(self) -> capi.BamMarkdupStats:
         """the stage times and counts of the markdup() that made this object"""
         return self._stats(capi.BamMarkdupStats, "markdup_stats")
+
+    def pileup(self, begin: int = 0, end=None, min_mapq: int = 0, min_baseq: int = 0, exclude_flags=None) -> "Pileup":
+        """The per-base pileup of this coordinate-sorted object over [begin, end) (spm_hip_bam_pileup; the rule is in spm_hip.h):
+        how many records show A, C, G, T, another symbol, a deletion, an insertion behind the position or a base below
+        min_baseq.  end None: the reference's length.  exclude_flags None: 0x704, so the duplicates markdup() marked stay out;
+        0x4 is always excluded.  Records with a MAPQ below min_mapq stay out.  An unsorted object is refused."""
+        opts = pileup_opts(begin, end, min_mapq, min_baseq, exclude_flags)
+        return Pileup(self.ctx, self._new("pileup", C.byref(opts)), int(begin))
 
     def index(self, deflated: "Bgzf | None" = None) -> "Bai":
         """The BAI index of this coordinate-sorted file (spm_hip_bam_index), or, with deflated = self.deflate(block_data) in
