@@ -180,6 +180,18 @@ struct jst_sam_pairing
     std::uint32_t k{0};
 };
 
+// one genotyped site of jst_bam::calls: spm_variant_call of spm_hip.h, field for field
+struct jst_variant_call
+{
+    std::uint32_t pos, depth, qual, len;
+    std::uint64_t offset;
+    std::uint8_t status, gq;
+    std::array<std::uint8_t, 2> gt;
+    std::uint8_t n_alt;
+    std::array<std::uint8_t, 2> alt;
+    bool operator==(jst_variant_call const &) const noexcept = default;
+};
+
 // A BAM file of a mapping (journaled_sequence_tree::map_bam; spm_hip_jst_ref_loci_bam in spm_hip.h): the complete file (header
 // section, record blocks, EOF block), the uncompressed record stream, and one record per BAM record as for map_sam, whose
 // offset / len locate it in that stream
@@ -196,6 +208,10 @@ struct jst_bam_options
                                         // (spm_hip_bam_markdup / spm_hip_bam_markdup_host; default min_qual)
     bool pileup{false};                 // with sort: jst_bam::pileup, the per-base counts of the file over the whole reference, behind
                                         // mark_duplicates (spm_hip_bam_pileup / spm_hip_bam_pileup_host; default options)
+    bool call_variants{false};          // with pileup: jst_bam::vcf and jst_bam::calls, the sites of that pileup against the tree's
+                                        // reference genotyped (spm_hip_pileup_sites, spm_hip_pileup_sites_vcf / the host twins; default
+                                        // options, CHROM sam.rname, the sample column `sample`)
+    std::string sample{"sample"};
 };
 
 struct jst_bam
@@ -206,6 +222,8 @@ struct jst_bam
     std::vector<std::uint64_t> block_offsets; // with jst_bam_options::deflate only: the file offset of every record block, then their end
     std::string bai;                    // with jst_bam_options::index: the bytes of the file's .bai
     std::vector<std::uint32_t> pileup;  // with jst_bam_options::pileup: 8 planes (SPM_PILEUP_A ..) x ref_len counts, plane-major
+    std::string vcf;                    // with jst_bam_options::call_variants: the VCF file of the pileup's sites
+    std::vector<jst_variant_call> calls; // ... and one call record per site
     bool operator==(jst_bam const &) const noexcept = default;
     // the BGZF virtual file offset of record i
     std::uint64_t virtual_offset(std::size_t i, std::uint32_t block_data = 0) const
@@ -1033,6 +1051,8 @@ public:
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
         if (options.pileup && !options.sort)
             hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", hip::default_context());
+        if (options.call_variants && !options.pileup)
+            hip::fatal("journaled_sequence_tree::map_bam (call_variants without pileup: the calls are made from a pileup's sites)", hip::default_context());
         if (device_ready())
             return map_bam_device(needles, window, strands, n_reads, pairing, options, selection, block, stats);
         return map_bam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options, selection, block, stats);
@@ -1048,6 +1068,8 @@ public:
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", hip::default_context());
         if (options.pileup && !options.sort)
             hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", hip::default_context());
+        if (options.call_variants && !options.pileup)
+            hip::fatal("journaled_sequence_tree::map_bam (call_variants without pileup: the calls are made from a pileup's sites)", hip::default_context());
         jst_bam out;
         std::vector<jst_read> reads;
         std::vector<jst_pair> pairs;
@@ -1070,13 +1092,14 @@ public:
     {
         return bam_of_sam(map_sam_host(needles, window, needle_ranks, reports_begin, strands, n_reads, pairing, options.sam, selection,
                                        block, stats),
-                          options);
+                          options, &_reference);
     }
 
     // SAM lines to a BAM file, from the text alone and the SAM specification (section 4.2): every field parsed back out of its
     // line.  Tags are written as the contract of spm_hip.h types them: NM XH XR int32, XN X0 X1 uint32, a Z tag (MD) as its
     // string and a NUL.  QUAL "*" is absent (ff), any other is its values.
-    static jst_bam bam_of_sam(jst_sam const & sam, jst_bam_options const & o)
+    // reference: the tree's reference ranks, read with jst_bam_options::call_variants alone.
+    static jst_bam bam_of_sam(jst_sam const & sam, jst_bam_options const & o, std::vector<std::uint8_t> const * reference = nullptr)
     {
         spm_ctx const * const ctx = nullptr; // (no device is needed: the host-only calls leave their message without a context)
         auto const put = [](std::string & to, std::uint64_t v, int bytes) {
@@ -1097,6 +1120,8 @@ public:
             hip::fatal("journaled_sequence_tree::map_bam (index without sort: an index needs a coordinate-sorted file)", ctx);
         if (o.pileup && !o.sort)
             hip::fatal("journaled_sequence_tree::map_bam (pileup without sort: a pileup needs a coordinate-sorted file)", ctx);
+        if (o.call_variants && !o.pileup)
+            hip::fatal("journaled_sequence_tree::map_bam (call_variants without pileup: the calls are made from a pileup's sites)", ctx);
         jst_bam out;
         // the records in read order, and what coordinate order looks at: without a position or not, POS, the reverse strand
         struct converted
@@ -1222,6 +1247,40 @@ public:
             if (spm_hip_bam_pileup_host(out.records.data(), out.records.size(), lines.data(), lines.size(), o.ref_len, nullptr,
                                         out.pileup.data()) != SPM_OK)
                 hip::fatal("spm_hip_bam_pileup_host", ctx);
+        }
+        if (o.call_variants) { // the host twins over the counts just made: sites, then calls and text
+            if (reference == nullptr || reference->size() < o.ref_len)
+                hip::fatal("journaled_sequence_tree::map_bam (call_variants: no reference of ref_len ranks)", ctx);
+            std::uint64_t n_sites = 0, n_text = 0;
+            int const sized = spm_hip_pileup_sites_host(out.pileup.data(), 0, o.ref_len, reference->data(), reference->size(), nullptr, nullptr,
+                                                        0, &n_sites); // (how many: SPM_E_OVERFLOW unless there is none)
+            std::vector<spm_pileup_site> sites(n_sites);
+            if ((sized != SPM_OK && sized != SPM_E_OVERFLOW) ||
+                spm_hip_pileup_sites_host(out.pileup.data(), 0, o.ref_len, reference->data(), reference->size(), nullptr, sites.data(),
+                                          sites.size(), &n_sites) != SPM_OK)
+                hip::fatal("spm_hip_pileup_sites_host", ctx);
+            std::vector<spm_variant_call> calls(n_sites);
+            if (spm_hip_pileup_sites_calls_host(sites.data(), n_sites, nullptr, calls.data()) != SPM_OK)
+                hip::fatal("spm_hip_pileup_sites_calls_host", ctx);
+            if (spm_hip_pileup_sites_vcf_host(sites.data(), n_sites, o.sam.rname.c_str(), o.sample.c_str(), o.ref_len, nullptr, nullptr, 0,
+                                              &n_text) != SPM_E_OVERFLOW)
+                hip::fatal("spm_hip_pileup_sites_vcf_host", ctx);
+            out.vcf.assign(n_text, '\0');
+            if (spm_hip_pileup_sites_vcf_host(sites.data(), n_sites, o.sam.rname.c_str(), o.sample.c_str(), o.ref_len, nullptr, out.vcf.data(),
+                                              n_text, &n_text) != SPM_OK)
+                hip::fatal("spm_hip_pileup_sites_vcf_host", ctx);
+            // the host twin of the calls knows no text: offset and len are those of the lines, in site order behind the header
+            std::uint64_t header = 0;
+            if (spm_hip_vcf_header(o.sam.rname.c_str(), o.sample.c_str(), o.ref_len, nullptr, 0, &header) != SPM_E_OVERFLOW)
+                hip::fatal("spm_hip_vcf_header", ctx);
+            std::uint64_t at = header;
+            for (spm_variant_call & c : calls) {
+                std::uint64_t const end = c.status == SPM_CALL_VARIANT ? out.vcf.find('\n', at) + 1 : at;
+                c.offset = at;
+                c.len = static_cast<std::uint32_t>(end - at);
+                at = end;
+            }
+            calls_of(calls.data(), calls.size(), out.calls);
         }
         // the header: BAM\1, l_text, the SAM header, one reference; framed on its own, then the records and the EOF block
         std::uint64_t n_text = 0;
@@ -1892,6 +1951,15 @@ private:
     };
 
     // what loci_of needs for the SAM lines behind everything else it was asked for: the options, the needles, where the answer goes
+    static void calls_of(spm_variant_call const * calls, std::uint64_t n, std::vector<jst_variant_call> & out)
+    {
+        out.clear();
+        for (std::uint64_t i = 0; i < n; ++i) {
+            spm_variant_call const & c = calls[i];
+            out.push_back(jst_variant_call{c.pos, c.depth, c.qual, c.len, c.offset, c.status, c.gq, {c.gt[0], c.gt[1]}, c.n_alt, {c.alt[0], c.alt[1]}});
+        }
+    }
+
     struct sam_request
     {
         jst_sam_options const * options;
@@ -1964,6 +2032,25 @@ private:
                 if (spm_hip_pileup_view(p, &counts, &n) != SPM_OK)
                     hip::fatal("spm_hip_pileup_view", ctx);
                 req.bam_out->pileup.assign(counts, counts + SPM_PILEUP_PLANES * n);
+                req.bam_out->vcf.clear();
+                req.bam_out->calls.clear();
+                if (req.bam_options->call_variants) { // the sites of these counts against the resident reference, genotyped on the device
+                    spm_pileup_sites * sites = nullptr;
+                    if (spm_hip_pileup_sites(p, req.reference, nullptr, &sites) != SPM_OK)
+                        hip::fatal("spm_hip_pileup_sites", ctx);
+                    std::unique_ptr<spm_pileup_sites, decltype(&spm_hip_pileup_sites_destroy)> sites_owner{sites, &spm_hip_pileup_sites_destroy};
+                    spm_vcf * v = nullptr;
+                    if (spm_hip_pileup_sites_vcf(sites, o.rname.c_str(), req.bam_options->sample.c_str(), req.bam_options->ref_len, nullptr, &v) != SPM_OK)
+                        hip::fatal("spm_hip_pileup_sites_vcf", ctx);
+                    std::unique_ptr<spm_vcf, decltype(&spm_hip_vcf_destroy)> vcf_owner{v, &spm_hip_vcf_destroy};
+                    char const * text = nullptr;
+                    spm_variant_call const * calls = nullptr;
+                    std::uint64_t n_bytes = 0, n_calls = 0;
+                    if (spm_hip_vcf_view(v, &text, &n_bytes, &calls, &n_calls) != SPM_OK)
+                        hip::fatal("spm_hip_vcf_view", ctx);
+                    req.bam_out->vcf.assign(text, n_bytes);
+                    calls_of(calls, n_calls, req.bam_out->calls);
+                }
             }
             spm_bgzf * index_of = nullptr; // the deflated file, where the index is the deflated file's
             auto const index = [&] {

@@ -1637,6 +1637,119 @@ void spm_hip_pileup_sites_destroy(spm_pileup_sites *s);
 int spm_hip_pileup_sites_host(const uint32_t *counts, uint64_t begin, uint64_t n_positions, const uint8_t *ref_ranks, uint64_t ref_len,
                               const spm_pileup_site_opts *opts /* NULL: defaults */, spm_pileup_site *dst, uint64_t cap, uint64_t *n);
 
+/* ---- genotype calls for pileup sites and the VCF text of the variant ones (one sample, SNV alleles): the end of the chain ----
+ * spm_hip_pileup_sites_vcf genotypes every site record of a spm_pileup_sites handle and writes, on the device, a complete VCF
+ * file: the header of spm_hip_vcf_header, then one line per site whose best genotype is not ref/ref, in site order.
+ * spm_hip_pileup_sites_vcf_records is the raw form over any device array of spm_pileup_site records; the two host twins give the
+ * same call records and the same bytes by a serial loop, no device needed.  The rule is integer arithmetic throughout (its
+ * functions are in libspm_amd/csrc/pileup_vcf_core.hpp, one source for host and device), so both sides agree byte for byte:
+ *   * Options (spm_vcf_opts; NULL: the defaults).  ploidy 1 or 2 (0: 2).  cost_match, cost_het, cost_miss: what one read base
+ *     costs, in milli-Phred (1/1000 of -10 log10), when it agrees with a homozygous genotype, with one allele of a heterozygous
+ *     one, with no allele; all three 0: 44, 3039, 24771, which are round(-10000 log10 p) for p = 1 - e, (1 - e) / 2 + e / 6 and
+ *     e / 3 at e = 0.01.  prior_het, prior_hom_alt, milli-Phred, both 0: 30000 and 33010 (theta = 1e-3 and theta / 2): ref/ref
+ *     pays nothing, ref/alt prior_het, alt/alt prior_hom_alt, alt1/alt2 2 * prior_het; with ploidy 1 a non-reference genotype
+ *     pays prior_hom_alt.  min_qual, Phred: FILTER is PASS at or above it, LowQual below (NULL opts: 20; with opts the value as
+ *     given, so 0 passes every line).  A cost or prior above 1 000 000, a ploidy above 2, nonzero flags or reserved fields:
+ *     SPM_E_INVALID.
+ *   * A site whose ref rank is above 3 gets no call: status SPM_CALL_REF_N, no line.
+ *   * The alleles are the ranks A C G T; a genotype is a pair a <= b (10 of them; with ploidy 1 the 4 with a == b).  In uint64
+ *       cost(g) = sum over x of counts[x] * c(x, g) + prior(g),   c = cost_match if a == b == x, cost_het if a != b and x is a or b,
+ *     cost_miss otherwise.  Only counts[4] and ref are read of the evidence: N, DEL and INS take no part.  Counts up to 2^32 - 1
+ *     do not overflow.
+ *   * The best genotype has the least cost; ties go to the one that comes first in VCF genotype order (0,0) (0,1) (1,1) (0,2)
+ *     (1,2) (2,2) (0,3) ... over (the reference rank, then the other ranks ascending).
+ *   * Best is ref/ref: status SPM_CALL_REF, a record and no line.  Otherwise SPM_CALL_VARIANT: ALT lists the non-reference
+ *     alleles of the best genotype by ascending rank (one or two), GT indexes into REF, ALT.
+ *   * PL, over the kept alleles in VCF genotype order F(j, k) = k (k + 1) / 2 + j: min((cost(g) - cost(best) + 500) / 1000,
+ *     2^31 - 1); 3 or 6 values with ploidy 2, 2 with ploidy 1.  QUAL is the PL of ref/ref, GQ = min(99, second-smallest PL), AD
+ *     the counts of the kept alleles, DP the site's depth.
+ *   * The line, tabs between the fields and one \n behind:
+ *       CHROM POS . REF ALT QUAL FILTER DP=<depth> GT:AD:GQ:PL <gt>:<ad,..>:<gq>:<pl,..>
+ *     POS is 1-based, the separator inside GT is '/'.
+ * Worked table (reference A, defaults, ploidy 2):
+ *     counts A,C,G,T   depth   tail of the line
+ *     10,10,0,0        20      A C 157 PASS DP=20 GT:AD:GQ:PL 0/1:10,10:99:157,0,190
+ *     0,0,3,0          3       A G 41 PASS DP=3 GT:AD:GQ:PL 1/1:0,3:6:41,6,0
+ *     0,8,0,8          16      A C,T 288 PASS DP=16 GT:AD:GQ:PL 1/2:0,8,8:99:288,144,123,144,0,123
+ *     19,1,0,0         20      no line: ref/ref wins (25607 against 90780 for A/C)
+ *   The first row: AA = 10 * 44 + 10 * 24771 = 248150, AC = 20 * 3039 + 30000 = 90780, CC = 248150 + 33010 = 281160; the
+ *   differences 157370 and 190380 give the PLs 157 and 190.
+ * The header (spm_hip_vcf_header, host only; *len / SPM_E_OVERFLOW as spm_hip_sam_header has them; rname under that call's rule,
+ * sample 1 .. 254 bytes of '!' .. '~'), these bytes, \t a tab, every line ended by \n:
+ *     ##fileformat=VCFv4.2
+ *     ##contig=<ID=<rname>,length=<ref_len>>
+ *     ##FILTER=<ID=LowQual,Description="QUAL below the threshold">
+ *     ##INFO=<ID=DP,Number=1,Type=Integer,Description="Depth: A + C + G + T + N + DEL">
+ *     ##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">
+ *     ##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Base counts of the REF and ALT alleles">
+ *     ##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality">
+ *     ##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype costs">
+ *     #CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t<sample>
+ * The handle has two views, each on the host (downloaded when first asked for) and on the device: the text, and one 32-byte
+ * spm_variant_call per site (offset and len: the site's line in the text; len 0 where there is none, offset then where the next
+ * line starts).  Refused with SPM_E_INVALID and a message, nothing returned: NULL arguments (opts may be NULL; sites may be NULL
+ * with n_sites 0), what the options list above, a bad rname or sample, and -- counted on the device in the pass that makes the
+ * calls and read back once -- sites whose pos is not strictly ascending or reaches ref_len.  SPM_E_UNSUPPORTED: more than
+ * 2^32 - 1 sites, a ref_len above 2^32 - 1 (a site's pos is 32 bits), or, on the device, a text of 2^32 bytes or more (its
+ * line offsets are 32 bits).  Zero sites give the header
+ * alone.  Out of scope: indel alleles (the pileup keeps no inserted sequence), several samples, a tabix index, BCF, per-base
+ * quality likelihoods (a site has counts only), overlap resolution of mates. */
+enum { SPM_CALL_REF = 0, SPM_CALL_VARIANT = 1, SPM_CALL_REF_N = 2 };
+typedef struct spm_vcf_opts {      /* 40 bytes */
+    uint32_t ploidy;               /* 1 or 2; 0: 2 */
+    uint32_t cost_match, cost_het, cost_miss; /* all 0: 44, 3039, 24771 */
+    uint32_t prior_het, prior_hom_alt;        /* both 0: 30000, 33010 */
+    uint32_t min_qual;             /* as given; NULL opts: 20 */
+    uint32_t flags;                /* must be 0 */
+    uint32_t reserved0, reserved1; /* must be 0 */
+} spm_vcf_opts;
+typedef struct spm_variant_call {  /* 32 bytes */
+    uint32_t pos;                  /* 0-based, the site's */
+    uint32_t depth;                /* the site's: DP */
+    uint32_t qual;                 /* the PL of ref/ref; 0 without a call */
+    uint32_t len;                  /* bytes of the line; 0: the site has none */
+    uint64_t offset;               /* of the line in the text, the header included */
+    uint8_t status;                /* SPM_CALL_REF, SPM_CALL_VARIANT, SPM_CALL_REF_N */
+    uint8_t gq;                    /* 0 where the site has no line */
+    uint8_t gt[2];                /* the best genotype as allele ranks, gt[0] <= gt[1]; ploidy 1: both the same */
+    uint8_t n_alt;                 /* 0 .. 2 */
+    uint8_t alt[2];                /* the ALT ranks, ascending; 0 where unused */
+    uint8_t reserved;
+} spm_variant_call;
+typedef struct spm_vcf_stats {     /* 80 bytes */
+    float ms_total;                /* device: the three stages below (HIP events) */
+    float ms_call;                 /* every site genotyped: call record, line length, order test, counters */
+    float ms_scan;                 /* the exclusive sum of the line lengths */
+    float ms_write;                /* the lines formatted in LDS and stored, the header copied in front */
+    float ms_host;                 /* wall clock of the whole call */
+    uint32_t group_sites;          /* sites per workgroup of the write stage of this build (not part of the ABI's promises) */
+    uint64_t n_sites;
+    uint64_t n_variant;            /* lines */
+    uint64_t n_ref;                /* best genotype ref/ref */
+    uint64_t n_ref_n;              /* reference rank above 3: no call */
+    uint64_t n_low_qual;           /* lines with FILTER LowQual */
+    uint64_t n_header_bytes;
+    uint64_t n_text_bytes;         /* header and lines */
+} spm_vcf_stats;
+typedef struct spm_vcf spm_vcf;
+int spm_hip_pileup_sites_vcf(spm_pileup_sites *s, const char *rname, const char *sample, uint64_t ref_len,
+                             const spm_vcf_opts *opts /* NULL: defaults */, spm_vcf **out);
+int spm_hip_pileup_sites_vcf_records(spm_ctx *ctx, const void *device_sites, uint64_t n_sites, const char *rname, const char *sample,
+                                     uint64_t ref_len, const spm_vcf_opts *opts /* NULL: defaults */, spm_vcf **out);
+/* the host views are downloaded when first asked for; every out pointer may be NULL */
+int spm_hip_vcf_view(spm_vcf *v, const char **text, uint64_t *n_bytes, const spm_variant_call **calls, uint64_t *n_calls);
+int spm_hip_vcf_device(spm_vcf *v, const void **text, uint64_t *n_bytes, const void **calls, uint64_t *n_calls);
+int spm_hip_vcf_stats(const spm_vcf *v, spm_vcf_stats *out);
+void spm_hip_vcf_destroy(spm_vcf *v);
+/* calls: n records, written only when the call succeeds; offset and len stay 0, they belong to a text and this call makes
+ * none.  Sites whose pos is not strictly ascending: SPM_E_INVALID */
+int spm_hip_pileup_sites_calls_host(const spm_pileup_site *sites, uint64_t n, const spm_vcf_opts *opts /* NULL: defaults */,
+                                    spm_variant_call *calls);
+/* the whole file into dst: *len its length, SPM_E_OVERFLOW with *len set when cap is too small */
+int spm_hip_pileup_sites_vcf_host(const spm_pileup_site *sites, uint64_t n, const char *rname, const char *sample, uint64_t ref_len,
+                                  const spm_vcf_opts *opts /* NULL: defaults */, char *dst, uint64_t cap, uint64_t *len);
+int spm_hip_vcf_header(const char *rname, const char *sample, uint64_t ref_len, char *buf, uint64_t cap, uint64_t *len);
+
 /* ---- projected alignments with every indel at its leftmost equivalent place ---------------------------------------------
  * Two haplotypes may differ only in WHICH copy of a homopolymer or tandem repeat an indel removes or adds.  They project to
  * different transcripts over the same reference range, and spm_hip_jst_ref_alns_collapse, which decides on content, keeps

@@ -362,6 +362,28 @@ class PileupSiteOpts(C.Structure):
 PILEUP_PLANES = ("A", "C", "G", "T", "N", "DEL", "INS", "LOWQ")  # SPM_PILEUP_A .. SPM_PILEUP_LOWQ
 
 
+class VcfOpts(C.Structure):
+    _fields_ = [("ploidy", C.c_uint32), ("cost_match", C.c_uint32), ("cost_het", C.c_uint32), ("cost_miss", C.c_uint32),
+                ("prior_het", C.c_uint32), ("prior_hom_alt", C.c_uint32), ("min_qual", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
+class VariantCall(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("depth", C.c_uint32), ("qual", C.c_uint32), ("len", C.c_uint32), ("offset", C.c_uint64),
+                ("status", C.c_uint8), ("gq", C.c_uint8), ("gt", C.c_uint8 * 2), ("n_alt", C.c_uint8), ("alt", C.c_uint8 * 2),
+                ("reserved", C.c_uint8)]
+
+
+class VcfStats(C.Structure):
+    _fields_ = [("ms_total", C.c_float), ("ms_call", C.c_float), ("ms_scan", C.c_float), ("ms_write", C.c_float),
+                ("ms_host", C.c_float), ("group_sites", C.c_uint32), ("n_sites", C.c_uint64), ("n_variant", C.c_uint64),
+                ("n_ref", C.c_uint64), ("n_ref_n", C.c_uint64), ("n_low_qual", C.c_uint64), ("n_header_bytes", C.c_uint64),
+                ("n_text_bytes", C.c_uint64)]
+
+
+CALL_REF, CALL_VARIANT, CALL_REF_N = 0, 1, 2  # SPM_CALL_*
+
+
 class BaiStats(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_records", C.c_float), ("ms_chunks", C.c_float), ("ms_bins", C.c_float),
                 ("ms_write", C.c_float), ("ms_host", C.c_float), ("n_bins", C.c_uint64), ("n_chunks", C.c_uint64),
@@ -634,6 +656,17 @@ SIGNATURES = {
     "spm_hip_pileup_sites_destroy": (None, [_vp]),
     "spm_hip_pileup_sites_host": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.POINTER(PileupSiteOpts), _vp, C.c_uint64,
                                             C.POINTER(C.c_uint64)]),
+    "spm_hip_pileup_sites_vcf": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(VcfOpts), C.POINTER(_vp)]),
+    "spm_hip_pileup_sites_vcf_records": (C.c_int, [_vp, _vp, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(VcfOpts),
+                                                   C.POINTER(_vp)]),
+    "spm_hip_vcf_view": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(VariantCall)), C.POINTER(C.c_uint64)]),
+    "spm_hip_vcf_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "spm_hip_vcf_stats": (C.c_int, [_vp, C.POINTER(VcfStats)]),
+    "spm_hip_vcf_destroy": (None, [_vp]),
+    "spm_hip_pileup_sites_calls_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(VcfOpts), _vp]),
+    "spm_hip_pileup_sites_vcf_host": (C.c_int, [_vp, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(VcfOpts), _vp, C.c_uint64,
+                                                C.POINTER(C.c_uint64)]),
+    "spm_hip_vcf_header": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "spm_hip_jst_hits_select": (C.c_int, [_vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_records_select": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(SelectOpts), C.POINTER(_vp)]),
     "spm_hip_jst_hits_select_stats": (C.c_int, [_vp, C.POINTER(SelectStats)]),

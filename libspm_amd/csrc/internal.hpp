@@ -231,6 +231,7 @@ void spm_warm_jst_reads_kernels();
 void spm_warm_jst_sam_kernels();
 void spm_warm_bam_index_kernels();
 void spm_warm_bam_pileup_kernels();
+void spm_warm_pileup_vcf_kernels();
 void spm_warm_device_order_kernels(spm_ctx *ctx); // (hipcub's kernels have no name to ask for: it sorts one pair in ctx's scratch)
 #pragma GCC visibility pop
 

@@ -5,12 +5,14 @@
 //   spm_bgzf   bgzf.hip                             framed or deflated blocks and their offsets; read by bam_index.hpp (index)
 //   spm_bai    bam_index.hpp                        the bytes of a BAI index
 //   spm_pileup, spm_pileup_sites   bam_pileup.hpp   the eight count planes of a region; the site records compacted from them
+//   spm_vcf    pileup_vcf.hpp                       the VCF text of a site array and one call record per site
 // Behind them: the lazy download of a handle's host view, the synchronise-and-free of its device buffers, the copy-out of
 // optional out-parameters and of a stats struct; the BAM file around a record stream that spm_hip_jst_ref_loci_bam,
 // spm_hip_bam_sort and spm_hip_bam_markdup make; the refusal both BGZF calls and the BAM call word alike.  Host code only: no kernel, no C-ABI
 // definition.
 #pragma once
 
+#include <cstddef>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -109,6 +111,22 @@ struct spm_pileup_sites
 };
 static_assert(sizeof(spm_pileup_opts) == 32 && sizeof(spm_pileup_stats) == 88, "spm_hip.h states these sizes");
 static_assert(sizeof(spm_pileup_site) == 32 && sizeof(spm_pileup_site_opts) == 16, "spm_hip.h states these sizes");
+
+struct spm_vcf
+{
+    spm_ctx *ctx = nullptr;
+    char *d_text = nullptr;
+    spm_variant_call *d_calls = nullptr;
+    uint64_t n_bytes = 0, n_calls = 0;
+    bool have_host = false; // the views are downloaded when first asked for
+    std::vector<char> host_text;
+    std::vector<spm_variant_call> host_calls;
+    spm_vcf_stats stats{};
+};
+static_assert(sizeof(spm_vcf_opts) == 40 && sizeof(spm_variant_call) == 32 && sizeof(spm_vcf_stats) == 80, "spm_hip.h states these sizes");
+static_assert(offsetof(spm_variant_call, len) == 12 && offsetof(spm_variant_call, offset) == 16 && offsetof(spm_variant_call, status) == 24 &&
+                  offsetof(spm_variant_call, gt) == 26 && offsetof(spm_variant_call, n_alt) == 28 && offsetof(spm_variant_call, alt) == 29,
+              "spm_hip.h states this layout");
 
 #pragma GCC visibility push(hidden) // (inline code of the library's own units, not part of its surface)
 namespace spm_hip

@@ -101,6 +101,7 @@ extern "C" int spm_hip_init(int device, void *stream, spm_ctx **out)
     spm_warm_bgzf_kernels();
     spm_warm_bam_index_kernels();
     spm_warm_bam_pileup_kernels();
+    spm_warm_pileup_vcf_kernels();
     spm_warm_device_order_kernels(ctx.get());
     *out = ctx.release();
     return SPM_OK;

@@ -31,6 +31,7 @@ JST_RESCUE_DTYPE = _dtype(capi.JstRescue)
 SAM_LINE_DTYPE = _dtype(capi.SamLine)
 PILEUP_SITE_DTYPE = _dtype(capi.PileupSite)
 PILEUP_PLANES = capi.PILEUP_PLANES
+VARIANT_CALL_DTYPE = _dtype(capi.VariantCall)
 _CIGAR_CHAR = {capi.CIGAR_INS: "I", capi.CIGAR_DEL: "D", capi.CIGAR_EQ: "=", capi.CIGAR_X: "X"}
 
 
@@ -215,6 +216,14 @@ class Context:
         _check(capi.lib().spm_hip_bam_pileup_records(self._h, C.c_void_p(records), int(n_record_bytes), C.c_void_p(lines), int(n_lines),
                                                      int(ref_len), C.byref(opts), C.byref(h)), self._h)
         return Pileup(self, h, int(begin))
+
+    def pileup_sites_vcf(self, sites: int, n_sites: int, rname, sample, ref_len: int, **opts) -> "Vcf":
+        """Genotype calls and the VCF text of site records in device memory (spm_hip_pileup_sites_vcf_records), the raw form of
+        PileupSites.vcf(): sites is a device pointer to n_sites PILEUP_SITE_DTYPE records in ascending pos.  opts: vcf_opts'."""
+        o, h = vcf_opts(**opts), C.c_void_p()
+        _check(capi.lib().spm_hip_pileup_sites_vcf_records(self._h, C.c_void_p(sites), int(n_sites), _name(rname), _name(sample),
+                                                           int(ref_len), C.byref(o), C.byref(h)), self._h)
+        return Vcf(self, h)
 
     def bgzf_deflate(self, device_ptr: int, n: int, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
         """bgzf() with the blocks compressed on the device (spm_hip_bgzf_deflate: LZ77 matches and the fixed Huffman code per
@@ -1114,16 +1123,25 @@ class Pileup(_Handle):
     def sites(self, reference: "Text", min_depth: int = 1, min_alt: int = 2, min_alt_permille: int = 200) -> np.ndarray:
         """The columns that depart from the resident reference (spm_hip_pileup_sites; the rule is in spm_hip.h), in position
         order, as PILEUP_SITE_DTYPE records.  reference: the dna4 Text of ranks that sam_extras takes."""
-        opts = pileup_site_opts(min_depth, min_alt, min_alt_permille)
-        s = _PileupSites(self.ctx, self._new("sites", reference._h, C.byref(opts)))
+        s = self.site_records(reference, min_depth, min_alt, min_alt_permille)
         try:
             return s.view()
         finally:
             s.close()
 
+    def site_records(self, reference: "Text", min_depth: int = 1, min_alt: int = 2, min_alt_permille: int = 200) -> "PileupSites":
+        """sites() as an object that keeps the records in device memory: .view() is what sites() returns, .vcf() genotypes them"""
+        opts = pileup_site_opts(min_depth, min_alt, min_alt_permille)
+        return PileupSites(self.ctx, self._new("sites", reference._h, C.byref(opts)))
 
-class _PileupSites(_Handle):
+
+class PileupSites(_Handle):
+    """Result of Pileup.site_records(): the site records of a pileup in device memory, in position order.  (Made by that call
+    only, so the package does not export the name; it is libspm_amd.engine.PileupSites.)"""
     _PREFIX = "pileup_sites"
+
+    def __len__(self):
+        return self.device()[1]
 
     def view(self) -> np.ndarray:
         rec, n = C.POINTER(capi.PileupSite)(), C.c_uint64()
@@ -1131,7 +1149,98 @@ class _PileupSites(_Handle):
         return _as_array(rec, n.value, capi.PileupSite, PILEUP_SITE_DTYPE)
 
     def device(self):
+        """(sites, n): device pointer and count"""
         return self._span("device")
+
+    def vcf(self, rname, sample, ref_len: int, **opts) -> "Vcf":
+        """Genotype calls for these sites and the VCF text of the variant ones, on the device (spm_hip_pileup_sites_vcf; the rule
+        is in spm_hip.h): one sample, SNV alleles.  opts: vcf_opts' (ploidy, the three costs, the two priors, min_qual)."""
+        o = vcf_opts(**opts)
+        return Vcf(self.ctx, self._new("vcf", _name(rname), _name(sample), int(ref_len), C.byref(o)))
+
+
+_PileupSites = PileupSites
+
+
+def _name(s) -> bytes:
+    return s.encode() if isinstance(s, str) else bytes(s)
+
+
+def vcf_opts(ploidy: int = 2, cost_match: int = 0, cost_het: int = 0, cost_miss: int = 0, prior_het: int = 0, prior_hom_alt: int = 0,
+             min_qual: int = 20) -> capi.VcfOpts:
+    """the three costs all 0: 44, 3039, 24771; the two priors both 0: 30000, 33010 (milli-Phred); min_qual in Phred, as given"""
+    return capi.VcfOpts(ploidy=int(ploidy), cost_match=int(cost_match), cost_het=int(cost_het), cost_miss=int(cost_miss),
+                        prior_het=int(prior_het), prior_hom_alt=int(prior_hom_alt), min_qual=int(min_qual), flags=0, reserved0=0,
+                        reserved1=0)
+
+
+def vcf_header(rname, sample, ref_len: int) -> bytes:
+    """The meta lines and the #CHROM line of the files Vcf.text() gives (spm_hip_vcf_header).  Needs no device."""
+    rname, sample = _name(rname), _name(sample)
+    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_vcf_header(rname, sample, int(ref_len), buf, cap, need))
+
+
+def pileup_sites_calls_host(sites, **opts) -> np.ndarray:
+    """The VARIANT_CALL_DTYPE records of PILEUP_SITE_DTYPE records by the serial host builder (spm_hip_pileup_sites_calls_host);
+    offset and len stay 0, they belong to a text.  opts: vcf_opts'.  Needs no device."""
+    sites = np.ascontiguousarray(sites, dtype=PILEUP_SITE_DTYPE)
+    o, calls = vcf_opts(**opts), np.zeros(len(sites), dtype=VARIANT_CALL_DTYPE)
+    _check(capi.lib().spm_hip_pileup_sites_calls_host(sites.ctypes.data, len(sites), C.byref(o), calls.ctypes.data), None)
+    return calls
+
+
+def pileup_sites_vcf_host(sites, rname, sample, ref_len: int, **opts) -> bytes:
+    """The VCF file of PILEUP_SITE_DTYPE records by the serial host builder (spm_hip_pileup_sites_vcf_host): the bytes of
+    Vcf.text().  opts: vcf_opts'.  Needs no device."""
+    sites = np.ascontiguousarray(sites, dtype=PILEUP_SITE_DTYPE)
+    o, rname, sample = vcf_opts(**opts), _name(rname), _name(sample)
+    return _size_then_fill(lambda buf, cap, need: capi.lib().spm_hip_pileup_sites_vcf_host(
+        sites.ctypes.data, len(sites), rname, sample, int(ref_len), C.byref(o), buf, cap, need))
+
+
+class Vcf(_Handle):
+    """Result of PileupSites.vcf() and Context.pileup_sites_vcf(): a VCF file and one VARIANT_CALL_DTYPE record per site, in
+    device memory.  (Made by those two calls only, so the package does not export the name; it is libspm_amd.engine.Vcf.)"""
+    _PREFIX = "vcf"
+
+    def _view(self):
+        t, rec = C.c_void_p(), C.POINTER(capi.VariantCall)()
+        nb, nc = C.c_uint64(), C.c_uint64()
+        self._call("view", C.byref(t), C.byref(nb), C.byref(rec), C.byref(nc))
+        return t, nb.value, rec, nc.value
+
+    def __len__(self):
+        return self.device()[3]
+
+    def text(self) -> bytes:
+        """the file: header, then one line per site whose best genotype is not ref/ref"""
+        t, nb, _rec, _nc = self._view()
+        return C.string_at(t, nb) if nb else b""
+
+    def calls(self) -> np.ndarray:
+        """one record per site; text()[offset:offset + len] is the site's line"""
+        _t, _nb, rec, nc = self._view()
+        return _as_array(rec, nc, capi.VariantCall, VARIANT_CALL_DTYPE)
+
+    def device(self):
+        """(text, n_bytes, calls, n_calls): device pointers and counts"""
+        t, rec = C.c_void_p(), C.c_void_p()
+        nb, nc = C.c_uint64(), C.c_uint64()
+        self._call("device", C.byref(t), C.byref(nb), C.byref(rec), C.byref(nc))
+        return int(t.value or 0), int(nb.value), int(rec.value or 0), int(nc.value)
+
+    def stats(self) -> capi.VcfStats:
+        return self._stats(capi.VcfStats)
+
+    def bgzf(self, *, block_data: int = 0, eof: bool = True) -> "Bgzf":
+        """The file framed where it lies in device memory (Context.bgzf): bytes() is a .vcf.gz of stored blocks."""
+        text, n_bytes, _calls, _n = self.device()
+        return self.ctx.bgzf(text, n_bytes, block_data=block_data, eof=eof)
+
+    def bgzf_deflate(self, *, block_data: int = 0, eof: bool = True, dynamic: bool = False) -> "Bgzf":
+        """bgzf() with the blocks compressed on the device (Context.bgzf_deflate): bytes() is a .vcf.gz."""
+        text, n_bytes, _calls, _n = self.device()
+        return self.ctx.bgzf_deflate(text, n_bytes, block_data=block_data, eof=eof, dynamic=dynamic)
 
 
 class Bam(_Handle):
